@@ -6,8 +6,10 @@ the whole tree, all 64 voice rows), 48 kHz synthetic tree, plus achieved rates a
 
 A "step" is one `fill_buffer` call of T = 4800 frames (0.1 s of audio) over the full tree, through the
 C ABI's device-resident entry point: the time-ramp input and the output buffer are already in HBM when
-the timed region starts.  The K-step timed loop (barrier + synchronize on both sides, max over ranks) is
-repeated R times; `ms_per_step` / `value` are the MEDIAN repeat, min and max are reported beside it.
+the timed region starts.  The timed region is exactly K = --steps steps after W = --warmup untimed ones
+(barrier + synchronize on both sides, max over ranks); `ms_per_step` / `value` come from it.  Right before
+it a second renderer of the same tree keeps the device busy for DEVICE_WARMUP_S (clock ramp, see run).
+`--dump-outputs DIR` writes what the last timed step left in the caller's output buffer (see dump_output).
 The reference-shaped host-buffer call (`fr_fill_buffer`: host rows in, host buffer out, synchronous) is
 timed separately as `host_api` -- PCIe- and sync-inclusive, never `value`.
 
@@ -43,10 +45,27 @@ OPS_EXECUTED_PER_PF = 6                     # VALU ops the fused kernel issues p
 ISSUE_SLOTS_PER_PF = 7                      # v_fract_f32 issues at half rate on gfx950 (measured 4.07 vs 2.2 cyc, profiles/r01_valu_rate.txt)
 OPS_GRAPH_PER_PF = 12                       # primitive nodes the reference evaluates per partial-frame (11 + Sum2)
 PMC_SUMMARY = os.path.join(ROOT, "profiles", "r03_bank_pmc_summary.json")
+DUMP_MAX_BYTES = 64 << 20
+DEVICE_WARMUP_S = 0.2                       # seconds of sustained load right before the timed loop (see run)
 
 
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
+
+
+def dump_output(directory, out):
+    """`out` (the [rows, T] f32 buffer a caller of the timed path receives) as <directory>/output.npy.  Above
+    DUMP_MAX_BYTES a fixed, seeded sample of its elements is written instead (1-D, row-major order), with their flat
+    indices into [rows, T] in output_index.npy (f64, exact), both files together within the limit."""
+    os.makedirs(directory, exist_ok=True)
+    out = np.ascontiguousarray(out, dtype=np.float32)
+    if out.nbytes > DUMP_MAX_BYTES:
+        n = (DUMP_MAX_BYTES - 4096) // 12        # 4 B value + 8 B index per element; 4 KiB for the two .npy headers
+        idx = np.sort(np.random.default_rng(0).choice(out.size, n, replace=False))
+        np.save(os.path.join(directory, "output_index.npy"), idx.astype(np.float64))
+        out = out.reshape(-1)[idx]
+    np.save(os.path.join(directory, "output.npy"), out)
+    log(f"dumped the last timed step's output to {directory}: {out.shape} f32")
 
 
 def shader_clock_mhz():
@@ -294,11 +313,11 @@ def main():
 def run():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200)
-    ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--repeats", type=int, default=0,
-                    help="how many times the K-step timed loop runs (median reported); 0 = as many as make the timed loops "
-                         "last about 0.6 s in all, at least 3, at most 50")
+    ap.add_argument("--steps", type=int, default=200, help="timed steps (K): the timed region is exactly these K calls")
+    ap.add_argument("--warmup", type=int, default=20, help="untimed steps before the timed region (W)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the output of the last timed step (rank 0's rows) as DIR/output.npy; the inputs depend only "
+                         "on the arguments, so runs of two builds with the same arguments can be compared")
     ap.add_argument("--voices", type=int, default=64)
     ap.add_argument("--partials", type=int, default=4096)
     ap.add_argument("--frames", type=int, default=4800, help="frames per fill_buffer call (T)")
@@ -330,6 +349,8 @@ def run():
     ap.add_argument("--cpu-frames", type=int, default=144,
                     help="frames the CPU path renders single-threaded for cpu_baseline and the parity check (about 12 s)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     import torch
     import torch.distributed as dist
@@ -414,8 +435,7 @@ def run():
 
     # Every step's time-ramp row is already resident in HBM.  The ramp is the f32 frame number, exact below 2^24, so
     # its VALUES wrap at 2^23 (idx itself, a u64, keeps counting); rows live in a ring of at most 64 steps.
-    R_MAX = 50
-    stripe0 = rank * (W + (R_MAX + 2) * K + 64) * T if shard_mode == "time" else 0
+    stripe0 = rank * (W + 52 * K + 64) * T if shard_mode == "time" else 0     # (more frames than any rank renders)
     ring_steps = min(W + K, 64)
     WRAP = 1 << 23
 
@@ -469,20 +489,35 @@ def run():
         barrier()
         return max_over_ranks(dt)
 
-    times = [timed_loop(W)]
-    R = args.repeats or int(min(R_MAX, max(3, np.ceil(0.6 / max(times[0], 1e-6)))))
-    if use_dist:   # every rank must run the same number of loops
-        rt = torch.tensor([R], dtype=torch.int64, device="cuda" if args.backend == "nccl" else "cpu")
-        dist.broadcast(rt, 0)
-        R = int(rt.item())
-    clocks = []
-    for r_i in range(1, R):
-        times.append(timed_loop(W + r_i * K))
-        c = shader_clock_mhz()
-        if c:
-            clocks.append(c)
-    elapsed = statistics.median(times)
-    next_k = W + R * K
+    # Device warm-up.  The first ~30 ms of sustained load run 5-13% slower than the steady state (clock ramp), and W steps
+    # of a tree can take well under a millisecond.  A second renderer of the same tree keeps the device busy with the same
+    # calls for DEVICE_WARMUP_S right before the timed region, so the measured renderer itself runs exactly W untimed and
+    # K timed steps and what it computes depends only on the arguments.
+    warm = libfriendship_amd.HipRenderer(mode=args.mode, device=local_rank)
+    synth.install(warm, tree)
+    warm_out = torch.empty_like(d_out)
+
+    def warm_step(k):
+        warm.fill_buffer_device(warm_out.data_ptr(), V, T, k * T, d_time[(k % ring_steps) * T:][:T].data_ptr(), [0, T], stream)
+
+    warm_step(0)                 # lowering
+    torch.cuda.synchronize()
+    n_warm, t0 = 0, time.perf_counter()
+    while time.perf_counter() - t0 < DEVICE_WARMUP_S:
+        for _ in range(8):
+            n_warm += 1
+            warm_step(n_warm)
+        torch.cuda.synchronize()
+    warm_s = time.perf_counter() - t0
+
+    elapsed = timed_loop(W)
+    clock = shader_clock_mhz()
+    warm.close()
+    next_k = W + K
+    # what the last timed step left in the buffer its caller reads (the timed loop ended in a device-wide synchronize)
+    last = (side_outs[(next_k - 1) % n_streams] if side_streams else d_out).cpu().numpy()
+    if args.dump_outputs and rank == 0:
+        dump_output(args.dump_outputs, last[row_lo:row_hi])
     # Partial-block sharding: the same steps with the exchange as ONE serial step behind the bank kernels (round 2's form,
     # FR_SHARD_SERIAL_EXCHANGE) beside the time-tiled, overlapped exchange measured above (SURVEY 8e asks for both numbers)
     exchange = None
@@ -508,7 +543,6 @@ def run():
             step(k)
         torch.cuda.synchronize()
         next_k += 3
-    last = (side_outs[(next_k - 1) % n_streams] if side_streams else d_out).cpu().numpy()
 
     # kernel-level timing for the roofline: K more steps with HIP events around every launch, recorded on the
     # stream the kernels run on (engine-side, fr_set_timing)
@@ -727,11 +761,10 @@ def run():
                    "ranks": world, "launcher": launcher, "shard_world": plan.get("shard", {}).get("world"),
                    "rccl_ranks": world if transport == "rccl" else 0,
                    "rows_of_rank0": [row_lo, row_hi], "plan": plan},
-        "repeats": {"n": R, "statistic": "median of R timed loops of K steps each", "ms_per_step_min": min(times) / K * 1e3,
-                    "ms_per_step_max": max(times) / K * 1e3, "ms_per_step_all": [t / K * 1e3 for t in times],
-                    "timed_seconds_total": sum(times),
-                    "shader_clock_mhz": {"samples": len(clocks), "median": statistics.median(clocks) if clocks else None,
-                                         "min": min(clocks) if clocks else None, "source": "sysfs pp_dpm_sclk after each loop"}},
+        "timed": {"steps": K, "seconds": elapsed, "statistic": "one timed loop of K steps after W untimed ones",
+                  "shader_clock_mhz": clock, "clock_source": "sysfs pp_dpm_sclk after the timed loop",
+                  "device_warmup": {"seconds": warm_s, "calls": n_warm,
+                                    "what": "the same calls on a second renderer of the tree, right before the timed loop"}},
         "partial_frames_per_s": K * T * float(V) * P * (world if shard_mode == "time" else 1) / elapsed,
         "roofline": roofline,
         "host_api": host_api,

@@ -82,15 +82,42 @@ def test_bench_main_with_world_size_set_does_not_launch(tmp_path):
     assert out.returncode == 99, (out.returncode, out.stderr[-2000:])
 
 
+def test_dump_output_writes_the_buffer_or_a_fixed_sample_within_the_limit(tmp_path, monkeypatch):
+    """--dump-outputs: the whole [rows, T] buffer when it fits; above the limit the same seeded sample of elements on every
+    run, with its flat indices, both files within the limit."""
+    import numpy as np
+    import bench
+    out = np.arange(6 * 10, dtype=np.float32).reshape(6, 10)
+    bench.dump_output(str(tmp_path / "small"), out)
+    assert sorted(os.listdir(tmp_path / "small")) == ["output.npy"]
+    got = np.load(tmp_path / "small" / "output.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, out)
+
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 8192)
+    big = np.random.default_rng(5).normal(size=(40, 100)).astype(np.float32)     # 16000 B
+    for run in ("a", "b"):
+        bench.dump_output(str(tmp_path / run), big)
+    files = ["output.npy", "output_index.npy"]
+    assert sorted(os.listdir(tmp_path / "a")) == files
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 8192
+    idx = np.load(tmp_path / "a" / "output_index.npy")
+    vals = np.load(tmp_path / "a" / "output.npy")
+    assert idx.dtype == np.float64 and vals.dtype == np.float32 and len(idx) == len(vals) > 0
+    assert np.all(np.diff(idx) > 0) and np.array_equal(vals, big.reshape(-1)[idx.astype(np.int64)])
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))
+
+
 @pytest.mark.gpu
-def test_bench_starts_its_own_two_ranks_on_the_gpu(hip_lib):
+def test_bench_starts_its_own_two_ranks_on_the_gpu(hip_lib, tmp_path):
     """The real thing on the one-GPU box: two ranks sharing the device, gloo for the barrier (`--backend gloo`), voices
     sharding inside the engine; a small tree so that the run takes seconds."""
     env = dict(os.environ)
     env.pop("WORLD_SIZE", None)
     env.pop("RANK", None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--voices", "8",
-                          "--partials", "256", "--frames", "512", "--steps", "5", "--warmup", "2", "--repeats", "3"],
+                          "--partials", "256", "--frames", "512", "--steps", "5", "--warmup", "2",
+                          "--dump-outputs", str(tmp_path)],
                          cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
@@ -100,3 +127,7 @@ def test_bench_starts_its_own_two_ranks_on_the_gpu(hip_lib):
     assert res["config"]["launcher"].startswith("bench.py") and res["config"]["ranks"] == 2
     assert res["config"]["rows_of_rank0"] == [0, 4]
     assert res["value"] > 0
+    import numpy as np
+    dumped = np.load(os.path.join(tmp_path, "output.npy"))          # rank 0's rows of the last timed step
+    assert dumped.dtype == np.float32 and dumped.shape == (4, 512) and np.isfinite(dumped).all()
+    assert res["checksum"] == float(np.abs(dumped.astype(np.float64)).sum())

@@ -29,7 +29,7 @@ pf = V * P * T
 avg_s = stats.get("average_ns", 0) * 1e-9
 summ = {
     "commit": commit,
-    "command": "tools/collect_profiles.sh (rocprofv3 --pmc <counters> -- python3 bench.py --no-cpu-baseline --no-extras --steps 5 --warmup 2 --repeats 1; one pass per TCC counter)",
+    "command": "tools/collect_profiles.sh (rocprofv3 --pmc <counters> -- python3 bench.py --no-cpu-baseline --no-extras --steps 5 --warmup 2; one pass per TCC counter)",
     "kernel": "fr::bank_kernel<1, 1, 4>", "per": "launch (one 4800-frame fill_buffer over 64 voices x 4096 partials)",
     "kernel_trace_stats": stats, "counters": out,
     "derived": {
