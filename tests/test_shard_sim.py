@@ -310,3 +310,37 @@ def test_voices_mode_with_feedback_loops(sim, oracle_lib, world):
         job.fill(made[1], 0, 8, [np.ones(8, np.float32), np.ones(8, np.float32)])
     assert ei.value.status == 10
     job.close()
+
+
+@pytest.mark.timeout(900)
+@pytest.mark.parametrize("world", [2, 4])
+@pytest.mark.parametrize("kind", ["additive", "effects", "half-delayed"])
+def test_default_tile_geometry_call_sequence(sim, oracle_lib, world, kind, monkeypatch):
+    """The time-tiled exchange at its DEFAULT geometry (at most 4 tiles, none under 1024 frames; FR_EXCHANGE_TILES only
+    switches tiling on for the host-callback transport) through the call sequence of tests/shard_sequence.py: steady calls
+    whose deferred row each tile appends at its own offset, ragged / two-tile / one-tile / 2-frame calls, an edit whose
+    look-back window reads that history, a backward seek whose first frame lies inside a tile (the final combine's
+    out_skip -- its output rows are those of the half-delayed tree's direct voices), a device-resident call.  Sampled against the oracle, including both sides of every tile boundary; same bits
+    and same bytes as the serial exchange.  The CPU twin of tests/test_hip_shard.py."""
+    import shard_sequence
+    monkeypatch.setenv("FR_EXCHANGE_TILES", "4")          # (read when a renderer is created)
+    monkeypatch.delenv("FR_EXCHANGE_MIN_TILE", raising=False)
+    V, P = 5, 256 * world
+    if kind == "additive":
+        tree, lmax, lags = synth.additive_tree(V, P, seed=3, detune=True), None, ()
+    else:
+        taps, d = 3, 400
+        tree = (synth.effects_tree if kind == "effects" else shard_sequence.half_delayed_tree)(V, P, taps=taps, base_delay=float(d))
+        lmax, lags = d * taps * (taps + 1) // 2, tuple(d * (j + 1) for j in range(taps))
+    calls = shard_sequence.standard_calls(lmax or 0)
+    tiled = shard_harness.Job(sim, world, "partials")
+    serial = shard_harness.Job(sim, world, "partials", serial_exchange=True)
+    with Renderer(oracle_lib) as ref:
+        for ren in tiled.ranks + serial.ranks:
+            synth.install(ren, tree)
+        first, _ = shard_sequence.run(tiled, ref, tree, V, calls, lmax=lmax, lags=lags, serial=serial)
+    for r, plan in enumerate(first):
+        assert plan["shard"]["split_voices"] == V and plan["max_lookback"] == (lmax or 0), plan
+        assert [(b["voices"], b["partials"], b["to_exchange"]) for b in plan["banks"]] == [(V, P // world, True)], plan
+    tiled.close()
+    serial.close()
