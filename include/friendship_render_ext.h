@@ -1,0 +1,46 @@
+/*
+ * friendship_render_ext.h -- entry points of the MI355X engine beyond the drop-in boundary of friendship_render.h.
+ *
+ * friendship_render.h is the symbol set every renderer library exports (the product and the CPU oracle alike).  What is
+ * declared here only the product exports: a host that loads a renderer library at run time resolves these with dlsym and
+ * copes with their absence (libfriendship_amd/host/friendship.hpp PluginRenderer, libfriendship_amd/capi.py).
+ */
+#ifndef FRIENDSHIP_RENDER_EXT_H
+#define FRIENDSHIP_RENDER_EXT_H
+
+#include "friendship_render.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* ---- per-renderer options --------------------------------------------------------------------
+ * Every tuning switch of the engine is named like the environment variable that sets it for the whole process
+ * (INTEGRATION.md §5), and its value string means what it means in the environment.  Most of them can also be given to
+ * one renderer when it is created, so that two renderers of one process (a real-time instance with short blocks next to
+ * an offline bounce) can differ.  Precedence: an option beats the environment, the environment beats the built-in
+ * default.  Everything is read once, when the renderer is created.
+ *
+ * Options are checked strictly: an unknown name, a name that is process-wide only (FR_JIT_CACHE, FR_JIT_DUMP,
+ * FR_HOST_TRACE, FR_LOWER_TRACE, FR_PLAN_TRACE, FR_LOWER_HUGEPAGES), a name given twice, a value that does not parse
+ * (decimal digits, or a word the switch documents such as "force") or is out of range: FR_ERR_INVALID_ARG and no
+ * renderer.  (The environment keeps its lenient reading: atoi and clamping, as always.)
+ */
+typedef struct fr_option {
+    const char *name;              /* e.g. "FR_BANK_SHORT" */
+    const char *value;             /* e.g. "0" */
+} fr_option;
+
+/* fr_renderer_create plus options.  options == NULL with n_options == 0 is exactly fr_renderer_create. */
+fr_status fr_renderer_create_with_options(const fr_config *cfg, const fr_option *options, size_t n_options,
+                                          fr_renderer **out);
+
+/* Every per-renderer option as a JSON object: {"FR_BANK_SHORT": {"value": "0", "source": "option"}, ...}; the source is
+ * "default", "env" or "option".  The string belongs to the handle and is valid until the next call on it. */
+const char *fr_options_json(fr_renderer *r);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif /* FRIENDSHIP_RENDER_EXT_H */

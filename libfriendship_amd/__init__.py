@@ -37,6 +37,7 @@ def hip_lib():
     return _hip_lib
 
 
-def HipRenderer(mode="auto", device=-1):
-    """A renderer on the HIP engine (the analogue of `SparkleRenderer::default()` in the reference's tests)."""
-    return Renderer(hip_lib(), mode=mode, device=device)
+def HipRenderer(mode="auto", device=-1, options=None):
+    """A renderer on the HIP engine (the analogue of `SparkleRenderer::default()` in the reference's tests).
+    options: {name: value} of the engine's switches for this renderer alone (friendship_render_ext.h)."""
+    return Renderer(hip_lib(), mode=mode, device=device, options=options)

@@ -1,8 +1,9 @@
-"""ctypes binding of include/friendship_render.h.
+"""ctypes binding of include/friendship_render.h (and of include/friendship_render_ext.h where the library has it).
 
 The same binding drives the product library (libfriendship_hip.so, HIP/gfx950) and -- from tests and
 the bench's cpu_baseline leg only -- the CPU oracle (oracle/_build/libfr_oracle.so): both export the
-identical C ABI.  This module contains no compute and no fallback: it marshals arguments.
+identical C ABI of friendship_render.h; only the product exports the extension.  This module contains no
+compute and no fallback: it marshals arguments.
 """
 import ctypes as C
 import json
@@ -69,6 +70,10 @@ class fr_config(C.Structure):
 
 
 SENDRECV_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t)
+
+
+class fr_option(C.Structure):
+    _fields_ = [("name", C.c_char_p), ("value", C.c_char_p)]
 
 
 class fr_comm(C.Structure):
@@ -206,6 +211,13 @@ class RendererLib:
         L.fr_comm_selftest.restype = C.c_int32
         L.fr_comm_unique_id.argtypes = [P(C.c_uint8)]
         L.fr_comm_unique_id.restype = C.c_int32
+        # friendship_render_ext.h: the product only (the oracle does not export it)
+        self.has_options = hasattr(L, "fr_renderer_create_with_options") and hasattr(L, "fr_options_json")
+        if self.has_options:
+            L.fr_renderer_create_with_options.argtypes = [P(fr_config), P(fr_option), C.c_size_t, P(vp)]
+            L.fr_renderer_create_with_options.restype = C.c_int32
+            L.fr_options_json.argtypes = [vp]
+            L.fr_options_json.restype = C.c_char_p
         if L.fr_abi_version() != FR_ABI_VERSION:
             raise RuntimeError(f"{path}: ABI version {L.fr_abi_version()} != {FR_ABI_VERSION}")
 
@@ -234,18 +246,31 @@ class RendererLib:
 class Renderer:
     """Handle-owning wrapper: one method per entry point, arguments as in the reference's traits."""
 
-    def __init__(self, rlib, mode="auto", device=-1, semantics="reference", history_frames=0, sync_compile=True):
+    def __init__(self, rlib, mode="auto", device=-1, semantics="reference", history_frames=0, sync_compile=True, options=None):
         """sync_compile: hipRTC specialisations are compiled inside the call that first needs them (deterministic plans:
-        what tests and benchmarks want); False = the ABI's default, compile on a worker thread and switch over when ready."""
+        what tests and benchmarks want); False = the ABI's default, compile on a worker thread and switch over when ready.
+        options: {name: value} strings (or (name, value) pairs), this renderer's settings of the engine's switches
+        (friendship_render_ext.h: named like the environment variables, and beating them); a library without the extension
+        raises FR_ERR_UNSUPPORTED."""
         self.rlib = rlib
         self.L = rlib.lib
         self._stream_slots = 0
         cfg = fr_config(FR_ABI_VERSION, device, MODES[mode] if isinstance(mode, str) else mode, FR_CONFIG_SYNC_COMPILE if sync_compile else 0,
                         SEMANTICS[semantics] if isinstance(semantics, str) else semantics, 0, history_frames)
         h = C.c_void_p()
-        st = self.L.fr_renderer_create(C.byref(cfg), C.byref(h))
+        if options is None:
+            st = self.L.fr_renderer_create(C.byref(cfg), C.byref(h))
+            what = "fr_renderer_create"
+        else:
+            if not rlib.has_options:
+                raise RenderError(FR_ERR_UNSUPPORTED, rlib.status_string(FR_ERR_UNSUPPORTED),
+                                  f"{rlib.path} has no per-renderer options (fr_renderer_create_with_options)")
+            items = [(str(k), str(v)) for k, v in (options.items() if hasattr(options, "items") else options)]
+            arr = (fr_option * max(len(items), 1))(*[fr_option(k.encode(), v.encode()) for k, v in items])
+            st = self.L.fr_renderer_create_with_options(C.byref(cfg), arr if items else None, len(items), C.byref(h))
+            what = "fr_renderer_create_with_options: " + ", ".join(f"{k}={v}" for k, v in items)
         if st != FR_OK:
-            raise RenderError(st, rlib.status_string(st), "fr_renderer_create")
+            raise RenderError(st, rlib.status_string(st), what)
         self.h = h
         self._offs1 = np.zeros(2, dtype=np.uint64)
         self._keep = []  # effects passed in stay alive as long as the renderer (not required by the ABI)
@@ -429,6 +454,12 @@ class Renderer:
     def plan(self):
         s = self.L.fr_plan_json(self.h)
         return json.loads(s.decode()) if s else {}
+
+    def options(self):
+        """Every per-renderer switch: {name: {"value": str, "source": "default" | "env" | "option"}} (fr_options_json)."""
+        if not self.rlib.has_options:
+            raise RenderError(FR_ERR_UNSUPPORTED, self.rlib.status_string(FR_ERR_UNSUPPORTED), f"{self.rlib.path} has no fr_options_json")
+        return json.loads(self.L.fr_options_json(self.h).decode())
 
     def set_timing(self, on=True):
         self._check(self.L.fr_set_timing(self.h, 1 if on else 0))

@@ -18,6 +18,7 @@
 #include <unordered_set>
 #include <vector>
 
+#include "../../include/friendship_render_ext.h"
 #include "comm.hpp"
 #include "graph.hpp"
 #include "jit.hpp"
@@ -124,6 +125,15 @@ struct Plan {
     std::string json;
 };
 
+// One bank launch of the last call, as fr_plan_json's "bank_launches" shows it.
+struct BankLaunchNote {
+    const char *kernel;
+    uint32_t voices, partials, chunk_log2, waves_per_group, frames_per_lane, voices_per_wave;   // (chunk_log2 0: whole voices, gbank)
+    uint64_t frames;
+};
+
+constexpr size_t N_OPTIONS = 26;         // per-renderer options (friendship_render_ext.h; the table below fr_renderer)
+
 struct TimerClass {
     double ms = 0;
     uint64_t launches = 0;
@@ -191,7 +201,7 @@ struct fr_renderer {
             BankArgs a{};
             a.log2_p = bs.grp.log2_p;
             a.n_voices = (uint32_t)bs.grp.rows.size();
-            bank_shape(a.log2_p, a.n_voices, n_times, a.chunk_log2, a.frames_per_lane, a.waves_per_group, a.small_call, a.voices_per_wave);
+            shape_bank(a.log2_p, a.n_voices, n_times, a.chunk_log2, a.frames_per_lane, a.waves_per_group, a.small_call, a.voices_per_wave);
             if (a.voices_per_wave && !allow_multi) { a.voices_per_wave = 0; a.frames_per_lane = 1; }
             a.leaf_variant = 1;
             a.host_flags = (uint32_t *)1;   // (asking "would it")
@@ -260,7 +270,7 @@ struct fr_renderer {
     hipStream_t xstream = nullptr;
     std::vector<hipEvent_t> x_events;    // [tile] banks of the tile done (call's stream) ... and x_events.back(): exchange done (xstream)
     uint32_t x_max_tiles = 4, x_min_tile = 1024;
-    bool x_tiles_explicit = false;       // either knob came from the environment: tile whatever the transport
+    bool x_tiles_explicit = false;       // either knob was set (environment or option): tile whatever the transport
     uint64_t exchange_bytes = 0;         // sent by this rank since the renderer was made (fr_plan_json)
     uint64_t exchange_calls = 0, exchange_tiles = 0;
     PinnedBuf h_xsend, h_xrecv;
@@ -362,8 +372,28 @@ struct fr_renderer {
     }
 
     bool timing = false;
-    // A/B switches (environment, read at create; defaults are the measured best):
+    // A/B switches (per-renderer options or the environment, read at create: the option table below; defaults are the
+    // measured best):
+    int64_t option_value[N_OPTIONS];
+    uint8_t option_source[N_OPTIONS];
+    std::string options_json_cache;
     uint32_t bank_leaf_variant = 1;      // FR_BANK_LEAF=0: product-form leaves (kernels.hpp BankArgs::leaf_variant)
+    BankTuning bank_tune;                // FR_BANK_SHORT, FR_SHORT_*, FR_BANK_F, FR_BANK_NW: what bank_shape sees for this renderer
+    void shape_bank(uint32_t log2_p, uint32_t n_voices, uint64_t n_times, uint32_t &chunk_log2, uint32_t &frames_per_lane,
+                    uint32_t &waves_per_group, uint32_t &small_call, uint32_t &voices_per_wave, bool many_pairs_whole = false) const {
+        const BankTuning *outer = bank_tuning;
+        bank_tuning = &bank_tune;
+        bank_shape(log2_p, n_voices, n_times, chunk_log2, frames_per_lane, waves_per_group, small_call, voices_per_wave, many_pairs_whole);
+        bank_tuning = outer;
+    }
+    bool jit_fma = true;                 // FR_JIT_FMA=0: generated leaves without the fused multiply-add fold (jit.hpp)
+    unsigned lower_threads = 1;          // FR_LOWER_THREADS, FR_LOWER_PAR_MIN_NODES, FR_LOWER_PAR_MIN_EDIT (Lowering::set_parallel)
+    size_t lower_min_nodes = 0, lower_min_edit = 0;
+    std::vector<BankLaunchNote> bank_launches;   // the last call's (fr_plan_json), at most 256
+    void note_bank_launch(const char *kernel, uint32_t voices, uint32_t partials, uint32_t chunk_log2, uint32_t waves_per_group,
+                          uint32_t frames_per_lane, uint32_t voices_per_wave, uint64_t frames) {
+        if (bank_launches.size() < 256) bank_launches.push_back({kernel, voices, partials, chunk_log2, waves_per_group, frames_per_lane, voices_per_wave, frames});
+    }
     // Block streaming (fr_stream_*): one resident launch renders 64-frame blocks on a doorbell (kernels.hpp BankStreamCtl)
     bool streaming = false;
     double stream_trace_us[2] = {0, 0};
@@ -559,7 +589,7 @@ struct fr_renderer {
         for (const BankStage &bs : plan.banks) {
             if (bs.grp.jit || bs.grp.general || bs.grp.input_slot != slot) continue;
             uint32_t c, f, w, small, vpw;
-            bank_shape(bs.grp.log2_p, (uint32_t)bs.grp.rows.size(), n_times, c, f, w, small, vpw);
+            shape_bank(bs.grp.log2_p, (uint32_t)bs.grp.rows.size(), n_times, c, f, w, small, vpw);
             if (small == 1) return false;
         }
         // a window with look-back reads the stored history, so the row must be there first; in steady state the bank
@@ -917,6 +947,7 @@ struct fr_renderer {
 
     // ---- execution --------------------------------------------------------------------------------
     void execute(float *d_dst, uint32_t n_slots, uint64_t n_times, uint64_t idx, hipStream_t st) {
+        bank_launches.clear();
         ensure_plan(n_slots, st);
         if (n_slots == 0 || n_times == 0) return;
         const StagedPlan &sp = plan.sp;
@@ -1094,6 +1125,7 @@ struct fr_renderer {
                     j.track_stride = call_track_stride;
                     j.track_limit = (uint32_t)std::min<uint64_t>((uint64_t)track_from + call_track_rows, 0xFFFFFFFFull);
                 }
+                note_bank_launch("jit_bank", a.n_voices, 1u << a.log2_p, j.log2_p, 4, 1, j.voices_per_wave, blen);
                 Scope sc(this, &t_bank, st);
                 HIP_CHECK(launch_jit_bank(*bs.jit, j, st));
                 if (pieces_log2) {
@@ -1123,6 +1155,7 @@ struct fr_renderer {
                     while (vpw > 1 && nb(vpw) < 2048) vpw >>= 1;
                     if (nb(vpw) >= 1024) a.voices_per_wave = vpw;
                 }
+                note_bank_launch("gbank", a.n_voices, bs.grp.max_leaves, 0, 4, 1, a.voices_per_wave, blen);
                 Scope sc(this, &t_bank, st);
                 HIP_CHECK(launch_gbank(a, st));
                 sc.done();
@@ -1131,7 +1164,7 @@ struct fr_renderer {
             // (a host that renders ahead on alternating streams gets launches that can overlap: a GPU's share of a voice-sharded
             //  job, 8 x 4096 x 4800, takes 16.3 us per call that way against 20.9 with chunks + tickets on one stream -- the tail of
             //  one call's few latency-bound waves fills with the next call's first; profiles/r03_fewvoices.txt)
-            bank_shape(a.log2_p, a.n_voices, blen, a.chunk_log2, a.frames_per_lane, a.waves_per_group, a.small_call, a.voices_per_wave, host_pipelines);
+            shape_bank(a.log2_p, a.n_voices, blen, a.chunk_log2, a.frames_per_lane, a.waves_per_group, a.small_call, a.voices_per_wave, host_pipelines);
             if (a.voices_per_wave && !allow_multi) {   // A/B: the quarter-voice-per-wave kernel, one frame per lane
                 a.voices_per_wave = 0;
                 a.frames_per_lane = 1;
@@ -1163,6 +1196,8 @@ struct fr_renderer {
                     a.tickets = d_tickets.as<uint32_t>();
                 }
             }
+            note_bank_launch(a.small_call == 2 ? "bank_short_kernel" : a.small_call ? "bank_small_kernel" : a.voices_per_wave ? "bank_multi_kernel" : "bank_kernel",
+                             a.n_voices, 1u << a.log2_p, a.chunk_log2, a.waves_per_group, a.frames_per_lane, a.voices_per_wave, blen);
             Scope sc(this, &t_bank, st);
             HIP_CHECK(launch_bank(a, st));
             sc.done();
@@ -1398,14 +1433,135 @@ void check_fill_args(const void *out, uint32_t n_slots, uint64_t n_times, const 
     if (n_slots && n_times > (1ull << 40) / n_slots) throw Error(FR_ERR_INVALID_ARG, "render range too large");
 }
 
+// ---- per-renderer options (friendship_render_ext.h) -------------------------------------------------------------------
+// One row per switch; the environment and fr_renderer_create_with_options both go through it.  `env`: the lenient reading
+// the variable has always had (atoi, clamping).  An option must be decimal digits in [lo, hi] -- with `set`, one of the
+// values whose bits it has -- or `word`, which stands for `word_value`.  `apply` stores a value in the renderer; `given`:
+// it came from the environment or an option, not from the default.
+enum OptionSource : uint8_t { OPTION_DEFAULT, OPTION_ENV, OPTION_GIVEN };
+struct Knob {
+    const char *name;
+    int64_t dflt, lo, hi;
+    uint32_t set;
+    const char *word;
+    int64_t word_value;
+    int64_t (*env)(const char *e);
+    void (*apply)(fr_renderer &r, int64_t v, bool given);
+};
+
+int64_t env_on(const char *e) { return e[0] != '0'; }
+int64_t env_int(const char *e) { return std::atoi(e); }
+int64_t env_long(const char *e) { return std::atoll(e); }
+int64_t env_clamp(const char *e, int lo, int hi) { return std::min(hi, std::max(lo, std::atoi(e))); }
+
+const Knob kKnobs[] = {
+    {"FR_JIT", 1, 0, 1, 0, nullptr, 0, env_on, [](fr_renderer &r, int64_t v, bool) { r.allow_jit = v != 0; }},
+    {"FR_STAGE_JIT", 1, 0, 1, 0, "force", 2, [](const char *e) -> int64_t { return e[0] == '0' ? 0 : (e[0] == '1' ? 1 : 2); },
+     [](fr_renderer &r, int64_t v, bool) { r.stage_jit_mode = (int)v; }},
+    {"FR_JIT_FMA", 1, 0, 1, 0, nullptr, 0, env_on, [](fr_renderer &r, int64_t v, bool) { r.jit_fma = v != 0; }},
+    {"FR_JIT_CHUNKS", 1, 0, 1, 0, nullptr, 0, env_on, [](fr_renderer &r, int64_t v, bool) { r.jit_chunks = v != 0; }},
+    {"FR_JIT_CHUNK_TARGET", 0, 0, 1 << 24, 0, nullptr, 0, [](const char *e) -> int64_t { return std::max(1, std::atoi(e)); },
+     [](fr_renderer &r, int64_t v, bool) { r.jit_chunk_target = (uint64_t)v; }},
+    {"FR_BANK_TEMPLATE", 1, 0, 1, 0, nullptr, 0, env_on, [](fr_renderer &r, int64_t v, bool) { r.allow_template = v != 0; }},
+    {"FR_BANK_LEAF", 1, 0, 1, 0, nullptr, 0, [](const char *e) -> int64_t { return e[0] == '1'; },
+     [](fr_renderer &r, int64_t v, bool) { r.bank_leaf_variant = v ? 1u : 0u; }},
+    {"FR_BANK_MULTI", 1, 0, 1, 0, nullptr, 0, env_on, [](fr_renderer &r, int64_t v, bool) { r.allow_multi = v != 0; }},
+    {"FR_BANK_SHORT", 1, 0, 1, 0, nullptr, 0, env_on, [](fr_renderer &r, int64_t v, bool) { r.bank_tune.short_kernel = v != 0; }},
+    {"FR_SHORT_PAIRS", 1000, 0, 1 << 30, 0, nullptr, 0, env_int, [](fr_renderer &r, int64_t v, bool) { r.bank_tune.short_pairs = (uint64_t)v; }},
+    {"FR_SHORT_WGS", 0, 0, 1 << 30, 0, nullptr, 0, env_int, [](fr_renderer &r, int64_t v, bool) { r.bank_tune.short_wgs = (uint64_t)v; }},
+    {"FR_SHORT_NW", 0, 0, 16, 1u << 0 | 1u << 4 | 1u << 8 | 1u << 16, nullptr, 0, env_int,
+     [](fr_renderer &r, int64_t v, bool) { r.bank_tune.short_nw = (uint32_t)v; }},
+    {"FR_BANK_NW", 0, 0, 8, 1u << 0 | 1u << 4 | 1u << 8, nullptr, 0, env_int, [](fr_renderer &r, int64_t v, bool) { r.bank_tune.bank_nw = (uint32_t)v; }},
+    {"FR_BANK_F", 0, 0, 4, 1u << 0 | 1u << 1 | 1u << 2 | 1u << 4, nullptr, 0, env_int,
+     [](fr_renderer &r, int64_t v, bool) { r.bank_tune.bank_f = (uint32_t)v; }},
+    {"FR_HOST_MAPPED", 2, 0, 3, 0, nullptr, 0, env_int, [](fr_renderer &r, int64_t v, bool) {
+         r.host_out_mapped = (v & 1) != 0;
+         r.host_rows_mapped = (v & 2) != 0;
+     }},
+    {"FR_HOST_STREAM", 1, 0, 1, 0, nullptr, 0, env_on, [](fr_renderer &r, int64_t v, bool) { r.host_stream = v != 0; }},
+    {"FR_HOST_SMALL_KB", 96, 0, 1 << 20, 0, nullptr, 0, [](const char *e) -> int64_t { return std::max(0, std::atoi(e)); },
+     [](fr_renderer &r, int64_t v, bool) { r.host_small_bytes = (size_t)v << 10; }},
+    {"FR_HOST_DIRECT", 1, 0, 1, 0, nullptr, 0, env_on, [](fr_renderer &r, int64_t v, bool) { r.host_direct = v != 0; }},
+    {"FR_STREAM_IDLE_MS", BANK_STREAM_IDLE_MS, 1, 60000, 0, nullptr, 0, [](const char *e) { return env_clamp(e, 1, 60000); },
+     [](fr_renderer &r, int64_t v, bool) { r.stream_idle_ms = (uint32_t)v; }},
+    {"FR_STAGE_STRIDED", 1, 0, 1, 0, nullptr, 0, env_on, [](fr_renderer &r, int64_t v, bool) { r.fused_strided_ok = v != 0; }},
+    {"FR_STAGE_BLOCK", 0, 0, 16, 0, nullptr, 0, [](const char *e) -> int64_t { return std::max(0, std::atoi(e)); },
+     [](fr_renderer &r, int64_t v, bool) { r.stage_block_env = (uint32_t)v; }},
+    // (setting either exchange knob also tiles over the host-callback transport)
+    {"FR_EXCHANGE_TILES", 4, 1, 64, 0, nullptr, 0, [](const char *e) { return env_clamp(e, 1, 64); }, [](fr_renderer &r, int64_t v, bool given) {
+         r.x_max_tiles = (uint32_t)v;
+         r.x_tiles_explicit = r.x_tiles_explicit || given;
+     }},
+    {"FR_EXCHANGE_MIN_TILE", 1024, 64, 1 << 20, 0, nullptr, 0, [](const char *e) { return env_clamp(e, 64, 1 << 20); },
+     [](fr_renderer &r, int64_t v, bool given) {
+         r.x_min_tile = (uint32_t)v;
+         r.x_tiles_explicit = r.x_tiles_explicit || given;
+     }},
+    // (the helper threads are a process-wide pool; how many of them a renderer's lowering uses is its own)
+    {"FR_LOWER_THREADS", (int64_t)default_lowering_threads(), 1, 1024, 0, nullptr, 0, [](const char *e) -> int64_t { return std::max(1, std::atoi(e)); },
+     [](fr_renderer &r, int64_t v, bool) { r.lower_threads = (unsigned)v; }},
+    {"FR_LOWER_PAR_MIN_NODES", 200000, 0, 1ll << 40, 0, nullptr, 0, env_long, [](fr_renderer &r, int64_t v, bool) { r.lower_min_nodes = (size_t)v; }},
+    {"FR_LOWER_PAR_MIN_EDIT", 16384, 0, 1ll << 40, 0, nullptr, 0, env_long, [](fr_renderer &r, int64_t v, bool) { r.lower_min_edit = (size_t)v; }},
+};
+static_assert(sizeof kKnobs / sizeof kKnobs[0] == N_OPTIONS, "N_OPTIONS counts the rows of kKnobs");
+
+bool parse_option(const Knob &k, const char *s, int64_t &v) {
+    if (k.word && std::strcmp(s, k.word) == 0) {
+        v = k.word_value;
+        return true;
+    }
+    const size_t n = std::strlen(s);
+    if (n == 0 || n > 15) return false;   // (15 digits cannot overflow an int64_t)
+    v = 0;
+    for (size_t i = 0; i < n; ++i) {
+        if (s[i] < '0' || s[i] > '9') return false;
+        v = v * 10 + (s[i] - '0');
+    }
+    if (v < k.lo || v > k.hi) return false;
+    return !k.set || (v < 32 && ((k.set >> v) & 1u));
+}
+
+std::string option_text(const Knob &k, int64_t v) { return k.word && v == k.word_value ? std::string(k.word) : std::to_string(v); }
+
+// Every knob's value and source: the default, then the environment, then the options.  False (nothing resolved) for an
+// option the table refuses.
+bool resolve_options(const fr_option *options, size_t n_options, int64_t *value, uint8_t *source) {
+    if (n_options && !options) return false;
+    for (size_t i = 0; i < N_OPTIONS; ++i) {
+        value[i] = kKnobs[i].dflt;
+        source[i] = OPTION_DEFAULT;
+        if (const char *e = std::getenv(kKnobs[i].name)) {
+            value[i] = kKnobs[i].env(e);
+            source[i] = OPTION_ENV;
+        }
+    }
+    for (size_t j = 0; j < n_options; ++j) {
+        const fr_option &o = options[j];
+        if (!o.name || !o.value) return false;
+        size_t i = 0;
+        while (i < N_OPTIONS && std::strcmp(o.name, kKnobs[i].name) != 0) ++i;
+        // (not in the table: unknown, or process-wide -- FR_JIT_CACHE, FR_JIT_DUMP, FR_HOST_TRACE, FR_LOWER_TRACE, FR_PLAN_TRACE
+        //  and FR_LOWER_HUGEPAGES act on the process: files, stderr, the memory allocator)
+        if (i == N_OPTIONS) return false;
+        if (source[i] == OPTION_GIVEN || !parse_option(kKnobs[i], o.value, value[i])) return false;
+        source[i] = OPTION_GIVEN;
+    }
+    return true;
+}
+
 }  // namespace
 
 extern "C" {
 
-fr_status fr_renderer_create(const fr_config *cfg, fr_renderer **out) {
+fr_status fr_renderer_create(const fr_config *cfg, fr_renderer **out) { return fr_renderer_create_with_options(cfg, nullptr, 0, out); }
+
+fr_status fr_renderer_create_with_options(const fr_config *cfg, const fr_option *options, size_t n_options, fr_renderer **out) {
     if (!out) return FR_ERR_INVALID_ARG;
     *out = nullptr;
     if (cfg && cfg->abi_version != FR_ABI_VERSION) return FR_ERR_INVALID_ARG;
+    int64_t opt_value[N_OPTIONS];
+    uint8_t opt_source[N_OPTIONS];
+    if (!resolve_options(options, n_options, opt_value, opt_source)) return FR_ERR_INVALID_ARG;
     int mode = cfg ? cfg->mode : FR_MODE_AUTO;
     if (mode < FR_MODE_AUTO || mode > FR_MODE_STAGED) return FR_ERR_INVALID_ARG;
     if (cfg && ((cfg->flags & ~FR_CONFIG_SYNC_COMPILE) != 0 || cfg->reserved != 0)) return FR_ERR_INVALID_ARG;
@@ -1436,27 +1592,14 @@ fr_status fr_renderer_create(const fr_config *cfg, fr_renderer **out) {
     r->mirror.sparkle = cfg && cfg->semantics == FR_SEMANTICS_SPARKLE;
     r->semantics = cfg ? cfg->semantics : FR_SEMANTICS_REFERENCE;
     r->history_frames = cfg ? cfg->history_frames : 0;
-    if (const char *lv = std::getenv("FR_BANK_LEAF")) r->bank_leaf_variant = (lv[0] == '1') ? 1u : 0u;
-    if (const char *jv = std::getenv("FR_JIT")) r->allow_jit = jv[0] != '0';
-    if (const char *tv = std::getenv("FR_BANK_TEMPLATE")) r->allow_template = tv[0] != '0';
-    if (const char *mv = std::getenv("FR_BANK_MULTI")) r->allow_multi = mv[0] != '0';
-    if (const char *tv2 = std::getenv("FR_HOST_TRACE")) r->host_trace = tv2[0] == '1';
-    if (const char *dv = std::getenv("FR_HOST_DIRECT")) r->host_direct = dv[0] != '0';
-    if (const char *kv = std::getenv("FR_HOST_SMALL_KB")) r->host_small_bytes = (size_t)std::max(0, std::atoi(kv)) << 10;
-    if (const char *sv2 = std::getenv("FR_HOST_STREAM")) r->host_stream = sv2[0] != '0';
-    if (const char *hv = std::getenv("FR_HOST_MAPPED")) {
-        const int m = std::atoi(hv);
-        r->host_out_mapped = (m & 1) != 0;
-        r->host_rows_mapped = (m & 2) != 0;
+    for (size_t i = 0; i < N_OPTIONS; ++i) {
+        kKnobs[i].apply(*r, opt_value[i], opt_source[i] != OPTION_DEFAULT);
+        r->option_value[i] = opt_value[i];
+        r->option_source[i] = opt_source[i];
     }
-    if (const char *sv = std::getenv("FR_STAGE_JIT")) r->stage_jit_mode = sv[0] == '0' ? 0 : (sv[0] == '1' ? 1 : 2);
-    if (const char *fv = std::getenv("FR_STAGE_STRIDED")) r->fused_strided_ok = fv[0] != '0';
-    if (const char *cv = std::getenv("FR_JIT_CHUNKS")) r->jit_chunks = cv[0] != '0';
-    if (const char *bv = std::getenv("FR_STAGE_BLOCK")) r->stage_block_env = (uint32_t)std::max(0, std::atoi(bv));
-    if (const char *cv = std::getenv("FR_JIT_CHUNK_TARGET")) r->jit_chunk_target = (uint64_t)std::max(1, std::atoi(cv));
-    if (const char *xv = std::getenv("FR_EXCHANGE_TILES")) { r->x_max_tiles = (uint32_t)std::min(64, std::max(1, std::atoi(xv))); r->x_tiles_explicit = true; }
-    if (const char *xv = std::getenv("FR_EXCHANGE_MIN_TILE")) { r->x_min_tile = (uint32_t)std::min(1 << 20, std::max(64, std::atoi(xv))); r->x_tiles_explicit = true; }
-    if (const char *iv = std::getenv("FR_STREAM_IDLE_MS")) r->stream_idle_ms = (uint32_t)std::min(60000, std::max(1, std::atoi(iv)));
+    r->jit_cache.set_fma_fold(r->jit_fma);
+    r->lowering.set_parallel(r->lower_threads, r->lower_min_nodes, r->lower_min_edit);
+    if (const char *tv2 = std::getenv("FR_HOST_TRACE")) r->host_trace = tv2[0] == '1';   // (process-wide switches: environment only)
     r->device_cus = prop.multiProcessorCount;
     if (hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking) != hipSuccess) {
         delete r;
@@ -1955,12 +2098,32 @@ uint32_t fr_abi_version(void) { return FR_ABI_VERSION; }
 const char *fr_plan_json(fr_renderer *r) {
     if (!r) return "{}";
     r->plan_json_cache = r->plan.valid ? r->plan.json : "{}";
-    if (r->plan.valid && r->plan_json_cache.size() > 1) {   // live counters of the exchange step (partial-block sharding)
+    if (r->plan.valid && r->plan_json_cache.size() > 1) {   // live: counters of the exchange step (partial-block sharding), the last call's bank launches
         r->plan_json_cache.pop_back();
         r->plan_json_cache += ",\"exchange_stats\":{\"calls\":" + std::to_string(r->exchange_calls) + ",\"tiles\":" + std::to_string(r->exchange_tiles) +
-                              ",\"bytes_sent\":" + std::to_string(r->exchange_bytes) + "}}";
+                              ",\"bytes_sent\":" + std::to_string(r->exchange_bytes) + "},\"bank_launches\":[";
+        for (size_t i = 0; i < r->bank_launches.size(); ++i) {
+            const BankLaunchNote &b = r->bank_launches[i];
+            r->plan_json_cache += std::string(i ? "," : "") + "{\"kernel\":\"" + b.kernel + "\",\"voices\":" + std::to_string(b.voices) +
+                                  ",\"partials\":" + std::to_string(b.partials) + ",\"frames\":" + std::to_string(b.frames) +
+                                  ",\"chunk_log2\":" + std::to_string(b.chunk_log2) + ",\"waves_per_group\":" + std::to_string(b.waves_per_group) +
+                                  ",\"frames_per_lane\":" + std::to_string(b.frames_per_lane) + ",\"voices_per_wave\":" + std::to_string(b.voices_per_wave) + "}";
+        }
+        r->plan_json_cache += "]}";
     }
     return r->plan_json_cache.c_str();
+}
+
+const char *fr_options_json(fr_renderer *r) {
+    if (!r) return "{}";
+    static const char *const kSource[] = {"default", "env", "option"};
+    std::string &js = r->options_json_cache;
+    js = "{";
+    for (size_t i = 0; i < N_OPTIONS; ++i)
+        js += std::string(i ? "," : "") + "\"" + kKnobs[i].name + "\":{\"value\":\"" + option_text(kKnobs[i], r->option_value[i]) +
+              "\",\"source\":\"" + kSource[r->option_source[i]] + "\"}";
+    js += "}";
+    return js.c_str();
 }
 
 fr_status fr_set_timing(fr_renderer *r, int32_t enabled) {

@@ -847,17 +847,23 @@ struct Lowering::Impl {
         return result;
     }
 
-    // (read at every from-scratch lowering, which is rare: tests switch them inside one process)
-    static unsigned par_threads() {
+    // Set by a renderer (Lowering::set_parallel, its options); otherwise read at every from-scratch lowering, which is rare:
+    // tests switch them inside one process.
+    bool par_configured = false;
+    unsigned par_threads_set = 1;
+    size_t par_min_nodes_set = 0, par_min_edit_set = 0;
+    unsigned par_threads() const {
+        if (par_configured) return par_threads_set;
         if (const char *e = std::getenv("FR_LOWER_THREADS")) return (unsigned)std::max(1, std::atoi(e));
-        const unsigned hw = std::thread::hardware_concurrency();
-        return std::min(32u, std::max(1u, hw));   // (measured on the 256-thread host of an MI355X box: 16 / 32 / 64 threads 92 / 59 / 113 ms at config C)
+        return default_lowering_threads();
     }
-    static size_t par_min_nodes() {
+    size_t par_min_nodes() const {
+        if (par_configured) return par_min_nodes_set;
         const char *e = std::getenv("FR_LOWER_PAR_MIN_NODES");
         return e ? (size_t)std::atoll(e) : (size_t)200000;
     }
-    static size_t par_min_edit() {   // journalled edits (a new node and its two edges are three) from which an incremental update goes parallel
+    size_t par_min_edit() const {   // journalled edits (a new node and its two edges are three) from which an incremental update goes parallel
+        if (par_configured) return par_min_edit_set;
         const char *e = std::getenv("FR_LOWER_PAR_MIN_EDIT");
         return e ? (size_t)std::atoll(e) : (size_t)16384;
     }
@@ -1106,6 +1112,12 @@ uint64_t Lowering::generation() const { return impl_->generation; }
 bool Lowering::last_was_full() const { return impl_->was_full; }
 uint64_t Lowering::last_relowered() const { return impl_->relowered; }
 uint64_t Lowering::last_parallel_subtrees() const { return impl_->par_items; }
+void Lowering::set_parallel(unsigned threads, size_t min_nodes, size_t min_edit) {
+    impl_->par_configured = true;
+    impl_->par_threads_set = std::max(1u, threads);
+    impl_->par_min_nodes_set = min_nodes;
+    impl_->par_min_edit_set = min_edit;
+}
 
 FlatGraph lower(const Mirror &m, uint32_t n_slots) {
     Lowering::Impl one_shot;

@@ -160,8 +160,8 @@ extern "C" __global__ void __launch_bounds__(256) jit_bank_multi(JitBankArgs a) 
 )JIT";
 
 std::string JitCache::generate_source(const LeafShape &shape, const std::vector<bool> &varying, const std::vector<uint32_t> &literal_bits,
-                                      const std::vector<uint32_t> &alias, bool sparkle) {
-    LeafSource ls = generate_leaf_source(shape, varying, literal_bits, alias, sparkle);
+                                      const std::vector<uint32_t> &alias, bool sparkle, bool fma_fold) {
+    LeafSource ls = generate_leaf_source(shape, varying, literal_bits, alias, sparkle, fma_fold);
     std::ostringstream call;
     call << "leaf<FAST>(x" << (ls.tracks ? ", trk, tstride, tlimit, tt" : "");
     auto track_index = [&](uint32_t i) { for (size_t q = 0; q < ls.track_params.size(); ++q) if (ls.track_params[q] == i) return (int)q; return -1; };
@@ -253,7 +253,7 @@ size_t JitCache::disk_hits() const { std::lock_guard<std::mutex> g(impl_->mu); r
 
 std::shared_ptr<JitKernel> JitCache::get(const LeafShape &shape, const std::vector<bool> &varying, const std::vector<uint32_t> &literal_bits,
                                          const std::vector<uint32_t> &alias) {
-    std::shared_ptr<JitKernel> jk = get_source(generate_source(shape, varying, literal_bits, alias, sparkle_), "jit_bank");
+    std::shared_ptr<JitKernel> jk = get_source(generate_source(shape, varying, literal_bits, alias, sparkle_, fma_fold_), "jit_bank");
     if (jk && !jk->k)
         for (size_t c = 0; c < varying.size(); ++c) jk->k += (varying[c] && alias[c] == c) ? 1 : 0;
     return jk;

@@ -97,7 +97,8 @@ bool plan_stage_jit(const std::vector<StageProg> &progs, const std::vector<Stage
 
 // Text of `template <bool FAST> float leaf(const float *x, float p0, ...)` for one leaf shape, preceded by the helper
 // functions it calls.  FAST = the body in which Modulo(x, 1.0) is one v_fract_f32 (valid under the conditions of
-// match.cpp's fract_form_is_exact + the kernel's per-wave input test).
+// match.cpp's fract_form_is_exact + the kernel's per-wave input test).  `fma_fold` (FR_JIT_FMA): y + (+-2^k * v) as one
+// exact fused multiply-add where it applies.
 struct LeafSource {
     std::string text;
     uint32_t k = 1;              // parameters per leaf (>= 1)
@@ -107,7 +108,7 @@ struct LeafSource {
     std::vector<uint32_t> track_params;   // parameters (0 .. k-1) that are per-leaf track slots: the leaf takes the row's VALUE there
 };
 LeafSource generate_leaf_source(const LeafShape &shape, const std::vector<bool> &varying, const std::vector<uint32_t> &literal_bits,
-                                const std::vector<uint32_t> &alias, bool sparkle = false);
+                                const std::vector<uint32_t> &alias, bool sparkle = false, bool fma_fold = true);
 
 // One compiled specialisation.
 struct JitKernel {
@@ -136,9 +137,10 @@ public:
     // any generated source with one extern "C" kernel `fn_name` (cached by source text)
     std::shared_ptr<JitKernel> get_source(const std::string &src, const char *fn_name);
     static std::string generate_source(const LeafShape &shape, const std::vector<bool> &varying, const std::vector<uint32_t> &literal_bits,
-                                       const std::vector<uint32_t> &alias, bool sparkle = false);
+                                       const std::vector<uint32_t> &alias, bool sparkle = false, bool fma_fold = true);
     void set_async(bool on) { async_ = on; }
     void set_sparkle(bool on) { sparkle_ = on; }   // FR_SEMANTICS_SPARKLE: baked into the generated leaves
+    void set_fma_fold(bool on) { fma_fold_ = on; } // FR_JIT_FMA=0: generated leaves without the exact fused multiply-add fold
     uint64_t epoch() const;        // bumped whenever a background compile finishes (successfully or not)
     size_t compiled() const;
     double compile_ms() const;
@@ -149,6 +151,7 @@ private:
     Impl *impl_;
     bool async_ = true;
     bool sparkle_ = false;
+    bool fma_fold_ = true;
 };
 
 hipError_t launch_jit_bank(const JitKernel &k, const JitBankArgs &a, hipStream_t s);

@@ -1011,13 +1011,12 @@ static hipError_t launch_bank_f(const BankArgs &a, hipStream_t s) {
 //    pass (T = 32: 13.9 us vs 31 us) and beats the lanes-over-partials kernel from T = 8 up (13.8 vs 17.4 us;
 //    T = 32: 13.9 vs 37 us); lanes-over-partials only ties at T = 1 (11.4 us), so it is used for T <= 2;
 //  * voices larger than one workgroup's capacity (8192 / 16384 partials) are split into chunks.
-static bool short_kernel_enabled() {   // FR_BANK_SHORT=0: A/B against the time-major kernel
-    static const bool on = [] { const char *e = std::getenv("FR_BANK_SHORT"); return !(e && e[0] == '0'); }();
-    return on;
-}
-
+//  * the renderer's options (bank_tuning) override parts of the rule for A/B runs: FR_BANK_SHORT=0 against the time-major
+//    kernel, FR_SHORT_PAIRS / FR_SHORT_WGS / FR_SHORT_NW / FR_BANK_F / FR_BANK_NW.
 void bank_shape(uint32_t log2_p, uint32_t n_voices, uint64_t n_times, uint32_t &chunk_log2, uint32_t &frames_per_lane,
                 uint32_t &waves_per_group, uint32_t &small_call, uint32_t &voices_per_wave, bool many_pairs_whole) {
+    static const BankTuning defaults;
+    const BankTuning &tu = bank_tuning ? *bank_tuning : defaults;
     frames_per_lane = 1;
     voices_per_wave = 0;
     small_call = 0;
@@ -1027,8 +1026,7 @@ void bank_shape(uint32_t log2_p, uint32_t n_voices, uint64_t n_times, uint32_t &
         // time-major one: T <= 64: 7.4 vs 11.2; 128: 8.3 vs 11.4; 256: 10.6 vs 11.6; 512: 19.5 vs 17.8 -- hence pairs <= 320.
         // 512 or 1024 workgroups (more, smaller chunks) cost 2-3 us more in ticket traffic; 8 waves +0.3 us, 4 waves +2.4.
         const uint64_t pairs = ((n_times + 63) / 64) * n_voices;
-        static const uint64_t max_pairs = [] { const char *e = std::getenv("FR_SHORT_PAIRS"); return e ? (uint64_t)std::atoi(e) : 1000ull; }();
-        if (short_kernel_enabled() && pairs <= max_pairs && log2_p >= 9 && log2_p <= 20 && pairs > 0) {
+        if (tu.short_kernel && pairs <= tu.short_pairs && log2_p >= 9 && log2_p <= 20 && pairs > 0) {
             // up to 320 pairs: ~256 workgroups of 16 waves; up to 1000 (a GPU's share of a voice-sharded job: 8 voices x 75
             // tiles): ~1200 workgroups of 8 waves -- 600 one-voice workgroups deal 2 or 3 to a CU (28 % idle), twice as
             // many half as long deal 4 or 5 (24.2 -> 21.9 us at 8 x 4096 x 4800; profiles/r02_short_calls.txt)
@@ -1036,15 +1034,13 @@ void bank_shape(uint32_t log2_p, uint32_t n_voices, uint64_t n_times, uint32_t &
             // (only where whole workgroups deal unevenly over the 256 CUs: 512 pairs are 2 per CU, and splitting them costs
             //  4 us of ticket traffic for nothing -- 17.7 -> 22.0 us at 64 x 4096 x 512)
             const bool lumpy = ((pairs + 255) / 256) * 256 * 100 >= pairs * 115;
-            static const uint64_t target_env = [] { const char *e = std::getenv("FR_SHORT_WGS"); return e ? (uint64_t)std::atoi(e) : 0ull; }();
-            static const uint32_t nw_env = [] { const char *e = std::getenv("FR_SHORT_NW"); return e ? (uint32_t)std::atoi(e) : 0u; }();
-            const uint64_t target = target_env ? target_env : (few ? 256ull : 1200ull);
+            const uint64_t target = tu.short_wgs ? tu.short_wgs : (few ? 256ull : 1200ull);
             uint32_t c = log2_p;
             uint64_t wgs = pairs;
             while (c > 9 && (wgs < target || c > 13)) { --c; wgs *= 2; }
             if (log2_p - c <= 8 && (few || (lumpy && c != log2_p && !many_pairs_whole))) {
                 chunk_log2 = c;
-                waves_per_group = nw_env ? nw_env : (few ? 16u : 8u);
+                waves_per_group = tu.short_nw ? tu.short_nw : (few ? 16u : 8u);
                 while ((1u << c) / waves_per_group < 8u) waves_per_group /= 2;   // a wave needs a whole group of 8
                 small_call = 2;
                 return;
@@ -1079,10 +1075,7 @@ void bank_shape(uint32_t log2_p, uint32_t n_voices, uint64_t n_times, uint32_t &
     // 2 or 4 frames per lane amortise it (measured with tools/bank_bench: 32 partials 2.1 -> 3.2 T partial-frames/s,
     // 128 partials 5.3 -> 6.2, 512 partials 8.5 -> 8.8; at 4096 one frame per lane is best)
     if (n_times >= 1024 && blocks >= 4096) frames_per_lane = log2_p <= 7 ? 4 : (log2_p <= 9 ? 2 : 1);
-    {   // A/B switch for measurements
-        static const uint32_t f_env = [] { const char *e = std::getenv("FR_BANK_F"); return e ? (uint32_t)std::atoi(e) : 0u; }();
-        if (f_env == 1 || f_env == 2 || f_env == 4) frames_per_lane = f_env;
-    }
+    if (tu.bank_f == 1 || tu.bank_f == 2 || tu.bank_f == 4) frames_per_lane = tu.bank_f;   // A/B switch for measurements
     if (n_times >= 512 && blocks < 320 && log2_p >= 10) {
         // a few big voices on a long call: too few workgroups to hide the scalar-load latency of the parameter stream
         // (one 8-wave workgroup per tile leaves a SIMD with 1-2 waves).  Split the voices into chunks of >= 512 partials,
@@ -1099,11 +1092,8 @@ void bank_shape(uint32_t log2_p, uint32_t n_voices, uint64_t n_times, uint32_t &
     // (64 x 4096 at 512 / 1024 frames, 512 / 1024 workgroups: 8 waves 20.7 / 32.3 us, 4 waves 23.4 / 35.5 us, chunks of 2^11 35 / 47 us)
     // (32 x 4096 x 4800, 2400 workgroups: 8 waves 65.2 us, 4 waves 66.9; 16 x 4096: 36.0 vs 38.5; 64 x 4096: equal)
     waves_per_group = (log2_p >= 14 || (blocks < 4096 && log2_p >= 6)) ? 8 : 4;
-    {
-        static const uint32_t nw_env = [] { const char *e = std::getenv("FR_BANK_NW"); return e ? (uint32_t)std::atoi(e) : 0u; }();
-        if (nw_env == 4 && log2_p < 14) waves_per_group = 4;   // A/B
-        if (nw_env == 8 && log2_p >= 6) waves_per_group = 8;
-    }
+    if (tu.bank_nw == 4 && log2_p < 14) waves_per_group = 4;   // A/B
+    if (tu.bank_nw == 8 && log2_p >= 6) waves_per_group = 8;
     const uint32_t cmax = waves_per_group == 8 ? 14 : 13;
     chunk_log2 = log2_p < cmax ? log2_p : cmax;
 }

@@ -53,7 +53,7 @@ __device__ __forceinline__ float jit_min(float a, float b) {   // Rust >= 1.20 f
 )JIT";
 
 LeafSource generate_leaf_source(const LeafShape &shape, const std::vector<bool> &varying, const std::vector<uint32_t> &literal_bits,
-                                const std::vector<uint32_t> &alias, bool sparkle) {
+                                const std::vector<uint32_t> &alias, bool sparkle, bool fma_fold) {
     std::ostringstream leaf;
     uint32_t k = 0;
     std::vector<int> pidx(shape.n_consts, -1);
@@ -119,8 +119,7 @@ LeafSource generate_leaf_source(const LeafShape &shape, const std::vector<bool> 
             // same real number the graph's two operations round -- bit for bit, zero signs included (a product that is
             // exact keeps its sign into the sum either way).  E.g. a triangle's 1 + (-4 * |u|).
             int prod = -1, other = -1;
-            static const bool fold = [] { const char *e = std::getenv("FR_JIT_FMA"); return !(e && e[0] == '0'); }();   // A/B switch
-            for (int side = 0; fold && side < 2 && prod < 0; ++side) {
+            for (int side = 0; fma_fold && side < 2 && prod < 0; ++side) {
                 const uint32_t m = side ? o.b : o.a;
                 const LeafShape::Op &mo = shape.ops[m];
                 if (mo.op != OP_MUL) continue;

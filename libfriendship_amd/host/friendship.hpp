@@ -41,6 +41,7 @@
 #include <sstream>
 
 #include "../../include/friendship_render.h"
+#include "../../include/friendship_render_ext.h"
 #include "json_sha.hpp"
 
 namespace friendship {
@@ -659,6 +660,7 @@ protected:
         decltype(&fr_set_track_inputs) set_track_inputs;
         decltype(&fr_fill_buffer_dense) fill_dense;
     } api_{};
+    decltype(&fr_options_json) options_json_ = nullptr;   // (optional: the product's extension)
 
     template <class T>
     void sym(T &fn, const char *name) {
@@ -699,10 +701,15 @@ protected:
     }
 
 public:
+    using Options = std::vector<std::pair<std::string, std::string>>;   // (name, value) of friendship_render_ext.h options
+
     // `semantics`: FR_SEMANTICS_REFERENCE (RefRenderer, the default) or FR_SEMANTICS_SPARKLE; `history_frames`: 0 = keep
     // every input sample since the last seek (the reference); `flags`: FR_CONFIG_SYNC_COMPILE for deterministic plans.
+    // `options`: this renderer's settings of the engine's switches (friendship_render_ext.h, e.g. {"FR_BANK_SHORT", "0"});
+    // they need a library that exports fr_renderer_create_with_options (Panic with FR_ERR_UNSUPPORTED otherwise).
     explicit PluginRenderer(const std::string &library_path, int mode = FR_MODE_AUTO, int device = -1,
-                            int semantics = FR_SEMANTICS_REFERENCE, uint64_t history_frames = 0, uint32_t flags = 0) {
+                            int semantics = FR_SEMANTICS_REFERENCE, uint64_t history_frames = 0, uint32_t flags = 0,
+                            const Options &options = {}) {
         dl_ = dlopen(library_path.c_str(), RTLD_NOW | RTLD_LOCAL);
         if (!dl_) throw std::runtime_error(std::string("cannot load renderer library: ") + dlerror());
         sym(api_.create, "fr_renderer_create");
@@ -723,12 +730,25 @@ public:
         sym(api_.set_track_inputs, "fr_set_track_inputs");
         sym(api_.fill_dense, "fr_fill_buffer_dense");
         fr_config cfg{FR_ABI_VERSION, device, mode, flags, semantics, 0, history_frames};
-        fr_status s = api_.create(&cfg, &h_);
+        fr_status s;
+        if (options.empty()) {
+            s = api_.create(&cfg, &h_);
+        } else {
+            auto create_with = (decltype(&fr_renderer_create_with_options))dlsym(dl_, "fr_renderer_create_with_options");
+            if (!create_with) {
+                dlclose(dl_);
+                throw Panic(FR_ERR_UNSUPPORTED, "renderer plugin " + library_path + " lacks fr_renderer_create_with_options: it takes no per-renderer options");
+            }
+            std::vector<fr_option> opts;
+            for (const auto &o : options) opts.push_back(fr_option{o.first.c_str(), o.second.c_str()});
+            s = create_with(&cfg, opts.data(), opts.size(), &h_);
+        }
         if (s != FR_OK) {
             std::string what = api_.status_string(s);
             dlclose(dl_);
-            throw Panic(s, "fr_renderer_create: " + what);
+            throw Panic(s, (options.empty() ? "fr_renderer_create: " : "fr_renderer_create_with_options: ") + what);
         }
+        options_json_ = (decltype(&fr_options_json))dlsym(dl_, "fr_options_json");
     }
     PluginRenderer(const PluginRenderer &) = delete;
     PluginRenderer &operator=(const PluginRenderer &) = delete;
@@ -737,6 +757,8 @@ public:
         if (dl_) dlclose(dl_);
     }
     std::string backend() const { return api_.backend_name(); }
+    // friendship_render_ext.h fr_options_json: every per-renderer option with its value and source ("" if the plugin has none).
+    std::string options_json() const { return options_json_ ? options_json_(h_) : ""; }
 
     // One process (and one renderer) per GPU: this renderer becomes rank `rank` of `world` (friendship_render.h
     // fr_set_shard).  Every rank is sent the same RouteGraph messages and the same RenderRange; it fills the rows
@@ -807,7 +829,8 @@ public:
         if (const char *p = std::getenv("FRIENDSHIP_HIP_LIB")) return p;
         return "libfriendship_hip.so";
     }
-    explicit HipRenderer(int mode = FR_MODE_AUTO, int device = -1) : PluginRenderer(default_path(), mode, device) {}
+    explicit HipRenderer(int mode = FR_MODE_AUTO, int device = -1, const Options &options = {})
+        : PluginRenderer(default_path(), mode, device, FR_SEMANTICS_REFERENCE, 0, 0, options) {}
 };
 
 }  // namespace render
