@@ -9,6 +9,8 @@
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
+#include <cfloat>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <chrono>
@@ -122,6 +124,8 @@ struct Plan {
     DevBuf d_split_dst;                  // partial-block sharding: destination (row, or ring | 1 << 31) per exchange workspace row
     DevBuf d_nodes, d_roots;             // pull: nodes (input slots remapped dense), roots per pull row
     std::vector<uint32_t> input_slots;   // dense input index -> external slot
+    const FlatGraph *graph = nullptr;    // the lowered graph the plan was made from (Lowering::update: stable)
+    bool observed_stale = false;         // FR_DELAY_OBSERVED: stored rows widened an input range past a planned look-back
     std::string json;
 };
 
@@ -132,13 +136,32 @@ struct BankLaunchNote {
     uint64_t frames;
 };
 
-constexpr size_t N_OPTIONS = 26;         // per-renderer options (friendship_render_ext.h; the table below fr_renderer)
+constexpr size_t N_OPTIONS = 28;         // per-renderer options (friendship_render_ext.h; the table below fr_renderer)
 
 struct TimerClass {
     double ms = 0;
     uint64_t launches = 0;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
 };
+
+// A host-loop definition of the range launch for builds without kernels.hip (the host-logic simulator, whose "device"
+// memory is host memory); the HIP library's kernels.hip defines the real one, which the linker takes instead of this.
+__attribute__((weak)) hipError_t launch_input_range(const RangeArgs &a, hipStream_t) {
+    for (uint32_t r = 0; r < a.n_rows; ++r)
+        for (uint32_t b = 0; b < a.blocks; ++b) {
+            RangePart o{HUGE_VALF, -HUGE_VALF, 0, 0};
+            for (uint64_t i = (uint64_t)b * RANGE_THREADS; i < a.len[r]; i += (uint64_t)a.blocks * RANGE_THREADS)
+                for (uint64_t j = i; j < std::min<uint64_t>(i + RANGE_THREADS, a.len[r]); ++j) {
+                    const float v = a.row[r][j];
+                    if (v != v) o.flags |= RANGE_NAN;
+                    else if (v == HUGE_VALF) o.flags |= RANGE_POS_INF;
+                    else if (v == -HUGE_VALF) o.flags |= RANGE_NEG_INF;
+                    else { o.lo = std::min(o.lo, v); o.hi = std::max(o.hi, v); }
+                }
+            a.out[(size_t)r * a.blocks + b] = o;
+        }
+    return hipSuccess;
+}
 
 }  // namespace fr
 
@@ -282,7 +305,7 @@ struct fr_renderer {
     }
     bool plan_current(uint32_t n_slots) const {
         return plan.valid && plan.version == mirror.version && plan.n_slots == n_slots && plan.shard_epoch == shard_epoch &&
-               !(plan.jit_pending && plan.jit_epoch != jit_cache.epoch());
+               !(plan.jit_pending && plan.jit_epoch != jit_cache.epoch()) && !plan.observed_stale;
     }
 
     // Pairwise exchange with `peer` on stream st (device pointers, counts in floats).
@@ -507,6 +530,120 @@ struct fr_renderer {
         tc.pending.clear();
     }
 
+    // ---- observed input ranges (FR_DELAY_OBSERVED, stage.hpp ObservedInputs) ---------------------------------------
+    // One hull per input slot of every value stored since the last seek.  It holds +0.0 from the start (unfed slots, zero
+    // prefixes and frames beyond what was stored read 0.0), only ever widens until a seek, and a history_frames cap never
+    // shrinks it.  Only the slots the plan's observed amounts read are scanned as rows arrive (plan.sp.observed_slots); any
+    // other slot that receives data becomes unknown, and is reduced over its stored history when a plan first asks for it.
+    bool delay_observed = false;         // FR_DELAY_OBSERVED
+    uint64_t delay_observed_max = 1u << 20;   // FR_DELAY_OBSERVED_MAX: the largest look-back the mode plans
+    struct Hull {
+        float lo = 0.0f, hi = 0.0f;      // finite values
+        uint32_t flags = 0;              // kernels.hpp RANGE_*
+        bool known = true;
+    };
+    std::vector<Hull> hulls;
+    uint64_t lookback_growths = 0;       // re-plans because stored rows widened an amount's bound past its planned look-back
+    uint64_t range_launches = 0;         // input_range_kernel launches
+    uint64_t deferred_len = 0;           // frames of every row in `deferred` (the call's n_times)
+    PinnedBuf h_range;
+    static bool widen(Hull &h, float lo, float hi, uint32_t flags) {
+        const bool w = lo < h.lo || hi > h.hi || (flags & ~h.flags) != 0;
+        h.lo = std::min(h.lo, lo);
+        h.hi = std::max(h.hi, hi);
+        h.flags |= flags;
+        return w;
+    }
+    // Reduces device rows with input_range_kernel and waits for the result.  `hull_of[i]` receives row i's values.
+    bool reduce_device_rows(const std::vector<std::pair<const float *, uint64_t>> &rows, const std::vector<Hull *> &hull_of, hipStream_t st) {
+        bool widened = false;
+        for (size_t first = 0; first < rows.size(); first += RANGE_MAX_ROWS) {
+            RangeArgs a{};
+            a.n_rows = (uint32_t)std::min<size_t>(RANGE_MAX_ROWS, rows.size() - first);
+            uint64_t longest = 0;
+            for (uint32_t i = 0; i < a.n_rows; ++i) {
+                a.row[i] = rows[first + i].first;
+                a.len[i] = rows[first + i].second;
+                longest = std::max(longest, a.len[i]);
+            }
+            // (a block per 16 K values: one block covers a real-time call's row, long histories spread over up to 64)
+            a.blocks = (uint32_t)std::min<uint64_t>(RANGE_MAX_BLOCKS, std::max<uint64_t>(1, (longest + 16383) / 16384));
+            h_range.ensure((size_t)a.n_rows * a.blocks * sizeof(RangePart));
+            a.out = h_range.as_dev<RangePart>();
+            HIP_CHECK(launch_input_range(a, st));
+            ++range_launches;
+            HIP_CHECK(hipStreamSynchronize(st));   // the plan depends on the result
+            const RangePart *part = h_range.as<RangePart>();
+            for (uint32_t i = 0; i < a.n_rows; ++i)
+                for (uint32_t b = 0; b < a.blocks; ++b) {
+                    const RangePart &o = part[(size_t)i * a.blocks + b];
+                    widened = widen(*hull_of[first + i], o.lo, o.hi, o.flags) || widened;
+                }
+        }
+        return widened;
+    }
+    // The observed range of `slot` for the planner; an unknown hull is first rebuilt from the slot's visible history (plus a
+    // row of this call that a bank kernel will append).
+    Range observed_range(uint32_t slot, hipStream_t st) {
+        if (slot >= hulls.size() || slot >= n_vecs) return Range{0.0, 0.0, false};
+        Hull &h = hulls[slot];
+        if (!h.known) {
+            h = Hull{};
+            std::vector<std::pair<const float *, uint64_t>> rows;
+            const DevInput d = dev_input(slot);
+            if (d.data && d.len > d.base) rows.push_back({d.data, d.len - d.base});
+            for (const Deferred &df : deferred)
+                if (df.slot == slot && df.dst) rows.push_back({df.src, deferred_len});
+            reduce_device_rows(rows, std::vector<Hull *>(rows.size(), &h), st);
+        }
+        return Range{(h.flags & RANGE_NEG_INF) ? -HUGE_VAL : (double)h.lo, (h.flags & RANGE_POS_INF) ? HUGE_VAL : (double)h.hi,
+                     (h.flags & RANGE_NAN) != 0};
+    }
+    ObservedInputs observed_inputs(hipStream_t st) {
+        ObservedInputs o;
+        o.max_lookback = delay_observed_max;
+        o.range = [this, st](uint32_t slot) { return observed_range(slot, st); };
+        return o;
+    }
+    // store_inputs, before any row is stored: takes this call's rows of the observed slots into their hulls, and marks the
+    // plan stale when they widen a bound past its planned look-back (the call re-plans, rebuilding the rings' window with
+    // the larger look-back) or when a seek lets bounds shrink.  Only plans with observed slots scan; only device rows wait.
+    void observe_rows(uint32_t n_slots, uint32_t rows, const float *in_data, const uint64_t *offs, bool device_rows, bool seek, hipStream_t st) {
+        if (seek) {
+            for (Hull &h : hulls) h = Hull{};
+            if (plan.valid && (!plan.sp.observed.empty() || plan.sp.observed_refused)) plan.observed_stale = true;
+        }
+        if (hulls.size() < rows) hulls.resize(rows);
+        const std::vector<uint32_t> &want = plan.sp.observed_slots;   // (the plan in hand: its successor reads the same slots)
+        std::vector<std::pair<const float *, uint64_t>> dev_rows;
+        std::vector<Hull *> dev_hulls;
+        bool widened = false;
+        for (uint32_t r = 0; r < rows; ++r) {
+            const uint64_t rl = offs[r + 1] - offs[r];
+            if (!rl) continue;   // (padding repeats the last stored value, or 0.0: both already in the hull)
+            Hull &h = hulls[r];
+            if (!h.known || !std::binary_search(want.begin(), want.end(), r)) { h.known = false; continue; }
+            if (device_rows) {
+                dev_rows.push_back({in_data + offs[r], rl});
+                dev_hulls.push_back(&h);
+                continue;
+            }
+            float lo = HUGE_VALF, hi = -HUGE_VALF;
+            uint32_t fl = 0;
+            for (const float *v = in_data + offs[r], *e = v + rl; v != e; ++v) {
+                const float x = *v;
+                if (x >= -FLT_MAX && x <= FLT_MAX) { lo = std::min(lo, x); hi = std::max(hi, x); }
+                else fl |= x != x ? RANGE_NAN : x > 0.0f ? RANGE_POS_INF : RANGE_NEG_INF;
+            }
+            widened = widen(h, lo, hi, fl) || widened;
+        }
+        if (!dev_rows.empty()) widened = reduce_device_rows(dev_rows, dev_hulls, st) || widened;
+        if (widened && !seek && plan_current(n_slots) && !plan.sp.observed.empty() && !observed_plan_holds(*plan.graph, plan.sp, observed_inputs(st))) {
+            plan.observed_stale = true;
+            ++lookback_growths;
+        }
+    }
+
     // ---- input store (reference.rs:47-75) -------------------------------------------------------
     // Frames of input history kept per slot (0 = everything since the last seek: the reference, reference.rs:25).  With
     // fr_config.history_frames set, at least what the current plan's constant delays and proven bounds can reach.
@@ -716,6 +853,8 @@ struct fr_renderer {
         if (n_vecs < want) { segs.push_back({n_vecs, want, idx}); n_vecs = want; }
         uint32_t rows = (uint32_t)std::min<uint64_t>(n_rows, n_vecs);   // zip stops at the shorter (:68)
         if (rows > slots.size()) slots.resize(rows);
+        deferred_len = n_times;
+        if (delay_observed) observe_rows(n_slots, rows, in_data, offs, device_rows, seek, st);
         // (every host-buffer call ends with a stream synchronisation, so the staging buffer is idle here)
         if (!device_rows && rows) h_in_stage.ensure((size_t)rows * n_times * sizeof(float));
         for (uint32_t r = 0; r < rows; ++r) {
@@ -798,7 +937,10 @@ struct fr_renderer {
             matcher.reset(new BankMatcher(fg, 20, use_jit, allow_template, track_from));
             matcher_gen = lowering.generation();
         }
-        p.sp = plan_stages(fg, mode == FR_MODE_AUTO, mode != FR_MODE_PULL, 20, use_jit, allow_template, matcher.get(), shard_spec, track_from);
+        p.graph = &fg;
+        const ObservedInputs obs = observed_inputs(st);
+        const ObservedInputs *observed = delay_observed ? &obs : nullptr;
+        p.sp = plan_stages(fg, mode == FR_MODE_AUTO, mode != FR_MODE_PULL, 20, use_jit, allow_template, matcher.get(), shard_spec, track_from, observed);
         std::vector<std::shared_ptr<JitKernel>> jits(p.sp.banks.size());
         p.jit_epoch = jit_cache.epoch();   // (read first: a compile finishing from here on makes this plan stale)
         if (use_jit) {
@@ -824,7 +966,7 @@ struct fr_renderer {
                     throw Error(FR_ERR_DEVICE, std::string("a kernel of the sharded plan could not be compiled on this rank (every rank must plan alike): ") + e.what());
             }
             if (without) {
-                p.sp = plan_stages(fg, true, true, 20, false, true, nullptr, shard_spec, track_from);
+                p.sp = plan_stages(fg, true, true, 20, false, true, nullptr, shard_spec, track_from, observed);
                 jits.assign(p.sp.banks.size(), nullptr);
             }
         }
@@ -927,6 +1069,9 @@ struct fr_renderer {
            << ",\"stage_jit\":" << (p.stage_jit ? "true" : "false") << ",\"stage_shapes\":" << p.stage_shapes
            << ",\"rings\":" << p.sp.n_rings << ",\"max_lookback\":" << p.sp.lmax
            << ",\"input_lookback\":" << p.sp.input_lookback << ",\"input_lookback_unbounded\":" << (p.sp.input_lookback_unbounded ? "true" : "false")
+           << ",\"delay_observed\":" << (delay_observed ? "true" : "false") << ",\"delay_observed_max\":" << delay_observed_max
+           << ",\"observed_delays\":" << p.sp.observed.size() << ",\"observed_lookback\":" << p.sp.observed_lookback
+           << ",\"observed_refused\":" << p.sp.observed_refused
            << ",\"history_frames\":" << history_frames
            << ",\"jit_pending\":" << (p.jit_pending ? "true" : "false") << ",\"jit_kernels_compiled\":" << jit_cache.compiled() << ",\"jit_compile_ms\":" << jit_cache.compile_ms() << ",\"jit_disk_hits\":" << jit_cache.disk_hits()
            << ",\"pull_rows\":" << p.pull_rows.size()
@@ -1447,6 +1592,7 @@ struct Knob {
     int64_t word_value;
     int64_t (*env)(const char *e);
     void (*apply)(fr_renderer &r, int64_t v, bool given);
+    bool listed = true;   // in fr_options_json
 };
 
 int64_t env_on(const char *e) { return e[0] != '0'; }
@@ -1502,6 +1648,11 @@ const Knob kKnobs[] = {
      [](fr_renderer &r, int64_t v, bool) { r.lower_threads = (unsigned)v; }},
     {"FR_LOWER_PAR_MIN_NODES", 200000, 0, 1ll << 40, 0, nullptr, 0, env_long, [](fr_renderer &r, int64_t v, bool) { r.lower_min_nodes = (size_t)v; }},
     {"FR_LOWER_PAR_MIN_EDIT", 16384, 0, 1ll << 40, 0, nullptr, 0, env_long, [](fr_renderer &r, int64_t v, bool) { r.lower_min_edit = (size_t)v; }},
+    // Rendering modes rather than tuning: fr_plan_json reports them (delay_observed, delay_observed_max), fr_options_json lists
+    // the tuning switches only
+    {"FR_DELAY_OBSERVED", 0, 0, 1, 0, nullptr, 0, env_on, [](fr_renderer &r, int64_t v, bool) { r.delay_observed = v != 0; }, false},
+    {"FR_DELAY_OBSERVED_MAX", 1 << 20, 1024, 1 << 28, 0, nullptr, 0, [](const char *e) { return env_clamp(e, 1024, 1 << 28); },
+     [](fr_renderer &r, int64_t v, bool) { r.delay_observed_max = (uint64_t)v; }, false},
 };
 static_assert(sizeof kKnobs / sizeof kKnobs[0] == N_OPTIONS, "N_OPTIONS counts the rows of kKnobs");
 
@@ -2100,6 +2251,7 @@ const char *fr_plan_json(fr_renderer *r) {
     r->plan_json_cache = r->plan.valid ? r->plan.json : "{}";
     if (r->plan.valid && r->plan_json_cache.size() > 1) {   // live: counters of the exchange step (partial-block sharding), the last call's bank launches
         r->plan_json_cache.pop_back();
+        r->plan_json_cache += ",\"lookback_growths\":" + std::to_string(r->lookback_growths) + ",\"range_launches\":" + std::to_string(r->range_launches);
         r->plan_json_cache += ",\"exchange_stats\":{\"calls\":" + std::to_string(r->exchange_calls) + ",\"tiles\":" + std::to_string(r->exchange_tiles) +
                               ",\"bytes_sent\":" + std::to_string(r->exchange_bytes) + "},\"bank_launches\":[";
         for (size_t i = 0; i < r->bank_launches.size(); ++i) {
@@ -2120,7 +2272,8 @@ const char *fr_options_json(fr_renderer *r) {
     std::string &js = r->options_json_cache;
     js = "{";
     for (size_t i = 0; i < N_OPTIONS; ++i)
-        js += std::string(i ? "," : "") + "\"" + kKnobs[i].name + "\":{\"value\":\"" + option_text(kKnobs[i], r->option_value[i]) +
+        if (kKnobs[i].listed)
+            js += std::string(js.size() > 1 ? "," : "") + "\"" + kKnobs[i].name + "\":{\"value\":\"" + option_text(kKnobs[i], r->option_value[i]) +
               "\",\"source\":\"" + kSource[r->option_source[i]] + "\"}";
     js += "}";
     return js.c_str();

@@ -1633,4 +1633,49 @@ hipError_t launch_pad(float *dst, uint64_t n, const float *src_last, hipStream_t
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------------------------
+// Observed input ranges (kernels.hpp RangeArgs): per thread over a strided part of the row, then across the wave64 with
+// lane shuffles, then across the block's four waves through LDS.  One partial result per block: no atomics on the mapped
+// result.
+__global__ __launch_bounds__(RANGE_THREADS) void input_range_kernel(RangeArgs a) {
+    const uint32_t r = blockIdx.y;
+    const float *p = a.row[r];
+    const uint64_t n = a.len[r];
+    float lo = __builtin_huge_valf(), hi = -__builtin_huge_valf();
+    uint32_t fl = 0;
+    const uint64_t step = (uint64_t)a.blocks * RANGE_THREADS;
+    for (uint64_t i = (uint64_t)blockIdx.x * RANGE_THREADS + threadIdx.x; i < n; i += step) {
+        const float v = p[i];
+        if (v != v) fl |= RANGE_NAN;
+        else if (v == __builtin_huge_valf()) fl |= RANGE_POS_INF;
+        else if (v == -__builtin_huge_valf()) fl |= RANGE_NEG_INF;
+        else { lo = fminf(lo, v); hi = fmaxf(hi, v); }
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        lo = fminf(lo, __shfl_xor(lo, o, 64));
+        hi = fmaxf(hi, __shfl_xor(hi, o, 64));
+        fl |= __shfl_xor(fl, o, 64);
+    }
+    __shared__ float s_lo[RANGE_THREADS / 64], s_hi[RANGE_THREADS / 64];
+    __shared__ uint32_t s_fl[RANGE_THREADS / 64];
+    const uint32_t wave = threadIdx.x / 64;
+    if ((threadIdx.x & 63u) == 0) { s_lo[wave] = lo; s_hi[wave] = hi; s_fl[wave] = fl; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (uint32_t w = 1; w < RANGE_THREADS / 64; ++w) { lo = fminf(lo, s_lo[w]); hi = fmaxf(hi, s_hi[w]); fl |= s_fl[w]; }
+        RangePart &o = a.out[(size_t)r * a.blocks + blockIdx.x];
+        o.lo = lo;
+        o.hi = hi;
+        o.flags = fl;
+        o.pad = 0;
+    }
+}
+
+hipError_t launch_input_range(const RangeArgs &a, hipStream_t s) {
+    if (a.n_rows == 0) return hipSuccess;
+    if (a.n_rows > RANGE_MAX_ROWS || a.blocks == 0 || a.blocks > RANGE_MAX_BLOCKS) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(input_range_kernel, dim3(a.blocks, a.n_rows), dim3(RANGE_THREADS), 0, s, a);
+    return hipGetLastError();
+}
+
 }  // namespace fr

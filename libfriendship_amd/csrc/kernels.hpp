@@ -243,4 +243,21 @@ hipError_t launch_chunk_combine(const ChunkCombineArgs &a, hipStream_t s);
 // row (reference.rs:72-73) for the device-resident entry point.
 hipError_t launch_pad(float *dst, uint64_t n, const float *src_last, hipStream_t s);
 
+// Value range of input rows (FR_DELAY_OBSERVED, stage.hpp ObservedInputs): block (b, r) reduces the elements
+// b*256 + tid, stepping by blocks*256, of row r into out[r * blocks + b] -- min and max of the finite values, and flags for
+// NaN, +inf and -inf.  The host merges a row's `blocks` partial results; `out` is mapped pinned memory.
+constexpr uint32_t RANGE_NAN = 1u, RANGE_POS_INF = 2u, RANGE_NEG_INF = 4u;
+constexpr uint32_t RANGE_MAX_ROWS = 32, RANGE_MAX_BLOCKS = 64, RANGE_THREADS = 256;
+struct RangePart {
+    float lo, hi;        // +inf / -inf: no finite value
+    uint32_t flags, pad;
+};
+struct RangeArgs {
+    const float *row[RANGE_MAX_ROWS];
+    uint64_t len[RANGE_MAX_ROWS];
+    uint32_t n_rows, blocks;
+    RangePart *out;
+};
+hipError_t launch_input_range(const RangeArgs &a, hipStream_t s);
+
 }  // namespace fr

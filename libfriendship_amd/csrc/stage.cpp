@@ -66,11 +66,17 @@ struct Planner {
     // frame offset per sample.  Bounds come from interval arithmetic over the amount's expression (doubles, widened
     // outward after every step so that f32 rounding cannot escape them).  `nan` = the value may also be NaN (which
     // as a delay amount means 0 frames, reference.rs:206-211).  Infinite bounds make everything downstream unbounded.
+    // With `observed` (FR_DELAY_OBSERVED), an amount left without a bound is bounded again from the inputs' observed
+    // ranges (stage.hpp ObservedInputs); such a Delay plans a power-of-two look-back and is listed in `observed_dyn`.
     using Range = fr::Range;
-    std::unordered_map<uint32_t, Range> range_memo;
+    std::unordered_map<uint32_t, Range> range_memo, obs_memo;
     std::unordered_map<uint32_t, uint64_t> dyn_max;   // Delay node with a signal amount -> bound on the delay in frames
+    const ObservedInputs *observed = nullptr;
+    std::unordered_set<uint32_t> observed_dyn;        // Delay nodes whose dyn_max came from observed ranges
+    std::unordered_set<uint32_t> observed_refused;    // signal Delays still without a bound in observed mode
 
-    Range range(uint32_t root) {
+    Range range(uint32_t root, bool use_observed = false) {
+        std::unordered_map<uint32_t, Range> &range_memo = use_observed ? obs_memo : this->range_memo;
         std::vector<uint32_t> st{root};
         while (!st.empty()) {
             uint32_t n = st.back();
@@ -82,6 +88,7 @@ struct Planner {
                 st.pop_back();
                 continue;
             }
+            if (x.op == OP_INPUT && use_observed) { range_memo[n] = observed->range(x.a); st.pop_back(); continue; }
             if (x.op == OP_INPUT || x.op == OP_FBREF) { range_memo[n] = Range::unbounded(); st.pop_back(); continue; }   // (feedback: no bound known)
             bool need_a = !range_memo.count(x.a);
             bool need_b = x.op != OP_DELAY && !range_memo.count(x.b);
@@ -106,9 +113,26 @@ struct Planner {
             return true;
         }
         Range r = range(g.nodes[n].b);
-        if (!(r.hi < 2147483648.0)) return false;   // unbounded (or NaN bound)
+        if (!(r.hi < 2147483648.0)) {   // unbounded (or NaN bound)
+            if (!observed) return false;
+            const uint64_t planned = observed_lookback(range(g.nodes[n].b, true), observed->max_lookback);
+            if (!planned) { observed_refused.insert(n); return false; }
+            dyn_max[n] = planned;
+            observed_dyn.insert(n);
+            return true;
+        }
         dyn_max[n] = r.hi <= 0.0 ? 0 : (uint64_t)r.hi;
         return true;
+    }
+    // The look-back planned for an amount of observed range r: its bound rounded up to a power of two (so that a bound that
+    // keeps growing re-plans O(log) times), at most `max`; 0 when there is no bound or it exceeds `max`.
+    static uint64_t observed_lookback(const Range &r, uint64_t max) {
+        if (!(r.hi < 2147483648.0)) return 0;
+        const uint64_t bound = r.hi <= 0.0 ? 0 : (uint64_t)r.hi;
+        if (bound > max) return 0;
+        uint64_t l = 1;
+        while (l < bound) l <<= 1;
+        return std::min(l, max);
     }
 
     // iterative post-order "is everything under n stageable"
@@ -410,10 +434,38 @@ void check_tracks(const FlatGraph &g, const StagedPlan &sp, uint32_t track_from)
     }
 }
 
+// The observed Delays the plan stages (those the staged rows reach), the input slots their amounts read, and the signal
+// Delays the observed mode left unstaged (they stay with the pull interpreter).
+void note_observed(const FlatGraph &g, const Planner &P, StagedPlan &sp) {
+    std::vector<uint32_t> nodes(P.observed_dyn.begin(), P.observed_dyn.end());
+    std::sort(nodes.begin(), nodes.end());
+    std::unordered_set<uint32_t> slots, seen;
+    for (uint32_t n : nodes) {
+        if (!P.visited.count(n)) continue;   // (its row went to the pull interpreter after all)
+        const uint32_t amount = g.nodes[n].b;
+        sp.observed.push_back({amount, P.dyn_max.at(n)});
+        sp.observed_lookback = std::max(sp.observed_lookback, P.dyn_max.at(n));
+        std::vector<uint32_t> st{amount};   // the inputs Planner::range reads for the amount (a Delay's range is its source's)
+        while (!st.empty()) {
+            const uint32_t m = st.back();
+            st.pop_back();
+            if (!seen.insert(m).second) continue;
+            const FlatNode &x = g.nodes[m];
+            if (x.op == OP_INPUT) slots.insert(x.a);
+            if (x.op == OP_CONST || x.op == OP_INPUT || x.op == OP_FBREF) continue;
+            st.push_back(x.a);
+            if (x.op != OP_DELAY) st.push_back(x.b);
+        }
+    }
+    sp.observed_slots.assign(slots.begin(), slots.end());
+    std::sort(sp.observed_slots.begin(), sp.observed_slots.end());
+    sp.observed_refused = (uint32_t)P.observed_refused.size();
+}
+
 }  // namespace
 
 StagedPlan plan_stages(const FlatGraph &g, bool allow_banks, bool allow_programs, uint32_t max_log2_p, bool allow_jit, bool allow_template,
-                       BankMatcher *reuse, const ShardSpec *shard, uint32_t track_from) {
+                       BankMatcher *reuse, const ShardSpec *shard, uint32_t track_from, const ObservedInputs *observed) {
     StagedPlan sp;
     PlanTrace plan_trace;
     const uint32_t n_rows = (uint32_t)g.outputs.size();
@@ -435,6 +487,8 @@ StagedPlan plan_stages(const FlatGraph &g, bool allow_banks, bool allow_programs
     }
     struct Retain { BankMatcher *m; ~Retain() { if (m) m->retain_used(); } } retain{reuse ? matcher : nullptr};
     Planner P(g, matcher);
+    // (feedback plans replay from frame 0 and keep the rule of proven bounds: the observed mode leaves them as they are)
+    if (observed && observed->range && g.fb_target.empty()) P.observed = observed;
 
     FR_PT("A_rows");
     std::vector<uint32_t> staged_rows;
@@ -1011,8 +1065,19 @@ StagedPlan plan_stages(const FlatGraph &g, bool allow_banks, bool allow_programs
     }
     FR_PT("H_end");
     std::sort(sp.pull_rows.begin(), sp.pull_rows.end());
+    if (P.observed) note_observed(g, P, sp);
     check_tracks(g, sp, track_from);
     return sp;
+}
+
+bool observed_plan_holds(const FlatGraph &g, const StagedPlan &sp, const ObservedInputs &obs) {
+    Planner P(g, nullptr);
+    P.observed = &obs;
+    for (const StagedPlan::ObservedDelay &od : sp.observed) {
+        const uint64_t l = Planner::observed_lookback(P.range(od.amount, true), obs.max_lookback);
+        if (!l || l > od.planned) return false;
+    }
+    return true;
 }
 
 }  // namespace fr

@@ -3,12 +3,14 @@
 
 #include <algorithm>
 #include <cstdint>
+#include <functional>
 #include <memory>
 #include <vector>
 
 #include "graph.hpp"
 #include "kernels.hpp"
 #include "match.hpp"
+#include "range.hpp"
 
 namespace fr {
 
@@ -94,7 +96,24 @@ struct StagedPlan {
     bool input_lookback_unbounded = false;
     std::vector<uint32_t> input_slots;     // dense input index used by programs -> external slot
     std::vector<uint32_t> pull_rows;       // output rows left to the pull interpreter
+    // Observed-amount mode (ObservedInputs): the staged Delays whose bound came from the inputs' observed ranges, with the
+    // look-back planned for each (a power of two at least that bound); the input slots those amounts read; signal Delays the
+    // mode had to leave unstaged (an input range holding an infinity, a divisor range holding 0, a bound over the maximum).
+    struct ObservedDelay { uint32_t amount; uint64_t planned; };
+    std::vector<ObservedDelay> observed;
+    std::vector<uint32_t> observed_slots;
+    uint64_t observed_lookback = 0;
+    uint32_t observed_refused = 0;
     bool uses_rings() const { return n_rings != 0; }
+};
+
+// FR_DELAY_OBSERVED: a signal Delay amount with no proven bound is bounded from the values its inputs have actually held
+// since the last seek.  `range(slot)` is that slot's hull (always holding 0.0: unfed slots, zero prefixes and frames beyond
+// what was stored read 0.0); a staged Delay plans a look-back of the bound rounded up to a power of two, at most
+// `max_lookback` frames.  The engine re-plans when new rows widen a hull past a planned look-back (observed_plan_holds).
+struct ObservedInputs {
+    std::function<Range(uint32_t slot)> range;
+    uint64_t max_lookback = 1u << 20;
 };
 
 // allow_banks: recognise fused oscillator banks; allow_programs: stage everything else that qualifies.
@@ -104,6 +123,11 @@ class BankMatcher;
 // `track_from`: input slots >= it are control-rate tracks (fr_set_track_inputs): visible only to the call that supplies them,
 // readable only by the leaves of shape-matched voices (anything else that reads one makes the plan FR_ERR_UNSUPPORTED).
 StagedPlan plan_stages(const FlatGraph &g, bool allow_banks, bool allow_programs, uint32_t max_log2_p, bool allow_jit = false,
-                       bool allow_template = true, BankMatcher *reuse = nullptr, const ShardSpec *shard = nullptr, uint32_t track_from = 0xFFFFFFFFu);
+                       bool allow_template = true, BankMatcher *reuse = nullptr, const ShardSpec *shard = nullptr, uint32_t track_from = 0xFFFFFFFFu,
+                       const ObservedInputs *observed = nullptr);
+
+// Do the observed Delays of `sp` (planned from `g` with observed ranges) still fit their planned look-backs under the ranges
+// `obs` gives now?  False: some bound grew past its plan, or has none any more.
+bool observed_plan_holds(const FlatGraph &g, const StagedPlan &sp, const ObservedInputs &obs);
 
 }  // namespace fr
