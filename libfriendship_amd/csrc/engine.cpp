@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "../../include/friendship_render_ext.h"
+#include "bankplan.hpp"
 #include "comm.hpp"
 #include "graph.hpp"
 #include "jit.hpp"
@@ -131,8 +132,8 @@ struct Plan {
 
 // One bank launch of the last call, as fr_plan_json's "bank_launches" shows it.
 struct BankLaunchNote {
-    const char *kernel;
-    uint32_t voices, partials, chunk_log2, waves_per_group, frames_per_lane, voices_per_wave;   // (chunk_log2 0: whole voices, gbank)
+    BankPlan launch;
+    uint32_t voices, partials;
     uint64_t frames;
 };
 
@@ -197,9 +198,7 @@ struct fr_renderer {
     // shape-matched voices rendered in pieces (few voices x short call): the pieces' sums and the identity row list
     DevBuf d_chunk_ws, d_chunk_rows;
     uint32_t d_chunk_rows_n = 0;
-    bool jit_chunks = true;                 // FR_JIT_CHUNKS=0: one workgroup per (voice, tile) always (A/B)
     uint32_t stage_block_env = 0;           // FR_STAGE_BLOCK: iterations per block of compiled strided programs (A/B; 0 = the rule in build_plan)
-    uint64_t jit_chunk_target = 0;          // FR_JIT_CHUNK_TARGET: workgroups below which a voice is cut further (0: 1024, tracks 16384)
     // FR_HOST_MAPPED (A/B): bit 0 = kernels write the output through the mapping, bit 1 = the bank kernel reads the
     // input row through the mapping; 0 = the staged copies of round 1 (H2D row, D2H of the whole buffer)
     bool host_out_mapped = false, host_rows_mapped = true;
@@ -214,21 +213,13 @@ struct fr_renderer {
     uint32_t host_seq = 0;
     std::vector<uint32_t> stream_pending;
     struct FlagOut { uint32_t *host_flags = nullptr; uint32_t *row_done = nullptr; uint32_t value = 0; } flag_out;
-    // every output row is a voice of a bank launch that can publish its completion (kernels.hpp bank_publishes_rows)?
+    // every output row is a voice of a bank launch that can publish its completion (bankplan.hpp BankPlan::publishes_rows)?
     bool can_stream_rows(uint32_t n_slots, uint64_t n_times) const {
-        if (!host_stream || sharded() || !plan_current(n_slots) || plan.banks.empty() || bank_leaf_variant != 1) return false;
+        if (!host_stream || sharded() || !plan_current(n_slots) || plan.banks.empty()) return false;
         if (!plan.sp.progs.empty() || plan.sp.uses_rings() || !plan.pull_rows.empty() || !plan.sp.split.empty()) return false;
         size_t voices = 0;
         for (const BankStage &bs : plan.banks) {
-            if (bs.grp.jit || bs.grp.general || bs.grp.to_ring || bs.grp.to_ws) return false;
-            BankArgs a{};
-            a.log2_p = bs.grp.log2_p;
-            a.n_voices = (uint32_t)bs.grp.rows.size();
-            shape_bank(a.log2_p, a.n_voices, n_times, a.chunk_log2, a.frames_per_lane, a.waves_per_group, a.small_call, a.voices_per_wave);
-            if (a.voices_per_wave && !allow_multi) { a.voices_per_wave = 0; a.frames_per_lane = 1; }
-            a.leaf_variant = 1;
-            a.host_flags = (uint32_t *)1;   // (asking "would it")
-            if (!bank_publishes_rows(a)) return false;
+            if (!plan_bank_launch(bs, n_times, true).publishes_rows) return false;
             voices += bs.grp.rows.size();
         }
         return voices == n_slots;   // (each row is written by exactly one voice: a row fed by nothing would be a program)
@@ -400,22 +391,19 @@ struct fr_renderer {
     int64_t option_value[N_OPTIONS];
     uint8_t option_source[N_OPTIONS];
     std::string options_json_cache;
-    uint32_t bank_leaf_variant = 1;      // FR_BANK_LEAF=0: product-form leaves (kernels.hpp BankArgs::leaf_variant)
-    BankTuning bank_tune;                // FR_BANK_SHORT, FR_SHORT_*, FR_BANK_F, FR_BANK_NW: what bank_shape sees for this renderer
-    void shape_bank(uint32_t log2_p, uint32_t n_voices, uint64_t n_times, uint32_t &chunk_log2, uint32_t &frames_per_lane,
-                    uint32_t &waves_per_group, uint32_t &small_call, uint32_t &voices_per_wave, bool many_pairs_whole = false) const {
-        const BankTuning *outer = bank_tuning;
-        bank_tuning = &bank_tune;
-        bank_shape(log2_p, n_voices, n_times, chunk_log2, frames_per_lane, waves_per_group, small_call, voices_per_wave, many_pairs_whole);
-        bank_tuning = outer;
+    BankTuning bank_tune;                // FR_BANK_*, FR_SHORT_*, FR_JIT_CHUNKS, FR_JIT_CHUNK_TARGET: this renderer's bank launch rule
+    // A bank group's launch over `n_times` frames in this call (bankplan.hpp): the launch itself, the input store's row
+    // deferral and the streamed host output all ask this, so they agree by construction.
+    BankPlan plan_bank_launch(const BankStage &bs, uint64_t n_times, bool row_flags) const {
+        return plan_bank(bs.grp, BankCall{n_times, host_pipelines, row_flags, bs.jit && bs.jit->fn_multi}, bank_tune);
     }
     bool jit_fma = true;                 // FR_JIT_FMA=0: generated leaves without the fused multiply-add fold (jit.hpp)
     unsigned lower_threads = 1;          // FR_LOWER_THREADS, FR_LOWER_PAR_MIN_NODES, FR_LOWER_PAR_MIN_EDIT (Lowering::set_parallel)
     size_t lower_min_nodes = 0, lower_min_edit = 0;
     std::vector<BankLaunchNote> bank_launches;   // the last call's (fr_plan_json), at most 256
-    void note_bank_launch(const char *kernel, uint32_t voices, uint32_t partials, uint32_t chunk_log2, uint32_t waves_per_group,
-                          uint32_t frames_per_lane, uint32_t voices_per_wave, uint64_t frames) {
-        if (bank_launches.size() < 256) bank_launches.push_back({kernel, voices, partials, chunk_log2, waves_per_group, frames_per_lane, voices_per_wave, frames});
+    void note_bank_launch(const BankPlan &bp, const BankStage &bs, uint64_t frames) {
+        const uint32_t partials = bs.grp.general ? bs.grp.max_leaves : 1u << bs.grp.log2_p;
+        if (bank_launches.size() < 256) bank_launches.push_back({bp, (uint32_t)bs.grp.rows.size(), partials, frames});
     }
     // Block streaming (fr_stream_*): one resident launch renders 64-frame blocks on a doorbell (kernels.hpp BankStreamCtl)
     bool streaming = false;
@@ -453,7 +441,6 @@ struct fr_renderer {
     }
     bool allow_jit = true;               // FR_JIT=0: no hipRTC specialisation (those voices run as programs / pull)
     bool allow_template = true;          // FR_BANK_TEMPLATE=0: template voices go through the JIT path literally
-    bool allow_multi = true;             // FR_BANK_MULTI=0: never the whole-voices-per-wave kernel for small voices
     bool fused_strided_ok = true;        // FR_STAGE_STRIDED=0: a long steady call of the fused form as one launch per sub-window (A/B)
     int stage_jit_mode = 1;              // FR_STAGE_JIT=0: programs always interpreted; 1: compiled when >= 4 programs share
                                          // a skeleton on average; 2 ("force"): compiled whenever they fit one kernel
@@ -722,24 +709,16 @@ struct fr_renderer {
     }
     bool bank_time_slot(uint32_t n_slots, uint64_t n_times, uint32_t slot, uint64_t idx) const {
         if (!plan_current(n_slots)) return false;
-        // (bank_small_kernel, used for the shortest calls of shapes the short-call kernel does not take, does not append)
-        for (const BankStage &bs : plan.banks) {
-            if (bs.grp.jit || bs.grp.general || bs.grp.input_slot != slot) continue;
-            uint32_t c, f, w, small, vpw;
-            shape_bank(bs.grp.log2_p, (uint32_t)bs.grp.rows.size(), n_times, c, f, w, small, vpw);
-            if (small == 1) return false;
-        }
         // a window with look-back reads the stored history, so the row must be there first; in steady state the bank
         // launch (always ahead of the programs on the stream) reads the caller's row and appends it like any other
         if ((plan.sp.uses_rings() || !plan.sp.progs.empty()) && !steady_call(idx, n_times)) return false;
         bool any = false;
         for (const BankStage &bs : plan.banks) {
-            if (bs.grp.jit) {
-                for (uint32_t sl : bs.grp.shape.input_slots) if (sl == slot) return false;
-                continue;
-            }
-            if (bs.grp.input_slot != slot) continue;
-            if (bs.grp.general || bs.grp.jit) return false;   // only the balanced hand-written kernel appends history
+            const std::vector<uint32_t> &in = bs.grp.shape.input_slots;
+            if (bs.grp.jit ? std::find(in.begin(), in.end(), slot) == in.end() : bs.grp.input_slot != slot) continue;
+            // only a launch that appends history may take the row: not the compiled or schedule kernels, nor bank_small_kernel
+            // (row flags do not change that answer)
+            if (!plan_bank_launch(bs, n_times, false).appends_rows) return false;
             any = true;
         }
         return any;
@@ -914,6 +893,17 @@ struct fr_renderer {
             }
         }
         return d;
+    }
+    // A slot's stored history over the window [b0, b0 + len) (BankArgs::time, JitBankArgs::in): `data` holds window frame
+    // `skip` onwards, `valid` frames of it; zero before the stored history (seek) and beyond it.  Untouched without history.
+    template <class U>
+    void input_window(uint32_t slot, uint64_t b0, uint64_t len, const float *&data, U &skip, U &valid) const {
+        const DevInput d = dev_input(slot);
+        if (!d.data || d.len <= d.base) return;
+        const uint64_t start = std::max(b0, d.base);
+        skip = std::min(start - b0, len);
+        data = d.data + (start - d.base);
+        valid = d.len > start ? d.len - start : 0;
     }
 
     // ---- planning ---------------------------------------------------------------------------------
@@ -1158,16 +1148,10 @@ struct fr_renderer {
         // written to the tile-major workspace; such a launch appends ITS part of a deferred input row.
         auto launch_bank_window = [&](BankStage &bs, uint64_t b0, uint64_t blen, int64_t tile_off) {
             const bool ring = bs.grp.to_ring, ws = bs.grp.to_ws;
+            const BankPlan bp = plan_bank_launch(bs, blen, flag_out.host_flags != nullptr);
             BankArgs a{};
             a.params = bs.d_params.as<float2>();
-            // time-slot history for window [b0, b0 + blen): zero before the stored history (seek), zero beyond it
-            DevInput di = dev_input(bs.grp.input_slot);
-            if (di.data && di.len > di.base) {
-                uint64_t start = std::max(b0, di.base);
-                a.time_skip = std::min(start - b0, blen);
-                a.time = di.data + (start - di.base);
-                a.time_valid = di.len > start ? di.len - start : 0;
-            }
+            input_window(bs.grp.input_slot, b0, blen, a.time, a.time_skip, a.time_valid);   // time-slot history for the window
             if (tile_off < 0 && b0 == idx && blen == n_times)   // (direct output, or a ring in steady state)
                 for (Deferred &d : deferred)
                     if (d.slot == bs.grp.input_slot) {   // read the caller's row; the first bank on this slot appends it
@@ -1207,50 +1191,25 @@ struct fr_renderer {
             if (bs.grp.jit) {
                 JitBankArgs j{};
                 j.params = bs.d_params.as<float>();
-                for (size_t i = 0; i < bs.grp.shape.input_slots.size(); ++i) {   // every input row over the same window
-                    DevInput dj = dev_input(bs.grp.shape.input_slots[i]);
-                    if (dj.data && dj.len > dj.base) {
-                        uint64_t start = std::max(b0, dj.base);
-                        j.in_skip[i] = std::min(start - b0, blen);
-                        j.in[i] = dj.data + (start - dj.base);
-                        j.in_valid[i] = dj.len > start ? dj.len - start : 0;
-                    }
-                }
+                for (size_t i = 0; i < bs.grp.shape.input_slots.size(); ++i)   // every input row over the same window
+                    input_window(bs.grp.shape.input_slots[i], b0, blen, j.in[i], j.in_skip[i], j.in_valid[i]);
                 j.out = a.out;
                 j.rows = a.rows;
                 j.out_stride = a.out_stride;
                 j.ring_mask = a.ring_mask;
                 j.ring_t0 = a.ring_t0;
                 j.n_times = blen;
-                j.n_voices = a.n_voices;
-                j.log2_p = a.log2_p;
+                j.n_voices = a.n_voices << bp.pieces_log2;
+                j.log2_p = bp.chunk_log2;
                 j.tiles = (uint32_t)((blen + 63) / 64);
-                j.nblocks = j.tiles * j.n_voices;
-                if (allow_multi && a.log2_p <= 8 && bs.jit->fn_multi) {   // many small voices: whole voices per wave
-                    uint32_t vpw = std::max(2u, 256u >> a.log2_p);
-                    auto nb = [&](uint32_t per_wave) { return ((a.n_voices + 4ull * per_wave - 1) / (4ull * per_wave)) * j.tiles; };
-                    while (vpw > 1 && nb(vpw) < 2048) vpw >>= 1;
-                    if (nb(vpw) >= 1024) { j.voices_per_wave = vpw; j.nblocks = (uint32_t)nb(vpw); }
-                }
+                j.nblocks = (uint32_t)bp.jit_blocks;
+                j.voices_per_wave = bp.voices_per_wave;
                 j.fract_ok = bs.grp.fast_ok ? 1u : 0u;
-                // Few voices, short call: one workgroup per (voice, 64-frame tile) leaves most of the chip idle (64 voices x 64
-                // frames = 64 workgroups).  Render every voice as 2^c consecutive pieces of its leaves instead -- to the kernel
-                // 2^c times as many voices of 2^-c the size, rows of a workspace -- and add the pieces up in the tree's order.
-                uint32_t pieces_log2 = 0;
-                if (jit_chunks && !ring && !ws && !j.voices_per_wave && a.n_voices <= 1024u) {
-                    // (voices that stream tracks from HBM want many small workgroups -- 64 x 4096 x 1024 frames: 0.84 of the achievable
-                    //  bandwidth with 1024 workgroups, 0.93 with 16 384; profiles/r03_tracks.txt -- the arithmetic-bound ones only a full chip)
-                    const uint64_t target = jit_chunk_target ? jit_chunk_target : (bs.grp.tracks ? 16384u : 1024u);
-                    while (pieces_log2 < 6 && a.log2_p - pieces_log2 > 5 && ((uint64_t)j.nblocks << pieces_log2) < target) ++pieces_log2;
-                    // (T = 64: pieces of 256 partials beat 128 and 64 -- 34.5 / 37.3 / 35.3 us at 64 x 4096)
-                    if (bs.grp.tracks && a.n_times <= 128 && a.log2_p >= 8 && a.log2_p - pieces_log2 < 8) pieces_log2 = a.log2_p - 8;
-                }
-                if (pieces_log2) {
+                if (bp.pieces_log2) {   // every voice as pieces, to the kernel rows of a workspace, added up below in the tree's order
                     used_scratch = true;   // (the pieces' workspace is shared between calls: no overlap with the next one on another stream)
-                    const uint32_t pv = a.n_voices << pieces_log2;
-                    d_chunk_ws.ensure((size_t)pv * blen * sizeof(float));
-                    if (d_chunk_rows_n < pv) {
-                        std::vector<uint32_t> seq(std::max<uint32_t>(pv, 4096));
+                    d_chunk_ws.ensure(bp.ws_floats * sizeof(float));
+                    if (d_chunk_rows_n < j.n_voices) {
+                        std::vector<uint32_t> seq(std::max<uint32_t>(j.n_voices, 4096));
                         for (uint32_t i = 0; i < seq.size(); ++i) seq[i] = i;
                         d_chunk_rows.ensure(seq.size() * sizeof(uint32_t));
                         HIP_CHECK(hipMemcpyAsync(d_chunk_rows.p, seq.data(), seq.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
@@ -1260,9 +1219,6 @@ struct fr_renderer {
                     j.out = d_chunk_ws.as<float>();
                     j.rows = d_chunk_rows.as<uint32_t>();
                     j.out_stride = blen;
-                    j.n_voices = pv;
-                    j.log2_p = a.log2_p - pieces_log2;
-                    j.nblocks = j.tiles * j.n_voices;
                 }
                 if (bs.grp.tracks && call_tracks) {
                     if (b0 != idx || blen != n_times) throw Error(FR_ERR_UNSUPPORTED, "internal: a voice that reads tracks rendered over another window than the call's");
@@ -1270,10 +1226,10 @@ struct fr_renderer {
                     j.track_stride = call_track_stride;
                     j.track_limit = (uint32_t)std::min<uint64_t>((uint64_t)track_from + call_track_rows, 0xFFFFFFFFull);
                 }
-                note_bank_launch("jit_bank", a.n_voices, 1u << a.log2_p, j.log2_p, 4, 1, j.voices_per_wave, blen);
+                note_bank_launch(bp, bs, blen);
                 Scope sc(this, &t_bank, st);
                 HIP_CHECK(launch_jit_bank(*bs.jit, j, st));
-                if (pieces_log2) {
+                if (bp.pieces_log2) {
                     ChunkCombineArgs c{};
                     c.ws = d_chunk_ws.as<float>();
                     c.out = a.out;
@@ -1281,58 +1237,41 @@ struct fr_renderer {
                     c.out_stride = a.out_stride;
                     c.n_times = blen;
                     c.n_voices = a.n_voices;
-                    c.log2_c = pieces_log2;
+                    c.log2_c = bp.pieces_log2;
                     HIP_CHECK(launch_chunk_combine(c, st));
                 }
                 sc.done();
                 return;
             }
+            a.voices_per_wave = bp.voices_per_wave;
             if (bs.grp.general) {
                 a.groups = bs.d_groups.as<uint32_t>();
                 a.group_off = bs.d_group_off.as<uint32_t>();
                 a.hist_dst = nullptr;   // (the schedule kernel does not append history)
-                // many small voices: whole voices per wave (gbank_multi_kernel), like bank_multi_kernel for balanced ones
-                a.voices_per_wave = 0;
-                if (allow_multi && bs.grp.max_leaves <= 512) {
-                    const uint64_t tiles = (blen + 63) / 64;
-                    uint32_t vpw = std::max<uint32_t>(1u, std::min<uint32_t>(8u, 256u / std::max<uint32_t>(bs.grp.max_leaves, 1u)));
-                    auto nb = [&](uint32_t per_wave) { return ((a.n_voices + 4ull * per_wave - 1) / (4ull * per_wave)) * tiles; };
-                    while (vpw > 1 && nb(vpw) < 2048) vpw >>= 1;
-                    if (nb(vpw) >= 1024) a.voices_per_wave = vpw;
-                }
-                note_bank_launch("gbank", a.n_voices, bs.grp.max_leaves, 0, 4, 1, a.voices_per_wave, blen);
+                note_bank_launch(bp, bs, blen);
                 Scope sc(this, &t_bank, st);
                 HIP_CHECK(launch_gbank(a, st));
                 sc.done();
                 return;
             }
-            // (a host that renders ahead on alternating streams gets launches that can overlap: a GPU's share of a voice-sharded
-            //  job, 8 x 4096 x 4800, takes 16.3 us per call that way against 20.9 with chunks + tickets on one stream -- the tail of
-            //  one call's few latency-bound waves fills with the next call's first; profiles/r03_fewvoices.txt)
-            shape_bank(a.log2_p, a.n_voices, blen, a.chunk_log2, a.frames_per_lane, a.waves_per_group, a.small_call, a.voices_per_wave, host_pipelines);
-            if (a.voices_per_wave && !allow_multi) {   // A/B: the quarter-voice-per-wave kernel, one frame per lane
-                a.voices_per_wave = 0;
-                a.frames_per_lane = 1;
-            }
-            if (a.small_call == 1 && a.hist_dst) throw Error(FR_ERR_DEVICE, "internal: deferred history append on a short call");
-            a.leaf_variant = bank_leaf_variant;
-            // small voices, many workgroups: ONE wave per (voice, tile) -- no LDS combine, no barrier (256 x 512 x 4800: 71.6 -> 66.4 us;
-            // at 1024 partials and above 4 waves are as fast or faster: profiles/r03_bank_waves.txt)
-            if (a.log2_p <= 9 && a.log2_p >= 3 && a.chunk_log2 == a.log2_p && !a.small_call && !a.voices_per_wave && a.waves_per_group == 4 &&
-                a.leaf_variant == 1 && !flag_out.host_flags && a.frames_per_lane == 1 && bank_blocks(a) >= 4096)
-                a.waves_per_group = 1;
+            if (a.hist_dst && !bp.appends_rows) throw Error(FR_ERR_DEVICE, "internal: deferred history append on a short call");
+            a.chunk_log2 = bp.chunk_log2;
+            a.frames_per_lane = bp.frames_per_lane;
+            a.waves_per_group = bp.waves_per_group;
+            a.small_call = bp.small_call;
+            a.leaf_variant = bank_tune.leaf_variant;
             if (flag_out.host_flags) {
+                if (!bp.publishes_rows) throw Error(FR_ERR_DEVICE, "internal: a bank launch cannot publish row flags");
                 a.host_flags = flag_out.host_flags;
                 a.row_done = flag_out.row_done;
                 a.flag_value = flag_out.value;
-                if (!bank_publishes_rows(a)) throw Error(FR_ERR_DEVICE, "internal: a bank launch cannot publish row flags");
             }
-            if (a.chunk_log2 != a.log2_p) {
+            if (bp.ws_floats) {
                 used_scratch = true;
-                d_bank_ws.ensure(((size_t)a.n_voices << (a.log2_p - a.chunk_log2)) * blen * sizeof(float));
+                d_bank_ws.ensure(bp.ws_floats * sizeof(float));
                 a.ws = d_bank_ws.as<float>();
-                if (a.small_call == 2) {   // arrival counters of the in-launch combine: zero between launches (the kernel resets them)
-                    const size_t need = (size_t)a.n_voices * ((blen + 63) / 64) * BANK_TICKET_STRIDE * sizeof(uint32_t);
+                if (bp.ticket_words) {   // arrival counters of the in-launch combine: zero between launches (the kernel resets them)
+                    const size_t need = bp.ticket_words * sizeof(uint32_t);
                     clean_counters(st);
                     if (need > d_tickets.bytes) {
                         d_tickets.ensure(need * 2);
@@ -1341,8 +1280,7 @@ struct fr_renderer {
                     a.tickets = d_tickets.as<uint32_t>();
                 }
             }
-            note_bank_launch(a.small_call == 2 ? "bank_short_kernel" : a.small_call ? "bank_small_kernel" : a.voices_per_wave ? "bank_multi_kernel" : "bank_kernel",
-                             a.n_voices, 1u << a.log2_p, a.chunk_log2, a.waves_per_group, a.frames_per_lane, a.voices_per_wave, blen);
+            note_bank_launch(bp, bs, blen);
             Scope sc(this, &t_bank, st);
             HIP_CHECK(launch_bank(a, st));
             sc.done();
@@ -1605,13 +1543,13 @@ const Knob kKnobs[] = {
     {"FR_STAGE_JIT", 1, 0, 1, 0, "force", 2, [](const char *e) -> int64_t { return e[0] == '0' ? 0 : (e[0] == '1' ? 1 : 2); },
      [](fr_renderer &r, int64_t v, bool) { r.stage_jit_mode = (int)v; }},
     {"FR_JIT_FMA", 1, 0, 1, 0, nullptr, 0, env_on, [](fr_renderer &r, int64_t v, bool) { r.jit_fma = v != 0; }},
-    {"FR_JIT_CHUNKS", 1, 0, 1, 0, nullptr, 0, env_on, [](fr_renderer &r, int64_t v, bool) { r.jit_chunks = v != 0; }},
+    {"FR_JIT_CHUNKS", 1, 0, 1, 0, nullptr, 0, env_on, [](fr_renderer &r, int64_t v, bool) { r.bank_tune.jit_chunks = v != 0; }},
     {"FR_JIT_CHUNK_TARGET", 0, 0, 1 << 24, 0, nullptr, 0, [](const char *e) -> int64_t { return std::max(1, std::atoi(e)); },
-     [](fr_renderer &r, int64_t v, bool) { r.jit_chunk_target = (uint64_t)v; }},
+     [](fr_renderer &r, int64_t v, bool) { r.bank_tune.jit_chunk_target = (uint64_t)v; }},
     {"FR_BANK_TEMPLATE", 1, 0, 1, 0, nullptr, 0, env_on, [](fr_renderer &r, int64_t v, bool) { r.allow_template = v != 0; }},
     {"FR_BANK_LEAF", 1, 0, 1, 0, nullptr, 0, [](const char *e) -> int64_t { return e[0] == '1'; },
-     [](fr_renderer &r, int64_t v, bool) { r.bank_leaf_variant = v ? 1u : 0u; }},
-    {"FR_BANK_MULTI", 1, 0, 1, 0, nullptr, 0, env_on, [](fr_renderer &r, int64_t v, bool) { r.allow_multi = v != 0; }},
+     [](fr_renderer &r, int64_t v, bool) { r.bank_tune.leaf_variant = v ? 1u : 0u; }},
+    {"FR_BANK_MULTI", 1, 0, 1, 0, nullptr, 0, env_on, [](fr_renderer &r, int64_t v, bool) { r.bank_tune.multi = v != 0; }},
     {"FR_BANK_SHORT", 1, 0, 1, 0, nullptr, 0, env_on, [](fr_renderer &r, int64_t v, bool) { r.bank_tune.short_kernel = v != 0; }},
     {"FR_SHORT_PAIRS", 1000, 0, 1 << 30, 0, nullptr, 0, env_int, [](fr_renderer &r, int64_t v, bool) { r.bank_tune.short_pairs = (uint64_t)v; }},
     {"FR_SHORT_WGS", 0, 0, 1 << 30, 0, nullptr, 0, env_int, [](fr_renderer &r, int64_t v, bool) { r.bank_tune.short_wgs = (uint64_t)v; }},
@@ -2037,7 +1975,7 @@ fr_status fr_stream_begin(fr_renderer *r, uint32_t n_slots) {
         const BankStage &bs = r->plan.banks[0];
         if (bs.grp.general || bs.grp.jit || bs.grp.to_ring || bs.grp.to_ws || bs.grp.rows.size() != n_slots || !sp.pull_rows.empty())
             throw Error(FR_ERR_UNSUPPORTED, "block streaming needs balanced template voices, one per output row");
-        if (r->bank_leaf_variant != 1) throw Error(FR_ERR_UNSUPPORTED, "block streaming with FR_BANK_LEAF=0");
+        if (r->bank_tune.leaf_variant != 1) throw Error(FR_ERR_UNSUPPORTED, "block streaming with FR_BANK_LEAF=0");
         if (bs.grp.input_slot != 0) throw Error(FR_ERR_UNSUPPORTED, "block streaming feeds input slot 0; these voices read another slot");
         if (bs.grp.log2_p < 7) throw Error(FR_ERR_UNSUPPORTED, "block streaming needs voices of at least 128 partials (16 waves x one group of 8)");
         BankArgs a{};
@@ -2256,10 +2194,10 @@ const char *fr_plan_json(fr_renderer *r) {
                               ",\"bytes_sent\":" + std::to_string(r->exchange_bytes) + "},\"bank_launches\":[";
         for (size_t i = 0; i < r->bank_launches.size(); ++i) {
             const BankLaunchNote &b = r->bank_launches[i];
-            r->plan_json_cache += std::string(i ? "," : "") + "{\"kernel\":\"" + b.kernel + "\",\"voices\":" + std::to_string(b.voices) +
+            r->plan_json_cache += std::string(i ? "," : "") + "{\"kernel\":\"" + b.launch.kernel + "\",\"voices\":" + std::to_string(b.voices) +
                                   ",\"partials\":" + std::to_string(b.partials) + ",\"frames\":" + std::to_string(b.frames) +
-                                  ",\"chunk_log2\":" + std::to_string(b.chunk_log2) + ",\"waves_per_group\":" + std::to_string(b.waves_per_group) +
-                                  ",\"frames_per_lane\":" + std::to_string(b.frames_per_lane) + ",\"voices_per_wave\":" + std::to_string(b.voices_per_wave) + "}";
+                                  ",\"chunk_log2\":" + std::to_string(b.launch.chunk_log2) + ",\"waves_per_group\":" + std::to_string(b.launch.waves_per_group) +
+                                  ",\"frames_per_lane\":" + std::to_string(b.launch.frames_per_lane) + ",\"voices_per_wave\":" + std::to_string(b.launch.voices_per_wave) + "}";
         }
         r->plan_json_cache += "]}";
     }

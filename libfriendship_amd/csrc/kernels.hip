@@ -962,13 +962,6 @@ hipError_t launch_bank_stream(const BankArgs &a, BankStreamCtl *ctl_dev, BankStr
     return hipGetLastError();
 }
 
-// Will launch_bank publish row-completion flags for these arguments (host_flags set)?  Only the time-major kernel with
-// one chunk per voice and the FMA-form leaves does.
-bool bank_publishes_rows(const BankArgs &a) {
-    return a.host_flags && !a.small_call && !a.voices_per_wave && a.leaf_variant == 1 && a.chunk_log2 == a.log2_p &&
-           (a.frames_per_lane == 1 || a.frames_per_lane == 2 || a.frames_per_lane == 4);
-}
-
 // Workgroups launch_bank uses for this shape.
 uint64_t bank_blocks(const BankArgs &a) {
     uint64_t f = a.frames_per_lane;
@@ -1001,101 +994,6 @@ static hipError_t launch_bank_f(const BankArgs &a, hipStream_t s) {
     uint64_t total = (uint64_t)a.n_voices * a.n_times;
     hipLaunchKernelGGL(bank_combine_kernel, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, s, a);
     return hipGetLastError();
-}
-
-// Chooses the launch shape for this call.  Measured on MI355X at 64 voices x 4096 partials
-// (tools/bank_bench.hip, profiles/r01_bank_variants.txt, profiles/r01_bank_small_calls.txt):
-//  * one 64-frame tile per wave (F = 1) is never slower than 2 or 4;
-//  * long calls (>= 512 workgroups): 4 waves x 1024 partials per workgroup; 8 waves measured equal;
-//  * short calls: ONE workgroup of 8 waves per (voice, tile) beats splitting voices into chunks + a combine
-//    pass (T = 32: 13.9 us vs 31 us) and beats the lanes-over-partials kernel from T = 8 up (13.8 vs 17.4 us;
-//    T = 32: 13.9 vs 37 us); lanes-over-partials only ties at T = 1 (11.4 us), so it is used for T <= 2;
-//  * voices larger than one workgroup's capacity (8192 / 16384 partials) are split into chunks.
-//  * the renderer's options (bank_tuning) override parts of the rule for A/B runs: FR_BANK_SHORT=0 against the time-major
-//    kernel, FR_SHORT_PAIRS / FR_SHORT_WGS / FR_SHORT_NW / FR_BANK_F / FR_BANK_NW.
-void bank_shape(uint32_t log2_p, uint32_t n_voices, uint64_t n_times, uint32_t &chunk_log2, uint32_t &frames_per_lane,
-                uint32_t &waves_per_group, uint32_t &small_call, uint32_t &voices_per_wave, bool many_pairs_whole) {
-    static const BankTuning defaults;
-    const BankTuning &tu = bank_tuning ? *bank_tuning : defaults;
-    frames_per_lane = 1;
-    voices_per_wave = 0;
-    small_call = 0;
-    {
-        // short calls: few (voice, tile) pairs.  Chunks of >= 512 partials until there are ~256 workgroups of 16 waves.
-        // Measured at 64 x 4096 (tools/short_call_probe.py, profiles/r02_short_calls.txt), us per call, this kernel vs the
-        // time-major one: T <= 64: 7.4 vs 11.2; 128: 8.3 vs 11.4; 256: 10.6 vs 11.6; 512: 19.5 vs 17.8 -- hence pairs <= 320.
-        // 512 or 1024 workgroups (more, smaller chunks) cost 2-3 us more in ticket traffic; 8 waves +0.3 us, 4 waves +2.4.
-        const uint64_t pairs = ((n_times + 63) / 64) * n_voices;
-        if (tu.short_kernel && pairs <= tu.short_pairs && log2_p >= 9 && log2_p <= 20 && pairs > 0) {
-            // up to 320 pairs: ~256 workgroups of 16 waves; up to 1000 (a GPU's share of a voice-sharded job: 8 voices x 75
-            // tiles): ~1200 workgroups of 8 waves -- 600 one-voice workgroups deal 2 or 3 to a CU (28 % idle), twice as
-            // many half as long deal 4 or 5 (24.2 -> 21.9 us at 8 x 4096 x 4800; profiles/r02_short_calls.txt)
-            const bool few = pairs <= 320;
-            // (only where whole workgroups deal unevenly over the 256 CUs: 512 pairs are 2 per CU, and splitting them costs
-            //  4 us of ticket traffic for nothing -- 17.7 -> 22.0 us at 64 x 4096 x 512)
-            const bool lumpy = ((pairs + 255) / 256) * 256 * 100 >= pairs * 115;
-            const uint64_t target = tu.short_wgs ? tu.short_wgs : (few ? 256ull : 1200ull);
-            uint32_t c = log2_p;
-            uint64_t wgs = pairs;
-            while (c > 9 && (wgs < target || c > 13)) { --c; wgs *= 2; }
-            if (log2_p - c <= 8 && (few || (lumpy && c != log2_p && !many_pairs_whole))) {
-                chunk_log2 = c;
-                waves_per_group = tu.short_nw ? tu.short_nw : (few ? 16u : 8u);
-                while ((1u << c) / waves_per_group < 8u) waves_per_group /= 2;   // a wave needs a whole group of 8
-                small_call = 2;
-                return;
-            }
-        }
-    }
-    if (n_times <= 2 && log2_p >= 8 && n_voices <= 65535u) {   // lanes over partials (only where the short-call kernel does not apply)
-        small_call = 1;
-        chunk_log2 = 8;
-        waves_per_group = 4;
-        return;
-    }
-    if (log2_p <= 8) {
-        // many small voices: whole voices per wave (bank_multi_kernel).  Measured with tools/bank_bench at 4800 frames:
-        // 4096 x 32 partials 2.1 -> 6.7 T partial-frames/s (8 voices in a row, 2 frames per lane), 1024 x 128 5.6 -> 8.2 and
-        // 512 x 256 7.1 -> 8.5 (2 in a row); profiles/r01_small_and_silent_voices.txt.  Needs enough voices to fill the chip.
-        const uint32_t F = (log2_p <= 5 && n_times >= 1024) ? 2u : 1u;
-        const uint64_t tiles = (n_times + 64 * F - 1) / (64 * F);
-        uint32_t vpw = std::max(2u, 256u >> log2_p);
-        auto nblocks = [&](uint32_t per_wave) { return ((n_voices + 4ull * per_wave - 1) / (4ull * per_wave)) * tiles; };
-        while (vpw > 1 && nblocks(vpw) < 2048) vpw >>= 1;
-        if (nblocks(vpw) >= 1024) {
-            voices_per_wave = vpw;
-            frames_per_lane = F;
-            chunk_log2 = log2_p;
-            waves_per_group = 4;
-            return;
-        }
-    }
-    const uint64_t blocks = ((n_times + 63) / 64) * n_voices;
-    // small voices: a wave's share of the partials is a handful of groups, so the fixed cost per workgroup dominates;
-    // 2 or 4 frames per lane amortise it (measured with tools/bank_bench: 32 partials 2.1 -> 3.2 T partial-frames/s,
-    // 128 partials 5.3 -> 6.2, 512 partials 8.5 -> 8.8; at 4096 one frame per lane is best)
-    if (n_times >= 1024 && blocks >= 4096) frames_per_lane = log2_p <= 7 ? 4 : (log2_p <= 9 ? 2 : 1);
-    if (tu.bank_f == 1 || tu.bank_f == 2 || tu.bank_f == 4) frames_per_lane = tu.bank_f;   // A/B switch for measurements
-    if (n_times >= 512 && blocks < 320 && log2_p >= 10) {
-        // a few big voices on a long call: too few workgroups to hide the scalar-load latency of the parameter stream
-        // (one 8-wave workgroup per tile leaves a SIMD with 1-2 waves).  Split the voices into chunks of >= 512 partials,
-        // about 1024 workgroups in all, plus the combine pass (tools/bank_bench: 1 x 16384 at 4800 frames 25.7 -> 21.4 us,
-        // 41 us with one 2^14 chunk; 4 x 4096 20.2 -> 17.8 us; at 512 frames 13.6 -> 11.2 us)
-        uint32_t c = log2_p;
-        uint64_t b2 = blocks;
-        while (c > 9 && b2 < 1024) { --c; b2 *= 2; }
-        chunk_log2 = c;
-        waves_per_group = 4;
-        frames_per_lane = 1;
-        return;
-    }
-    // (64 x 4096 at 512 / 1024 frames, 512 / 1024 workgroups: 8 waves 20.7 / 32.3 us, 4 waves 23.4 / 35.5 us, chunks of 2^11 35 / 47 us)
-    // (32 x 4096 x 4800, 2400 workgroups: 8 waves 65.2 us, 4 waves 66.9; 16 x 4096: 36.0 vs 38.5; 64 x 4096: equal)
-    waves_per_group = (log2_p >= 14 || (blocks < 4096 && log2_p >= 6)) ? 8 : 4;
-    if (tu.bank_nw == 4 && log2_p < 14) waves_per_group = 4;   // A/B
-    if (tu.bank_nw == 8 && log2_p >= 6) waves_per_group = 8;
-    const uint32_t cmax = waves_per_group == 8 ? 14 : 13;
-    chunk_log2 = log2_p < cmax ? log2_p : cmax;
 }
 
 hipError_t launch_bank(const BankArgs &a, hipStream_t s) {

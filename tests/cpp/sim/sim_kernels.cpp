@@ -93,17 +93,6 @@ hipError_t launch_pull(const PullArgs &a, hipStream_t) {
     return hipSuccess;
 }
 
-void bank_shape(uint32_t log2_p, uint32_t, uint64_t, uint32_t &chunk_log2, uint32_t &frames_per_lane, uint32_t &waves_per_group,
-                uint32_t &small_call, uint32_t &voices_per_wave, bool) {
-    chunk_log2 = log2_p;   // (one chunk: the simulator never needs the combine workspace)
-    frames_per_lane = 1;
-    waves_per_group = 4;
-    small_call = 0;
-    voices_per_wave = 0;
-}
-uint64_t bank_blocks(const BankArgs &a) { return ((a.n_times + 63) / 64) * a.n_voices; }
-bool bank_publishes_rows(const BankArgs &a) { return a.host_flags && !a.small_call && !a.voices_per_wave && a.leaf_variant == 1 && a.chunk_log2 == a.log2_p; }
-
 hipError_t launch_bank_stream(const BankArgs &, BankStreamCtl *, BankStreamDev *, uint32_t, hipStream_t) { return hipErrorNotSupported; }   // (no resident launches on the simulator)
 hipError_t launch_bank(const BankArgs &a, hipStream_t) {
     ++fr_sim_launches[C_BANK];

@@ -53,3 +53,21 @@ def test_engine_host_logic_against_oracle(oracle_lib):
     env = dict(os.environ, FRIENDSHIP_ORACLE_LIB=oracle_lib.path)
     p = subprocess.run([PLAN_BIN], env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0 and "16 passed; 0 failed" in p.stdout, p.stdout + p.stderr
+
+
+# ---- the bank launch rule (csrc/bankplan.hpp) over a pinned table of groups, calls and options -----------------------
+BANKPLAN_SRC = os.path.join(ROOT, "tests", "cpp", "bankplan_tests.cpp")
+BANKPLAN_BIN = os.path.join(ROOT, "tests", "cpp", "_build", "bankplan_tests")
+
+
+def test_bank_launch_rule_table():
+    """tests/cpp/bankplan_tests.cpp: plan_bank picks the pinned kernel, shape, workspace and row-flag / history-append
+    answers at every point of the grid (every branch of the rule, each option that overrides it, host_pipelines, the
+    benchmark's shapes); a mismatch is printed."""
+    deps = [BANKPLAN_SRC] + [os.path.join(CSRC, f) for f in ("bankplan.hpp", "stage.hpp", "graph.hpp", "match.hpp", "range.hpp", "kernels.hpp")]
+    if not os.path.exists(BANKPLAN_BIN) or os.path.getmtime(BANKPLAN_BIN) < max(os.path.getmtime(d) for d in deps):
+        os.makedirs(os.path.dirname(BANKPLAN_BIN), exist_ok=True)
+        subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-I/opt/rocm/include", "-D__HIP_PLATFORM_AMD__", "-o", BANKPLAN_BIN,
+                        BANKPLAN_SRC], check=True)
+    p = subprocess.run([BANKPLAN_BIN], capture_output=True, text=True, timeout=60)
+    assert p.returncode == 0 and "211 passed; 0 failed" in p.stdout, p.stdout + p.stderr

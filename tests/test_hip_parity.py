@@ -2057,6 +2057,31 @@ def test_few_voice_calls_pipelined_on_two_streams(hip_lib):
         assert same_bits(outs[1].cpu().numpy(), exp[1])
 
 
+def test_pipelined_two_frame_calls_keep_the_input_row(hip_lib, oracle_lib):
+    """Two-frame device calls of 400 voices x 4096 partials on alternating streams: from the second call on, each launch stays
+    whole (bank_small_kernel, which does not append the caller's input row), so the input store keeps the row itself.  Every
+    call succeeds and holds the oracle's bits (tests/test_sim_engine.py runs the same sequence on the simulator)."""
+    import torch
+    V, P, T, calls = 400, 4096, 2, 4
+    tree = synth.additive_tree(n_voices=V, n_partials=P, seed=1)
+    t = synth.time_ramp(0, calls * T)
+    with Renderer(hip_lib) as hip, Renderer(oracle_lib) as ref:
+        synth.install(hip, tree)
+        synth.install(ref, tree)
+        d_t = torch.from_numpy(t).cuda()
+        streams = [torch.cuda.Stream(), torch.cuda.Stream()]
+        outs = [torch.empty((V, T), dtype=torch.float32, device="cuda") for _ in range(calls)]
+        torch.cuda.synchronize()
+        for k in range(calls):
+            hip.fill_buffer_device(outs[k].data_ptr(), V, T, k * T, d_t[k * T:].data_ptr(), [0, T], streams[k % 2].cuda_stream)
+            kernels = [b["kernel"] for b in hip.plan()["bank_launches"]]
+            assert kernels == ["bank_short_kernel" if k == 0 else "bank_small_kernel"], (k, kernels)
+        torch.cuda.synchronize()
+        for k in range(calls):
+            got, exp = outs[k].cpu().numpy(), ref.fill_buffer(V, k * T, (k + 1) * T, [t[k * T:(k + 1) * T]])
+            assert same_bits(got, exp), f"call {k}: " + first_diff(got, exp)
+
+
 def test_feedback_inside_composite_instances(hip_lib, oracle_lib):
     """A composite effect whose own graph holds the loop (an echo: out = x = in + 0.5 * Delay(x, 2)), instantiated twice in series:
     each instance context gets its own cut (two OP_FBREF leaves), rows on the inner and the outer instance."""

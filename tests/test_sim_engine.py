@@ -402,6 +402,28 @@ def test_bounded_history_with_banks_and_device_rows(sim, oracle_lib):
         assert plan["history_frames"] == 2000 and plan["input_lookback"] == 1500 and len(plan["banks"]) == 1, plan
 
 
+def test_pipelined_two_frame_calls_keep_the_input_row(sim, oracle_lib):
+    """Two-frame device calls of 400 voices x 4096 partials on alternating streams 1, 2, 1, 2 (the simulator's stream handles).
+    From the second call on, each comes on another stream than the still-pending previous one, so its launch stays whole: the
+    lanes-over-partials kernel instead of the short-call kernel, and that kernel does not append the caller's input row to the
+    history.  The input store must ask the same rule with the same call, store the row itself, and every call succeed,
+    bit-exact with the oracle."""
+    V, P, T = 400, 4096, 2
+    tree = synth.additive_tree(n_voices=V, n_partials=P, seed=1)
+    with Renderer(sim) as r, Renderer(oracle_lib) as ref:
+        synth.install(r, tree)
+        synth.install(ref, tree)
+        out_ptr, row_ptr, read, write, _ = _device_buffers(sim, V, T)
+        for k, stream in enumerate([1, 2, 1, 2]):
+            t = synth.time_ramp(k * T, (k + 1) * T)
+            write(t)
+            r.fill_buffer_device(out_ptr, V, T, k * T, row_ptr, [0, T], stream)
+            kernels = [b["kernel"] for b in r.plan()["bank_launches"]]
+            assert kernels == ["bank_short_kernel" if k == 0 else "bank_small_kernel"], (k, kernels)
+            got, exp = read(), ref.fill_buffer(V, k * T, (k + 1) * T, [t])
+            assert same_bits(got, exp), f"call {k}: " + G.first_diff(got, exp)
+
+
 def test_registered_destination_is_written_directly(sim, oracle_lib):
     """fr_host_register: a page-locked destination is filled by the kernels themselves (no D2H copy); same bits, and a
     buffer that merely overlaps a registered range, or an unregistered one, takes the ordinary path."""
