@@ -5,6 +5,7 @@
 
 #include <algorithm>
 #include <cstdint>
+#include <string>
 
 #include "stage.hpp"
 
@@ -192,6 +193,40 @@ inline BankPlan plan_bank(const BankLaunch &g, const BankCall &c, const BankTuni
         if (p.small_call == 2) p.ticket_words = voices * tiles * BANK_TICKET_STRIDE;
     }
     return p;
+}
+
+// The kernel instance a launch of plan `p` runs, as one key (fr_plan_json "bank_launches" "variant"): the template arguments
+// and the passes kernels.hip / jit.cpp pick for it.  `log2_p`: the group's; `leaf_variant`: BankTuning::leaf_variant;
+// `row_flags`: BankCall::row_flags (the engine hands the launch the host's flags exactly then).  Mirrors the dispatch of
+//   kernels.hip:999-1042 launch_bank: bank_short_kernel<NW> (its switch on waves_per_group, tickets when chunked),
+//     bank_small_kernel and its bank_combine_kernel pass unless log2_p == 8, bank_multi_kernel<F, MODE> (MODE = leaf_variant
+//     > 2 ? 1 : leaf_variant);
+//   kernels.hip:972-997 launch_bank_f: bank_kernel<F, MODE, NW, FLAGS> -- FLAGS iff leaf_variant == 1 with host flags and one
+//     chunk; NW 2 only for chunks <= 2^12, 1 only for chunks <= 2^11, else 4; MODE 2 always NW 4 -- and bank_combine_kernel
+//     after a chunked launch;
+//   kernels.hip:1335 launch_gbank: gbank_multi_kernel iff voices_per_wave;
+//   jit.cpp:425 launch_jit_bank: jit_bank_multi iff voices_per_wave (plan_bank sets it only where the module has the entry),
+//     and engine.cpp's launch_chunk_combine after a launch in pieces.
+// tests/cpp/bankplan_sweep.cpp lists every key the rule can produce; tests/bank_variants.py has a GPU case for each.
+inline std::string bank_variant(const BankPlan &p, uint32_t log2_p, uint32_t leaf_variant, bool row_flags) {
+    const std::string k = p.kernel;
+    if (k == "jit_bank") {
+        if (p.voices_per_wave) return "jit_bank_multi";
+        return p.pieces_log2 ? "jit_bank/pieces" + std::to_string(p.pieces_log2) : "jit_bank";
+    }
+    if (k == "gbank") return p.voices_per_wave ? "gbank_multi_kernel" : "gbank_kernel";
+    if (k == "bank_short_kernel")
+        return "bank_short_kernel<NW" + std::to_string(p.waves_per_group) + ">" + (p.chunk_log2 != log2_p ? "+tickets" : "");
+    if (k == "bank_small_kernel") return std::string("bank_small_kernel") + (log2_p != 8 ? "+combine" : "");
+    const std::string F = "F" + std::to_string(p.frames_per_lane);
+    if (k == "bank_multi_kernel") return "bank_multi_kernel<" + F + ",M" + std::to_string(leaf_variant > 2 ? 1u : leaf_variant) + ">";
+    const uint32_t w = p.waves_per_group;
+    const bool flags = leaf_variant == 1 && row_flags && p.chunk_log2 == log2_p;
+    uint32_t nw = 4;
+    if (leaf_variant == 0 || flags) nw = w == 8 ? 8 : 4;
+    else if (leaf_variant == 1) nw = w == 8 ? 8 : (w == 2 && p.chunk_log2 <= 12) ? 2 : (w == 1 && p.chunk_log2 <= 11) ? 1 : 4;
+    const std::string mode = "M" + std::to_string(leaf_variant == 0 ? 0u : leaf_variant == 1 ? 1u : 2u);
+    return "bank_kernel<" + F + "," + mode + ",NW" + std::to_string(nw) + (flags ? ",flags" : "") + ">" + (p.chunk_log2 != log2_p ? "+combine" : "");
 }
 
 }  // namespace fr

@@ -135,6 +135,8 @@ struct BankLaunchNote {
     BankPlan launch;
     uint32_t voices, partials;
     uint64_t frames;
+    uint32_t log2_p, leaf_variant;       // (with row_flags: what bankplan.hpp bank_variant reads besides the plan)
+    bool row_flags;
 };
 
 constexpr size_t N_OPTIONS = 28;         // per-renderer options (friendship_render_ext.h; the table below fr_renderer)
@@ -401,9 +403,10 @@ struct fr_renderer {
     unsigned lower_threads = 1;          // FR_LOWER_THREADS, FR_LOWER_PAR_MIN_NODES, FR_LOWER_PAR_MIN_EDIT (Lowering::set_parallel)
     size_t lower_min_nodes = 0, lower_min_edit = 0;
     std::vector<BankLaunchNote> bank_launches;   // the last call's (fr_plan_json), at most 256
-    void note_bank_launch(const BankPlan &bp, const BankStage &bs, uint64_t frames) {
+    void note_bank_launch(const BankPlan &bp, const BankStage &bs, uint64_t frames, bool row_flags) {
         const uint32_t partials = bs.grp.general ? bs.grp.max_leaves : 1u << bs.grp.log2_p;
-        if (bank_launches.size() < 256) bank_launches.push_back({bp, (uint32_t)bs.grp.rows.size(), partials, frames});
+        if (bank_launches.size() < 256)
+            bank_launches.push_back({bp, (uint32_t)bs.grp.rows.size(), partials, frames, bs.grp.log2_p, bank_tune.leaf_variant, row_flags});
     }
     // Block streaming (fr_stream_*): one resident launch renders 64-frame blocks on a doorbell (kernels.hpp BankStreamCtl)
     bool streaming = false;
@@ -1226,7 +1229,7 @@ struct fr_renderer {
                     j.track_stride = call_track_stride;
                     j.track_limit = (uint32_t)std::min<uint64_t>((uint64_t)track_from + call_track_rows, 0xFFFFFFFFull);
                 }
-                note_bank_launch(bp, bs, blen);
+                note_bank_launch(bp, bs, blen, flag_out.host_flags != nullptr);
                 Scope sc(this, &t_bank, st);
                 HIP_CHECK(launch_jit_bank(*bs.jit, j, st));
                 if (bp.pieces_log2) {
@@ -1248,7 +1251,7 @@ struct fr_renderer {
                 a.groups = bs.d_groups.as<uint32_t>();
                 a.group_off = bs.d_group_off.as<uint32_t>();
                 a.hist_dst = nullptr;   // (the schedule kernel does not append history)
-                note_bank_launch(bp, bs, blen);
+                note_bank_launch(bp, bs, blen, flag_out.host_flags != nullptr);
                 Scope sc(this, &t_bank, st);
                 HIP_CHECK(launch_gbank(a, st));
                 sc.done();
@@ -1280,7 +1283,7 @@ struct fr_renderer {
                     a.tickets = d_tickets.as<uint32_t>();
                 }
             }
-            note_bank_launch(bp, bs, blen);
+            note_bank_launch(bp, bs, blen, flag_out.host_flags != nullptr);
             Scope sc(this, &t_bank, st);
             HIP_CHECK(launch_bank(a, st));
             sc.done();
@@ -2197,7 +2200,10 @@ const char *fr_plan_json(fr_renderer *r) {
             r->plan_json_cache += std::string(i ? "," : "") + "{\"kernel\":\"" + b.launch.kernel + "\",\"voices\":" + std::to_string(b.voices) +
                                   ",\"partials\":" + std::to_string(b.partials) + ",\"frames\":" + std::to_string(b.frames) +
                                   ",\"chunk_log2\":" + std::to_string(b.launch.chunk_log2) + ",\"waves_per_group\":" + std::to_string(b.launch.waves_per_group) +
-                                  ",\"frames_per_lane\":" + std::to_string(b.launch.frames_per_lane) + ",\"voices_per_wave\":" + std::to_string(b.launch.voices_per_wave) + "}";
+                                  ",\"frames_per_lane\":" + std::to_string(b.launch.frames_per_lane) + ",\"voices_per_wave\":" + std::to_string(b.launch.voices_per_wave) +
+                                  ",\"publishes_rows\":" + (b.launch.publishes_rows ? "true" : "false") + ",\"leaf_variant\":" + std::to_string(b.leaf_variant) +
+                                  ",\"small_call\":" + std::to_string(b.launch.small_call) + ",\"pieces_log2\":" + std::to_string(b.launch.pieces_log2) +
+                                  ",\"variant\":\"" + bank_variant(b.launch, b.log2_p, b.leaf_variant, b.row_flags) + "\"}";
         }
         r->plan_json_cache += "]}";
     }
