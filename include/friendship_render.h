@@ -296,6 +296,12 @@ fr_status fr_stream_end(fr_renderer *r);
  * fill_buffer return FR_ERR_UNSUPPORTED, as does a voice whose track slots the call did not supply.  Results are those of
  * the reference given the same rows.  UINT32_MAX (the default): no tracks.  This is the one workload of the hot path that
  * is HBM-bound (bench.py `tracks`).
+ * With the per-renderer option FR_TRACK_HISTORY = H > 0 (frames, at most 2^24) the renderer keeps the last H frames of
+ * every track row on the device (appended after each successful call; rows a call does not supply read +0.0, and a seek
+ * clears it).  Then stage programs, Delays of tracks, template voices timed by a track, rows left to the pull interpreter
+ * and track voices that feed delay lines may read tracks too, as long as no read reaches more than H frames before the
+ * call (fr_plan_json `track_lookback`).  What it cannot serve -- a deeper read, a Delay of a track with no bound, a
+ * feedback plan, a track voice split across GPUs -- is FR_ERR_UNSUPPORTED, and the renderer is left as it was.
  * The _dense calls take the reference's own input shape, `in` = [n_in_rows][n_times] row-major (host / device memory), and
  * cost O(1) host work per track row where the CSR form costs a length check each. */
 fr_status fr_set_track_inputs(fr_renderer *r, uint32_t first_slot);

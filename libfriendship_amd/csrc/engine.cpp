@@ -139,7 +139,7 @@ struct BankLaunchNote {
     bool row_flags;
 };
 
-constexpr size_t N_OPTIONS = 28;         // per-renderer options (friendship_render_ext.h; the table below fr_renderer)
+constexpr size_t N_OPTIONS = 29;         // per-renderer options (friendship_render_ext.h; the table below fr_renderer)
 
 struct TimerClass {
     double ms = 0;
@@ -163,6 +163,21 @@ __attribute__((weak)) hipError_t launch_input_range(const RangeArgs &a, hipStrea
                 }
             a.out[(size_t)r * a.blocks + b] = o;
         }
+    return hipSuccess;
+}
+
+// Host loops of the track-history launches for the simulator, the same pattern as launch_input_range above.
+__attribute__((weak)) hipError_t launch_track_tail(const TrackTailArgs &a, hipStream_t) {
+    const uint64_t cap = a.mask + 1;
+    for (uint64_t r = 0; r < a.rows; ++r)
+        for (uint64_t i = 0; i < a.count; ++i)
+            a.tail[r * cap + ((a.first + i) & a.mask)] = r < a.src_rows ? a.src[r * a.src_stride + a.col0 + i] : 0.0f;
+    return hipSuccess;
+}
+__attribute__((weak)) hipError_t launch_track_window(const TrackWindowArgs &a, hipStream_t) {
+    for (uint32_t r = 0; r < a.n_rows; ++r)
+        for (uint64_t i = 0; i < a.back + a.n; ++i)
+            a.dst[r][i] = i < a.back ? (a.tail[r] ? a.tail[r][(a.idx - a.back + i) & a.mask] : 0.0f) : (a.call[r] ? a.call[r][i - a.back] : 0.0f);
     return hipSuccess;
 }
 
@@ -197,6 +212,17 @@ struct fr_renderer {
     const float *call_tracks = nullptr;     // row of slot 0 if the matrix started there (never dereferenced below track_from)
     uint64_t call_track_stride = 0, call_track_rows = 0;
     DevBuf d_tracks_stage;                  // host-buffer calls: the rows' copy in HBM
+    // Track history (FR_TRACK_HISTORY = H frames, 0 = off): the last frames of every track row stay on the device, in a ring of
+    // tail_cap (a power of two >= H) floats per row addressed by absolute frame (kernels.hpp TrackTailArgs), appended by every
+    // call after all of its readers.  Readers through an input table (programs, the pull interpreter, template voices) get
+    // this call's DevInput of the slot in track_dev; voices that read tracks over a look-back window read the ring itself.
+    uint64_t track_history = 0, tail_cap = 0;
+    DevBuf d_tail, d_track_win;
+    uint32_t tail_rows = 0;
+    uint64_t tail_end = 0;                  // frame after the last one the ring holds (a call that starts elsewhere seeks)
+    uint64_t tail_launches = 0;             // track_tail_kernel launches of the last call (fr_plan_json)
+    std::vector<std::pair<uint32_t, DevInput>> track_dev;   // (slot, this call's rows of it), by slot
+    bool tail_on() const { return track_history != 0 && track_from != 0xFFFFFFFFu; }
     // shape-matched voices rendered in pieces (few voices x short call): the pieces' sums and the identity row list
     DevBuf d_chunk_ws, d_chunk_rows;
     uint32_t d_chunk_rows_n = 0;
@@ -242,7 +268,8 @@ struct fr_renderer {
     // Calls of a plan without delay lines, programs or pull rows touch only their own input rows and output buffer (and
     // append their own, disjoint part of the input history): on different streams they may overlap on the device.
     bool plan_is_stateless(uint32_t n_slots) const {
-        return plan_current(n_slots) && !plan.sp.uses_rings() && plan.sp.progs.empty() && plan.pull_rows.empty() && plan.sp.split.empty();
+        return plan_current(n_slots) && !plan.sp.uses_rings() && plan.sp.progs.empty() && plan.pull_rows.empty() && plan.sp.split.empty() &&
+               !tail_on();   // (every call appends to the track history)
     }
     void order_after_previous(hipStream_t st, bool this_independent = false) {
         if (!last_pending) return;
@@ -575,6 +602,8 @@ struct fr_renderer {
     // The observed range of `slot` for the planner; an unknown hull is first rebuilt from the slot's visible history (plus a
     // row of this call that a bank kernel will append).
     Range observed_range(uint32_t slot, hipStream_t st) {
+        // (track slots are never stored, so nothing was observed of them: with a track history their amounts stay unbounded)
+        if (tail_on() && slot >= track_from) return Range{-HUGE_VAL, HUGE_VAL, true};
         if (slot >= hulls.size() || slot >= n_vecs) return Range{0.0, 0.0, false};
         Hull &h = hulls[slot];
         if (!h.known) {
@@ -775,6 +804,7 @@ struct fr_renderer {
     void store_inputs(uint32_t n_slots, uint64_t n_times, uint64_t idx, const float *in_data,
                       const uint64_t *offs, uint32_t n_rows, bool device_rows, hipStream_t st, bool dense = false) {
         deferred.clear();
+        track_dev.clear();
         reap();
         call_idx = idx;
         call_tracks = nullptr;
@@ -882,6 +912,11 @@ struct fr_renderer {
 
     DevInput dev_input(uint32_t slot) const {
         DevInput d{nullptr, 0, 0};
+        if (slot >= track_from && !track_dev.empty()) {   // a track read through an input table (track history)
+            auto it = std::lower_bound(track_dev.begin(), track_dev.end(), std::make_pair(slot, d),
+                                       [](const std::pair<uint32_t, DevInput> &x, const std::pair<uint32_t, DevInput> &y) { return x.first < y.first; });
+            return it != track_dev.end() && it->first == slot ? it->second : d;
+        }
         if (slot < slots.size() && slots[slot].fed && slot < n_vecs) {
             const InSlot &s = slots[slot];
             d.data = s.buf.as<float>();
@@ -933,7 +968,7 @@ struct fr_renderer {
         p.graph = &fg;
         const ObservedInputs obs = observed_inputs(st);
         const ObservedInputs *observed = delay_observed ? &obs : nullptr;
-        p.sp = plan_stages(fg, mode == FR_MODE_AUTO, mode != FR_MODE_PULL, 20, use_jit, allow_template, matcher.get(), shard_spec, track_from, observed);
+        p.sp = plan_stages(fg, mode == FR_MODE_AUTO, mode != FR_MODE_PULL, 20, use_jit, allow_template, matcher.get(), shard_spec, track_from, observed, track_history);
         std::vector<std::shared_ptr<JitKernel>> jits(p.sp.banks.size());
         p.jit_epoch = jit_cache.epoch();   // (read first: a compile finishing from here on makes this plan stale)
         if (use_jit) {
@@ -959,7 +994,7 @@ struct fr_renderer {
                     throw Error(FR_ERR_DEVICE, std::string("a kernel of the sharded plan could not be compiled on this rank (every rank must plan alike): ") + e.what());
             }
             if (without) {
-                p.sp = plan_stages(fg, true, true, 20, false, true, nullptr, shard_spec, track_from, observed);
+                p.sp = plan_stages(fg, true, true, 20, false, true, nullptr, shard_spec, track_from, observed, track_history);
                 jits.assign(p.sp.banks.size(), nullptr);
             }
         }
@@ -1066,6 +1101,8 @@ struct fr_renderer {
            << ",\"observed_delays\":" << p.sp.observed.size() << ",\"observed_lookback\":" << p.sp.observed_lookback
            << ",\"observed_refused\":" << p.sp.observed_refused
            << ",\"history_frames\":" << history_frames
+           << ",\"track_history\":" << track_history << ",\"track_lookback\":" << p.sp.track_lookback
+           << ",\"track_window_slots\":" << p.sp.track_window_slots.size()
            << ",\"jit_pending\":" << (p.jit_pending ? "true" : "false") << ",\"jit_kernels_compiled\":" << jit_cache.compiled() << ",\"jit_compile_ms\":" << jit_cache.compile_ms() << ",\"jit_disk_hits\":" << jit_cache.disk_hits()
            << ",\"pull_rows\":" << p.pull_rows.size()
            << ",\"shard\":{\"rank\":" << shard.rank << ",\"world\":" << shard.world << ",\"mode\":" << (sharded() ? shard.mode : 0)
@@ -1083,11 +1120,97 @@ struct fr_renderer {
         if (!plan_current(n_slots)) build_plan(n_slots, st);
     }
 
+    // ---- track history (FR_TRACK_HISTORY) ------------------------------------------------------------
+    // Before the call's readers: a call that does not continue the ring's frames seeks (every frame before idx reads +0.0);
+    // rows the call supplies beyond the ring's are added as zeros; the slots read through an input table get their DevInput --
+    // the call's rows in place when nothing reads before idx, else their window gathered from the ring and the call's rows.
+    void prepare_tracks(uint64_t n_times, uint64_t idx, hipStream_t st) {
+        track_dev.clear();
+        if (!tail_on()) return;
+        if (call_track_rows > tail_rows) {
+            DevBuf nb;
+            nb.ensure(call_track_rows * tail_cap * sizeof(float));
+            HIP_CHECK(hipMemsetAsync(nb.p, 0, call_track_rows * tail_cap * sizeof(float), st));
+            if (tail_rows && tail_end == idx) HIP_CHECK(hipMemcpyAsync(nb.p, d_tail.p, tail_rows * tail_cap * sizeof(float), hipMemcpyDeviceToDevice, st));
+            if (d_tail.p) bury(std::move(d_tail), st);
+            d_tail = std::move(nb);
+            tail_rows = (uint32_t)call_track_rows;
+            tail_end = idx;
+        }
+        if (tail_end != idx) {
+            if (tail_rows) HIP_CHECK(hipMemsetAsync(d_tail.p, 0, tail_rows * tail_cap * sizeof(float), st));
+            tail_end = idx;
+        }
+        const std::vector<uint32_t> &slots = plan.sp.track_window_slots;
+        if (slots.empty()) return;
+        const uint64_t back = std::min(idx, plan.sp.track_lookback);
+        auto call_row = [&](uint32_t sl) -> const float * {
+            return call_tracks && sl - track_from < call_track_rows ? call_tracks + (uint64_t)sl * call_track_stride : nullptr;
+        };
+        if (back == 0) {
+            for (uint32_t sl : slots) {
+                const float *row = call_row(sl);
+                track_dev.push_back({sl, row ? DevInput{row, idx, idx + n_times} : DevInput{nullptr, 0, 0}});
+            }
+            return;
+        }
+        const uint64_t len = back + n_times;
+        used_scratch = true;
+        d_track_win.ensure(slots.size() * len * sizeof(float));
+        TrackWindowArgs a{};
+        a.mask = tail_cap - 1;
+        a.idx = idx;
+        a.back = back;
+        a.n = n_times;
+        for (size_t i = 0; i < slots.size(); ++i) {
+            float *dst = d_track_win.as<float>() + i * len;
+            const uint32_t row = slots[i] - track_from;
+            a.dst[a.n_rows] = dst;
+            a.tail[a.n_rows] = row < tail_rows ? d_tail.as<float>() + (uint64_t)row * tail_cap : nullptr;
+            a.call[a.n_rows] = call_row(slots[i]);
+            if (++a.n_rows == TRACK_WINDOW_MAX_ROWS || i + 1 == slots.size()) {
+                HIP_CHECK(launch_track_window(a, st));
+                a.n_rows = 0;
+            }
+            track_dev.push_back({slots[i], DevInput{dst, idx - back, idx + n_times}});
+        }
+    }
+    // After every reader of the call: its last min(n, ring) columns of every track row into the ring (rows it did not supply,
+    // or that the buff.len() limit dropped, as +0.0).
+    void append_tracks(uint64_t n_times, uint64_t idx, hipStream_t st) {
+        tail_launches = 0;
+        if (!tail_on() || n_times == 0) return;
+        track_dev.clear();
+        used_scratch = true;
+        if (tail_rows) {
+            TrackTailArgs a{};
+            a.tail = d_tail.as<float>();
+            a.src = call_tracks ? call_tracks + (uint64_t)track_from * call_track_stride : nullptr;
+            a.src_stride = call_track_stride;
+            a.src_rows = call_tracks ? (uint32_t)std::min<uint64_t>(call_track_rows, tail_rows) : 0;
+            a.rows = tail_rows;
+            a.mask = tail_cap - 1;
+            a.count = std::min(n_times, tail_cap);
+            a.col0 = n_times - a.count;
+            a.first = idx + a.col0;
+            Scope sc(this, &t_stage, st);
+            HIP_CHECK(launch_track_tail(a, st));
+            sc.done();
+            ++tail_launches;
+        }
+        tail_end = idx + n_times;
+    }
+
     // ---- execution --------------------------------------------------------------------------------
     void execute(float *d_dst, uint32_t n_slots, uint64_t n_times, uint64_t idx, hipStream_t st) {
         bank_launches.clear();
         ensure_plan(n_slots, st);
-        if (n_slots == 0 || n_times == 0) return;
+        if (n_slots == 0 || n_times == 0) {   // (nothing to render: the track history still moves on as the reference's inputs do)
+            prepare_tracks(n_times, idx, st);
+            append_tracks(n_times, idx, st);
+            return;
+        }
+        prepare_tracks(n_times, idx, st);
         const StagedPlan &sp = plan.sp;
 
         // Window of the staged part.  Contiguous with what the rings already hold: just this call's frames.
@@ -1149,7 +1272,10 @@ struct fr_renderer {
         std::unordered_set<uint32_t> tile_slots, tile_appended;   // input slots whose deferred row the tiles append / this tile has appended
         // One bank launch over the window [b0, b0 + blen).  `tile_off` >= 0: a tile of the exchange window (b0 = x0 + tile_off),
         // written to the tile-major workspace; such a launch appends ITS part of a deferred input row.
-        auto launch_bank_window = [&](BankStage &bs, uint64_t b0, uint64_t blen, int64_t tile_off) {
+        // `trk`: where a voice that reads tracks finds them for this window (a span of the track history's ring), instead of the
+        // call's own matrix
+        struct TrackSrc { const float *p; uint64_t stride; uint32_t limit; };
+        auto launch_bank_part = [&](BankStage &bs, uint64_t b0, uint64_t blen, int64_t tile_off, const TrackSrc *trk) {
             const bool ring = bs.grp.to_ring, ws = bs.grp.to_ws;
             const BankPlan bp = plan_bank_launch(bs, blen, flag_out.host_flags != nullptr);
             BankArgs a{};
@@ -1223,7 +1349,11 @@ struct fr_renderer {
                     j.rows = d_chunk_rows.as<uint32_t>();
                     j.out_stride = blen;
                 }
-                if (bs.grp.tracks && call_tracks) {
+                if (bs.grp.tracks && trk) {
+                    j.tracks = trk->p;
+                    j.track_stride = trk->stride;
+                    j.track_limit = trk->limit;
+                } else if (bs.grp.tracks && call_tracks) {
                     if (b0 != idx || blen != n_times) throw Error(FR_ERR_UNSUPPORTED, "internal: a voice that reads tracks rendered over another window than the call's");
                     j.tracks = call_tracks;
                     j.track_stride = call_track_stride;
@@ -1287,6 +1417,27 @@ struct fr_renderer {
             Scope sc(this, &t_bank, st);
             HIP_CHECK(launch_bank(a, st));
             sc.done();
+        };
+        // A voice that reads tracks over a window that starts before idx (it feeds a delay line: the call after a seek, an edit
+        // or a ring growth) is launched per span: the frames before idx from the track history, cut again where its ring
+        // wraps, then the call's own frames as in steady state.  Every span is the same generated kernel.
+        auto launch_bank_window = [&](BankStage &bs, uint64_t b0, uint64_t blen, int64_t tile_off) {
+            if (!(bs.grp.tracks && tail_on() && tile_off < 0 && b0 < idx && b0 + blen == idx + n_times)) {
+                launch_bank_part(bs, b0, blen, tile_off, nullptr);
+                return;
+            }
+            for (uint64_t s0 = b0; s0 < idx;) {
+                const uint64_t pos = s0 & (tail_cap - 1);
+                const uint64_t len = std::min(idx - s0, tail_cap - pos);
+                TrackSrc ts{nullptr, tail_cap, 0};
+                if (tail_rows) {
+                    ts.p = reinterpret_cast<const float *>(reinterpret_cast<uintptr_t>(d_tail.as<float>() + pos) - (uintptr_t)track_from * tail_cap * sizeof(float));
+                    ts.limit = (uint32_t)std::min<uint64_t>((uint64_t)track_from + tail_rows, 0xFFFFFFFFull);
+                }
+                launch_bank_part(bs, s0, len, -1, &ts);
+                s0 += len;
+            }
+            launch_bank_part(bs, idx, n_times, -1, nullptr);
         };
         // Stage programs: the input table of a launch and the launch itself (a range of programs over a window of frames).
         std::vector<DevInput> tab(sp.input_slots.size());
@@ -1439,6 +1590,7 @@ struct fr_renderer {
             plan.stage_end = idx + n_times;
         }
         if (!plan.pull_rows.empty()) run_pull(d_dst, n_slots, n_times, idx, st);
+        append_tracks(n_times, idx, st);
     }
 
     void run_pull(float *d_dst, uint32_t n_slots, uint64_t n_times, uint64_t idx, hipStream_t st) {
@@ -1525,6 +1677,7 @@ void check_fill_args(const void *out, uint32_t n_slots, uint64_t n_times, const 
 // values whose bits it has -- or `word`, which stands for `word_value`.  `apply` stores a value in the renderer; `given`:
 // it came from the environment or an option, not from the default.
 enum OptionSource : uint8_t { OPTION_DEFAULT, OPTION_ENV, OPTION_GIVEN };
+enum OptionListing : uint8_t { UNLISTED, LISTED, LISTED_WHEN_SET };
 struct Knob {
     const char *name;
     int64_t dflt, lo, hi;
@@ -1533,13 +1686,16 @@ struct Knob {
     int64_t word_value;
     int64_t (*env)(const char *e);
     void (*apply)(fr_renderer &r, int64_t v, bool given);
-    bool listed = true;   // in fr_options_json
+    uint8_t listed = LISTED;   // in fr_options_json: always, never, or once the environment or an option set it
 };
 
 int64_t env_on(const char *e) { return e[0] != '0'; }
 int64_t env_int(const char *e) { return std::atoi(e); }
 int64_t env_long(const char *e) { return std::atoll(e); }
 int64_t env_clamp(const char *e, int lo, int hi) { return std::min(hi, std::max(lo, std::atoi(e))); }
+constexpr int64_t ENV_REFUSED = INT64_MIN;   // an `env` reading that makes create fail (resolve_options)
+int64_t env_strict_track_history(const char *e);
+bool parse_option(const Knob &k, const char *s, int64_t &v);
 
 const Knob kKnobs[] = {
     {"FR_JIT", 1, 0, 1, 0, nullptr, 0, env_on, [](fr_renderer &r, int64_t v, bool) { r.allow_jit = v != 0; }},
@@ -1594,8 +1750,25 @@ const Knob kKnobs[] = {
     {"FR_DELAY_OBSERVED", 0, 0, 1, 0, nullptr, 0, env_on, [](fr_renderer &r, int64_t v, bool) { r.delay_observed = v != 0; }, false},
     {"FR_DELAY_OBSERVED_MAX", 1 << 20, 1024, 1 << 28, 0, nullptr, 0, [](const char *e) { return env_clamp(e, 1024, 1 << 28); },
      [](fr_renderer &r, int64_t v, bool) { r.delay_observed_max = (uint64_t)v; }, false},
+    // Track history (frames of every track row kept on the device; 0 = tracks are readable by voice leaves of their own call
+    // only).  The environment is read as strictly as an option: a value the table refuses makes create fail.  A rendering
+    // mode too (fr_plan_json: track_history), listed by fr_options_json once it is set.
+    {"FR_TRACK_HISTORY", 0, 0, 1 << 24, 0, nullptr, 0, env_strict_track_history,
+     [](fr_renderer &r, int64_t v, bool) {
+         r.track_history = (uint64_t)v;
+         uint64_t cap = 64;
+         while (cap < r.track_history) cap <<= 1;
+         r.tail_cap = v ? cap : 0;
+     }, LISTED_WHEN_SET},
 };
 static_assert(sizeof kKnobs / sizeof kKnobs[0] == N_OPTIONS, "N_OPTIONS counts the rows of kKnobs");
+
+int64_t env_strict_track_history(const char *e) {
+    int64_t v = 0;
+    for (const Knob &k : kKnobs)
+        if (std::strcmp(k.name, "FR_TRACK_HISTORY") == 0) return parse_option(k, e, v) ? v : ENV_REFUSED;
+    return ENV_REFUSED;
+}
 
 bool parse_option(const Knob &k, const char *s, int64_t &v) {
     if (k.word && std::strcmp(s, k.word) == 0) {
@@ -1624,6 +1797,7 @@ bool resolve_options(const fr_option *options, size_t n_options, int64_t *value,
         source[i] = OPTION_DEFAULT;
         if (const char *e = std::getenv(kKnobs[i].name)) {
             value[i] = kKnobs[i].env(e);
+            if (value[i] == ENV_REFUSED) return false;
             source[i] = OPTION_ENV;
         }
     }
@@ -2193,6 +2367,8 @@ const char *fr_plan_json(fr_renderer *r) {
     if (r->plan.valid && r->plan_json_cache.size() > 1) {   // live: counters of the exchange step (partial-block sharding), the last call's bank launches
         r->plan_json_cache.pop_back();
         r->plan_json_cache += ",\"lookback_growths\":" + std::to_string(r->lookback_growths) + ",\"range_launches\":" + std::to_string(r->range_launches);
+        r->plan_json_cache += ",\"track_tail_bytes\":" + std::to_string((uint64_t)r->tail_rows * r->tail_cap * sizeof(float)) +
+                              ",\"track_tail_launches\":" + std::to_string(r->tail_launches);
         r->plan_json_cache += ",\"exchange_stats\":{\"calls\":" + std::to_string(r->exchange_calls) + ",\"tiles\":" + std::to_string(r->exchange_tiles) +
                               ",\"bytes_sent\":" + std::to_string(r->exchange_bytes) + "},\"bank_launches\":[";
         for (size_t i = 0; i < r->bank_launches.size(); ++i) {
@@ -2216,7 +2392,7 @@ const char *fr_options_json(fr_renderer *r) {
     std::string &js = r->options_json_cache;
     js = "{";
     for (size_t i = 0; i < N_OPTIONS; ++i)
-        if (kKnobs[i].listed)
+        if (kKnobs[i].listed == LISTED || (kKnobs[i].listed == LISTED_WHEN_SET && r->option_source[i] != OPTION_DEFAULT))
             js += std::string(js.size() > 1 ? "," : "") + "\"" + kKnobs[i].name + "\":{\"value\":\"" + option_text(kKnobs[i], r->option_value[i]) +
               "\",\"source\":\"" + kSource[r->option_source[i]] + "\"}";
     js += "}";

@@ -1576,4 +1576,73 @@ hipError_t launch_input_range(const RangeArgs &a, hipStream_t s) {
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------------------------
+// Track history (kernels.hpp TrackTailArgs): a pure streaming copy.  One wave per row, lanes over consecutive frames; the
+// append is at most two contiguous spans of the ring (before and after its wrap).  A span whose source and destination are
+// equally aligned moves as 16-byte loads and stores, with its unaligned head and tail element by element; otherwise, and
+// for rows not supplied (+0.0), dword accesses, still 256 contiguous bytes per wave.
+__device__ inline void track_span(float *dst, const float *src, uint64_t n, uint32_t lane) {
+    const uint64_t mis = ((uintptr_t)dst & 15u) >> 2;                          // dst floats past a 16-byte boundary
+    const bool vec = !src || (((uintptr_t)dst ^ (uintptr_t)src) & 15u) == 0;
+    if (!vec) {
+        for (uint64_t i = lane; i < n; i += 64) dst[i] = src[i];
+        return;
+    }
+    const uint64_t head = mis ? (4 - mis < n ? 4 - mis : n) : 0;
+    if (lane < head) dst[lane] = src ? src[lane] : 0.0f;
+    const uint64_t nv = (n - head) >> 2;
+    float4 *d4 = reinterpret_cast<float4 *>(dst + head);
+    if (src) {
+        const float4 *s4 = reinterpret_cast<const float4 *>(src + head);
+        for (uint64_t i = lane; i < nv; i += 64) d4[i] = s4[i];
+    } else {
+        for (uint64_t i = lane; i < nv; i += 64) d4[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    }
+    const uint64_t done = head + (nv << 2);
+    if (lane < n - done) dst[done + lane] = src ? src[done + lane] : 0.0f;
+}
+
+__global__ __launch_bounds__(256) void track_tail_kernel(TrackTailArgs a) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t cap = a.mask + 1, p0 = a.first & a.mask;
+    const uint64_t len0 = a.count < cap - p0 ? a.count : cap - p0;
+    for (uint64_t r = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6); r < a.rows; r += (uint64_t)gridDim.x * 4) {
+        float *row = a.tail + r * cap;
+        const float *src = r < a.src_rows ? a.src + r * a.src_stride + a.col0 : nullptr;
+        track_span(row + p0, src, len0, lane);
+        if (a.count > len0) track_span(row, src ? src + len0 : nullptr, a.count - len0, lane);
+    }
+}
+
+hipError_t launch_track_tail(const TrackTailArgs &a, hipStream_t s) {
+    if (a.rows == 0 || a.count == 0) return hipSuccess;
+    if (a.count > a.mask + 1 || (a.src_rows && !a.src)) return hipErrorInvalidValue;
+    uint64_t blocks = (a.rows + 3) / 4;
+    if (blocks > 8192) blocks = 8192;
+    hipLaunchKernelGGL(track_tail_kernel, dim3((uint32_t)blocks), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+__global__ __launch_bounds__(256) void track_window_kernel(TrackWindowArgs a) {
+    const uint32_t r = blockIdx.y;
+    float *dst = a.dst[r];
+    const float *tail = a.tail[r], *call = a.call[r];
+    const uint64_t len = a.back + a.n, t0 = a.idx - a.back;
+    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < len; i += (uint64_t)gridDim.x * 256) {
+        float v = 0.0f;
+        if (i < a.back) { if (tail) v = tail[(t0 + i) & a.mask]; }
+        else if (call) v = call[i - a.back];
+        dst[i] = v;
+    }
+}
+
+hipError_t launch_track_window(const TrackWindowArgs &a, hipStream_t s) {
+    if (a.n_rows == 0 || a.back + a.n == 0) return hipSuccess;
+    if (a.n_rows > TRACK_WINDOW_MAX_ROWS || a.back > a.idx) return hipErrorInvalidValue;
+    uint64_t blocks = (a.back + a.n + 255) / 256;
+    if (blocks > 64) blocks = 64;
+    hipLaunchKernelGGL(track_window_kernel, dim3((uint32_t)blocks, a.n_rows), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
 }  // namespace fr

@@ -244,4 +244,33 @@ struct RangeArgs {
 };
 hipError_t launch_input_range(const RangeArgs &a, hipStream_t s);
 
+// Track history (FR_TRACK_HISTORY): the renderer keeps the last frames of every track row (fr_set_track_inputs) in a ring of
+// mask + 1 floats per row (a power of two), frame f of row r at tail[r * (mask + 1) + (f & mask)].  A call appends the last
+// `count` columns of its rows: lanes over consecutive frames of a row, a wave per row, 16-byte loads and stores where the
+// source and the destination are equally aligned; rows [src_rows, rows) -- not supplied -- are appended as +0.0.
+struct TrackTailArgs {
+    float *tail;
+    const float *src;          // the call's row of the first track slot (rows src_stride floats apart); null: none supplied
+    uint64_t src_stride;
+    uint32_t src_rows, rows;
+    uint64_t mask;
+    uint64_t first;            // absolute frame of the first appended column
+    uint64_t col0;             // ... and its column in the call's rows
+    uint64_t count;            // columns appended per row (at most mask + 1)
+};
+hipError_t launch_track_tail(const TrackTailArgs &a, hipStream_t s);
+
+// A track slot read further back than the call's own frames (programs, the pull interpreter, template voices): its window
+// [idx - back, idx + n) gathered into dst[i] -- the `back` frames before idx from the tail ring (null: +0.0), the call's
+// frames from its row (null: not supplied, +0.0).  Row i of the launch is blockIdx.y.
+constexpr uint32_t TRACK_WINDOW_MAX_ROWS = 32;
+struct TrackWindowArgs {
+    float *dst[TRACK_WINDOW_MAX_ROWS];
+    const float *tail[TRACK_WINDOW_MAX_ROWS];
+    const float *call[TRACK_WINDOW_MAX_ROWS];
+    uint32_t n_rows;
+    uint64_t mask, idx, back, n;
+};
+hipError_t launch_track_window(const TrackWindowArgs &a, hipStream_t s);
+
 }  // namespace fr

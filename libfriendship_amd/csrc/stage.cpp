@@ -407,8 +407,99 @@ bool build_program(const FlatGraph &g, const Planner &P, uint32_t m, std::unorde
     return true;
 }
 
-// Tracks (fr_set_track_inputs) are never stored: only a voice leaf of the call that supplies them can read one.
-void check_tracks(const FlatGraph &g, const StagedPlan &sp, uint32_t track_from) {
+// Track history (FR_TRACK_HISTORY): how far back the rows left to the pull interpreter read track slots -- the sum of the
+// constant delays on a path from a row's root to a track.  A track under a Delay whose amount is not a constant has no
+// bound there: refused.
+uint64_t pull_track_lookback(const FlatGraph &g, const StagedPlan &sp, uint32_t track_from) {
+    constexpr uint64_t NONE = ~0ull;   // no track below
+    std::unordered_map<uint32_t, uint64_t> below;
+    std::vector<std::pair<uint32_t, bool>> st;
+    for (uint32_t row : sp.pull_rows) st.push_back({g.outputs[row], false});
+    while (!st.empty()) {
+        auto [n, done] = st.back();
+        st.pop_back();
+        const FlatNode &x = g.nodes[n];
+        const bool leaf = x.op == OP_CONST || x.op == OP_INPUT || x.op == OP_FBREF;
+        if (!done) {
+            if (below.count(n)) continue;
+            if (leaf) { below[n] = (x.op == OP_INPUT && x.a >= track_from) ? 0 : NONE; continue; }
+            st.push_back({n, true});
+            st.push_back({x.a, false});
+            st.push_back({x.b, false});
+            continue;
+        }
+        if (below.count(n)) continue;
+        const uint64_t a = below.at(x.a), b = below.at(x.b);
+        uint64_t v = b;   // (a Delay's amount is evaluated at the frame itself)
+        if (x.op == OP_DELAY) {
+            if (a != NONE) {
+                uint64_t d = 0;
+                if (!Planner::delay_frames_ok(g, x, d))
+                    throw Error(FR_ERR_UNSUPPORTED, "a track input (fr_set_track_inputs) is reached through a Delay with no bound: "
+                                                    "the track history cannot serve it");
+                v = v == NONE ? a + d : std::max(v, a + d);
+            }
+        } else if (a != NONE) {
+            v = v == NONE ? a : std::max(v, a);
+        }
+        below[n] = v;
+    }
+    uint64_t lb = 0;
+    for (uint32_t row : sp.pull_rows) {
+        const uint64_t v = below.at(g.outputs[row]);
+        if (v != NONE) lb = std::max(lb, v);
+    }
+    return lb;
+}
+
+// Tracks (fr_set_track_inputs) are never stored: only a voice leaf of the call that supplies them can read one -- unless the
+// renderer keeps a track history (`track_history` frames, FR_TRACK_HISTORY): then any reader whose look-back into the tracks
+// is bounded by it may read them (sp.track_lookback, sp.track_window_slots), and the refusals name what is out of reach.
+void check_tracks(const FlatGraph &g, StagedPlan &sp, uint32_t track_from, uint64_t track_history) {
+    if (track_history && track_from != 0xFFFFFFFFu && g.has_input && g.max_input_slot >= track_from) {
+        auto refuse = [](const std::string &why) { throw Error(FR_ERR_UNSUPPORTED, "a track input (fr_set_track_inputs) " + why); };
+        std::vector<uint32_t> slots;
+        for (uint32_t sl : sp.input_slots) if (sl >= track_from) slots.push_back(sl);
+        bool ring_voice_reads = false;
+        for (const BankLaunch &bl : sp.banks) {
+            if (bl.tracks && bl.to_ws) refuse("is read by a voice split across GPUs (FR_SHARD_PARTIALS)");
+            if (!bl.jit && bl.input_slot >= track_from) slots.push_back(bl.input_slot);
+            // (a voice that reads tracks and feeds a ring is rendered over the rings' whole look-back window)
+            if (bl.tracks && bl.to_ring) {
+                sp.track_lookback = std::max(sp.track_lookback, sp.lmax);
+                ring_voice_reads = true;
+            }
+        }
+        // (what a feedback plan replays from frame 0 -- its programs and ring-bound voices -- would need every frame of the tracks)
+        if (sp.feedback && (ring_voice_reads || !slots.empty())) refuse("is read by a feedback loop (its rings are replayed from frame 0)");
+        for (uint32_t sl : sp.observed_slots)
+            if (sl >= track_from) refuse("is read by the amount of a Delay bounded by observed values (FR_DELAY_OBSERVED)");
+        if (sp.track_unbounded) refuse("is reached through a Delay with no bound: the track history cannot serve it");
+        if (!sp.pull_rows.empty()) {
+            const uint64_t lb = pull_track_lookback(g, sp, track_from);
+            sp.track_lookback = std::max(sp.track_lookback, lb);
+            std::unordered_set<uint32_t> seen;
+            std::vector<uint32_t> st;
+            for (uint32_t row : sp.pull_rows) st.push_back(g.outputs[row]);
+            while (!st.empty()) {
+                const uint32_t n = st.back();
+                st.pop_back();
+                if (!seen.insert(n).second) continue;
+                const FlatNode &x = g.nodes[n];
+                if (x.op == OP_INPUT && x.a >= track_from) slots.push_back(x.a);
+                if (x.op == OP_CONST || x.op == OP_INPUT || x.op == OP_FBREF) continue;
+                st.push_back(x.a);
+                st.push_back(x.b);
+            }
+        }
+        if (sp.track_lookback > track_history)
+            refuse("is read " + std::to_string(sp.track_lookback) + " frames back, more than the track history keeps (FR_TRACK_HISTORY = " +
+                   std::to_string(track_history) + ")");
+        std::sort(slots.begin(), slots.end());
+        slots.erase(std::unique(slots.begin(), slots.end()), slots.end());
+        sp.track_window_slots = std::move(slots);
+        return;
+    }
     if (track_from != 0xFFFFFFFFu && g.has_input && g.max_input_slot >= track_from) {
         // tracks are never stored: only a voice leaf of the call that supplies them can read one
         auto refuse = [](const char *who) { throw Error(FR_ERR_UNSUPPORTED, std::string("a track input (fr_set_track_inputs) is read by ") + who +
@@ -465,7 +556,7 @@ void note_observed(const FlatGraph &g, const Planner &P, StagedPlan &sp) {
 }  // namespace
 
 StagedPlan plan_stages(const FlatGraph &g, bool allow_banks, bool allow_programs, uint32_t max_log2_p, bool allow_jit, bool allow_template,
-                       BankMatcher *reuse, const ShardSpec *shard, uint32_t track_from, const ObservedInputs *observed) {
+                       BankMatcher *reuse, const ShardSpec *shard, uint32_t track_from, const ObservedInputs *observed, uint64_t track_history) {
     StagedPlan sp;
     PlanTrace plan_trace;
     const uint32_t n_rows = (uint32_t)g.outputs.size();
@@ -594,7 +685,7 @@ StagedPlan plan_stages(const FlatGraph &g, bool allow_banks, bool allow_programs
             add_voice(fb.banks, grp, vm, row, false);
         }
         std::sort(fb.pull_rows.begin(), fb.pull_rows.end());
-        check_tracks(g, fb, track_from);
+        check_tracks(g, fb, track_from, track_history);
         return fb;
     }
 
@@ -641,6 +732,20 @@ StagedPlan plan_stages(const FlatGraph &g, bool allow_banks, bool allow_programs
     }
     for (auto &kv : P.bank_of) sp.input_lookback = std::max(sp.input_lookback, L[kv.first]);
     if (!sp.pull_rows.empty()) sp.input_lookback_unbounded = true;
+    // the same per track slot (check_tracks): an ordinary slot's long delay does not count against the track history
+    if (track_history && track_from != 0xFFFFFFFFu) {
+        for (uint32_t m : cuts) {
+            const uint64_t lm = L[m];
+            for (const StageInstr &in : built[m].instrs) {
+                if ((in.op != S_INPUT && in.op != S_READ_INPUT && in.op != S_READ_INPUT_DYN) || sp.input_slots[in.imm] < track_from) continue;
+                if (in.op == S_INPUT) sp.track_lookback = std::max(sp.track_lookback, lm);
+                else if (in.op == S_READ_INPUT_DYN && in.d_lo == 0xFFFFFFFFu) sp.track_unbounded = true;
+                else sp.track_lookback = std::max(sp.track_lookback, lm + in.d_lo);
+            }
+        }
+        for (auto &kv : P.bank_of)
+            if (!kv.second->jit && kv.second->input_slot >= track_from) sp.track_lookback = std::max(sp.track_lookback, L[kv.first]);
+    }
 
     // rings
     std::unordered_map<uint32_t, uint32_t> ring_of;
@@ -1066,7 +1171,7 @@ StagedPlan plan_stages(const FlatGraph &g, bool allow_banks, bool allow_programs
     FR_PT("H_end");
     std::sort(sp.pull_rows.begin(), sp.pull_rows.end());
     if (P.observed) note_observed(g, P, sp);
-    check_tracks(g, sp, track_from);
+    check_tracks(g, sp, track_from, track_history);
     return sp;
 }
 

@@ -104,6 +104,12 @@ struct StagedPlan {
     std::vector<uint32_t> observed_slots;
     uint64_t observed_lookback = 0;
     uint32_t observed_refused = 0;
+    // Track history (FR_TRACK_HISTORY): the deepest frame before the call's first one that any read of a track slot reaches
+    // (ring windows of the voices that read tracks, constant delays and proven bounds on the paths from a track), and the
+    // track slots that programs, the pull interpreter and template voices read through an input table (stage.cpp check_tracks)
+    uint64_t track_lookback = 0;
+    std::vector<uint32_t> track_window_slots;
+    bool track_unbounded = false;          // (planning only) a staged read of a track by a signal amount without a bound
     bool uses_rings() const { return n_rings != 0; }
 };
 
@@ -122,9 +128,11 @@ struct ObservedInputs {
 class BankMatcher;
 // `track_from`: input slots >= it are control-rate tracks (fr_set_track_inputs): visible only to the call that supplies them,
 // readable only by the leaves of shape-matched voices (anything else that reads one makes the plan FR_ERR_UNSUPPORTED).
+// `track_history` (FR_TRACK_HISTORY, frames): the engine keeps that many frames of every track row, so programs, the pull
+// interpreter, template voices and voices that feed delay lines may read tracks too, as far back as that.
 StagedPlan plan_stages(const FlatGraph &g, bool allow_banks, bool allow_programs, uint32_t max_log2_p, bool allow_jit = false,
                        bool allow_template = true, BankMatcher *reuse = nullptr, const ShardSpec *shard = nullptr, uint32_t track_from = 0xFFFFFFFFu,
-                       const ObservedInputs *observed = nullptr);
+                       const ObservedInputs *observed = nullptr, uint64_t track_history = 0);
 
 // Do the observed Delays of `sp` (planned from `g` with observed ranges) still fit their planned look-backs under the ranges
 // `obs` gives now?  False: some bound grew past its plan, or has none any more.
