@@ -119,6 +119,7 @@ struct Plan {
     std::shared_ptr<JitKernel> stage_jit;   // compiled form of the programs (null: interpreted by stage_kernel)
     DevBuf d_jprogs, d_ptab;
     uint32_t stage_shapes = 0;
+    StageJitPlan stage_jit_form;         // stage_jit's generated form (deep ... blk; its source and rows are not kept)
     bool stage_valid = false;            // rings hold [stage_end - lmax, stage_end) of the current graph + history
     uint64_t stage_end = 0;
     std::vector<uint32_t> pull_rows;     // output rows evaluated by the pull interpreter
@@ -138,6 +139,52 @@ struct BankLaunchNote {
     uint32_t log2_p, leaf_variant;       // (with row_flags: what bankplan.hpp bank_variant reads besides the plan)
     bool row_flags;
 };
+
+// One stage-program launch of the last call, as fr_plan_json's "stage_launches" shows it.
+struct StageLaunchNote {
+    const char *form;                    // levels, fused, strided, feedback, copy, replay
+    bool jit;                            // jit_stage (else stage_kernel)
+    uint32_t programs;
+    uint64_t frames, stride;
+    bool carry, carry_only, table;       // use_carry (stage_kernel's LDS carry), carry_only, input table in device memory
+    uint32_t grid_parts;                 // launches of at most 65535 programs (grid.y) it was cut into
+};
+
+// fr_plan_json "stage_jit_form": the #defines plan_stage_jit wrote for the plan's compiled programs, null when interpreted.
+static std::string stage_jit_form_json(const Plan &p) {
+    if (!p.stage_jit) return "null";
+    const StageJitPlan &f = p.stage_jit_form;
+    return std::string("{\"deep\":") + (f.deep ? "true" : "false") + ",\"maxp\":" + std::to_string(f.maxp) + ",\"maxld\":" + std::to_string(f.maxld) +
+           ",\"maxst\":" + std::to_string(f.maxst) + ",\"defer\":" + (f.defer ? "true" : "false") + ",\"blk\":" + std::to_string(f.blk) +
+           ",\"shapes\":" + std::to_string(p.stage_shapes) + "}";
+}
+
+// fr_plan_json "stage_hoisted_max": the most loads any program issues back to back before its other instructions (StageProg
+// n_loads; 0 where a program has more than STAGE_MAX_HOISTED loads and constants: each is then issued where it is used).
+static uint32_t stage_hoisted_max(const StagedPlan &sp) {
+    uint32_t m = 0;
+    for (const StageProg &pg : sp.progs) m = std::max(m, pg.n_loads);
+    return m;
+}
+
+// A stage launch as one key (fr_plan_json "stage_launches" "variant"): the kernel -- jit_stage with its generated form
+// [plain|deep, P (MAXP > 0), defer, B<BLK>] -- then the launch form and the paths the launch's arguments select:
+// +carry / +carry_only (stage_kernel: use_carry, the LDS carry; jit_stage keeps it in registers whenever it strides),
+// +table (more than STAGE_INLINE_INPUTS input slots: the table in device memory), +grid<N> (cut into N launches of at most
+// 65535 programs).  tests/stage_variants.py has a GPU case for each key the rule produces.
+static std::string stage_variant(const StageLaunchNote &n, const Plan &p) {
+    std::string k = "stage_kernel";
+    if (n.jit) {
+        const StageJitPlan &f = p.stage_jit_form;
+        k = std::string("jit_stage[") + (f.deep ? "deep" : "plain") + (f.maxp ? ",P" : "") + (f.defer ? ",defer" : "") + ",B" + std::to_string(f.blk) + "]";
+    }
+    k += std::string("/") + n.form;
+    if (n.carry_only) k += "+carry_only";
+    else if (n.carry) k += "+carry";
+    if (n.table) k += "+table";
+    if (n.grid_parts > 1) k += "+grid" + std::to_string(n.grid_parts);
+    return k;
+}
 
 constexpr size_t N_OPTIONS = 29;         // per-renderer options (friendship_render_ext.h; the table below fr_renderer)
 
@@ -430,6 +477,7 @@ struct fr_renderer {
     unsigned lower_threads = 1;          // FR_LOWER_THREADS, FR_LOWER_PAR_MIN_NODES, FR_LOWER_PAR_MIN_EDIT (Lowering::set_parallel)
     size_t lower_min_nodes = 0, lower_min_edit = 0;
     std::vector<BankLaunchNote> bank_launches;   // the last call's (fr_plan_json), at most 256
+    std::vector<StageLaunchNote> stage_launches; // (likewise)
     void note_bank_launch(const BankPlan &bp, const BankStage &bs, uint64_t frames, bool row_flags) {
         const uint32_t partials = bs.grp.general ? bs.grp.max_leaves : 1u << bs.grp.log2_p;
         if (bank_launches.size() < 256)
@@ -1039,6 +1087,12 @@ struct fr_renderer {
                         throw Error(FR_OK, "");
                     }
                     p.stage_shapes = sj.n_shapes;
+                    p.stage_jit_form.deep = sj.deep;
+                    p.stage_jit_form.defer = sj.defer;
+                    p.stage_jit_form.maxp = sj.maxp;
+                    p.stage_jit_form.maxld = sj.maxld;
+                    p.stage_jit_form.maxst = sj.maxst;
+                    p.stage_jit_form.blk = sj.blk;
                     p.d_jprogs.ensure(sj.progs.size() * sizeof(JitStageProg));
                     p.d_ptab.ensure(std::max<size_t>(sj.ptab.size(), 1) * sizeof(uint32_t));
                     HIP_CHECK(hipMemcpyAsync(p.d_jprogs.p, sj.progs.data(), sj.progs.size() * sizeof(JitStageProg), hipMemcpyHostToDevice, st));
@@ -1095,6 +1149,9 @@ struct fr_renderer {
            << ",\"fused_levels\":" << (p.sp.fused_level_first.empty() ? 0 : p.sp.fused_level_first.size() - 1) << ",\"copy_programs\":" << p.sp.post_count
            << ",\"stage_levels\":" << (p.sp.level_first.empty() ? 0 : p.sp.level_first.size() - 1)
            << ",\"stage_jit\":" << (p.stage_jit ? "true" : "false") << ",\"stage_shapes\":" << p.stage_shapes
+           << ",\"stage_jit_form\":" << stage_jit_form_json(p)
+           << ",\"fused_carry_only\":" << (p.sp.feedback && p.sp.fused_carry_only ? "true" : "false")
+           << ",\"stage_hoisted_max\":" << stage_hoisted_max(p.sp)
            << ",\"rings\":" << p.sp.n_rings << ",\"max_lookback\":" << p.sp.lmax
            << ",\"input_lookback\":" << p.sp.input_lookback << ",\"input_lookback_unbounded\":" << (p.sp.input_lookback_unbounded ? "true" : "false")
            << ",\"delay_observed\":" << (delay_observed ? "true" : "false") << ",\"delay_observed_max\":" << delay_observed_max
@@ -1204,6 +1261,7 @@ struct fr_renderer {
     // ---- execution --------------------------------------------------------------------------------
     void execute(float *d_dst, uint32_t n_slots, uint64_t n_times, uint64_t idx, hipStream_t st) {
         bank_launches.clear();
+        stage_launches.clear();
         ensure_plan(n_slots, st);
         if (n_slots == 0 || n_times == 0) {   // (nothing to render: the track history still moves on as the reference's inputs do)
             prepare_tracks(n_times, idx, st);
@@ -1450,7 +1508,13 @@ struct fr_renderer {
             }
         };
         uint64_t launch_stride = 0;
+        const char *launch_form = "levels";
         auto launch_range = [&](uint32_t first, uint32_t count, uint64_t s0, uint64_t slen) {
+            if (count && stage_launches.size() < 256) {
+                const bool carry_only = launch_stride && sp.feedback && sp.fused_carry_only;
+                stage_launches.push_back({launch_form, plan.stage_jit != nullptr, count, slen, launch_stride, launch_stride && sp.feedback,
+                                          carry_only, tab.size() > STAGE_INLINE_INPUTS, (count - 1) / 65535u + 1});
+            }
             for (uint32_t off = 0; off < count && plan.stage_jit; off += 65535u) {   // grid.y limit
                 JitStageArgs a{};
                 a.ptab = plan.d_ptab.as<uint32_t>();
@@ -1495,7 +1559,8 @@ struct fr_renderer {
                 sc.done();
             }
         };
-        auto launch_fused_levels = [&](uint64_t s0, uint64_t slen) {   // a feedback plan's fused form: a strided launch per level
+        auto launch_fused_levels = [&](uint64_t s0, uint64_t slen, const char *form) {   // a feedback plan's fused form: a strided launch per level
+            launch_form = form;
             launch_stride = sp.fused_stride;
             for (size_t l = 0; l + 1 < sp.fused_level_first.size(); ++l)
                 launch_range(sp.fused_first + sp.fused_level_first[l], sp.fused_level_first[l + 1] - sp.fused_level_first[l], s0, slen);
@@ -1507,7 +1572,7 @@ struct fr_renderer {
                 const uint64_t len = std::min<uint64_t>(FB_CHUNK, idx - c0);
                 for (BankStage &bs : plan.banks)
                     if (bs.grp.to_ring) launch_bank_window(bs, c0, len, -1);
-                launch_fused_levels(c0, len);
+                launch_fused_levels(c0, len, "replay");
             }
         }
         // The exchange window first, tile by tile, every tile's bank kernels on the call's stream; then the tiles' exchanges on
@@ -1568,19 +1633,23 @@ struct fr_renderer {
             const bool strided = sp.fused_count != 0 && w0 == idx && plan.stage_valid && sp.fused_stride >= 256 && strided_sub >= 2 &&
                                  strided_sub <= 8 && fused_strided_ok;
             if (sp.feedback) {
-                launch_fused_levels(idx, n_times);
+                launch_fused_levels(idx, n_times, "feedback");
+                launch_form = "copy";
                 launch_range(sp.post_first, sp.post_count, idx, n_times);
             } else if (strided) {
+                launch_form = "strided";
                 launch_stride = sp.fused_stride;
                 launch_range(sp.fused_first, sp.fused_count, idx, n_times);
                 launch_stride = 0;
             } else if (fused) {
+                launch_form = "fused";
                 for (uint64_t done = 0; done < n_times;) {   // by frames still to do: no sum that could wrap
                     const uint64_t len = std::min<uint64_t>(fused_step, n_times - done);
                     launch_range(sp.fused_first, sp.fused_count, idx + done, len);
                     done += len;
                 }
             } else {
+                launch_form = "levels";
                 for (size_t l = 0; l < n_levels; ++l)
                     launch_range(sp.level_first[l], sp.level_first[l + 1] - sp.level_first[l], w0, w_len);
             }
@@ -2380,6 +2449,15 @@ const char *fr_plan_json(fr_renderer *r) {
                                   ",\"publishes_rows\":" + (b.launch.publishes_rows ? "true" : "false") + ",\"leaf_variant\":" + std::to_string(b.leaf_variant) +
                                   ",\"small_call\":" + std::to_string(b.launch.small_call) + ",\"pieces_log2\":" + std::to_string(b.launch.pieces_log2) +
                                   ",\"variant\":\"" + bank_variant(b.launch, b.log2_p, b.leaf_variant, b.row_flags) + "\"}";
+        }
+        r->plan_json_cache += "],\"stage_launches\":[";
+        for (size_t i = 0; i < r->stage_launches.size(); ++i) {
+            const StageLaunchNote &n = r->stage_launches[i];
+            r->plan_json_cache += std::string(i ? "," : "") + "{\"form\":\"" + n.form + "\",\"kernel\":\"" + (n.jit ? "jit_stage" : "stage_kernel") +
+                                  "\",\"programs\":" + std::to_string(n.programs) + ",\"frames\":" + std::to_string(n.frames) +
+                                  ",\"stride\":" + std::to_string(n.stride) + ",\"carry\":" + (n.carry ? "true" : "false") +
+                                  ",\"carry_only\":" + (n.carry_only ? "true" : "false") + ",\"table_inputs\":" + (n.table ? "true" : "false") +
+                                  ",\"grid_parts\":" + std::to_string(n.grid_parts) + ",\"variant\":\"" + stage_variant(n, r->plan) + "\"}";
         }
         r->plan_json_cache += "]}";
     }

@@ -82,6 +82,9 @@ struct StageJitPlan {
     std::vector<uint32_t> ptab;
     std::string source;
     uint32_t n_shapes = 0;
+    // the generated form: exactly the values of the source's #defines (fr_plan_json "stage_jit_form")
+    bool deep = false, defer = false;
+    uint32_t maxp = 0, maxld = 0, maxst = 0, blk = 1;
 };
 // Groups the programs by skeleton and writes the kernel source.  Returns false when specialisation is not worth a
 // compile: more than `max_shapes` skeletons, or (unless `force`) fewer than 4 programs per skeleton on average.

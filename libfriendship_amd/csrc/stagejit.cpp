@@ -414,9 +414,15 @@ bool plan_stage_jit(const std::vector<StageProg> &progs, const std::vector<Stage
         store_cases << "                case " << si << ": shape" << si << "_st(a, P, t, sv); break;\n";
         load_cases << "        case " << si << ": shape" << si << "_ld(a, P, t, ldn); break;\n";
     }
+    out.deep = deep;
+    out.maxld = max_nld;
+    out.maxp = (deep && max_np <= 64) ? max_np : 0u;
+    out.maxst = max_nst;
+    out.defer = defer_stores && max_nst <= 8;
+    out.blk = std::max(1u, std::min(block, std::max(1u, 32u / (max_nld + (out.defer ? max_nst + 1 : 0)))));
     std::ostringstream src;
-    src << "#pragma clang fp contract(off)\n#define FR_SPARKLE " << (sparkle ? 1 : 0) << "\n#define MAXLD " << max_nld << "\n#define MAXP " << ((deep && max_np <= 64) ? max_np : 0u) << "\n#define MAXST " << max_nst << "\n#define DEFER " << ((defer_stores && max_nst <= 8) ? 1 : 0)
-        << "\n#define BLK " << std::max(1u, std::min(block, std::max(1u, 32u / (max_nld + ((defer_stores && max_nst <= 8) ? max_nst + 1 : 0))))) << "\n" << FR_STR(FR_JIT_STAGE_ARGS_TEXT) << "\n";
+    src << "#pragma clang fp contract(off)\n#define FR_SPARKLE " << (sparkle ? 1 : 0) << "\n#define MAXLD " << out.maxld << "\n#define MAXP " << out.maxp << "\n#define MAXST " << out.maxst << "\n#define DEFER " << (out.defer ? 1 : 0)
+        << "\n#define BLK " << out.blk << "\n" << FR_STR(FR_JIT_STAGE_ARGS_TEXT) << "\n";
     std::string body = kStageSkeleton;
     auto put = [&](const std::string &tag, const std::string &text) { body.replace(body.find(tag), tag.size(), text); };
     put("SHAPE_FUNCTIONS", fns.str());
