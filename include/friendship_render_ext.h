@@ -25,6 +25,16 @@ extern "C" {
  * FR_HOST_TRACE, FR_LOWER_TRACE, FR_PLAN_TRACE, FR_LOWER_HUGEPAGES), a name given twice, a value that does not parse
  * (decimal digits, or a word the switch documents such as "force") or is out of range: FR_ERR_INVALID_ARG and no
  * renderer.  (The environment keeps its lenient reading: atoi and clamping, as always.)
+ *
+ * FR_RING_KEEP = 0 / 1 (default 0; read strictly from the environment too): kept delay lines.  A graph edit, a finished
+ * run-time compile or a call longer than any before makes the renderer re-plan; without the option the first call of the
+ * new plan re-renders the look-back window of every delay line, and a plan with feedback loops replays every frame since 0.
+ * With it, delay lines whose contents the edit cannot have changed (same lowered node, same loops, enough frames held)
+ * are kept -- moved to their new place on the device if the plan renumbers them -- and only the others are rebuilt
+ * before the call.  Results are the same bits.  fr_plan_json: "ring_keep", and per call "ring_state" {kept, rebuilt, moved,
+ * move_launches, repair_from, inert}; launches of form "repair" / "replay" in bank_launches and stage_launches.  The option
+ * does nothing ("inert" names why) under FR_SHARD_PARTIALS, with a track history that feeds delay lines, and with a
+ * bounded input history (fr_config.history_frames).
  */
 typedef struct fr_option {
     const char *name;              /* e.g. "FR_BANK_SHORT" */

@@ -139,9 +139,10 @@ inline void bank_shape(uint32_t log2_p, uint32_t n_voices, uint64_t n_times, con
 }
 
 // The launch of bank group `g` in call `c` under the renderer's options `tu`.
-inline BankPlan plan_bank(const BankLaunch &g, const BankCall &c, const BankTuning &tu) {
+// `n_voices`: the launch takes only that many of the group's voices (a run of them: engine.cpp's repair of kept delay lines).
+inline BankPlan plan_bank(const BankLaunch &g, const BankCall &c, const BankTuning &tu, uint32_t n_voices = UINT32_MAX) {
     BankPlan p;
-    const uint32_t voices = (uint32_t)g.rows.size();
+    const uint32_t voices = std::min<uint32_t>(n_voices, (uint32_t)g.rows.size());
     const uint64_t tiles = (c.n_times + 63) / 64;
     if (g.jit) {
         p.kernel = "jit_bank";

@@ -15,6 +15,7 @@
 #include <cstdlib>
 #include <chrono>
 #include <cstring>
+#include <map>
 #include <sstream>
 #include <string>
 #include <unordered_set>
@@ -138,11 +139,12 @@ struct BankLaunchNote {
     uint64_t frames;
     uint32_t log2_p, leaf_variant;       // (with row_flags: what bankplan.hpp bank_variant reads besides the plan)
     bool row_flags;
+    const char *form;                    // FR_RING_KEEP: "call", "repair" (rebuilt rings up to idx) or "replay" (a loop from 0)
 };
 
 // One stage-program launch of the last call, as fr_plan_json's "stage_launches" shows it.
 struct StageLaunchNote {
-    const char *form;                    // levels, fused, strided, feedback, copy, replay
+    const char *form;                    // levels, fused, strided, feedback, copy, replay, repair
     bool jit;                            // jit_stage (else stage_kernel)
     uint32_t programs;
     uint64_t frames, stride;
@@ -186,7 +188,7 @@ static std::string stage_variant(const StageLaunchNote &n, const Plan &p) {
     return k;
 }
 
-constexpr size_t N_OPTIONS = 29;         // per-renderer options (friendship_render_ext.h; the table below fr_renderer)
+constexpr size_t N_OPTIONS = 30;         // per-renderer options (friendship_render_ext.h; the table below fr_renderer)
 
 struct TimerClass {
     double ms = 0;
@@ -219,6 +221,15 @@ __attribute__((weak)) hipError_t launch_track_tail(const TrackTailArgs &a, hipSt
     for (uint64_t r = 0; r < a.rows; ++r)
         for (uint64_t i = 0; i < a.count; ++i)
             a.tail[r * cap + ((a.first + i) & a.mask)] = r < a.src_rows ? a.src[r * a.src_stride + a.col0 + i] : 0.0f;
+    return hipSuccess;
+}
+__attribute__((weak)) hipError_t launch_ring_move(const RingMoveArgs &a, hipStream_t) {
+    if (!ring_move_in_bounds(a)) return hipErrorInvalidValue;
+    for (uint32_t i = 0; i < a.n_desc; ++i) {
+        const RingMoveDesc &d = a.desc[i];
+        for (uint64_t t = d.first; t != d.first + d.count; ++t)
+            a.dst[(uint64_t)d.dst_row * (a.dst_mask + 1) + (t & a.dst_mask)] = a.src[(uint64_t)d.src_row * (a.src_mask + 1) + (t & a.src_mask)];
+    }
     return hipSuccess;
 }
 __attribute__((weak)) hipError_t launch_track_window(const TrackWindowArgs &a, hipStream_t) {
@@ -470,18 +481,19 @@ struct fr_renderer {
     BankTuning bank_tune;                // FR_BANK_*, FR_SHORT_*, FR_JIT_CHUNKS, FR_JIT_CHUNK_TARGET: this renderer's bank launch rule
     // A bank group's launch over `n_times` frames in this call (bankplan.hpp): the launch itself, the input store's row
     // deferral and the streamed host output all ask this, so they agree by construction.
-    BankPlan plan_bank_launch(const BankStage &bs, uint64_t n_times, bool row_flags) const {
-        return plan_bank(bs.grp, BankCall{n_times, host_pipelines, row_flags, bs.jit && bs.jit->fn_multi}, bank_tune);
+    BankPlan plan_bank_launch(const BankStage &bs, uint64_t n_times, bool row_flags, uint32_t n_voices = UINT32_MAX) const {
+        return plan_bank(bs.grp, BankCall{n_times, host_pipelines, row_flags, bs.jit && bs.jit->fn_multi}, bank_tune, n_voices);
     }
     bool jit_fma = true;                 // FR_JIT_FMA=0: generated leaves without the fused multiply-add fold (jit.hpp)
     unsigned lower_threads = 1;          // FR_LOWER_THREADS, FR_LOWER_PAR_MIN_NODES, FR_LOWER_PAR_MIN_EDIT (Lowering::set_parallel)
     size_t lower_min_nodes = 0, lower_min_edit = 0;
     std::vector<BankLaunchNote> bank_launches;   // the last call's (fr_plan_json), at most 256
     std::vector<StageLaunchNote> stage_launches; // (likewise)
-    void note_bank_launch(const BankPlan &bp, const BankStage &bs, uint64_t frames, bool row_flags) {
+    const char *bank_form = "call";      // what the bank launches being issued are for (BankLaunchNote::form)
+    void note_bank_launch(const BankPlan &bp, const BankStage &bs, uint32_t voices, uint64_t frames, bool row_flags) {
         const uint32_t partials = bs.grp.general ? bs.grp.max_leaves : 1u << bs.grp.log2_p;
         if (bank_launches.size() < 256)
-            bank_launches.push_back({bp, (uint32_t)bs.grp.rows.size(), partials, frames, bs.grp.log2_p, bank_tune.leaf_variant, row_flags});
+            bank_launches.push_back({bp, voices, partials, frames, bs.grp.log2_p, bank_tune.leaf_variant, row_flags, bank_form});
     }
     // Block streaming (fr_stream_*): one resident launch renders 64-frame blocks on a doorbell (kernels.hpp BankStreamCtl)
     bool streaming = false;
@@ -531,6 +543,276 @@ struct fr_renderer {
     TimerClass t_bank, t_pull, t_stage;
     DevBuf d_rings, d_in_table_stage;
     uint64_t ring_cap = 0;               // floats per ring (power of two)
+    // ---- kept delay lines (FR_RING_KEEP) ----------------------------------------------------------------------------
+    // What d_rings holds, per physical ring, outliving the plan: the lowering generation and the key of the function the ring
+    // holds (StagedPlan::ring_node, then ring_fb: equal keys in one generation are the same function of the same history) and
+    // the oldest frame it holds for that key; `end` is the frame after the last one every ring holds.  The first call after a
+    // re-plan keeps the rings of the new plan it finds here with enough frames for their look-back, moves them to their new
+    // rows (ring_move_kernel) and brings only the others up to idx before it runs as a steady call.
+    bool ring_keep = false;
+    struct RingEntry { uint64_t generation; std::vector<uint32_t> key; uint64_t valid_from; };
+    struct RingTable {
+        bool valid = false;
+        uint64_t end = 0, shard_epoch = 0;
+        std::vector<RingEntry> rings;
+    } ring_table;
+    struct RingState { uint32_t kept = 0, rebuilt = 0, moved = 0, move_launches = 0; uint64_t repair_from = 0; std::string inert; } ring_state;
+    bool rings_touched = false;          // the call in hand has reached execute(): its launches may have written rings
+    PinnedBuf h_ring_desc;               // the move's descriptors (the kernel reads them through the mapping)
+    hipEvent_t ev_ring_move = nullptr;   // ... free for the next move once this has passed
+    // What the repair launches (execute()): bank voices as runs [first, first + count) of a stage's voices, programs as runs
+    // of plan.sp.progs level by level, all over [from, idx); `replay`: a feedback plan's loops, from frame 0 in chunks.
+    struct RingRepair {
+        bool replay = false;
+        uint64_t from = 0;
+        struct Run { uint32_t stage, first, count; };
+        std::vector<Run> voices;
+        std::vector<std::vector<std::pair<uint32_t, uint32_t>>> levels;   // per level: (first program, count)
+        bool empty() const { return voices.empty() && levels.empty(); }
+    };
+    // Why the option does nothing for this plan ("" = it acts): everything is rebuilt as without it.
+    std::string ring_keep_inert() const {
+        const StagedPlan &sp = plan.sp;
+        if (sharded() && shard.mode == FR_SHARD_PARTIALS) return "partial-block sharding";
+        if (!sp.split.empty()) return "partial-block sharding";
+        if (!sp.track_window_slots.empty()) return "track history";
+        for (const BankStage &bs : plan.banks)
+            if (bs.grp.tracks && bs.grp.to_ring) return "track history";
+        // (A repair, like the window rebuild without the option, reads the stored inputs over the look-back; with a bounded
+        //  history those reads return 0.0 below history_floor, which only ever rises.  A ring kept from before the floor rose
+        //  holds what the full history gave, a rebuilt one what the floored history gives: the option would change bits.)
+        if (history_frames != 0) return "bounded input history";
+        if (!sp.uses_rings()) return "no delay lines";
+        return "";
+    }
+    static std::vector<uint32_t> ring_key(const StagedPlan &sp, uint32_t r) {
+        std::vector<uint32_t> key{sp.ring_node[r]};
+        if (r < sp.ring_fb.size()) key.insert(key.end(), sp.ring_fb[r].begin(), sp.ring_fb[r].end());
+        return key;
+    }
+    // build_plan: the planner numbers rings by node id, and an edit appends nodes, so the rings behind an edited node would all
+    // shift by a few rows.  Rings the table already holds get the row they are in and the new ones the rows left over (a
+    // permutation of the plan's numbering, applied before anything is uploaded or compiled): a knob turn then moves nothing.
+    void renumber_rings(StagedPlan &sp) const {
+        const uint32_t n = sp.n_rings;
+        if (!ring_keep || n == 0 || !sp.split.empty() || ring_table.rings.empty()) return;
+        const uint64_t gen = lowering.generation();
+        std::map<std::vector<uint32_t>, uint32_t> held;
+        for (uint32_t o = 0; o < ring_table.rings.size() && o < n; ++o)
+            if (ring_table.rings[o].generation == gen) held.emplace(ring_table.rings[o].key, o);
+        std::vector<uint32_t> perm(n, UINT32_MAX);
+        std::vector<uint8_t> used(n, 0);
+        for (uint32_t r = 0; r < n; ++r) {
+            auto it = held.find(ring_key(sp, r));
+            if (it != held.end() && !used[it->second]) { perm[r] = it->second; used[it->second] = 1; }
+        }
+        uint32_t free_row = 0;
+        for (uint32_t r = 0; r < n; ++r) {
+            if (perm[r] != UINT32_MAX) continue;
+            while (used[free_row]) ++free_row;
+            perm[r] = free_row;
+            used[free_row] = 1;
+        }
+        for (StageInstr &in : sp.instrs)
+            if (in.op == S_READ || in.op == S_READ_DYN || in.op == S_STORE) in.buf = perm[in.buf];
+        for (StageProg &pg : sp.progs)
+            if (pg.dst_ring < n) pg.dst_ring = perm[pg.dst_ring];
+        for (BankLaunch &bl : sp.banks)
+            if (bl.to_ring) for (uint32_t &row : bl.rows) row = perm[row];
+        for (std::vector<uint32_t> &pr : sp.prog_rings) {
+            for (uint32_t &r : pr) r = perm[r];
+            std::sort(pr.begin(), pr.end());
+        }
+        std::vector<uint32_t> node(n);
+        std::vector<uint64_t> lb(n);
+        std::vector<std::vector<uint32_t>> fb(sp.ring_fb.size());
+        for (uint32_t r = 0; r < n; ++r) {
+            node[perm[r]] = sp.ring_node[r];
+            lb[perm[r]] = sp.ring_lookback[r];
+            if (r < sp.ring_fb.size()) fb[perm[r]] = std::move(sp.ring_fb[r]);
+        }
+        sp.ring_node = std::move(node);
+        sp.ring_lookback = std::move(lb);
+        sp.ring_fb = std::move(fb);
+    }
+    static bool ring_in(const std::vector<uint8_t> &set, const std::vector<uint32_t> &rings) {
+        for (uint32_t r : rings) if (set[r]) return true;
+        return false;
+    }
+    static void add_run(std::vector<std::pair<uint32_t, uint32_t>> &runs, uint32_t i) {
+        if (!runs.empty() && runs.back().first + runs.back().second == i) ++runs.back().second;
+        else runs.push_back({i, 1});
+    }
+    // The first call of a plan whose rings are not known to be current (a new plan, a longer call than any before, a seek, a
+    // failed call): which rings of the table serve the new plan, the move, and what must be launched to rebuild the rest.
+    // Leaves d_rings / ring_cap as the call needs them and the table describing the new plan's rings as they will be at idx.
+    RingRepair keep_rings(uint64_t cap_needed, uint64_t idx, bool table_was_valid, hipStream_t st) {
+        const StagedPlan &sp = plan.sp;
+        const uint32_t n = sp.n_rings;
+        const uint64_t gen = lowering.generation();
+        const bool live = table_was_valid && ring_table.end == idx && ring_table.shard_epoch == shard_epoch && d_rings.p && ring_cap;
+        std::vector<std::vector<uint32_t>> keys(n);
+        for (uint32_t r = 0; r < n; ++r) keys[r] = ring_key(sp, r);
+        std::vector<int64_t> src(n, -1);
+        if (live) {
+            std::map<std::vector<uint32_t>, uint32_t> held;
+            for (uint32_t o = 0; o < ring_table.rings.size(); ++o)
+                if (ring_table.rings[o].generation == gen) held.emplace(ring_table.rings[o].key, o);
+            for (uint32_t r = 0; r < n; ++r) {
+                auto it = held.find(keys[r]);
+                const uint64_t lb = sp.ring_lookback[r];
+                if (it != held.end() && ring_table.rings[it->second].valid_from <= (idx > lb ? idx - lb : 0)) src[r] = it->second;
+            }
+        }
+        uint32_t kept = 0;
+        bool permuted = false;
+        for (uint32_t r = 0; r < n; ++r)
+            if (src[r] >= 0) { ++kept; permuted = permuted || src[r] != (int64_t)r; }
+        const uint64_t new_cap = std::max(ring_cap, cap_needed);
+        const size_t new_bytes = (size_t)n * new_cap * sizeof(float);
+        std::vector<RingEntry> now(n);
+        for (uint32_t r = 0; r < n; ++r) now[r] = RingEntry{gen, std::move(keys[r]), src[r] >= 0 ? ring_table.rings[(size_t)src[r]].valid_from : UINT64_MAX};
+        ring_state.kept = kept;
+        ring_state.rebuilt = n - kept;
+        if (kept && (permuted || new_cap != ring_cap || new_bytes > d_rings.bytes)) {
+            // rows permute and capacities differ: into a second allocation, the old one retired behind the stream
+            DevBuf nb;
+            nb.ensure(new_bytes + new_bytes / 4 + 8 * new_cap * sizeof(float));   // (rows to spare: the next note-on moves nothing)
+            // (the one host wait of the path, on an event and not on the device: the previous move -- at least one call ago,
+            //  moves are rare -- must have read its descriptors before the pinned buffer is written again; normally long past)
+            if (ev_ring_move) HIP_CHECK(hipEventSynchronize(ev_ring_move));
+            else HIP_CHECK(hipEventCreateWithFlags(&ev_ring_move, hipEventDisableTiming));
+            h_ring_desc.ensure((size_t)kept * sizeof(RingMoveDesc));
+            RingMoveDesc *desc = h_ring_desc.as<RingMoveDesc>();
+            const uint64_t reach = std::min(ring_cap, new_cap);
+            uint32_t nd = 0;
+            for (uint32_t r = 0; r < n; ++r) {
+                if (src[r] < 0) continue;
+                const uint64_t first = std::max(now[r].valid_from, idx > reach ? idx - reach : 0);
+                now[r].valid_from = first;
+                if (first < idx) desc[nd++] = RingMoveDesc{(uint32_t)src[r], r, first, idx - first};
+            }
+            RingMoveArgs a{};
+            a.src = d_rings.as<float>();
+            a.dst = nb.as<float>();
+            a.src_mask = ring_cap - 1;
+            a.dst_mask = new_cap - 1;
+            a.src_rows = (uint32_t)std::min<uint64_t>(ring_table.rings.size(), d_rings.bytes / (ring_cap * sizeof(float)));
+            a.dst_rows = n;
+            a.desc = h_ring_desc.as_dev<RingMoveDesc>();
+            a.host_desc = desc;
+            a.n_desc = nd;
+            if (nd) {
+                Scope sc(this, &t_stage, st);
+                HIP_CHECK(launch_ring_move(a, st));
+                sc.done();
+                HIP_CHECK(hipEventRecord(ev_ring_move, st));
+                ring_state.move_launches = 1;
+            }
+            ring_state.moved = nd;
+            bury(std::move(d_rings), st);
+            d_rings = std::move(nb);
+        } else if (new_bytes > d_rings.bytes) {
+            d_rings.ensure(new_bytes + new_bytes / 4 + 8 * new_cap * sizeof(float));   // (nothing kept: nothing to carry over)
+        }
+        ring_cap = new_cap;
+
+        // what to rebuild
+        RingRepair rp;
+        rp.from = idx;
+        std::vector<uint8_t> need(n, 0);
+        uint64_t deepest = 0;
+        bool any = false;
+        for (uint32_t r = 0; r < n; ++r) {
+            if (src[r] >= 0) continue;
+            now[r].valid_from = idx;                 // (until something below writes older frames of it)
+            if (sp.ring_lookback[r] == 0) continue;  // read at its own frame only: the call itself fills it
+            need[r] = 1;
+            any = true;
+            deepest = std::max(deepest, sp.ring_lookback[r]);
+        }
+        if (idx == 0) {                              // nothing before frame 0: every ring is current, and stays valid from 0
+            for (RingEntry &e : now) e.valid_from = 0;
+            any = false;
+        }
+        std::vector<uint8_t> bank_ring(n, 0);
+        for (const BankStage &bs : plan.banks)
+            if (bs.grp.to_ring) for (uint32_t row : bs.grp.rows) bank_ring[row] = 1;
+        auto add_voices = [&](const std::vector<uint8_t> &want) {
+            for (uint32_t b = 0; b < plan.banks.size(); ++b) {
+                const BankLaunch &g = plan.banks[b].grp;
+                if (!g.to_ring) continue;
+                std::vector<std::pair<uint32_t, uint32_t>> runs;
+                for (uint32_t v = 0; v < g.rows.size(); ++v) if (want[g.rows[v]]) add_run(runs, v);
+                // (the schedule kernel's voices index shared tables: all of them, rewriting the kept ones with what they hold)
+                if (g.general && !runs.empty()) runs.assign(1, {0u, (uint32_t)g.rows.size()});
+                for (auto &run : runs) rp.voices.push_back({b, run.first, run.second});
+            }
+        };
+        if (any && !sp.feedback) {
+            rp.from = idx - std::min(idx, deepest);
+            add_voices(need);
+            // the oldest frame each written ring is right from: a bank's from the window's start (it reads inputs only), a
+            // program's as far as everything it reads reaches (frames before 0 are zeros by definition)
+            for (uint32_t r = 0; r < n; ++r) if (need[r] && bank_ring[r]) now[r].valid_from = rp.from;
+            const size_t n_levels = sp.level_first.empty() ? 0 : sp.level_first.size() - 1;
+            for (size_t l = 0; l < n_levels; ++l) {
+                std::vector<std::pair<uint32_t, uint32_t>> runs;
+                for (uint32_t i = sp.level_first[l]; i < sp.level_first[l + 1]; ++i) {
+                    if (!ring_in(need, sp.prog_rings[i])) continue;
+                    add_run(runs, i);
+                    const StageProg &pg = sp.progs[i];
+                    uint64_t from = rp.from;
+                    for (uint32_t k = 0; k < pg.n_instr; ++k) {
+                        const StageInstr &in = sp.instrs[pg.first_instr + k];
+                        if (in.op != S_READ && in.op != S_READ_DYN) continue;
+                        const uint64_t vf = now[in.buf].valid_from;
+                        if (vf != 0) from = std::max(from, vf + in.d_lo);
+                    }
+                    for (uint32_t r : sp.prog_rings[i]) now[r].valid_from = std::min(from, idx);
+                }
+                if (!runs.empty()) rp.levels.push_back(std::move(runs));
+            }
+        } else if (any) {
+            // Feedback: a loop's state at idx is a function of every frame since 0.  The programs that store a ring to rebuild
+            // are replayed from 0, together with everything upstream they read while replaying (kept rings hold their last
+            // frames only; the replay rewrites them and they end where they were).
+            rp.replay = true;
+            rp.from = 0;
+            const uint32_t f0 = sp.fused_first, f1 = sp.fused_first + sp.fused_count;
+            std::vector<int64_t> stored_by(n, -1);
+            for (uint32_t i = f0; i < f1; ++i) for (uint32_t r : sp.prog_rings[i]) stored_by[r] = i;
+            std::vector<uint8_t> in_set(sp.progs.size(), 0), voice_ring(n, 0);
+            std::vector<uint32_t> work;
+            for (uint32_t i = f0; i < f1; ++i) if (ring_in(need, sp.prog_rings[i])) { in_set[i] = 1; work.push_back(i); }
+            for (uint32_t r = 0; r < n; ++r) if (need[r] && bank_ring[r]) voice_ring[r] = 1;
+            while (!work.empty()) {
+                const StageProg &pg = sp.progs[work.back()];
+                work.pop_back();
+                for (uint32_t k = 0; k < pg.n_instr; ++k) {
+                    const StageInstr &in = sp.instrs[pg.first_instr + k];
+                    if (in.op != S_READ && in.op != S_READ_DYN) continue;
+                    if (bank_ring[in.buf]) voice_ring[in.buf] = 1;
+                    else if (stored_by[in.buf] >= 0 && !in_set[(size_t)stored_by[in.buf]]) { in_set[(size_t)stored_by[in.buf]] = 1; work.push_back((uint32_t)stored_by[in.buf]); }
+                }
+            }
+            add_voices(voice_ring);
+            for (uint32_t r = 0; r < n; ++r) if (voice_ring[r]) now[r].valid_from = 0;
+            for (size_t l = 0; l + 1 < sp.fused_level_first.size(); ++l) {
+                std::vector<std::pair<uint32_t, uint32_t>> runs;
+                for (uint32_t i = f0 + sp.fused_level_first[l]; i < f0 + sp.fused_level_first[l + 1]; ++i) {
+                    if (!in_set[i]) continue;
+                    add_run(runs, i);
+                    for (uint32_t r : sp.prog_rings[i]) now[r].valid_from = 0;
+                }
+                if (!runs.empty()) rp.levels.push_back(std::move(runs));
+            }
+        }
+        ring_state.repair_from = rp.from;
+        ring_table.rings = std::move(now);
+        ring_table.shard_epoch = shard_epoch;
+        return rp;
+    }
     std::vector<hipEvent_t> event_pool;
     std::string last_error;
     std::string jit_error;
@@ -544,6 +826,7 @@ struct fr_renderer {
         for (hipEvent_t e : event_pool) (void)hipEventDestroy(e);
         for (Retired &g : graveyard) (void)hipEventDestroy(g.ev);
         if (ev_last) (void)hipEventDestroy(ev_last);
+        if (ev_ring_move) (void)hipEventDestroy(ev_ring_move);
         for (hipEvent_t e : x_events) (void)hipEventDestroy(e);
         if (xstream) (void)hipStreamDestroy(xstream);
         // ranges the host registered and never unregistered: the page-lock and the device mapping must not outlive the
@@ -779,6 +1062,9 @@ struct fr_renderer {
     std::vector<Deferred> deferred;
     // Will execute() render exactly [idx, idx + n_times) for the staged part (steady state), or rebuild a look-back
     // window first?  Same conditions as execute() uses (ring capacity, contiguity with what the rings hold).
+    // (FR_RING_KEEP: conservative.  The first call of a new plan answers "not steady" here even when execute() then keeps every
+    //  ring and runs the call in its steady form: whether it repairs is known only once the rings are matched, and a repair
+    //  reads the stored history.  The row is then stored ahead and nothing is deferred -- one row copy, once per re-plan.)
     bool steady_call(uint64_t idx, uint64_t n_times) const {
         const StagedPlan &sp = plan.sp;
         if (!sp.uses_rings()) return true;
@@ -829,6 +1115,7 @@ struct fr_renderer {
     void rollback_store(const StoreSnapshot &sn) {
         deferred.clear();
         plan.stage_valid = false;   // rings may hold part of the failed call's window
+        if (rings_touched) ring_table.valid = false;   // (a call refused before it launched anything left the rings as they were)
         counters_dirty = true;      // a launch of the failed call may have stopped half-way through its tickets / row counts
         if (sn.seeked) {
             for (InSlot &s : slots) { s.base = sn.idx; s.len = sn.idx; }
@@ -854,6 +1141,7 @@ struct fr_renderer {
         deferred.clear();
         track_dev.clear();
         reap();
+        rings_touched = false;
         call_idx = idx;
         call_tracks = nullptr;
         call_track_stride = call_track_rows = 0;
@@ -1017,6 +1305,7 @@ struct fr_renderer {
         const ObservedInputs obs = observed_inputs(st);
         const ObservedInputs *observed = delay_observed ? &obs : nullptr;
         p.sp = plan_stages(fg, mode == FR_MODE_AUTO, mode != FR_MODE_PULL, 20, use_jit, allow_template, matcher.get(), shard_spec, track_from, observed, track_history);
+        renumber_rings(p.sp);
         std::vector<std::shared_ptr<JitKernel>> jits(p.sp.banks.size());
         p.jit_epoch = jit_cache.epoch();   // (read first: a compile finishing from here on makes this plan stale)
         if (use_jit) {
@@ -1043,6 +1332,7 @@ struct fr_renderer {
             }
             if (without) {
                 p.sp = plan_stages(fg, true, true, 20, false, true, nullptr, shard_spec, track_from, observed, track_history);
+                renumber_rings(p.sp);
                 jits.assign(p.sp.banks.size(), nullptr);
             }
         }
@@ -1157,7 +1447,7 @@ struct fr_renderer {
            << ",\"delay_observed\":" << (delay_observed ? "true" : "false") << ",\"delay_observed_max\":" << delay_observed_max
            << ",\"observed_delays\":" << p.sp.observed.size() << ",\"observed_lookback\":" << p.sp.observed_lookback
            << ",\"observed_refused\":" << p.sp.observed_refused
-           << ",\"history_frames\":" << history_frames
+           << ",\"history_frames\":" << history_frames << ",\"ring_keep\":" << (ring_keep ? "true" : "false")
            << ",\"track_history\":" << track_history << ",\"track_lookback\":" << p.sp.track_lookback
            << ",\"track_window_slots\":" << p.sp.track_window_slots.size()
            << ",\"jit_pending\":" << (p.jit_pending ? "true" : "false") << ",\"jit_kernels_compiled\":" << jit_cache.compiled() << ",\"jit_compile_ms\":" << jit_cache.compile_ms() << ",\"jit_disk_hits\":" << jit_cache.disk_hits()
@@ -1263,6 +1553,7 @@ struct fr_renderer {
         bank_launches.clear();
         stage_launches.clear();
         ensure_plan(n_slots, st);
+        rings_touched = true;
         if (n_slots == 0 || n_times == 0) {   // (nothing to render: the track history still moves on as the reference's inputs do)
             prepare_tracks(n_times, idx, st);
             append_tracks(n_times, idx, st);
@@ -1274,6 +1565,11 @@ struct fr_renderer {
         // Window of the staged part.  Contiguous with what the rings already hold: just this call's frames.
         // Otherwise (first call, seek, graph edit, larger call): rebuild the look-back from the input history.
         uint64_t w0 = idx;
+        bool rings_current = false;          // the rings hold everything before idx that this call reads
+        ring_state = RingState{};
+        if (ring_keep) ring_state.inert = ring_keep_inert();
+        const bool keep_on = ring_keep && ring_state.inert.empty();
+        RingRepair repair;
         // Feedback plans (stage.hpp StagedPlan::feedback): no window bounds a loop's look-back, so rings that are not current
         // are brought up to date by replaying every frame from 0 in chunks -- the ring-bound banks and the fused programs over
         // [c0, c0 + len), nothing written to the output -- before the call's own frames run in steady-state form.
@@ -1285,19 +1581,40 @@ struct fr_renderer {
             uint64_t need = sp.lmax + std::max<uint64_t>(n_times, sp.feedback ? FB_CHUNK : 0);
             uint64_t cap = 1024;
             while (cap < need) cap <<= 1;
-            if (cap > ring_cap) {
-                d_rings.ensure((size_t)sp.n_rings * cap * sizeof(float));
-                ring_cap = cap;
-                plan.stage_valid = false;
-            } else if ((size_t)sp.n_rings * ring_cap * sizeof(float) > d_rings.bytes) {
-                d_rings.ensure((size_t)sp.n_rings * ring_cap * sizeof(float));
-                plan.stage_valid = false;
+            if (keep_on) {
+                // (FR_RING_KEEP: the rings this plan finds in the table stay, the others are brought up to idx by the repair
+                //  below, and the call itself always runs in its steady form)
+                const bool table_was_valid = ring_table.valid;
+                ring_table.valid = false;            // (until the call is through: a failure leaves nothing to keep)
+                const bool fits = cap <= ring_cap && (size_t)sp.n_rings * ring_cap * sizeof(float) <= d_rings.bytes;
+                if (plan.stage_valid && plan.stage_end == idx && fits && table_was_valid && ring_table.end == idx &&
+                    ring_table.rings.size() == sp.n_rings) {
+                    ring_state.kept = sp.n_rings;
+                    ring_state.repair_from = idx;
+                } else {
+                    repair = keep_rings(cap, idx, table_was_valid, st);
+                }
+                rings_current = true;
+            } else {
+                ring_table.valid = false;
+                if (cap > ring_cap) {
+                    d_rings.ensure((size_t)sp.n_rings * cap * sizeof(float));
+                    ring_cap = cap;
+                    plan.stage_valid = false;
+                } else if ((size_t)sp.n_rings * ring_cap * sizeof(float) > d_rings.bytes) {
+                    d_rings.ensure((size_t)sp.n_rings * ring_cap * sizeof(float));
+                    plan.stage_valid = false;
+                }
+                rings_current = plan.stage_valid && plan.stage_end == idx;
+                if (ring_keep) (rings_current ? ring_state.kept : ring_state.rebuilt) = sp.n_rings;
+                if (!rings_current) w0 = idx > sp.lmax ? idx - sp.lmax : 0;
+                if (sp.feedback) w0 = idx;   // (the replay below has brought the rings to idx by the time this window runs)
             }
-            if (!(plan.stage_valid && plan.stage_end == idx)) w0 = idx > sp.lmax ? idx - sp.lmax : 0;
-            if (sp.feedback) w0 = idx;   // (the replay below has brought the rings to idx by the time this window runs)
         }
         // (decided AFTER the rings may have been re-allocated above: a longer call than any before loses what they held)
-        const bool fb_replay = sp.feedback && !(plan.stage_valid && plan.stage_end == idx) && idx != 0;
+        const bool fb_replay = sp.feedback && !keep_on && !rings_current && idx != 0;
+        if (repair.replay && idx > FB_MAX_REPLAY)
+            throw Error(FR_ERR_UNSUPPORTED, "a feedback loop's state at frame " + std::to_string(idx) + " would take replaying more than 2^28 frames");
         if (fb_replay && idx > FB_MAX_REPLAY)
             throw Error(FR_ERR_UNSUPPORTED, "a feedback loop's state at frame " + std::to_string(idx) + " would take replaying more than 2^28 frames");
         const uint64_t w_len = idx + n_times - w0;
@@ -1333,11 +1650,16 @@ struct fr_renderer {
         // `trk`: where a voice that reads tracks finds them for this window (a span of the track history's ring), instead of the
         // call's own matrix
         struct TrackSrc { const float *p; uint64_t stride; uint32_t limit; };
-        auto launch_bank_part = [&](BankStage &bs, uint64_t b0, uint64_t blen, int64_t tile_off, const TrackSrc *trk) {
+        // `v0`, `nv`: a run of the stage's voices (a repair renders only the voices whose rings it rebuilds; parameters and rows are
+        // voice-major, so a run is the same launch at offset pointers)
+        auto launch_bank_part = [&](BankStage &bs, uint64_t b0, uint64_t blen, int64_t tile_off, const TrackSrc *trk, uint32_t v0 = 0, uint32_t nv = UINT32_MAX) {
             const bool ring = bs.grp.to_ring, ws = bs.grp.to_ws;
-            const BankPlan bp = plan_bank_launch(bs, blen, flag_out.host_flags != nullptr);
+            const bool whole = v0 == 0 && nv >= bs.grp.rows.size();
+            if (whole) nv = (uint32_t)bs.grp.rows.size();
+            else if (bs.grp.general || (uint64_t)v0 + nv > bs.grp.rows.size()) throw Error(FR_ERR_DEVICE, "internal: a run of voices the bank stage cannot launch");
+            const BankPlan bp = plan_bank_launch(bs, blen, flag_out.host_flags != nullptr, nv);   // (the one rule, asked about the run's voices)
             BankArgs a{};
-            a.params = bs.d_params.as<float2>();
+            a.params = bs.d_params.as<float2>() + ((size_t)v0 << bs.grp.log2_p);
             input_window(bs.grp.input_slot, b0, blen, a.time, a.time_skip, a.time_valid);   // time-slot history for the window
             if (tile_off < 0 && b0 == idx && blen == n_times)   // (direct output, or a ring in steady state)
                 for (Deferred &d : deferred)
@@ -1358,7 +1680,7 @@ struct fr_renderer {
                         tile_slots.insert(d.slot);
                         tile_appended.insert(d.slot);
                     }
-            a.rows = bs.d_rows.as<uint32_t>();
+            a.rows = bs.d_rows.as<uint32_t>() + v0;
             if (ring) {
                 a.out = d_rings.as<float>();
                 a.out_stride = ring_cap;
@@ -1371,13 +1693,13 @@ struct fr_renderer {
                 a.out = d_dst;
                 a.out_stride = n_times;
             }
-            a.n_voices = (uint32_t)bs.grp.rows.size();
+            a.n_voices = nv;
             a.log2_p = bs.grp.log2_p;
             a.n_times = blen;
             a.fast_ok = bs.grp.fast_ok ? 1u : 0u;
             if (bs.grp.jit) {
                 JitBankArgs j{};
-                j.params = bs.d_params.as<float>();
+                j.params = bs.d_params.as<float>() + ((size_t)v0 << bs.grp.log2_p) * bs.grp.k;
                 for (size_t i = 0; i < bs.grp.shape.input_slots.size(); ++i)   // every input row over the same window
                     input_window(bs.grp.shape.input_slots[i], b0, blen, j.in[i], j.in_skip[i], j.in_valid[i]);
                 j.out = a.out;
@@ -1417,7 +1739,7 @@ struct fr_renderer {
                     j.track_stride = call_track_stride;
                     j.track_limit = (uint32_t)std::min<uint64_t>((uint64_t)track_from + call_track_rows, 0xFFFFFFFFull);
                 }
-                note_bank_launch(bp, bs, blen, flag_out.host_flags != nullptr);
+                note_bank_launch(bp, bs, nv, blen, flag_out.host_flags != nullptr);
                 Scope sc(this, &t_bank, st);
                 HIP_CHECK(launch_jit_bank(*bs.jit, j, st));
                 if (bp.pieces_log2) {
@@ -1439,7 +1761,7 @@ struct fr_renderer {
                 a.groups = bs.d_groups.as<uint32_t>();
                 a.group_off = bs.d_group_off.as<uint32_t>();
                 a.hist_dst = nullptr;   // (the schedule kernel does not append history)
-                note_bank_launch(bp, bs, blen, flag_out.host_flags != nullptr);
+                note_bank_launch(bp, bs, nv, blen, flag_out.host_flags != nullptr);
                 Scope sc(this, &t_bank, st);
                 HIP_CHECK(launch_gbank(a, st));
                 sc.done();
@@ -1471,7 +1793,7 @@ struct fr_renderer {
                     a.tickets = d_tickets.as<uint32_t>();
                 }
             }
-            note_bank_launch(bp, bs, blen, flag_out.host_flags != nullptr);
+            note_bank_launch(bp, bs, nv, blen, flag_out.host_flags != nullptr);
             Scope sc(this, &t_bank, st);
             HIP_CHECK(launch_bank(a, st));
             sc.done();
@@ -1566,6 +1888,23 @@ struct fr_renderer {
                 launch_range(sp.fused_first + sp.fused_level_first[l], sp.fused_level_first[l + 1] - sp.fused_level_first[l], s0, slen);
             launch_stride = 0;
         };
+        if (!repair.empty()) {
+            // Kept rings (FR_RING_KEEP): the rings to rebuild are brought up to idx -- their voices, then their programs level by
+            // level, nothing written to the output -- over the look-back window, or for a feedback plan's loops from frame 0
+            fill_tab();
+            bank_form = repair.replay ? "replay" : "repair";
+            struct FormReset { const char *&f; ~FormReset() { f = "call"; } } form_reset{bank_form};
+            for (uint64_t c0 = repair.from; c0 < idx;) {
+                const uint64_t len = repair.replay ? std::min<uint64_t>(FB_CHUNK, idx - c0) : idx - c0;
+                for (const RingRepair::Run &run : repair.voices) launch_bank_part(plan.banks[run.stage], c0, len, -1, nullptr, run.first, run.count);
+                launch_form = bank_form;
+                launch_stride = repair.replay ? sp.fused_stride : 0;
+                for (const auto &level : repair.levels)
+                    for (const auto &run : level) launch_range(run.first, run.second, c0, len);
+                launch_stride = 0;
+                c0 += len;
+            }
+        }
         if (fb_replay) {
             fill_tab();
             for (uint64_t c0 = 0; c0 < idx; c0 += FB_CHUNK) {
@@ -1624,13 +1963,13 @@ struct fr_renderer {
             const size_t n_levels = sp.level_first.size() - 1;
             const uint64_t fused_step = std::max<uint64_t>(sp.fused_max_frames, 1);
             const uint64_t n_sub = sp.fused_count ? (n_times - 1) / fused_step + 1 : 0;   // (n_times > 0 here; no overflow)
-            const bool fused = sp.fused_count != 0 && w0 == idx && plan.stage_valid && n_sub < n_levels;
+            const bool fused = sp.fused_count != 0 && w0 == idx && rings_current && n_sub < n_levels;
             // ... or ONE launch whose threads stride through the sub-windows themselves, when every delayed read of a program ring
             // reaches back a multiple of fused_stride frames into a ring its own program stores (the delay chains of an effects
             // patch: 2400, 4800, 7200 ...): a thread then reads only what it stored itself.  Worth it for a handful of strides
             // (each one is a dependent round trip to memory inside the launch; a launch boundary costs ~5 us at this size).
             const uint64_t strided_sub = sp.fused_stride ? (n_times - 1) / sp.fused_stride + 1 : 0;
-            const bool strided = sp.fused_count != 0 && w0 == idx && plan.stage_valid && sp.fused_stride >= 256 && strided_sub >= 2 &&
+            const bool strided = sp.fused_count != 0 && w0 == idx && rings_current && sp.fused_stride >= 256 && strided_sub >= 2 &&
                                  strided_sub <= 8 && fused_strided_ok;
             if (sp.feedback) {
                 launch_fused_levels(idx, n_times, "feedback");
@@ -1657,6 +1996,12 @@ struct fr_renderer {
         if (sp.uses_rings()) {
             plan.stage_valid = true;
             plan.stage_end = idx + n_times;
+            if (keep_on) {                   // the call's frames are in; the oldest ones of a full ring are gone
+                ring_table.end = idx + n_times;
+                const uint64_t oldest = ring_table.end > ring_cap ? ring_table.end - ring_cap : 0;
+                for (RingEntry &e : ring_table.rings) e.valid_from = std::max(e.valid_from, oldest);
+                ring_table.valid = true;
+            }
         }
         if (!plan.pull_rows.empty()) run_pull(d_dst, n_slots, n_times, idx, st);
         append_tracks(n_times, idx, st);
@@ -1764,6 +2109,7 @@ int64_t env_long(const char *e) { return std::atoll(e); }
 int64_t env_clamp(const char *e, int lo, int hi) { return std::min(hi, std::max(lo, std::atoi(e))); }
 constexpr int64_t ENV_REFUSED = INT64_MIN;   // an `env` reading that makes create fail (resolve_options)
 int64_t env_strict_track_history(const char *e);
+int64_t env_strict_ring_keep(const char *e);
 bool parse_option(const Knob &k, const char *s, int64_t &v);
 
 const Knob kKnobs[] = {
@@ -1829,15 +2175,20 @@ const Knob kKnobs[] = {
          while (cap < r.track_history) cap <<= 1;
          r.tail_cap = v ? cap : 0;
      }, LISTED_WHEN_SET},
+    // Kept delay lines: a re-plan keeps the rings an edit cannot have changed (fr_plan_json: ring_keep, ring_state).  Strict
+    // like FR_TRACK_HISTORY, and listed once set.
+    {"FR_RING_KEEP", 0, 0, 1, 0, nullptr, 0, env_strict_ring_keep, [](fr_renderer &r, int64_t v, bool) { r.ring_keep = v != 0; }, LISTED_WHEN_SET},
 };
 static_assert(sizeof kKnobs / sizeof kKnobs[0] == N_OPTIONS, "N_OPTIONS counts the rows of kKnobs");
 
-int64_t env_strict_track_history(const char *e) {
+static int64_t env_strict(const char *name, const char *e) {
     int64_t v = 0;
     for (const Knob &k : kKnobs)
-        if (std::strcmp(k.name, "FR_TRACK_HISTORY") == 0) return parse_option(k, e, v) ? v : ENV_REFUSED;
+        if (std::strcmp(k.name, name) == 0) return parse_option(k, e, v) ? v : ENV_REFUSED;
     return ENV_REFUSED;
 }
+int64_t env_strict_track_history(const char *e) { return env_strict("FR_TRACK_HISTORY", e); }
+int64_t env_strict_ring_keep(const char *e) { return env_strict("FR_RING_KEEP", e); }
 
 bool parse_option(const Knob &k, const char *s, int64_t &v) {
     if (k.word && std::strcmp(s, k.word) == 0) {
@@ -2438,6 +2789,12 @@ const char *fr_plan_json(fr_renderer *r) {
         r->plan_json_cache += ",\"lookback_growths\":" + std::to_string(r->lookback_growths) + ",\"range_launches\":" + std::to_string(r->range_launches);
         r->plan_json_cache += ",\"track_tail_bytes\":" + std::to_string((uint64_t)r->tail_rows * r->tail_cap * sizeof(float)) +
                               ",\"track_tail_launches\":" + std::to_string(r->tail_launches);
+        if (r->ring_keep) {
+            const fr_renderer::RingState &rs = r->ring_state;
+            r->plan_json_cache += ",\"ring_state\":{\"kept\":" + std::to_string(rs.kept) + ",\"rebuilt\":" + std::to_string(rs.rebuilt) +
+                                  ",\"moved\":" + std::to_string(rs.moved) + ",\"move_launches\":" + std::to_string(rs.move_launches) +
+                                  ",\"repair_from\":" + std::to_string(rs.repair_from) + ",\"inert\":\"" + rs.inert + "\"}";
+        }
         r->plan_json_cache += ",\"exchange_stats\":{\"calls\":" + std::to_string(r->exchange_calls) + ",\"tiles\":" + std::to_string(r->exchange_tiles) +
                               ",\"bytes_sent\":" + std::to_string(r->exchange_bytes) + "},\"bank_launches\":[";
         for (size_t i = 0; i < r->bank_launches.size(); ++i) {
@@ -2448,7 +2805,8 @@ const char *fr_plan_json(fr_renderer *r) {
                                   ",\"frames_per_lane\":" + std::to_string(b.launch.frames_per_lane) + ",\"voices_per_wave\":" + std::to_string(b.launch.voices_per_wave) +
                                   ",\"publishes_rows\":" + (b.launch.publishes_rows ? "true" : "false") + ",\"leaf_variant\":" + std::to_string(b.leaf_variant) +
                                   ",\"small_call\":" + std::to_string(b.launch.small_call) + ",\"pieces_log2\":" + std::to_string(b.launch.pieces_log2) +
-                                  ",\"variant\":\"" + bank_variant(b.launch, b.log2_p, b.leaf_variant, b.row_flags) + "\"}";
+                                  ",\"variant\":\"" + bank_variant(b.launch, b.log2_p, b.leaf_variant, b.row_flags) + "\"" +
+                                  (r->ring_keep ? std::string(",\"form\":\"") + b.form + "\"" : std::string()) + "}";
         }
         r->plan_json_cache += "],\"stage_launches\":[";
         for (size_t i = 0; i < r->stage_launches.size(); ++i) {

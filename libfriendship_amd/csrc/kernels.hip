@@ -1645,4 +1645,33 @@ hipError_t launch_track_window(const TrackWindowArgs &a, hipStream_t s) {
     return hipGetLastError();
 }
 
+// Kept delay lines (kernels.hpp RingMoveArgs): one wave per RING_MOVE_SEG-aligned segment of a descriptor's frames, lanes
+// over consecutive frames (track_span: 16-byte accesses between equally aligned spans, heads and tails element by element).
+__global__ __launch_bounds__(256) void ring_move_kernel(RingMoveArgs a) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t wave = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6), waves = (uint64_t)gridDim.x * 4;
+    for (uint32_t di = blockIdx.y; di < a.n_desc; di += gridDim.y) {
+        const RingMoveDesc d = a.desc[di];
+        const uint64_t end = d.first + d.count;
+        const float *src = a.src + (uint64_t)d.src_row * (a.src_mask + 1);
+        float *dst = a.dst + (uint64_t)d.dst_row * (a.dst_mask + 1);
+        for (uint64_t s0 = (d.first & ~(RING_MOVE_SEG - 1)) + wave * RING_MOVE_SEG; s0 < end; s0 += waves * RING_MOVE_SEG) {
+            const uint64_t t0 = s0 > d.first ? s0 : d.first, t1 = s0 + RING_MOVE_SEG < end ? s0 + RING_MOVE_SEG : end;
+            track_span(dst + (t0 & a.dst_mask), src + (t0 & a.src_mask), t1 - t0, lane);
+        }
+    }
+}
+
+hipError_t launch_ring_move(const RingMoveArgs &a, hipStream_t s) {
+    if (a.n_desc == 0) return hipSuccess;
+    if (!ring_move_in_bounds(a)) return hipErrorInvalidValue;
+    uint64_t longest = 0;
+    for (uint32_t i = 0; i < a.n_desc; ++i) longest = std::max(longest, a.host_desc[i].count);
+    if (longest == 0) return hipSuccess;
+    const uint64_t segs = longest / RING_MOVE_SEG + 2;   // (a span that starts inside a segment touches one more)
+    const uint32_t bx = (uint32_t)std::min<uint64_t>((segs + 3) / 4, 64);
+    hipLaunchKernelGGL(ring_move_kernel, dim3(bx, std::min<uint32_t>(a.n_desc, 65535u)), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
 }  // namespace fr

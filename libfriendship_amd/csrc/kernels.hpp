@@ -273,4 +273,36 @@ struct TrackWindowArgs {
 };
 hipError_t launch_track_window(const TrackWindowArgs &a, hipStream_t s);
 
+// Kept delay lines (FR_RING_KEEP): after a re-plan the rings whose contents are still right go from the old allocation
+// (rows of src_mask + 1 floats, frame f at f & src_mask) to the row and capacity the new plan gives them in a second
+// allocation: a streaming gather over a device array of descriptors.  A wave takes one segment of a descriptor's frames, cut
+// at multiples of RING_MOVE_SEG: capacities are powers of two of at least that, so a segment is contiguous on both sides
+// (no ring wraps inside one) and source and destination are equally aligned -- 16-byte accesses with element-wise heads
+// and tails.  `host_desc`: the same descriptors in host memory; the launch bounds every one of them before it starts.
+constexpr uint64_t RING_MOVE_SEG = 1024;
+struct RingMoveDesc {
+    uint32_t src_row, dst_row;
+    uint64_t first, count;     // absolute frames [first, first + count)
+};
+struct RingMoveArgs {
+    const float *src;
+    float *dst;
+    uint64_t src_mask, dst_mask;
+    uint32_t src_rows, dst_rows;       // rows of the two allocations
+    const RingMoveDesc *desc;          // as the device addresses them
+    const RingMoveDesc *host_desc;
+    uint32_t n_desc;
+};
+inline bool ring_move_in_bounds(const RingMoveArgs &a) {
+    if (!a.src || !a.dst || !a.desc || !a.host_desc) return false;
+    const uint64_t sc = a.src_mask + 1, dc = a.dst_mask + 1;
+    if ((sc & a.src_mask) != 0 || (dc & a.dst_mask) != 0 || sc < RING_MOVE_SEG || dc < RING_MOVE_SEG) return false;
+    for (uint32_t i = 0; i < a.n_desc; ++i) {
+        const RingMoveDesc &d = a.host_desc[i];
+        if (d.src_row >= a.src_rows || d.dst_row >= a.dst_rows || d.count > sc || d.count > dc || d.first + d.count < d.first) return false;
+    }
+    return true;
+}
+hipError_t launch_ring_move(const RingMoveArgs &a, hipStream_t s);
+
 }  // namespace fr

@@ -754,6 +754,8 @@ StagedPlan plan_stages(const FlatGraph &g, bool allow_banks, bool allow_programs
     for (uint32_t n : ring_nodes) {
         ring_of[n] = sp.n_rings++;
         sp.lmax = std::max(sp.lmax, L[n]);
+        sp.ring_node.push_back(n);
+        sp.ring_lookback.push_back(L[n]);
     }
     if (feedback) {
         // The look-back of a loop has no bound; the rings are never rebuilt from a window.  They are brought up to date by
@@ -762,6 +764,31 @@ StagedPlan plan_stages(const FlatGraph &g, bool allow_banks, bool allow_programs
         for (auto &kv : built)
             for (auto &rd : kv.second.reads) sp.lmax = std::max(sp.lmax, rd.second);
         sp.input_lookback_unbounded = true;
+        // what each ring is, for a renderer that keeps rings across re-plans (StagedPlan::ring_fb, ring_lookback)
+        std::fill(sp.ring_lookback.begin(), sp.ring_lookback.end(), 0);
+        for (auto &kv : built)
+            for (auto &rd : kv.second.reads) {
+                uint64_t &lb = sp.ring_lookback[ring_of.at(rd.first)];
+                lb = std::max(lb, rd.second);
+            }
+        sp.ring_fb.resize(sp.n_rings);
+        for (uint32_t r = 0; r < sp.n_rings; ++r) {
+            std::unordered_set<uint32_t> seen;
+            std::vector<uint32_t> st{sp.ring_node[r]};
+            std::vector<std::pair<uint32_t, uint32_t>> loops;
+            while (!st.empty()) {
+                const uint32_t n = st.back();
+                st.pop_back();
+                if (!seen.insert(n).second || P.bank_of.count(n)) continue;   // (a voice is oscillators of inputs: no loop below it)
+                const FlatNode &x = g.nodes[n];
+                if (x.op == OP_CONST || x.op == OP_INPUT) continue;
+                if (x.op == OP_FBREF) { loops.push_back({x.a, g.fb_target[x.a]}); st.push_back(g.fb_target[x.a]); continue; }
+                st.push_back(x.a);
+                st.push_back(x.b);
+            }
+            std::sort(loops.begin(), loops.end());
+            for (auto &lp : loops) { sp.ring_fb[r].push_back(lp.first); sp.ring_fb[r].push_back(lp.second); }
+        }
     }
 
     // Which ranks need each cut node / voice (partial-block sharding): everything reachable from the roots of a rank's
@@ -1169,6 +1196,16 @@ StagedPlan plan_stages(const FlatGraph &g, bool allow_banks, bool allow_programs
         }
     }
     FR_PT("H_end");
+    sp.prog_rings.resize(sp.progs.size());
+    for (size_t i = 0; i < sp.progs.size(); ++i) {
+        const StageProg &pg = sp.progs[i];
+        std::vector<uint32_t> &pr = sp.prog_rings[i];
+        if (pg.dst_ring != NO_RING) pr.push_back(pg.dst_ring);
+        for (uint32_t k = 0; k < pg.n_instr; ++k)
+            if (sp.instrs[pg.first_instr + k].op == S_STORE) pr.push_back(sp.instrs[pg.first_instr + k].buf);
+        std::sort(pr.begin(), pr.end());
+        pr.erase(std::unique(pr.begin(), pr.end()), pr.end());
+    }
     std::sort(sp.pull_rows.begin(), sp.pull_rows.end());
     if (P.observed) note_observed(g, P, sp);
     check_tracks(g, sp, track_from, track_history);

@@ -110,6 +110,15 @@ struct StagedPlan {
     uint64_t track_lookback = 0;
     std::vector<uint32_t> track_window_slots;
     bool track_unbounded = false;          // (planning only) a staged read of a track by a signal amount without a bound
+    // What each ring holds (FR_RING_KEEP, engine.cpp RingTable): the lowered node whose value it is -- ids are append-only and
+    // hash-consed, so within one Lowering::generation() the id names the function --, the look-back it must serve (feedback
+    // plans: the deepest delay it is read with; its older frames only ever matter to a replay from 0), and for feedback plans
+    // the loops its value passes through: {j, fb_target[j]} of every OP_FBREF its expression reaches, through the targets too.
+    // prog_rings: the rings every program stores (dst_ring and its S_STOREs).
+    std::vector<uint32_t> ring_node;
+    std::vector<uint64_t> ring_lookback;
+    std::vector<std::vector<uint32_t>> ring_fb;
+    std::vector<std::vector<uint32_t>> prog_rings;
     bool uses_rings() const { return n_rings != 0; }
 };
 
