@@ -265,9 +265,17 @@ fr_status fr_fill_buffer_device(fr_renderer *r, float *d_out, uint32_t n_slots, 
  * arithmetic takes 1.3 us.  fr_stream_begin launches ONE kernel that stays resident; fr_stream_block then hands it a block
  * of 1..64 frames through a doorbell in mapped memory and returns when the rows have arrived in `out`, which must hold
  * [n_slots of fr_stream_begin, n_times] floats, row-major.
- * Served: plans that are one bank of balanced template voices, one voice per output row, at most one workgroup per compute
- * unit of the device (256 on a whole MI355X; FR_ERR_UNSUPPORTED otherwise -- render such graphs with fr_fill_buffer).
- * `row` is the block's input row for slot 0; such plans read no other input and no history.  A row shorter than n_times is
+ * Served: plans that are one bank of balanced template voices of at least 128 partials, one voice per output row, at most
+ * one workgroup per compute unit of the device (256 on a whole MI355X; FR_ERR_UNSUPPORTED otherwise -- render such graphs
+ * with fr_fill_buffer).  With the option FR_STREAM_PROGRAMS=1 (friendship_render_ext.h) also plans with stage programs and
+ * delay lines behind that one bank -- an envelope on every voice, feed-forward delay taps, echoes (feedback through Delay) --
+ * as long as every Delay of a computed value reaches at least 64 frames back, no program mixes two voices of the same block,
+ * and the programs read input slot 0 at the current frame only (no delayed reads of the input row, no signal-amount
+ * delays); fr_last_error names what a refused plan has.  For such a plan the first block, and every block that does not
+ * continue the previous one, first brings the delay lines up to `idx` the way fr_fill_buffer does after a seek there
+ * (the look-back window, or a loop's replay from frame 0, every input before `idx` reading 0.0) and then (re)starts the
+ * resident launch: a seek costs what it costs fr_fill_buffer, continuing blocks only ring the doorbell.
+ * `row` is the block's input row for slot 0; served plans read no other input and no input history.  A row shorter than n_times is
  * padded as fill_buffer pads it (reference.rs:72-73) with the slot's last stored value: the row's own last value, or -- an
  * empty row -- the last value of the previous block when `idx` continues it (idx == previous idx + previous n_times); the
  * first block of a stream, and a block that does not continue the previous one, find nothing stored (as after a seek) and
@@ -280,7 +288,10 @@ fr_status fr_fill_buffer_device(fr_renderer *r, float *d_out, uint32_t n_slots, 
  * resident: something else holds compute units).
  * The resident launch keeps one compute unit per (voice, chunk) workgroup -- a whole MI355X for 64 voices of 4096
  * partials, 40 of its 256 units for 5 voices of 1024 -- and nothing else runs on THOSE units until the stream is closed
- * or ends itself; other kernels, of this process or any other, run on the units it leaves. */
+ * or ends itself; other kernels, of this process or any other, run on the units it leaves.  Work of THIS process on
+ * another stream (another renderer's calls included) may still be queued behind the resident launch when the runtime puts
+ * both streams on one of its few hardware queues: it then waits until the stream is closed or the launch ends itself, so
+ * render elsewhere before fr_stream_begin or after fr_stream_end. */
 fr_status fr_stream_begin(fr_renderer *r, uint32_t n_slots);
 fr_status fr_stream_block(fr_renderer *r, float *out, uint64_t n_times, uint64_t idx, const float *row, uint64_t row_len);
 fr_status fr_stream_end(fr_renderer *r);

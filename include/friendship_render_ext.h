@@ -35,6 +35,15 @@ extern "C" {
  * move_launches, repair_from, inert}; launches of form "repair" / "replay" in bank_launches and stage_launches.  The option
  * does nothing ("inert" names why) under FR_SHARD_PARTIALS, with a track history that feeds delay lines, and with a
  * bounded input history (fr_config.history_frames).
+ *
+ * FR_STREAM_PROGRAMS = 0 / 1 (default 0; read strictly from the environment too): block streaming (fr_stream_begin /
+ * fr_stream_block / fr_stream_end, friendship_render.h) also serves plans with stage programs and delay lines behind one
+ * bank of balanced template voices: a second resident kernel runs each voice's programs in the wave that finishes the voice.
+ * With 0 nothing changes: the same plans are served and refused, by the same kernel.  With 1, fr_plan_json carries "stream"
+ * {servable, reason, voices, chunks, programs_per_voice, min_ring_delay, rings, kernel} after any call: whether
+ * fr_stream_begin would take the plan and why not.  Refused (FR_ERR_UNSUPPORTED, the reason in fr_last_error): a Delay of a
+ * computed value shorter than 64 frames, a program that needs two voices of the same block (a mix bus), delayed reads of
+ * the input row, signal-amount delays, more than one bank, compiled, general and track voices, pull rows, sharding.
  */
 typedef struct fr_option {
     const char *name;              /* e.g. "FR_BANK_SHORT" */

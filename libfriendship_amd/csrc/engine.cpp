@@ -29,6 +29,7 @@
 #include "kernels.hpp"
 #include "match.hpp"
 #include "stage.hpp"
+#include "streamplan.hpp"
 
 namespace fr {
 
@@ -188,7 +189,7 @@ static std::string stage_variant(const StageLaunchNote &n, const Plan &p) {
     return k;
 }
 
-constexpr size_t N_OPTIONS = 30;         // per-renderer options (friendship_render_ext.h; the table below fr_renderer)
+constexpr size_t N_OPTIONS = 31;         // per-renderer options (friendship_render_ext.h; the table below fr_renderer)
 
 struct TimerClass {
     double ms = 0;
@@ -231,6 +232,10 @@ __attribute__((weak)) hipError_t launch_ring_move(const RingMoveArgs &a, hipStre
             a.dst[(uint64_t)d.dst_row * (a.dst_mask + 1) + (t & a.dst_mask)] = a.src[(uint64_t)d.src_row * (a.src_mask + 1) + (t & a.src_mask)];
     }
     return hipSuccess;
+}
+// (no resident launches on the simulator: the serving rule and the tables are what it tests, through fr_plan_json)
+__attribute__((weak)) hipError_t launch_bank_stream_prog(const BankArgs &, const StreamProgArgs &, BankStreamCtl *, BankStreamDev *, uint32_t, hipStream_t) {
+    return hipErrorNotSupported;
 }
 __attribute__((weak)) hipError_t launch_track_window(const TrackWindowArgs &a, hipStream_t) {
     for (uint32_t r = 0; r < a.n_rows; ++r)
@@ -517,18 +522,53 @@ struct fr_renderer {
     }
     PinnedBuf h_stream_ctl, h_stream_out;
     DevBuf d_stream_dev;
-    // `clean`: the launch was answering when the stop was rung (every block it took was finished).  Otherwise some chunks of
-    // a voice may have taken their ticket and others never run: the counters are cleared before anyone uses them again.
-    void end_stream(bool clean = true) {
-        if (!streaming) return;
-        BankStreamCtl *ctl = (BankStreamCtl *)h_stream_ctl.p;
-        for (int i = 0; i < 64; ++i) __atomic_store_n(&ctl->row[i], (unsigned long long)BANK_STREAM_STOP << 32, __ATOMIC_RELEASE);
-        if (hipStreamSynchronize(stream) != hipSuccess) { (void)hipGetLastError(); clean = false; }   // the kernel sees the stop within a poll, or ends itself after its bound
-        streaming = false;
+    // Plans with programs (FR_STREAM_PROGRAMS, streamplan.hpp): fr_stream_begin deals the programs to the voices and uploads
+    // the tables; the resident launch (bank_stream_prog_kernel) starts with the first block and again with every block that
+    // does not continue the previous one, after the rings were brought up to that block's first frame.
+    bool stream_programs = false;        // the option
+    bool stream_prog = false;            // the open stream is of that kind
+    bool stream_launched = false;        // its resident launch is running
+    const char *stream_kernel = "";      // the last resident launch's kernel (fr_plan_json "stream")
+    StreamPlan stream_plan;
+    DevBuf d_stream_progs, d_stream_vfirst;
+    StreamPlan plan_stream_now() const {
+        std::vector<const BankLaunch *> banks;
+        for (const BankStage &bs : plan.banks) banks.push_back(&bs.grp);
+        StreamEnv env;
+        env.n_slots = plan.n_slots;
+        env.device_cus = (uint32_t)std::max(device_cus, 0);
+        env.leaf_variant = bank_tune.leaf_variant;
+        env.pull_mode = mode == FR_MODE_PULL;
+        env.sharded = sharded();
+        env.track_history = tail_on();
+        return plan_stream(plan.sp, banks, env);
+    }
+    // Rings the stop and waits for the resident launch to end.  `clean`: the launch was answering when the stop was rung
+    // (every block it took was finished).  Otherwise some chunks of a voice may have taken their ticket and others never
+    // run: the counters are cleared before anyone uses them again.
+    void stop_resident(bool clean) {
+        if (stream_launched) {
+            BankStreamCtl *ctl = (BankStreamCtl *)h_stream_ctl.p;
+            for (int i = 0; i < 64; ++i) __atomic_store_n(&ctl->row[i], (unsigned long long)BANK_STREAM_STOP << 32, __ATOMIC_RELEASE);
+            if (hipStreamSynchronize(stream) != hipSuccess) { (void)hipGetLastError(); clean = false; }   // the kernel sees the stop within a poll, or ends itself after its bound
+        }
+        stream_launched = false;
         stream_have_last = false;
         if (!clean) counters_dirty = true;
+    }
+    void end_stream(bool clean = true) {
+        if (!streaming) return;
+        stop_resident(clean);
+        streaming = false;
+        if (stream_prog) {                       // the rings moved on with frames the input store never saw
+            plan.stage_valid = false;
+            ring_table.valid = false;
+        }
+        stream_prog = false;
         head = UINT64_MAX;                       // the streamed frames were not stored: whatever comes next is a seek
     }
+    void begin_program_stream(uint32_t n_slots);
+    void seek_program_stream(uint64_t idx);
     bool allow_jit = true;               // FR_JIT=0: no hipRTC specialisation (those voices run as programs / pull)
     bool allow_template = true;          // FR_BANK_TEMPLATE=0: template voices go through the JIT path literally
     bool fused_strided_ok = true;        // FR_STAGE_STRIDED=0: a long steady call of the fused form as one launch per sub-window (A/B)
@@ -2055,6 +2095,136 @@ struct fr_renderer {
     }
 };
 
+// fr_stream_begin of a plan with programs (FR_STREAM_PROGRAMS): the rule, the per-voice program tables, the rings' size.  The
+// resident launch starts with the first block (seek_program_stream).
+void fr_renderer::begin_program_stream(uint32_t n_slots) {
+    const StagedPlan &sp = plan.sp;
+    if (!plan_current(n_slots)) throw Error(FR_ERR_UNSUPPORTED, "block streaming: the plan is not current");
+    StreamPlan s = plan_stream_now();
+    if (!s.servable) throw Error(FR_ERR_UNSUPPORTED, "block streaming (FR_STREAM_PROGRAMS): " + s.reason);
+    std::vector<StageProg> progs(s.progs.size());
+    for (size_t i = 0; i < progs.size(); ++i) {
+        progs[i] = sp.progs[s.progs[i]];
+        const StageProg &pg = progs[i];
+        if ((uint64_t)pg.first_instr + pg.n_instr > sp.instrs.size() || (pg.dst_ring != 0xFFFFFFFFu && pg.dst_ring >= sp.n_rings) || pg.out_row >= (int64_t)n_slots)
+            throw Error(FR_ERR_DEVICE, "internal: a streamed program out of the plan's bounds");
+        for (uint32_t k = 0; k < pg.n_instr; ++k) {
+            const StageInstr &in = sp.instrs[pg.first_instr + k];
+            if ((in.op == S_READ || in.op == S_STORE) && in.buf >= sp.n_rings) throw Error(FR_ERR_DEVICE, "internal: a streamed program reads a ring the plan does not have");
+        }
+    }
+    const BankLaunch &grp = plan.banks[0].grp;
+    for (uint32_t row : grp.rows)
+        if (row >= (grp.to_ring ? sp.n_rings : n_slots)) throw Error(FR_ERR_DEVICE, "internal: a streamed voice's row out of bounds");
+    d_stream_progs.ensure(std::max<size_t>(progs.size(), 1) * sizeof(StageProg));
+    d_stream_vfirst.ensure(s.voice_first.size() * sizeof(uint32_t));
+    if (!progs.empty()) HIP_CHECK(hipMemcpyAsync(d_stream_progs.p, progs.data(), progs.size() * sizeof(StageProg), hipMemcpyHostToDevice, stream));
+    HIP_CHECK(hipMemcpyAsync(d_stream_vfirst.p, s.voice_first.data(), s.voice_first.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    HIP_CHECK(hipStreamSynchronize(stream));   // (host vectors go out of scope)
+    // rings: the deepest look-back and a block, as execute() sizes them for a 64-frame call (which the seek then finds in place)
+    if (sp.uses_rings()) {
+        uint64_t cap = 1024;
+        while (cap < sp.lmax + STREAM_BLOCK) cap <<= 1;
+        cap = std::max(cap, ring_cap);
+        if (cap > ring_cap || (size_t)sp.n_rings * cap * sizeof(float) > d_rings.bytes) {
+            d_rings.ensure((size_t)sp.n_rings * cap * sizeof(float));
+            ring_cap = cap;
+            plan.stage_valid = false;
+            ring_table.valid = false;
+        }
+    }
+    h_stream_ctl.ensure(sizeof(BankStreamCtl));
+    h_stream_out.ensure((size_t)n_slots * 64 * sizeof(float));
+    d_stream_dev.ensure(sizeof(BankStreamDev));
+    std::memset(h_stream_ctl.p, 0, sizeof(BankStreamCtl));
+    stream_plan = std::move(s);
+    streaming = true;
+    stream_prog = true;
+    stream_launched = false;
+    stream_seq = 0;
+    stream_slots = n_slots;
+    stream_have_last = false;
+    last_pending = false;
+}
+
+// A block that does not continue the previous one (the first block included): the running launch is retired, the rings are
+// brought up to idx by the ordinary path -- a call of the frames just before idx after a seek there: every input before idx
+// reads 0.0, the look-back window (a feedback plan: the replay from 0) is rebuilt, its output goes nowhere -- and the resident
+// launch starts with head = idx.
+void fr_renderer::seek_program_stream(uint64_t idx) {
+    HIP_CHECK(hipSetDevice(device));
+    stop_resident(true);
+    const uint32_t n_slots = stream_slots;
+    const StagedPlan &sp = plan.sp;
+    if (!plan_current(n_slots)) throw Error(FR_ERR_DEVICE, "internal: a stream outlived its plan");
+    const uint64_t warm = sp.uses_rings() ? std::min<uint64_t>(idx, STREAM_BLOCK) : 0;
+    plan.stage_valid = false;                    // whatever the rings hold, they do not hold a seek to idx
+    ring_table.valid = false;
+    head = UINT64_MAX;
+    if (warm) {
+        const uint64_t offs[1] = {0};
+        const auto snap = snapshot_store(idx - warm);
+        try {
+            store_inputs(n_slots, warm, idx - warm, nullptr, offs, 0, false, stream);
+            d_out.ensure((size_t)n_slots * warm * sizeof(float));
+            execute(d_out.as<float>(), n_slots, warm, idx - warm, stream);
+        } catch (...) {
+            rollback_store(snap);
+            throw;
+        }
+    }
+    plan.stage_valid = false;                    // from here on the rings run ahead of the input store
+    ring_table.valid = false;
+    const BankStage &bs = plan.banks[0];
+    const StreamPlan &s = stream_plan;
+    if ((sp.uses_rings() && (ring_cap < sp.lmax + STREAM_BLOCK || (size_t)sp.n_rings * ring_cap * sizeof(float) > d_rings.bytes)) || s.voices != bs.grp.rows.size())
+        throw Error(FR_ERR_DEVICE, "internal: the rings do not hold a streamed block's look-back");
+    BankArgs a{};
+    a.params = bs.d_params.as<float2>();
+    a.rows = bs.d_rows.as<uint32_t>();
+    a.n_voices = s.voices;
+    a.log2_p = bs.grp.log2_p;
+    a.n_times = 64;
+    a.fast_ok = bs.grp.fast_ok ? 1u : 0u;
+    a.leaf_variant = 1;
+    a.small_call = 2;
+    a.waves_per_group = 16;
+    a.frames_per_lane = 1;
+    a.chunk_log2 = s.chunk_log2;
+    if (s.chunks > 1) {
+        d_bank_ws.ensure((size_t)s.voices * s.chunks * 64 * sizeof(float));
+        a.ws = d_bank_ws.as<float>();
+        const size_t need = (size_t)s.voices * BANK_TICKET_STRIDE * sizeof(uint32_t);
+        clean_counters(stream);
+        if (need > d_tickets.bytes) {
+            d_tickets.ensure(need * 2);
+            HIP_CHECK(hipMemsetAsync(d_tickets.p, 0, d_tickets.bytes, stream));
+        }
+        a.tickets = d_tickets.as<uint32_t>();
+    }
+    a.out = h_stream_out.as_dev<float>();
+    a.out_stride = 64;
+    StreamProgArgs p{};
+    p.instrs = plan.d_instrs.as<StageInstr>();
+    p.progs = d_stream_progs.as<StageProg>();
+    p.voice_first = d_stream_vfirst.as<uint32_t>();
+    p.rings = sp.uses_rings() ? d_rings.as<float>() : nullptr;
+    p.ring_mask = sp.uses_rings() ? ring_cap - 1 : 0;
+    p.n_rings = sp.n_rings;
+    p.n_rows = n_slots;
+    p.head = idx;
+    p.bank_to_ring = bs.grp.to_ring ? 1u : 0u;
+    p.sparkle = mirror.sparkle ? 1u : 0u;
+    // (the previous launch's last doorbell and stop are still in the control words: a new launch starts from a clean slate)
+    std::memset(h_stream_ctl.p, 0, sizeof(BankStreamCtl));
+    HIP_CHECK(hipMemsetAsync(d_stream_dev.p, 0, sizeof(BankStreamDev), stream));
+    HIP_CHECK(launch_bank_stream_prog(a, p, h_stream_ctl.as_dev<BankStreamCtl>(), d_stream_dev.as<BankStreamDev>(), stream_idle_ms, stream));
+    stream_kernel = "bank_stream_prog_kernel";
+    stream_launched = true;
+    stream_have_last = false;
+    last_pending = false;
+}
+
 namespace {
 
 template <class F>
@@ -2110,6 +2280,7 @@ int64_t env_clamp(const char *e, int lo, int hi) { return std::min(hi, std::max(
 constexpr int64_t ENV_REFUSED = INT64_MIN;   // an `env` reading that makes create fail (resolve_options)
 int64_t env_strict_track_history(const char *e);
 int64_t env_strict_ring_keep(const char *e);
+int64_t env_strict_stream_programs(const char *e);
 bool parse_option(const Knob &k, const char *s, int64_t &v);
 
 const Knob kKnobs[] = {
@@ -2178,6 +2349,9 @@ const Knob kKnobs[] = {
     // Kept delay lines: a re-plan keeps the rings an edit cannot have changed (fr_plan_json: ring_keep, ring_state).  Strict
     // like FR_TRACK_HISTORY, and listed once set.
     {"FR_RING_KEEP", 0, 0, 1, 0, nullptr, 0, env_strict_ring_keep, [](fr_renderer &r, int64_t v, bool) { r.ring_keep = v != 0; }, LISTED_WHEN_SET},
+    // Block streaming of plans with stage programs and rings behind one voice bank (streamplan.hpp; fr_plan_json: stream).
+    // Strict and listed once set, like the two above.
+    {"FR_STREAM_PROGRAMS", 0, 0, 1, 0, nullptr, 0, env_strict_stream_programs, [](fr_renderer &r, int64_t v, bool) { r.stream_programs = v != 0; }, LISTED_WHEN_SET},
 };
 static_assert(sizeof kKnobs / sizeof kKnobs[0] == N_OPTIONS, "N_OPTIONS counts the rows of kKnobs");
 
@@ -2189,6 +2363,7 @@ static int64_t env_strict(const char *name, const char *e) {
 }
 int64_t env_strict_track_history(const char *e) { return env_strict("FR_TRACK_HISTORY", e); }
 int64_t env_strict_ring_keep(const char *e) { return env_strict("FR_RING_KEEP", e); }
+int64_t env_strict_stream_programs(const char *e) { return env_strict("FR_STREAM_PROGRAMS", e); }
 
 bool parse_option(const Knob &k, const char *s, int64_t &v) {
     if (k.word && std::strcmp(s, k.word) == 0) {
@@ -2564,6 +2739,10 @@ fr_status fr_stream_begin(fr_renderer *r, uint32_t n_slots) {
         r->order_after_previous(r->stream);
         r->ensure_plan(n_slots, r->stream);
         const StagedPlan &sp = r->plan.sp;
+        if (r->stream_programs && (!sp.progs.empty() || sp.uses_rings())) {
+            r->begin_program_stream(n_slots);
+            return;
+        }
         // what one resident launch can serve: every row straight from one balanced template voice, nothing stored between calls
         if (!r->plan_is_stateless(n_slots) || r->plan.banks.size() != 1)
             throw Error(FR_ERR_UNSUPPORTED, "block streaming needs a plan that is one voice bank (this one: " + std::to_string(r->plan.banks.size()) + " bank launches, " +
@@ -2613,7 +2792,10 @@ fr_status fr_stream_begin(fr_renderer *r, uint32_t n_slots) {
         a.out = r->h_stream_out.as_dev<float>();
         a.out_stride = 64;
         HIP_CHECK(launch_bank_stream(a, r->h_stream_ctl.as_dev<BankStreamCtl>(), r->d_stream_dev.as<BankStreamDev>(), r->stream_idle_ms, r->stream));
+        r->stream_kernel = "bank_stream_kernel";
         r->streaming = true;
+        r->stream_launched = true;
+        r->stream_prog = false;
         r->stream_seq = 0;
         r->stream_slots = n_slots;
         r->stream_have_last = false;
@@ -2625,6 +2807,9 @@ fr_status fr_stream_block(fr_renderer *r, float *out, uint64_t n_times, uint64_t
     return guarded(r, [&] {
         if (!r->streaming) throw Error(FR_ERR_INVALID_ARG, "no stream is open (fr_stream_begin; any other call on the renderer closes it)");
         if (!out || n_times == 0 || n_times > 64 || row_len > n_times || (row_len && !row)) throw Error(FR_ERR_INVALID_ARG, "a streamed block is 1..64 frames");
+        // a plan with programs: the first block, and a block that does not continue the previous one, is a seek -- the rings
+        // are brought up to idx and the resident launch starts there
+        if (r->stream_prog && (!r->stream_launched || !r->stream_have_last || idx != r->stream_head)) r->seek_program_stream(idx);
         // (a plan served here reads nothing but this block's row: `idx` enters only through the padding rule)
         BankStreamCtl *ctl = (BankStreamCtl *)r->h_stream_ctl.p;
         const auto t_in = std::chrono::steady_clock::now();
@@ -2648,10 +2833,8 @@ fr_status fr_stream_block(fr_renderer *r, float *out, uint64_t n_times, uint64_t
             if ((++spins & 0xFFFFFu) != 0) continue;
             if (hipStreamQuery(r->stream) != hipErrorNotReady) {   // the launch is gone (its own bound, or a fault)
                 (void)hipStreamSynchronize(r->stream);
-                r->streaming = false;
-                r->stream_have_last = false;
-                r->counters_dirty = true;                          // (it may have ended between two chunks of a voice)
-                r->head = UINT64_MAX;
+                r->stream_launched = false;
+                r->end_stream(false);                              // (it may have ended between two chunks of a voice)
                 throw Error(FR_ERR_DEVICE, "the resident launch ended before the block was rendered");
             }
             // a resident launch answers in tens of microseconds; a quarter of a second without an answer means it is not all
@@ -2794,6 +2977,17 @@ const char *fr_plan_json(fr_renderer *r) {
             r->plan_json_cache += ",\"ring_state\":{\"kept\":" + std::to_string(rs.kept) + ",\"rebuilt\":" + std::to_string(rs.rebuilt) +
                                   ",\"moved\":" + std::to_string(rs.moved) + ",\"move_launches\":" + std::to_string(rs.move_launches) +
                                   ",\"repair_from\":" + std::to_string(rs.repair_from) + ",\"inert\":\"" + rs.inert + "\"}";
+        }
+        if (r->stream_programs) {
+            const StreamPlan s = r->plan_stream_now();
+            std::string per;
+            for (uint32_t n : s.programs_per_voice()) per += (per.empty() ? "" : ",") + std::to_string(n);
+            std::string why;
+            for (char c : s.reason) { if (c == '"' || c == '\\') why += '\\'; why += c; }
+            r->plan_json_cache += std::string(",\"stream\":{\"servable\":") + (s.servable ? "true" : "false") + ",\"reason\":\"" + why +
+                                  "\",\"voices\":" + std::to_string(s.voices) + ",\"chunks\":" + std::to_string(s.chunks) + ",\"programs_per_voice\":[" + per +
+                                  "],\"min_ring_delay\":" + std::to_string(s.min_ring_delay) + ",\"rings\":" + std::to_string(r->plan.sp.n_rings) +
+                                  ",\"kernel\":\"" + r->stream_kernel + "\"}";
         }
         r->plan_json_cache += ",\"exchange_stats\":{\"calls\":" + std::to_string(r->exchange_calls) + ",\"tiles\":" + std::to_string(r->exchange_tiles) +
                               ",\"bytes_sent\":" + std::to_string(r->exchange_bytes) + "},\"bank_launches\":[";

@@ -188,6 +188,28 @@ struct StageArgs {
 constexpr uint32_t STAGE_CARRY = 8;
 hipError_t launch_stage(const StageArgs &a, hipStream_t s);
 
+// ---- block streaming of plans with programs (FR_STREAM_PROGRAMS, streamplan.hpp) ----------------------------------------
+// bank_stream_prog_kernel: bank_stream_kernel with an epilogue.  Wave 0 of the workgroup that finishes voice v holds the
+// voice's frames head + lane; it stores them to the voice's ring (bank_to_ring; else to the voice's output row), then
+// interprets progs[voice_first[v] .. voice_first[v + 1]) in order, lane = frame, the interpreter's registers in LDS: S_INPUT
+// is the block's row, ring reads and stores go through L2 (relaxed agent-scope atomics: the finisher of a voice changes CU
+// from block to block), output rows go to the mapped host buffer.  Ring and row stores alike are acknowledged before the
+// voice is counted in, so block k's done tag implies that every ring store of block k has landed.  `head` advances by each
+// block's length inside the launch; the host launches again for a block that does not continue the previous one.
+struct StreamProgArgs {
+    const StageInstr *instrs;      // the plan's instructions (StageProg::first_instr indexes them)
+    const StageProg *progs;        // the streamed programs, voice by voice
+    const uint32_t *voice_first;   // [n_voices + 1] into progs
+    float *rings;                  // [n_rings][ring_mask + 1]
+    uint64_t ring_mask;
+    uint32_t n_rings;
+    uint32_t n_rows;               // output rows of the mapped host result ([n_rows][64])
+    uint64_t head;                 // absolute frame of the first block's first frame
+    uint32_t bank_to_ring;         // BankArgs::rows are ring indices
+    uint32_t sparkle;              // FR_SEMANTICS_SPARKLE
+};
+hipError_t launch_bank_stream_prog(const BankArgs &a, const StreamProgArgs &p, BankStreamCtl *ctl_dev, BankStreamDev *dev, uint32_t idle_ms, hipStream_t s);
+
 // One step of the partial-block exchange (friendship_render.h FR_SHARD_PARTIALS): row i, window frame t:
 //   v = lo[i][t] + hi[i][t]         the Sum2 node one level up: left sub-tree + right sub-tree, one f32 add
 // stored to dst_ws[i][t] (steps before the last; may alias lo or hi), or -- the last step, dst_ws == null -- where the

@@ -1,0 +1,185 @@
+// streamplan.hpp -- which plans block streaming (fr_stream_*, FR_STREAM_PROGRAMS=1) can serve with one resident launch, and
+// how their stage programs are dealt to the voices.  Plain host logic, no HIP runtime calls, all inline (as bankplan.hpp):
+// fr_stream_begin and fr_plan_json's "stream" ask the same rule, and the host-logic simulator compiles it with the engine.
+//
+// The resident kernel (kernels.hip bank_stream_prog_kernel) renders one bank of balanced template voices per block; wave 0 of
+// the workgroup that finishes voice v holds the voice's <= 64 frames, stores them to the voice's ring and interprets the
+// programs assigned to v, lane = frame.  No workgroup waits for another one's result, so inside a block a program may read
+//   * at a delay < 64 frames: rings of ITS OWN voice's bank only (what its own wave has just stored),
+//   * at a delay >= 64 frames: any ring (an earlier block stored those frames, and that block's done tag was seen).
+#pragma once
+
+#include <algorithm>
+#include <cstdint>
+#include <string>
+#include <unordered_map>
+#include <vector>
+
+#include "stage.hpp"
+
+namespace fr {
+
+constexpr uint32_t STREAM_BLOCK = 64;        // the longest block a stream accepts
+constexpr uint32_t STREAM_MAX_WGS = 256;     // (= kernels.hpp BANK_STREAM_WGS)
+
+// What the rule needs to know besides the plan.
+struct StreamEnv {
+    uint32_t n_slots = 0;
+    uint32_t device_cus = 0;         // 0: unknown (the simulator): the kernel's own limit stands in
+    uint32_t leaf_variant = 1;       // FR_BANK_LEAF
+    bool pull_mode = false;          // FR_MODE_PULL
+    bool sharded = false;
+    bool track_history = false;      // FR_TRACK_HISTORY is on (every call appends to the track rings)
+};
+
+struct StreamPlan {
+    bool servable = false;
+    std::string reason;              // why not ("" when servable)
+    uint32_t voices = 0, chunk_log2 = 0, chunks = 0;   // chunks per voice; the launch has voices * chunks workgroups
+    bool bank_to_ring = false;
+    std::vector<uint32_t> progs;         // indices into StagedPlan::progs, voice by voice, in the order they run
+    std::vector<uint32_t> voice_first;   // [voices + 1] into `progs`
+    uint64_t min_ring_delay = 0;         // shortest delayed read of a ring that a program stores (0: there is none)
+    uint64_t lookback = 0;               // deepest ring read of the assigned programs
+    std::vector<uint32_t> programs_per_voice() const {
+        std::vector<uint32_t> n;
+        for (size_t v = 0; v + 1 < voice_first.size(); ++v) n.push_back(voice_first[v + 1] - voice_first[v]);
+        return n;
+    }
+};
+
+inline const char *stage_op_name(uint8_t op) {
+    static const char *const names[] = {"S_CONST", "S_INPUT", "S_READ", "S_READ_INPUT", "S_STEP", "S_SUM2", "S_MUL", "S_DIV", "S_MOD", "S_MIN",
+                                        "S_STORE", "S_READ_DYN", "S_READ_INPUT_DYN", "S_STEP_DYN"};
+    return op < sizeof names / sizeof names[0] ? names[op] : "an unknown op";
+}
+
+// `banks`: the plan's bank launches (the engine moves them out of StagedPlan::banks when it uploads them).
+inline StreamPlan plan_stream(const StagedPlan &sp, const std::vector<const BankLaunch *> &banks, const StreamEnv &env) {
+    StreamPlan s;
+    auto refuse = [&](const std::string &why) { s.servable = false; s.reason = why; return s; };
+    if (env.n_slots == 0) return refuse("no output slots");
+    if (env.sharded || !sp.split.empty()) return refuse("block streaming of a sharded renderer");
+    if (env.pull_mode) return refuse("block streaming of a renderer in FR_MODE_PULL");
+    if (!sp.pull_rows.empty()) return refuse(std::to_string(sp.pull_rows.size()) + " output rows are left to the pull interpreter");
+    if (env.track_history || !sp.track_window_slots.empty() || sp.track_lookback != 0) return refuse("block streaming with a track history");
+    if (banks.size() != 1) return refuse("block streaming needs a plan with one voice bank (this one: " + std::to_string(banks.size()) + " bank launches)");
+    const BankLaunch &b = *banks[0];
+    if (b.general || b.jit || b.tracks || b.to_ws) return refuse("block streaming needs balanced template voices (these are general, compiled or track voices)");
+    if (env.leaf_variant != 1) return refuse("block streaming with FR_BANK_LEAF=0");
+    if (b.input_slot != 0) return refuse("block streaming feeds input slot 0; these voices read another slot");
+    if (b.log2_p < 7) return refuse("block streaming needs voices of at least 128 partials (16 waves x one group of 8)");
+    const uint32_t V = (uint32_t)b.rows.size();
+    if (V == 0) return refuse("block streaming needs a plan with one voice bank (this one has no voices)");
+    // every workgroup of the launch must be resident at once, one per CU: chunks of >= 128 partials until the CUs are used
+    const uint64_t max_wgs = std::min<uint64_t>(STREAM_MAX_WGS, env.device_cus ? env.device_cus : STREAM_MAX_WGS);
+    uint32_t c = b.log2_p;
+    while (c > 7 && ((uint64_t)V << (b.log2_p - c + 1)) <= max_wgs && b.log2_p - c < 8) --c;
+    if (((uint64_t)V << (b.log2_p - c)) > max_wgs) return refuse("block streaming serves at most one voice per CU (" + std::to_string(max_wgs) + " here)");
+    s.voices = V;
+    s.chunk_log2 = c;
+    s.chunks = 1u << (b.log2_p - c);
+    s.bank_to_ring = b.to_ring;
+
+    // the programs that do a block's work: the fused form (a feedback plan: level by level, then its row copies); a plan whose
+    // programs are ONE level deep has no fused form because that level already is one
+    std::vector<uint32_t> run;
+    uint32_t first_copy = UINT32_MAX;                // position in `run` of the first row copy of a feedback plan
+    if (sp.feedback) {
+        for (uint32_t i = 0; i < sp.fused_count; ++i) run.push_back(sp.fused_first + i);
+        first_copy = (uint32_t)run.size();
+        for (uint32_t i = 0; i < sp.post_count; ++i) run.push_back(sp.post_first + i);
+    } else if (sp.fused_count) {
+        for (uint32_t i = 0; i < sp.fused_count; ++i) run.push_back(sp.fused_first + i);
+    } else if (!sp.progs.empty()) {
+        size_t levels = 0, only = 0;
+        for (size_t l = 0; l + 1 < sp.level_first.size(); ++l)
+            if (sp.level_first[l + 1] > sp.level_first[l]) { ++levels; only = l; }
+        if (levels != 1)
+            return refuse("the plan has no fused form: a program's ring is read less than " + std::to_string(STREAM_BLOCK) +
+                          " frames back (or the fused programs exceed the interpreter's budget)");
+        for (uint32_t i = sp.level_first[only]; i < sp.level_first[only + 1]; ++i) run.push_back(i);
+    }
+    std::unordered_map<uint32_t, uint32_t> bank_ring_voice;   // ring -> voice whose frames it holds
+    if (b.to_ring)
+        for (uint32_t v = 0; v < V; ++v) bank_ring_voice[b.rows[v]] = v;
+    std::unordered_map<uint32_t, uint32_t> stored_by;         // ring -> position in `run` of the program that stores it
+    for (uint32_t k = 0; k < run.size(); ++k) {
+        const StageProg &pg = sp.progs[run[k]];
+        if (pg.dst_ring != 0xFFFFFFFFu) stored_by.emplace(pg.dst_ring, k);
+        for (uint32_t i = 0; i < pg.n_instr; ++i) {
+            const StageInstr &in = sp.instrs[pg.first_instr + i];
+            if (in.op == S_STORE) stored_by.emplace(in.buf, k);
+        }
+    }
+    constexpr uint32_t NONE = UINT32_MAX;
+    std::vector<uint32_t> voice_of(run.size(), NONE);
+    uint64_t min_delay = UINT64_MAX;
+    for (uint32_t k = 0; k < run.size(); ++k) {
+        const StageProg &pg = sp.progs[run[k]];
+        const bool copy = k >= first_copy;
+        uint32_t mine = NONE;
+        for (uint32_t i = 0; i < pg.n_instr; ++i) {
+            const StageInstr &in = sp.instrs[pg.first_instr + i];
+            switch (in.op) {
+            case S_CONST: case S_STEP: case S_SUM2: case S_MUL: case S_DIV: case S_MOD: case S_MIN: case S_STORE: break;
+            case S_INPUT:
+                if (in.imm >= sp.input_slots.size() || sp.input_slots[in.imm] != 0)
+                    return refuse("a program reads input slot " + std::to_string(in.imm < sp.input_slots.size() ? sp.input_slots[in.imm] : in.imm) +
+                                  "; block streaming feeds slot 0 only");
+                break;
+            case S_READ: {
+                s.lookback = std::max<uint64_t>(s.lookback, in.d_lo);
+                auto bv = bank_ring_voice.find(in.buf);
+                if (bv != bank_ring_voice.end()) {
+                    if (in.d_lo >= STREAM_BLOCK) break;             // an earlier block's frames: any voice's
+                    if (mine != NONE && mine != bv->second)
+                        return refuse("a program reads voices " + std::to_string(mine) + " and " + std::to_string(bv->second) +
+                                      " in the same block (a mix bus across voices); each streamed program follows one voice");
+                    mine = bv->second;
+                    break;
+                }
+                if (copy && in.d_lo == 0) {                          // a row copy: after the program that stores the ring, on its voice
+                    auto st = stored_by.find(in.buf);
+                    if (st == stored_by.end() || voice_of[st->second] == NONE) return refuse("internal: a row copy of a ring no streamed program stores");
+                    mine = voice_of[st->second];
+                    break;
+                }
+                if (in.d_lo < STREAM_BLOCK)
+                    return refuse("a program's ring is read " + std::to_string(in.d_lo) + " frames back; a streamed block needs delays of at least " +
+                                  std::to_string(STREAM_BLOCK) + " frames");
+                min_delay = std::min<uint64_t>(min_delay, in.d_lo);
+                break;
+            }
+            default:
+                return refuse(std::string("a program uses ") + stage_op_name(in.op) +
+                              (in.op == S_READ_INPUT ? " (a delayed read of the input row)" : " (a Delay by a signal amount)") + ", which block streaming does not serve yet");
+            }
+            if (in.dst >= STAGE_REGS || in.a >= STAGE_REGS || in.b >= STAGE_REGS) return refuse("a program needs more registers than the streamed interpreter has");
+        }
+        if (pg.result_reg >= STAGE_REGS) return refuse("a program needs more registers than the streamed interpreter has");
+        voice_of[k] = mine != NONE ? mine : run[k] % V;   // (reads no voice at a short delay: any one voice, the same every time)
+    }
+    // each output row: one assigned program, or the bank itself
+    std::vector<uint32_t> writers(env.n_slots, 0);
+    auto writes = [&](int64_t row) { if (row >= 0 && row < (int64_t)env.n_slots) ++writers[(size_t)row]; return row < (int64_t)env.n_slots; };
+    if (!b.to_ring)
+        for (uint32_t row : b.rows)
+            if (!writes(row)) return refuse("a voice writes output row " + std::to_string(row) + " of " + std::to_string(env.n_slots));
+    for (uint32_t k = 0; k < run.size(); ++k)
+        if (!writes(sp.progs[run[k]].out_row)) return refuse("a program writes output row " + std::to_string(sp.progs[run[k]].out_row) + " of " + std::to_string(env.n_slots));
+    for (uint32_t r = 0; r < env.n_slots; ++r)
+        if (writers[r] != 1)
+            return refuse("output row " + std::to_string(r) + " is written by " + std::to_string(writers[r]) + " streamed programs or voices (exactly one is needed)");
+    s.voice_first.assign(V + 1, 0);
+    for (uint32_t k = 0; k < run.size(); ++k) ++s.voice_first[voice_of[k] + 1];
+    for (uint32_t v = 0; v < V; ++v) s.voice_first[v + 1] += s.voice_first[v];
+    s.progs.resize(run.size());
+    std::vector<uint32_t> at(s.voice_first.begin(), s.voice_first.end() - 1);
+    for (uint32_t k = 0; k < run.size(); ++k) s.progs[at[voice_of[k]]++] = run[k];   // (stable: the order of `run` inside a voice)
+    s.min_ring_delay = min_delay == UINT64_MAX ? 0 : min_delay;
+    s.servable = true;
+    return s;
+}
+
+}  // namespace fr
