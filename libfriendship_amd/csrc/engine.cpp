@@ -18,11 +18,11 @@
 #include <map>
 #include <sstream>
 #include <string>
-#include <unordered_set>
 #include <vector>
 
 #include "../../include/friendship_render_ext.h"
 #include "bankplan.hpp"
+#include "callplan.hpp"
 #include "comm.hpp"
 #include "graph.hpp"
 #include "jit.hpp"
@@ -520,6 +520,16 @@ struct fr_renderer {
         if (d_row_done.p) HIP_CHECK(hipMemsetAsync(d_row_done.p, 0, d_row_done.bytes, st));
         counters_dirty = false;
     }
+    // `words` arrival counters for a launch with an in-launch combine: zero between launches (the kernel resets them).
+    uint32_t *ticket_counters(size_t words, hipStream_t st) {
+        const size_t need = words * sizeof(uint32_t);
+        clean_counters(st);
+        if (need > d_tickets.bytes) {
+            d_tickets.ensure(need * 2);
+            HIP_CHECK(hipMemsetAsync(d_tickets.p, 0, d_tickets.bytes, st));
+        }
+        return d_tickets.as<uint32_t>();
+    }
     PinnedBuf h_stream_ctl, h_stream_out;
     DevBuf d_stream_dev;
     // Plans with programs (FR_STREAM_PROGRAMS, streamplan.hpp): fr_stream_begin deals the programs to the voices and uploads
@@ -600,7 +610,7 @@ struct fr_renderer {
     bool rings_touched = false;          // the call in hand has reached execute(): its launches may have written rings
     PinnedBuf h_ring_desc;               // the move's descriptors (the kernel reads them through the mapping)
     hipEvent_t ev_ring_move = nullptr;   // ... free for the next move once this has passed
-    // What the repair launches (execute()): bank voices as runs [first, first + count) of a stage's voices, programs as runs
+    // What the repair launches (repair_rings): bank voices as runs [first, first + count) of a stage's voices, programs as runs
     // of plan.sp.progs level by level, all over [from, idx); `replay`: a feedback plan's loops, from frame 0 in chunks.
     struct RingRepair {
         bool replay = false;
@@ -1098,7 +1108,8 @@ struct fr_renderer {
 
     // A full-length device-resident row feeding a bank's time slot is not copied here: the bank kernel reads
     // the caller's row directly and appends it to the history itself (BankArgs::hist_dst).
-    struct Deferred { uint32_t slot; const float *src; float *dst; };
+    // (`appended_tile`: the exchange-window tile whose launch last appended its part of the row, by offset; -1: none has)
+    struct Deferred { uint32_t slot; const float *src; float *dst; int64_t appended_tile = -1; };
     std::vector<Deferred> deferred;
     // Will execute() render exactly [idx, idx + n_times) for the staged part (steady state), or rebuild a look-back
     // window first?  Same conditions as execute() uses (ring capacity, contiguity with what the rings hold).
@@ -1589,462 +1600,466 @@ struct fr_renderer {
     }
 
     // ---- execution --------------------------------------------------------------------------------
+    // One render call, as its phases see it: the destination, the call itself (callplan.hpp CallIn, filled in by
+    // prepare_rings) and what the per-call rule answered for it.
+    struct Call : CallIn {
+        float *dst;
+        uint32_t n_slots;
+        hipStream_t st;
+        Call(float *d, uint32_t slots, uint64_t n, uint64_t first, hipStream_t s) : dst(d), n_slots(slots), st(s) { idx = first; n_times = n; }
+        CallWindows w;
+        ExchangeTiles xt;
+        StageForm form;
+        bool x_window_is_call() const { return w.x0 == idx && w.xlen == n_times; }
+        bool pipelined() const { return xt.count > 1; }   // the tiles' exchanges run on the exchange stream, under later tiles' kernels
+    };
+
     void execute(float *d_dst, uint32_t n_slots, uint64_t n_times, uint64_t idx, hipStream_t st) {
         bank_launches.clear();
         stage_launches.clear();
+        bank_form = "call";
         ensure_plan(n_slots, st);
         rings_touched = true;
-        if (n_slots == 0 || n_times == 0) {   // (nothing to render: the track history still moves on as the reference's inputs do)
-            prepare_tracks(n_times, idx, st);
-            append_tracks(n_times, idx, st);
-            return;
-        }
         prepare_tracks(n_times, idx, st);
-        const StagedPlan &sp = plan.sp;
+        if (n_slots != 0 && n_times != 0) {   // (nothing to render: the track history still moves on as the reference's inputs do)
+            const StagedPlan &sp = plan.sp;
+            Call c(d_dst, n_slots, n_times, idx, st);
+            const RingRepair repair = prepare_rings(c);
+            // (decided AFTER the rings may have been re-allocated above: a longer call than any before loses what they held)
+            c.w = call_windows(sp, c);
+            const bool serial = exchange_serial((shard_flags & FR_SHARD_SERIAL_EXCHANGE) != 0, rccl != nullptr, x_tiles_explicit);
+            if (!sp.split.empty()) c.xt = fr::exchange_tiles(c.w.xlen, serial, x_max_tiles, x_min_tile);
+            c.form = stage_form(sp, c, c.w, STRIDED_MIN_STRIDE, fused_strided_ok);
+            repair_rings(c, repair);
+            replay_feedback(c);
+            exchange_split_voices(c);
+            launch_whole_banks(c);
+            launch_stage_programs(c);
+            commit_rings(c);
+            if (!plan.pull_rows.empty()) run_pull(d_dst, n_slots, n_times, idx, st);
+        }
+        append_tracks(n_times, idx, st);
+    }
 
-        // Window of the staged part.  Contiguous with what the rings already hold: just this call's frames.
-        // Otherwise (first call, seek, graph edit, larger call): rebuild the look-back from the input history.
-        uint64_t w0 = idx;
-        bool rings_current = false;          // the rings hold everything before idx that this call reads
+    // Rings of at least `cap` floats each for the plan in hand (execute(), begin_program_stream); what they held does not
+    // survive a re-allocation.
+    void grow_rings(uint64_t cap) {
+        cap = std::max(cap, ring_cap);
+        const size_t bytes = (size_t)plan.sp.n_rings * cap * sizeof(float);
+        if (cap <= ring_cap && bytes <= d_rings.bytes) return;
+        d_rings.ensure(bytes);
+        ring_cap = cap;
+        plan.stage_valid = false;
+        ring_table.valid = false;
+    }
+
+    // The one step that changes state before the call's windows are decided: the rings get the size the call needs and are
+    // kept (FR_RING_KEEP: what the repair must rebuild is returned) or grown.  Fills in what callplan.hpp asks about them.
+    RingRepair prepare_rings(Call &c) {
+        const StagedPlan &sp = plan.sp;
         ring_state = RingState{};
         if (ring_keep) ring_state.inert = ring_keep_inert();
-        const bool keep_on = ring_keep && ring_state.inert.empty();
+        c.keep_on = ring_keep && ring_state.inert.empty();
         RingRepair repair;
-        // Feedback plans (stage.hpp StagedPlan::feedback): no window bounds a loop's look-back, so rings that are not current
-        // are brought up to date by replaying every frame from 0 in chunks -- the ring-bound banks and the fused programs over
-        // [c0, c0 + len), nothing written to the output -- before the call's own frames run in steady-state form.
-        constexpr uint64_t FB_CHUNK = 16384, FB_MAX_REPLAY = 1ull << 28;
         if (sp.feedback && history_frames != 0)
             throw Error(FR_ERR_UNSUPPORTED, "feedback through Delay needs the full input history (fr_config.history_frames = 0)");
-        if (sp.uses_rings()) {
-            // (a feedback plan's rings always have room for a replay chunk: growing them later would lose the loop's state)
-            uint64_t need = sp.lmax + std::max<uint64_t>(n_times, sp.feedback ? FB_CHUNK : 0);
-            uint64_t cap = 1024;
-            while (cap < need) cap <<= 1;
-            if (keep_on) {
-                // (FR_RING_KEEP: the rings this plan finds in the table stay, the others are brought up to idx by the repair
-                //  below, and the call itself always runs in its steady form)
-                const bool table_was_valid = ring_table.valid;
-                ring_table.valid = false;            // (until the call is through: a failure leaves nothing to keep)
-                const bool fits = cap <= ring_cap && (size_t)sp.n_rings * ring_cap * sizeof(float) <= d_rings.bytes;
-                if (plan.stage_valid && plan.stage_end == idx && fits && table_was_valid && ring_table.end == idx &&
-                    ring_table.rings.size() == sp.n_rings) {
-                    ring_state.kept = sp.n_rings;
-                    ring_state.repair_from = idx;
-                } else {
-                    repair = keep_rings(cap, idx, table_was_valid, st);
-                }
-                rings_current = true;
+        if (!sp.uses_rings()) return repair;
+        const uint64_t cap = ring_capacity(sp, c.n_times);
+        const bool table_was_valid = ring_table.valid;
+        ring_table.valid = false;            // (until the call is through: a failure leaves nothing to keep)
+        if (c.keep_on) {
+            // (FR_RING_KEEP: the rings this plan finds in the table stay, the others are brought up to idx by the repair,
+            //  and the call itself always runs in its steady form)
+            const bool fits = cap <= ring_cap && (size_t)sp.n_rings * ring_cap * sizeof(float) <= d_rings.bytes;
+            if (plan.stage_valid && plan.stage_end == c.idx && fits && table_was_valid && ring_table.end == c.idx &&
+                ring_table.rings.size() == sp.n_rings) {
+                ring_state.kept = sp.n_rings;
+                ring_state.repair_from = c.idx;
             } else {
-                ring_table.valid = false;
-                if (cap > ring_cap) {
-                    d_rings.ensure((size_t)sp.n_rings * cap * sizeof(float));
-                    ring_cap = cap;
-                    plan.stage_valid = false;
-                } else if ((size_t)sp.n_rings * ring_cap * sizeof(float) > d_rings.bytes) {
-                    d_rings.ensure((size_t)sp.n_rings * ring_cap * sizeof(float));
-                    plan.stage_valid = false;
-                }
-                rings_current = plan.stage_valid && plan.stage_end == idx;
-                if (ring_keep) (rings_current ? ring_state.kept : ring_state.rebuilt) = sp.n_rings;
-                if (!rings_current) w0 = idx > sp.lmax ? idx - sp.lmax : 0;
-                if (sp.feedback) w0 = idx;   // (the replay below has brought the rings to idx by the time this window runs)
+                repair = keep_rings(cap, c.idx, table_was_valid, c.st);
+                c.repair_replay = repair.replay;
             }
+        } else {
+            grow_rings(cap);
+            c.rings_valid = plan.stage_valid && plan.stage_end == c.idx;
+            if (ring_keep) (c.rings_valid ? ring_state.kept : ring_state.rebuilt) = sp.n_rings;
         }
-        // (decided AFTER the rings may have been re-allocated above: a longer call than any before loses what they held)
-        const bool fb_replay = sp.feedback && !keep_on && !rings_current && idx != 0;
-        if (repair.replay && idx > FB_MAX_REPLAY)
-            throw Error(FR_ERR_UNSUPPORTED, "a feedback loop's state at frame " + std::to_string(idx) + " would take replaying more than 2^28 frames");
-        if (fb_replay && idx > FB_MAX_REPLAY)
-            throw Error(FR_ERR_UNSUPPORTED, "a feedback loop's state at frame " + std::to_string(idx) + " would take replaying more than 2^28 frames");
-        const uint64_t w_len = idx + n_times - w0;
-        // Split voices (partial-block sharding): every rank renders its sub-trees over the SAME window -- the look-back
-        // window when any split voice feeds a ring (lmax, ring capacity and validity are the same on every rank: same
-        // graph, same calls), else just this call's frames.
-        bool x_ring = false;
-        for (const SplitVoice &v : sp.split) x_ring = x_ring || v.to_ring;
-        const uint64_t x0 = x_ring ? w0 : idx, xlen = x_ring ? w_len : n_times;
-        if (!sp.split.empty()) {
-            used_scratch = true;
-            d_ws.ensure(sp.split.size() * xlen * sizeof(float));
-            d_xrecv.ensure(sp.split.size() * xlen * sizeof(float));
-        }
+        return repair;
+    }
 
-        // Tiles of the exchange window (partial-block sharding): whole 64-frame kernel tiles, at most x_max_tiles of them, none
-        // shorter than x_min_tile.  One tile = the serial form of round 2.
-        std::vector<std::pair<uint64_t, uint64_t>> xt;   // (offset in the window, frames)
-        if (!sp.split.empty()) {
-            // (the host-callback transport pays a host round trip and a stream synchronisation per message -- 4 tiles over gloo
-            //  measured 0.63 ms per call against 0.28 serial, profiles/r03_exchange_rehearsal.txt: it stays serial unless asked;
-            //  RCCL sends are enqueued like kernels, there tiling hides them)
-            const bool serial = (shard_flags & FR_SHARD_SERIAL_EXCHANGE) || (!rccl && !x_tiles_explicit);
-            uint64_t nt = serial ? 1 : std::min<uint64_t>(x_max_tiles, xlen / std::max<uint32_t>(x_min_tile, 64u));
-            nt = std::max<uint64_t>(nt, 1);
-            const uint64_t tl = (((xlen + nt - 1) / nt) + 63) / 64 * 64;
-            for (uint64_t off = 0; off < xlen; off += tl) xt.push_back({off, std::min(tl, xlen - off)});
-        }
-        const bool x_window_is_call = x0 == idx && xlen == n_times;
-        std::unordered_set<uint32_t> tile_slots, tile_appended;   // input slots whose deferred row the tiles append / this tile has appended
-        // One bank launch over the window [b0, b0 + blen).  `tile_off` >= 0: a tile of the exchange window (b0 = x0 + tile_off),
-        // written to the tile-major workspace; such a launch appends ITS part of a deferred input row.
-        // `trk`: where a voice that reads tracks finds them for this window (a span of the track history's ring), instead of the
-        // call's own matrix
-        struct TrackSrc { const float *p; uint64_t stride; uint32_t limit; };
-        // `v0`, `nv`: a run of the stage's voices (a repair renders only the voices whose rings it rebuilds; parameters and rows are
-        // voice-major, so a run is the same launch at offset pointers)
-        auto launch_bank_part = [&](BankStage &bs, uint64_t b0, uint64_t blen, int64_t tile_off, const TrackSrc *trk, uint32_t v0 = 0, uint32_t nv = UINT32_MAX) {
-            const bool ring = bs.grp.to_ring, ws = bs.grp.to_ws;
-            const bool whole = v0 == 0 && nv >= bs.grp.rows.size();
-            if (whole) nv = (uint32_t)bs.grp.rows.size();
-            else if (bs.grp.general || (uint64_t)v0 + nv > bs.grp.rows.size()) throw Error(FR_ERR_DEVICE, "internal: a run of voices the bank stage cannot launch");
-            const BankPlan bp = plan_bank_launch(bs, blen, flag_out.host_flags != nullptr, nv);   // (the one rule, asked about the run's voices)
-            BankArgs a{};
-            a.params = bs.d_params.as<float2>() + ((size_t)v0 << bs.grp.log2_p);
-            input_window(bs.grp.input_slot, b0, blen, a.time, a.time_skip, a.time_valid);   // time-slot history for the window
-            if (tile_off < 0 && b0 == idx && blen == n_times)   // (direct output, or a ring in steady state)
-                for (Deferred &d : deferred)
-                    if (d.slot == bs.grp.input_slot) {   // read the caller's row; the first bank on this slot appends it
-                        a.time = d.src;
-                        a.time_skip = 0;
-                        a.time_valid = n_times;
-                        a.hist_dst = d.dst;
-                        d.dst = nullptr;
-                    }
-            if (tile_off >= 0 && x_window_is_call)   // a tile of the call itself: its part of the caller's row, appended by the first bank on the slot
-                for (Deferred &d : deferred)
-                    if (d.slot == bs.grp.input_slot) {
-                        a.time = d.src + tile_off;
-                        a.time_skip = 0;
-                        a.time_valid = blen;
-                        a.hist_dst = (d.dst && !tile_appended.count(d.slot)) ? d.dst + tile_off : nullptr;
-                        tile_slots.insert(d.slot);
-                        tile_appended.insert(d.slot);
-                    }
-            a.rows = bs.d_rows.as<uint32_t>() + v0;
-            if (ring) {
-                a.out = d_rings.as<float>();
-                a.out_stride = ring_cap;
-                a.ring_mask = ring_cap - 1;
-                a.ring_t0 = b0;
-            } else if (ws) {
-                a.out = d_ws.as<float>() + sp.split.size() * (uint64_t)(tile_off > 0 ? tile_off : 0);   // tile-major workspace
-                a.out_stride = blen;
+    // ---- bank launches ----
+    // `trk`: where a voice that reads tracks finds them for a window (a span of the track history's ring), instead of the
+    // call's own matrix
+    struct TrackSrc { const float *p; uint64_t stride; uint32_t limit; };
+    // One launch's window and voices.  `tile_off` >= 0: a tile of the exchange window (b0 = x0 + tile_off), written to the
+    // tile-major workspace.  `v0`, `nv`: a run of the stage's voices (a repair renders only the voices whose rings it
+    // rebuilds; parameters and rows are voice-major, so a run is the same launch at offset pointers).
+    struct BankPart {
+        uint64_t b0, blen;
+        int64_t tile_off;
+        const TrackSrc *trk;
+        uint32_t v0, nv;
+        const BankPlan &bp;
+    };
+
+    // The caller's row of input `slot`, deferred to the bank launches (Deferred): a launch over the call's own frames reads
+    // it in place -- `len` frames from column `off` -- and the first bank on the slot appends them to the history (a tile of
+    // the exchange window: its own part, once per tile).
+    void take_deferred_row(uint32_t slot, uint64_t off, uint64_t len, bool tile, BankArgs &a) {
+        for (Deferred &d : deferred) {
+            if (d.slot != slot) continue;
+            a.time = d.src + off;
+            a.time_skip = 0;
+            a.time_valid = len;
+            if (tile) {
+                a.hist_dst = (d.dst && d.appended_tile != (int64_t)off) ? d.dst + off : nullptr;
+                d.appended_tile = (int64_t)off;
             } else {
-                a.out = d_dst;
-                a.out_stride = n_times;
+                a.hist_dst = d.dst;
+                d.dst = nullptr;
             }
-            a.n_voices = nv;
-            a.log2_p = bs.grp.log2_p;
-            a.n_times = blen;
-            a.fast_ok = bs.grp.fast_ok ? 1u : 0u;
-            if (bs.grp.jit) {
-                JitBankArgs j{};
-                j.params = bs.d_params.as<float>() + ((size_t)v0 << bs.grp.log2_p) * bs.grp.k;
-                for (size_t i = 0; i < bs.grp.shape.input_slots.size(); ++i)   // every input row over the same window
-                    input_window(bs.grp.shape.input_slots[i], b0, blen, j.in[i], j.in_skip[i], j.in_valid[i]);
-                j.out = a.out;
-                j.rows = a.rows;
-                j.out_stride = a.out_stride;
-                j.ring_mask = a.ring_mask;
-                j.ring_t0 = a.ring_t0;
-                j.n_times = blen;
-                j.n_voices = a.n_voices << bp.pieces_log2;
-                j.log2_p = bp.chunk_log2;
-                j.tiles = (uint32_t)((blen + 63) / 64);
-                j.nblocks = (uint32_t)bp.jit_blocks;
-                j.voices_per_wave = bp.voices_per_wave;
-                j.fract_ok = bs.grp.fast_ok ? 1u : 0u;
-                if (bp.pieces_log2) {   // every voice as pieces, to the kernel rows of a workspace, added up below in the tree's order
-                    used_scratch = true;   // (the pieces' workspace is shared between calls: no overlap with the next one on another stream)
-                    d_chunk_ws.ensure(bp.ws_floats * sizeof(float));
-                    if (d_chunk_rows_n < j.n_voices) {
-                        std::vector<uint32_t> seq(std::max<uint32_t>(j.n_voices, 4096));
-                        for (uint32_t i = 0; i < seq.size(); ++i) seq[i] = i;
-                        d_chunk_rows.ensure(seq.size() * sizeof(uint32_t));
-                        HIP_CHECK(hipMemcpyAsync(d_chunk_rows.p, seq.data(), seq.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-                        HIP_CHECK(hipStreamSynchronize(st));   // (`seq` is a stack object; once per growth)
-                        d_chunk_rows_n = (uint32_t)seq.size();
-                    }
-                    j.out = d_chunk_ws.as<float>();
-                    j.rows = d_chunk_rows.as<uint32_t>();
-                    j.out_stride = blen;
-                }
-                if (bs.grp.tracks && trk) {
-                    j.tracks = trk->p;
-                    j.track_stride = trk->stride;
-                    j.track_limit = trk->limit;
-                } else if (bs.grp.tracks && call_tracks) {
-                    if (b0 != idx || blen != n_times) throw Error(FR_ERR_UNSUPPORTED, "internal: a voice that reads tracks rendered over another window than the call's");
-                    j.tracks = call_tracks;
-                    j.track_stride = call_track_stride;
-                    j.track_limit = (uint32_t)std::min<uint64_t>((uint64_t)track_from + call_track_rows, 0xFFFFFFFFull);
-                }
-                note_bank_launch(bp, bs, nv, blen, flag_out.host_flags != nullptr);
-                Scope sc(this, &t_bank, st);
-                HIP_CHECK(launch_jit_bank(*bs.jit, j, st));
-                if (bp.pieces_log2) {
-                    ChunkCombineArgs c{};
-                    c.ws = d_chunk_ws.as<float>();
-                    c.out = a.out;
-                    c.rows = a.rows;
-                    c.out_stride = a.out_stride;
-                    c.n_times = blen;
-                    c.n_voices = a.n_voices;
-                    c.log2_c = bp.pieces_log2;
-                    HIP_CHECK(launch_chunk_combine(c, st));
-                }
-                sc.done();
-                return;
+        }
+    }
+
+    // One bank launch over the window [b0, b0 + blen): the arguments every kernel family shares, then the family's launch.
+    void launch_bank_part(const Call &c, BankStage &bs, uint64_t b0, uint64_t blen, int64_t tile_off, const TrackSrc *trk, uint32_t v0 = 0, uint32_t nv = UINT32_MAX) {
+        const bool whole = v0 == 0 && nv >= bs.grp.rows.size();
+        if (whole) nv = (uint32_t)bs.grp.rows.size();
+        else if (bs.grp.general || (uint64_t)v0 + nv > bs.grp.rows.size()) throw Error(FR_ERR_DEVICE, "internal: a run of voices the bank stage cannot launch");
+        const BankPlan bp = plan_bank_launch(bs, blen, flag_out.host_flags != nullptr, nv);   // (the one rule, asked about the run's voices)
+        const BankPart part{b0, blen, tile_off, trk, v0, nv, bp};
+        BankArgs a{};
+        a.params = bs.d_params.as<float2>() + ((size_t)v0 << bs.grp.log2_p);
+        input_window(bs.grp.input_slot, b0, blen, a.time, a.time_skip, a.time_valid);   // time-slot history for the window
+        if (tile_off < 0 && b0 == c.idx && blen == c.n_times) take_deferred_row(bs.grp.input_slot, 0, c.n_times, false, a);   // (direct output, or a ring in steady state)
+        if (tile_off >= 0 && c.x_window_is_call()) take_deferred_row(bs.grp.input_slot, (uint64_t)tile_off, blen, true, a);   // a tile of the call itself
+        a.rows = bs.d_rows.as<uint32_t>() + v0;
+        if (bs.grp.to_ring) {
+            a.out = d_rings.as<float>();
+            a.out_stride = ring_cap;
+            a.ring_mask = ring_cap - 1;
+            a.ring_t0 = b0;
+        } else if (bs.grp.to_ws) {
+            a.out = d_ws.as<float>() + plan.sp.split.size() * (uint64_t)(tile_off > 0 ? tile_off : 0);   // tile-major workspace
+            a.out_stride = blen;
+        } else {
+            a.out = c.dst;
+            a.out_stride = c.n_times;
+        }
+        a.n_voices = nv;
+        a.log2_p = bs.grp.log2_p;
+        a.n_times = blen;
+        a.fast_ok = bs.grp.fast_ok ? 1u : 0u;
+        a.voices_per_wave = part.bp.voices_per_wave;
+        if (bs.grp.jit) launch_compiled_bank(c, bs, part, a);
+        else if (bs.grp.general) launch_general_bank(c, bs, part, a);
+        else launch_template_bank(c, bs, part, a);
+    }
+
+    // Compiled voices (jit_bank): every input row over the same window; few voices on a short call as pieces, added up in
+    // the tree's order by the combine pass.
+    void launch_compiled_bank(const Call &c, BankStage &bs, const BankPart &pt, const BankArgs &a) {
+        const BankPlan &bp = pt.bp;
+        JitBankArgs j{};
+        j.params = bs.d_params.as<float>() + ((size_t)pt.v0 << bs.grp.log2_p) * bs.grp.k;
+        for (size_t i = 0; i < bs.grp.shape.input_slots.size(); ++i)
+            input_window(bs.grp.shape.input_slots[i], pt.b0, pt.blen, j.in[i], j.in_skip[i], j.in_valid[i]);
+        j.out = a.out;
+        j.rows = a.rows;
+        j.out_stride = a.out_stride;
+        j.ring_mask = a.ring_mask;
+        j.ring_t0 = a.ring_t0;
+        j.n_times = pt.blen;
+        j.n_voices = a.n_voices << bp.pieces_log2;
+        j.log2_p = bp.chunk_log2;
+        j.tiles = (uint32_t)((pt.blen + 63) / 64);
+        j.nblocks = (uint32_t)bp.jit_blocks;
+        j.voices_per_wave = bp.voices_per_wave;
+        j.fract_ok = a.fast_ok;
+        if (bp.pieces_log2) {   // every voice as pieces, to the kernel rows of a workspace, added up below in the tree's order
+            used_scratch = true;   // (the pieces' workspace is shared between calls: no overlap with the next one on another stream)
+            d_chunk_ws.ensure(bp.ws_floats * sizeof(float));
+            if (d_chunk_rows_n < j.n_voices) {
+                std::vector<uint32_t> seq(std::max<uint32_t>(j.n_voices, 4096));
+                for (uint32_t i = 0; i < seq.size(); ++i) seq[i] = i;
+                d_chunk_rows.ensure(seq.size() * sizeof(uint32_t));
+                HIP_CHECK(hipMemcpyAsync(d_chunk_rows.p, seq.data(), seq.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c.st));
+                HIP_CHECK(hipStreamSynchronize(c.st));   // (`seq` is a stack object; once per growth)
+                d_chunk_rows_n = (uint32_t)seq.size();
             }
-            a.voices_per_wave = bp.voices_per_wave;
-            if (bs.grp.general) {
-                a.groups = bs.d_groups.as<uint32_t>();
-                a.group_off = bs.d_group_off.as<uint32_t>();
-                a.hist_dst = nullptr;   // (the schedule kernel does not append history)
-                note_bank_launch(bp, bs, nv, blen, flag_out.host_flags != nullptr);
-                Scope sc(this, &t_bank, st);
-                HIP_CHECK(launch_gbank(a, st));
-                sc.done();
-                return;
+            j.out = d_chunk_ws.as<float>();
+            j.rows = d_chunk_rows.as<uint32_t>();
+            j.out_stride = pt.blen;
+        }
+        if (bs.grp.tracks && pt.trk) {
+            j.tracks = pt.trk->p;
+            j.track_stride = pt.trk->stride;
+            j.track_limit = pt.trk->limit;
+        } else if (bs.grp.tracks && call_tracks) {
+            if (pt.b0 != c.idx || pt.blen != c.n_times) throw Error(FR_ERR_UNSUPPORTED, "internal: a voice that reads tracks rendered over another window than the call's");
+            j.tracks = call_tracks;
+            j.track_stride = call_track_stride;
+            j.track_limit = (uint32_t)std::min<uint64_t>((uint64_t)track_from + call_track_rows, 0xFFFFFFFFull);
+        }
+        note_bank_launch(bp, bs, pt.nv, pt.blen, flag_out.host_flags != nullptr);
+        Scope sc(this, &t_bank, c.st);
+        HIP_CHECK(launch_jit_bank(*bs.jit, j, c.st));
+        if (bp.pieces_log2) {
+            ChunkCombineArgs cc{};
+            cc.ws = d_chunk_ws.as<float>();
+            cc.out = a.out;
+            cc.rows = a.rows;
+            cc.out_stride = a.out_stride;
+            cc.n_times = pt.blen;
+            cc.n_voices = a.n_voices;
+            cc.log2_c = bp.pieces_log2;
+            HIP_CHECK(launch_chunk_combine(cc, c.st));
+        }
+        sc.done();
+    }
+
+    // General trees (gbank): the schedule kernel.
+    void launch_general_bank(const Call &c, BankStage &bs, const BankPart &pt, BankArgs &a) {
+        a.groups = bs.d_groups.as<uint32_t>();
+        a.group_off = bs.d_group_off.as<uint32_t>();
+        a.hist_dst = nullptr;   // (the schedule kernel does not append history)
+        note_bank_launch(pt.bp, bs, pt.nv, pt.blen, flag_out.host_flags != nullptr);
+        Scope sc(this, &t_bank, c.st);
+        HIP_CHECK(launch_gbank(a, c.st));
+        sc.done();
+    }
+
+    // Balanced template voices: the hand-written kernels, in the shape bankplan.hpp picked.
+    void launch_template_bank(const Call &c, BankStage &bs, const BankPart &pt, BankArgs &a) {
+        const BankPlan &bp = pt.bp;
+        if (a.hist_dst && !bp.appends_rows) throw Error(FR_ERR_DEVICE, "internal: deferred history append on a short call");
+        a.chunk_log2 = bp.chunk_log2;
+        a.frames_per_lane = bp.frames_per_lane;
+        a.waves_per_group = bp.waves_per_group;
+        a.small_call = bp.small_call;
+        a.leaf_variant = bank_tune.leaf_variant;
+        if (flag_out.host_flags) {
+            if (!bp.publishes_rows) throw Error(FR_ERR_DEVICE, "internal: a bank launch cannot publish row flags");
+            a.host_flags = flag_out.host_flags;
+            a.row_done = flag_out.row_done;
+            a.flag_value = flag_out.value;
+        }
+        if (bp.ws_floats) {
+            used_scratch = true;
+            d_bank_ws.ensure(bp.ws_floats * sizeof(float));
+            a.ws = d_bank_ws.as<float>();
+            if (bp.ticket_words) a.tickets = ticket_counters(bp.ticket_words, c.st);
+        }
+        note_bank_launch(bp, bs, pt.nv, pt.blen, flag_out.host_flags != nullptr);
+        Scope sc(this, &t_bank, c.st);
+        HIP_CHECK(launch_bank(a, c.st));
+        sc.done();
+    }
+
+    // A voice that reads tracks over a window that starts before idx (it feeds a delay line: the call after a seek, an edit
+    // or a ring growth) is launched per span: the frames before idx from the track history, cut again where its ring
+    // wraps, then the call's own frames as in steady state.  Every span is the same generated kernel.
+    void launch_bank_window(const Call &c, BankStage &bs, uint64_t b0, uint64_t blen, int64_t tile_off) {
+        if (!(bs.grp.tracks && tail_on() && tile_off < 0 && b0 < c.idx && b0 + blen == c.idx + c.n_times)) {
+            launch_bank_part(c, bs, b0, blen, tile_off, nullptr);
+            return;
+        }
+        for (uint64_t s0 = b0; s0 < c.idx;) {
+            const uint64_t pos = s0 & (tail_cap - 1);
+            const uint64_t len = std::min(c.idx - s0, tail_cap - pos);
+            TrackSrc ts{nullptr, tail_cap, 0};
+            if (tail_rows) {
+                ts.p = reinterpret_cast<const float *>(reinterpret_cast<uintptr_t>(d_tail.as<float>() + pos) - (uintptr_t)track_from * tail_cap * sizeof(float));
+                ts.limit = (uint32_t)std::min<uint64_t>((uint64_t)track_from + tail_rows, 0xFFFFFFFFull);
             }
-            if (a.hist_dst && !bp.appends_rows) throw Error(FR_ERR_DEVICE, "internal: deferred history append on a short call");
-            a.chunk_log2 = bp.chunk_log2;
-            a.frames_per_lane = bp.frames_per_lane;
-            a.waves_per_group = bp.waves_per_group;
-            a.small_call = bp.small_call;
-            a.leaf_variant = bank_tune.leaf_variant;
-            if (flag_out.host_flags) {
-                if (!bp.publishes_rows) throw Error(FR_ERR_DEVICE, "internal: a bank launch cannot publish row flags");
-                a.host_flags = flag_out.host_flags;
-                a.row_done = flag_out.row_done;
-                a.flag_value = flag_out.value;
-            }
-            if (bp.ws_floats) {
-                used_scratch = true;
-                d_bank_ws.ensure(bp.ws_floats * sizeof(float));
-                a.ws = d_bank_ws.as<float>();
-                if (bp.ticket_words) {   // arrival counters of the in-launch combine: zero between launches (the kernel resets them)
-                    const size_t need = bp.ticket_words * sizeof(uint32_t);
-                    clean_counters(st);
-                    if (need > d_tickets.bytes) {
-                        d_tickets.ensure(need * 2);
-                        HIP_CHECK(hipMemsetAsync(d_tickets.p, 0, d_tickets.bytes, st));
-                    }
-                    a.tickets = d_tickets.as<uint32_t>();
-                }
-            }
-            note_bank_launch(bp, bs, nv, blen, flag_out.host_flags != nullptr);
-            Scope sc(this, &t_bank, st);
-            HIP_CHECK(launch_bank(a, st));
-            sc.done();
-        };
-        // A voice that reads tracks over a window that starts before idx (it feeds a delay line: the call after a seek, an edit
-        // or a ring growth) is launched per span: the frames before idx from the track history, cut again where its ring
-        // wraps, then the call's own frames as in steady state.  Every span is the same generated kernel.
-        auto launch_bank_window = [&](BankStage &bs, uint64_t b0, uint64_t blen, int64_t tile_off) {
-            if (!(bs.grp.tracks && tail_on() && tile_off < 0 && b0 < idx && b0 + blen == idx + n_times)) {
-                launch_bank_part(bs, b0, blen, tile_off, nullptr);
-                return;
-            }
-            for (uint64_t s0 = b0; s0 < idx;) {
-                const uint64_t pos = s0 & (tail_cap - 1);
-                const uint64_t len = std::min(idx - s0, tail_cap - pos);
-                TrackSrc ts{nullptr, tail_cap, 0};
-                if (tail_rows) {
-                    ts.p = reinterpret_cast<const float *>(reinterpret_cast<uintptr_t>(d_tail.as<float>() + pos) - (uintptr_t)track_from * tail_cap * sizeof(float));
-                    ts.limit = (uint32_t)std::min<uint64_t>((uint64_t)track_from + tail_rows, 0xFFFFFFFFull);
-                }
-                launch_bank_part(bs, s0, len, -1, &ts);
-                s0 += len;
-            }
-            launch_bank_part(bs, idx, n_times, -1, nullptr);
-        };
-        // Stage programs: the input table of a launch and the launch itself (a range of programs over a window of frames).
-        std::vector<DevInput> tab(sp.input_slots.size());
-        auto fill_tab = [&] {
-            for (size_t i = 0; i < tab.size(); ++i) tab[i] = dev_input(sp.input_slots[i]);
-            if (tab.size() > STAGE_INLINE_INPUTS) {   // rare: more input slots than fit in the kernel arguments
-                d_in_table_stage.ensure(tab.size() * sizeof(DevInput));
-                HIP_CHECK(hipMemcpyAsync(d_in_table_stage.p, tab.data(), tab.size() * sizeof(DevInput), hipMemcpyHostToDevice, st));
-                HIP_CHECK(hipStreamSynchronize(st));   // `tab` is a stack object
-            }
-        };
-        uint64_t launch_stride = 0;
-        const char *launch_form = "levels";
-        auto launch_range = [&](uint32_t first, uint32_t count, uint64_t s0, uint64_t slen) {
-            if (count && stage_launches.size() < 256) {
-                const bool carry_only = launch_stride && sp.feedback && sp.fused_carry_only;
-                stage_launches.push_back({launch_form, plan.stage_jit != nullptr, count, slen, launch_stride, launch_stride && sp.feedback,
-                                          carry_only, tab.size() > STAGE_INLINE_INPUTS, (count - 1) / 65535u + 1});
-            }
-            for (uint32_t off = 0; off < count && plan.stage_jit; off += 65535u) {   // grid.y limit
+            launch_bank_part(c, bs, s0, len, -1, &ts);
+            s0 += len;
+        }
+        launch_bank_part(c, bs, c.idx, c.n_times, -1, nullptr);
+    }
+
+    // ---- stage launches ----
+    // The input table of the call's stage launches (the inputs as they stand when the launches are enqueued).
+    std::vector<DevInput> stage_tab;
+    void fill_stage_tab(hipStream_t st) {
+        const StagedPlan &sp = plan.sp;
+        stage_tab.resize(sp.input_slots.size());
+        for (size_t i = 0; i < stage_tab.size(); ++i) stage_tab[i] = dev_input(sp.input_slots[i]);
+        if (stage_tab.size() > STAGE_INLINE_INPUTS) {   // rare: more input slots than fit in the kernel arguments
+            d_in_table_stage.ensure(stage_tab.size() * sizeof(DevInput));
+            HIP_CHECK(hipMemcpyAsync(d_in_table_stage.p, stage_tab.data(), stage_tab.size() * sizeof(DevInput), hipMemcpyHostToDevice, st));
+            HIP_CHECK(hipStreamSynchronize(st));   // (the table is rewritten by the next fill)
+        }
+    }
+    // What a stage launch is for (StageLaunchNote::form) and the frames its threads stride by (0: one frame per thread).
+    struct StageLaunch { const char *form; uint64_t stride; };
+    // The fields JitStageArgs and StageArgs share.
+    template <class Args>
+    void fill_stage_args(Args &a, const Call &c, const StageLaunch &how, uint64_t s0, uint64_t slen, bool carry_only) const {
+        a.rings = d_rings.as<float>();
+        a.ring_mask = ring_cap ? ring_cap - 1 : 0;
+        a.n_inputs = (uint32_t)stage_tab.size();
+        a.out = c.dst;
+        a.n_times = c.n_times;
+        a.idx = c.idx;
+        a.w0 = s0;
+        a.w_len = slen;
+        a.stride = how.stride;
+        a.carry_only = carry_only ? 1u : 0u;
+    }
+    // Programs [first, first + count) over the frames [s0, s0 + slen), in launches of at most 65535 programs (grid.y).
+    void launch_range(const Call &c, const StageLaunch &how, uint32_t first, uint32_t count, uint64_t s0, uint64_t slen) {
+        const StagedPlan &sp = plan.sp;
+        const bool carry = how.stride && sp.feedback, carry_only = carry && sp.fused_carry_only;
+        const size_t n_inline = std::min<size_t>(stage_tab.size(), STAGE_INLINE_INPUTS);
+        if (count && stage_launches.size() < 256)
+            stage_launches.push_back({how.form, plan.stage_jit != nullptr, count, slen, how.stride, carry, carry_only,
+                                      stage_tab.size() > STAGE_INLINE_INPUTS, (count - 1) / 65535u + 1});
+        for (uint32_t off = 0; off < count; off += 65535u) {
+            const uint32_t n = std::min<uint32_t>(count - off, 65535u);
+            Scope sc(this, &t_stage, c.st);
+            if (plan.stage_jit) {
                 JitStageArgs a{};
+                fill_stage_args(a, c, how, s0, slen, carry_only);
                 a.ptab = plan.d_ptab.as<uint32_t>();
                 a.progs = plan.d_jprogs.as<JitStageProg>() + first + off;
-                a.rings = d_rings.as<float>();
-                a.ring_mask = ring_cap ? ring_cap - 1 : 0;
                 a.inputs = reinterpret_cast<const JitInput *>(d_in_table_stage.as<DevInput>());
-                a.n_inputs = (uint32_t)tab.size();
-                for (size_t i = 0; i < tab.size() && i < STAGE_INLINE_INPUTS; ++i) a.inline_inputs[i] = JitInput{tab[i].data, tab[i].base, tab[i].len};
-                a.out = d_dst;
-                a.n_times = n_times;
-                a.idx = idx;
-                a.w0 = s0;
-                a.w_len = slen;
-                a.stride = launch_stride;
-                a.carry_only = (launch_stride && sp.feedback && sp.fused_carry_only) ? 1u : 0u;
-                Scope sc(this, &t_stage, st);
-                HIP_CHECK(launch_jit_stage(*plan.stage_jit, a, std::min<uint32_t>(count - off, 65535u), st));
-                sc.done();
-            }
-            for (uint32_t off = 0; off < count && !plan.stage_jit; off += 65535u) {
+                for (size_t i = 0; i < n_inline; ++i) a.inline_inputs[i] = JitInput{stage_tab[i].data, stage_tab[i].base, stage_tab[i].len};
+                HIP_CHECK(launch_jit_stage(*plan.stage_jit, a, n, c.st));
+            } else {
                 StageArgs a{};
+                fill_stage_args(a, c, how, s0, slen, carry_only);
                 a.instrs = plan.d_instrs.as<StageInstr>();
                 a.progs = plan.d_progs.as<StageProg>() + first + off;
-                a.n_progs = std::min<uint32_t>(count - off, 65535u);
-                a.rings = d_rings.as<float>();
-                a.ring_mask = ring_cap ? ring_cap - 1 : 0;
+                a.n_progs = n;
                 a.inputs = d_in_table_stage.as<DevInput>();
-                a.n_inputs = (uint32_t)tab.size();
-                for (size_t i = 0; i < tab.size() && i < STAGE_INLINE_INPUTS; ++i) a.inline_inputs[i] = tab[i];
-                a.out = d_dst;
-                a.n_times = n_times;
-                a.idx = idx;
-                a.w0 = s0;
-                a.w_len = slen;
-                a.stride = launch_stride;
-                a.carry_only = (launch_stride && sp.feedback && sp.fused_carry_only) ? 1u : 0u;
-                a.use_carry = (launch_stride && sp.feedback) ? 1u : 0u;
+                for (size_t i = 0; i < n_inline; ++i) a.inline_inputs[i] = stage_tab[i];
+                a.use_carry = carry ? 1u : 0u;
                 a.sparkle = mirror.sparkle ? 1u : 0u;
-                Scope sc(this, &t_stage, st);
-                HIP_CHECK(launch_stage(a, st));
-                sc.done();
+                HIP_CHECK(launch_stage(a, c.st));
             }
-        };
-        auto launch_fused_levels = [&](uint64_t s0, uint64_t slen, const char *form) {   // a feedback plan's fused form: a strided launch per level
-            launch_form = form;
-            launch_stride = sp.fused_stride;
-            for (size_t l = 0; l + 1 < sp.fused_level_first.size(); ++l)
-                launch_range(sp.fused_first + sp.fused_level_first[l], sp.fused_level_first[l + 1] - sp.fused_level_first[l], s0, slen);
-            launch_stride = 0;
-        };
-        if (!repair.empty()) {
-            // Kept rings (FR_RING_KEEP): the rings to rebuild are brought up to idx -- their voices, then their programs level by
-            // level, nothing written to the output -- over the look-back window, or for a feedback plan's loops from frame 0
-            fill_tab();
-            bank_form = repair.replay ? "replay" : "repair";
-            struct FormReset { const char *&f; ~FormReset() { f = "call"; } } form_reset{bank_form};
-            for (uint64_t c0 = repair.from; c0 < idx;) {
-                const uint64_t len = repair.replay ? std::min<uint64_t>(FB_CHUNK, idx - c0) : idx - c0;
-                for (const RingRepair::Run &run : repair.voices) launch_bank_part(plan.banks[run.stage], c0, len, -1, nullptr, run.first, run.count);
-                launch_form = bank_form;
-                launch_stride = repair.replay ? sp.fused_stride : 0;
-                for (const auto &level : repair.levels)
-                    for (const auto &run : level) launch_range(run.first, run.second, c0, len);
-                launch_stride = 0;
-                c0 += len;
-            }
+            sc.done();
         }
-        if (fb_replay) {
-            fill_tab();
-            for (uint64_t c0 = 0; c0 < idx; c0 += FB_CHUNK) {
-                const uint64_t len = std::min<uint64_t>(FB_CHUNK, idx - c0);
-                for (BankStage &bs : plan.banks)
-                    if (bs.grp.to_ring) launch_bank_window(bs, c0, len, -1);
-                launch_fused_levels(c0, len, "replay");
-            }
+    }
+    // A feedback plan's fused form: a strided launch per level.
+    void launch_fused_levels(const Call &c, const char *form, uint64_t s0, uint64_t slen) {
+        const StagedPlan &sp = plan.sp;
+        for (size_t l = 0; l + 1 < sp.fused_level_first.size(); ++l)
+            launch_range(c, {form, sp.fused_stride}, sp.fused_first + sp.fused_level_first[l], sp.fused_level_first[l + 1] - sp.fused_level_first[l], s0, slen);
+    }
+
+    // ---- the call's phases ----
+    // Kept rings (FR_RING_KEEP): the rings to rebuild are brought up to idx -- their voices, then their programs level by
+    // level, nothing written to the output -- over the look-back window, or for a feedback plan's loops from frame 0
+    void repair_rings(const Call &c, const RingRepair &repair) {
+        if (repair.empty()) return;
+        fill_stage_tab(c.st);
+        bank_form = repair.replay ? "replay" : "repair";
+        const StageLaunch how{bank_form, repair.replay ? plan.sp.fused_stride : 0};
+        for (uint64_t c0 = repair.from; c0 < c.idx;) {
+            const uint64_t len = repair.replay ? std::min<uint64_t>(FB_CHUNK, c.idx - c0) : c.idx - c0;
+            for (const RingRepair::Run &run : repair.voices) launch_bank_part(c, plan.banks[run.stage], c0, len, -1, nullptr, run.first, run.count);
+            for (const auto &level : repair.levels)
+                for (const auto &run : level) launch_range(c, how, run.first, run.second, c0, len);
+            c0 += len;
         }
-        // The exchange window first, tile by tile, every tile's bank kernels on the call's stream; then the tiles' exchanges on
-        // the exchange stream, each behind its tile's event: tile i's exchange runs under the bank kernels of tiles i + 1 ...
-        // (also with a transport that blocks the host: the kernels are all enqueued before the first exchange starts).
-        const bool pipelined = !sp.split.empty() && xt.size() > 1;
-        if (pipelined) {
+        bank_form = "call";   // (a failure in between: execute() starts every call with it)
+    }
+    // A feedback plan whose rings are not current: every frame from 0 replayed in chunks -- the ring-bound banks and the fused
+    // programs over [c0, c0 + len), nothing written to the output -- before the call's own frames run in steady-state form.
+    void replay_feedback(const Call &c) {
+        if (!c.w.fb_replay) return;
+        fill_stage_tab(c.st);
+        for (uint64_t c0 = 0; c0 < c.idx; c0 += FB_CHUNK) {
+            const uint64_t len = std::min<uint64_t>(FB_CHUNK, c.idx - c0);
+            for (BankStage &bs : plan.banks)
+                if (bs.grp.to_ring) launch_bank_window(c, bs, c0, len, -1);
+            launch_fused_levels(c, "replay", c0, len);
+        }
+    }
+    // Split voices (partial-block sharding).  The exchange window first, tile by tile, every tile's bank kernels on the call's
+    // stream; then the tiles' exchanges on the exchange stream, each behind its tile's event: tile i's exchange runs under the
+    // bank kernels of tiles i + 1 ... (also with a transport that blocks the host: the kernels are all enqueued before the
+    // first exchange starts).  One tile = the serial form of round 2, all on the call's stream.
+    void exchange_split_voices(const Call &c) {
+        const StagedPlan &sp = plan.sp;
+        if (sp.split.empty()) return;
+        used_scratch = true;
+        d_ws.ensure(sp.split.size() * c.w.xlen * sizeof(float));
+        d_xrecv.ensure(sp.split.size() * c.w.xlen * sizeof(float));
+        if (c.pipelined()) {
             if (!xstream) HIP_CHECK(hipStreamCreateWithFlags(&xstream, hipStreamNonBlocking));
-            while (x_events.size() < xt.size() + 1) {
+            while (x_events.size() < c.xt.count + 1) {
                 hipEvent_t e;
                 HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
                 x_events.push_back(e);
             }
         }
-        if (!sp.split.empty()) {
-            ++exchange_calls;
-            exchange_tiles += xt.size();
-        }
-        for (size_t ti = 0; ti < xt.size(); ++ti) {
-            tile_appended.clear();       // (each tile appends its own part of a deferred row, once)
+        ++exchange_calls;
+        exchange_tiles += c.xt.count;
+        for (uint32_t ti = 0; ti < c.xt.count; ++ti) {
             for (BankStage &bs : plan.banks)
-                if (bs.grp.to_ws) launch_bank_window(bs, x0 + xt[ti].first, xt[ti].second, (int64_t)xt[ti].first);
-            if (pipelined) HIP_CHECK(hipEventRecord(x_events[ti], st));
+                if (bs.grp.to_ws) launch_bank_window(c, bs, c.w.x0 + c.xt.offset(ti), c.xt.frames(ti), (int64_t)c.xt.offset(ti));
+            if (c.pipelined()) HIP_CHECK(hipEventRecord(x_events[ti], c.st));
         }
-        for (size_t ti = 0; ti < xt.size(); ++ti) {
-            if (pipelined) HIP_CHECK(hipStreamWaitEvent(xstream, x_events[ti], 0));
-            run_exchange(d_dst, n_times, idx, x0, xt[ti].first, xt[ti].second, pipelined ? xstream : st);
+        for (uint32_t ti = 0; ti < c.xt.count; ++ti) {
+            if (c.pipelined()) HIP_CHECK(hipStreamWaitEvent(xstream, x_events[ti], 0));
+            run_exchange(c.dst, c.n_times, c.idx, c.w.x0, c.xt.offset(ti), c.xt.frames(ti), c.pipelined() ? xstream : c.st);
         }
-        if (!xt.empty() && x_window_is_call)
-            for (Deferred &d : deferred)
-                if (tile_slots.count(d.slot)) d.dst = nullptr;               // appended tile by tile
-        // everything else (voices that stay whole on this rank, unsharded plans) -- overlapping the exchange's tail
+        for (Deferred &d : deferred)
+            if (d.appended_tile >= 0) d.dst = nullptr;   // appended tile by tile
+    }
+    // Everything else (voices that stay whole on this rank, unsharded plans) -- overlapping the exchange's tail; the call's
+    // stream then goes on only behind the last tile's exchange.
+    void launch_whole_banks(const Call &c) {
         for (BankStage &bs : plan.banks) {
             if (bs.grp.to_ws) continue;
             const bool ring = bs.grp.to_ring;
-            launch_bank_window(bs, ring ? w0 : idx, ring ? w_len : n_times, -1);
+            launch_bank_window(c, bs, ring ? c.w.w0 : c.idx, ring ? c.w.w_len : c.n_times, -1);
         }
-        if (pipelined) {   // the call's stream goes on only behind the last tile's exchange
-            HIP_CHECK(hipEventRecord(x_events[xt.size()], xstream));
-            HIP_CHECK(hipStreamWaitEvent(st, x_events[xt.size()], 0));
+        if (c.pipelined()) {
+            HIP_CHECK(hipEventRecord(x_events[c.xt.count], xstream));
+            HIP_CHECK(hipStreamWaitEvent(c.st, x_events[c.xt.count], 0));
         }
-
         for (const Deferred &d : deferred)
             if (d.dst) throw Error(FR_ERR_DEVICE, "internal: an input row deferred to the bank launch was not appended");
-        if (!sp.progs.empty()) {
-            fill_tab();
-            // Steady state: every delayed ring read of the fused form reaches at least fused_max_frames back, so the call
-            // is cut into sub-windows of that length, one fused launch each, when that takes fewer launches than levels.
-            const size_t n_levels = sp.level_first.size() - 1;
-            const uint64_t fused_step = std::max<uint64_t>(sp.fused_max_frames, 1);
-            const uint64_t n_sub = sp.fused_count ? (n_times - 1) / fused_step + 1 : 0;   // (n_times > 0 here; no overflow)
-            const bool fused = sp.fused_count != 0 && w0 == idx && rings_current && n_sub < n_levels;
-            // ... or ONE launch whose threads stride through the sub-windows themselves, when every delayed read of a program ring
-            // reaches back a multiple of fused_stride frames into a ring its own program stores (the delay chains of an effects
-            // patch: 2400, 4800, 7200 ...): a thread then reads only what it stored itself.  Worth it for a handful of strides
-            // (each one is a dependent round trip to memory inside the launch; a launch boundary costs ~5 us at this size).
-            const uint64_t strided_sub = sp.fused_stride ? (n_times - 1) / sp.fused_stride + 1 : 0;
-            const bool strided = sp.fused_count != 0 && w0 == idx && rings_current && sp.fused_stride >= 256 && strided_sub >= 2 &&
-                                 strided_sub <= 8 && fused_strided_ok;
-            if (sp.feedback) {
-                launch_fused_levels(idx, n_times, "feedback");
-                launch_form = "copy";
-                launch_range(sp.post_first, sp.post_count, idx, n_times);
-            } else if (strided) {
-                launch_form = "strided";
-                launch_stride = sp.fused_stride;
-                launch_range(sp.fused_first, sp.fused_count, idx, n_times);
-                launch_stride = 0;
-            } else if (fused) {
-                launch_form = "fused";
-                for (uint64_t done = 0; done < n_times;) {   // by frames still to do: no sum that could wrap
-                    const uint64_t len = std::min<uint64_t>(fused_step, n_times - done);
-                    launch_range(sp.fused_first, sp.fused_count, idx + done, len);
-                    done += len;
-                }
-            } else {
-                launch_form = "levels";
-                for (size_t l = 0; l < n_levels; ++l)
-                    launch_range(sp.level_first[l], sp.level_first[l + 1] - sp.level_first[l], w0, w_len);
+    }
+    // The call's stage programs, in the form callplan.hpp picked (StageForm).
+    void launch_stage_programs(const Call &c) {
+        const StagedPlan &sp = plan.sp;
+        if (c.form.kind == StageForm::none) return;
+        fill_stage_tab(c.st);
+        switch (c.form.kind) {
+        case StageForm::feedback:
+            launch_fused_levels(c, "feedback", c.idx, c.n_times);
+            launch_range(c, {"copy", 0}, sp.post_first, sp.post_count, c.idx, c.n_times);
+            break;
+        case StageForm::strided:
+            launch_range(c, {"strided", sp.fused_stride}, sp.fused_first, sp.fused_count, c.idx, c.n_times);
+            break;
+        case StageForm::fused:
+            for (uint64_t done = 0; done < c.n_times;) {   // by frames still to do: no sum that could wrap
+                const uint64_t len = std::min<uint64_t>(c.form.fused_step, c.n_times - done);
+                launch_range(c, {"fused", 0}, sp.fused_first, sp.fused_count, c.idx + done, len);
+                done += len;
             }
+            break;
+        default:
+            for (size_t l = 0; l + 1 < sp.level_first.size(); ++l)
+                launch_range(c, {"levels", 0}, sp.level_first[l], sp.level_first[l + 1] - sp.level_first[l], c.w.w0, c.w.w_len);
         }
-        if (sp.uses_rings()) {
-            plan.stage_valid = true;
-            plan.stage_end = idx + n_times;
-            if (keep_on) {                   // the call's frames are in; the oldest ones of a full ring are gone
-                ring_table.end = idx + n_times;
-                const uint64_t oldest = ring_table.end > ring_cap ? ring_table.end - ring_cap : 0;
-                for (RingEntry &e : ring_table.rings) e.valid_from = std::max(e.valid_from, oldest);
-                ring_table.valid = true;
-            }
+    }
+    // The rings now hold the plan's frames up to the call's end.
+    void commit_rings(const Call &c) {
+        if (!plan.sp.uses_rings()) return;
+        plan.stage_valid = true;
+        plan.stage_end = c.idx + c.n_times;
+        if (c.keep_on) {                   // the call's frames are in; the oldest ones of a full ring are gone
+            ring_table.end = c.idx + c.n_times;
+            const uint64_t oldest = ring_table.end > ring_cap ? ring_table.end - ring_cap : 0;
+            for (RingEntry &e : ring_table.rings) e.valid_from = std::max(e.valid_from, oldest);
+            ring_table.valid = true;
         }
-        if (!plan.pull_rows.empty()) run_pull(d_dst, n_slots, n_times, idx, st);
-        append_tracks(n_times, idx, st);
     }
 
     void run_pull(float *d_dst, uint32_t n_slots, uint64_t n_times, uint64_t idx, hipStream_t st) {
@@ -2122,17 +2137,7 @@ void fr_renderer::begin_program_stream(uint32_t n_slots) {
     HIP_CHECK(hipMemcpyAsync(d_stream_vfirst.p, s.voice_first.data(), s.voice_first.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
     HIP_CHECK(hipStreamSynchronize(stream));   // (host vectors go out of scope)
     // rings: the deepest look-back and a block, as execute() sizes them for a 64-frame call (which the seek then finds in place)
-    if (sp.uses_rings()) {
-        uint64_t cap = 1024;
-        while (cap < sp.lmax + STREAM_BLOCK) cap <<= 1;
-        cap = std::max(cap, ring_cap);
-        if (cap > ring_cap || (size_t)sp.n_rings * cap * sizeof(float) > d_rings.bytes) {
-            d_rings.ensure((size_t)sp.n_rings * cap * sizeof(float));
-            ring_cap = cap;
-            plan.stage_valid = false;
-            ring_table.valid = false;
-        }
-    }
+    if (sp.uses_rings()) grow_rings(ring_capacity(sp, STREAM_BLOCK));
     h_stream_ctl.ensure(sizeof(BankStreamCtl));
     h_stream_out.ensure((size_t)n_slots * 64 * sizeof(float));
     d_stream_dev.ensure(sizeof(BankStreamDev));
@@ -2194,13 +2199,7 @@ void fr_renderer::seek_program_stream(uint64_t idx) {
     if (s.chunks > 1) {
         d_bank_ws.ensure((size_t)s.voices * s.chunks * 64 * sizeof(float));
         a.ws = d_bank_ws.as<float>();
-        const size_t need = (size_t)s.voices * BANK_TICKET_STRIDE * sizeof(uint32_t);
-        clean_counters(stream);
-        if (need > d_tickets.bytes) {
-            d_tickets.ensure(need * 2);
-            HIP_CHECK(hipMemsetAsync(d_tickets.p, 0, d_tickets.bytes, stream));
-        }
-        a.tickets = d_tickets.as<uint32_t>();
+        a.tickets = ticket_counters((size_t)s.voices * BANK_TICKET_STRIDE, stream);
     }
     a.out = h_stream_out.as_dev<float>();
     a.out_stride = 64;
@@ -2776,13 +2775,7 @@ fr_status fr_stream_begin(fr_renderer *r, uint32_t n_slots) {
         if (c != a.log2_p) {
             r->d_bank_ws.ensure(((size_t)n_slots << (a.log2_p - c)) * 64 * sizeof(float));
             a.ws = r->d_bank_ws.as<float>();
-            const size_t need = (size_t)n_slots * BANK_TICKET_STRIDE * sizeof(uint32_t);
-            r->clean_counters(r->stream);
-            if (need > r->d_tickets.bytes) {
-                r->d_tickets.ensure(need * 2);
-                HIP_CHECK(hipMemsetAsync(r->d_tickets.p, 0, r->d_tickets.bytes, r->stream));
-            }
-            a.tickets = r->d_tickets.as<uint32_t>();
+            a.tickets = r->ticket_counters((size_t)n_slots * BANK_TICKET_STRIDE, r->stream);
         }
         r->h_stream_ctl.ensure(sizeof(BankStreamCtl));
         r->h_stream_out.ensure((size_t)n_slots * 64 * sizeof(float));

@@ -759,7 +759,7 @@ StagedPlan plan_stages(const FlatGraph &g, bool allow_banks, bool allow_programs
     }
     if (feedback) {
         // The look-back of a loop has no bound; the rings are never rebuilt from a window.  They are brought up to date by
-        // replaying the frames from 0 in order (engine.cpp execute()), so a ring only ever serves its readers' own delays.
+        // replaying the frames from 0 in order (engine.cpp replay_feedback), so a ring only ever serves its readers' own delays.
         sp.lmax = 0;
         for (auto &kv : built)
             for (auto &rd : kv.second.reads) sp.lmax = std::max(sp.lmax, rd.second);

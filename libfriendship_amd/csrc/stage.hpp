@@ -76,7 +76,7 @@ struct StagedPlan {
     uint32_t fused_first = 0, fused_count = 0;
     uint64_t fused_max_frames = 0;
     // gcd of the delays of the fused form's reads of program rings (0: there are none).  A call longer than
-    // fused_max_frames is still ONE launch when its threads stride by this many frames (engine.cpp execute()).
+    // fused_max_frames is still ONE launch when its threads stride by this many frames (callplan.hpp StageForm).
     uint64_t fused_stride = 0;
     // Feedback plans (graph.hpp OP_FBREF): the fused form is the only valid one and always runs strided; its programs are
     // ordered in levels (progs[fused_first + fused_level_first[l] .. fused_first + fused_level_first[l + 1]), one launch each),

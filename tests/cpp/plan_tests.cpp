@@ -22,6 +22,7 @@
 #include "../../libfriendship_amd/csrc/stage.cpp"
 #include "../../libfriendship_amd/csrc/stagejit.cpp"
 #include "../../libfriendship_amd/csrc/leafjit.cpp"
+#include "../../libfriendship_amd/csrc/callplan.hpp"
 
 using namespace fr;
 
@@ -183,7 +184,7 @@ static float bank_voice_host(const BankLaunch &bl, size_t v, float t) {
     return st[0];
 }
 
-// Executes a StagedPlan call by call like engine.cpp does (rings by absolute time; level or fused form).
+// Executes a StagedPlan call by call like engine.cpp does (rings by absolute time; the form callplan.hpp picks).
 struct StagedSim {
     const StagedPlan &sp;
     std::vector<std::map<uint64_t, float>> rings;
@@ -235,14 +236,16 @@ struct StagedSim {
     }
 
     // renders [idx, idx+T) into out [n_rows, T]; `force_levels` disables the fused form
+    // (the windows and the launch form are the engine's own rule, callplan.hpp; min_stride 16 keeps small strided cases reachable)
     void call(uint64_t idx, uint64_t T, const Inputs &in, std::vector<float> &out, bool force_levels, bool *used_fused = nullptr) {
-        uint64_t w0 = idx;
-        if (sp.uses_rings() && !(valid && end == idx)) {
-            w0 = idx > sp.lmax ? idx - sp.lmax : 0;
+        const CallIn ci{idx, T, valid && end == idx, false, false};
+        const CallWindows cw = call_windows(sp, ci);
+        StageForm form = stage_form(sp, ci, cw, 16, true);
+        CHECK(form.kind != StageForm::feedback);   // (no feedback plans here: the replay is not emulated)
+        if (force_levels && form.kind != StageForm::none) form.kind = StageForm::levels;
+        if (sp.uses_rings() && !cw.rings_current)
             for (auto &r : rings) r.clear();   // stale contents must not leak into results
-            valid = false;
-        }
-        uint64_t wlen = idx + T - w0;
+        const uint64_t w0 = cw.w0, wlen = cw.w_len;
         for (const BankLaunch &bl : sp.banks)
             for (size_t v = 0; v < bl.rows.size(); ++v) {
                 uint64_t b0 = bl.to_ring ? w0 : idx, blen = bl.to_ring ? wlen : T;
@@ -252,31 +255,25 @@ struct StagedSim {
                     else out[(size_t)bl.rows[v] * T + (t - idx)] = val;
                 }
             }
-        size_t n_levels = sp.level_first.empty() ? 0 : sp.level_first.size() - 1;
-        const uint64_t fstep = std::max<uint64_t>(sp.fused_max_frames, 1);
-        uint64_t n_sub = sp.fused_count ? (T - 1) / fstep + 1 : 0;
-        bool fused = !force_levels && sp.fused_count && w0 == idx && valid && n_sub < n_levels;
-        if (used_fused) *used_fused = fused;
-        // the engine's ONE strided launch (engine.cpp execute()): frames wi, wi + stride, ... per thread.  Emulated in the
-        // order least friendly to a wrong plan: programs last to first, threads last to first -- a read of a ring that another
+        if (used_fused) *used_fused = form.kind == StageForm::fused || form.kind == StageForm::strided;
+        // the engine's ONE strided launch (callplan.hpp StageForm::strided): frames wi, wi + stride, ... per thread.  Emulated in
+        // the order least friendly to a wrong plan: programs last to first, threads last to first -- a read of a ring that another
         // program (or another thread) stores inside this launch finds nothing there yet.
-        const uint64_t ssub = sp.fused_stride ? (T - 1) / sp.fused_stride + 1 : 0;
-        if (!force_levels && sp.fused_count && w0 == idx && valid && sp.fused_stride >= 16 && ssub >= 2 && ssub <= 8) {
-            if (used_fused) *used_fused = true;
+        if (form.kind == StageForm::strided) {
             for (uint32_t pi = sp.fused_count; pi-- > 0;)
                 for (uint64_t wi = std::min<uint64_t>(sp.fused_stride, T); wi-- > 0;)
                     for (uint64_t off = wi; off < T; off += sp.fused_stride) run_progs(sp.fused_first + pi, 1, idx + off, 1, idx, T, in, out);
             ++fused_launches;
             ++strided_launches;
-        } else if (fused) {
+        } else if (form.kind == StageForm::fused) {
             for (uint64_t done = 0; done < T;) {
-                const uint64_t len = std::min<uint64_t>(fstep, T - done);
+                const uint64_t len = std::min<uint64_t>(form.fused_step, T - done);
                 run_progs(sp.fused_first, sp.fused_count, idx + done, len, idx, T, in, out);
                 done += len;
                 ++fused_launches;
             }
         } else {
-            for (size_t l = 0; l < n_levels; ++l)
+            for (size_t l = 0; l + 1 < sp.level_first.size(); ++l)
                 run_progs(sp.level_first[l], sp.level_first[l + 1] - sp.level_first[l], w0, wlen, idx, T, in, out);
         }
         if (sp.uses_rings()) { valid = true; end = idx + T; }
@@ -605,7 +602,7 @@ struct CpuJit {
     ~CpuJit() { if (so) dlclose(so); }
 };
 
-// engine.cpp's execute() for the compiled form: real ring arrays (power-of-two capacity, indexed t & mask).
+// engine.cpp's call path for the compiled form: real ring arrays (power-of-two capacity, indexed t & mask).
 struct JitSim {
     const StagedPlan &sp;
     StageJitPlan sj;
@@ -617,8 +614,7 @@ struct JitSim {
     JitSim(const StagedPlan &p, uint64_t T) : sp(p) {
         CHECK(plan_stage_jit(sp.progs, sp.instrs, 64, true, sj));
         jit.reset(new CpuJit(sj.source));
-        cap = 1024;
-        while (cap < sp.lmax + T) cap <<= 1;
+        cap = ring_capacity(sp, T);
         rings.assign((size_t)std::max<uint32_t>(sp.n_rings, 1) * cap, -55.0f);
     }
     void launch(uint32_t first, uint32_t count, uint64_t w0, uint64_t wlen, uint64_t idx, uint64_t T, const Inputs &in, std::vector<float> &out) {
@@ -640,9 +636,11 @@ struct JitSim {
                 for (uint32_t tx = 0; tx < 256; ++tx) { jit->set_thread(bx, y, tx); jit->kernel(a); }
     }
     void call(uint64_t idx, uint64_t T, const Inputs &in, std::vector<float> &out) {
-        uint64_t w0 = idx;
-        if (sp.uses_rings() && !(valid && end == idx)) w0 = idx > sp.lmax ? idx - sp.lmax : 0;
-        uint64_t wlen = idx + T - w0;
+        const CallIn ci{idx, T, valid && end == idx, false, false};
+        const CallWindows cw = call_windows(sp, ci);
+        const StageForm form = stage_form(sp, ci, cw, 16, false);   // (no strided form in this simulator)
+        CHECK(form.kind != StageForm::feedback);
+        const uint64_t w0 = cw.w0, wlen = cw.w_len;
         for (const BankLaunch &bl : sp.banks)
             for (size_t v = 0; v < bl.rows.size(); ++v) {
                 uint64_t b0 = bl.to_ring ? w0 : idx, blen = bl.to_ring ? wlen : T;
@@ -652,18 +650,14 @@ struct JitSim {
                     else out[(size_t)bl.rows[v] * T + (t - idx)] = val;
                 }
             }
-        size_t n_levels = sp.level_first.empty() ? 0 : sp.level_first.size() - 1;
-        const uint64_t fstep = std::max<uint64_t>(sp.fused_max_frames, 1);
-        uint64_t n_sub = sp.fused_count ? (T - 1) / fstep + 1 : 0;
-        bool fused = sp.fused_count && w0 == idx && valid && n_sub < n_levels;
-        if (fused) {
+        if (form.kind == StageForm::fused) {
             for (uint64_t done = 0; done < T;) {
-                const uint64_t len = std::min<uint64_t>(fstep, T - done);
+                const uint64_t len = std::min<uint64_t>(form.fused_step, T - done);
                 launch(sp.fused_first, sp.fused_count, idx + done, len, idx, T, in, out);
                 done += len;
             }
         } else {
-            for (size_t l = 0; l < n_levels; ++l)
+            for (size_t l = 0; l + 1 < sp.level_first.size(); ++l)
                 launch(sp.level_first[l], sp.level_first[l + 1] - sp.level_first[l], w0, wlen, idx, T, in, out);
         }
         if (sp.uses_rings()) { valid = true; end = idx + T; }

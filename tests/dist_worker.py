@@ -46,7 +46,7 @@ def main():
             recv[:] = rt.numpy()
 
     edits = []
-    if case.endswith("_tiled"):      # the exchange cut into time tiles on a second stream (engine.cpp execute()): small tiles for a small test
+    if case.endswith("_tiled"):      # the exchange cut into time tiles on a second stream (engine.cpp exchange_split_voices): small tiles for a small test
         os.environ["FR_EXCHANGE_MIN_TILE"] = "64"
         case = case[:-len("_tiled")]
         tiled = True

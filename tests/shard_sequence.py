@@ -1,5 +1,5 @@
 """A partial-block-sharded job (shard_harness.Job, FR_SHARD_PARTIALS) driven through a call sequence that takes every
-branch of the time-tiled exchange at its DEFAULT geometry (engine.cpp execute(): at most 4 tiles, none shorter than
+branch of the time-tiled exchange at its DEFAULT geometry (csrc/callplan.hpp exchange_tiles: at most 4 tiles, none shorter than
 1024 frames, 64-aligned), checked against the oracle by sampling.  Shared by the CPU twin on the host-logic simulator
 (test_shard_sim.py) and the HIP tests (test_hip_shard.py): the same calls, the same frame choice, the same assertions.
 
@@ -19,14 +19,14 @@ SENTINEL = np.float32(-12345.0)
 
 
 def exchange_tiles(xlen, max_tiles=MAX_TILES, min_tile=MIN_TILE):
-    """(offset in the window, frames) of every tile, as execute() cuts an exchange window of xlen frames."""
+    """(offset in the window, frames) of every tile, as callplan.hpp exchange_tiles cuts an exchange window of xlen frames."""
     nt = max(1, min(max_tiles, xlen // max(min_tile, 64)))
     tl = ((xlen + nt - 1) // nt + 63) // 64 * 64
     return [(off, min(tl, xlen - off)) for off in range(0, xlen, tl)]
 
 
 class Window:
-    """The window execute() renders the split voices over: the call's frames, or -- when split voices feed rings that do
+    """The window callplan.hpp call_windows has the split voices rendered over: the call's frames, or -- when split voices feed rings that do
     not hold [idx - lmax, idx) of the current graph (first call, seek, edit, ring growth) -- [idx - lmax, idx + n)."""
 
     def __init__(self, lmax=None):

@@ -45,7 +45,7 @@ def test_engine_host_logic_against_oracle(oracle_lib):
     """tests/cpp/plan_tests.cpp: the lowered graph and the staged plan (banks, rings, level and fused programs,
     general-tree schedules), executed by small CPU interpreters in the test, equal the oracle bit for bit; the source
     generated for compiled stage programs, built with g++, does too."""
-    deps = [PLAN_SRC, ABI] + [os.path.join(CSRC, f) for f in ("graph.cpp", "graph.hpp", "match.cpp", "match.hpp", "stage.cpp", "stage.hpp", "stagejit.cpp", "leafjit.cpp", "range.hpp", "jit.hpp", "kernels.hpp")]
+    deps = [PLAN_SRC, ABI] + [os.path.join(CSRC, f) for f in ("graph.cpp", "graph.hpp", "match.cpp", "match.hpp", "stage.cpp", "stage.hpp", "stagejit.cpp", "leafjit.cpp", "range.hpp", "jit.hpp", "kernels.hpp", "callplan.hpp")]
     if not os.path.exists(PLAN_BIN) or os.path.getmtime(PLAN_BIN) < max(os.path.getmtime(d) for d in deps):
         os.makedirs(os.path.dirname(PLAN_BIN), exist_ok=True)
         subprocess.run(["g++", "-std=c++17", "-O1", "-ffp-contract=off", "-I/opt/rocm/include", "-D__HIP_PLATFORM_AMD__",
@@ -71,3 +71,20 @@ def test_bank_launch_rule_table():
                         BANKPLAN_SRC], check=True)
     p = subprocess.run([BANKPLAN_BIN], capture_output=True, text=True, timeout=60)
     assert p.returncode == 0 and "211 passed; 0 failed" in p.stdout, p.stdout + p.stderr
+
+
+# ---- the per-call rule (csrc/callplan.hpp) over a pinned table of plans and calls -----------------------------------
+CALLPLAN_SRC = os.path.join(ROOT, "tests", "cpp", "callplan_tests.cpp")
+CALLPLAN_BIN = os.path.join(ROOT, "tests", "cpp", "_build", "callplan_tests")
+
+
+def test_call_rule_table():
+    """tests/cpp/callplan_tests.cpp: ring capacity, the call's windows (look-back, kept rings, a feedback plan's replay and
+    its refusal), the exchange tiles and the stage launch form give the pinned, hand-derived answers; a mismatch is printed."""
+    deps = [CALLPLAN_SRC] + [os.path.join(CSRC, f) for f in ("callplan.hpp", "stage.hpp", "graph.hpp", "match.hpp", "range.hpp", "kernels.hpp")]
+    if not os.path.exists(CALLPLAN_BIN) or os.path.getmtime(CALLPLAN_BIN) < max(os.path.getmtime(d) for d in deps):
+        os.makedirs(os.path.dirname(CALLPLAN_BIN), exist_ok=True)
+        subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-I/opt/rocm/include", "-D__HIP_PLATFORM_AMD__", "-o", CALLPLAN_BIN,
+                        CALLPLAN_SRC], check=True)
+    p = subprocess.run([CALLPLAN_BIN], capture_output=True, text=True, timeout=60)
+    assert p.returncode == 0 and "50 passed; 0 failed" in p.stdout, p.stdout + p.stderr
