@@ -44,6 +44,16 @@ extern "C" {
  * fr_stream_begin would take the plan and why not.  Refused (FR_ERR_UNSUPPORTED, the reason in fr_last_error): a Delay of a
  * computed value shorter than 64 frames, a program that needs two voices of the same block (a mix bus), delayed reads of
  * the input row, signal-amount delays, more than one bank, compiled, general and track voices, pull rows, sharding.
+ *
+ * FR_STREAM_BUS = 0 / 1 (default 0; read strictly from the environment too; does nothing unless FR_STREAM_PROGRAMS=1):
+ * block streaming also serves mix-bus programs across voices -- several voices, each with its own gain, envelope or taps,
+ * summed to a mono or stereo bus, with taps or an echo behind the bus.  A program that reads, less than 64 frames back, two or
+ * more voices (or what an earlier bus program stored) is a bus program: a third resident kernel runs the bus programs in the
+ * workgroup that counts the block's last voice in, before it reports the block done.  With 0 nothing changes: the same
+ * plans are served and refused, with the same reasons, by the same kernels.  "stream" gains "bus_programs": how many
+ * programs run after the last voice (programs_per_voice counts the others).  Still refused: a Delay shorter than 64 frames
+ * of a value computed by the reading program itself or a later one (a short loop, a bus echo of 32 frames), and everything
+ * else of the list above.
  */
 typedef struct fr_option {
     const char *name;              /* e.g. "FR_BANK_SHORT" */

@@ -189,7 +189,7 @@ static std::string stage_variant(const StageLaunchNote &n, const Plan &p) {
     return k;
 }
 
-constexpr size_t N_OPTIONS = 31;         // per-renderer options (friendship_render_ext.h; the table below fr_renderer)
+constexpr size_t N_OPTIONS = 32;         // per-renderer options (friendship_render_ext.h; the table below fr_renderer)
 
 struct TimerClass {
     double ms = 0;
@@ -235,6 +235,9 @@ __attribute__((weak)) hipError_t launch_ring_move(const RingMoveArgs &a, hipStre
 }
 // (no resident launches on the simulator: the serving rule and the tables are what it tests, through fr_plan_json)
 __attribute__((weak)) hipError_t launch_bank_stream_prog(const BankArgs &, const StreamProgArgs &, BankStreamCtl *, BankStreamDev *, uint32_t, hipStream_t) {
+    return hipErrorNotSupported;
+}
+__attribute__((weak)) hipError_t launch_bank_stream_bus(const BankArgs &, const StreamProgArgs &, BankStreamCtl *, BankStreamDev *, uint32_t, hipStream_t) {
     return hipErrorNotSupported;
 }
 __attribute__((weak)) hipError_t launch_track_window(const TrackWindowArgs &a, hipStream_t) {
@@ -536,6 +539,7 @@ struct fr_renderer {
     // the tables; the resident launch (bank_stream_prog_kernel) starts with the first block and again with every block that
     // does not continue the previous one, after the rings were brought up to that block's first frame.
     bool stream_programs = false;        // the option
+    bool stream_bus = false;             // FR_STREAM_BUS: mix-bus programs run after the block's last voice (bank_stream_bus_kernel)
     bool stream_prog = false;            // the open stream is of that kind
     bool stream_launched = false;        // its resident launch is running
     const char *stream_kernel = "";      // the last resident launch's kernel (fr_plan_json "stream")
@@ -551,6 +555,7 @@ struct fr_renderer {
         env.pull_mode = mode == FR_MODE_PULL;
         env.sharded = sharded();
         env.track_history = tail_on();
+        env.bus = stream_bus;
         return plan_stream(plan.sp, banks, env);
     }
     // Rings the stop and waits for the resident launch to end.  `clean`: the launch was answering when the stop was rung
@@ -2217,8 +2222,14 @@ void fr_renderer::seek_program_stream(uint64_t idx) {
     // (the previous launch's last doorbell and stop are still in the control words: a new launch starts from a clean slate)
     std::memset(h_stream_ctl.p, 0, sizeof(BankStreamCtl));
     HIP_CHECK(hipMemsetAsync(d_stream_dev.p, 0, sizeof(BankStreamDev), stream));
-    HIP_CHECK(launch_bank_stream_prog(a, p, h_stream_ctl.as_dev<BankStreamCtl>(), d_stream_dev.as<BankStreamDev>(), stream_idle_ms, stream));
-    stream_kernel = "bank_stream_prog_kernel";
+    // a plan with bus programs (FR_STREAM_BUS): the kernel whose last arriver of a block runs them; every other plan: as before
+    if (s.bus_programs()) {
+        HIP_CHECK(launch_bank_stream_bus(a, p, h_stream_ctl.as_dev<BankStreamCtl>(), d_stream_dev.as<BankStreamDev>(), stream_idle_ms, stream));
+        stream_kernel = "bank_stream_bus_kernel";
+    } else {
+        HIP_CHECK(launch_bank_stream_prog(a, p, h_stream_ctl.as_dev<BankStreamCtl>(), d_stream_dev.as<BankStreamDev>(), stream_idle_ms, stream));
+        stream_kernel = "bank_stream_prog_kernel";
+    }
     stream_launched = true;
     stream_have_last = false;
     last_pending = false;
@@ -2280,6 +2291,7 @@ constexpr int64_t ENV_REFUSED = INT64_MIN;   // an `env` reading that makes crea
 int64_t env_strict_track_history(const char *e);
 int64_t env_strict_ring_keep(const char *e);
 int64_t env_strict_stream_programs(const char *e);
+int64_t env_strict_stream_bus(const char *e);
 bool parse_option(const Knob &k, const char *s, int64_t &v);
 
 const Knob kKnobs[] = {
@@ -2351,6 +2363,9 @@ const Knob kKnobs[] = {
     // Block streaming of plans with stage programs and rings behind one voice bank (streamplan.hpp; fr_plan_json: stream).
     // Strict and listed once set, like the two above.
     {"FR_STREAM_PROGRAMS", 0, 0, 1, 0, nullptr, 0, env_strict_stream_programs, [](fr_renderer &r, int64_t v, bool) { r.stream_programs = v != 0; }, LISTED_WHEN_SET},
+    // Mix-bus programs across voices in block streaming (streamplan.hpp StreamEnv::bus; fr_plan_json: stream.bus_programs).
+    // Inert without FR_STREAM_PROGRAMS.  Strict and listed once set.
+    {"FR_STREAM_BUS", 0, 0, 1, 0, nullptr, 0, env_strict_stream_bus, [](fr_renderer &r, int64_t v, bool) { r.stream_bus = v != 0; }, LISTED_WHEN_SET},
 };
 static_assert(sizeof kKnobs / sizeof kKnobs[0] == N_OPTIONS, "N_OPTIONS counts the rows of kKnobs");
 
@@ -2363,6 +2378,7 @@ static int64_t env_strict(const char *name, const char *e) {
 int64_t env_strict_track_history(const char *e) { return env_strict("FR_TRACK_HISTORY", e); }
 int64_t env_strict_ring_keep(const char *e) { return env_strict("FR_RING_KEEP", e); }
 int64_t env_strict_stream_programs(const char *e) { return env_strict("FR_STREAM_PROGRAMS", e); }
+int64_t env_strict_stream_bus(const char *e) { return env_strict("FR_STREAM_BUS", e); }
 
 bool parse_option(const Knob &k, const char *s, int64_t &v) {
     if (k.word && std::strcmp(s, k.word) == 0) {
@@ -2979,7 +2995,7 @@ const char *fr_plan_json(fr_renderer *r) {
             for (char c : s.reason) { if (c == '"' || c == '\\') why += '\\'; why += c; }
             r->plan_json_cache += std::string(",\"stream\":{\"servable\":") + (s.servable ? "true" : "false") + ",\"reason\":\"" + why +
                                   "\",\"voices\":" + std::to_string(s.voices) + ",\"chunks\":" + std::to_string(s.chunks) + ",\"programs_per_voice\":[" + per +
-                                  "],\"min_ring_delay\":" + std::to_string(s.min_ring_delay) + ",\"rings\":" + std::to_string(r->plan.sp.n_rings) +
+                                  "],\"bus_programs\":" + std::to_string(s.bus_programs()) + ",\"min_ring_delay\":" + std::to_string(s.min_ring_delay) + ",\"rings\":" + std::to_string(r->plan.sp.n_rings) +
                                   ",\"kernel\":\"" + r->stream_kernel + "\"}";
         }
         r->plan_json_cache += ",\"exchange_stats\":{\"calls\":" + std::to_string(r->exchange_calls) + ",\"tiles\":" + std::to_string(r->exchange_tiles) +

@@ -1690,6 +1690,243 @@ hipError_t launch_bank_stream_prog(const BankArgs &a, const StreamProgArgs &p, B
 }
 
 // ---------------------------------------------------------------------------------------------------
+// Block streaming with mix-bus programs (FR_STREAM_BUS, streamplan.hpp): bank_stream_prog_kernel, and after the per-voice
+// programs one more segment, progs[voice_first[n_voices] .. voice_first[n_voices + 1]): the bus programs, which read several
+// voices of the SAME block (and what earlier programs of the block stored).  Still no workgroup waits for another one: the
+// wave whose voices_done ticket comes back as n_voices - 1 -- the one that writes the block's done tag -- knows that every
+// voice has been counted in, and every voice acknowledged its ring and row stores (vmcnt(0)) before it took its ticket.  That
+// wave interprets the bus programs, lane = frame, its ring loads relaxed agent-scope atomics issued after the ticket returned
+// (the hand-over of the chunk sums: store, vmcnt(0), ticket | ticket, load), vmcnt(0) between programs and before the tag.
+// The interpreter is the text of bank_stream_prog_kernel's as a function; that kernel and bank_stream_kernel keep their own
+// text, so their code does not change with this one.
+// ---------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void stream_run_programs(const BankArgs &a, const StreamProgArgs &p, float (*regs)[64], uint32_t p_first, uint32_t p_end, uint64_t frame,
+                                                    uint32_t lane, bool live, float t) {
+    const uint64_t ring_cap = p.ring_mask + 1;
+    for (uint32_t pi = p_first; pi < p_end; ++pi) {
+        // what this wave has stored so far (the voice's ring, an earlier program's rings) is in L2 before it is read back
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        const StageProg pg = p.progs[pi];
+        const StageInstr *ins = p.instrs + pg.first_instr;
+        uint32_t i = 0;
+        for (; i + 4u <= pg.n_loads; i += 4u) {   // the program's leading loads, four round trips to L2 in flight together
+            float ld[4];
+#pragma unroll
+            for (uint32_t j = 0; j < 4u; ++j) ld[j] = stream_prog_load(p, ins[i + j], frame, t);
+#pragma unroll
+            for (uint32_t j = 0; j < 4u; ++j) regs[ins[i + j].dst][lane] = ld[j];
+        }
+        for (; i < pg.n_instr; ++i) {
+            const StageInstr in = ins[i];
+            float v;
+            switch (in.op) {
+            case S_SUM2: v = regs[in.a][lane] + regs[in.b][lane]; break;
+            case S_MUL: v = regs[in.a][lane] * regs[in.b][lane]; break;
+            case S_DIV: v = regs[in.a][lane] / regs[in.b][lane]; break;
+            case S_MOD: v = prim_mod(regs[in.a][lane], regs[in.b][lane]); break;
+            case S_MIN: v = prim_min(regs[in.a][lane], regs[in.b][lane], p.sparkle != 0u); break;
+            case S_STORE:
+                if (live) __hip_atomic_store(p.rings + (size_t)in.buf * ring_cap + (frame & p.ring_mask), regs[in.a][lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                continue;
+            default: v = stream_prog_load(p, in, frame, t); break;
+            }
+            regs[in.dst][lane] = v;
+        }
+        const float res = regs[pg.result_reg][lane];
+        if (live && pg.dst_ring != 0xFFFFFFFFu)
+            __hip_atomic_store(p.rings + (size_t)pg.dst_ring * ring_cap + (frame & p.ring_mask), res, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (live && pg.out_row >= 0) __hip_atomic_store(a.out + (size_t)pg.out_row * 64u + lane, res, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+}
+
+__global__ void __launch_bounds__(1024) bank_stream_bus_kernel(BankArgs a, StreamProgArgs p, BankStreamCtl *ctl, BankStreamDev *dev, uint32_t idle_ms) {
+    constexpr int NW = 16;
+    __shared__ float sm[NW][64];
+    __shared__ float regs[STAGE_REGS][64];                   // the interpreter's registers: [register][lane] of wave 0
+    __shared__ unsigned long long zshared;
+    __shared__ uint32_t s_seq, s_T;
+    const uint32_t clog = a.log2_p - a.chunk_log2, nchunks = 1u << clog;
+    const uint32_t chunk = blockIdx.x & (nchunks - 1u);
+    const uint32_t voice = blockIdx.x >> clog;               // (the grid is exactly n_voices * nchunks workgroups)
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t Pc = 1u << a.chunk_log2;
+    const uint32_t Pw = Pc / NW, ngroups = Pw >> 3;
+    uint32_t levels = 0;
+    while ((1u << levels) < ngroups) ++levels;
+    const unsigned long long idle_ticks = (unsigned long long)idle_ms * 100000ull;
+    const float *mine = (const float *)(a.params + ((size_t)voice << a.log2_p) + (size_t)chunk * Pc + (size_t)wave * Pw);
+    const size_t vstride = (size_t)a.n_voices * 64u;
+    const uint64_t ring_cap = p.ring_mask + 1;
+    uint64_t head = p.head;                                  // first frame of the block being rendered (the same in every workgroup)
+    uint32_t seen = 0;
+    if (blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store(&ctl->alive, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    for (;;) {
+        // ---- wait for the next block (bounded), as bank_stream_prog_kernel ----
+        if (blockIdx.x == 0) {
+            if (wave == 0u) {
+                uint32_t tag = seen;
+                float v = 0.0f;
+                bool fresh = false;
+                const unsigned long long wait_from = __builtin_amdgcn_s_memrealtime();
+                for (;;) {
+                    const unsigned long long word = __hip_atomic_load(&ctl->row[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                    tag = (uint32_t)(word >> 32);
+                    v = __uint_as_float((uint32_t)word);
+                    fresh = __all(tag != seen) && (uint32_t)__builtin_amdgcn_readfirstlane(tag) == tag;
+                    fresh = __all(fresh);
+                    if (fresh || __builtin_amdgcn_s_memrealtime() - wait_from > idle_ticks) break;
+                }
+                const uint32_t seq = fresh ? __builtin_amdgcn_readfirstlane(tag) : BANK_STREAM_STOP;
+                uint32_t T = 0;
+                if (seq != BANK_STREAM_STOP) {
+                    T = seq & 0xFFu;
+                    T = T > 64u ? 64u : T;
+                    __hip_atomic_store(&dev->row[lane], lane < T ? v : 0.0f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                }
+                if (lane == 0u) {
+                    __hip_atomic_store(&dev->n_times, T, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                    __hip_atomic_store(&dev->seq, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    s_seq = seq;
+                    s_T = T;
+                }
+            }
+        } else if (threadIdx.x == 0) {
+            uint32_t seq = seen;
+            const unsigned long long wait_from = __builtin_amdgcn_s_memrealtime();
+            for (;;) {
+                seq = __hip_atomic_load(&dev->seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (seq != seen || __builtin_amdgcn_s_memrealtime() - wait_from > 2ull * idle_ticks + 10000000ull) break;
+                __builtin_amdgcn_s_sleep(4);
+            }
+            if (seq == seen) seq = BANK_STREAM_STOP;
+            s_seq = seq;
+            s_T = __hip_atomic_load(&dev->n_times, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        __syncthreads();
+        const uint32_t seq = s_seq, T = s_T;
+        if (seq == BANK_STREAM_STOP) break;
+        seen = seq;
+        {
+            // ---- one (voice, chunk) of one tile, as bank_stream_prog_kernel ----
+            const bool live = lane < T;
+            ParamGroup first;
+            load_group(first, (const_f32_ptr)mine, 0);
+            const float t = live ? __hip_atomic_load(&dev->row[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0f;
+            const bool fast = a.fast_ok && __all(t >= 0.0f && t <= 4294967296.0f);
+            const float tt[1] = {t};
+            float r_wave[1];
+            if (fast) bank_wave_sum<1, true, false>(mine, ngroups, levels, tt, r_wave, &first);
+            else bank_wave_sum<1, false, false>(mine, ngroups, levels, tt, r_wave, &first);
+            sm[wave][lane] = r_wave[0];
+            __syncthreads();
+            float r = 0.0f;
+            if (wave == 0u) {
+                float s[NW];
+                static_for<0, NW>([&](auto w) { s[w] = sm[w][lane]; });
+                static_for<0, NW / 2>([&](auto i) { s[i] = s[2 * i] + s[2 * i + 1]; });
+                static_for<0, NW / 4>([&](auto i) { s[i] = s[2 * i] + s[2 * i + 1]; });
+                static_for<0, NW / 8>([&](auto i) { s[i] = s[2 * i] + s[2 * i + 1]; });
+                static_for<0, NW / 16>([&](auto i) { s[i] = s[2 * i] + s[2 * i + 1]; });
+                r = s[0];
+                const unsigned long long z = __ballot(live && r == 0.0f);
+                if (lane == 0u) zshared = z;
+            }
+            __syncthreads();
+            const unsigned long long zm = zshared;
+            if (zm != 0ull) {
+                const bool ok = fast ? wave_leaves_all_negzero<true>(mine, ngroups, t, zm) : wave_leaves_all_negzero<false>(mine, ngroups, t, zm);
+                sm[wave][lane] = ok ? 1.0f : 0.0f;
+                __syncthreads();
+                if (wave == 0u && ((zm >> lane) & 1ull)) {
+                    bool all = true;
+                    static_for<0, NW>([&](auto w) { all = all && sm[w][lane] != 0.0f; });
+                    r = all ? -0.0f : 0.0f;
+                }
+            }
+            if (wave == 0u) {
+                bool finished_voice = nchunks == 1u;
+                float result = r;
+                if (nchunks > 1u) {
+                    float *slot = a.ws + (size_t)voice * 64u;
+                    __hip_atomic_store(slot + (size_t)chunk * vstride + lane, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                    uint32_t old = 0u;
+                    if (lane == 0u) old = __hip_atomic_fetch_add(a.tickets + (size_t)voice * TICKET_STRIDE, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    old = __builtin_amdgcn_readfirstlane(old);
+                    if (old == nchunks - 1u) {
+                        finished_voice = true;
+                        float c0 = 0.0f, c1 = 0.0f, c2 = 0.0f, c3 = 0.0f, c4 = 0.0f, c5 = 0.0f, c6 = 0.0f, c7 = 0.0f, c8 = 0.0f;
+                        for (uint32_t c = 0; c < nchunks; ++c) {
+                            float v = c == chunk ? r : __hip_atomic_load(slot + (size_t)c * vstride + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                            do {
+                                if (!(c & 1u)) { c0 = v; break; } v = c0 + v;
+                                if (!(c & 2u)) { c1 = v; break; } v = c1 + v;
+                                if (!(c & 4u)) { c2 = v; break; } v = c2 + v;
+                                if (!(c & 8u)) { c3 = v; break; } v = c3 + v;
+                                if (!(c & 16u)) { c4 = v; break; } v = c4 + v;
+                                if (!(c & 32u)) { c5 = v; break; } v = c5 + v;
+                                if (!(c & 64u)) { c6 = v; break; } v = c6 + v;
+                                if (!(c & 128u)) { c7 = v; break; } v = c7 + v;
+                                c8 = v;
+                            } while (0);
+                        }
+                        result = c8;
+                        result = clog == 7u ? c7 : result; result = clog == 6u ? c6 : result; result = clog == 5u ? c5 : result;
+                        result = clog == 4u ? c4 : result; result = clog == 3u ? c3 : result; result = clog == 2u ? c2 : result;
+                        result = clog == 1u ? c1 : result;
+                        if (lane == 0u) __hip_atomic_store(a.tickets + (size_t)voice * TICKET_STRIDE, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    }
+                }
+                if (finished_voice) {
+                    // ---- the voice's frames head + lane: to its ring (or its row), then its programs, lane = frame (as bank_stream_prog_kernel) ----
+                    const uint64_t frame = head + lane;
+                    const uint32_t dst = a.rows[voice];
+                    if (live) {
+                        if (p.bank_to_ring) __hip_atomic_store(p.rings + (size_t)dst * ring_cap + (frame & p.ring_mask), result, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        else __hip_atomic_store(a.out + (size_t)dst * 64u + lane, result, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                    }
+                    stream_run_programs(a, p, regs, p.voice_first[voice], p.voice_first[voice + 1], frame, lane, live, t);
+                    // ring and row stores alike are acknowledged before the voice is counted in: the block's done tag then implies
+                    // that every ring store of the block has landed
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                    // the ticket goes to the whole wave: the last arriver of the block runs the bus programs, lane = frame
+                    uint32_t n = 0u;
+                    if (lane == 0u) n = __hip_atomic_fetch_add(&dev->voices_done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    n = __builtin_amdgcn_readfirstlane(n);
+                    if (n == a.n_voices - 1u) {
+                        // every voice's ring and row stores were acknowledged before its ticket, and this wave's loads are issued
+                        // after its own ticket came back: the hand-over of the chunk sums
+                        stream_run_programs(a, p, regs, p.voice_first[a.n_voices], p.voice_first[a.n_voices + 1], frame, lane, live, t);
+                        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // host rows and rings have landed before the done tag
+                        if (lane == 0u) {
+                            __hip_atomic_store(&dev->voices_done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                            __hip_atomic_store(&ctl->done, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                        }
+                    }
+                }
+            }
+        }
+        head += T;
+        __syncthreads();   // LDS is reused by the next block
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store(&ctl->alive, 0u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+hipError_t launch_bank_stream_bus(const BankArgs &a, const StreamProgArgs &p, BankStreamCtl *ctl_dev, BankStreamDev *dev, uint32_t idle_ms, hipStream_t s) {
+    if (a.chunk_log2 < 7 || a.chunk_log2 > 13 || a.chunk_log2 > a.log2_p || a.log2_p - a.chunk_log2 > 8) return hipErrorInvalidValue;
+    if (((uint64_t)a.n_voices << (a.log2_p - a.chunk_log2)) > BANK_STREAM_WGS || a.n_voices == 0) return hipErrorInvalidValue;
+    if (a.chunk_log2 != a.log2_p && (!a.ws || !a.tickets)) return hipErrorInvalidValue;
+    if (a.leaf_variant != 1 || !a.out || !a.rows || !ctl_dev || !dev || !p.voice_first) return hipErrorInvalidValue;
+    if ((p.ring_mask & (p.ring_mask + 1)) != 0 || (p.n_rings && (!p.rings || p.ring_mask + 1 < 64u)) || (p.bank_to_ring && !p.n_rings)) return hipErrorInvalidValue;
+    const uint32_t wgs = a.n_voices << (a.log2_p - a.chunk_log2);
+    hipLaunchKernelGGL(bank_stream_bus_kernel, dim3(wgs), dim3(1024), 0, s, a, p, ctl_dev, dev, idle_ms ? idle_ms : BANK_STREAM_IDLE_MS);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------------
 // Partial-block exchange, one level of the voices' Sum2 trees (kernels.hpp ShardCombineArgs).  HBM-bound: 12 bytes per
 // frame of a row; rows are contiguous and lanes run over frames, so every access is a full 256-byte line per wave.
 __global__ void __launch_bounds__(256) shard_combine_kernel(ShardCombineArgs a) {

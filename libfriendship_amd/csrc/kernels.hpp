@@ -199,7 +199,7 @@ hipError_t launch_stage(const StageArgs &a, hipStream_t s);
 struct StreamProgArgs {
     const StageInstr *instrs;      // the plan's instructions (StageProg::first_instr indexes them)
     const StageProg *progs;        // the streamed programs, voice by voice
-    const uint32_t *voice_first;   // [n_voices + 1] into progs
+    const uint32_t *voice_first;   // [n_voices + 2] into progs; the last segment: the bus programs (bank_stream_bus_kernel only)
     float *rings;                  // [n_rings][ring_mask + 1]
     uint64_t ring_mask;
     uint32_t n_rings;
@@ -209,6 +209,11 @@ struct StreamProgArgs {
     uint32_t sparkle;              // FR_SEMANTICS_SPARKLE
 };
 hipError_t launch_bank_stream_prog(const BankArgs &a, const StreamProgArgs &p, BankStreamCtl *ctl_dev, BankStreamDev *dev, uint32_t idle_ms, hipStream_t s);
+// bank_stream_bus_kernel (FR_STREAM_BUS): bank_stream_prog_kernel, and the wave whose voices_done ticket is the block's last
+// (n_voices - 1) interprets progs[voice_first[n_voices] .. voice_first[n_voices + 1]) -- the bus programs, which read several
+// voices of the same block -- before it resets the counter and stores the done tag.  Every voice acknowledged its ring and
+// row stores before its ticket, the last arriver loads after its own: no wait, no acquire or release, no new polling loop.
+hipError_t launch_bank_stream_bus(const BankArgs &a, const StreamProgArgs &p, BankStreamCtl *ctl_dev, BankStreamDev *dev, uint32_t idle_ms, hipStream_t s);
 
 // One step of the partial-block exchange (friendship_render.h FR_SHARD_PARTIALS): row i, window frame t:
 //   v = lo[i][t] + hi[i][t]         the Sum2 node one level up: left sub-tree + right sub-tree, one f32 add

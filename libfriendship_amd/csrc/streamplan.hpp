@@ -7,6 +7,11 @@
 // programs assigned to v, lane = frame.  No workgroup waits for another one's result, so inside a block a program may read
 //   * at a delay < 64 frames: rings of ITS OWN voice's bank only (what its own wave has just stored),
 //   * at a delay >= 64 frames: any ring (an earlier block stored those frames, and that block's done tag was seen).
+// With FR_STREAM_BUS=1 (StreamEnv::bus) a program that needs two or more voices of the same block -- a mix bus -- is served
+// too, still without a wait: the workgroup whose `voices_done` ticket is the last of the block (the one that writes the done
+// tag) knows that every voice and every voice's programs have finished, and runs the BUS PROGRAMS before it writes the tag
+// (kernels.hip bank_stream_bus_kernel).  A bus program may read below 64 frames any voice's ring and any ring that an earlier
+// program of the block stores.
 #pragma once
 
 #include <algorithm>
@@ -30,6 +35,7 @@ struct StreamEnv {
     bool pull_mode = false;          // FR_MODE_PULL
     bool sharded = false;
     bool track_history = false;      // FR_TRACK_HISTORY is on (every call appends to the track rings)
+    bool bus = false;                // FR_STREAM_BUS: programs that read several voices of a block run after the last voice
 };
 
 struct StreamPlan {
@@ -37,15 +43,16 @@ struct StreamPlan {
     std::string reason;              // why not ("" when servable)
     uint32_t voices = 0, chunk_log2 = 0, chunks = 0;   // chunks per voice; the launch has voices * chunks workgroups
     bool bank_to_ring = false;
-    std::vector<uint32_t> progs;         // indices into StagedPlan::progs, voice by voice, in the order they run
-    std::vector<uint32_t> voice_first;   // [voices + 1] into `progs`
+    std::vector<uint32_t> progs;         // indices into StagedPlan::progs, voice by voice, then the bus programs, in the order they run
+    std::vector<uint32_t> voice_first;   // [voices + 2] into `progs`: [voice_first[voices], voice_first[voices + 1]) is the bus segment
     uint64_t min_ring_delay = 0;         // shortest delayed read of a ring that a program stores (0: there is none)
     uint64_t lookback = 0;               // deepest ring read of the assigned programs
     std::vector<uint32_t> programs_per_voice() const {
         std::vector<uint32_t> n;
-        for (size_t v = 0; v + 1 < voice_first.size(); ++v) n.push_back(voice_first[v + 1] - voice_first[v]);
+        for (size_t v = 0; v + 2 < voice_first.size(); ++v) n.push_back(voice_first[v + 1] - voice_first[v]);
         return n;
     }
+    uint32_t bus_programs() const { return voice_first.size() >= 2 ? voice_first[voice_first.size() - 1] - voice_first[voice_first.size() - 2] : 0; }
 };
 
 inline const char *stage_op_name(uint8_t op) {
@@ -113,11 +120,33 @@ inline StreamPlan plan_stream(const StagedPlan &sp, const std::vector<const Bank
         }
     }
     constexpr uint32_t NONE = UINT32_MAX;
+    const uint32_t BUS = V;                                   // "voice" of a bus program: the segment after the last voice's
     std::vector<uint32_t> voice_of(run.size(), NONE);
+    // FR_STREAM_BUS: a program is a bus program when, at a delay below a block, it reads the bank rings of two or more voices
+    // or a ring that an earlier bus program stores (a feedback plan's row copy of such a ring included)
+    auto is_bus = [&](uint32_t k) {
+        if (!env.bus) return false;
+        const StageProg &pg = sp.progs[run[k]];
+        uint32_t one = NONE;
+        for (uint32_t i = 0; i < pg.n_instr; ++i) {
+            const StageInstr &in = sp.instrs[pg.first_instr + i];
+            if (in.op != S_READ || in.d_lo >= STREAM_BLOCK) continue;
+            auto bv = bank_ring_voice.find(in.buf);
+            if (bv != bank_ring_voice.end()) {
+                if (one != NONE && one != bv->second) return true;
+                one = bv->second;
+                continue;
+            }
+            auto st = stored_by.find(in.buf);
+            if (st != stored_by.end() && st->second < k && voice_of[st->second] == BUS) return true;
+        }
+        return false;
+    };
     uint64_t min_delay = UINT64_MAX;
     for (uint32_t k = 0; k < run.size(); ++k) {
         const StageProg &pg = sp.progs[run[k]];
         const bool copy = k >= first_copy;
+        const bool bus = is_bus(k);
         uint32_t mine = NONE;
         for (uint32_t i = 0; i < pg.n_instr; ++i) {
             const StageInstr &in = sp.instrs[pg.first_instr + i];
@@ -133,11 +162,18 @@ inline StreamPlan plan_stream(const StagedPlan &sp, const std::vector<const Bank
                 auto bv = bank_ring_voice.find(in.buf);
                 if (bv != bank_ring_voice.end()) {
                     if (in.d_lo >= STREAM_BLOCK) break;             // an earlier block's frames: any voice's
+                    if (bus) break;                                 // every voice of the block has finished
                     if (mine != NONE && mine != bv->second)
                         return refuse("a program reads voices " + std::to_string(mine) + " and " + std::to_string(bv->second) +
                                       " in the same block (a mix bus across voices); each streamed program follows one voice");
                     mine = bv->second;
                     break;
+                }
+                if (bus && in.d_lo < STREAM_BLOCK) {                 // a ring an EARLIER program of the block stores: it has finished
+                    auto st = stored_by.find(in.buf);
+                    if (st != stored_by.end() && st->second < k) break;
+                    return refuse("a program's ring is read " + std::to_string(in.d_lo) + " frames back; a streamed block needs delays of at least " +
+                                  std::to_string(STREAM_BLOCK) + " frames");
                 }
                 if (copy && in.d_lo == 0) {                          // a row copy: after the program that stores the ring, on its voice
                     auto st = stored_by.find(in.buf);
@@ -158,7 +194,7 @@ inline StreamPlan plan_stream(const StagedPlan &sp, const std::vector<const Bank
             if (in.dst >= STAGE_REGS || in.a >= STAGE_REGS || in.b >= STAGE_REGS) return refuse("a program needs more registers than the streamed interpreter has");
         }
         if (pg.result_reg >= STAGE_REGS) return refuse("a program needs more registers than the streamed interpreter has");
-        voice_of[k] = mine != NONE ? mine : run[k] % V;   // (reads no voice at a short delay: any one voice, the same every time)
+        voice_of[k] = bus ? BUS : mine != NONE ? mine : run[k] % V;   // (reads no voice at a short delay: any one voice, the same every time)
     }
     // each output row: one assigned program, or the bank itself
     std::vector<uint32_t> writers(env.n_slots, 0);
@@ -171,9 +207,9 @@ inline StreamPlan plan_stream(const StagedPlan &sp, const std::vector<const Bank
     for (uint32_t r = 0; r < env.n_slots; ++r)
         if (writers[r] != 1)
             return refuse("output row " + std::to_string(r) + " is written by " + std::to_string(writers[r]) + " streamed programs or voices (exactly one is needed)");
-    s.voice_first.assign(V + 1, 0);
+    s.voice_first.assign(V + 2, 0);
     for (uint32_t k = 0; k < run.size(); ++k) ++s.voice_first[voice_of[k] + 1];
-    for (uint32_t v = 0; v < V; ++v) s.voice_first[v + 1] += s.voice_first[v];
+    for (uint32_t v = 0; v <= V; ++v) s.voice_first[v + 1] += s.voice_first[v];
     s.progs.resize(run.size());
     std::vector<uint32_t> at(s.voice_first.begin(), s.voice_first.end() - 1);
     for (uint32_t k = 0; k < run.size(); ++k) s.progs[at[voice_of[k]]++] = run[k];   // (stable: the order of `run` inside a voice)
