@@ -54,6 +54,16 @@ extern "C" {
  * programs run after the last voice (programs_per_voice counts the others).  Still refused: a Delay shorter than 64 frames
  * of a value computed by the reading program itself or a later one (a short loop, a bus echo of 32 frames), and everything
  * else of the list above.
+ *
+ * FR_STREAM_INPUTS = 0 / 1 (default 0; read strictly from the environment too; does nothing unless FR_STREAM_PROGRAMS=1):
+ * block streaming also serves plans whose programs read, at the current frame, input slots other than 0 -- control rows: a
+ * gain per voice, a gate, a mod wheel, a master volume -- up to 8 distinct slots, slot 0 included, in per-voice and in bus
+ * programs alike.  fr_stream_block_rows (below) hands in a block's rows; a fourth resident kernel takes all of them in one
+ * look at the doorbell.  With 0 nothing changes: the same plans are served and refused, with the same reasons, by the same
+ * kernels.  "stream" gains "input_slots": the slots whose rows the resident launch reads, slot 0 first, the others ascending
+ * ([0] for a plan that reads nothing else); "kernel" is "bank_stream_in_kernel" exactly when a program reads another slot.
+ * Still refused: more than 8 distinct slots, delayed reads of an input row (a stream keeps no input history), voices whose
+ * time is not slot 0, and everything else of the lists above.
  */
 typedef struct fr_option {
     const char *name;              /* e.g. "FR_BANK_SHORT" */
@@ -67,6 +77,22 @@ fr_status fr_renderer_create_with_options(const fr_config *cfg, const fr_option 
 /* Every per-renderer option as a JSON object: {"FR_BANK_SHORT": {"value": "0", "source": "option"}, ...}; the source is
  * "default", "env" or "option".  The string belongs to the handle and is valid until the next call on it. */
 const char *fr_options_json(fr_renderer *r);
+
+/* ---- block streaming with control rows --------------------------------------------------------
+ * fr_stream_block (friendship_render.h) with the block's input rows in fr_fill_buffer's own shape: row i -- the floats
+ * in_data[in_row_offsets[i] .. in_row_offsets[i + 1]) -- feeds input slot i; fr_stream_block(r, out, n, idx, row, len) is this
+ * call with one row.  `out` receives the stream's rows of n_times (1..64) floats each.
+ *
+ * Statuses and output bits are those of fr_fill_buffer for the same sequence of calls (same slot count, idx and rows) on a
+ * renderer whose first call is a seek, although a stream stores no input samples: a short row is padded with its own last
+ * value, an empty row that continues with the previous block's last value; a slot that gets no row in a block reads +0.0
+ * there; a supplied row must continue its slot's length exactly (FR_ERR_INPUT_HISTORY) and may not be longer than n_times
+ * (FR_ERR_INPUT_TOO_LONG); rows at or beyond the input vector count (slots x frames of the largest call so far) are dropped
+ * and read +0.0.  Rows of slots that no program reads are checked and otherwise ignored.  A refused block leaves the stream
+ * open and everything as it was.  A block that does not continue the previous one is a seek: every input before idx reads
+ * 0.0 and every slot starts again.  Plans whose programs read slots other than 0 need FR_STREAM_INPUTS=1 (above). */
+fr_status fr_stream_block_rows(fr_renderer *r, float *out, uint64_t n_times, uint64_t idx, const float *in_data,
+                               const uint64_t *in_row_offsets, uint32_t n_in_rows);
 
 #ifdef __cplusplus
 }

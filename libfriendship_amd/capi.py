@@ -218,6 +218,10 @@ class RendererLib:
             L.fr_renderer_create_with_options.restype = C.c_int32
             L.fr_options_json.argtypes = [vp]
             L.fr_options_json.restype = C.c_char_p
+        self.has_stream_rows = hasattr(L, "fr_stream_block_rows")
+        if self.has_stream_rows:
+            L.fr_stream_block_rows.argtypes = [vp, vp, C.c_uint64, C.c_uint64, vp, vp, C.c_uint32]
+            L.fr_stream_block_rows.restype = C.c_int32
         if L.fr_abi_version() != FR_ABI_VERSION:
             raise RuntimeError(f"{path}: ABI version {L.fr_abi_version()} != {FR_ABI_VERSION}")
 
@@ -311,6 +315,24 @@ class Renderer:
         if out.dtype != np.float32 or not out.flags["C_CONTIGUOUS"] or out.shape != (self._stream_slots, n):
             raise ValueError(f"stream_block: out must be a C-contiguous float32 array of shape ({self._stream_slots}, {n}), got {out.dtype} {out.shape}")
         self._check(self.L.fr_stream_block(self.h, out.ctypes.data, n, start, row.ctypes.data, n))
+        return out
+
+    def stream_block_rows(self, start, rows, n_times=None, out=None):
+        """Render the frames [start, start + n_times) of every slot from the block's input rows (fr_stream_block_rows): rows[i]
+        feeds input slot i and may be shorter than the block, or empty; n_times defaults to the longest row's length."""
+        if not self.rlib.has_stream_rows:
+            raise RenderError(FR_ERR_UNSUPPORTED, self.rlib.status_string(FR_ERR_UNSUPPORTED), f"{self.rlib.path} has no fr_stream_block_rows")
+        rows = [np.ascontiguousarray(r, dtype=np.float32).ravel() for r in rows]
+        n = max((len(r) for r in rows), default=0) if n_times is None else int(n_times)
+        offs = np.zeros(len(rows) + 1, dtype=np.uint64)
+        if rows:
+            offs[1:] = np.cumsum([len(r) for r in rows])
+        data = np.concatenate(rows) if rows and offs[-1] else np.zeros(1, np.float32)
+        if out is None:
+            out = np.empty((self._stream_slots, n), dtype=np.float32)
+        if out.dtype != np.float32 or not out.flags["C_CONTIGUOUS"] or out.shape != (self._stream_slots, n):
+            raise ValueError(f"stream_block_rows: out must be a C-contiguous float32 array of shape ({self._stream_slots}, {n}), got {out.dtype} {out.shape}")
+        self._check(self.L.fr_stream_block_rows(self.h, out.ctypes.data, n, start, data.ctypes.data, offs.ctypes.data, len(rows)))
         return out
 
     def stream_end(self):

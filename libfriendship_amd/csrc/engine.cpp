@@ -30,6 +30,7 @@
 #include "match.hpp"
 #include "stage.hpp"
 #include "streamplan.hpp"
+#include "streamrows.hpp"
 
 namespace fr {
 
@@ -189,7 +190,7 @@ static std::string stage_variant(const StageLaunchNote &n, const Plan &p) {
     return k;
 }
 
-constexpr size_t N_OPTIONS = 32;         // per-renderer options (friendship_render_ext.h; the table below fr_renderer)
+constexpr size_t N_OPTIONS = 33;         // per-renderer options (friendship_render_ext.h; the table below fr_renderer)
 
 struct TimerClass {
     double ms = 0;
@@ -238,6 +239,9 @@ __attribute__((weak)) hipError_t launch_bank_stream_prog(const BankArgs &, const
     return hipErrorNotSupported;
 }
 __attribute__((weak)) hipError_t launch_bank_stream_bus(const BankArgs &, const StreamProgArgs &, BankStreamCtl *, BankStreamDev *, uint32_t, hipStream_t) {
+    return hipErrorNotSupported;
+}
+__attribute__((weak)) hipError_t launch_bank_stream_in(const BankArgs &, const StreamProgArgs &, uint32_t, BankStreamInCtl *, BankStreamInDev *, uint32_t, hipStream_t) {
     return hipErrorNotSupported;
 }
 __attribute__((weak)) hipError_t launch_track_window(const TrackWindowArgs &a, hipStream_t) {
@@ -509,7 +513,6 @@ struct fr_renderer {
     uint64_t stream_trace_n = 0;
     uint32_t stream_seq = 0, stream_slots = 0;
     uint64_t stream_head = 0;            // first frame after the last streamed block
-    float stream_last = 0.0f;            // that block's last (padded) input value: what a short row continuing it is padded with
     bool stream_have_last = false;
     uint32_t stream_idle_ms = BANK_STREAM_IDLE_MS;   // FR_STREAM_IDLE_MS (tests shorten it)
     int device_cus = 0;
@@ -540,7 +543,11 @@ struct fr_renderer {
     // does not continue the previous one, after the rings were brought up to that block's first frame.
     bool stream_programs = false;        // the option
     bool stream_bus = false;             // FR_STREAM_BUS: mix-bus programs run after the block's last voice (bank_stream_bus_kernel)
+    bool stream_inputs = false;          // FR_STREAM_INPUTS: programs read control rows, up to STREAM_MAX_INPUTS slots (bank_stream_in_kernel)
     bool stream_prog = false;            // the open stream is of that kind
+    bool stream_in = false;              // ... and its doorbell is the rows of stream_plan.input_slots (BankStreamInCtl / BankStreamInDev)
+    StreamRows stream_rows;              // the input store's rules for the open stream's rows, without the samples (streamrows.hpp)
+    DevBuf d_stream_instrs;              // bank_stream_in_kernel: the programs' instructions with S_INPUT's operand rewritten to the streamed row
     bool stream_launched = false;        // its resident launch is running
     const char *stream_kernel = "";      // the last resident launch's kernel (fr_plan_json "stream")
     StreamPlan stream_plan;
@@ -556,6 +563,7 @@ struct fr_renderer {
         env.sharded = sharded();
         env.track_history = tail_on();
         env.bus = stream_bus;
+        env.inputs = stream_inputs;
         return plan_stream(plan.sp, banks, env);
     }
     // Rings the stop and waits for the resident launch to end.  `clean`: the launch was answering when the stop was rung
@@ -563,8 +571,10 @@ struct fr_renderer {
     // run: the counters are cleared before anyone uses them again.
     void stop_resident(bool clean) {
         if (stream_launched) {
-            BankStreamCtl *ctl = (BankStreamCtl *)h_stream_ctl.p;
-            for (int i = 0; i < 64; ++i) __atomic_store_n(&ctl->row[i], (unsigned long long)BANK_STREAM_STOP << 32, __ATOMIC_RELEASE);
+            // (BankStreamCtl::row is BankStreamInCtl::rows[0]: the stop goes to every row the launch looks at)
+            unsigned long long *words = (unsigned long long *)h_stream_ctl.p;
+            const size_t n_words = stream_in ? (size_t)BANK_STREAM_ROWS * 64 : 64;
+            for (size_t i = 0; i < n_words; ++i) __atomic_store_n(&words[i], (unsigned long long)BANK_STREAM_STOP << 32, __ATOMIC_RELEASE);
             if (hipStreamSynchronize(stream) != hipSuccess) { (void)hipGetLastError(); clean = false; }   // the kernel sees the stop within a poll, or ends itself after its bound
         }
         stream_launched = false;
@@ -2136,6 +2146,28 @@ void fr_renderer::begin_program_stream(uint32_t n_slots) {
     const BankLaunch &grp = plan.banks[0].grp;
     for (uint32_t row : grp.rows)
         if (row >= (grp.to_ring ? sp.n_rings : n_slots)) throw Error(FR_ERR_DEVICE, "internal: a streamed voice's row out of bounds");
+    // programs that read control rows (FR_STREAM_INPUTS): the stream's own copy of their instructions, S_INPUT's operand the
+    // streamed row (the position of its slot in input_slots) instead of the plan's input index
+    const bool rows_in = s.input_slots.size() > 1;
+    std::vector<StageInstr> instrs;
+    if (rows_in) {
+        if (s.input_slots.size() > BANK_STREAM_ROWS) throw Error(FR_ERR_DEVICE, "internal: more streamed rows than the kernel takes");
+        for (StageProg &pg : progs) {
+            const uint32_t first = (uint32_t)instrs.size();
+            for (uint32_t k = 0; k < pg.n_instr; ++k) {
+                StageInstr in = sp.instrs[pg.first_instr + k];
+                if (in.op == S_INPUT) {
+                    const auto it = in.imm < sp.input_slots.size() ? std::find(s.input_slots.begin(), s.input_slots.end(), sp.input_slots[in.imm]) : s.input_slots.end();
+                    if (it == s.input_slots.end()) throw Error(FR_ERR_DEVICE, "internal: a streamed program reads a slot the stream does not feed");
+                    in.imm = (uint32_t)(it - s.input_slots.begin());
+                }
+                instrs.push_back(in);
+            }
+            pg.first_instr = first;
+        }
+        d_stream_instrs.ensure(std::max<size_t>(instrs.size(), 1) * sizeof(StageInstr));
+        if (!instrs.empty()) HIP_CHECK(hipMemcpyAsync(d_stream_instrs.p, instrs.data(), instrs.size() * sizeof(StageInstr), hipMemcpyHostToDevice, stream));
+    }
     d_stream_progs.ensure(std::max<size_t>(progs.size(), 1) * sizeof(StageProg));
     d_stream_vfirst.ensure(s.voice_first.size() * sizeof(uint32_t));
     if (!progs.empty()) HIP_CHECK(hipMemcpyAsync(d_stream_progs.p, progs.data(), progs.size() * sizeof(StageProg), hipMemcpyHostToDevice, stream));
@@ -2143,13 +2175,15 @@ void fr_renderer::begin_program_stream(uint32_t n_slots) {
     HIP_CHECK(hipStreamSynchronize(stream));   // (host vectors go out of scope)
     // rings: the deepest look-back and a block, as execute() sizes them for a 64-frame call (which the seek then finds in place)
     if (sp.uses_rings()) grow_rings(ring_capacity(sp, STREAM_BLOCK));
-    h_stream_ctl.ensure(sizeof(BankStreamCtl));
+    h_stream_ctl.ensure(rows_in ? sizeof(BankStreamInCtl) : sizeof(BankStreamCtl));
     h_stream_out.ensure((size_t)n_slots * 64 * sizeof(float));
-    d_stream_dev.ensure(sizeof(BankStreamDev));
-    std::memset(h_stream_ctl.p, 0, sizeof(BankStreamCtl));
+    d_stream_dev.ensure(rows_in ? sizeof(BankStreamInDev) : sizeof(BankStreamDev));
+    std::memset(h_stream_ctl.p, 0, rows_in ? sizeof(BankStreamInCtl) : sizeof(BankStreamCtl));
     stream_plan = std::move(s);
+    stream_rows.open(n_vecs);
     streaming = true;
     stream_prog = true;
+    stream_in = rows_in;
     stream_launched = false;
     stream_seq = 0;
     stream_slots = n_slots;
@@ -2182,6 +2216,9 @@ void fr_renderer::seek_program_stream(uint64_t idx) {
             rollback_store(snap);
             throw;
         }
+        // the warm-up is no call of the host's: the input vectors it made room for (n_slots * warm, reference.rs:60) are not
+        // counted.  (Whatever follows the stream is a seek, which rebuilds the segments from the count.)
+        n_vecs = snap.n_vecs;
     }
     plan.stage_valid = false;                    // from here on the rings run ahead of the input store
     ring_table.valid = false;
@@ -2220,10 +2257,15 @@ void fr_renderer::seek_program_stream(uint64_t idx) {
     p.bank_to_ring = bs.grp.to_ring ? 1u : 0u;
     p.sparkle = mirror.sparkle ? 1u : 0u;
     // (the previous launch's last doorbell and stop are still in the control words: a new launch starts from a clean slate)
-    std::memset(h_stream_ctl.p, 0, sizeof(BankStreamCtl));
-    HIP_CHECK(hipMemsetAsync(d_stream_dev.p, 0, sizeof(BankStreamDev), stream));
-    // a plan with bus programs (FR_STREAM_BUS): the kernel whose last arriver of a block runs them; every other plan: as before
-    if (s.bus_programs()) {
+    std::memset(h_stream_ctl.p, 0, stream_in ? sizeof(BankStreamInCtl) : sizeof(BankStreamCtl));
+    HIP_CHECK(hipMemsetAsync(d_stream_dev.p, 0, stream_in ? sizeof(BankStreamInDev) : sizeof(BankStreamDev), stream));
+    // a plan whose programs read control rows (FR_STREAM_INPUTS): the kernel with a doorbell of rows; a plan with bus programs
+    // (FR_STREAM_BUS): the kernel whose last arriver of a block runs them; every other plan: as before
+    if (stream_in) {
+        p.instrs = d_stream_instrs.as<StageInstr>();
+        HIP_CHECK(launch_bank_stream_in(a, p, (uint32_t)s.input_slots.size(), h_stream_ctl.as_dev<BankStreamInCtl>(), d_stream_dev.as<BankStreamInDev>(), stream_idle_ms, stream));
+        stream_kernel = "bank_stream_in_kernel";
+    } else if (s.bus_programs()) {
         HIP_CHECK(launch_bank_stream_bus(a, p, h_stream_ctl.as_dev<BankStreamCtl>(), d_stream_dev.as<BankStreamDev>(), stream_idle_ms, stream));
         stream_kernel = "bank_stream_bus_kernel";
     } else {
@@ -2292,6 +2334,7 @@ int64_t env_strict_track_history(const char *e);
 int64_t env_strict_ring_keep(const char *e);
 int64_t env_strict_stream_programs(const char *e);
 int64_t env_strict_stream_bus(const char *e);
+int64_t env_strict_stream_inputs(const char *e);
 bool parse_option(const Knob &k, const char *s, int64_t &v);
 
 const Knob kKnobs[] = {
@@ -2366,6 +2409,10 @@ const Knob kKnobs[] = {
     // Mix-bus programs across voices in block streaming (streamplan.hpp StreamEnv::bus; fr_plan_json: stream.bus_programs).
     // Inert without FR_STREAM_PROGRAMS.  Strict and listed once set.
     {"FR_STREAM_BUS", 0, 0, 1, 0, nullptr, 0, env_strict_stream_bus, [](fr_renderer &r, int64_t v, bool) { r.stream_bus = v != 0; }, LISTED_WHEN_SET},
+    // Control rows in block streaming: programs read up to STREAM_MAX_INPUTS input slots at the current frame (streamplan.hpp
+    // StreamEnv::inputs; fr_stream_block_rows; fr_plan_json: stream.input_slots).  Inert without FR_STREAM_PROGRAMS.  Strict and
+    // listed once set.
+    {"FR_STREAM_INPUTS", 0, 0, 1, 0, nullptr, 0, env_strict_stream_inputs, [](fr_renderer &r, int64_t v, bool) { r.stream_inputs = v != 0; }, LISTED_WHEN_SET},
 };
 static_assert(sizeof kKnobs / sizeof kKnobs[0] == N_OPTIONS, "N_OPTIONS counts the rows of kKnobs");
 
@@ -2379,6 +2426,7 @@ int64_t env_strict_track_history(const char *e) { return env_strict("FR_TRACK_HI
 int64_t env_strict_ring_keep(const char *e) { return env_strict("FR_RING_KEEP", e); }
 int64_t env_strict_stream_programs(const char *e) { return env_strict("FR_STREAM_PROGRAMS", e); }
 int64_t env_strict_stream_bus(const char *e) { return env_strict("FR_STREAM_BUS", e); }
+int64_t env_strict_stream_inputs(const char *e) { return env_strict("FR_STREAM_INPUTS", e); }
 
 bool parse_option(const Knob &k, const char *s, int64_t &v) {
     if (k.word && std::strcmp(s, k.word) == 0) {
@@ -2805,6 +2853,8 @@ fr_status fr_stream_begin(fr_renderer *r, uint32_t n_slots) {
         r->streaming = true;
         r->stream_launched = true;
         r->stream_prog = false;
+        r->stream_in = false;
+        r->stream_rows.open(r->n_vecs);
         r->stream_seq = 0;
         r->stream_slots = n_slots;
         r->stream_have_last = false;
@@ -2812,58 +2862,88 @@ fr_status fr_stream_begin(fr_renderer *r, uint32_t n_slots) {
     });
 }
 
+// One block of the open stream: `n_rows` input rows in fr_fill_buffer's shape (row i feeds input slot i).  Statuses and output
+// bits are fr_fill_buffer's for the same sequence of calls: the input store's rules are kept for the rows without storing them
+// (streamrows.hpp), and the rows of the slots the plan reads (StreamPlan::input_slots; a plan without FR_STREAM_INPUTS: slot 0)
+// are the doorbell.
+static void stream_block_rows(fr_renderer *r, float *out, uint64_t n_times, uint64_t idx, const float *in_data, const uint64_t *offs, uint32_t n_rows) {
+    if (n_rows && !offs) throw Error(FR_ERR_INVALID_ARG, "null row offsets");
+    if (n_rows && offs[n_rows] > offs[0] && !in_data) throw Error(FR_ERR_INVALID_ARG, "null input data");
+    if (r->track_from != 0xFFFFFFFFu && n_rows > r->track_from) throw Error(FR_ERR_UNSUPPORTED, "block streaming takes no rows of track slots");
+    // the first block of a stream, and a block that does not continue the previous one, is a seek: every slot unfed, every
+    // input before idx 0.0.  A refused block changes nothing: the next one may follow as if it had not been made.
+    const bool seek = !r->stream_have_last || idx != r->stream_head || (r->stream_prog && !r->stream_launched);
+    {
+        std::string why;
+        const StreamRowsStatus rs = r->stream_rows.check(r->stream_slots, n_times, idx, seek, offs, n_rows, &why);
+        if (rs != STREAM_ROWS_OK) throw Error(rs == STREAM_ROWS_HISTORY ? FR_ERR_INPUT_HISTORY : FR_ERR_INPUT_TOO_LONG, why);
+    }
+    // a plan with programs: the rings are brought up to idx and the resident launch starts there
+    if (r->stream_prog && seek) r->seek_program_stream(idx);
+    const auto t_in = std::chrono::steady_clock::now();
+    // the rows of the slots the plan reads, padded like short rows of fill_buffer (reference.rs:72-73); a slot without a row: +0.0
+    static const uint32_t kSlot0[1] = {0};
+    const uint32_t K = r->stream_in ? (uint32_t)r->stream_plan.input_slots.size() : 1u;
+    const uint32_t *want = r->stream_in ? r->stream_plan.input_slots.data() : kSlot0;
+    float rows[BANK_STREAM_ROWS][STREAM_ROW_FRAMES];
+    r->stream_rows.accept(r->stream_slots, n_times, idx, seek, in_data, offs, n_rows, want, K, rows);
+    r->n_vecs = std::max(r->n_vecs, r->stream_rows.n_vecs);   // (the count the stream reached stays with the renderer)
+    // every word is tagged with the block's number and length: the words are the doorbell (kernels.hpp BankStreamCtl, BankStreamInCtl)
+    r->stream_seq = (r->stream_seq + 1u) & 0xFFFFFFu;
+    if (r->stream_seq == 0 || r->stream_seq == 0xFFFFFFu) r->stream_seq = 1;
+    const uint32_t seq = r->stream_seq << 8 | (uint32_t)n_times;
+    unsigned long long *words = (unsigned long long *)r->h_stream_ctl.p;   // (BankStreamCtl::row is BankStreamInCtl::rows[0])
+    for (uint32_t j = 0; j < K; ++j)
+        for (uint64_t i = 0; i < 64; ++i) {
+            uint32_t bits;
+            std::memcpy(&bits, &rows[j][i], 4);
+            __atomic_store_n(&words[(size_t)j * 64 + i], (unsigned long long)seq << 32 | bits, __ATOMIC_RELAXED);
+        }
+    uint32_t *done = r->stream_in ? &((BankStreamInCtl *)r->h_stream_ctl.p)->done : &((BankStreamCtl *)r->h_stream_ctl.p)->done;
+    uint64_t spins = 0;
+    const auto t_ring = std::chrono::steady_clock::now();
+    while (__atomic_load_n(done, __ATOMIC_ACQUIRE) != seq) {
+        if ((++spins & 0xFFFFFu) != 0) continue;
+        if (hipStreamQuery(r->stream) != hipErrorNotReady) {   // the launch is gone (its own bound, or a fault)
+            (void)hipStreamSynchronize(r->stream);
+            r->stream_launched = false;
+            r->end_stream(false);                              // (it may have ended between two chunks of a voice)
+            throw Error(FR_ERR_DEVICE, "the resident launch ended before the block was rendered");
+        }
+        // a resident launch answers in tens of microseconds; a quarter of a second without an answer means it is not all
+        // resident (something else holds CUs) or the device is in trouble: give the audio thread back
+        if (std::chrono::steady_clock::now() - t_ring > std::chrono::milliseconds(250)) {
+            r->end_stream(false);
+            throw Error(FR_ERR_DEVICE, "the resident launch did not answer within 250 ms");
+        }
+    }
+    const auto t_done = std::chrono::steady_clock::now();
+    const float *res = r->h_stream_out.as<float>();
+    for (uint32_t v = 0; v < r->stream_slots; ++v) std::memcpy(out + (size_t)v * n_times, res + (size_t)v * 64, n_times * sizeof(float));
+    r->stream_head = idx + n_times;
+    r->stream_have_last = true;
+    if (r->host_trace) {   // FR_HOST_TRACE=1: inside the call, without the caller's wrapper
+        r->stream_trace_us[0] += std::chrono::duration<double, std::micro>(t_done - t_in).count();
+        r->stream_trace_us[1] += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_done).count();
+        ++r->stream_trace_n;
+    }
+}
+
+fr_status fr_stream_block_rows(fr_renderer *r, float *out, uint64_t n_times, uint64_t idx, const float *in_data, const uint64_t *in_row_offsets, uint32_t n_in_rows) {
+    return guarded(r, [&] {
+        if (!r->streaming) throw Error(FR_ERR_INVALID_ARG, "no stream is open (fr_stream_begin; any other call on the renderer closes it)");
+        if (!out || n_times == 0 || n_times > 64) throw Error(FR_ERR_INVALID_ARG, "a streamed block is 1..64 frames");
+        stream_block_rows(r, out, n_times, idx, in_data, in_row_offsets, n_in_rows);
+    }, true);
+}
+
+// (one row, for input slot 0: fr_stream_block_rows with that row)
 fr_status fr_stream_block(fr_renderer *r, float *out, uint64_t n_times, uint64_t idx, const float *row, uint64_t row_len) {
     return guarded(r, [&] {
         if (!r->streaming) throw Error(FR_ERR_INVALID_ARG, "no stream is open (fr_stream_begin; any other call on the renderer closes it)");
         if (!out || n_times == 0 || n_times > 64 || row_len > n_times || (row_len && !row)) throw Error(FR_ERR_INVALID_ARG, "a streamed block is 1..64 frames");
-        // a plan with programs: the first block, and a block that does not continue the previous one, is a seek -- the rings
-        // are brought up to idx and the resident launch starts there
-        if (r->stream_prog && (!r->stream_launched || !r->stream_have_last || idx != r->stream_head)) r->seek_program_stream(idx);
-        // (a plan served here reads nothing but this block's row: `idx` enters only through the padding rule)
-        BankStreamCtl *ctl = (BankStreamCtl *)r->h_stream_ctl.p;
-        const auto t_in = std::chrono::steady_clock::now();
-        // the row, padded like a short row of fill_buffer (reference.rs:72-73) with the slot's last stored value: its own last
-        // value, or -- an empty row -- the last value of the block it continues (idx == where that block ended); the first
-        // block of a stream and a block that does not continue the previous one are what a seek leaves: nothing stored, pad 0.
-        // Every word is tagged with the block's number and length: the words are the doorbell (kernels.hpp BankStreamCtl)
-        const float pad = row_len ? row[row_len - 1] : ((r->stream_have_last && idx == r->stream_head) ? r->stream_last : 0.0f);
-        r->stream_seq = (r->stream_seq + 1u) & 0xFFFFFFu;
-        if (r->stream_seq == 0 || r->stream_seq == 0xFFFFFFu) r->stream_seq = 1;
-        const uint32_t seq = r->stream_seq << 8 | (uint32_t)n_times;
-        for (uint64_t i = 0; i < 64; ++i) {
-            const float v = i < row_len ? row[i] : (i < n_times ? pad : 0.0f);
-            uint32_t bits;
-            std::memcpy(&bits, &v, 4);
-            __atomic_store_n(&ctl->row[i], (unsigned long long)seq << 32 | bits, __ATOMIC_RELAXED);
-        }
-        uint64_t spins = 0;
-        const auto t_ring = std::chrono::steady_clock::now();
-        while (__atomic_load_n(&ctl->done, __ATOMIC_ACQUIRE) != seq) {
-            if ((++spins & 0xFFFFFu) != 0) continue;
-            if (hipStreamQuery(r->stream) != hipErrorNotReady) {   // the launch is gone (its own bound, or a fault)
-                (void)hipStreamSynchronize(r->stream);
-                r->stream_launched = false;
-                r->end_stream(false);                              // (it may have ended between two chunks of a voice)
-                throw Error(FR_ERR_DEVICE, "the resident launch ended before the block was rendered");
-            }
-            // a resident launch answers in tens of microseconds; a quarter of a second without an answer means it is not all
-            // resident (something else holds CUs) or the device is in trouble: give the audio thread back
-            if (std::chrono::steady_clock::now() - t_ring > std::chrono::milliseconds(250)) {
-                r->end_stream(false);
-                throw Error(FR_ERR_DEVICE, "the resident launch did not answer within 250 ms");
-            }
-        }
-        const auto t_done = std::chrono::steady_clock::now();
-        const float *res = r->h_stream_out.as<float>();
-        for (uint32_t v = 0; v < r->stream_slots; ++v) std::memcpy(out + (size_t)v * n_times, res + (size_t)v * 64, n_times * sizeof(float));
-        r->stream_last = n_times <= row_len ? row[n_times - 1] : pad;
-        r->stream_head = idx + n_times;
-        r->stream_have_last = true;
-        if (r->host_trace) {   // FR_HOST_TRACE=1: inside the call, without the caller's wrapper
-            r->stream_trace_us[0] += std::chrono::duration<double, std::micro>(t_done - t_in).count();
-            r->stream_trace_us[1] += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_done).count();
-            ++r->stream_trace_n;
-        }
+        const uint64_t offs[2] = {0, row_len};
+        stream_block_rows(r, out, n_times, idx, row, offs, 1);
     }, true);
 }
 
@@ -2991,12 +3071,14 @@ const char *fr_plan_json(fr_renderer *r) {
             const StreamPlan s = r->plan_stream_now();
             std::string per;
             for (uint32_t n : s.programs_per_voice()) per += (per.empty() ? "" : ",") + std::to_string(n);
+            std::string ins;
+            for (uint32_t n : s.input_slots) ins += (ins.empty() ? "" : ",") + std::to_string(n);
             std::string why;
             for (char c : s.reason) { if (c == '"' || c == '\\') why += '\\'; why += c; }
             r->plan_json_cache += std::string(",\"stream\":{\"servable\":") + (s.servable ? "true" : "false") + ",\"reason\":\"" + why +
                                   "\",\"voices\":" + std::to_string(s.voices) + ",\"chunks\":" + std::to_string(s.chunks) + ",\"programs_per_voice\":[" + per +
                                   "],\"bus_programs\":" + std::to_string(s.bus_programs()) + ",\"min_ring_delay\":" + std::to_string(s.min_ring_delay) + ",\"rings\":" + std::to_string(r->plan.sp.n_rings) +
-                                  ",\"kernel\":\"" + r->stream_kernel + "\"}";
+                                  ",\"input_slots\":[" + ins + "],\"kernel\":\"" + (s.servable && s.input_slots.size() > 1 ? "bank_stream_in_kernel" : std::strcmp(r->stream_kernel, "bank_stream_in_kernel") ? r->stream_kernel : "") + "\"}";
         }
         r->plan_json_cache += ",\"exchange_stats\":{\"calls\":" + std::to_string(r->exchange_calls) + ",\"tiles\":" + std::to_string(r->exchange_tiles) +
                               ",\"bytes_sent\":" + std::to_string(r->exchange_bytes) + "},\"bank_launches\":[";

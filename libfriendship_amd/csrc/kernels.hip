@@ -1927,6 +1927,282 @@ hipError_t launch_bank_stream_bus(const BankArgs &a, const StreamProgArgs &p, Ba
 }
 
 // ---------------------------------------------------------------------------------------------------
+// Block streaming with control rows (FR_STREAM_INPUTS, streamplan.hpp, kernels.hpp BankStreamInCtl): what
+// bank_stream_bus_kernel does -- per-voice programs in the wave that finishes a voice, the bus programs (a segment that may be
+// empty) in the wave that counts the block's last voice in -- with a doorbell of n_rows rows and S_INPUT by row.  Workgroup 0's
+// one polling loop looks at every row's words at once and republishes the rows to device memory before it releases the others
+// (stores, vmcnt(0), seq); a finishing wave reads row j > 0 of the republished rows after it has seen that seq, a relaxed
+// agent-scope load with the program's other leading loads.  Row 0 is the `t` it already holds.  No new polling loop, no acquire
+// or release.  The kernel and its interpreter have their own text: the three older streaming kernels' code does not change.
+// ---------------------------------------------------------------------------------------------------
+__device__ __forceinline__ float stream_in_load(const StreamProgArgs &p, const BankStreamInDev *dev, const StageInstr &in, uint64_t frame, uint32_t lane, float t) {
+    switch (in.op) {
+    case S_CONST: return __uint_as_float(in.imm);
+    case S_INPUT:   // imm: the streamed row (the host rewrote it); rows the launch does not stream hold +0.0
+        return in.imm == 0u ? t : __hip_atomic_load(&dev->rows[in.imm & (BANK_STREAM_ROWS - 1u)][lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    case S_READ:
+        return frame >= in.d_lo ? __hip_atomic_load(p.rings + (size_t)in.buf * (p.ring_mask + 1) + ((frame - in.d_lo) & p.ring_mask), __ATOMIC_RELAXED,
+                                                    __HIP_MEMORY_SCOPE_AGENT)
+                                : 0.0f;
+    default: return frame >= in.d_lo ? __uint_as_float(in.imm) : 0.0f;   // S_STEP
+    }
+}
+
+__device__ __forceinline__ void stream_in_run_programs(const BankArgs &a, const StreamProgArgs &p, const BankStreamInDev *dev, float (*regs)[64], uint32_t p_first,
+                                                       uint32_t p_end, uint64_t frame, uint32_t lane, bool live, float t) {
+    const uint64_t ring_cap = p.ring_mask + 1;
+    for (uint32_t pi = p_first; pi < p_end; ++pi) {
+        // what this wave has stored so far (the voice's ring, an earlier program's rings) is in L2 before it is read back
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        const StageProg pg = p.progs[pi];
+        const StageInstr *ins = p.instrs + pg.first_instr;
+        uint32_t i = 0;
+        for (; i + 4u <= pg.n_loads; i += 4u) {   // the program's leading loads (rings and control rows), four round trips to L2 in flight together
+            float ld[4];
+#pragma unroll
+            for (uint32_t j = 0; j < 4u; ++j) ld[j] = stream_in_load(p, dev, ins[i + j], frame, lane, t);
+#pragma unroll
+            for (uint32_t j = 0; j < 4u; ++j) regs[ins[i + j].dst][lane] = ld[j];
+        }
+        for (; i < pg.n_instr; ++i) {
+            const StageInstr in = ins[i];
+            float v;
+            switch (in.op) {
+            case S_SUM2: v = regs[in.a][lane] + regs[in.b][lane]; break;
+            case S_MUL: v = regs[in.a][lane] * regs[in.b][lane]; break;
+            case S_DIV: v = regs[in.a][lane] / regs[in.b][lane]; break;
+            case S_MOD: v = prim_mod(regs[in.a][lane], regs[in.b][lane]); break;
+            case S_MIN: v = prim_min(regs[in.a][lane], regs[in.b][lane], p.sparkle != 0u); break;
+            case S_STORE:
+                if (live) __hip_atomic_store(p.rings + (size_t)in.buf * ring_cap + (frame & p.ring_mask), regs[in.a][lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                continue;
+            default: v = stream_in_load(p, dev, in, frame, lane, t); break;
+            }
+            regs[in.dst][lane] = v;
+        }
+        const float res = regs[pg.result_reg][lane];
+        if (live && pg.dst_ring != 0xFFFFFFFFu)
+            __hip_atomic_store(p.rings + (size_t)pg.dst_ring * ring_cap + (frame & p.ring_mask), res, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (live && pg.out_row >= 0) __hip_atomic_store(a.out + (size_t)pg.out_row * 64u + lane, res, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+}
+
+// Workgroup 0's wait for the next block, the one polling loop of the kernel (bounded on the wall clock as in bank_stream_kernel),
+// for a doorbell of K rows.  One look = the loads of all K rows in flight together, then one wait: a word whose tag is new
+// carries its sample with it, so however many rows there are the block costs one trip across PCIe.  The block has arrived
+// when every lane of every row holds the same new tag; the rows are then republished to device memory (acknowledged before
+// the caller stores n_times and seq).  Returns the block's tag (BANK_STREAM_STOP: stop, or no block within the bound).
+template <uint32_t K>
+__device__ __forceinline__ uint32_t stream_in_wait(BankStreamInCtl *ctl, BankStreamInDev *dev, uint32_t lane, uint32_t seen, unsigned long long idle_ticks, uint32_t &T) {
+    unsigned long long word[K];
+    uint32_t tag = seen;
+    bool fresh = false;
+    const unsigned long long wait_from = __builtin_amdgcn_s_memrealtime();
+    for (;;) {
+        static_for<0, K>([&](auto j) { word[j] = __hip_atomic_load(&ctl->rows[j][lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); });
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        tag = (uint32_t)(word[0] >> 32);
+        const uint32_t first = (uint32_t)__builtin_amdgcn_readfirstlane(tag);
+        bool same = tag != seen && tag == first;
+        static_for<1, K>([&](auto j) { same = same && (uint32_t)(word[j] >> 32) == first; });
+        fresh = __all(same);
+        if (fresh || __builtin_amdgcn_s_memrealtime() - wait_from > idle_ticks) break;
+    }
+    const uint32_t seq = fresh ? __builtin_amdgcn_readfirstlane(tag) : BANK_STREAM_STOP;
+    T = 0;
+    if (seq != BANK_STREAM_STOP) {
+        T = seq & 0xFFu;
+        T = T > 64u ? 64u : T;
+        static_for<0, K>([&](auto j) {
+            __hip_atomic_store(&dev->rows[j][lane], lane < T ? __uint_as_float((uint32_t)word[j]) : 0.0f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        });
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    return seq;
+}
+
+__global__ void __launch_bounds__(1024) bank_stream_in_kernel(BankArgs a, StreamProgArgs p, uint32_t n_rows, BankStreamInCtl *ctl, BankStreamInDev *dev, uint32_t idle_ms) {
+    constexpr int NW = 16;
+    __shared__ float sm[NW][64];
+    __shared__ float regs[STAGE_REGS][64];                   // the interpreter's registers: [register][lane] of wave 0
+    __shared__ unsigned long long zshared;
+    __shared__ uint32_t s_seq, s_T;
+    const uint32_t clog = a.log2_p - a.chunk_log2, nchunks = 1u << clog;
+    const uint32_t chunk = blockIdx.x & (nchunks - 1u);
+    const uint32_t voice = blockIdx.x >> clog;               // (the grid is exactly n_voices * nchunks workgroups)
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t Pc = 1u << a.chunk_log2;
+    const uint32_t Pw = Pc / NW, ngroups = Pw >> 3;
+    uint32_t levels = 0;
+    while ((1u << levels) < ngroups) ++levels;
+    const unsigned long long idle_ticks = (unsigned long long)idle_ms * 100000ull;
+    const float *mine = (const float *)(a.params + ((size_t)voice << a.log2_p) + (size_t)chunk * Pc + (size_t)wave * Pw);
+    const size_t vstride = (size_t)a.n_voices * 64u;
+    const uint64_t ring_cap = p.ring_mask + 1;
+    uint64_t head = p.head;                                  // first frame of the block being rendered (the same in every workgroup)
+    uint32_t seen = 0;
+    if (blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store(&ctl->alive, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    for (;;) {
+        // ---- wait for the next block (bounded), as bank_stream_kernel; the doorbell is n_rows rows ----
+        if (blockIdx.x == 0) {
+            if (wave == 0u) {
+                // (launch-uniform row count: one jump, then a loop whose every look is straight-line code)
+                uint32_t T = 0, seq;
+                switch (n_rows) {
+                case 1: seq = stream_in_wait<1>(ctl, dev, lane, seen, idle_ticks, T); break;
+                case 2: seq = stream_in_wait<2>(ctl, dev, lane, seen, idle_ticks, T); break;
+                case 3: seq = stream_in_wait<3>(ctl, dev, lane, seen, idle_ticks, T); break;
+                case 4: seq = stream_in_wait<4>(ctl, dev, lane, seen, idle_ticks, T); break;
+                case 5: seq = stream_in_wait<5>(ctl, dev, lane, seen, idle_ticks, T); break;
+                case 6: seq = stream_in_wait<6>(ctl, dev, lane, seen, idle_ticks, T); break;
+                case 7: seq = stream_in_wait<7>(ctl, dev, lane, seen, idle_ticks, T); break;
+                default: seq = stream_in_wait<8>(ctl, dev, lane, seen, idle_ticks, T); break;
+                }
+                if (lane == 0u) {
+                    __hip_atomic_store(&dev->n_times, T, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                    __hip_atomic_store(&dev->seq, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    s_seq = seq;
+                    s_T = T;
+                }
+            }
+        } else if (threadIdx.x == 0) {
+            uint32_t seq = seen;
+            const unsigned long long wait_from = __builtin_amdgcn_s_memrealtime();
+            for (;;) {
+                seq = __hip_atomic_load(&dev->seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (seq != seen || __builtin_amdgcn_s_memrealtime() - wait_from > 2ull * idle_ticks + 10000000ull) break;
+                __builtin_amdgcn_s_sleep(4);
+            }
+            if (seq == seen) seq = BANK_STREAM_STOP;
+            s_seq = seq;
+            s_T = __hip_atomic_load(&dev->n_times, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        __syncthreads();
+        const uint32_t seq = s_seq, T = s_T;
+        if (seq == BANK_STREAM_STOP) break;
+        seen = seq;
+        {
+            // ---- one (voice, chunk) of one tile, as bank_stream_kernel ----
+            const bool live = lane < T;
+            ParamGroup first;
+            load_group(first, (const_f32_ptr)mine, 0);
+            const float t = live ? __hip_atomic_load(&dev->rows[0][lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0f;
+            const bool fast = a.fast_ok && __all(t >= 0.0f && t <= 4294967296.0f);
+            const float tt[1] = {t};
+            float r_wave[1];
+            if (fast) bank_wave_sum<1, true, false>(mine, ngroups, levels, tt, r_wave, &first);
+            else bank_wave_sum<1, false, false>(mine, ngroups, levels, tt, r_wave, &first);
+            sm[wave][lane] = r_wave[0];
+            __syncthreads();
+            float r = 0.0f;
+            if (wave == 0u) {
+                float s[NW];
+                static_for<0, NW>([&](auto w) { s[w] = sm[w][lane]; });
+                static_for<0, NW / 2>([&](auto i) { s[i] = s[2 * i] + s[2 * i + 1]; });
+                static_for<0, NW / 4>([&](auto i) { s[i] = s[2 * i] + s[2 * i + 1]; });
+                static_for<0, NW / 8>([&](auto i) { s[i] = s[2 * i] + s[2 * i + 1]; });
+                static_for<0, NW / 16>([&](auto i) { s[i] = s[2 * i] + s[2 * i + 1]; });
+                r = s[0];
+                const unsigned long long z = __ballot(live && r == 0.0f);
+                if (lane == 0u) zshared = z;
+            }
+            __syncthreads();
+            const unsigned long long zm = zshared;
+            if (zm != 0ull) {
+                const bool ok = fast ? wave_leaves_all_negzero<true>(mine, ngroups, t, zm) : wave_leaves_all_negzero<false>(mine, ngroups, t, zm);
+                sm[wave][lane] = ok ? 1.0f : 0.0f;
+                __syncthreads();
+                if (wave == 0u && ((zm >> lane) & 1ull)) {
+                    bool all = true;
+                    static_for<0, NW>([&](auto w) { all = all && sm[w][lane] != 0.0f; });
+                    r = all ? -0.0f : 0.0f;
+                }
+            }
+            if (wave == 0u) {
+                bool finished_voice = nchunks == 1u;
+                float result = r;
+                if (nchunks > 1u) {
+                    float *slot = a.ws + (size_t)voice * 64u;
+                    __hip_atomic_store(slot + (size_t)chunk * vstride + lane, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                    uint32_t old = 0u;
+                    if (lane == 0u) old = __hip_atomic_fetch_add(a.tickets + (size_t)voice * TICKET_STRIDE, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    old = __builtin_amdgcn_readfirstlane(old);
+                    if (old == nchunks - 1u) {
+                        finished_voice = true;
+                        float c0 = 0.0f, c1 = 0.0f, c2 = 0.0f, c3 = 0.0f, c4 = 0.0f, c5 = 0.0f, c6 = 0.0f, c7 = 0.0f, c8 = 0.0f;
+                        for (uint32_t c = 0; c < nchunks; ++c) {
+                            float v = c == chunk ? r : __hip_atomic_load(slot + (size_t)c * vstride + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                            do {
+                                if (!(c & 1u)) { c0 = v; break; } v = c0 + v;
+                                if (!(c & 2u)) { c1 = v; break; } v = c1 + v;
+                                if (!(c & 4u)) { c2 = v; break; } v = c2 + v;
+                                if (!(c & 8u)) { c3 = v; break; } v = c3 + v;
+                                if (!(c & 16u)) { c4 = v; break; } v = c4 + v;
+                                if (!(c & 32u)) { c5 = v; break; } v = c5 + v;
+                                if (!(c & 64u)) { c6 = v; break; } v = c6 + v;
+                                if (!(c & 128u)) { c7 = v; break; } v = c7 + v;
+                                c8 = v;
+                            } while (0);
+                        }
+                        result = c8;
+                        result = clog == 7u ? c7 : result; result = clog == 6u ? c6 : result; result = clog == 5u ? c5 : result;
+                        result = clog == 4u ? c4 : result; result = clog == 3u ? c3 : result; result = clog == 2u ? c2 : result;
+                        result = clog == 1u ? c1 : result;
+                        if (lane == 0u) __hip_atomic_store(a.tickets + (size_t)voice * TICKET_STRIDE, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    }
+                }
+                if (finished_voice) {
+                    // ---- the voice's frames head + lane: to its ring (or its row), then its programs, lane = frame (as bank_stream_prog_kernel) ----
+                    const uint64_t frame = head + lane;
+                    const uint32_t dst = a.rows[voice];
+                    if (live) {
+                        if (p.bank_to_ring) __hip_atomic_store(p.rings + (size_t)dst * ring_cap + (frame & p.ring_mask), result, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        else __hip_atomic_store(a.out + (size_t)dst * 64u + lane, result, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                    }
+                    stream_in_run_programs(a, p, dev, regs, p.voice_first[voice], p.voice_first[voice + 1], frame, lane, live, t);
+                    // ring and row stores alike are acknowledged before the voice is counted in: the block's done tag then implies
+                    // that every ring store of the block has landed
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                    // the ticket goes to the whole wave: the last arriver of the block runs the bus programs, lane = frame
+                    uint32_t n = 0u;
+                    if (lane == 0u) n = __hip_atomic_fetch_add(&dev->voices_done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    n = __builtin_amdgcn_readfirstlane(n);
+                    if (n == a.n_voices - 1u) {
+                        // every voice's ring and row stores were acknowledged before its ticket, and this wave's loads are issued
+                        // after its own ticket came back: the hand-over of the chunk sums
+                        stream_in_run_programs(a, p, dev, regs, p.voice_first[a.n_voices], p.voice_first[a.n_voices + 1], frame, lane, live, t);
+                        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // host rows and rings have landed before the done tag
+                        if (lane == 0u) {
+                            __hip_atomic_store(&dev->voices_done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                            __hip_atomic_store(&ctl->done, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                        }
+                    }
+                }
+            }
+        }
+        head += T;
+        __syncthreads();   // LDS is reused by the next block
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store(&ctl->alive, 0u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+hipError_t launch_bank_stream_in(const BankArgs &a, const StreamProgArgs &p, uint32_t n_rows, BankStreamInCtl *ctl_dev, BankStreamInDev *dev, uint32_t idle_ms,
+                                 hipStream_t s) {
+    if (a.chunk_log2 < 7 || a.chunk_log2 > 13 || a.chunk_log2 > a.log2_p || a.log2_p - a.chunk_log2 > 8) return hipErrorInvalidValue;
+    if (((uint64_t)a.n_voices << (a.log2_p - a.chunk_log2)) > BANK_STREAM_WGS || a.n_voices == 0) return hipErrorInvalidValue;
+    if (a.chunk_log2 != a.log2_p && (!a.ws || !a.tickets)) return hipErrorInvalidValue;
+    if (a.leaf_variant != 1 || !a.out || !a.rows || !ctl_dev || !dev || !p.voice_first) return hipErrorInvalidValue;
+    if ((p.ring_mask & (p.ring_mask + 1)) != 0 || (p.n_rings && (!p.rings || p.ring_mask + 1 < 64u)) || (p.bank_to_ring && !p.n_rings)) return hipErrorInvalidValue;
+    if (n_rows == 0 || n_rows > BANK_STREAM_ROWS) return hipErrorInvalidValue;
+    const uint32_t wgs = a.n_voices << (a.log2_p - a.chunk_log2);
+    hipLaunchKernelGGL(bank_stream_in_kernel, dim3(wgs), dim3(1024), 0, s, a, p, n_rows, ctl_dev, dev, idle_ms ? idle_ms : BANK_STREAM_IDLE_MS);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------------
 // Partial-block exchange, one level of the voices' Sum2 trees (kernels.hpp ShardCombineArgs).  HBM-bound: 12 bytes per
 // frame of a row; rows are contiguous and lanes run over frames, so every access is a full 256-byte line per wave.
 __global__ void __launch_bounds__(256) shard_combine_kernel(ShardCombineArgs a) {

@@ -215,6 +215,32 @@ hipError_t launch_bank_stream_prog(const BankArgs &a, const StreamProgArgs &p, B
 // row stores before its ticket, the last arriver loads after its own: no wait, no acquire or release, no new polling loop.
 hipError_t launch_bank_stream_bus(const BankArgs &a, const StreamProgArgs &p, BankStreamCtl *ctl_dev, BankStreamDev *dev, uint32_t idle_ms, hipStream_t s);
 
+// bank_stream_in_kernel (FR_STREAM_INPUTS): bank_stream_bus_kernel's work -- per-voice programs, then the bus programs in the
+// block's last arriver, a segment that may be empty -- for programs that read control rows: up to BANK_STREAM_ROWS input slots
+// at the current frame.  The doorbell is the block's `n_rows` rows (launch-uniform, 1..BANK_STREAM_ROWS; row 0 is the time
+// slot's): every word carries its sample and the block's tag as in BankStreamCtl, wave 0 of workgroup 0 has the loads of all
+// the rows in flight together in each look, and the block has arrived when every lane of every row holds the same new tag --
+// one trip across PCIe however many rows there are.  It republishes the rows to BankStreamInDev::rows and releases the other
+// workgroups as bank_stream_kernel does.  S_INPUT's operand is the ROW: `instrs` is the stream's own copy of the programs'
+// instructions with every S_INPUT's imm rewritten to its streamed row (engine.cpp begin_program_stream); row 0 stays the `t`
+// the finishing wave holds in a register, the others are loaded with the program's leading loads.
+constexpr uint32_t BANK_STREAM_ROWS = 8;
+struct BankStreamInCtl {      // mapped pinned host memory
+    unsigned long long rows[BANK_STREAM_ROWS][64];   // host -> device: word i of row j = rows[j][i] (low half) | tag (high half)
+    uint32_t done;            // device -> host: tag of the last finished block
+    uint32_t alive;           // device -> host: 1 while the kernel is resident, 0 once it has ended
+    uint32_t pad1[14];
+};
+struct BankStreamInDev {      // device memory
+    uint32_t seq;             // the doorbell, republished by workgroup 0 (0xFFFFFFFF = stop)
+    uint32_t n_times;
+    uint32_t voices_done;
+    uint32_t pad[13];
+    float rows[BANK_STREAM_ROWS][64];
+};
+hipError_t launch_bank_stream_in(const BankArgs &a, const StreamProgArgs &p, uint32_t n_rows, BankStreamInCtl *ctl_dev, BankStreamInDev *dev,
+                                 uint32_t idle_ms, hipStream_t s);
+
 // One step of the partial-block exchange (friendship_render.h FR_SHARD_PARTIALS): row i, window frame t:
 //   v = lo[i][t] + hi[i][t]         the Sum2 node one level up: left sub-tree + right sub-tree, one f32 add
 // stored to dst_ws[i][t] (steps before the last; may alias lo or hi), or -- the last step, dst_ws == null -- where the

@@ -12,6 +12,9 @@
 // tag) knows that every voice and every voice's programs have finished, and runs the BUS PROGRAMS before it writes the tag
 // (kernels.hip bank_stream_bus_kernel).  A bus program may read below 64 frames any voice's ring and any ring that an earlier
 // program of the block stores.
+// With FR_STREAM_INPUTS=1 (StreamEnv::inputs) a program may read, at the current frame, input slots other than 0 -- control
+// rows: a gain, a gate, a fader -- up to STREAM_MAX_INPUTS distinct slots, slot 0 included.  The block then brings one row per
+// slot of StreamPlan::input_slots, in that order (kernels.hip bank_stream_in_kernel; streamrows.hpp keeps the slots' books).
 #pragma once
 
 #include <algorithm>
@@ -26,6 +29,7 @@ namespace fr {
 
 constexpr uint32_t STREAM_BLOCK = 64;        // the longest block a stream accepts
 constexpr uint32_t STREAM_MAX_WGS = 256;     // (= kernels.hpp BANK_STREAM_WGS)
+constexpr uint32_t STREAM_MAX_INPUTS = 8;    // most distinct input slots the streamed programs may read, slot 0 included (= kernels.hpp BANK_STREAM_ROWS)
 
 // What the rule needs to know besides the plan.
 struct StreamEnv {
@@ -36,6 +40,7 @@ struct StreamEnv {
     bool sharded = false;
     bool track_history = false;      // FR_TRACK_HISTORY is on (every call appends to the track rings)
     bool bus = false;                // FR_STREAM_BUS: programs that read several voices of a block run after the last voice
+    bool inputs = false;             // FR_STREAM_INPUTS: programs may read input slots other than 0 at the current frame
 };
 
 struct StreamPlan {
@@ -47,6 +52,8 @@ struct StreamPlan {
     std::vector<uint32_t> voice_first;   // [voices + 2] into `progs`: [voice_first[voices], voice_first[voices + 1]) is the bus segment
     uint64_t min_ring_delay = 0;         // shortest delayed read of a ring that a program stores (0: there is none)
     uint64_t lookback = 0;               // deepest ring read of the assigned programs
+    std::vector<uint32_t> input_slots{0};   // the distinct input slots the voices and the assigned programs read: slot 0 (the voices' time)
+                                         // first, the others ascending -- the order of a block's streamed rows
     std::vector<uint32_t> programs_per_voice() const {
         std::vector<uint32_t> n;
         for (size_t v = 0; v + 2 < voice_first.size(); ++v) n.push_back(voice_first[v + 1] - voice_first[v]);
@@ -87,6 +94,7 @@ inline StreamPlan plan_stream(const StagedPlan &sp, const std::vector<const Bank
     s.chunk_log2 = c;
     s.chunks = 1u << (b.log2_p - c);
     s.bank_to_ring = b.to_ring;
+    std::vector<uint32_t> others;                    // slots other than 0 that the assigned programs read (StreamEnv::inputs)
 
     // the programs that do a block's work: the fused form (a feedback plan: level by level, then its row copies); a plan whose
     // programs are ONE level deep has no fused form because that level already is one
@@ -153,6 +161,10 @@ inline StreamPlan plan_stream(const StagedPlan &sp, const std::vector<const Bank
             switch (in.op) {
             case S_CONST: case S_STEP: case S_SUM2: case S_MUL: case S_DIV: case S_MOD: case S_MIN: case S_STORE: break;
             case S_INPUT:
+                if (env.inputs && in.imm < sp.input_slots.size()) {
+                    if (sp.input_slots[in.imm] != 0) others.push_back(sp.input_slots[in.imm]);
+                    break;
+                }
                 if (in.imm >= sp.input_slots.size() || sp.input_slots[in.imm] != 0)
                     return refuse("a program reads input slot " + std::to_string(in.imm < sp.input_slots.size() ? sp.input_slots[in.imm] : in.imm) +
                                   "; block streaming feeds slot 0 only");
@@ -196,6 +208,11 @@ inline StreamPlan plan_stream(const StagedPlan &sp, const std::vector<const Bank
         if (pg.result_reg >= STAGE_REGS) return refuse("a program needs more registers than the streamed interpreter has");
         voice_of[k] = bus ? BUS : mine != NONE ? mine : run[k] % V;   // (reads no voice at a short delay: any one voice, the same every time)
     }
+    std::sort(others.begin(), others.end());
+    others.erase(std::unique(others.begin(), others.end()), others.end());
+    if (1 + others.size() > STREAM_MAX_INPUTS)
+        return refuse("the programs read " + std::to_string(1 + others.size()) + " distinct input slots (slot 0 included); block streaming feeds at most " +
+                      std::to_string(STREAM_MAX_INPUTS));
     // each output row: one assigned program, or the bank itself
     std::vector<uint32_t> writers(env.n_slots, 0);
     auto writes = [&](int64_t row) { if (row >= 0 && row < (int64_t)env.n_slots) ++writers[(size_t)row]; return row < (int64_t)env.n_slots; };
@@ -214,6 +231,7 @@ inline StreamPlan plan_stream(const StagedPlan &sp, const std::vector<const Bank
     std::vector<uint32_t> at(s.voice_first.begin(), s.voice_first.end() - 1);
     for (uint32_t k = 0; k < run.size(); ++k) s.progs[at[voice_of[k]]++] = run[k];   // (stable: the order of `run` inside a voice)
     s.min_ring_delay = min_delay == UINT64_MAX ? 0 : min_delay;
+    s.input_slots.insert(s.input_slots.end(), others.begin(), others.end());
     s.servable = true;
     return s;
 }

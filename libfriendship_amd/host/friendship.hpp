@@ -661,6 +661,7 @@ protected:
         decltype(&fr_fill_buffer_dense) fill_dense;
     } api_{};
     decltype(&fr_options_json) options_json_ = nullptr;   // (optional: the product's extension)
+    decltype(&fr_stream_block_rows) stream_block_rows_ = nullptr;   // (optional too: block streaming with control rows)
 
     template <class T>
     void sym(T &fn, const char *name) {
@@ -749,6 +750,7 @@ public:
             throw Panic(s, (options.empty() ? "fr_renderer_create: " : "fr_renderer_create_with_options: ") + what);
         }
         options_json_ = (decltype(&fr_options_json))dlsym(dl_, "fr_options_json");
+        stream_block_rows_ = (decltype(&fr_stream_block_rows))dlsym(dl_, "fr_stream_block_rows");
     }
     PluginRenderer(const PluginRenderer &) = delete;
     PluginRenderer &operator=(const PluginRenderer &) = delete;
@@ -790,6 +792,27 @@ public:
         if (buff.rows != stream_slots_ || buff.data.size() != (size_t)buff.rows * buff.cols)
             throw std::invalid_argument("stream_block: the buffer must have the " + std::to_string(stream_slots_) + " rows the stream was begun with");
         check(api_.stream_block(h_, buff.data.data(), buff.cols, idx, row.data(), row.size()));
+    }
+    // A block with control rows (friendship_render_ext.h fr_stream_block_rows): inputs[i] feeds input slot i, as fill_buffer's
+    // Jagged2.  A plugin without the entry point serves the one-row form only (Panic with FR_ERR_UNSUPPORTED for more rows).
+    bool has_stream_rows() const { return stream_block_rows_ != nullptr; }
+    void stream_block_rows(Array2 &buff, uint64_t idx, const std::vector<std::vector<float>> &inputs) {
+        if (buff.rows != stream_slots_ || buff.data.size() != (size_t)buff.rows * buff.cols)
+            throw std::invalid_argument("stream_block_rows: the buffer must have the " + std::to_string(stream_slots_) + " rows the stream was begun with");
+        if (!stream_block_rows_) {
+            if (inputs.size() > 1) throw Panic(FR_ERR_UNSUPPORTED, "the renderer plugin lacks fr_stream_block_rows: a streamed block takes one row");
+            static const std::vector<float> none;
+            const std::vector<float> &row = inputs.empty() ? none : inputs[0];
+            check(api_.stream_block(h_, buff.data.data(), buff.cols, idx, row.data(), row.size()));
+            return;
+        }
+        std::vector<float> data;
+        std::vector<uint64_t> offs(1, 0);
+        for (const auto &row : inputs) {
+            data.insert(data.end(), row.begin(), row.end());
+            offs.push_back(data.size());
+        }
+        check(stream_block_rows_(h_, buff.data.data(), buff.cols, idx, data.data(), offs.data(), (uint32_t)inputs.size()));
     }
     void stream_end() { check(api_.stream_end(h_)); }
 
