@@ -665,12 +665,13 @@ struct JitSim {
 };
 
 static void check_compiled_programs(const Build &b, uint32_t n_slots, uint64_t T, const std::vector<uint64_t> &starts, const char *what,
-                                    std::function<void(const StageJitPlan &)> inspect = nullptr) {
+                                    std::function<void(const StageJitPlan &)> inspect = nullptr, const std::vector<float> *values = nullptr) {
     Mirror m;
     b.apply(m);
     FlatGraph fg = lower(m, n_slots);
     StagedPlan sp = plan_stages(fg, true, true, 20);
     CHECK(!sp.progs.empty());
+    if (values) CHECK(sp.pull_rows.empty());   // (every row is compared: none may have left for the pull interpreter)
     JitSim sim(sp, T);
     if (std::getenv("FR_TEST_VERBOSE")) std::fprintf(stderr, "%s: progs %zu fused %u levels %zu shapes %u\n", what, sp.progs.size(), sp.fused_count, sp.level_first.size() - 1, sim.sj.n_shapes);
     if (inspect) inspect(sim.sj);
@@ -681,6 +682,8 @@ static void check_compiled_programs(const Build &b, uint32_t n_slots, uint64_t T
     for (uint64_t idx : starts) {
         std::vector<float> row0(T), row1(T);
         for (uint64_t i = 0; i < T; ++i) { row0[i] = (float)(idx + i); row1[i] = nd(rng); }
+        if (values)   // the caller's operands instead: row 0 repeats each, row 1 cycles through them (every pair where T = n * n)
+            for (uint64_t i = 0; i < T; ++i) { row0[i] = (*values)[(idx + i) / values->size() % values->size()]; row1[i] = (*values)[(idx + i) % values->size()]; }
         for (auto &h : hist) h.resize(idx, 0.0f);   // a seek leaves zeros behind (reference.rs:52-60); starts only grow here
         hist[0].insert(hist[0].end(), row0.begin(), row0.end());
         hist[1].insert(hist[1].end(), row1.begin(), row1.end());
@@ -745,6 +748,39 @@ static void stage_programs_compile_to_source() {
         }
         for (uint32_t s = 0; s < 3; ++s) g.out(N(pool[pool.size() - 1 - s]), s);
         check_compiled_programs(g, 3, 64, {0, 64, 128, 900}, "compiled random graph");
+    }
+}
+
+// The five arithmetic primitives beside a BAKED literal (stagejit.cpp literal_worthy: +-0, +-1, +-0.5, +-2), on either side,
+// and between two signals, over the edge operands of tests/prim_pairs.py (zeros, subnormals, FLT_MIN, the negative integers,
+// 2^24, 2^32, FLT_MAX, infinities, NaN): the generated source under g++ against the oracle, which tests/test_prim_pairs.py
+// shows equal to a float64 reference on exactly these operands.  One renderer per literal, every row a shape of its own, so
+// the constant is a literal in the source (asserted from the text) -- the forms in which jit_mod1 and the literal folds live.
+static void stage_literal_forms_over_edge_operands() {
+    const float mags[] = {0.0f, 1e-45f, 3e-39f, 1.1754942e-38f, 1.17549435e-38f, 1e-30f, 0.1f, 0.5f, 0.75f, 1.0f, 1.0000001f, 1.5f, 2.0f, 3.0f, 7.25f,
+                          16777216.0f, 16777217.0f, 4294967296.0f, 1e20f, 1e30f, 1.7014118e38f, 3.4028235e38f, INFINITY};
+    std::vector<float> H;
+    for (float m : mags) { H.push_back(m); H.push_back(-m); }
+    H.push_back(NAN);
+    CHECK(H.size() == 47);
+    const int kinds[5] = {FR_PRIM_SUM2, FR_PRIM_MULTIPLY, FR_PRIM_DIVIDE, FR_PRIM_MODULO, FR_PRIM_MINIMUM};
+    const float literals[8] = {0.0f, -0.0f, 1.0f, -1.0f, 0.5f, -0.5f, 2.0f, -2.0f};
+    const uint64_t T = H.size() * H.size();   // row 0 = repeat(H), row 1 = tile(H): every pair
+    for (float L : literals) {
+        Build b;
+        uint32_t row = 0;
+        for (int kind : kinds) {
+            b.out(N(b.op(kind, In(0), Cf(L))), row++);      // SL
+            b.out(N(b.op(kind, Cf(L), In(0))), row++);      // LS
+            b.out(N(b.op(kind, In(0), In(1))), row++);      // SS
+        }
+        char lit[32];
+        std::snprintf(lit, sizeof lit, "f32(0x%08xu)", f32_to_bits(L));
+        check_compiled_programs(b, row, T, {0}, "literal operand forms", [&](const StageJitPlan &sj) {
+            CHECK(sj.source.find(lit) != std::string::npos);                                   // baked, not a parameter
+            CHECK((sj.source.find("jit_mod1(v") != std::string::npos) == (L == 1.0f && !std::signbit(L)));
+            CHECK(sj.source.find("jit_min(v") != std::string::npos && sj.source.find("jit_mod(v") != std::string::npos);
+        }, &H);
     }
 }
 
@@ -1344,6 +1380,7 @@ int main(int argc, char **argv) {
         {"shared_root_without_delays_is_one_launch", shared_root_without_delays_is_one_launch},
         {"composite_instances_are_interned", composite_instances_are_interned},
         {"stage_programs_compile_to_source", stage_programs_compile_to_source},
+        {"stage_literal_forms_over_edge_operands", stage_literal_forms_over_edge_operands},
         {"incremental_lowering_equals_from_scratch", incremental_lowering_equals_from_scratch},
         {"bounded_signal_delays_are_staged", bounded_signal_delays_are_staged},
         {"value_ranges_are_sound", value_ranges_are_sound},

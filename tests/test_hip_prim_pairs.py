@@ -1,0 +1,201 @@
+"""The operand-pair matrix (tests/prim_pairs.py) on the device: op x operand form x evaluator against the float64 reference, bit
+for bit, every sample compared.  Each test asserts from fr_plan_json that the evaluator it names is the one that ran.
+
+Evaluators: pull_kernel (mode="pull": SS, SP / PS, CC), stage_kernel (mode="staged", FR_STAGE_JIT=0: SS, SP / PS, SL / LS), the
+hipRTC-compiled stage programs (FR_STAGE_JIT=force: SS, SP / PS, SL / LS; for the literal forms the generated source is read back
+through FR_JIT_DUMP to show that the constant was baked), the hipRTC-compiled voice leaves (SS, SL / LS, the fma form with
+FR_JIT_FMA on and off, Modulo(x, 1) in its fract and its general body) and the three block-streaming interpreters.
+
+What the leaf forms cannot carry as the design had it: a compiled voice has 32 to 8192 leaves (match.cpp), so P = 2 does not
+exist, and P IDENTICAL leaves are one interned node; every leaf is the operation times its own power of two (prim_pairs.py).
+A constant that is the same within a voice is a literal of that voice's kernel, so SP / PS (a constant as a PARAMETER of a
+leaf) would need constants that differ within a voice, whose sum no longer shows one leaf's bits: not built."""
+import numpy as np
+import pytest
+
+import prim_pairs as pp
+from libfriendship_amd import synth
+from libfriendship_amd.capi import Renderer
+
+pytestmark = pytest.mark.gpu
+
+SEMANTICS, EVALUATORS, CC_FRAMES = pp.SEMANTICS, pp.EVALUATORS, pp.CC_FRAMES
+render, semantics_of = pp.render, pp.semantics_of
+
+
+@pytest.fixture(scope="module")
+def reference_rows():
+    return pp.reference_rows()
+
+
+@pytest.mark.parametrize("op", pp.OPS)
+@pytest.mark.parametrize("ev", list(EVALUATORS))
+def test_two_signals(hip_lib, reference_rows, ev, op):
+    """SS: op(In0, In1) on H x H and the 4096 random bit patterns, 6305 frames."""
+    a, b = pp.both_blocks()
+    tree, _ = pp.ss_graph([op])
+    for semantics in semantics_of(op):
+        got = render(hip_lib, tree, 1, [a, b], ev, semantics)
+        msg = pp.first_diff(op, f"SS {semantics} on {ev}", a, b, got[0], reference_rows[semantics][pp.OPS.index(op)])
+        assert not msg, msg
+
+
+@pytest.mark.parametrize("op", pp.OPS)
+@pytest.mark.parametrize("ev", list(EVALUATORS))
+def test_signal_and_parameter(hip_lib, ev, op):
+    """SP / PS: op(In0, C(H[j])) and its mirror, a row per j (94 rows): the constants differ from row to row, so generated code
+    gets them as parameters.  The input is H and 512 random patterns."""
+    x = pp.signal_row()
+    tree, meta = pp.sp_graph([op])
+    for semantics in semantics_of(op):
+        got = render(hip_lib, tree, len(meta), [x], ev, semantics)
+        exp, A, B = pp.one_signal_expected(meta, x, semantics)
+        msg = pp.first_diff(op, f"SP, PS {semantics} on {ev}", A, B, got, exp)
+        assert not msg, msg
+
+
+@pytest.mark.parametrize("semantics", SEMANTICS)
+@pytest.mark.parametrize("literal", pp.STAGE_LITERALS, ids=[repr(float(v)) for v in pp.STAGE_LITERALS])
+@pytest.mark.parametrize("ev", ["stage_kernel", "stage_jit"])
+def test_signal_and_literal(hip_lib, ev, literal, semantics, tmp_path, monkeypatch):
+    """SL / LS: one renderer per literal, ten rows (five ops, two sides), every row a shape of its own and every constant of
+    the graph the same, so a compiled stage program bakes it: the dumped source must hold the literal's f32(0x...u) spelling,
+    and jit_mod1( exactly where the literal is +1 (Modulo(x, 1)).  The interpreter does not tell literals apart; it runs the
+    same rows."""
+    if ev == "stage_jit":
+        monkeypatch.setenv("FR_JIT_DUMP", str(tmp_path))
+    x = pp.signal_row()
+    tree, meta = pp.sl_graph(literal)
+    got = render(hip_lib, tree, len(meta), [x], ev, semantics)
+    if ev == "stage_jit":
+        dumped = sorted(tmp_path.glob("jit_stage_*.hip"))
+        assert dumped, "no generated stage source was dumped: the programs of this case were compiled before, by another test"
+        text = "".join(p.read_text() for p in dumped)
+        assert f"f32({int(np.float32(literal).view(np.uint32)):#010x}u)" in text, literal
+        assert ("jit_mod1(v" in text) == (np.float32(literal).view(np.uint32) == 0x3F800000), literal
+        assert "jit_min(v" in text and "jit_mod(v" in text
+    exp, A, B = pp.one_signal_expected(meta, x, semantics)
+    for r, (op, form, _) in enumerate(meta):
+        msg = pp.first_diff(op, f"{form} {literal!r} {semantics} on {ev}", A[r], B[r], got[r], exp[r])
+        assert not msg, msg
+
+
+@pytest.mark.parametrize("op", pp.OPS)
+def test_both_constants_on_the_device_build(hip_lib, op):
+    """CC: op(C(a), C(b)) for the 2209 pairs of H x H, a node and an output row per pair, folded by the device library's own
+    build of the constant folder; what is left are constant rows for pull_kernel."""
+    a, b = pp.pair_block()
+    tree = pp.cc_graph(op, a, b)
+    for semantics in semantics_of(op):
+        with Renderer(hip_lib, mode="pull", semantics=semantics) as r:
+            synth.install(r, tree)
+            got = r.fill_buffer(len(a), 0, CC_FRAMES, [np.zeros(CC_FRAMES, np.float32)])
+            plan = r.plan()
+        assert plan["pull_rows"] == len(a) and not plan["stage_launches"] and not plan["banks"], plan["pull_rows"]
+        exp = pp.reference(op, a, b, semantics)
+        msg = pp.first_diff(op, f"CC {semantics} (device build)", a[:, None], b[:, None], got, np.repeat(exp[:, None], CC_FRAMES, axis=1))
+        assert not msg, msg
+
+
+# ---- generated voice leaves (leafjit.cpp: jit_bank) ------------------------------------------------------------------------------
+@pytest.mark.parametrize("op,P", [(op, 32) for op in pp.OPS] + [("Divide", 64)])
+def test_leaves_two_signals(hip_lib, op, P):
+    """SS: one voice of P leaves 2^-(k + 1) * op(In0, In1) on both blocks; the one varying parameter is the scale."""
+    a, b = pp.both_blocks()
+    tree = pp.leaf_graph(op, "SS", [0.0], P)
+    for semantics in semantics_of(op):
+        got = pp.render_leaves(hip_lib, tree, 1, [a, b], P, 1, semantics=semantics)
+        exp, A, B = pp.leaf_expected(op, "SS", [0.0], P, a, b, semantics)
+        msg = pp.first_diff(op, f"leaves SS P={P} {semantics}", A, B, got, exp)
+        assert not msg, msg
+
+
+@pytest.mark.parametrize("form", ["SL", "LS"])
+@pytest.mark.parametrize("op", pp.OPS)
+def test_leaves_signal_and_literal(hip_lib, op, form):
+    """SL / LS: a voice (and a kernel: 11 hipRTC compiles) per literal of {+-0, +-1, 0.5, 2, -2, 4, inf, NaN, 1e-45}; the
+    constant is the same in every leaf, so it is baked and the scale stays the only parameter (leaf_params == 1).  The input
+    is H and 512 random patterns; for Modulo(x, 1) see test_leaves_modulo_by_one_both_bodies."""
+    x = pp.signal_row()
+    tree = pp.leaf_graph(op, form, pp.LEAF_LITERALS, 32)
+    for semantics in semantics_of(op):
+        got = pp.render_leaves(hip_lib, tree, len(pp.LEAF_LITERALS), [x], 32, 1, semantics=semantics)
+        exp, A, B = pp.leaf_expected(op, form, pp.LEAF_LITERALS, 32, x, None, semantics)
+        msg = pp.first_diff(op, f"leaves {form} {semantics}", A, B, got, exp)
+        assert not msg, msg
+
+
+@pytest.mark.parametrize("fma", ["1", "0"])
+def test_leaves_fma_fold(hip_lib, fma):
+    """Sum2(x, Multiply(L, y)) with L = 2 and -4 (an exact product: folded into one fma unless FR_JIT_FMA=0) on both blocks."""
+    a, b = pp.both_blocks()
+    got = pp.render_leaves(hip_lib, pp.leaf_graph("Sum2", "FMA", pp.FMA_LITERALS, 32), 2, [a, b], 32, 1, options={"FR_JIT_FMA": fma})
+    exp, A, B = pp.leaf_expected("Sum2", "FMA", pp.FMA_LITERALS, 32, a, b)
+    msg = pp.first_diff("Sum2", f"leaves Sum2(x, Multiply(L, y)) FR_JIT_FMA={fma}", A, B, got, exp)
+    assert not msg, msg
+
+
+def test_leaves_modulo_by_one_both_bodies(hip_lib):
+    """Modulo(x, 1): a call whose inputs all lie in [+0, 2^32] (the fract body where the host proved it exact) and a call with
+    H and random patterns (the general body), same renderer."""
+    inside = np.concatenate([pp.H[(pp.H.view(np.uint32) <= 0x4F800000)], np.abs(pp.random_block()[0][:512])])
+    inside = inside[inside.view(np.uint32) <= 0x4F800000]
+    assert len(inside) > 300 and 4294967296.0 in inside and 0.0 in inside
+    tree = pp.leaf_graph("Modulo", "SL", [1.0], 32)
+    for what, x in (("inputs in [+0, 2^32]", inside), ("hostile inputs", pp.signal_row())):
+        got = pp.render_leaves(hip_lib, tree, 1, [x], 32, 1)
+        exp, A, B = pp.leaf_expected("Modulo", "SL", [1.0], 32, x)
+        msg = pp.first_diff("Modulo", f"leaves SL 1.0, {what}", A, B, got, exp)
+        assert not msg, msg
+
+
+# ---- the block-streaming interpreters --------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def stream_voices(oracle_lib):
+    """The oracle's rendering of the six streaming voices on the time ramp of both blocks (used for the voice only)."""
+    N = len(pp.both_blocks()[0])
+    with Renderer(oracle_lib) as o:
+        synth.install(o, pp.voices_tree(6, 128))
+        v = o.fill_buffer(6, 0, N, [synth.time_ramp(0, N)])
+    v.setflags(write=False)
+    return v
+
+
+@pytest.mark.parametrize("bus", [False, True], ids=["voice_programs", "bus_programs"])
+def test_stream_control_rows(hip_lib, stream_voices, bus):
+    """bank_stream_in_kernel: row v = Sum2(Multiply(voice_v, In1), op_v(In2, In3)) -- the Sum2 form is served -- with In1 a row
+    of +0 and the 6305 pairs in In2, In3, fed in blocks of 64 frames; bus: rows summed in pairs (its bus programs).  The gate
+    makes the voice +-0, so every result survives the sum except a -0 beside a +0 voice term, which the expectation (float64
+    reference on the oracle's voice) gives as +0 too."""
+    import stream_input_cases as I
+    a, b = pp.both_blocks()
+    ops = pp.OPS + ("Minimum",) if bus else pp.OPS
+    n = len(ops) // 2 if bus else len(ops)
+    rows = [synth.time_ramp(0, len(a)), np.zeros(len(a), np.float32), a, b]
+    got, plan = pp.stream_blocks(hip_lib, pp.stream_graph(ops, bus=bus), n, rows, I.STREAM_OPTIONS)
+    s = plan["stream"]
+    assert s["servable"] and s["kernel"] == "bank_stream_in_kernel" and s["input_slots"] == [0, 1, 2, 3], s
+    assert s["bus_programs"] == (3 if bus else 0) and s["programs_per_voice"] == ([0] * 6 if bus else [1] * 5), s
+    exp = pp.stream_expected(stream_voices[:len(ops)], rows[1], a, b, ops, bus=bus)
+    msg = pp.first_diff("every op", f"stream control rows bus={bus}", a, b, got, exp)
+    assert not msg, msg
+
+
+@pytest.mark.parametrize("bus", [False, True], ids=["bank_stream_prog_kernel", "bank_stream_bus_kernel"])
+@pytest.mark.parametrize("op", pp.OPS)
+def test_stream_slot_0_programs(hip_lib, oracle_lib, op, bus):
+    """The two interpreters without control rows read slot 0 only, so the signal is the voices' own time row: row v =
+    Sum2(Multiply(voice_v, C(+0)), op(In0, C(H[v]))), 46 voices of 128 partials; bus: summed in pairs.  The row is a ramp, then
+    H and 512 random patterns; the voice comes from the oracle on the same row."""
+    import stream_input_cases as I
+    consts = pp.H[:46]
+    x = np.concatenate([synth.time_ramp(0, 81), pp.signal_row()])
+    with Renderer(oracle_lib) as o:
+        synth.install(o, pp.voices_tree(46, 128))
+        voice = o.fill_buffer(46, 0, len(x), [x])
+    got, plan = pp.stream_blocks(hip_lib, pp.stream_slot0_graph(op, consts, bus=bus), 23 if bus else 46, [x], I.STREAM_OPTIONS)
+    s = plan["stream"]
+    assert s["servable"] and s["input_slots"] == [0] and s["kernel"] == ("bank_stream_bus_kernel" if bus else "bank_stream_prog_kernel"), s
+    exp = pp.stream_slot0_expected(voice, op, consts, x, bus=bus)
+    msg = pp.first_diff(op, f"stream slot 0 bus={bus}", x, 0, got, exp)
+    assert not msg, msg
