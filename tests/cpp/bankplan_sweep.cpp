@@ -11,6 +11,9 @@
 //   short_kernel short_pairs short_wgs short_nw bank_f bank_nw multi leaf_variant jit_chunks jit_chunk_target
 // (kind: 0 balanced, 1 compiled, 2 general).
 //
+// `--tracks`: the same sweep over the groups that stream tracks only (compiled voices with `tracks` set), in the same
+// format: the keys tests/track_variants.py must cover (tests/test_track_variants.py).
+//
 // Build: g++ -std=c++17 -O2 -I/opt/rocm/include -D__HIP_PLATFORM_AMD__ -o bankplan_sweep bankplan_sweep.cpp
 #include <cstdio>
 #include <cstring>
@@ -80,6 +83,7 @@ int query() {
 
 int main(int argc, char **argv) {
     if (argc > 1 && std::strcmp(argv[1], "--query") == 0) return query();
+    const bool tracks_only = argc > 1 && std::strcmp(argv[1], "--tracks") == 0;
     // voices 1 .. 4096 and frames 1 .. 8192: every threshold of the rule (64-frame tiles, 320 / 1000 pairs, 1024 / 2048 / 4096
     // workgroups, 512 / 1024 frames, the 2-frame small call) lies between two neighbours of these lists
     const std::vector<uint32_t> voice_counts = {1, 2, 3, 4, 5, 7, 8, 12, 16, 31, 64, 100, 128, 255, 256, 257, 400, 512, 700, 1000, 1024, 1025, 2000, 4096};
@@ -90,6 +94,7 @@ int main(int argc, char **argv) {
     uint64_t points = 0;
     auto note = [&](Kind k, const char *kind, uint32_t log2_p, uint32_t voices, uint32_t leaves, bool tracks, bool jm, uint64_t T, bool hp, bool rf,
                     const BankTuning &tu) {
+        if (tracks_only && !tracks) return;
         ++points;
         const BankPlan p = launch(k, log2_p, voices, leaves, tracks, jm, T, hp, rf, tu);
         if (!seen.insert(pack(p, log2_p, tu.leaf_variant, rf)).second) return;
