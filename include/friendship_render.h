@@ -272,7 +272,8 @@ fr_status fr_fill_buffer_device(fr_renderer *r, float *d_out, uint32_t n_slots, 
  * as long as every Delay of a computed value reaches at least 64 frames back, no program mixes two voices of the same block
  * (with FR_STREAM_BUS=1 that too is served: voices with their own gain, envelope or taps summed to a mono or stereo bus,
  * taps and echoes behind the bus), and the programs read input slot 0 at the current frame only (no delayed reads of the input row, no signal-amount
- * delays); fr_last_error names what a refused plan has.  For such a plan the first block, and every block that does not
+ * delays); with FR_STREAM_BANKS=1 the voices may be of 2 to 8 banks -- several partial counts, voices to rows next to voices
+ * behind programs; fr_last_error names what a refused plan has.  For such a plan the first block, and every block that does not
  * continue the previous one, first brings the delay lines up to `idx` the way fr_fill_buffer does after a seek there
  * (the look-back window, or a loop's replay from frame 0, every input before `idx` reading 0.0) and then (re)starts the
  * resident launch: a seek costs what it costs fr_fill_buffer, continuing blocks only ring the doorbell.

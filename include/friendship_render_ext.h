@@ -64,6 +64,18 @@ extern "C" {
  * ([0] for a plan that reads nothing else); "kernel" is "bank_stream_in_kernel" exactly when a program reads another slot.
  * Still refused: more than 8 distinct slots, delayed reads of an input row (a stream keeps no input history), voices whose
  * time is not slot 0, and everything else of the lists above.
+ *
+ * FR_STREAM_BANKS = 0 / 1 (default 0; read strictly from the environment too; does nothing unless FR_STREAM_PROGRAMS=1):
+ * block streaming also serves plans of 2 to 8 voice banks -- a chord whose notes have 1024, 256 and 128 partials, dry voices
+ * that go straight to their rows next to enveloped voices on a bus -- with or without programs behind them.  A fifth
+ * resident kernel takes the bank table as a launch argument; every bank gets its own chunk size, the largest chunk halved
+ * first, so that the partials per workgroup even out.  It composes with FR_STREAM_BUS and FR_STREAM_INPUTS, which such a
+ * patch needs as a one-bank patch does.  With 0 nothing changes: the same plans are served and refused, with the same
+ * reasons, by the same kernels.  "stream" gains "banks" ({voices, partials, chunks, to_ring} per bank, in plan order),
+ * "workgroups" and "max_workgroups"; for several banks "voices" is their total, "chunks" the largest per-voice count,
+ * programs_per_voice runs over the voices bank by bank, and "kernel" is "bank_stream_banks_kernel" exactly when the plan has
+ * more than one bank.  Still refused: more than 8 banks, more voices in total than workgroups, and for every bank what is
+ * refused for one: general, compiled and track voices, voices under 128 partials, voices whose time is not slot 0.
  */
 typedef struct fr_option {
     const char *name;              /* e.g. "FR_BANK_SHORT" */

@@ -190,7 +190,7 @@ static std::string stage_variant(const StageLaunchNote &n, const Plan &p) {
     return k;
 }
 
-constexpr size_t N_OPTIONS = 33;         // per-renderer options (friendship_render_ext.h; the table below fr_renderer)
+constexpr size_t N_OPTIONS = 34;         // per-renderer options (friendship_render_ext.h; the table below fr_renderer)
 
 struct TimerClass {
     double ms = 0;
@@ -242,6 +242,10 @@ __attribute__((weak)) hipError_t launch_bank_stream_bus(const BankArgs &, const 
     return hipErrorNotSupported;
 }
 __attribute__((weak)) hipError_t launch_bank_stream_in(const BankArgs &, const StreamProgArgs &, uint32_t, BankStreamInCtl *, BankStreamInDev *, uint32_t, hipStream_t) {
+    return hipErrorNotSupported;
+}
+__attribute__((weak)) hipError_t launch_bank_stream_banks(const StreamBanksArgs &, const BankArgs &, const StreamProgArgs &, uint32_t, BankStreamInCtl *, BankStreamInDev *, uint32_t,
+                                                          hipStream_t) {
     return hipErrorNotSupported;
 }
 __attribute__((weak)) hipError_t launch_track_window(const TrackWindowArgs &a, hipStream_t) {
@@ -544,6 +548,7 @@ struct fr_renderer {
     bool stream_programs = false;        // the option
     bool stream_bus = false;             // FR_STREAM_BUS: mix-bus programs run after the block's last voice (bank_stream_bus_kernel)
     bool stream_inputs = false;          // FR_STREAM_INPUTS: programs read control rows, up to STREAM_MAX_INPUTS slots (bank_stream_in_kernel)
+    bool stream_banks = false;           // FR_STREAM_BANKS: 2..STREAM_MAX_BANKS bank launches in one resident launch (bank_stream_banks_kernel)
     bool stream_prog = false;            // the open stream is of that kind
     bool stream_in = false;              // ... and its doorbell is the rows of stream_plan.input_slots (BankStreamInCtl / BankStreamInDev)
     StreamRows stream_rows;              // the input store's rules for the open stream's rows, without the samples (streamrows.hpp)
@@ -564,6 +569,7 @@ struct fr_renderer {
         env.track_history = tail_on();
         env.bus = stream_bus;
         env.inputs = stream_inputs;
+        env.banks = stream_banks;
         return plan_stream(plan.sp, banks, env);
     }
     // Rings the stop and waits for the resident launch to end.  `clean`: the launch was answering when the stop was rung
@@ -2143,12 +2149,17 @@ void fr_renderer::begin_program_stream(uint32_t n_slots) {
             if ((in.op == S_READ || in.op == S_STORE) && in.buf >= sp.n_rings) throw Error(FR_ERR_DEVICE, "internal: a streamed program reads a ring the plan does not have");
         }
     }
-    const BankLaunch &grp = plan.banks[0].grp;
-    for (uint32_t row : grp.rows)
-        if (row >= (grp.to_ring ? sp.n_rings : n_slots)) throw Error(FR_ERR_DEVICE, "internal: a streamed voice's row out of bounds");
+    if (s.banks.size() != plan.banks.size() || s.banks.size() > BANK_STREAM_BANKS) throw Error(FR_ERR_DEVICE, "internal: the stream's banks are not the plan's");
+    for (size_t i = 0; i < plan.banks.size(); ++i) {
+        const BankLaunch &grp = plan.banks[i].grp;
+        if (grp.rows.size() != s.banks[i].voices) throw Error(FR_ERR_DEVICE, "internal: the stream's banks are not the plan's");
+        for (uint32_t row : grp.rows)
+            if (row >= (grp.to_ring ? sp.n_rings : n_slots)) throw Error(FR_ERR_DEVICE, "internal: a streamed voice's row out of bounds");
+    }
     // programs that read control rows (FR_STREAM_INPUTS): the stream's own copy of their instructions, S_INPUT's operand the
     // streamed row (the position of its slot in input_slots) instead of the plan's input index
-    const bool rows_in = s.input_slots.size() > 1;
+    // (several banks: bank_stream_banks_kernel, whose control words and S_INPUT are those of the kernel with control rows)
+    const bool rows_in = s.input_slots.size() > 1 || s.banks.size() > 1;
     std::vector<StageInstr> instrs;
     if (rows_in) {
         if (s.input_slots.size() > BANK_STREAM_ROWS) throw Error(FR_ERR_DEVICE, "internal: more streamed rows than the kernel takes");
@@ -2224,7 +2235,10 @@ void fr_renderer::seek_program_stream(uint64_t idx) {
     ring_table.valid = false;
     const BankStage &bs = plan.banks[0];
     const StreamPlan &s = stream_plan;
-    if ((sp.uses_rings() && (ring_cap < sp.lmax + STREAM_BLOCK || (size_t)sp.n_rings * ring_cap * sizeof(float) > d_rings.bytes)) || s.voices != bs.grp.rows.size())
+    size_t plan_voices = 0;
+    for (const BankStage &b : plan.banks) plan_voices += b.grp.rows.size();
+    if ((sp.uses_rings() && (ring_cap < sp.lmax + STREAM_BLOCK || (size_t)sp.n_rings * ring_cap * sizeof(float) > d_rings.bytes)) || s.voices != plan_voices ||
+        s.banks.size() != plan.banks.size())
         throw Error(FR_ERR_DEVICE, "internal: the rings do not hold a streamed block's look-back");
     BankArgs a{};
     a.params = bs.d_params.as<float2>();
@@ -2261,7 +2275,36 @@ void fr_renderer::seek_program_stream(uint64_t idx) {
     HIP_CHECK(hipMemsetAsync(d_stream_dev.p, 0, stream_in ? sizeof(BankStreamInDev) : sizeof(BankStreamDev), stream));
     // a plan whose programs read control rows (FR_STREAM_INPUTS): the kernel with a doorbell of rows; a plan with bus programs
     // (FR_STREAM_BUS): the kernel whose last arriver of a block runs them; every other plan: as before
-    if (stream_in) {
+    if (s.banks.size() > 1) {
+        // voices of several banks (FR_STREAM_BANKS): the bank table travels in the kernel arguments; chunk sums and tickets
+        // are laid out by global voice
+        StreamBanksArgs t{};
+        t.n_banks = (uint32_t)s.banks.size();
+        for (size_t i = 0; i < s.banks.size(); ++i) {
+            const BankStage &b = plan.banks[i];
+            const StreamBank &sb = s.banks[i];
+            if (b.grp.rows.size() != sb.voices || b.grp.log2_p != sb.log2_p) throw Error(FR_ERR_DEVICE, "internal: the stream's banks are not the plan's");
+            t.bank[i].params = b.d_params.as<float2>();
+            t.bank[i].rows = b.d_rows.as<uint32_t>();
+            t.bank[i].first_wg = sb.first_wg;
+            t.bank[i].first_voice = sb.first_voice;
+            t.bank[i].n_voices = sb.voices;
+            t.bank[i].log2_p = sb.log2_p;
+            t.bank[i].chunk_log2 = sb.chunk_log2;
+            t.bank[i].fast_ok = b.grp.fast_ok ? 1u : 0u;
+            t.bank[i].to_ring = b.grp.to_ring ? 1u : 0u;
+        }
+        a.params = nullptr;
+        a.rows = nullptr;
+        a.chunk_log2 = 0;
+        a.log2_p = 0;
+        a.fast_ok = 0;
+        p.bank_to_ring = 0;
+        p.instrs = d_stream_instrs.as<StageInstr>();
+        HIP_CHECK(launch_bank_stream_banks(t, a, p, (uint32_t)s.input_slots.size(), h_stream_ctl.as_dev<BankStreamInCtl>(), d_stream_dev.as<BankStreamInDev>(), stream_idle_ms,
+                                           stream));
+        stream_kernel = "bank_stream_banks_kernel";
+    } else if (stream_in) {
         p.instrs = d_stream_instrs.as<StageInstr>();
         HIP_CHECK(launch_bank_stream_in(a, p, (uint32_t)s.input_slots.size(), h_stream_ctl.as_dev<BankStreamInCtl>(), d_stream_dev.as<BankStreamInDev>(), stream_idle_ms, stream));
         stream_kernel = "bank_stream_in_kernel";
@@ -2335,6 +2378,7 @@ int64_t env_strict_ring_keep(const char *e);
 int64_t env_strict_stream_programs(const char *e);
 int64_t env_strict_stream_bus(const char *e);
 int64_t env_strict_stream_inputs(const char *e);
+int64_t env_strict_stream_banks(const char *e);
 bool parse_option(const Knob &k, const char *s, int64_t &v);
 
 const Knob kKnobs[] = {
@@ -2413,6 +2457,10 @@ const Knob kKnobs[] = {
     // StreamEnv::inputs; fr_stream_block_rows; fr_plan_json: stream.input_slots).  Inert without FR_STREAM_PROGRAMS.  Strict and
     // listed once set.
     {"FR_STREAM_INPUTS", 0, 0, 1, 0, nullptr, 0, env_strict_stream_inputs, [](fr_renderer &r, int64_t v, bool) { r.stream_inputs = v != 0; }, LISTED_WHEN_SET},
+    // Voices of several banks in block streaming: 2..STREAM_MAX_BANKS bank launches -- several partial counts, voices to rows
+    // next to voices behind programs -- in one resident launch (streamplan.hpp StreamEnv::banks; fr_plan_json: stream.banks).
+    // Inert without FR_STREAM_PROGRAMS.  Strict and listed once set.
+    {"FR_STREAM_BANKS", 0, 0, 1, 0, nullptr, 0, env_strict_stream_banks, [](fr_renderer &r, int64_t v, bool) { r.stream_banks = v != 0; }, LISTED_WHEN_SET},
 };
 static_assert(sizeof kKnobs / sizeof kKnobs[0] == N_OPTIONS, "N_OPTIONS counts the rows of kKnobs");
 
@@ -2427,6 +2475,7 @@ int64_t env_strict_ring_keep(const char *e) { return env_strict("FR_RING_KEEP", 
 int64_t env_strict_stream_programs(const char *e) { return env_strict("FR_STREAM_PROGRAMS", e); }
 int64_t env_strict_stream_bus(const char *e) { return env_strict("FR_STREAM_BUS", e); }
 int64_t env_strict_stream_inputs(const char *e) { return env_strict("FR_STREAM_INPUTS", e); }
+int64_t env_strict_stream_banks(const char *e) { return env_strict("FR_STREAM_BANKS", e); }
 
 bool parse_option(const Knob &k, const char *s, int64_t &v) {
     if (k.word && std::strcmp(s, k.word) == 0) {
@@ -2802,7 +2851,8 @@ fr_status fr_stream_begin(fr_renderer *r, uint32_t n_slots) {
         r->order_after_previous(r->stream);
         r->ensure_plan(n_slots, r->stream);
         const StagedPlan &sp = r->plan.sp;
-        if (r->stream_programs && (!sp.progs.empty() || sp.uses_rings())) {
+        // (FR_STREAM_BANKS: a plan of several banks takes this path even when it has no programs and no rings)
+        if (r->stream_programs && (!sp.progs.empty() || sp.uses_rings() || (r->stream_banks && r->plan.banks.size() > 1))) {
             r->begin_program_stream(n_slots);
             return;
         }
@@ -3078,7 +3128,20 @@ const char *fr_plan_json(fr_renderer *r) {
             r->plan_json_cache += std::string(",\"stream\":{\"servable\":") + (s.servable ? "true" : "false") + ",\"reason\":\"" + why +
                                   "\",\"voices\":" + std::to_string(s.voices) + ",\"chunks\":" + std::to_string(s.chunks) + ",\"programs_per_voice\":[" + per +
                                   "],\"bus_programs\":" + std::to_string(s.bus_programs()) + ",\"min_ring_delay\":" + std::to_string(s.min_ring_delay) + ",\"rings\":" + std::to_string(r->plan.sp.n_rings) +
-                                  ",\"input_slots\":[" + ins + "],\"kernel\":\"" + (s.servable && s.input_slots.size() > 1 ? "bank_stream_in_kernel" : std::strcmp(r->stream_kernel, "bank_stream_in_kernel") ? r->stream_kernel : "") + "\"}";
+                                  ",\"input_slots\":[" + ins + "]";
+            // (the kernel a servable plan will get where the plan decides it; else the last resident launch's, unless that was one of those)
+            const bool last_stands = std::strcmp(r->stream_kernel, "bank_stream_in_kernel") && std::strcmp(r->stream_kernel, "bank_stream_banks_kernel");
+            const char *kernel = s.servable && s.banks.size() > 1 ? "bank_stream_banks_kernel"
+                                 : s.servable && s.input_slots.size() > 1 ? "bank_stream_in_kernel" : last_stands ? r->stream_kernel : "";
+            if (r->stream_banks) {                               // FR_STREAM_BANKS: the banks of the launch, in plan order
+                std::string bl;
+                for (const StreamBank &b : s.banks)
+                    bl += std::string(bl.empty() ? "" : ",") + "{\"voices\":" + std::to_string(b.voices) + ",\"partials\":" + std::to_string(1u << b.log2_p) +
+                          ",\"chunks\":" + std::to_string(1u << (b.log2_p - b.chunk_log2)) + ",\"to_ring\":" + (b.to_ring ? "true" : "false") + "}";
+                r->plan_json_cache += ",\"banks\":[" + bl + "],\"workgroups\":" + std::to_string(s.workgroups()) +
+                                      ",\"max_workgroups\":" + std::to_string(stream_max_wgs((uint32_t)std::max(r->device_cus, 0)));
+            }
+            r->plan_json_cache += std::string(",\"kernel\":\"") + kernel + "\"}";
         }
         r->plan_json_cache += ",\"exchange_stats\":{\"calls\":" + std::to_string(r->exchange_calls) + ",\"tiles\":" + std::to_string(r->exchange_tiles) +
                               ",\"bytes_sent\":" + std::to_string(r->exchange_bytes) + "},\"bank_launches\":[";

@@ -2203,6 +2203,222 @@ hipError_t launch_bank_stream_in(const BankArgs &a, const StreamProgArgs &p, uin
 }
 
 // ---------------------------------------------------------------------------------------------------
+// Block streaming of plans with several banks (FR_STREAM_BANKS, streamplan.hpp, kernels.hpp StreamBanksArgs): what
+// bank_stream_in_kernel does -- a doorbell of n_rows rows, per-voice programs in the wave that finishes a voice, the bus
+// segment in the block's last arriver -- for voices of 2..8 banks, each with its own partial count, chunk size, fast path and
+// destination kind.  What differs is how a workgroup finds its work: the bank table is a launch argument, the workgroup
+// compares its index with the banks' first workgroups (uniform, once, before the block loop) and keeps that bank's fields in
+// scalar registers.  Voices are numbered globally: chunk sums, tickets, voice_first and the voices_done count all go by that
+// number.  Every hand-over is bank_stream_in_kernel's: relaxed atomics, vmcnt(0) before each ticket, between programs and
+// before the done tag; no acquire or release, no new polling loop, and no workgroup waits for another one's result.  The
+// kernel has its own text and uses the control-row kernel's interpreter and wait as they are: the four older streaming
+// kernels' code does not change.
+// ---------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(1024) bank_stream_banks_kernel(StreamBanksArgs t, BankArgs a, StreamProgArgs p, uint32_t n_rows, BankStreamInCtl *ctl,
+                                                                 BankStreamInDev *dev, uint32_t idle_ms) {
+    constexpr int NW = 16;
+    __shared__ float sm[NW][64];
+    __shared__ float regs[STAGE_REGS][64];                   // the interpreter's registers: [register][lane] of wave 0
+    __shared__ unsigned long long zshared;
+    __shared__ uint32_t s_seq, s_T;
+    // ---- this workgroup's bank: the last one whose first workgroup is not after it (the table is in ascending order) ----
+    StreamBanksArgs::Bank bk = t.bank[0];
+    static_for<1, (int)BANK_STREAM_BANKS>([&](auto j) {
+        if ((uint32_t)j < t.n_banks && blockIdx.x >= t.bank[j].first_wg) bk = t.bank[j];
+    });
+    const uint32_t clog = bk.log2_p - bk.chunk_log2, nchunks = 1u << clog;
+    const uint32_t local = blockIdx.x - bk.first_wg;         // (the grid is exactly the sum of the banks' n_voices * nchunks workgroups)
+    const uint32_t chunk = local & (nchunks - 1u);
+    const uint32_t bank_voice = local >> clog;               // the voice inside its bank: its parameters and its destination
+    const uint32_t voice = bk.first_voice + bank_voice;      // the global voice: its chunk sums, ticket and programs
+    const uint32_t n_voices = a.n_voices;                    // of all banks
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t Pc = 1u << bk.chunk_log2;
+    const uint32_t Pw = Pc / NW, ngroups = Pw >> 3;
+    uint32_t levels = 0;
+    while ((1u << levels) < ngroups) ++levels;
+    const unsigned long long idle_ticks = (unsigned long long)idle_ms * 100000ull;
+    const float *mine = (const float *)(bk.params + ((size_t)bank_voice << bk.log2_p) + (size_t)chunk * Pc + (size_t)wave * Pw);
+    const size_t vstride = (size_t)n_voices * 64u;
+    const uint64_t ring_cap = p.ring_mask + 1;
+    uint64_t head = p.head;                                  // first frame of the block being rendered (the same in every workgroup)
+    uint32_t seen = 0;
+    if (blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store(&ctl->alive, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    for (;;) {
+        // ---- wait for the next block (bounded), as bank_stream_in_kernel ----
+        if (blockIdx.x == 0) {
+            if (wave == 0u) {
+                uint32_t T = 0, seq;
+                switch (n_rows) {
+                case 1: seq = stream_in_wait<1>(ctl, dev, lane, seen, idle_ticks, T); break;
+                case 2: seq = stream_in_wait<2>(ctl, dev, lane, seen, idle_ticks, T); break;
+                case 3: seq = stream_in_wait<3>(ctl, dev, lane, seen, idle_ticks, T); break;
+                case 4: seq = stream_in_wait<4>(ctl, dev, lane, seen, idle_ticks, T); break;
+                case 5: seq = stream_in_wait<5>(ctl, dev, lane, seen, idle_ticks, T); break;
+                case 6: seq = stream_in_wait<6>(ctl, dev, lane, seen, idle_ticks, T); break;
+                case 7: seq = stream_in_wait<7>(ctl, dev, lane, seen, idle_ticks, T); break;
+                default: seq = stream_in_wait<8>(ctl, dev, lane, seen, idle_ticks, T); break;
+                }
+                if (lane == 0u) {
+                    __hip_atomic_store(&dev->n_times, T, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                    __hip_atomic_store(&dev->seq, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    s_seq = seq;
+                    s_T = T;
+                }
+            }
+        } else if (threadIdx.x == 0) {
+            uint32_t seq = seen;
+            const unsigned long long wait_from = __builtin_amdgcn_s_memrealtime();
+            for (;;) {
+                seq = __hip_atomic_load(&dev->seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (seq != seen || __builtin_amdgcn_s_memrealtime() - wait_from > 2ull * idle_ticks + 10000000ull) break;
+                __builtin_amdgcn_s_sleep(4);
+            }
+            if (seq == seen) seq = BANK_STREAM_STOP;
+            s_seq = seq;
+            s_T = __hip_atomic_load(&dev->n_times, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        __syncthreads();
+        const uint32_t seq = s_seq, T = s_T;
+        if (seq == BANK_STREAM_STOP) break;
+        seen = seq;
+        {
+            // ---- one (voice, chunk) of one tile, as bank_stream_kernel, at this bank's chunk size ----
+            const bool live = lane < T;
+            ParamGroup first;
+            load_group(first, (const_f32_ptr)mine, 0);
+            const float t_in = live ? __hip_atomic_load(&dev->rows[0][lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0f;
+            const bool fast = bk.fast_ok && __all(t_in >= 0.0f && t_in <= 4294967296.0f);
+            const float tt[1] = {t_in};
+            float r_wave[1];
+            if (fast) bank_wave_sum<1, true, false>(mine, ngroups, levels, tt, r_wave, &first);
+            else bank_wave_sum<1, false, false>(mine, ngroups, levels, tt, r_wave, &first);
+            sm[wave][lane] = r_wave[0];
+            __syncthreads();
+            float r = 0.0f;
+            if (wave == 0u) {
+                float s[NW];
+                static_for<0, NW>([&](auto w) { s[w] = sm[w][lane]; });
+                static_for<0, NW / 2>([&](auto i) { s[i] = s[2 * i] + s[2 * i + 1]; });
+                static_for<0, NW / 4>([&](auto i) { s[i] = s[2 * i] + s[2 * i + 1]; });
+                static_for<0, NW / 8>([&](auto i) { s[i] = s[2 * i] + s[2 * i + 1]; });
+                static_for<0, NW / 16>([&](auto i) { s[i] = s[2 * i] + s[2 * i + 1]; });
+                r = s[0];
+                const unsigned long long z = __ballot(live && r == 0.0f);
+                if (lane == 0u) zshared = z;
+            }
+            __syncthreads();
+            const unsigned long long zm = zshared;
+            if (zm != 0ull) {
+                const bool ok = fast ? wave_leaves_all_negzero<true>(mine, ngroups, t_in, zm) : wave_leaves_all_negzero<false>(mine, ngroups, t_in, zm);
+                sm[wave][lane] = ok ? 1.0f : 0.0f;
+                __syncthreads();
+                if (wave == 0u && ((zm >> lane) & 1ull)) {
+                    bool all = true;
+                    static_for<0, NW>([&](auto w) { all = all && sm[w][lane] != 0.0f; });
+                    r = all ? -0.0f : 0.0f;
+                }
+            }
+            if (wave == 0u) {
+                bool finished_voice = nchunks == 1u;
+                float result = r;
+                if (nchunks > 1u) {
+                    // the chunk sums of all banks share one workspace, laid out by global voice
+                    float *slot = a.ws + (size_t)voice * 64u;
+                    __hip_atomic_store(slot + (size_t)chunk * vstride + lane, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                    uint32_t old = 0u;
+                    if (lane == 0u) old = __hip_atomic_fetch_add(a.tickets + (size_t)voice * TICKET_STRIDE, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    old = __builtin_amdgcn_readfirstlane(old);
+                    if (old == nchunks - 1u) {
+                        finished_voice = true;
+                        float c0 = 0.0f, c1 = 0.0f, c2 = 0.0f, c3 = 0.0f, c4 = 0.0f, c5 = 0.0f, c6 = 0.0f, c7 = 0.0f, c8 = 0.0f;
+                        for (uint32_t c = 0; c < nchunks; ++c) {
+                            float v = c == chunk ? r : __hip_atomic_load(slot + (size_t)c * vstride + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                            do {
+                                if (!(c & 1u)) { c0 = v; break; } v = c0 + v;
+                                if (!(c & 2u)) { c1 = v; break; } v = c1 + v;
+                                if (!(c & 4u)) { c2 = v; break; } v = c2 + v;
+                                if (!(c & 8u)) { c3 = v; break; } v = c3 + v;
+                                if (!(c & 16u)) { c4 = v; break; } v = c4 + v;
+                                if (!(c & 32u)) { c5 = v; break; } v = c5 + v;
+                                if (!(c & 64u)) { c6 = v; break; } v = c6 + v;
+                                if (!(c & 128u)) { c7 = v; break; } v = c7 + v;
+                                c8 = v;
+                            } while (0);
+                        }
+                        // (the ladder's top is this bank's: its voices have 1 << clog chunks)
+                        result = c8;
+                        result = clog == 7u ? c7 : result; result = clog == 6u ? c6 : result; result = clog == 5u ? c5 : result;
+                        result = clog == 4u ? c4 : result; result = clog == 3u ? c3 : result; result = clog == 2u ? c2 : result;
+                        result = clog == 1u ? c1 : result;
+                        if (lane == 0u) __hip_atomic_store(a.tickets + (size_t)voice * TICKET_STRIDE, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    }
+                }
+                if (finished_voice) {
+                    // ---- the voice's frames head + lane: to its ring or its row, as its bank says; then its programs, lane = frame ----
+                    const uint64_t frame = head + lane;
+                    const uint32_t dst = bk.rows[bank_voice];
+                    if (live) {
+                        if (bk.to_ring) __hip_atomic_store(p.rings + (size_t)dst * ring_cap + (frame & p.ring_mask), result, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        else __hip_atomic_store(a.out + (size_t)dst * 64u + lane, result, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                    }
+                    stream_in_run_programs(a, p, dev, regs, p.voice_first[voice], p.voice_first[voice + 1], frame, lane, live, t_in);
+                    // ring and row stores alike are acknowledged before the voice is counted in: the block's done tag then implies
+                    // that every ring store of the block has landed
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                    // the ticket goes to the whole wave: the last arriver of the block, whichever bank it is of, runs the bus programs
+                    uint32_t n = 0u;
+                    if (lane == 0u) n = __hip_atomic_fetch_add(&dev->voices_done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    n = __builtin_amdgcn_readfirstlane(n);
+                    if (n == n_voices - 1u) {
+                        // every voice's ring and row stores were acknowledged before its ticket, and this wave's loads are issued
+                        // after its own ticket came back
+                        stream_in_run_programs(a, p, dev, regs, p.voice_first[n_voices], p.voice_first[n_voices + 1], frame, lane, live, t_in);
+                        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // host rows and rings have landed before the done tag
+                        if (lane == 0u) {
+                            __hip_atomic_store(&dev->voices_done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                            __hip_atomic_store(&ctl->done, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                        }
+                    }
+                }
+            }
+        }
+        head += T;
+        __syncthreads();   // LDS is reused by the next block
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store(&ctl->alive, 0u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+hipError_t launch_bank_stream_banks(const StreamBanksArgs &t, const BankArgs &a, const StreamProgArgs &p, uint32_t n_rows, BankStreamInCtl *ctl_dev, BankStreamInDev *dev,
+                                    uint32_t idle_ms, hipStream_t s) {
+    if (t.n_banks == 0 || t.n_banks > BANK_STREAM_BANKS) return hipErrorInvalidValue;
+    // every bank as launch_bank_stream_in validates its one; the banks' workgroups and voices follow one another without a gap
+    uint64_t wgs = 0, voices = 0;
+    bool chunked = false, to_ring = false;
+    for (uint32_t i = 0; i < t.n_banks; ++i) {
+        const StreamBanksArgs::Bank &b = t.bank[i];
+        if (b.chunk_log2 < 7 || b.chunk_log2 > 13 || b.chunk_log2 > b.log2_p || b.log2_p - b.chunk_log2 > 8) return hipErrorInvalidValue;
+        if (b.n_voices == 0 || b.n_voices > BANK_STREAM_WGS || !b.params || !b.rows) return hipErrorInvalidValue;
+        if (b.first_wg != wgs || b.first_voice != voices) return hipErrorInvalidValue;
+        wgs += (uint64_t)b.n_voices << (b.log2_p - b.chunk_log2);
+        voices += b.n_voices;
+        if (wgs > BANK_STREAM_WGS) return hipErrorInvalidValue;   // all workgroups must be resident
+        chunked = chunked || b.chunk_log2 != b.log2_p;
+        to_ring = to_ring || b.to_ring != 0;
+    }
+    if (voices != a.n_voices) return hipErrorInvalidValue;
+    if (chunked && (!a.ws || !a.tickets)) return hipErrorInvalidValue;
+    if (a.leaf_variant != 1 || !a.out || !ctl_dev || !dev || !p.voice_first) return hipErrorInvalidValue;
+    if ((p.ring_mask & (p.ring_mask + 1)) != 0 || (p.n_rings && (!p.rings || p.ring_mask + 1 < 64u)) || (to_ring && !p.n_rings)) return hipErrorInvalidValue;
+    if (n_rows == 0 || n_rows > BANK_STREAM_ROWS) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(bank_stream_banks_kernel, dim3((uint32_t)wgs), dim3(1024), 0, s, t, a, p, n_rows, ctl_dev, dev, idle_ms ? idle_ms : BANK_STREAM_IDLE_MS);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------------
 // Partial-block exchange, one level of the voices' Sum2 trees (kernels.hpp ShardCombineArgs).  HBM-bound: 12 bytes per
 // frame of a row; rows are contiguous and lanes run over frames, so every access is a full 256-byte line per wave.
 __global__ void __launch_bounds__(256) shard_combine_kernel(ShardCombineArgs a) {

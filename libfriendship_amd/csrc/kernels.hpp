@@ -241,6 +241,27 @@ struct BankStreamInDev {      // device memory
 hipError_t launch_bank_stream_in(const BankArgs &a, const StreamProgArgs &p, uint32_t n_rows, BankStreamInCtl *ctl_dev, BankStreamInDev *dev,
                                  uint32_t idle_ms, hipStream_t s);
 
+// bank_stream_banks_kernel (FR_STREAM_BANKS): bank_stream_in_kernel's work for a plan of 2..BANK_STREAM_BANKS bank launches --
+// voices of several partial counts, voices that write rows next to voices that feed rings -- in ONE resident launch.  The bank
+// table is a by-value launch argument (kernarg, then SGPRs: nothing is uploaded); a workgroup finds its bank with at most
+// n_banks - 1 uniform compares of its index against first_wg, once, before the block loop, and takes voice, chunk and chunk
+// size from that bank's fields.  Voices are numbered globally (banks in table order, then voices in bank order): the chunk
+// sums meet at ws + voice * 64 + chunk * (V_total * 64), V_total * (largest chunk count) * 64 floats in all, one ticket per
+// global voice; StreamProgArgs::voice_first is indexed by the global voice and the block is done when V_total voices are.
+// BankArgs gives n_voices = V_total, out, ws and tickets; its params, rows, log2_p, chunk_log2 and fast_ok, and
+// StreamProgArgs::bank_to_ring, are not read (each bank has its own).
+constexpr uint32_t BANK_STREAM_BANKS = 8;
+struct StreamBanksArgs {
+    uint32_t n_banks;
+    struct Bank {
+        const float2 *params;      // [n_voices][1 << log2_p] {w, -4*amp}
+        const uint32_t *rows;      // [n_voices] destination of each voice: a ring (to_ring) or an output row
+        uint32_t first_wg, first_voice, n_voices, log2_p, chunk_log2, fast_ok, to_ring;
+    } bank[BANK_STREAM_BANKS];
+};
+hipError_t launch_bank_stream_banks(const StreamBanksArgs &t, const BankArgs &a, const StreamProgArgs &p, uint32_t n_rows, BankStreamInCtl *ctl_dev, BankStreamInDev *dev,
+                                    uint32_t idle_ms, hipStream_t s);
+
 // One step of the partial-block exchange (friendship_render.h FR_SHARD_PARTIALS): row i, window frame t:
 //   v = lo[i][t] + hi[i][t]         the Sum2 node one level up: left sub-tree + right sub-tree, one f32 add
 // stored to dst_ws[i][t] (steps before the last; may alias lo or hi), or -- the last step, dst_ws == null -- where the

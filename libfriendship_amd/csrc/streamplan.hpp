@@ -15,6 +15,10 @@
 // With FR_STREAM_INPUTS=1 (StreamEnv::inputs) a program may read, at the current frame, input slots other than 0 -- control
 // rows: a gain, a gate, a fader -- up to STREAM_MAX_INPUTS distinct slots, slot 0 included.  The block then brings one row per
 // slot of StreamPlan::input_slots, in that order (kernels.hip bank_stream_in_kernel; streamrows.hpp keeps the slots' books).
+// With FR_STREAM_BANKS=1 (StreamEnv::banks) a plan with 2..STREAM_MAX_BANKS bank launches -- voices of several sizes, voices
+// that write rows next to voices that feed programs -- is one resident launch too (kernels.hip bank_stream_banks_kernel).
+// Voices are numbered GLOBALLY, banks in plan order, then voices in bank order: everything below that says "voice" means that
+// number.  Each bank has its own chunk size (deal_stream_chunks).
 #pragma once
 
 #include <algorithm>
@@ -30,6 +34,7 @@ namespace fr {
 constexpr uint32_t STREAM_BLOCK = 64;        // the longest block a stream accepts
 constexpr uint32_t STREAM_MAX_WGS = 256;     // (= kernels.hpp BANK_STREAM_WGS)
 constexpr uint32_t STREAM_MAX_INPUTS = 8;    // most distinct input slots the streamed programs may read, slot 0 included (= kernels.hpp BANK_STREAM_ROWS)
+constexpr uint32_t STREAM_MAX_BANKS = 8;     // most bank launches one resident launch serves (= kernels.hpp BANK_STREAM_BANKS)
 
 // What the rule needs to know besides the plan.
 struct StreamEnv {
@@ -41,13 +46,63 @@ struct StreamEnv {
     bool track_history = false;      // FR_TRACK_HISTORY is on (every call appends to the track rings)
     bool bus = false;                // FR_STREAM_BUS: programs that read several voices of a block run after the last voice
     bool inputs = false;             // FR_STREAM_INPUTS: programs may read input slots other than 0 at the current frame
+    bool banks = false;              // FR_STREAM_BANKS: 2..STREAM_MAX_BANKS bank launches in one resident launch
 };
+
+// One bank of a streamed plan.  Voices [first_voice, first_voice + voices) of the global numbering; workgroups
+// [first_wg, first_wg + (voices << (log2_p - chunk_log2))) of the launch, voice-major, then chunk.
+struct StreamBank {
+    uint32_t first_voice = 0, voices = 0, log2_p = 0, chunk_log2 = 0;
+    bool to_ring = false;
+    uint32_t first_wg = 0;
+};
+
+// Every workgroup of the launch must be resident at once, one per CU: as many as the device has CUs (0: unknown, the kernel's
+// own limit stands in), and no more than the kernel's limit.
+inline uint64_t stream_max_wgs(uint32_t device_cus) { return std::min<uint64_t>(STREAM_MAX_WGS, device_cus ? device_cus : STREAM_MAX_WGS); }
+
+// The chunk size of every bank (voices, log2_p set; chunk_log2 and first_wg are written).  Every bank starts at one chunk per
+// voice; false when even that is more than max_wgs workgroups.  Then, until no bank qualifies: the bank with the largest chunk
+// (on a tie the lower index) among those whose chunk is above 128 partials (a wave needs a group of 8), that have fewer than
+// 256 chunks per voice and whose halving keeps the total within max_wgs, has its chunk halved.  A block is only as fast as its
+// largest chunk, so this evens out the partials per workgroup; for one bank it is the short-call kernel's loop.
+inline bool deal_stream_chunks(std::vector<StreamBank> &banks, uint64_t max_wgs) {
+    uint64_t total = 0;
+    for (StreamBank &b : banks) { b.chunk_log2 = b.log2_p; total += b.voices; }
+    if (total > max_wgs) return false;
+    for (;;) {
+        StreamBank *pick = nullptr;
+        for (StreamBank &b : banks) {
+            if (!(b.chunk_log2 > 7 && b.log2_p - b.chunk_log2 < 8)) continue;
+            if (total + ((uint64_t)b.voices << (b.log2_p - b.chunk_log2)) > max_wgs) continue;
+            if (!pick || b.chunk_log2 > pick->chunk_log2) pick = &b;
+        }
+        if (!pick) break;
+        total += (uint64_t)pick->voices << (pick->log2_p - pick->chunk_log2);
+        --pick->chunk_log2;
+    }
+    uint32_t wg = 0, v = 0;
+    for (StreamBank &b : banks) {
+        b.first_wg = wg;
+        b.first_voice = v;
+        wg += b.voices << (b.log2_p - b.chunk_log2);
+        v += b.voices;
+    }
+    return true;
+}
 
 struct StreamPlan {
     bool servable = false;
     std::string reason;              // why not ("" when servable)
-    uint32_t voices = 0, chunk_log2 = 0, chunks = 0;   // chunks per voice; the launch has voices * chunks workgroups
+    uint32_t voices = 0, chunk_log2 = 0, chunks = 0;   // chunks per voice; one bank: the launch has voices * chunks workgroups
     bool bank_to_ring = false;
+    std::vector<StreamBank> banks;       // one per bank launch, in plan order.  Several: `voices` is their total, `chunks` the
+                                         // largest per-voice chunk count, chunk_log2 / bank_to_ring are bank 0's
+    uint32_t workgroups() const {
+        uint32_t n = 0;
+        for (const StreamBank &b : banks) n += b.voices << (b.log2_p - b.chunk_log2);
+        return n;
+    }
     std::vector<uint32_t> progs;         // indices into StagedPlan::progs, voice by voice, then the bus programs, in the order they run
     std::vector<uint32_t> voice_first;   // [voices + 2] into `progs`: [voice_first[voices], voice_first[voices + 1]) is the bus segment
     uint64_t min_ring_delay = 0;         // shortest delayed read of a ring that a program stores (0: there is none)
@@ -71,29 +126,47 @@ inline const char *stage_op_name(uint8_t op) {
 // `banks`: the plan's bank launches (the engine moves them out of StagedPlan::banks when it uploads them).
 inline StreamPlan plan_stream(const StagedPlan &sp, const std::vector<const BankLaunch *> &banks, const StreamEnv &env) {
     StreamPlan s;
-    auto refuse = [&](const std::string &why) { s.servable = false; s.reason = why; return s; };
+    auto refuse = [&](const std::string &why) {
+        s.servable = false;
+        s.reason = why;
+        if (!s.voices) s.banks.clear();              // (refused before the banks were dealt)
+        return s;
+    };
     if (env.n_slots == 0) return refuse("no output slots");
     if (env.sharded || !sp.split.empty()) return refuse("block streaming of a sharded renderer");
     if (env.pull_mode) return refuse("block streaming of a renderer in FR_MODE_PULL");
     if (!sp.pull_rows.empty()) return refuse(std::to_string(sp.pull_rows.size()) + " output rows are left to the pull interpreter");
     if (env.track_history || !sp.track_window_slots.empty() || sp.track_lookback != 0) return refuse("block streaming with a track history");
-    if (banks.size() != 1) return refuse("block streaming needs a plan with one voice bank (this one: " + std::to_string(banks.size()) + " bank launches)");
-    const BankLaunch &b = *banks[0];
-    if (b.general || b.jit || b.tracks || b.to_ws) return refuse("block streaming needs balanced template voices (these are general, compiled or track voices)");
-    if (env.leaf_variant != 1) return refuse("block streaming with FR_BANK_LEAF=0");
-    if (b.input_slot != 0) return refuse("block streaming feeds input slot 0; these voices read another slot");
-    if (b.log2_p < 7) return refuse("block streaming needs voices of at least 128 partials (16 waves x one group of 8)");
-    const uint32_t V = (uint32_t)b.rows.size();
-    if (V == 0) return refuse("block streaming needs a plan with one voice bank (this one has no voices)");
+    if (banks.size() != 1 && !(env.banks && banks.size() >= 2 && banks.size() <= STREAM_MAX_BANKS)) {
+        if (env.banks && banks.size() > STREAM_MAX_BANKS)
+            return refuse("block streaming serves at most " + std::to_string(STREAM_MAX_BANKS) + " voice banks in one launch (this plan: " +
+                          std::to_string(banks.size()) + " bank launches)");
+        return refuse("block streaming needs a plan with one voice bank (this one: " + std::to_string(banks.size()) + " bank launches)");
+    }
+    for (const BankLaunch *bp : banks) {             // (one bank: the checks and their order are what they have always been)
+        const BankLaunch &b = *bp;
+        if (b.general || b.jit || b.tracks || b.to_ws) return refuse("block streaming needs balanced template voices (these are general, compiled or track voices)");
+        if (env.leaf_variant != 1) return refuse("block streaming with FR_BANK_LEAF=0");
+        if (b.input_slot != 0) return refuse("block streaming feeds input slot 0; these voices read another slot");
+        if (b.log2_p < 7) return refuse("block streaming needs voices of at least 128 partials (16 waves x one group of 8)");
+        if (b.rows.empty()) return refuse("block streaming needs a plan with one voice bank (this one has no voices)");
+        StreamBank sb;
+        sb.voices = (uint32_t)b.rows.size();
+        sb.log2_p = b.log2_p;
+        sb.to_ring = b.to_ring;
+        s.banks.push_back(sb);
+    }
     // every workgroup of the launch must be resident at once, one per CU: chunks of >= 128 partials until the CUs are used
-    const uint64_t max_wgs = std::min<uint64_t>(STREAM_MAX_WGS, env.device_cus ? env.device_cus : STREAM_MAX_WGS);
-    uint32_t c = b.log2_p;
-    while (c > 7 && ((uint64_t)V << (b.log2_p - c + 1)) <= max_wgs && b.log2_p - c < 8) --c;
-    if (((uint64_t)V << (b.log2_p - c)) > max_wgs) return refuse("block streaming serves at most one voice per CU (" + std::to_string(max_wgs) + " here)");
+    const uint64_t max_wgs = stream_max_wgs(env.device_cus);
+    if (!deal_stream_chunks(s.banks, max_wgs)) return refuse("block streaming serves at most one voice per CU (" + std::to_string(max_wgs) + " here)");
+    uint32_t V = 0;
+    for (const StreamBank &sb : s.banks) {
+        V += sb.voices;
+        s.chunks = std::max(s.chunks, 1u << (sb.log2_p - sb.chunk_log2));
+    }
     s.voices = V;
-    s.chunk_log2 = c;
-    s.chunks = 1u << (b.log2_p - c);
-    s.bank_to_ring = b.to_ring;
+    s.chunk_log2 = s.banks[0].chunk_log2;
+    s.bank_to_ring = s.banks[0].to_ring;
     std::vector<uint32_t> others;                    // slots other than 0 that the assigned programs read (StreamEnv::inputs)
 
     // the programs that do a block's work: the fused form (a feedback plan: level by level, then its row copies); a plan whose
@@ -116,8 +189,9 @@ inline StreamPlan plan_stream(const StagedPlan &sp, const std::vector<const Bank
         for (uint32_t i = sp.level_first[only]; i < sp.level_first[only + 1]; ++i) run.push_back(i);
     }
     std::unordered_map<uint32_t, uint32_t> bank_ring_voice;   // ring -> voice whose frames it holds
-    if (b.to_ring)
-        for (uint32_t v = 0; v < V; ++v) bank_ring_voice[b.rows[v]] = v;
+    for (size_t i = 0; i < banks.size(); ++i)
+        if (banks[i]->to_ring)
+            for (uint32_t v = 0; v < s.banks[i].voices; ++v) bank_ring_voice[banks[i]->rows[v]] = s.banks[i].first_voice + v;
     std::unordered_map<uint32_t, uint32_t> stored_by;         // ring -> position in `run` of the program that stores it
     for (uint32_t k = 0; k < run.size(); ++k) {
         const StageProg &pg = sp.progs[run[k]];
@@ -216,9 +290,10 @@ inline StreamPlan plan_stream(const StagedPlan &sp, const std::vector<const Bank
     // each output row: one assigned program, or the bank itself
     std::vector<uint32_t> writers(env.n_slots, 0);
     auto writes = [&](int64_t row) { if (row >= 0 && row < (int64_t)env.n_slots) ++writers[(size_t)row]; return row < (int64_t)env.n_slots; };
-    if (!b.to_ring)
-        for (uint32_t row : b.rows)
-            if (!writes(row)) return refuse("a voice writes output row " + std::to_string(row) + " of " + std::to_string(env.n_slots));
+    for (const BankLaunch *bp : banks)
+        if (!bp->to_ring)
+            for (uint32_t row : bp->rows)
+                if (!writes(row)) return refuse("a voice writes output row " + std::to_string(row) + " of " + std::to_string(env.n_slots));
     for (uint32_t k = 0; k < run.size(); ++k)
         if (!writes(sp.progs[run[k]].out_row)) return refuse("a program writes output row " + std::to_string(sp.progs[run[k]].out_row) + " of " + std::to_string(env.n_slots));
     for (uint32_t r = 0; r < env.n_slots; ++r)
