@@ -787,163 +787,398 @@ static hipError_t launch_bank_short(const BankArgs &a, hipStream_t s) {
 }
 
 // ---------------------------------------------------------------------------------------------------
-// Block streaming: the short-call kernel as ONE resident launch (kernels.hpp, BankStreamCtl).
+// Block streaming: the short-call kernel as ONE resident launch (kernels.hpp, BankStreamCtl).  Five kernels -- bank_stream_kernel
+// below, the four that also run programs after stage_kernel -- are compositions of the pieces in this section; each step of the
+// protocol is written once, here.
+//
+// A block.  The host rings a doorbell in mapped pinned memory: every word carries a sample and the block's tag.  Wave 0 of
+// workgroup 0 polls it (stream_row_wait: one row; stream_in_wait: K rows), republishes the rows to device memory, has them
+// acknowledged, then stores n_times and -- acknowledged in between -- seq (stream_next_block).  Thread 0 of every other
+// workgroup polls seq.  Every workgroup then renders its (voice, chunk) of the block as bank_short_kernel does
+// (stream_render_chunk); the chunk sums of a voice meet through a ticket, the last arriver adds them in tree order
+// (stream_hand_over) and so finishes the voice: wave 0 of that workgroup stores the voice's 64 frames to its row or ring
+// (stream_store_voice), runs the voice's programs, lane = frame (stream_run_programs), and counts the voice in (stream_finish,
+// stream_finish_bus); whoever counts the last voice in writes the block's done tag to the host.
+//
+// The hand-overs.  No workgroup waits for another one's result and there is no acquire or release inside the block loop: all
+// traffic between workgroups is relaxed atomics at agent scope (sc1: served by L2, never by a CU's L1 -- the finisher of a voice
+// changes CU from block to block), what goes to the host is stored at system scope, and a wave has its own stores acknowledged
+// (s_waitcnt vmcnt(0)) before it takes a ticket, before it reads them back, and before the done tag; the wave that draws the
+// last ticket issues its loads after that ticket came back (MI355X_MICROARCH.md, inter-workgroup visibility).  What the rule
+// on the host guarantees for programs (streamplan.hpp): a program reads at a delay below 64 frames only the ring its own wave
+// has just stored, or a ring an earlier program of the same voice stored; everything else was stored by an earlier block, whose
+// done tag the host has seen -- except in the bus segment, which runs after every voice of the block was counted in.
+//
+// The bounds.  Every polling loop is bounded on the 100 MHz wall clock (s_memrealtime): with no block for `idle_ms` workgroup 0
+// publishes STOP and the launch ends itself (friendship_render.h: FR_STREAM_IDLE_MS), whatever a look across PCIe happens to
+// cost; the followers' bound outlasts workgroup 0's.
+//
+// 1024 threads per workgroup: at most 128 VGPRs and no scratch -- the interpreter's registers are LDS columns.  The pieces are
+// __forceinline__; what they compile to inside each kernel is compared with the kernels' earlier, separately written text in
+// profiles/stream_shared_text.txt (registers, LDS, scratch, and the count of every barrier, sleep, clock read, vmcnt(0) and
+// atomic), which is where a change to a piece is checked.
 // ---------------------------------------------------------------------------------------------------
+constexpr int STREAM_NW = 16;   // waves of a streaming workgroup
+
+// What a workgroup renders in every block of the launch (uniform: lives in SGPRs).
+struct StreamWork {
+    uint32_t voice;        // the global voice: its chunk sums, its ticket and its programs
+    uint32_t bank_voice;   // the voice inside its bank: its parameters and its destination
+    uint32_t chunk, clog, nchunks;
+    uint32_t ngroups, levels;
+    const float *mine;     // this wave's partials
+    uint32_t fast_ok;
+    const uint32_t *rows;  // the bank's destinations: rings (to_ring) or output rows
+    uint32_t to_ring;
+};
+
+// Workgroup `local` of a bank whose voices are cut into chunks of 1 << chunk_log2 partials; the bank's first voice is global voice `first_voice`.
+__device__ __forceinline__ StreamWork stream_work(const float2 *params, const uint32_t *rows, uint32_t log2_p, uint32_t chunk_log2, uint32_t fast_ok, uint32_t to_ring,
+                                                  uint32_t first_voice, uint32_t local, uint32_t wave) {
+    StreamWork w;
+    w.clog = log2_p - chunk_log2;
+    w.nchunks = 1u << w.clog;
+    w.chunk = local & (w.nchunks - 1u);   // the chunks of one voice are neighbours in the grid
+    w.bank_voice = local >> w.clog;
+    w.voice = first_voice + w.bank_voice;
+    const uint32_t Pc = 1u << chunk_log2;
+    const uint32_t Pw = Pc / STREAM_NW;
+    w.ngroups = Pw >> 3;
+    w.levels = 0;
+    while ((1u << w.levels) < w.ngroups) ++w.levels;
+    w.mine = (const float *)(params + ((size_t)w.bank_voice << log2_p) + (size_t)w.chunk * Pc + (size_t)wave * Pw);
+    w.fast_ok = fast_ok;
+    w.rows = rows;
+    w.to_ring = to_ring;
+    return w;
+}
+
+// Workgroup 0's wait for the next block on the one-row doorbell (BankStreamCtl): lane i polls word i.  The block has arrived
+// when every lane holds the same new tag; the row is then republished to device memory (acknowledged before the caller stores
+// n_times and seq).  Returns the block's tag (BANK_STREAM_STOP: stop, or no block within the bound).
+__device__ __forceinline__ uint32_t stream_row_wait(BankStreamCtl *ctl, BankStreamDev *dev, uint32_t lane, uint32_t seen, unsigned long long idle_ticks, uint32_t &T) {
+    uint32_t tag = seen;
+    float v = 0.0f;
+    bool fresh = false;
+    const unsigned long long wait_from = __builtin_amdgcn_s_memrealtime();
+    for (;;) {
+        const unsigned long long word = __hip_atomic_load(&ctl->row[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        tag = (uint32_t)(word >> 32);
+        v = __uint_as_float((uint32_t)word);
+        fresh = __all(tag != seen) && (uint32_t)__builtin_amdgcn_readfirstlane(tag) == tag;   // every lane holds the same new tag
+        fresh = __all(fresh);
+        if (fresh || __builtin_amdgcn_s_memrealtime() - wait_from > idle_ticks) break;
+    }
+    const uint32_t seq = fresh ? __builtin_amdgcn_readfirstlane(tag) : BANK_STREAM_STOP;   // nobody rang: end
+    T = 0;
+    if (seq != BANK_STREAM_STOP) {
+        T = seq & 0xFFu;
+        T = T > 64u ? 64u : T;
+        __hip_atomic_store(&dev->row[lane], lane < T ? v : 0.0f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    return seq;
+}
+
+// The same for a doorbell of K rows (BankStreamInCtl).  One look = the loads of all K rows in flight together, then one wait: a
+// word whose tag is new carries its sample with it, so however many rows there are the block costs one trip across PCIe.  The
+// block has arrived when every lane of every row holds the same new tag.
+template <uint32_t K>
+__device__ __forceinline__ uint32_t stream_in_wait(BankStreamInCtl *ctl, BankStreamInDev *dev, uint32_t lane, uint32_t seen, unsigned long long idle_ticks, uint32_t &T) {
+    unsigned long long word[K];
+    uint32_t tag = seen;
+    bool fresh = false;
+    const unsigned long long wait_from = __builtin_amdgcn_s_memrealtime();
+    for (;;) {
+        static_for<0, K>([&](auto j) { word[j] = __hip_atomic_load(&ctl->rows[j][lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); });
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        tag = (uint32_t)(word[0] >> 32);
+        const uint32_t first = (uint32_t)__builtin_amdgcn_readfirstlane(tag);
+        bool same = tag != seen && tag == first;
+        static_for<1, K>([&](auto j) { same = same && (uint32_t)(word[j] >> 32) == first; });
+        fresh = __all(same);
+        if (fresh || __builtin_amdgcn_s_memrealtime() - wait_from > idle_ticks) break;
+    }
+    const uint32_t seq = fresh ? __builtin_amdgcn_readfirstlane(tag) : BANK_STREAM_STOP;
+    T = 0;
+    if (seq != BANK_STREAM_STOP) {
+        T = seq & 0xFFu;
+        T = T > 64u ? 64u : T;
+        static_for<0, K>([&](auto j) {
+            __hip_atomic_store(&dev->rows[j][lane], lane < T ? __uint_as_float((uint32_t)word[j]) : 0.0f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        });
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    return seq;
+}
+
+// (launch-uniform row count: one jump, then a loop whose every look is straight-line code)
+__device__ __forceinline__ uint32_t stream_rows_wait(uint32_t n_rows, BankStreamInCtl *ctl, BankStreamInDev *dev, uint32_t lane, uint32_t seen,
+                                                     unsigned long long idle_ticks, uint32_t &T) {
+    switch (n_rows) {
+    case 1: return stream_in_wait<1>(ctl, dev, lane, seen, idle_ticks, T);
+    case 2: return stream_in_wait<2>(ctl, dev, lane, seen, idle_ticks, T);
+    case 3: return stream_in_wait<3>(ctl, dev, lane, seen, idle_ticks, T);
+    case 4: return stream_in_wait<4>(ctl, dev, lane, seen, idle_ticks, T);
+    case 5: return stream_in_wait<5>(ctl, dev, lane, seen, idle_ticks, T);
+    case 6: return stream_in_wait<6>(ctl, dev, lane, seen, idle_ticks, T);
+    case 7: return stream_in_wait<7>(ctl, dev, lane, seen, idle_ticks, T);
+    default: return stream_in_wait<8>(ctl, dev, lane, seen, idle_ticks, T);
+    }
+}
+
+// Every workgroup's wait for the next block.  Wave 0 of workgroup 0 runs `doorbell` (one of the waits above) and publishes what
+// it brought: n_times, acknowledged, then seq (the rows were acknowledged by the wait).  Thread 0 of any other workgroup polls
+// seq; its bound outlasts workgroup 0's, which ends in a STOP for everybody.  Returns the block's tag and its frames in T.
+template <class Dev, class Doorbell>
+__device__ __forceinline__ uint32_t stream_next_block(Dev *dev, uint32_t wave, uint32_t lane, uint32_t seen, unsigned long long idle_ticks, uint32_t &s_seq, uint32_t &s_T,
+                                                      uint32_t &T, Doorbell &&doorbell) {
+    if (blockIdx.x == 0) {
+        if (wave == 0u) {
+            uint32_t T0 = 0;
+            const uint32_t seq = doorbell(T0);
+            if (lane == 0u) {
+                __hip_atomic_store(&dev->n_times, T0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                __hip_atomic_store(&dev->seq, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // (rows and n_times are acknowledged)
+                s_seq = seq;
+                s_T = T0;
+            }
+        }
+    } else if (threadIdx.x == 0) {
+        uint32_t seq = seen;
+        const unsigned long long wait_from = __builtin_amdgcn_s_memrealtime();
+        for (;;) {
+            seq = __hip_atomic_load(&dev->seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (seq != seen || __builtin_amdgcn_s_memrealtime() - wait_from > 2ull * idle_ticks + 10000000ull) break;
+            __builtin_amdgcn_s_sleep(4);
+        }
+        if (seq == seen) seq = BANK_STREAM_STOP;
+        s_seq = seq;
+        s_T = __hip_atomic_load(&dev->n_times, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __syncthreads();
+    T = s_T;
+    return s_seq;
+}
+
+// One (voice, chunk) of one tile, as bank_short_kernel: lane = frame, `trow` the block's republished time row (its load is
+// requested after the first parameter group's, so the two trips to memory overlap).  Returns the chunk's sum in wave 0, a zero
+// with the sign the graph's arithmetic gives it; `t` is the lane's time in every wave.  Two barriers, a third when a sum is zero.
+__device__ __forceinline__ float stream_render_chunk(const StreamWork &w, const float *trow, bool live, uint32_t wave, uint32_t lane, float (&sm)[STREAM_NW][64],
+                                                     unsigned long long &zshared, float &t) {
+    constexpr int NW = STREAM_NW;
+    ParamGroup first;
+    load_group(first, (const_f32_ptr)w.mine, 0);
+    t = live ? __hip_atomic_load(&trow[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0f;
+    const bool fast = w.fast_ok && __all(t >= 0.0f && t <= 4294967296.0f);
+    const float tt[1] = {t};
+    float r_wave[1];
+    if (fast) bank_wave_sum<1, true, false>(w.mine, w.ngroups, w.levels, tt, r_wave, &first);
+    else bank_wave_sum<1, false, false>(w.mine, w.ngroups, w.levels, tt, r_wave, &first);
+    sm[wave][lane] = r_wave[0];
+    __syncthreads();
+    float r = 0.0f;
+    if (wave == 0u) {   // the NW wave sums in tree order: adjacent pairs, level by level
+        float s[NW];
+        static_for<0, NW>([&](auto i) { s[i] = sm[i][lane]; });
+        static_for<0, NW / 2>([&](auto i) { s[i] = s[2 * i] + s[2 * i + 1]; });
+        static_for<0, NW / 4>([&](auto i) { s[i] = s[2 * i] + s[2 * i + 1]; });
+        static_for<0, NW / 8>([&](auto i) { s[i] = s[2 * i] + s[2 * i + 1]; });
+        static_for<0, NW / 16>([&](auto i) { s[i] = s[2 * i] + s[2 * i + 1]; });
+        r = s[0];
+        const unsigned long long z = __ballot(live && r == 0.0f);
+        if (lane == 0u) zshared = z;
+    }
+    __syncthreads();
+    const unsigned long long zm = zshared;                // workgroup-uniform
+    if (zm != 0ull) {   // the sign of a zero chunk sum: -0 iff every leaf of the chunk is -0 in the graph's arithmetic
+        const bool ok = fast ? wave_leaves_all_negzero<true>(w.mine, w.ngroups, t, zm) : wave_leaves_all_negzero<false>(w.mine, w.ngroups, t, zm);
+        sm[wave][lane] = ok ? 1.0f : 0.0f;
+        __syncthreads();
+        if (wave == 0u && ((zm >> lane) & 1ull)) {
+            bool all = true;
+            static_for<0, NW>([&](auto i) { all = all && sm[i][lane] != 0.0f; });
+            r = all ? -0.0f : 0.0f;
+        }
+    }
+    return r;
+}
+
+// Wave 0 hands its chunk sum `r` over: store, acknowledged, then a ticket; the wave whose ticket is the voice's last reads all
+// chunks back and adds them in tree order, takes the top of the ladder for this voice's chunk count and resets the ticket for
+// the next block.  The chunk sums of all voices share one workspace, [chunk][n_voices][64] by global voice; one ticket per
+// voice.  True in the wave that finished the voice, with its frames in `result`.
+__device__ __forceinline__ bool stream_hand_over(const StreamWork &w, float *ws, uint32_t *tickets, uint32_t n_voices, uint32_t lane, float r, float &result) {
+    result = r;
+    if (w.nchunks == 1u) return true;
+    const size_t vstride = (size_t)n_voices * 64u;
+    float *slot = ws + (size_t)w.voice * 64u;
+    __hip_atomic_store(slot + (size_t)w.chunk * vstride + lane, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    uint32_t old = 0u;
+    if (lane == 0u) old = __hip_atomic_fetch_add(tickets + (size_t)w.voice * TICKET_STRIDE, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    old = __builtin_amdgcn_readfirstlane(old);
+    if (old != w.nchunks - 1u) return false;
+    // binary-counter carry over the chunks (nchunks = 2^clog <= 256): level k holds the finished left sibling of height k;
+    // named registers, so nothing is indexed dynamically (no scratch)
+    float c0 = 0.0f, c1 = 0.0f, c2 = 0.0f, c3 = 0.0f, c4 = 0.0f, c5 = 0.0f, c6 = 0.0f, c7 = 0.0f, c8 = 0.0f;
+    for (uint32_t c = 0; c < w.nchunks; ++c) {
+        float v = c == w.chunk ? r : __hip_atomic_load(slot + (size_t)c * vstride + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        do {
+            if (!(c & 1u)) { c0 = v; break; } v = c0 + v;
+            if (!(c & 2u)) { c1 = v; break; } v = c1 + v;
+            if (!(c & 4u)) { c2 = v; break; } v = c2 + v;
+            if (!(c & 8u)) { c3 = v; break; } v = c3 + v;
+            if (!(c & 16u)) { c4 = v; break; } v = c4 + v;
+            if (!(c & 32u)) { c5 = v; break; } v = c5 + v;
+            if (!(c & 64u)) { c6 = v; break; } v = c6 + v;
+            if (!(c & 128u)) { c7 = v; break; } v = c7 + v;
+            c8 = v;
+        } while (0);
+    }
+    const uint32_t clog = w.clog;
+    result = c8;   // after the last chunk (all ones) the chain stopped at level clog
+    result = clog == 7u ? c7 : result; result = clog == 6u ? c6 : result; result = clog == 5u ? c5 : result;
+    result = clog == 4u ? c4 : result; result = clog == 3u ? c3 : result; result = clog == 2u ? c2 : result;
+    result = clog == 1u ? c1 : result;
+    if (lane == 0u) __hip_atomic_store(tickets + (size_t)w.voice * TICKET_STRIDE, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return true;
+}
+
+// A program's load.  `input(row)` is S_INPUT: the block's one row, or a republished control row.
+template <class Input>
+__device__ __forceinline__ float stream_prog_load(const StreamProgArgs &p, const StageInstr &in, uint64_t frame, Input &&input) {
+    switch (in.op) {
+    case S_CONST: return __uint_as_float(in.imm);
+    case S_INPUT: return input(in.imm);
+    case S_READ:
+        return frame >= in.d_lo ? __hip_atomic_load(p.rings + (size_t)in.buf * (p.ring_mask + 1) + ((frame - in.d_lo) & p.ring_mask), __ATOMIC_RELAXED,
+                                                    __HIP_MEMORY_SCOPE_AGENT)
+                                : 0.0f;
+    default: return frame >= in.d_lo ? __uint_as_float(in.imm) : 0.0f;   // S_STEP
+    }
+}
+
+// The interpreter: programs [p_first, p_end) in order, lane = frame, in wave 0 of a finishing workgroup; `regs` are its
+// registers, [register][lane] in LDS; `out` the mapped host rows.
+template <class Input>
+__device__ __forceinline__ void stream_run_programs(float *out, const StreamProgArgs &p, float (&regs)[STAGE_REGS][64], uint32_t p_first, uint32_t p_end, uint64_t frame,
+                                                    uint32_t lane, bool live, Input &&input) {
+    const uint64_t ring_cap = p.ring_mask + 1;
+    for (uint32_t pi = p_first; pi < p_end; ++pi) {
+        // what this wave has stored so far (the voice's ring, an earlier program's rings) is in L2 before it is read back
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        const StageProg pg = p.progs[pi];
+        const StageInstr *ins = p.instrs + pg.first_instr;
+        uint32_t i = 0;
+        for (; i + 4u <= pg.n_loads; i += 4u) {   // the program's leading loads (rings and control rows), four round trips to L2 in flight together
+            float ld[4];
+#pragma unroll
+            for (uint32_t j = 0; j < 4u; ++j) ld[j] = stream_prog_load(p, ins[i + j], frame, input);
+#pragma unroll
+            for (uint32_t j = 0; j < 4u; ++j) regs[ins[i + j].dst][lane] = ld[j];
+        }
+        for (; i < pg.n_instr; ++i) {
+            const StageInstr in = ins[i];
+            float v;
+            switch (in.op) {
+            case S_SUM2: v = regs[in.a][lane] + regs[in.b][lane]; break;
+            case S_MUL: v = regs[in.a][lane] * regs[in.b][lane]; break;
+            case S_DIV: v = regs[in.a][lane] / regs[in.b][lane]; break;
+            case S_MOD: v = prim_mod(regs[in.a][lane], regs[in.b][lane]); break;
+            case S_MIN: v = prim_min(regs[in.a][lane], regs[in.b][lane], p.sparkle != 0u); break;
+            case S_STORE:
+                if (live) __hip_atomic_store(p.rings + (size_t)in.buf * ring_cap + (frame & p.ring_mask), regs[in.a][lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                continue;
+            default: v = stream_prog_load(p, in, frame, input); break;
+            }
+            regs[in.dst][lane] = v;
+        }
+        const float res = regs[pg.result_reg][lane];
+        if (live && pg.dst_ring != 0xFFFFFFFFu)
+            __hip_atomic_store(p.rings + (size_t)pg.dst_ring * ring_cap + (frame & p.ring_mask), res, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (live && pg.out_row >= 0) __hip_atomic_store(out + (size_t)pg.out_row * 64u + lane, res, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+}
+
+// A finished voice's frames, head + lane, go to its ring or -- a host row: system scope -- to its row, as its bank says.
+__device__ __forceinline__ void stream_store_voice(const StreamWork &w, float *out, const StreamProgArgs &p, uint64_t frame, uint32_t lane, bool live, float result) {
+    const uint32_t dst = w.rows[w.bank_voice];
+    if (live) {
+        if (w.to_ring) __hip_atomic_store(p.rings + (size_t)dst * (p.ring_mask + 1) + (frame & p.ring_mask), result, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        else __hip_atomic_store(out + (size_t)dst * 64u + lane, result, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+}
+
+// The finishing wave counts its voice in.  Ring and row stores alike are acknowledged before the ticket, so the block's done
+// tag -- written by the lane that counts the last voice in -- implies that every store of the block has landed.
+template <class Ctl, class Dev>
+__device__ __forceinline__ void stream_finish(Ctl *ctl, Dev *dev, uint32_t n_voices, uint32_t lane, uint32_t seq) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (lane == 0u) {
+        const uint32_t n = __hip_atomic_fetch_add(&dev->voices_done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (n == n_voices - 1u) {
+            __hip_atomic_store(&dev->voices_done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(&ctl->done, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+    }
+}
+
+// The same with a bus segment: the ticket goes to the whole wave, and the block's last arriver runs `bus` (the programs that
+// read several voices of this block), lane = frame, before the tag.  Every voice's stores were acknowledged before its ticket,
+// and this wave's loads are issued after its own ticket came back: the hand-over of the chunk sums.
+template <class Ctl, class Dev, class Bus>
+__device__ __forceinline__ void stream_finish_bus(Ctl *ctl, Dev *dev, uint32_t n_voices, uint32_t lane, uint32_t seq, Bus &&bus) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    uint32_t n = 0u;
+    if (lane == 0u) n = __hip_atomic_fetch_add(&dev->voices_done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    n = __builtin_amdgcn_readfirstlane(n);
+    if (n == n_voices - 1u) {
+        bus();
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // host rows and rings have landed before the done tag
+        if (lane == 0u) {
+            __hip_atomic_store(&dev->voices_done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(&ctl->done, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+    }
+}
+
+// What every streaming launch checks of a bank's shape, and of the programs' arguments.
+static bool stream_bank_ok(uint32_t log2_p, uint32_t chunk_log2, uint32_t n_voices, const float *ws, const uint32_t *tickets) {
+    if (chunk_log2 < 7 || chunk_log2 > 13 || chunk_log2 > log2_p || log2_p - chunk_log2 > 8) return false;
+    if (((uint64_t)n_voices << (log2_p - chunk_log2)) > BANK_STREAM_WGS || n_voices == 0) return false;   // all workgroups must be resident
+    return chunk_log2 == log2_p || (ws && tickets);
+}
+static bool stream_progs_ok(const StreamProgArgs &p, bool to_ring) {
+    if (!p.voice_first || (p.ring_mask & (p.ring_mask + 1)) != 0) return false;
+    return !(p.n_rings && (!p.rings || p.ring_mask + 1 < 64u)) && !(to_ring && !p.n_rings);
+}
+
+// bank_stream_kernel: banks alone.  One-row doorbell, render, hand-over; the finished voice goes to its row of the mapped host
+// result (system scope) and is counted in by lane 0.  No programs, no interpreter registers in LDS.
 __global__ void __launch_bounds__(1024) bank_stream_kernel(BankArgs a, BankStreamCtl *ctl, BankStreamDev *dev, uint32_t idle_ms) {
-    constexpr int NW = 16;
-    __shared__ float sm[NW][64];
+    __shared__ float sm[STREAM_NW][64];
     __shared__ unsigned long long zshared;
     __shared__ uint32_t s_seq, s_T;
-    const uint32_t clog = a.log2_p - a.chunk_log2, nchunks = 1u << clog;
-    const uint32_t chunk = blockIdx.x & (nchunks - 1u);
-    const uint32_t voice = blockIdx.x >> clog;
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint32_t Pc = 1u << a.chunk_log2;
-    const uint32_t Pw = Pc / NW, ngroups = Pw >> 3;
-    uint32_t levels = 0;
-    while ((1u << levels) < ngroups) ++levels;
-    const bool working = voice < a.n_voices;                 // (the grid is exactly n_voices * nchunks workgroups: always true)
-    // Every polling loop below is bounded on the 100 MHz wall clock (s_memrealtime): with no block for `idle_ms` the launch
-    // ends itself (friendship_render.h: FR_STREAM_IDLE_MS), whatever a look across PCIe happens to cost.
+    const StreamWork w = stream_work(a.params, a.rows, a.log2_p, a.chunk_log2, a.fast_ok, 0u, 0u, blockIdx.x, wave);   // (the grid is exactly n_voices * nchunks workgroups)
     const unsigned long long idle_ticks = (unsigned long long)idle_ms * 100000ull;
-    const float *mine = (const float *)(a.params + ((size_t)(working ? voice : 0u) << a.log2_p) + (size_t)chunk * Pc + (size_t)wave * Pw);
-    const size_t vstride = (size_t)a.n_voices * 64u;
     uint32_t seen = 0;
     if (blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store(&ctl->alive, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     for (;;) {
-        // ---- wait for the next block (bounded) ----
-        if (blockIdx.x == 0) {
-            if (wave == 0u) {
-                uint32_t tag = seen;
-                float v = 0.0f;
-                bool fresh = false;
-                const unsigned long long wait_from = __builtin_amdgcn_s_memrealtime();
-                for (;;) {
-                    const unsigned long long word = __hip_atomic_load(&ctl->row[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                    tag = (uint32_t)(word >> 32);
-                    v = __uint_as_float((uint32_t)word);
-                    fresh = __all(tag != seen) && (uint32_t)__builtin_amdgcn_readfirstlane(tag) == tag;   // every lane holds the same new tag
-                    fresh = __all(fresh);
-                    if (fresh || __builtin_amdgcn_s_memrealtime() - wait_from > idle_ticks) break;
-                }
-                const uint32_t seq = fresh ? __builtin_amdgcn_readfirstlane(tag) : BANK_STREAM_STOP;   // nobody rang: end
-                uint32_t T = 0;
-                if (seq != BANK_STREAM_STOP) {
-                    T = seq & 0xFFu;
-                    T = T > 64u ? 64u : T;
-                    __hip_atomic_store(&dev->row[lane], lane < T ? v : 0.0f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                }
-                if (lane == 0u) {
-                    __hip_atomic_store(&dev->n_times, T, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                    __hip_atomic_store(&dev->seq, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // (row and n_times are acknowledged)
-                    s_seq = seq;
-                    s_T = T;
-                }
-            }
-        } else if (threadIdx.x == 0) {
-            uint32_t seq = seen;
-            const unsigned long long wait_from = __builtin_amdgcn_s_memrealtime();
-            for (;;) {                                                       // (outlasts workgroup 0's bound, which ends in a STOP for everybody)
-                seq = __hip_atomic_load(&dev->seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (seq != seen || __builtin_amdgcn_s_memrealtime() - wait_from > 2ull * idle_ticks + 10000000ull) break;
-                __builtin_amdgcn_s_sleep(4);
-            }
-            if (seq == seen) seq = BANK_STREAM_STOP;
-            s_seq = seq;
-            s_T = __hip_atomic_load(&dev->n_times, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        __syncthreads();
-        const uint32_t seq = s_seq, T = s_T;
+        uint32_t T;
+        const uint32_t seq = stream_next_block(dev, wave, lane, seen, idle_ticks, s_seq, s_T, T, [&](uint32_t &T0) { return stream_row_wait(ctl, dev, lane, seen, idle_ticks, T0); });
         if (seq == BANK_STREAM_STOP) break;
         seen = seq;
-        if (working) {
-            // ---- one (voice, chunk) of one tile, as bank_short_kernel ----
-            const bool live = lane < T;
-            ParamGroup first;
-            load_group(first, (const_f32_ptr)mine, 0);
-            const float t = live ? __hip_atomic_load(&dev->row[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0f;
-            const bool fast = a.fast_ok && __all(t >= 0.0f && t <= 4294967296.0f);
-            const float tt[1] = {t};
-            float r_wave[1];
-            if (fast) bank_wave_sum<1, true, false>(mine, ngroups, levels, tt, r_wave, &first);
-            else bank_wave_sum<1, false, false>(mine, ngroups, levels, tt, r_wave, &first);
-            sm[wave][lane] = r_wave[0];
-            __syncthreads();
-            float r = 0.0f;
-            if (wave == 0u) {
-                float s[NW];
-                static_for<0, NW>([&](auto w) { s[w] = sm[w][lane]; });
-                static_for<0, NW / 2>([&](auto i) { s[i] = s[2 * i] + s[2 * i + 1]; });
-                static_for<0, NW / 4>([&](auto i) { s[i] = s[2 * i] + s[2 * i + 1]; });
-                static_for<0, NW / 8>([&](auto i) { s[i] = s[2 * i] + s[2 * i + 1]; });
-                static_for<0, NW / 16>([&](auto i) { s[i] = s[2 * i] + s[2 * i + 1]; });
-                r = s[0];
-                const unsigned long long z = __ballot(live && r == 0.0f);
-                if (lane == 0u) zshared = z;
-            }
-            __syncthreads();
-            const unsigned long long zm = zshared;
-            if (zm != 0ull) {
-                const bool ok = fast ? wave_leaves_all_negzero<true>(mine, ngroups, t, zm) : wave_leaves_all_negzero<false>(mine, ngroups, t, zm);
-                sm[wave][lane] = ok ? 1.0f : 0.0f;
-                __syncthreads();
-                if (wave == 0u && ((zm >> lane) & 1ull)) {
-                    bool all = true;
-                    static_for<0, NW>([&](auto w) { all = all && sm[w][lane] != 0.0f; });
-                    r = all ? -0.0f : 0.0f;
-                }
-            }
-            if (wave == 0u) {
-                float *orow = a.out + (size_t)a.rows[voice] * 64u;
-                bool finished_voice = nchunks == 1u;
-                float result = r;
-                if (nchunks > 1u) {
-                    float *slot = a.ws + (size_t)voice * 64u;
-                    __hip_atomic_store(slot + (size_t)chunk * vstride + lane, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                    uint32_t old = 0u;
-                    if (lane == 0u) old = __hip_atomic_fetch_add(a.tickets + (size_t)voice * TICKET_STRIDE, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    old = __builtin_amdgcn_readfirstlane(old);
-                    if (old == nchunks - 1u) {
-                        finished_voice = true;
-                        float c0 = 0.0f, c1 = 0.0f, c2 = 0.0f, c3 = 0.0f, c4 = 0.0f, c5 = 0.0f, c6 = 0.0f, c7 = 0.0f, c8 = 0.0f;
-                        for (uint32_t c = 0; c < nchunks; ++c) {
-                            float v = c == chunk ? r : __hip_atomic_load(slot + (size_t)c * vstride + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            do {
-                                if (!(c & 1u)) { c0 = v; break; } v = c0 + v;
-                                if (!(c & 2u)) { c1 = v; break; } v = c1 + v;
-                                if (!(c & 4u)) { c2 = v; break; } v = c2 + v;
-                                if (!(c & 8u)) { c3 = v; break; } v = c3 + v;
-                                if (!(c & 16u)) { c4 = v; break; } v = c4 + v;
-                                if (!(c & 32u)) { c5 = v; break; } v = c5 + v;
-                                if (!(c & 64u)) { c6 = v; break; } v = c6 + v;
-                                if (!(c & 128u)) { c7 = v; break; } v = c7 + v;
-                                c8 = v;
-                            } while (0);
-                        }
-                        result = c8;
-                        result = clog == 7u ? c7 : result; result = clog == 6u ? c6 : result; result = clog == 5u ? c5 : result;
-                        result = clog == 4u ? c4 : result; result = clog == 3u ? c3 : result; result = clog == 2u ? c2 : result;
-                        result = clog == 1u ? c1 : result;
-                        if (lane == 0u) __hip_atomic_store(a.tickets + (size_t)voice * TICKET_STRIDE, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    }
-                }
-                if (finished_voice) {
-                    // the row goes to the host: system-scope stores, acknowledged before the voice is counted in
-                    if (live) __hip_atomic_store(&orow[lane], result, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                    if (lane == 0u) {
-                        const uint32_t n = __hip_atomic_fetch_add(&dev->voices_done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        if (n == a.n_voices - 1u) {
-                            __hip_atomic_store(&dev->voices_done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            __hip_atomic_store(&ctl->done, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);   // (every row's stores were acknowledged before its voice was counted)
-                        }
-                    }
-                }
-            }
+        const bool live = lane < T;
+        float t, result;
+        const float r = stream_render_chunk(w, dev->row, live, wave, lane, sm, zshared, t);
+        if (wave == 0u && stream_hand_over(w, a.ws, a.tickets, a.n_voices, lane, r, result)) {
+            // the row goes to the host: system-scope stores, acknowledged before the voice is counted in
+            if (live) __hip_atomic_store(a.out + (size_t)w.rows[w.bank_voice] * 64u + lane, result, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            stream_finish(ctl, dev, a.n_voices, lane, seq);
         }
         __syncthreads();   // LDS is reused by the next block
     }
@@ -951,10 +1186,8 @@ __global__ void __launch_bounds__(1024) bank_stream_kernel(BankArgs a, BankStrea
 }
 
 hipError_t launch_bank_stream(const BankArgs &a, BankStreamCtl *ctl_dev, BankStreamDev *dev, uint32_t idle_ms, hipStream_t s) {
-    if (a.chunk_log2 < 7 || a.chunk_log2 > 13 || a.chunk_log2 > a.log2_p || a.log2_p - a.chunk_log2 > 8) return hipErrorInvalidValue;
-    if (((uint64_t)a.n_voices << (a.log2_p - a.chunk_log2)) > BANK_STREAM_WGS || a.n_voices == 0) return hipErrorInvalidValue;
+    if (!stream_bank_ok(a.log2_p, a.chunk_log2, a.n_voices, a.ws, a.tickets)) return hipErrorInvalidValue;
     if ((1u << a.chunk_log2) / 16u < 8u) return hipErrorInvalidValue;          // a wave needs a whole group of 8 partials
-    if (a.chunk_log2 != a.log2_p && (!a.ws || !a.tickets)) return hipErrorInvalidValue;
     if (a.leaf_variant != 1 || !a.out || !a.rows || !ctl_dev || !dev) return hipErrorInvalidValue;
     // exactly the workgroups that render: a small patch leaves the other CUs to whatever else wants the device
     const uint32_t wgs = a.n_voices << (a.log2_p - a.chunk_log2);
@@ -1453,224 +1686,72 @@ hipError_t launch_stage(const StageArgs &a, hipStream_t s) {
 }
 
 // ---------------------------------------------------------------------------------------------------
-// Block streaming of plans with programs (kernels.hpp StreamProgArgs, streamplan.hpp): bank_stream_kernel -- doorbell, chunk
-// rendering, tickets and last-arriver combine exactly as there, every polling loop with the same bound -- and, in wave 0 of
-// the workgroup that finishes a voice, the voice's programs.  What the rule on the host guarantees: a program reads at a
-// delay below 64 frames only the ring its own wave has just stored (or a ring a program of the same voice stored before it:
-// a feedback plan's row copies); everything else it reads was stored by an earlier block, whose done tag the host has seen.
-// So there is no wait on another workgroup and no acquire or release anywhere in the loop: ring traffic is relaxed
-// agent-scope atomics (sc1: served by L2, never by a CU's L1 -- the finisher of a voice changes CU from block to block), and
-// a wave's own stores are acknowledged (vmcnt(0)) before it reads them back or counts the voice in.
-// 1024 threads per workgroup: at most 128 VGPRs and no scratch -- the interpreter's registers are LDS columns.
+// Block streaming of plans with programs (kernels.hpp StreamProgArgs, streamplan.hpp): four more compositions of the pieces
+// above bank_stream_kernel, where the protocol is described.  All four keep the interpreter's registers in LDS, advance `head`
+// (the first frame of the block, the same in every workgroup) by each block's length, and in the wave that finishes a voice
+// store the voice and run its programs (stream_voice_programs).  They differ in the doorbell, in where S_INPUT comes from, in
+// whether the block's last arriver runs a bus segment, and in how a workgroup finds its work:
+//
+//   kernel                     doorbell        S_INPUT                 bus segment   work
+//   bank_stream_prog_kernel    one row         the block's row         no            BankArgs
+//   bank_stream_bus_kernel     one row         the block's row         yes           BankArgs
+//   bank_stream_in_kernel      n_rows rows     the row the host named  yes           BankArgs
+//   bank_stream_banks_kernel   n_rows rows     the row the host named  yes           its entry of the bank table
+//
+// The bus segment is progs[voice_first[n_voices] .. voice_first[n_voices + 1]) and may be empty.  Which kernel a plan launches
+// is the host's rule (streamplan.hpp; fr_plan_json["stream"]["kernel"]).  The compiled kernels against their earlier,
+// separately written text: profiles/stream_shared_text.txt.
 // ---------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float stream_prog_load(const StreamProgArgs &p, const StageInstr &in, uint64_t frame, float row_value) {
-    switch (in.op) {
-    case S_CONST: return __uint_as_float(in.imm);
-    case S_INPUT: return row_value;
-    case S_READ:
-        return frame >= in.d_lo ? __hip_atomic_load(p.rings + (size_t)in.buf * (p.ring_mask + 1) + ((frame - in.d_lo) & p.ring_mask), __ATOMIC_RELAXED,
-                                                    __HIP_MEMORY_SCOPE_AGENT)
-                                : 0.0f;
-    default: return frame >= in.d_lo ? __uint_as_float(in.imm) : 0.0f;   // S_STEP
+
+// S_INPUT of the one-row kernels: the block's row, which the finishing wave holds as `t`.
+struct StreamRowInput {
+    float t;
+    __device__ __forceinline__ float operator()(uint32_t) const { return t; }
+};
+// S_INPUT of the control-row kernels.  imm is the streamed row (the host rewrote it); rows the launch does not stream hold +0.0.
+// Row 0 is `t`; the others were republished before this workgroup saw the block's seq: a relaxed agent-scope load, in flight
+// with the program's other leading loads.
+struct StreamRowsInput {
+    const BankStreamInDev *dev;
+    uint32_t lane;
+    float t;
+    __device__ __forceinline__ float operator()(uint32_t row) const {
+        return row == 0u ? t : __hip_atomic_load(&dev->rows[row & (BANK_STREAM_ROWS - 1u)][lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
+};
+
+// The finishing wave: the voice's frames head + lane to its ring or row, then its programs, lane = frame.
+template <class Input>
+__device__ __forceinline__ void stream_voice_programs(const StreamWork &w, float *out, const StreamProgArgs &p, float (&regs)[STAGE_REGS][64], uint64_t frame, uint32_t lane,
+                                                      bool live, float result, const Input &input) {
+    stream_store_voice(w, out, p, frame, lane, live, result);
+    stream_run_programs(out, p, regs, p.voice_first[w.voice], p.voice_first[w.voice + 1], frame, lane, live, input);
 }
 
+// One-row doorbell; per-voice programs; lane 0 counts the voice in.
 __global__ void __launch_bounds__(1024) bank_stream_prog_kernel(BankArgs a, StreamProgArgs p, BankStreamCtl *ctl, BankStreamDev *dev, uint32_t idle_ms) {
-    constexpr int NW = 16;
-    __shared__ float sm[NW][64];
+    __shared__ float sm[STREAM_NW][64];
     __shared__ float regs[STAGE_REGS][64];                   // the interpreter's registers: [register][lane] of wave 0
     __shared__ unsigned long long zshared;
     __shared__ uint32_t s_seq, s_T;
-    const uint32_t clog = a.log2_p - a.chunk_log2, nchunks = 1u << clog;
-    const uint32_t chunk = blockIdx.x & (nchunks - 1u);
-    const uint32_t voice = blockIdx.x >> clog;               // (the grid is exactly n_voices * nchunks workgroups)
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint32_t Pc = 1u << a.chunk_log2;
-    const uint32_t Pw = Pc / NW, ngroups = Pw >> 3;
-    uint32_t levels = 0;
-    while ((1u << levels) < ngroups) ++levels;
+    const StreamWork w = stream_work(a.params, a.rows, a.log2_p, a.chunk_log2, a.fast_ok, p.bank_to_ring, 0u, blockIdx.x, wave);   // (the grid is exactly n_voices * nchunks workgroups)
     const unsigned long long idle_ticks = (unsigned long long)idle_ms * 100000ull;
-    const float *mine = (const float *)(a.params + ((size_t)voice << a.log2_p) + (size_t)chunk * Pc + (size_t)wave * Pw);
-    const size_t vstride = (size_t)a.n_voices * 64u;
-    const uint64_t ring_cap = p.ring_mask + 1;
-    uint64_t head = p.head;                                  // first frame of the block being rendered (the same in every workgroup)
+    uint64_t head = p.head;
     uint32_t seen = 0;
     if (blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store(&ctl->alive, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     for (;;) {
-        // ---- wait for the next block (bounded), as bank_stream_kernel ----
-        if (blockIdx.x == 0) {
-            if (wave == 0u) {
-                uint32_t tag = seen;
-                float v = 0.0f;
-                bool fresh = false;
-                const unsigned long long wait_from = __builtin_amdgcn_s_memrealtime();
-                for (;;) {
-                    const unsigned long long word = __hip_atomic_load(&ctl->row[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                    tag = (uint32_t)(word >> 32);
-                    v = __uint_as_float((uint32_t)word);
-                    fresh = __all(tag != seen) && (uint32_t)__builtin_amdgcn_readfirstlane(tag) == tag;
-                    fresh = __all(fresh);
-                    if (fresh || __builtin_amdgcn_s_memrealtime() - wait_from > idle_ticks) break;
-                }
-                const uint32_t seq = fresh ? __builtin_amdgcn_readfirstlane(tag) : BANK_STREAM_STOP;
-                uint32_t T = 0;
-                if (seq != BANK_STREAM_STOP) {
-                    T = seq & 0xFFu;
-                    T = T > 64u ? 64u : T;
-                    __hip_atomic_store(&dev->row[lane], lane < T ? v : 0.0f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                }
-                if (lane == 0u) {
-                    __hip_atomic_store(&dev->n_times, T, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                    __hip_atomic_store(&dev->seq, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    s_seq = seq;
-                    s_T = T;
-                }
-            }
-        } else if (threadIdx.x == 0) {
-            uint32_t seq = seen;
-            const unsigned long long wait_from = __builtin_amdgcn_s_memrealtime();
-            for (;;) {
-                seq = __hip_atomic_load(&dev->seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (seq != seen || __builtin_amdgcn_s_memrealtime() - wait_from > 2ull * idle_ticks + 10000000ull) break;
-                __builtin_amdgcn_s_sleep(4);
-            }
-            if (seq == seen) seq = BANK_STREAM_STOP;
-            s_seq = seq;
-            s_T = __hip_atomic_load(&dev->n_times, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        __syncthreads();
-        const uint32_t seq = s_seq, T = s_T;
+        uint32_t T;
+        const uint32_t seq = stream_next_block(dev, wave, lane, seen, idle_ticks, s_seq, s_T, T, [&](uint32_t &T0) { return stream_row_wait(ctl, dev, lane, seen, idle_ticks, T0); });
         if (seq == BANK_STREAM_STOP) break;
         seen = seq;
-        {
-            // ---- one (voice, chunk) of one tile, as bank_stream_kernel ----
-            const bool live = lane < T;
-            ParamGroup first;
-            load_group(first, (const_f32_ptr)mine, 0);
-            const float t = live ? __hip_atomic_load(&dev->row[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0f;
-            const bool fast = a.fast_ok && __all(t >= 0.0f && t <= 4294967296.0f);
-            const float tt[1] = {t};
-            float r_wave[1];
-            if (fast) bank_wave_sum<1, true, false>(mine, ngroups, levels, tt, r_wave, &first);
-            else bank_wave_sum<1, false, false>(mine, ngroups, levels, tt, r_wave, &first);
-            sm[wave][lane] = r_wave[0];
-            __syncthreads();
-            float r = 0.0f;
-            if (wave == 0u) {
-                float s[NW];
-                static_for<0, NW>([&](auto w) { s[w] = sm[w][lane]; });
-                static_for<0, NW / 2>([&](auto i) { s[i] = s[2 * i] + s[2 * i + 1]; });
-                static_for<0, NW / 4>([&](auto i) { s[i] = s[2 * i] + s[2 * i + 1]; });
-                static_for<0, NW / 8>([&](auto i) { s[i] = s[2 * i] + s[2 * i + 1]; });
-                static_for<0, NW / 16>([&](auto i) { s[i] = s[2 * i] + s[2 * i + 1]; });
-                r = s[0];
-                const unsigned long long z = __ballot(live && r == 0.0f);
-                if (lane == 0u) zshared = z;
-            }
-            __syncthreads();
-            const unsigned long long zm = zshared;
-            if (zm != 0ull) {
-                const bool ok = fast ? wave_leaves_all_negzero<true>(mine, ngroups, t, zm) : wave_leaves_all_negzero<false>(mine, ngroups, t, zm);
-                sm[wave][lane] = ok ? 1.0f : 0.0f;
-                __syncthreads();
-                if (wave == 0u && ((zm >> lane) & 1ull)) {
-                    bool all = true;
-                    static_for<0, NW>([&](auto w) { all = all && sm[w][lane] != 0.0f; });
-                    r = all ? -0.0f : 0.0f;
-                }
-            }
-            if (wave == 0u) {
-                bool finished_voice = nchunks == 1u;
-                float result = r;
-                if (nchunks > 1u) {
-                    float *slot = a.ws + (size_t)voice * 64u;
-                    __hip_atomic_store(slot + (size_t)chunk * vstride + lane, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                    uint32_t old = 0u;
-                    if (lane == 0u) old = __hip_atomic_fetch_add(a.tickets + (size_t)voice * TICKET_STRIDE, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    old = __builtin_amdgcn_readfirstlane(old);
-                    if (old == nchunks - 1u) {
-                        finished_voice = true;
-                        float c0 = 0.0f, c1 = 0.0f, c2 = 0.0f, c3 = 0.0f, c4 = 0.0f, c5 = 0.0f, c6 = 0.0f, c7 = 0.0f, c8 = 0.0f;
-                        for (uint32_t c = 0; c < nchunks; ++c) {
-                            float v = c == chunk ? r : __hip_atomic_load(slot + (size_t)c * vstride + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            do {
-                                if (!(c & 1u)) { c0 = v; break; } v = c0 + v;
-                                if (!(c & 2u)) { c1 = v; break; } v = c1 + v;
-                                if (!(c & 4u)) { c2 = v; break; } v = c2 + v;
-                                if (!(c & 8u)) { c3 = v; break; } v = c3 + v;
-                                if (!(c & 16u)) { c4 = v; break; } v = c4 + v;
-                                if (!(c & 32u)) { c5 = v; break; } v = c5 + v;
-                                if (!(c & 64u)) { c6 = v; break; } v = c6 + v;
-                                if (!(c & 128u)) { c7 = v; break; } v = c7 + v;
-                                c8 = v;
-                            } while (0);
-                        }
-                        result = c8;
-                        result = clog == 7u ? c7 : result; result = clog == 6u ? c6 : result; result = clog == 5u ? c5 : result;
-                        result = clog == 4u ? c4 : result; result = clog == 3u ? c3 : result; result = clog == 2u ? c2 : result;
-                        result = clog == 1u ? c1 : result;
-                        if (lane == 0u) __hip_atomic_store(a.tickets + (size_t)voice * TICKET_STRIDE, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    }
-                }
-                if (finished_voice) {
-                    // ---- the voice's frames head + lane: to its ring (or its row), then its programs, lane = frame ----
-                    const uint64_t frame = head + lane;
-                    const uint32_t dst = a.rows[voice];
-                    if (live) {
-                        if (p.bank_to_ring) __hip_atomic_store(p.rings + (size_t)dst * ring_cap + (frame & p.ring_mask), result, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        else __hip_atomic_store(a.out + (size_t)dst * 64u + lane, result, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                    }
-                    const uint32_t p_end = p.voice_first[voice + 1];
-                    for (uint32_t pi = p.voice_first[voice]; pi < p_end; ++pi) {
-                        // what this wave has stored so far (the voice's ring, an earlier program's rings) is in L2 before it is read back
-                        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                        const StageProg pg = p.progs[pi];
-                        const StageInstr *ins = p.instrs + pg.first_instr;
-                        uint32_t i = 0;
-                        for (; i + 4u <= pg.n_loads; i += 4u) {   // the program's leading loads, four round trips to L2 in flight together
-                            float ld[4];
-#pragma unroll
-                            for (uint32_t j = 0; j < 4u; ++j) ld[j] = stream_prog_load(p, ins[i + j], frame, t);
-#pragma unroll
-                            for (uint32_t j = 0; j < 4u; ++j) regs[ins[i + j].dst][lane] = ld[j];
-                        }
-                        for (; i < pg.n_instr; ++i) {
-                            const StageInstr in = ins[i];
-                            float v;
-                            switch (in.op) {
-                            case S_SUM2: v = regs[in.a][lane] + regs[in.b][lane]; break;
-                            case S_MUL: v = regs[in.a][lane] * regs[in.b][lane]; break;
-                            case S_DIV: v = regs[in.a][lane] / regs[in.b][lane]; break;
-                            case S_MOD: v = prim_mod(regs[in.a][lane], regs[in.b][lane]); break;
-                            case S_MIN: v = prim_min(regs[in.a][lane], regs[in.b][lane], p.sparkle != 0u); break;
-                            case S_STORE:
-                                if (live) __hip_atomic_store(p.rings + (size_t)in.buf * ring_cap + (frame & p.ring_mask), regs[in.a][lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                                continue;
-                            default: v = stream_prog_load(p, in, frame, t); break;
-                            }
-                            regs[in.dst][lane] = v;
-                        }
-                        const float res = regs[pg.result_reg][lane];
-                        if (live && pg.dst_ring != 0xFFFFFFFFu)
-                            __hip_atomic_store(p.rings + (size_t)pg.dst_ring * ring_cap + (frame & p.ring_mask), res, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        if (live && pg.out_row >= 0) __hip_atomic_store(a.out + (size_t)pg.out_row * 64u + lane, res, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                    }
-                    // ring and row stores alike are acknowledged before the voice is counted in: the block's done tag then implies
-                    // that every ring store of the block has landed
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                    if (lane == 0u) {
-                        const uint32_t n = __hip_atomic_fetch_add(&dev->voices_done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        if (n == a.n_voices - 1u) {
-                            __hip_atomic_store(&dev->voices_done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            __hip_atomic_store(&ctl->done, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                        }
-                    }
-                }
-            }
+        const bool live = lane < T;
+        float t, result;
+        const float r = stream_render_chunk(w, dev->row, live, wave, lane, sm, zshared, t);
+        if (wave == 0u && stream_hand_over(w, a.ws, a.tickets, a.n_voices, lane, r, result)) {
+            stream_voice_programs(w, a.out, p, regs, head + lane, lane, live, result, StreamRowInput{t});
+            stream_finish(ctl, dev, a.n_voices, lane, seq);
         }
         head += T;
         __syncthreads();   // LDS is reused by the next block
@@ -1679,235 +1760,40 @@ __global__ void __launch_bounds__(1024) bank_stream_prog_kernel(BankArgs a, Stre
 }
 
 hipError_t launch_bank_stream_prog(const BankArgs &a, const StreamProgArgs &p, BankStreamCtl *ctl_dev, BankStreamDev *dev, uint32_t idle_ms, hipStream_t s) {
-    if (a.chunk_log2 < 7 || a.chunk_log2 > 13 || a.chunk_log2 > a.log2_p || a.log2_p - a.chunk_log2 > 8) return hipErrorInvalidValue;
-    if (((uint64_t)a.n_voices << (a.log2_p - a.chunk_log2)) > BANK_STREAM_WGS || a.n_voices == 0) return hipErrorInvalidValue;
-    if (a.chunk_log2 != a.log2_p && (!a.ws || !a.tickets)) return hipErrorInvalidValue;
-    if (a.leaf_variant != 1 || !a.out || !a.rows || !ctl_dev || !dev || !p.voice_first) return hipErrorInvalidValue;
-    if ((p.ring_mask & (p.ring_mask + 1)) != 0 || (p.n_rings && (!p.rings || p.ring_mask + 1 < 64u)) || (p.bank_to_ring && !p.n_rings)) return hipErrorInvalidValue;
+    if (!stream_bank_ok(a.log2_p, a.chunk_log2, a.n_voices, a.ws, a.tickets) || !stream_progs_ok(p, p.bank_to_ring != 0)) return hipErrorInvalidValue;
+    if (a.leaf_variant != 1 || !a.out || !a.rows || !ctl_dev || !dev) return hipErrorInvalidValue;
     const uint32_t wgs = a.n_voices << (a.log2_p - a.chunk_log2);
     hipLaunchKernelGGL(bank_stream_prog_kernel, dim3(wgs), dim3(1024), 0, s, a, p, ctl_dev, dev, idle_ms ? idle_ms : BANK_STREAM_IDLE_MS);
     return hipGetLastError();
 }
 
-// ---------------------------------------------------------------------------------------------------
-// Block streaming with mix-bus programs (FR_STREAM_BUS, streamplan.hpp): bank_stream_prog_kernel, and after the per-voice
-// programs one more segment, progs[voice_first[n_voices] .. voice_first[n_voices + 1]): the bus programs, which read several
-// voices of the SAME block (and what earlier programs of the block stored).  Still no workgroup waits for another one: the
-// wave whose voices_done ticket comes back as n_voices - 1 -- the one that writes the block's done tag -- knows that every
-// voice has been counted in, and every voice acknowledged its ring and row stores (vmcnt(0)) before it took its ticket.  That
-// wave interprets the bus programs, lane = frame, its ring loads relaxed agent-scope atomics issued after the ticket returned
-// (the hand-over of the chunk sums: store, vmcnt(0), ticket | ticket, load), vmcnt(0) between programs and before the tag.
-// The interpreter is the text of bank_stream_prog_kernel's as a function; that kernel and bank_stream_kernel keep their own
-// text, so their code does not change with this one.
-// ---------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void stream_run_programs(const BankArgs &a, const StreamProgArgs &p, float (*regs)[64], uint32_t p_first, uint32_t p_end, uint64_t frame,
-                                                    uint32_t lane, bool live, float t) {
-    const uint64_t ring_cap = p.ring_mask + 1;
-    for (uint32_t pi = p_first; pi < p_end; ++pi) {
-        // what this wave has stored so far (the voice's ring, an earlier program's rings) is in L2 before it is read back
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const StageProg pg = p.progs[pi];
-        const StageInstr *ins = p.instrs + pg.first_instr;
-        uint32_t i = 0;
-        for (; i + 4u <= pg.n_loads; i += 4u) {   // the program's leading loads, four round trips to L2 in flight together
-            float ld[4];
-#pragma unroll
-            for (uint32_t j = 0; j < 4u; ++j) ld[j] = stream_prog_load(p, ins[i + j], frame, t);
-#pragma unroll
-            for (uint32_t j = 0; j < 4u; ++j) regs[ins[i + j].dst][lane] = ld[j];
-        }
-        for (; i < pg.n_instr; ++i) {
-            const StageInstr in = ins[i];
-            float v;
-            switch (in.op) {
-            case S_SUM2: v = regs[in.a][lane] + regs[in.b][lane]; break;
-            case S_MUL: v = regs[in.a][lane] * regs[in.b][lane]; break;
-            case S_DIV: v = regs[in.a][lane] / regs[in.b][lane]; break;
-            case S_MOD: v = prim_mod(regs[in.a][lane], regs[in.b][lane]); break;
-            case S_MIN: v = prim_min(regs[in.a][lane], regs[in.b][lane], p.sparkle != 0u); break;
-            case S_STORE:
-                if (live) __hip_atomic_store(p.rings + (size_t)in.buf * ring_cap + (frame & p.ring_mask), regs[in.a][lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                continue;
-            default: v = stream_prog_load(p, in, frame, t); break;
-            }
-            regs[in.dst][lane] = v;
-        }
-        const float res = regs[pg.result_reg][lane];
-        if (live && pg.dst_ring != 0xFFFFFFFFu)
-            __hip_atomic_store(p.rings + (size_t)pg.dst_ring * ring_cap + (frame & p.ring_mask), res, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (live && pg.out_row >= 0) __hip_atomic_store(a.out + (size_t)pg.out_row * 64u + lane, res, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-}
-
+// bank_stream_prog_kernel with the bus segment (FR_STREAM_BUS): the voices_done ticket goes to the whole wave.
 __global__ void __launch_bounds__(1024) bank_stream_bus_kernel(BankArgs a, StreamProgArgs p, BankStreamCtl *ctl, BankStreamDev *dev, uint32_t idle_ms) {
-    constexpr int NW = 16;
-    __shared__ float sm[NW][64];
+    __shared__ float sm[STREAM_NW][64];
     __shared__ float regs[STAGE_REGS][64];                   // the interpreter's registers: [register][lane] of wave 0
     __shared__ unsigned long long zshared;
     __shared__ uint32_t s_seq, s_T;
-    const uint32_t clog = a.log2_p - a.chunk_log2, nchunks = 1u << clog;
-    const uint32_t chunk = blockIdx.x & (nchunks - 1u);
-    const uint32_t voice = blockIdx.x >> clog;               // (the grid is exactly n_voices * nchunks workgroups)
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint32_t Pc = 1u << a.chunk_log2;
-    const uint32_t Pw = Pc / NW, ngroups = Pw >> 3;
-    uint32_t levels = 0;
-    while ((1u << levels) < ngroups) ++levels;
+    const StreamWork w = stream_work(a.params, a.rows, a.log2_p, a.chunk_log2, a.fast_ok, p.bank_to_ring, 0u, blockIdx.x, wave);   // (the grid is exactly n_voices * nchunks workgroups)
     const unsigned long long idle_ticks = (unsigned long long)idle_ms * 100000ull;
-    const float *mine = (const float *)(a.params + ((size_t)voice << a.log2_p) + (size_t)chunk * Pc + (size_t)wave * Pw);
-    const size_t vstride = (size_t)a.n_voices * 64u;
-    const uint64_t ring_cap = p.ring_mask + 1;
-    uint64_t head = p.head;                                  // first frame of the block being rendered (the same in every workgroup)
+    uint64_t head = p.head;
     uint32_t seen = 0;
     if (blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store(&ctl->alive, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     for (;;) {
-        // ---- wait for the next block (bounded), as bank_stream_prog_kernel ----
-        if (blockIdx.x == 0) {
-            if (wave == 0u) {
-                uint32_t tag = seen;
-                float v = 0.0f;
-                bool fresh = false;
-                const unsigned long long wait_from = __builtin_amdgcn_s_memrealtime();
-                for (;;) {
-                    const unsigned long long word = __hip_atomic_load(&ctl->row[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                    tag = (uint32_t)(word >> 32);
-                    v = __uint_as_float((uint32_t)word);
-                    fresh = __all(tag != seen) && (uint32_t)__builtin_amdgcn_readfirstlane(tag) == tag;
-                    fresh = __all(fresh);
-                    if (fresh || __builtin_amdgcn_s_memrealtime() - wait_from > idle_ticks) break;
-                }
-                const uint32_t seq = fresh ? __builtin_amdgcn_readfirstlane(tag) : BANK_STREAM_STOP;
-                uint32_t T = 0;
-                if (seq != BANK_STREAM_STOP) {
-                    T = seq & 0xFFu;
-                    T = T > 64u ? 64u : T;
-                    __hip_atomic_store(&dev->row[lane], lane < T ? v : 0.0f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                }
-                if (lane == 0u) {
-                    __hip_atomic_store(&dev->n_times, T, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                    __hip_atomic_store(&dev->seq, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    s_seq = seq;
-                    s_T = T;
-                }
-            }
-        } else if (threadIdx.x == 0) {
-            uint32_t seq = seen;
-            const unsigned long long wait_from = __builtin_amdgcn_s_memrealtime();
-            for (;;) {
-                seq = __hip_atomic_load(&dev->seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (seq != seen || __builtin_amdgcn_s_memrealtime() - wait_from > 2ull * idle_ticks + 10000000ull) break;
-                __builtin_amdgcn_s_sleep(4);
-            }
-            if (seq == seen) seq = BANK_STREAM_STOP;
-            s_seq = seq;
-            s_T = __hip_atomic_load(&dev->n_times, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        __syncthreads();
-        const uint32_t seq = s_seq, T = s_T;
+        uint32_t T;
+        const uint32_t seq = stream_next_block(dev, wave, lane, seen, idle_ticks, s_seq, s_T, T, [&](uint32_t &T0) { return stream_row_wait(ctl, dev, lane, seen, idle_ticks, T0); });
         if (seq == BANK_STREAM_STOP) break;
         seen = seq;
-        {
-            // ---- one (voice, chunk) of one tile, as bank_stream_prog_kernel ----
-            const bool live = lane < T;
-            ParamGroup first;
-            load_group(first, (const_f32_ptr)mine, 0);
-            const float t = live ? __hip_atomic_load(&dev->row[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0f;
-            const bool fast = a.fast_ok && __all(t >= 0.0f && t <= 4294967296.0f);
-            const float tt[1] = {t};
-            float r_wave[1];
-            if (fast) bank_wave_sum<1, true, false>(mine, ngroups, levels, tt, r_wave, &first);
-            else bank_wave_sum<1, false, false>(mine, ngroups, levels, tt, r_wave, &first);
-            sm[wave][lane] = r_wave[0];
-            __syncthreads();
-            float r = 0.0f;
-            if (wave == 0u) {
-                float s[NW];
-                static_for<0, NW>([&](auto w) { s[w] = sm[w][lane]; });
-                static_for<0, NW / 2>([&](auto i) { s[i] = s[2 * i] + s[2 * i + 1]; });
-                static_for<0, NW / 4>([&](auto i) { s[i] = s[2 * i] + s[2 * i + 1]; });
-                static_for<0, NW / 8>([&](auto i) { s[i] = s[2 * i] + s[2 * i + 1]; });
-                static_for<0, NW / 16>([&](auto i) { s[i] = s[2 * i] + s[2 * i + 1]; });
-                r = s[0];
-                const unsigned long long z = __ballot(live && r == 0.0f);
-                if (lane == 0u) zshared = z;
-            }
-            __syncthreads();
-            const unsigned long long zm = zshared;
-            if (zm != 0ull) {
-                const bool ok = fast ? wave_leaves_all_negzero<true>(mine, ngroups, t, zm) : wave_leaves_all_negzero<false>(mine, ngroups, t, zm);
-                sm[wave][lane] = ok ? 1.0f : 0.0f;
-                __syncthreads();
-                if (wave == 0u && ((zm >> lane) & 1ull)) {
-                    bool all = true;
-                    static_for<0, NW>([&](auto w) { all = all && sm[w][lane] != 0.0f; });
-                    r = all ? -0.0f : 0.0f;
-                }
-            }
-            if (wave == 0u) {
-                bool finished_voice = nchunks == 1u;
-                float result = r;
-                if (nchunks > 1u) {
-                    float *slot = a.ws + (size_t)voice * 64u;
-                    __hip_atomic_store(slot + (size_t)chunk * vstride + lane, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                    uint32_t old = 0u;
-                    if (lane == 0u) old = __hip_atomic_fetch_add(a.tickets + (size_t)voice * TICKET_STRIDE, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    old = __builtin_amdgcn_readfirstlane(old);
-                    if (old == nchunks - 1u) {
-                        finished_voice = true;
-                        float c0 = 0.0f, c1 = 0.0f, c2 = 0.0f, c3 = 0.0f, c4 = 0.0f, c5 = 0.0f, c6 = 0.0f, c7 = 0.0f, c8 = 0.0f;
-                        for (uint32_t c = 0; c < nchunks; ++c) {
-                            float v = c == chunk ? r : __hip_atomic_load(slot + (size_t)c * vstride + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            do {
-                                if (!(c & 1u)) { c0 = v; break; } v = c0 + v;
-                                if (!(c & 2u)) { c1 = v; break; } v = c1 + v;
-                                if (!(c & 4u)) { c2 = v; break; } v = c2 + v;
-                                if (!(c & 8u)) { c3 = v; break; } v = c3 + v;
-                                if (!(c & 16u)) { c4 = v; break; } v = c4 + v;
-                                if (!(c & 32u)) { c5 = v; break; } v = c5 + v;
-                                if (!(c & 64u)) { c6 = v; break; } v = c6 + v;
-                                if (!(c & 128u)) { c7 = v; break; } v = c7 + v;
-                                c8 = v;
-                            } while (0);
-                        }
-                        result = c8;
-                        result = clog == 7u ? c7 : result; result = clog == 6u ? c6 : result; result = clog == 5u ? c5 : result;
-                        result = clog == 4u ? c4 : result; result = clog == 3u ? c3 : result; result = clog == 2u ? c2 : result;
-                        result = clog == 1u ? c1 : result;
-                        if (lane == 0u) __hip_atomic_store(a.tickets + (size_t)voice * TICKET_STRIDE, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    }
-                }
-                if (finished_voice) {
-                    // ---- the voice's frames head + lane: to its ring (or its row), then its programs, lane = frame (as bank_stream_prog_kernel) ----
-                    const uint64_t frame = head + lane;
-                    const uint32_t dst = a.rows[voice];
-                    if (live) {
-                        if (p.bank_to_ring) __hip_atomic_store(p.rings + (size_t)dst * ring_cap + (frame & p.ring_mask), result, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        else __hip_atomic_store(a.out + (size_t)dst * 64u + lane, result, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                    }
-                    stream_run_programs(a, p, regs, p.voice_first[voice], p.voice_first[voice + 1], frame, lane, live, t);
-                    // ring and row stores alike are acknowledged before the voice is counted in: the block's done tag then implies
-                    // that every ring store of the block has landed
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                    // the ticket goes to the whole wave: the last arriver of the block runs the bus programs, lane = frame
-                    uint32_t n = 0u;
-                    if (lane == 0u) n = __hip_atomic_fetch_add(&dev->voices_done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    n = __builtin_amdgcn_readfirstlane(n);
-                    if (n == a.n_voices - 1u) {
-                        // every voice's ring and row stores were acknowledged before its ticket, and this wave's loads are issued
-                        // after its own ticket came back: the hand-over of the chunk sums
-                        stream_run_programs(a, p, regs, p.voice_first[a.n_voices], p.voice_first[a.n_voices + 1], frame, lane, live, t);
-                        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // host rows and rings have landed before the done tag
-                        if (lane == 0u) {
-                            __hip_atomic_store(&dev->voices_done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            __hip_atomic_store(&ctl->done, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                        }
-                    }
-                }
-            }
+        const bool live = lane < T;
+        float t, result;
+        const float r = stream_render_chunk(w, dev->row, live, wave, lane, sm, zshared, t);
+        if (wave == 0u && stream_hand_over(w, a.ws, a.tickets, a.n_voices, lane, r, result)) {
+            const uint64_t frame = head + lane;
+            const StreamRowInput input{t};
+            stream_voice_programs(w, a.out, p, regs, frame, lane, live, result, input);
+            stream_finish_bus(ctl, dev, a.n_voices, lane, seq,
+                              [&] { stream_run_programs(a.out, p, regs, p.voice_first[a.n_voices], p.voice_first[a.n_voices + 1], frame, lane, live, input); });
         }
         head += T;
         __syncthreads();   // LDS is reused by the next block
@@ -1916,272 +1802,40 @@ __global__ void __launch_bounds__(1024) bank_stream_bus_kernel(BankArgs a, Strea
 }
 
 hipError_t launch_bank_stream_bus(const BankArgs &a, const StreamProgArgs &p, BankStreamCtl *ctl_dev, BankStreamDev *dev, uint32_t idle_ms, hipStream_t s) {
-    if (a.chunk_log2 < 7 || a.chunk_log2 > 13 || a.chunk_log2 > a.log2_p || a.log2_p - a.chunk_log2 > 8) return hipErrorInvalidValue;
-    if (((uint64_t)a.n_voices << (a.log2_p - a.chunk_log2)) > BANK_STREAM_WGS || a.n_voices == 0) return hipErrorInvalidValue;
-    if (a.chunk_log2 != a.log2_p && (!a.ws || !a.tickets)) return hipErrorInvalidValue;
-    if (a.leaf_variant != 1 || !a.out || !a.rows || !ctl_dev || !dev || !p.voice_first) return hipErrorInvalidValue;
-    if ((p.ring_mask & (p.ring_mask + 1)) != 0 || (p.n_rings && (!p.rings || p.ring_mask + 1 < 64u)) || (p.bank_to_ring && !p.n_rings)) return hipErrorInvalidValue;
+    if (!stream_bank_ok(a.log2_p, a.chunk_log2, a.n_voices, a.ws, a.tickets) || !stream_progs_ok(p, p.bank_to_ring != 0)) return hipErrorInvalidValue;
+    if (a.leaf_variant != 1 || !a.out || !a.rows || !ctl_dev || !dev) return hipErrorInvalidValue;
     const uint32_t wgs = a.n_voices << (a.log2_p - a.chunk_log2);
     hipLaunchKernelGGL(bank_stream_bus_kernel, dim3(wgs), dim3(1024), 0, s, a, p, ctl_dev, dev, idle_ms ? idle_ms : BANK_STREAM_IDLE_MS);
     return hipGetLastError();
 }
 
-// ---------------------------------------------------------------------------------------------------
-// Block streaming with control rows (FR_STREAM_INPUTS, streamplan.hpp, kernels.hpp BankStreamInCtl): what
-// bank_stream_bus_kernel does -- per-voice programs in the wave that finishes a voice, the bus programs (a segment that may be
-// empty) in the wave that counts the block's last voice in -- with a doorbell of n_rows rows and S_INPUT by row.  Workgroup 0's
-// one polling loop looks at every row's words at once and republishes the rows to device memory before it releases the others
-// (stores, vmcnt(0), seq); a finishing wave reads row j > 0 of the republished rows after it has seen that seq, a relaxed
-// agent-scope load with the program's other leading loads.  Row 0 is the `t` it already holds.  No new polling loop, no acquire
-// or release.  The kernel and its interpreter have their own text: the three older streaming kernels' code does not change.
-// ---------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float stream_in_load(const StreamProgArgs &p, const BankStreamInDev *dev, const StageInstr &in, uint64_t frame, uint32_t lane, float t) {
-    switch (in.op) {
-    case S_CONST: return __uint_as_float(in.imm);
-    case S_INPUT:   // imm: the streamed row (the host rewrote it); rows the launch does not stream hold +0.0
-        return in.imm == 0u ? t : __hip_atomic_load(&dev->rows[in.imm & (BANK_STREAM_ROWS - 1u)][lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    case S_READ:
-        return frame >= in.d_lo ? __hip_atomic_load(p.rings + (size_t)in.buf * (p.ring_mask + 1) + ((frame - in.d_lo) & p.ring_mask), __ATOMIC_RELAXED,
-                                                    __HIP_MEMORY_SCOPE_AGENT)
-                                : 0.0f;
-    default: return frame >= in.d_lo ? __uint_as_float(in.imm) : 0.0f;   // S_STEP
-    }
-}
-
-__device__ __forceinline__ void stream_in_run_programs(const BankArgs &a, const StreamProgArgs &p, const BankStreamInDev *dev, float (*regs)[64], uint32_t p_first,
-                                                       uint32_t p_end, uint64_t frame, uint32_t lane, bool live, float t) {
-    const uint64_t ring_cap = p.ring_mask + 1;
-    for (uint32_t pi = p_first; pi < p_end; ++pi) {
-        // what this wave has stored so far (the voice's ring, an earlier program's rings) is in L2 before it is read back
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const StageProg pg = p.progs[pi];
-        const StageInstr *ins = p.instrs + pg.first_instr;
-        uint32_t i = 0;
-        for (; i + 4u <= pg.n_loads; i += 4u) {   // the program's leading loads (rings and control rows), four round trips to L2 in flight together
-            float ld[4];
-#pragma unroll
-            for (uint32_t j = 0; j < 4u; ++j) ld[j] = stream_in_load(p, dev, ins[i + j], frame, lane, t);
-#pragma unroll
-            for (uint32_t j = 0; j < 4u; ++j) regs[ins[i + j].dst][lane] = ld[j];
-        }
-        for (; i < pg.n_instr; ++i) {
-            const StageInstr in = ins[i];
-            float v;
-            switch (in.op) {
-            case S_SUM2: v = regs[in.a][lane] + regs[in.b][lane]; break;
-            case S_MUL: v = regs[in.a][lane] * regs[in.b][lane]; break;
-            case S_DIV: v = regs[in.a][lane] / regs[in.b][lane]; break;
-            case S_MOD: v = prim_mod(regs[in.a][lane], regs[in.b][lane]); break;
-            case S_MIN: v = prim_min(regs[in.a][lane], regs[in.b][lane], p.sparkle != 0u); break;
-            case S_STORE:
-                if (live) __hip_atomic_store(p.rings + (size_t)in.buf * ring_cap + (frame & p.ring_mask), regs[in.a][lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                continue;
-            default: v = stream_in_load(p, dev, in, frame, lane, t); break;
-            }
-            regs[in.dst][lane] = v;
-        }
-        const float res = regs[pg.result_reg][lane];
-        if (live && pg.dst_ring != 0xFFFFFFFFu)
-            __hip_atomic_store(p.rings + (size_t)pg.dst_ring * ring_cap + (frame & p.ring_mask), res, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (live && pg.out_row >= 0) __hip_atomic_store(a.out + (size_t)pg.out_row * 64u + lane, res, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-}
-
-// Workgroup 0's wait for the next block, the one polling loop of the kernel (bounded on the wall clock as in bank_stream_kernel),
-// for a doorbell of K rows.  One look = the loads of all K rows in flight together, then one wait: a word whose tag is new
-// carries its sample with it, so however many rows there are the block costs one trip across PCIe.  The block has arrived
-// when every lane of every row holds the same new tag; the rows are then republished to device memory (acknowledged before
-// the caller stores n_times and seq).  Returns the block's tag (BANK_STREAM_STOP: stop, or no block within the bound).
-template <uint32_t K>
-__device__ __forceinline__ uint32_t stream_in_wait(BankStreamInCtl *ctl, BankStreamInDev *dev, uint32_t lane, uint32_t seen, unsigned long long idle_ticks, uint32_t &T) {
-    unsigned long long word[K];
-    uint32_t tag = seen;
-    bool fresh = false;
-    const unsigned long long wait_from = __builtin_amdgcn_s_memrealtime();
-    for (;;) {
-        static_for<0, K>([&](auto j) { word[j] = __hip_atomic_load(&ctl->rows[j][lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); });
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        tag = (uint32_t)(word[0] >> 32);
-        const uint32_t first = (uint32_t)__builtin_amdgcn_readfirstlane(tag);
-        bool same = tag != seen && tag == first;
-        static_for<1, K>([&](auto j) { same = same && (uint32_t)(word[j] >> 32) == first; });
-        fresh = __all(same);
-        if (fresh || __builtin_amdgcn_s_memrealtime() - wait_from > idle_ticks) break;
-    }
-    const uint32_t seq = fresh ? __builtin_amdgcn_readfirstlane(tag) : BANK_STREAM_STOP;
-    T = 0;
-    if (seq != BANK_STREAM_STOP) {
-        T = seq & 0xFFu;
-        T = T > 64u ? 64u : T;
-        static_for<0, K>([&](auto j) {
-            __hip_atomic_store(&dev->rows[j][lane], lane < T ? __uint_as_float((uint32_t)word[j]) : 0.0f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        });
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    return seq;
-}
-
+// bank_stream_bus_kernel with control rows (FR_STREAM_INPUTS, kernels.hpp BankStreamInCtl): a doorbell of n_rows rows, S_INPUT by row.
 __global__ void __launch_bounds__(1024) bank_stream_in_kernel(BankArgs a, StreamProgArgs p, uint32_t n_rows, BankStreamInCtl *ctl, BankStreamInDev *dev, uint32_t idle_ms) {
-    constexpr int NW = 16;
-    __shared__ float sm[NW][64];
+    __shared__ float sm[STREAM_NW][64];
     __shared__ float regs[STAGE_REGS][64];                   // the interpreter's registers: [register][lane] of wave 0
     __shared__ unsigned long long zshared;
     __shared__ uint32_t s_seq, s_T;
-    const uint32_t clog = a.log2_p - a.chunk_log2, nchunks = 1u << clog;
-    const uint32_t chunk = blockIdx.x & (nchunks - 1u);
-    const uint32_t voice = blockIdx.x >> clog;               // (the grid is exactly n_voices * nchunks workgroups)
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint32_t Pc = 1u << a.chunk_log2;
-    const uint32_t Pw = Pc / NW, ngroups = Pw >> 3;
-    uint32_t levels = 0;
-    while ((1u << levels) < ngroups) ++levels;
+    const StreamWork w = stream_work(a.params, a.rows, a.log2_p, a.chunk_log2, a.fast_ok, p.bank_to_ring, 0u, blockIdx.x, wave);   // (the grid is exactly n_voices * nchunks workgroups)
     const unsigned long long idle_ticks = (unsigned long long)idle_ms * 100000ull;
-    const float *mine = (const float *)(a.params + ((size_t)voice << a.log2_p) + (size_t)chunk * Pc + (size_t)wave * Pw);
-    const size_t vstride = (size_t)a.n_voices * 64u;
-    const uint64_t ring_cap = p.ring_mask + 1;
-    uint64_t head = p.head;                                  // first frame of the block being rendered (the same in every workgroup)
+    uint64_t head = p.head;
     uint32_t seen = 0;
     if (blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store(&ctl->alive, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     for (;;) {
-        // ---- wait for the next block (bounded), as bank_stream_kernel; the doorbell is n_rows rows ----
-        if (blockIdx.x == 0) {
-            if (wave == 0u) {
-                // (launch-uniform row count: one jump, then a loop whose every look is straight-line code)
-                uint32_t T = 0, seq;
-                switch (n_rows) {
-                case 1: seq = stream_in_wait<1>(ctl, dev, lane, seen, idle_ticks, T); break;
-                case 2: seq = stream_in_wait<2>(ctl, dev, lane, seen, idle_ticks, T); break;
-                case 3: seq = stream_in_wait<3>(ctl, dev, lane, seen, idle_ticks, T); break;
-                case 4: seq = stream_in_wait<4>(ctl, dev, lane, seen, idle_ticks, T); break;
-                case 5: seq = stream_in_wait<5>(ctl, dev, lane, seen, idle_ticks, T); break;
-                case 6: seq = stream_in_wait<6>(ctl, dev, lane, seen, idle_ticks, T); break;
-                case 7: seq = stream_in_wait<7>(ctl, dev, lane, seen, idle_ticks, T); break;
-                default: seq = stream_in_wait<8>(ctl, dev, lane, seen, idle_ticks, T); break;
-                }
-                if (lane == 0u) {
-                    __hip_atomic_store(&dev->n_times, T, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                    __hip_atomic_store(&dev->seq, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    s_seq = seq;
-                    s_T = T;
-                }
-            }
-        } else if (threadIdx.x == 0) {
-            uint32_t seq = seen;
-            const unsigned long long wait_from = __builtin_amdgcn_s_memrealtime();
-            for (;;) {
-                seq = __hip_atomic_load(&dev->seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (seq != seen || __builtin_amdgcn_s_memrealtime() - wait_from > 2ull * idle_ticks + 10000000ull) break;
-                __builtin_amdgcn_s_sleep(4);
-            }
-            if (seq == seen) seq = BANK_STREAM_STOP;
-            s_seq = seq;
-            s_T = __hip_atomic_load(&dev->n_times, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        __syncthreads();
-        const uint32_t seq = s_seq, T = s_T;
+        uint32_t T;
+        const uint32_t seq = stream_next_block(dev, wave, lane, seen, idle_ticks, s_seq, s_T, T, [&](uint32_t &T0) { return stream_rows_wait(n_rows, ctl, dev, lane, seen, idle_ticks, T0); });
         if (seq == BANK_STREAM_STOP) break;
         seen = seq;
-        {
-            // ---- one (voice, chunk) of one tile, as bank_stream_kernel ----
-            const bool live = lane < T;
-            ParamGroup first;
-            load_group(first, (const_f32_ptr)mine, 0);
-            const float t = live ? __hip_atomic_load(&dev->rows[0][lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0f;
-            const bool fast = a.fast_ok && __all(t >= 0.0f && t <= 4294967296.0f);
-            const float tt[1] = {t};
-            float r_wave[1];
-            if (fast) bank_wave_sum<1, true, false>(mine, ngroups, levels, tt, r_wave, &first);
-            else bank_wave_sum<1, false, false>(mine, ngroups, levels, tt, r_wave, &first);
-            sm[wave][lane] = r_wave[0];
-            __syncthreads();
-            float r = 0.0f;
-            if (wave == 0u) {
-                float s[NW];
-                static_for<0, NW>([&](auto w) { s[w] = sm[w][lane]; });
-                static_for<0, NW / 2>([&](auto i) { s[i] = s[2 * i] + s[2 * i + 1]; });
-                static_for<0, NW / 4>([&](auto i) { s[i] = s[2 * i] + s[2 * i + 1]; });
-                static_for<0, NW / 8>([&](auto i) { s[i] = s[2 * i] + s[2 * i + 1]; });
-                static_for<0, NW / 16>([&](auto i) { s[i] = s[2 * i] + s[2 * i + 1]; });
-                r = s[0];
-                const unsigned long long z = __ballot(live && r == 0.0f);
-                if (lane == 0u) zshared = z;
-            }
-            __syncthreads();
-            const unsigned long long zm = zshared;
-            if (zm != 0ull) {
-                const bool ok = fast ? wave_leaves_all_negzero<true>(mine, ngroups, t, zm) : wave_leaves_all_negzero<false>(mine, ngroups, t, zm);
-                sm[wave][lane] = ok ? 1.0f : 0.0f;
-                __syncthreads();
-                if (wave == 0u && ((zm >> lane) & 1ull)) {
-                    bool all = true;
-                    static_for<0, NW>([&](auto w) { all = all && sm[w][lane] != 0.0f; });
-                    r = all ? -0.0f : 0.0f;
-                }
-            }
-            if (wave == 0u) {
-                bool finished_voice = nchunks == 1u;
-                float result = r;
-                if (nchunks > 1u) {
-                    float *slot = a.ws + (size_t)voice * 64u;
-                    __hip_atomic_store(slot + (size_t)chunk * vstride + lane, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                    uint32_t old = 0u;
-                    if (lane == 0u) old = __hip_atomic_fetch_add(a.tickets + (size_t)voice * TICKET_STRIDE, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    old = __builtin_amdgcn_readfirstlane(old);
-                    if (old == nchunks - 1u) {
-                        finished_voice = true;
-                        float c0 = 0.0f, c1 = 0.0f, c2 = 0.0f, c3 = 0.0f, c4 = 0.0f, c5 = 0.0f, c6 = 0.0f, c7 = 0.0f, c8 = 0.0f;
-                        for (uint32_t c = 0; c < nchunks; ++c) {
-                            float v = c == chunk ? r : __hip_atomic_load(slot + (size_t)c * vstride + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            do {
-                                if (!(c & 1u)) { c0 = v; break; } v = c0 + v;
-                                if (!(c & 2u)) { c1 = v; break; } v = c1 + v;
-                                if (!(c & 4u)) { c2 = v; break; } v = c2 + v;
-                                if (!(c & 8u)) { c3 = v; break; } v = c3 + v;
-                                if (!(c & 16u)) { c4 = v; break; } v = c4 + v;
-                                if (!(c & 32u)) { c5 = v; break; } v = c5 + v;
-                                if (!(c & 64u)) { c6 = v; break; } v = c6 + v;
-                                if (!(c & 128u)) { c7 = v; break; } v = c7 + v;
-                                c8 = v;
-                            } while (0);
-                        }
-                        result = c8;
-                        result = clog == 7u ? c7 : result; result = clog == 6u ? c6 : result; result = clog == 5u ? c5 : result;
-                        result = clog == 4u ? c4 : result; result = clog == 3u ? c3 : result; result = clog == 2u ? c2 : result;
-                        result = clog == 1u ? c1 : result;
-                        if (lane == 0u) __hip_atomic_store(a.tickets + (size_t)voice * TICKET_STRIDE, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    }
-                }
-                if (finished_voice) {
-                    // ---- the voice's frames head + lane: to its ring (or its row), then its programs, lane = frame (as bank_stream_prog_kernel) ----
-                    const uint64_t frame = head + lane;
-                    const uint32_t dst = a.rows[voice];
-                    if (live) {
-                        if (p.bank_to_ring) __hip_atomic_store(p.rings + (size_t)dst * ring_cap + (frame & p.ring_mask), result, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        else __hip_atomic_store(a.out + (size_t)dst * 64u + lane, result, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                    }
-                    stream_in_run_programs(a, p, dev, regs, p.voice_first[voice], p.voice_first[voice + 1], frame, lane, live, t);
-                    // ring and row stores alike are acknowledged before the voice is counted in: the block's done tag then implies
-                    // that every ring store of the block has landed
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                    // the ticket goes to the whole wave: the last arriver of the block runs the bus programs, lane = frame
-                    uint32_t n = 0u;
-                    if (lane == 0u) n = __hip_atomic_fetch_add(&dev->voices_done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    n = __builtin_amdgcn_readfirstlane(n);
-                    if (n == a.n_voices - 1u) {
-                        // every voice's ring and row stores were acknowledged before its ticket, and this wave's loads are issued
-                        // after its own ticket came back: the hand-over of the chunk sums
-                        stream_in_run_programs(a, p, dev, regs, p.voice_first[a.n_voices], p.voice_first[a.n_voices + 1], frame, lane, live, t);
-                        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // host rows and rings have landed before the done tag
-                        if (lane == 0u) {
-                            __hip_atomic_store(&dev->voices_done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            __hip_atomic_store(&ctl->done, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                        }
-                    }
-                }
-            }
+        const bool live = lane < T;
+        float t, result;
+        const float r = stream_render_chunk(w, dev->rows[0], live, wave, lane, sm, zshared, t);
+        if (wave == 0u && stream_hand_over(w, a.ws, a.tickets, a.n_voices, lane, r, result)) {
+            const uint64_t frame = head + lane;
+            const StreamRowsInput input{dev, lane, t};
+            stream_voice_programs(w, a.out, p, regs, frame, lane, live, result, input);
+            stream_finish_bus(ctl, dev, a.n_voices, lane, seq,
+                              [&] { stream_run_programs(a.out, p, regs, p.voice_first[a.n_voices], p.voice_first[a.n_voices + 1], frame, lane, live, input); });
         }
         head += T;
         __syncthreads();   // LDS is reused by the next block
@@ -2191,33 +1845,22 @@ __global__ void __launch_bounds__(1024) bank_stream_in_kernel(BankArgs a, Stream
 
 hipError_t launch_bank_stream_in(const BankArgs &a, const StreamProgArgs &p, uint32_t n_rows, BankStreamInCtl *ctl_dev, BankStreamInDev *dev, uint32_t idle_ms,
                                  hipStream_t s) {
-    if (a.chunk_log2 < 7 || a.chunk_log2 > 13 || a.chunk_log2 > a.log2_p || a.log2_p - a.chunk_log2 > 8) return hipErrorInvalidValue;
-    if (((uint64_t)a.n_voices << (a.log2_p - a.chunk_log2)) > BANK_STREAM_WGS || a.n_voices == 0) return hipErrorInvalidValue;
-    if (a.chunk_log2 != a.log2_p && (!a.ws || !a.tickets)) return hipErrorInvalidValue;
-    if (a.leaf_variant != 1 || !a.out || !a.rows || !ctl_dev || !dev || !p.voice_first) return hipErrorInvalidValue;
-    if ((p.ring_mask & (p.ring_mask + 1)) != 0 || (p.n_rings && (!p.rings || p.ring_mask + 1 < 64u)) || (p.bank_to_ring && !p.n_rings)) return hipErrorInvalidValue;
+    if (!stream_bank_ok(a.log2_p, a.chunk_log2, a.n_voices, a.ws, a.tickets) || !stream_progs_ok(p, p.bank_to_ring != 0)) return hipErrorInvalidValue;
+    if (a.leaf_variant != 1 || !a.out || !a.rows || !ctl_dev || !dev) return hipErrorInvalidValue;
     if (n_rows == 0 || n_rows > BANK_STREAM_ROWS) return hipErrorInvalidValue;
     const uint32_t wgs = a.n_voices << (a.log2_p - a.chunk_log2);
     hipLaunchKernelGGL(bank_stream_in_kernel, dim3(wgs), dim3(1024), 0, s, a, p, n_rows, ctl_dev, dev, idle_ms ? idle_ms : BANK_STREAM_IDLE_MS);
     return hipGetLastError();
 }
 
-// ---------------------------------------------------------------------------------------------------
-// Block streaming of plans with several banks (FR_STREAM_BANKS, streamplan.hpp, kernels.hpp StreamBanksArgs): what
-// bank_stream_in_kernel does -- a doorbell of n_rows rows, per-voice programs in the wave that finishes a voice, the bus
-// segment in the block's last arriver -- for voices of 2..8 banks, each with its own partial count, chunk size, fast path and
-// destination kind.  What differs is how a workgroup finds its work: the bank table is a launch argument, the workgroup
-// compares its index with the banks' first workgroups (uniform, once, before the block loop) and keeps that bank's fields in
-// scalar registers.  Voices are numbered globally: chunk sums, tickets, voice_first and the voices_done count all go by that
-// number.  Every hand-over is bank_stream_in_kernel's: relaxed atomics, vmcnt(0) before each ticket, between programs and
-// before the done tag; no acquire or release, no new polling loop, and no workgroup waits for another one's result.  The
-// kernel has its own text and uses the control-row kernel's interpreter and wait as they are: the four older streaming
-// kernels' code does not change.
-// ---------------------------------------------------------------------------------------------------
+// bank_stream_in_kernel for voices of 2..8 banks (FR_STREAM_BANKS, kernels.hpp StreamBanksArgs), each with its own partial
+// count, chunk size, fast path and destination kind.  What differs is how a workgroup finds its work: the bank table is a
+// launch argument, the workgroup compares its index with the banks' first workgroups (uniform, once, before the block loop)
+// and keeps that bank's fields in scalar registers.  Voices are numbered globally: chunk sums, tickets, voice_first and the
+// voices_done count -- whichever bank the block's last arriver is of -- all go by that number.
 __global__ void __launch_bounds__(1024) bank_stream_banks_kernel(StreamBanksArgs t, BankArgs a, StreamProgArgs p, uint32_t n_rows, BankStreamInCtl *ctl,
                                                                  BankStreamInDev *dev, uint32_t idle_ms) {
-    constexpr int NW = 16;
-    __shared__ float sm[NW][64];
+    __shared__ float sm[STREAM_NW][64];
     __shared__ float regs[STAGE_REGS][64];                   // the interpreter's registers: [register][lane] of wave 0
     __shared__ unsigned long long zshared;
     __shared__ uint32_t s_seq, s_T;
@@ -2226,165 +1869,29 @@ __global__ void __launch_bounds__(1024) bank_stream_banks_kernel(StreamBanksArgs
     static_for<1, (int)BANK_STREAM_BANKS>([&](auto j) {
         if ((uint32_t)j < t.n_banks && blockIdx.x >= t.bank[j].first_wg) bk = t.bank[j];
     });
-    const uint32_t clog = bk.log2_p - bk.chunk_log2, nchunks = 1u << clog;
-    const uint32_t local = blockIdx.x - bk.first_wg;         // (the grid is exactly the sum of the banks' n_voices * nchunks workgroups)
-    const uint32_t chunk = local & (nchunks - 1u);
-    const uint32_t bank_voice = local >> clog;               // the voice inside its bank: its parameters and its destination
-    const uint32_t voice = bk.first_voice + bank_voice;      // the global voice: its chunk sums, ticket and programs
-    const uint32_t n_voices = a.n_voices;                    // of all banks
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint32_t Pc = 1u << bk.chunk_log2;
-    const uint32_t Pw = Pc / NW, ngroups = Pw >> 3;
-    uint32_t levels = 0;
-    while ((1u << levels) < ngroups) ++levels;
+    // (the grid is exactly the sum of the banks' n_voices * nchunks workgroups)
+    const StreamWork w = stream_work(bk.params, bk.rows, bk.log2_p, bk.chunk_log2, bk.fast_ok, bk.to_ring, bk.first_voice, blockIdx.x - bk.first_wg, wave);
+    const uint32_t n_voices = a.n_voices;                    // of all banks
     const unsigned long long idle_ticks = (unsigned long long)idle_ms * 100000ull;
-    const float *mine = (const float *)(bk.params + ((size_t)bank_voice << bk.log2_p) + (size_t)chunk * Pc + (size_t)wave * Pw);
-    const size_t vstride = (size_t)n_voices * 64u;
-    const uint64_t ring_cap = p.ring_mask + 1;
-    uint64_t head = p.head;                                  // first frame of the block being rendered (the same in every workgroup)
+    uint64_t head = p.head;
     uint32_t seen = 0;
     if (blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store(&ctl->alive, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     for (;;) {
-        // ---- wait for the next block (bounded), as bank_stream_in_kernel ----
-        if (blockIdx.x == 0) {
-            if (wave == 0u) {
-                uint32_t T = 0, seq;
-                switch (n_rows) {
-                case 1: seq = stream_in_wait<1>(ctl, dev, lane, seen, idle_ticks, T); break;
-                case 2: seq = stream_in_wait<2>(ctl, dev, lane, seen, idle_ticks, T); break;
-                case 3: seq = stream_in_wait<3>(ctl, dev, lane, seen, idle_ticks, T); break;
-                case 4: seq = stream_in_wait<4>(ctl, dev, lane, seen, idle_ticks, T); break;
-                case 5: seq = stream_in_wait<5>(ctl, dev, lane, seen, idle_ticks, T); break;
-                case 6: seq = stream_in_wait<6>(ctl, dev, lane, seen, idle_ticks, T); break;
-                case 7: seq = stream_in_wait<7>(ctl, dev, lane, seen, idle_ticks, T); break;
-                default: seq = stream_in_wait<8>(ctl, dev, lane, seen, idle_ticks, T); break;
-                }
-                if (lane == 0u) {
-                    __hip_atomic_store(&dev->n_times, T, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                    __hip_atomic_store(&dev->seq, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    s_seq = seq;
-                    s_T = T;
-                }
-            }
-        } else if (threadIdx.x == 0) {
-            uint32_t seq = seen;
-            const unsigned long long wait_from = __builtin_amdgcn_s_memrealtime();
-            for (;;) {
-                seq = __hip_atomic_load(&dev->seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (seq != seen || __builtin_amdgcn_s_memrealtime() - wait_from > 2ull * idle_ticks + 10000000ull) break;
-                __builtin_amdgcn_s_sleep(4);
-            }
-            if (seq == seen) seq = BANK_STREAM_STOP;
-            s_seq = seq;
-            s_T = __hip_atomic_load(&dev->n_times, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        __syncthreads();
-        const uint32_t seq = s_seq, T = s_T;
+        uint32_t T;
+        const uint32_t seq = stream_next_block(dev, wave, lane, seen, idle_ticks, s_seq, s_T, T, [&](uint32_t &T0) { return stream_rows_wait(n_rows, ctl, dev, lane, seen, idle_ticks, T0); });
         if (seq == BANK_STREAM_STOP) break;
         seen = seq;
-        {
-            // ---- one (voice, chunk) of one tile, as bank_stream_kernel, at this bank's chunk size ----
-            const bool live = lane < T;
-            ParamGroup first;
-            load_group(first, (const_f32_ptr)mine, 0);
-            const float t_in = live ? __hip_atomic_load(&dev->rows[0][lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0f;
-            const bool fast = bk.fast_ok && __all(t_in >= 0.0f && t_in <= 4294967296.0f);
-            const float tt[1] = {t_in};
-            float r_wave[1];
-            if (fast) bank_wave_sum<1, true, false>(mine, ngroups, levels, tt, r_wave, &first);
-            else bank_wave_sum<1, false, false>(mine, ngroups, levels, tt, r_wave, &first);
-            sm[wave][lane] = r_wave[0];
-            __syncthreads();
-            float r = 0.0f;
-            if (wave == 0u) {
-                float s[NW];
-                static_for<0, NW>([&](auto w) { s[w] = sm[w][lane]; });
-                static_for<0, NW / 2>([&](auto i) { s[i] = s[2 * i] + s[2 * i + 1]; });
-                static_for<0, NW / 4>([&](auto i) { s[i] = s[2 * i] + s[2 * i + 1]; });
-                static_for<0, NW / 8>([&](auto i) { s[i] = s[2 * i] + s[2 * i + 1]; });
-                static_for<0, NW / 16>([&](auto i) { s[i] = s[2 * i] + s[2 * i + 1]; });
-                r = s[0];
-                const unsigned long long z = __ballot(live && r == 0.0f);
-                if (lane == 0u) zshared = z;
-            }
-            __syncthreads();
-            const unsigned long long zm = zshared;
-            if (zm != 0ull) {
-                const bool ok = fast ? wave_leaves_all_negzero<true>(mine, ngroups, t_in, zm) : wave_leaves_all_negzero<false>(mine, ngroups, t_in, zm);
-                sm[wave][lane] = ok ? 1.0f : 0.0f;
-                __syncthreads();
-                if (wave == 0u && ((zm >> lane) & 1ull)) {
-                    bool all = true;
-                    static_for<0, NW>([&](auto w) { all = all && sm[w][lane] != 0.0f; });
-                    r = all ? -0.0f : 0.0f;
-                }
-            }
-            if (wave == 0u) {
-                bool finished_voice = nchunks == 1u;
-                float result = r;
-                if (nchunks > 1u) {
-                    // the chunk sums of all banks share one workspace, laid out by global voice
-                    float *slot = a.ws + (size_t)voice * 64u;
-                    __hip_atomic_store(slot + (size_t)chunk * vstride + lane, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                    uint32_t old = 0u;
-                    if (lane == 0u) old = __hip_atomic_fetch_add(a.tickets + (size_t)voice * TICKET_STRIDE, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    old = __builtin_amdgcn_readfirstlane(old);
-                    if (old == nchunks - 1u) {
-                        finished_voice = true;
-                        float c0 = 0.0f, c1 = 0.0f, c2 = 0.0f, c3 = 0.0f, c4 = 0.0f, c5 = 0.0f, c6 = 0.0f, c7 = 0.0f, c8 = 0.0f;
-                        for (uint32_t c = 0; c < nchunks; ++c) {
-                            float v = c == chunk ? r : __hip_atomic_load(slot + (size_t)c * vstride + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            do {
-                                if (!(c & 1u)) { c0 = v; break; } v = c0 + v;
-                                if (!(c & 2u)) { c1 = v; break; } v = c1 + v;
-                                if (!(c & 4u)) { c2 = v; break; } v = c2 + v;
-                                if (!(c & 8u)) { c3 = v; break; } v = c3 + v;
-                                if (!(c & 16u)) { c4 = v; break; } v = c4 + v;
-                                if (!(c & 32u)) { c5 = v; break; } v = c5 + v;
-                                if (!(c & 64u)) { c6 = v; break; } v = c6 + v;
-                                if (!(c & 128u)) { c7 = v; break; } v = c7 + v;
-                                c8 = v;
-                            } while (0);
-                        }
-                        // (the ladder's top is this bank's: its voices have 1 << clog chunks)
-                        result = c8;
-                        result = clog == 7u ? c7 : result; result = clog == 6u ? c6 : result; result = clog == 5u ? c5 : result;
-                        result = clog == 4u ? c4 : result; result = clog == 3u ? c3 : result; result = clog == 2u ? c2 : result;
-                        result = clog == 1u ? c1 : result;
-                        if (lane == 0u) __hip_atomic_store(a.tickets + (size_t)voice * TICKET_STRIDE, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    }
-                }
-                if (finished_voice) {
-                    // ---- the voice's frames head + lane: to its ring or its row, as its bank says; then its programs, lane = frame ----
-                    const uint64_t frame = head + lane;
-                    const uint32_t dst = bk.rows[bank_voice];
-                    if (live) {
-                        if (bk.to_ring) __hip_atomic_store(p.rings + (size_t)dst * ring_cap + (frame & p.ring_mask), result, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        else __hip_atomic_store(a.out + (size_t)dst * 64u + lane, result, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                    }
-                    stream_in_run_programs(a, p, dev, regs, p.voice_first[voice], p.voice_first[voice + 1], frame, lane, live, t_in);
-                    // ring and row stores alike are acknowledged before the voice is counted in: the block's done tag then implies
-                    // that every ring store of the block has landed
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                    // the ticket goes to the whole wave: the last arriver of the block, whichever bank it is of, runs the bus programs
-                    uint32_t n = 0u;
-                    if (lane == 0u) n = __hip_atomic_fetch_add(&dev->voices_done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    n = __builtin_amdgcn_readfirstlane(n);
-                    if (n == n_voices - 1u) {
-                        // every voice's ring and row stores were acknowledged before its ticket, and this wave's loads are issued
-                        // after its own ticket came back
-                        stream_in_run_programs(a, p, dev, regs, p.voice_first[n_voices], p.voice_first[n_voices + 1], frame, lane, live, t_in);
-                        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // host rows and rings have landed before the done tag
-                        if (lane == 0u) {
-                            __hip_atomic_store(&dev->voices_done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            __hip_atomic_store(&ctl->done, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                        }
-                    }
-                }
-            }
+        const bool live = lane < T;
+        float t_in, result;
+        const float r = stream_render_chunk(w, dev->rows[0], live, wave, lane, sm, zshared, t_in);
+        if (wave == 0u && stream_hand_over(w, a.ws, a.tickets, n_voices, lane, r, result)) {
+            const uint64_t frame = head + lane;
+            const StreamRowsInput input{dev, lane, t_in};
+            stream_voice_programs(w, a.out, p, regs, frame, lane, live, result, input);
+            stream_finish_bus(ctl, dev, n_voices, lane, seq,
+                              [&] { stream_run_programs(a.out, p, regs, p.voice_first[n_voices], p.voice_first[n_voices + 1], frame, lane, live, input); });
         }
         head += T;
         __syncthreads();   // LDS is reused by the next block
@@ -2395,24 +1902,20 @@ __global__ void __launch_bounds__(1024) bank_stream_banks_kernel(StreamBanksArgs
 hipError_t launch_bank_stream_banks(const StreamBanksArgs &t, const BankArgs &a, const StreamProgArgs &p, uint32_t n_rows, BankStreamInCtl *ctl_dev, BankStreamInDev *dev,
                                     uint32_t idle_ms, hipStream_t s) {
     if (t.n_banks == 0 || t.n_banks > BANK_STREAM_BANKS) return hipErrorInvalidValue;
-    // every bank as launch_bank_stream_in validates its one; the banks' workgroups and voices follow one another without a gap
+    // every bank as the one-bank launchers check theirs; the banks' workgroups and voices follow one another without a gap
     uint64_t wgs = 0, voices = 0;
-    bool chunked = false, to_ring = false;
+    bool to_ring = false;
     for (uint32_t i = 0; i < t.n_banks; ++i) {
         const StreamBanksArgs::Bank &b = t.bank[i];
-        if (b.chunk_log2 < 7 || b.chunk_log2 > 13 || b.chunk_log2 > b.log2_p || b.log2_p - b.chunk_log2 > 8) return hipErrorInvalidValue;
-        if (b.n_voices == 0 || b.n_voices > BANK_STREAM_WGS || !b.params || !b.rows) return hipErrorInvalidValue;
+        if (!stream_bank_ok(b.log2_p, b.chunk_log2, b.n_voices, a.ws, a.tickets) || !b.params || !b.rows) return hipErrorInvalidValue;
         if (b.first_wg != wgs || b.first_voice != voices) return hipErrorInvalidValue;
         wgs += (uint64_t)b.n_voices << (b.log2_p - b.chunk_log2);
         voices += b.n_voices;
         if (wgs > BANK_STREAM_WGS) return hipErrorInvalidValue;   // all workgroups must be resident
-        chunked = chunked || b.chunk_log2 != b.log2_p;
         to_ring = to_ring || b.to_ring != 0;
     }
-    if (voices != a.n_voices) return hipErrorInvalidValue;
-    if (chunked && (!a.ws || !a.tickets)) return hipErrorInvalidValue;
-    if (a.leaf_variant != 1 || !a.out || !ctl_dev || !dev || !p.voice_first) return hipErrorInvalidValue;
-    if ((p.ring_mask & (p.ring_mask + 1)) != 0 || (p.n_rings && (!p.rings || p.ring_mask + 1 < 64u)) || (to_ring && !p.n_rings)) return hipErrorInvalidValue;
+    if (voices != a.n_voices || !stream_progs_ok(p, to_ring)) return hipErrorInvalidValue;
+    if (a.leaf_variant != 1 || !a.out || !ctl_dev || !dev) return hipErrorInvalidValue;
     if (n_rows == 0 || n_rows > BANK_STREAM_ROWS) return hipErrorInvalidValue;
     hipLaunchKernelGGL(bank_stream_banks_kernel, dim3((uint32_t)wgs), dim3(1024), 0, s, t, a, p, n_rows, ctl_dev, dev, idle_ms ? idle_ms : BANK_STREAM_IDLE_MS);
     return hipGetLastError();

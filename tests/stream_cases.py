@@ -103,6 +103,32 @@ def block_rows(rng, starts):
     return rows
 
 
+def silence_voice(tree, V, P, v):
+    """The tree with every amplitude of voice v of its bank of V voices x P partials (synth.voice_params: amp = 1 / (k + 1))
+    replaced by +0.0: every leaf of the voice is +-0, every chunk sum of it is an exact zero, and the kernel has to find the
+    zero's sign from the leaves.  The amplitudes are the one batch of V * P constant edges into slot 0 of consecutive nodes
+    that holds exactly these values."""
+    want = synth.bits(np.tile(synth.voice_params(V, P, 0)["amp"][0], V))
+    e = tree["edges"].copy()
+    n = V * P
+    const = (e[:, 0] == synth.CONST_HANDLE) & (e[:, 3] == 0)
+    follows = np.concatenate([[False], const[1:] & const[:-1] & (e[1:, 1] == e[:-1, 1] + 1)])   # edge i continues edge i - 1's batch
+    for i in np.nonzero(const & ~follows)[0]:                                                   # where a batch begins
+        if i + n <= len(e) and follows[i + 1:i + n].all() and not (i + n < len(e) and follows[i + n]) and np.array_equal(e[i:i + n, 2], want):
+            e[i + v * P:i + (v + 1) * P, 2] = 0
+            return dict(tree, edges=e)
+    raise ValueError(f"no bank of {V} x {P} amplitudes in this tree")
+
+
+def short_blocks(idx=200, lengths=(64, 1, 37)):
+    """[(idx, row)]: a full block, a block of one frame and a last block shorter than 64 frames, one after the other."""
+    rows = []
+    for T in lengths:
+        rows.append((idx, synth.time_ramp(idx, idx + T)))
+        idx += T
+    return rows
+
+
 def same_bits(a, b):
     a, b = np.asarray(a, np.float32), np.asarray(b, np.float32)
     return a.shape == b.shape and bool(np.all((a.view(np.uint32) == b.view(np.uint32)) | (np.isnan(a) & np.isnan(b))))

@@ -207,3 +207,25 @@ def test_one_bank_keeps_its_kernel(hip_lib):
     got, plan = B.stream_against_fill_buffer(hip_lib, B.mixdown_tree(2, 1024, 1), 1, rows, options=M.STREAM_OPTIONS)
     s = plan["stream"]
     assert s["kernel"] == "bank_stream_bus_kernel" and len(s["banks"]) == 1 and s["workgroups"] == 16
+
+
+@pytest.mark.parametrize("silent", [(1, 128, 0), (2, 256, 1)])
+def test_a_silent_voice_in_short_blocks(hip_lib, silent):
+    """A bank of one voice of 128 partials (one chunk, one group of 8 partials per wave) next to a bank of two voices of 256 in
+    chunks of 128; a full block, a block of one frame and a last block of 37; one voice silent -- the one-chunk voice, then a
+    chunked one: its chunk sums are exact zeros, whose sign the kernel finds from the leaves."""
+    import stream_cases as K
+    V, P, v = silent
+    tree = K.silence_voice(M.rows_tree([(1, 128), (2, 256)]), V, P, v)
+    row = 0 if P == 128 else 1 + v
+    blocks = [(idx, len(t), [t]) for idx, t in K.short_blocks()]
+    with Renderer(hip_lib, options=M.STREAM_OPTIONS) as s:
+        synth.install(s, tree)
+        s.stream_begin(3)
+        got = [call(lambda: s.stream_block(idx, rows[0])) for idx, T, rows in blocks]
+        st = s.plan()["stream"]
+        s.stream_end()
+    assert st["servable"] and st["kernel"] == M.NEW_KERNEL and sorted((b["voices"], b["partials"], b["chunks"]) for b in st["banks"]) == [(1, 128, 1), (2, 256, 2)], st
+    compare(got, fill_all(hip_lib, tree, 3, blocks), blocks, "through fr_fill_buffer")
+    assert [a.shape for _, a in got] == [(3, 64), (3, 1), (3, 37)]
+    assert not any(a[row].any() for _, a in got) and loud(got) > 0.01

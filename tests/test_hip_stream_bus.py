@@ -166,3 +166,17 @@ def test_a_plan_without_a_bus_keeps_its_kernel(hip_lib):
     rows = K.block_rows(np.random.default_rng(2), [(50, 400)])
     got, plan = B.stream_against_fill_buffer(hip_lib, tree, V, rows)
     assert plan["stream"]["kernel"] == "bank_stream_prog_kernel" and plan["stream"]["bus_programs"] == 0
+
+
+@pytest.mark.parametrize("P,wgs", [(128, 2), (256, 4)])
+def test_a_silent_voice_in_short_blocks(hip_lib, P, wgs):
+    """Two voices (a bus has at least two) of one chunk and of two chunks each; a full block, a block of one frame and a last
+    block of 37; voice 1 silent: its chunk sums are exact zeros, whose sign the kernel finds from the leaves.  Rows 0 and 1 are
+    the voices, row 2 their mix."""
+    V = 2
+    tree = K.silence_voice(B.rows_and_bus_tree(V, P), V, P, 1)
+    got, plan = B.stream_against_fill_buffer(hip_lib, tree, V + 1, K.short_blocks())
+    s = plan["stream"]
+    assert s["servable"] and s["kernel"] == "bank_stream_bus_kernel" and s["bus_programs"] == 1 and s["voices"] * s["chunks"] == wgs, s
+    assert [a.shape for _, a in got] == [(V + 1, 64), (V + 1, 1), (V + 1, 37)]
+    assert not any(a[1].any() for _, a in got) and max(np.abs(a[2]).max() for _, a in got) > 0.01

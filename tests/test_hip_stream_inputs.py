@@ -167,3 +167,18 @@ def test_a_plan_that_reads_slot_0_only_keeps_its_kernel(hip_lib):
     got, plan = B.stream_against_fill_buffer(hip_lib, build(), V, rows, options=I.STREAM_OPTIONS)
     s = plan["stream"]
     assert s["kernel"] == "bank_stream_prog_kernel" and s["input_slots"] == [0] and s["programs_per_voice"] == [per_voice] * V
+
+
+@pytest.mark.parametrize("V,P,wgs", [(1, 128, 1), (2, 256, 4)])
+def test_a_silent_voice_in_short_blocks(hip_lib, V, P, wgs):
+    """One voice of one chunk (one group of 8 partials per wave) and two voices of two chunks each; a full block, a block of
+    one frame and a last block of 37; the last voice silent: its chunk sums are exact zeros, whose sign the kernel finds from
+    the leaves.  Row v = voice v x its gain row."""
+    tree = K.silence_voice(I.gain_tree(V, P), V, P, V - 1)
+    rng = np.random.default_rng(V)
+    blocks = [(idx, len(t), [t] + [rng.uniform(0.5, 1.5, size=len(t)).astype(np.float32) for _ in range(V)]) for idx, t in K.short_blocks()]
+    got, plan = stream_rows_against_fill_buffer(hip_lib, tree, V, blocks)
+    s = plan["stream"]
+    assert s["servable"] and s["kernel"] == I.NEW_KERNEL and s["voices"] * s["chunks"] == wgs, s
+    assert [st for st, _ in got] == [FR_OK] * 3 and [a.shape for _, a in got] == [(V, 64), (V, 1), (V, 37)]
+    assert not any(a[V - 1].any() for _, a in got) and (V == 1 or loud(got) > 0.01)

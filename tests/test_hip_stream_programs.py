@@ -186,3 +186,22 @@ def test_a_bare_bank_streams_through_the_old_kernel(hip_lib, oracle_lib):
         for idx, row in K.block_rows(rng, [(0, 600)]):
             assert same_bits(s.stream_block(idx, row), ref.fill_buffer(V, idx, idx + len(row), [row]))
         assert s.plan()["stream"]["kernel"] == "bank_stream_kernel"
+
+
+# The smallest shapes that reach every step of the resident kernels: one voice of 128 partials (one chunk per voice, one group of
+# 8 partials per wave) and two voices of 256 in chunks of 128 (the voice's finisher is whichever chunk arrives last); a full
+# block, a block of one frame and a last block of 37; the last voice silent, so that its chunk sums are exact zeros and the
+# pass that finds a zero's sign from the leaves runs.  (voices, partials, workgroups)
+ZERO_SUM = [(1, 128, 1), (2, 256, 4)]
+
+
+@pytest.mark.parametrize("V,P,wgs", ZERO_SUM)
+@pytest.mark.parametrize("kernel", ["bank_stream_kernel", "bank_stream_prog_kernel"])
+def test_a_silent_voice_in_short_blocks(hip_lib, kernel, V, P, wgs):
+    tree = synth.additive_tree(V, P) if kernel == "bank_stream_kernel" else synth.effects_tree(V, P, taps=1, base_delay=100.0)
+    got, plan = K.stream_against_fill_buffer(hip_lib, K.silence_voice(tree, V, P, V - 1), V, K.short_blocks())
+    s = plan["stream"]
+    assert s["servable"] and s["kernel"] == kernel and s["voices"] * s["chunks"] == wgs, s
+    assert [a.shape for _, a in got] == [(V, 64), (V, 1), (V, 37)]
+    assert not any(a[V - 1].any() for _, a in got)                         # the silent voice: zeros of either sign
+    assert V == 1 or max(np.abs(a[0]).max() for _, a in got) > 0.01
