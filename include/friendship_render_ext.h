@@ -76,6 +76,17 @@ extern "C" {
  * programs_per_voice runs over the voices bank by bank, and "kernel" is "bank_stream_banks_kernel" exactly when the plan has
  * more than one bank.  Still refused: more than 8 banks, more voices in total than workgroups, and for every bank what is
  * refused for one: general, compiled and track voices, voices under 128 partials, voices whose time is not slot 0.
+ *
+ * FR_LOOP_TILES = 0 / 1 (default 0; read strictly from the environment too): loop tiles.  Feedback through a Delay of at most
+ * 16 frames ("max_stride" below) -- a one-pole filter, a DC blocker, a short comb -- is rendered by launches whose threads walk the frames of the
+ * call in order; with the option, one wave per loop renders the call in tiles of up to 256 frames: all 64 lanes fetch the
+ * tile's inputs into on-chip memory, one lane per residue of the stride computes the frames from there, all lanes store the
+ * tile.  The steady call, the replay after a seek and the replay of FR_RING_KEEP take this form.  Results are the same bits.
+ * The stride of a feedback plan becomes the gcd of its loops' own delays (a later stage's read of a loop's output at another
+ * delay no longer shortens it).  fr_plan_json gains "loop_tiles" {frames, max_stride, reason} -- frames per tile, 0 with the
+ * reason when the plan is not tiled: a stride above max_stride, a loop that reads its own ring further back than one stride
+ * (taps at d and 2d), a program of more than 16 frame-only loads or 12 stores, a Delay of a signal amount -- the tiled
+ * launches' "variant" carries +tile, and "stage_jit_form" gains "tile".  With the option unset nothing changes.
  */
 typedef struct fr_option {
     const char *name;              /* e.g. "FR_BANK_SHORT" */

@@ -135,4 +135,58 @@ inline StageForm stage_form(const StagedPlan &sp, const CallIn &c, const CallWin
     return f;
 }
 
+// Loop tiles (FR_LOOP_TILES): the strided launches of a feedback plan -- the steady call, the replay after a seek, the replay
+// of kept rings -- run one wave per program that renders the window in tiles of `frames` frames: all 64 lanes fetch the
+// tile's frame-only loads into LDS, lanes < stride walk their residue's frames on LDS operands and the carry, all 64 lanes
+// store the tile (kernels.hip stage_tile_kernel, stagejit.cpp jit_stage_tile).  frames = stride * floor(256 / stride): a
+// multiple of the stride, so lane r always owns residue r.  A plan is tiled when the option is on, it has feedback, every
+// loop reads its own rings through the carry only, 1 <= stride <= LOOP_TILE_MAX_STRIDE, and
+// every fused program has no Delay of a signal amount, at most LOOP_TILE_LOADS frame-only loads (S_INPUT, S_READ_INPUT, S_READ
+// of a ring it does not store) and at most LOOP_TILE_STORES stores (S_STOREs, dst_ring, out_row).  Otherwise frames = 0 and
+// `reason` names the first condition that failed ("" for a plan without feedback: the option does not concern it).
+// LOOP_TILE_MAX_STRIDE: the kernels take strides up to 64 (a lane per residue); the rule stops where the tiled form measured faster
+// than the untiled one by more than the untiled rounds' spread in BOTH evaluators (profiles/loop_tiles.txt: compiled programs win
+// at d = 1, 2, 8, 16 and lose at 32 and 64 -- a wave whose 32 lanes each walk 8 frames per tile pays the tile's three phases for
+// little serial work --, the interpreter wins up to 32 and ties at 64; 17..31 were not measured).
+constexpr uint32_t LOOP_TILE_FRAMES = 256, LOOP_TILE_MAX_STRIDE = 16, LOOP_TILE_LOADS = 16, LOOP_TILE_STORES = 12;
+struct LoopTile {
+    uint32_t frames = 0;
+    std::string reason;
+};
+inline LoopTile loop_tile(const StagedPlan &sp, bool enabled) {
+    LoopTile lt;
+    if (!sp.feedback) return lt;
+    if (!enabled) { lt.reason = "FR_LOOP_TILES is off"; return lt; }
+    if (sp.fused_stride < 1 || sp.fused_stride > LOOP_TILE_MAX_STRIDE) {
+        lt.reason = "the loops' stride is " + std::to_string(sp.fused_stride) + " frames (1.." + std::to_string(LOOP_TILE_MAX_STRIDE) + " are tiled)";
+        return lt;
+    }
+    if (!sp.fused_carry_only) { lt.reason = "a loop reads its own ring further back than one stride"; return lt; }
+    for (uint32_t p = sp.fused_first; p < sp.fused_first + sp.fused_count && p < sp.progs.size(); ++p) {
+        const StageProg &pg = sp.progs[p];
+        uint32_t loads = 0, stores = (pg.dst_ring != 0xFFFFFFFFu ? 1u : 0u) + (pg.out_row >= 0 ? 1u : 0u);
+        for (uint32_t i = 0; i < pg.n_instr && pg.first_instr + i < sp.instrs.size(); ++i) {
+            const StageInstr &in = sp.instrs[pg.first_instr + i];
+            if (in.op == S_READ_DYN || in.op == S_READ_INPUT_DYN || in.op == S_STEP_DYN) {
+                lt.reason = "fused program " + std::to_string(p - sp.fused_first) + " delays by a signal amount";
+                return lt;
+            }
+            loads += in.op == S_INPUT || in.op == S_READ_INPUT || (in.op == S_READ && in.imm == 0) ? 1u : 0u;
+            stores += in.op == S_STORE ? 1u : 0u;
+        }
+        if (loads > LOOP_TILE_LOADS) {
+            lt.reason = "fused program " + std::to_string(p - sp.fused_first) + " has " + std::to_string(loads) + " frame-only loads (at most " +
+                        std::to_string(LOOP_TILE_LOADS) + " are tiled)";
+            return lt;
+        }
+        if (stores > LOOP_TILE_STORES) {
+            lt.reason = "fused program " + std::to_string(p - sp.fused_first) + " has " + std::to_string(stores) + " stores (at most " +
+                        std::to_string(LOOP_TILE_STORES) + " are tiled)";
+            return lt;
+        }
+    }
+    lt.frames = (uint32_t)(sp.fused_stride * (LOOP_TILE_FRAMES / sp.fused_stride));
+    return lt;
+}
+
 }  // namespace fr

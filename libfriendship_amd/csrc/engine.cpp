@@ -131,6 +131,7 @@ struct Plan {
     std::vector<uint32_t> input_slots;   // dense input index -> external slot
     const FlatGraph *graph = nullptr;    // the lowered graph the plan was made from (Lowering::update: stable)
     bool observed_stale = false;         // FR_DELAY_OBSERVED: stored rows widened an input range past a planned look-back
+    LoopTile loop_tile;                  // FR_LOOP_TILES (callplan.hpp loop_tile): frames per tile of the strided launches, 0: not tiled
     std::string json;
 };
 
@@ -152,15 +153,17 @@ struct StageLaunchNote {
     uint64_t frames, stride;
     bool carry, carry_only, table;       // use_carry (stage_kernel's LDS carry), carry_only, input table in device memory
     uint32_t grid_parts;                 // launches of at most 65535 programs (grid.y) it was cut into
+    bool tile = false;                   // FR_LOOP_TILES: stage_tile_kernel / jit_stage_tile
 };
 
 // fr_plan_json "stage_jit_form": the #defines plan_stage_jit wrote for the plan's compiled programs, null when interpreted.
-static std::string stage_jit_form_json(const Plan &p) {
+// `with_tile` (FR_LOOP_TILES was given): and "tile", the frames per tile its jit_stage_tile was generated for (0: it has none).
+static std::string stage_jit_form_json(const Plan &p, bool with_tile) {
     if (!p.stage_jit) return "null";
     const StageJitPlan &f = p.stage_jit_form;
     return std::string("{\"deep\":") + (f.deep ? "true" : "false") + ",\"maxp\":" + std::to_string(f.maxp) + ",\"maxld\":" + std::to_string(f.maxld) +
            ",\"maxst\":" + std::to_string(f.maxst) + ",\"defer\":" + (f.defer ? "true" : "false") + ",\"blk\":" + std::to_string(f.blk) +
-           ",\"shapes\":" + std::to_string(p.stage_shapes) + "}";
+           ",\"shapes\":" + std::to_string(p.stage_shapes) + (with_tile ? ",\"tile\":" + std::to_string(f.tile) : std::string()) + "}";
 }
 
 // fr_plan_json "stage_hoisted_max": the most loads any program issues back to back before its other instructions (StageProg
@@ -175,22 +178,26 @@ static uint32_t stage_hoisted_max(const StagedPlan &sp) {
 // [plain|deep, P (MAXP > 0), defer, B<BLK>] -- then the launch form and the paths the launch's arguments select:
 // +carry / +carry_only (stage_kernel: use_carry, the LDS carry; jit_stage keeps it in registers whenever it strides),
 // +table (more than STAGE_INLINE_INPUTS input slots: the table in device memory), +grid<N> (cut into N launches of at most
-// 65535 programs).  tests/stage_variants.py has a GPU case for each key the rule produces.
+// 65535 programs).  tests/stage_variants.py has a GPU case for each key the rule produces.  A tiled launch (FR_LOOP_TILES) is
+// jit_stage[tile] / jit_stage[tile,P] -- jit_stage_tile has no block and defers every store -- or stage_kernel, and carries +tile
+// after the carry flag (tests/loop_tile_cases.py).
 static std::string stage_variant(const StageLaunchNote &n, const Plan &p) {
     std::string k = "stage_kernel";
-    if (n.jit) {
+    if (n.jit && n.tile) k = std::string("jit_stage[tile") + (p.stage_jit_form.maxp ? ",P" : "") + "]";
+    else if (n.jit) {
         const StageJitPlan &f = p.stage_jit_form;
         k = std::string("jit_stage[") + (f.deep ? "deep" : "plain") + (f.maxp ? ",P" : "") + (f.defer ? ",defer" : "") + ",B" + std::to_string(f.blk) + "]";
     }
     k += std::string("/") + n.form;
     if (n.carry_only) k += "+carry_only";
     else if (n.carry) k += "+carry";
+    if (n.tile) k += "+tile";
     if (n.table) k += "+table";
     if (n.grid_parts > 1) k += "+grid" + std::to_string(n.grid_parts);
     return k;
 }
 
-constexpr size_t N_OPTIONS = 34;         // per-renderer options (friendship_render_ext.h; the table below fr_renderer)
+constexpr size_t N_OPTIONS = 35;         // per-renderer options (friendship_render_ext.h; the table below fr_renderer)
 
 struct TimerClass {
     double ms = 0;
@@ -621,6 +628,9 @@ struct fr_renderer {
     // re-plan keeps the rings of the new plan it finds here with enough frames for their look-back, moves them to their new
     // rows (ring_move_kernel) and brings only the others up to idx before it runs as a steady call.
     bool ring_keep = false;
+    // Loop tiles (FR_LOOP_TILES, callplan.hpp loop_tile): the strided launches of feedback plans of short strides render tiles
+    // staged in LDS.  `loop_tiles_given`: the option was set (either way): fr_plan_json then shows "loop_tiles".
+    bool loop_tiles = false, loop_tiles_given = false;
     struct RingEntry { uint64_t generation; std::vector<uint32_t> key; uint64_t valid_from; };
     struct RingTable {
         bool valid = false;
@@ -1376,7 +1386,7 @@ struct fr_renderer {
         p.graph = &fg;
         const ObservedInputs obs = observed_inputs(st);
         const ObservedInputs *observed = delay_observed ? &obs : nullptr;
-        p.sp = plan_stages(fg, mode == FR_MODE_AUTO, mode != FR_MODE_PULL, 20, use_jit, allow_template, matcher.get(), shard_spec, track_from, observed, track_history);
+        p.sp = plan_stages(fg, mode == FR_MODE_AUTO, mode != FR_MODE_PULL, 20, use_jit, allow_template, matcher.get(), shard_spec, track_from, observed, track_history, loop_tiles);
         renumber_rings(p.sp);
         std::vector<std::shared_ptr<JitKernel>> jits(p.sp.banks.size());
         p.jit_epoch = jit_cache.epoch();   // (read first: a compile finishing from here on makes this plan stale)
@@ -1403,7 +1413,7 @@ struct fr_renderer {
                     throw Error(FR_ERR_DEVICE, std::string("a kernel of the sharded plan could not be compiled on this rank (every rank must plan alike): ") + e.what());
             }
             if (without) {
-                p.sp = plan_stages(fg, true, true, 20, false, true, nullptr, shard_spec, track_from, observed, track_history);
+                p.sp = plan_stages(fg, true, true, 20, false, true, nullptr, shard_spec, track_from, observed, track_history, loop_tiles);
                 renumber_rings(p.sp);
                 jits.assign(p.sp.banks.size(), nullptr);
             }
@@ -1439,9 +1449,10 @@ struct fr_renderer {
             HIP_CHECK(hipMemcpyAsync(p.d_instrs.p, p.sp.instrs.data(), p.sp.instrs.size() * sizeof(StageInstr), hipMemcpyHostToDevice, st));
             HIP_CHECK(hipMemcpyAsync(p.d_progs.p, p.sp.progs.data(), p.sp.progs.size() * sizeof(StageProg), hipMemcpyHostToDevice, st));
             StageJitPlan sj;
+            p.loop_tile = loop_tile(p.sp, loop_tiles);
             if (allow_jit && stage_jit_mode != 0 && plan_stage_jit(p.sp.progs, p.sp.instrs, 32, stage_jit_mode == 2, sj, mirror.sparkle,
                                                                               stage_block_env ? stage_block_env : (p.sp.feedback ? 16u : 1u),
-                                                                              p.sp.feedback && p.sp.fused_carry_only)) {
+                                                                              p.sp.feedback && p.sp.fused_carry_only, p.loop_tile.frames)) {
                 try {
                     p.stage_jit = jit_cache.get_source(sj.source, "jit_stage");
                     if (!p.stage_jit) {   // still compiling: the interpreter serves the calls until the plan is rebuilt
@@ -1455,6 +1466,7 @@ struct fr_renderer {
                     p.stage_jit_form.maxld = sj.maxld;
                     p.stage_jit_form.maxst = sj.maxst;
                     p.stage_jit_form.blk = sj.blk;
+                    p.stage_jit_form.tile = sj.tile;
                     p.d_jprogs.ensure(sj.progs.size() * sizeof(JitStageProg));
                     p.d_ptab.ensure(std::max<size_t>(sj.ptab.size(), 1) * sizeof(uint32_t));
                     HIP_CHECK(hipMemcpyAsync(p.d_jprogs.p, sj.progs.data(), sj.progs.size() * sizeof(JitStageProg), hipMemcpyHostToDevice, st));
@@ -1511,7 +1523,7 @@ struct fr_renderer {
            << ",\"fused_levels\":" << (p.sp.fused_level_first.empty() ? 0 : p.sp.fused_level_first.size() - 1) << ",\"copy_programs\":" << p.sp.post_count
            << ",\"stage_levels\":" << (p.sp.level_first.empty() ? 0 : p.sp.level_first.size() - 1)
            << ",\"stage_jit\":" << (p.stage_jit ? "true" : "false") << ",\"stage_shapes\":" << p.stage_shapes
-           << ",\"stage_jit_form\":" << stage_jit_form_json(p)
+           << ",\"stage_jit_form\":" << stage_jit_form_json(p, loop_tiles_given)
            << ",\"fused_carry_only\":" << (p.sp.feedback && p.sp.fused_carry_only ? "true" : "false")
            << ",\"stage_hoisted_max\":" << stage_hoisted_max(p.sp)
            << ",\"rings\":" << p.sp.n_rings << ",\"max_lookback\":" << p.sp.lmax
@@ -1519,7 +1531,11 @@ struct fr_renderer {
            << ",\"delay_observed\":" << (delay_observed ? "true" : "false") << ",\"delay_observed_max\":" << delay_observed_max
            << ",\"observed_delays\":" << p.sp.observed.size() << ",\"observed_lookback\":" << p.sp.observed_lookback
            << ",\"observed_refused\":" << p.sp.observed_refused
-           << ",\"history_frames\":" << history_frames << ",\"ring_keep\":" << (ring_keep ? "true" : "false")
+           << ",\"history_frames\":" << history_frames << ",\"ring_keep\":" << (ring_keep ? "true" : "false");
+        if (loop_tiles_given)
+            js << ",\"loop_tiles\":{\"frames\":" << p.loop_tile.frames << ",\"max_stride\":" << LOOP_TILE_MAX_STRIDE << ",\"reason\":\""
+               << p.loop_tile.reason << "\"}";
+        js
            << ",\"track_history\":" << track_history << ",\"track_lookback\":" << p.sp.track_lookback
            << ",\"track_window_slots\":" << p.sp.track_window_slots.size()
            << ",\"jit_pending\":" << (p.jit_pending ? "true" : "false") << ",\"jit_kernels_compiled\":" << jit_cache.compiled() << ",\"jit_compile_ms\":" << jit_cache.compile_ms() << ",\"jit_disk_hits\":" << jit_cache.disk_hits()
@@ -1932,10 +1948,13 @@ struct fr_renderer {
     void launch_range(const Call &c, const StageLaunch &how, uint32_t first, uint32_t count, uint64_t s0, uint64_t slen) {
         const StagedPlan &sp = plan.sp;
         const bool carry = how.stride && sp.feedback, carry_only = carry && sp.fused_carry_only;
+        // (loop tiles: the rule looked at the fused programs, which are all a feedback plan ever launches strided)
+        const uint32_t tile = carry_only && how.stride == sp.fused_stride && first >= sp.fused_first && first + count <= sp.fused_first + sp.fused_count
+                                  ? plan.loop_tile.frames : 0u;
         const size_t n_inline = std::min<size_t>(stage_tab.size(), STAGE_INLINE_INPUTS);
         if (count && stage_launches.size() < 256)
             stage_launches.push_back({how.form, plan.stage_jit != nullptr, count, slen, how.stride, carry, carry_only,
-                                      stage_tab.size() > STAGE_INLINE_INPUTS, (count - 1) / 65535u + 1});
+                                      stage_tab.size() > STAGE_INLINE_INPUTS, (count - 1) / 65535u + 1, tile != 0});
         for (uint32_t off = 0; off < count; off += 65535u) {
             const uint32_t n = std::min<uint32_t>(count - off, 65535u);
             Scope sc(this, &t_stage, c.st);
@@ -1946,6 +1965,7 @@ struct fr_renderer {
                 a.progs = plan.d_jprogs.as<JitStageProg>() + first + off;
                 a.inputs = reinterpret_cast<const JitInput *>(d_in_table_stage.as<DevInput>());
                 for (size_t i = 0; i < n_inline; ++i) a.inline_inputs[i] = JitInput{stage_tab[i].data, stage_tab[i].base, stage_tab[i].len};
+                a.tile = tile;
                 HIP_CHECK(launch_jit_stage(*plan.stage_jit, a, n, c.st));
             } else {
                 StageArgs a{};
@@ -1957,6 +1977,7 @@ struct fr_renderer {
                 for (size_t i = 0; i < n_inline; ++i) a.inline_inputs[i] = stage_tab[i];
                 a.use_carry = carry ? 1u : 0u;
                 a.sparkle = mirror.sparkle ? 1u : 0u;
+                a.tile = tile;
                 HIP_CHECK(launch_stage(a, c.st));
             }
             sc.done();
@@ -2379,6 +2400,7 @@ int64_t env_strict_stream_programs(const char *e);
 int64_t env_strict_stream_bus(const char *e);
 int64_t env_strict_stream_inputs(const char *e);
 int64_t env_strict_stream_banks(const char *e);
+int64_t env_strict_loop_tiles(const char *e);
 bool parse_option(const Knob &k, const char *s, int64_t &v);
 
 const Knob kKnobs[] = {
@@ -2461,6 +2483,12 @@ const Knob kKnobs[] = {
     // next to voices behind programs -- in one resident launch (streamplan.hpp StreamEnv::banks; fr_plan_json: stream.banks).
     // Inert without FR_STREAM_PROGRAMS.  Strict and listed once set.
     {"FR_STREAM_BANKS", 0, 0, 1, 0, nullptr, 0, env_strict_stream_banks, [](fr_renderer &r, int64_t v, bool) { r.stream_banks = v != 0; }, LISTED_WHEN_SET},
+    // Loop tiles: the strided launches of feedback plans whose stride is at most LOOP_TILE_MAX_STRIDE frames stage a tile of frames
+    // in LDS (callplan.hpp loop_tile; fr_plan_json: loop_tiles, the launches' +tile).  Same bits.  Strict and listed once set.
+    {"FR_LOOP_TILES", 0, 0, 1, 0, nullptr, 0, env_strict_loop_tiles, [](fr_renderer &r, int64_t v, bool given) {
+         r.loop_tiles = v != 0;
+         r.loop_tiles_given = given;
+     }, LISTED_WHEN_SET},
 };
 static_assert(sizeof kKnobs / sizeof kKnobs[0] == N_OPTIONS, "N_OPTIONS counts the rows of kKnobs");
 
@@ -2476,6 +2504,7 @@ int64_t env_strict_stream_programs(const char *e) { return env_strict("FR_STREAM
 int64_t env_strict_stream_bus(const char *e) { return env_strict("FR_STREAM_BUS", e); }
 int64_t env_strict_stream_inputs(const char *e) { return env_strict("FR_STREAM_INPUTS", e); }
 int64_t env_strict_stream_banks(const char *e) { return env_strict("FR_STREAM_BANKS", e); }
+int64_t env_strict_loop_tiles(const char *e) { return env_strict("FR_LOOP_TILES", e); }
 
 bool parse_option(const Knob &k, const char *s, int64_t &v) {
     if (k.word && std::strcmp(s, k.word) == 0) {

@@ -412,6 +412,12 @@ std::shared_ptr<JitKernel> JitCache::get_source(const std::string &src, const ch
             throw Error(FR_ERR_DEVICE, e->error);
         }
         if (e->fn_name == "jit_bank" && hipModuleGetFunction(&jk->fn_multi, jk->module, "jit_bank_multi") != hipSuccess) jk->fn_multi = nullptr;
+        if (e->fn_name == "jit_stage" && it->first.find("jit_stage_tile") != std::string::npos &&   // (generated with loop tiles only)
+            hipModuleGetFunction(&jk->fn_tile, jk->module, "jit_stage_tile") != hipSuccess) {
+            e->state = Impl::Entry::FAILED;
+            e->error = "jit: the compiled code object has no jit_stage_tile";
+            throw Error(FR_ERR_DEVICE, e->error);
+        }
         e->code.clear();
         e->code.shrink_to_fit();
         e->kernel = jk;
@@ -433,6 +439,10 @@ hipError_t launch_jit_stage(const JitKernel &k, const JitStageArgs &a, uint32_t 
     if (n_progs == 0 || a.w_len == 0) return hipSuccess;
     JitStageArgs copy = a;
     void *args[] = {&copy};
+    if (a.tile) {   // loop tiles: one wave per program
+        if (!k.fn_tile || a.stride == 0 || a.stride > 64 || a.tile > 256 || a.tile % a.stride != 0) return hipErrorInvalidValue;
+        return hipModuleLaunchKernel(k.fn_tile, 1, n_progs, 1, 64, 1, 1, 0, s, args, nullptr);
+    }
     const unsigned long long span = a.stride ? std::min(a.stride, a.w_len) : a.w_len;   // (stride: one launch walks the window in strides)
     return hipModuleLaunchKernel(k.fn, (uint32_t)((span + 255) / 256), n_progs, 1, 256, 1, 1, 0, s, args, nullptr);
 }

@@ -58,7 +58,7 @@ FR_JIT_ARGS_TEXT
 // instruction skeleton (ops + register wiring; the usual case is one skeleton per voice position in an effects
 // chain) share one straight-line function; what differs between them -- constants, ring ids, delays, input slots --
 // comes from a per-program parameter row read through the scalar cache.  One kernel per plan, blockIdx.y = program.
-#define FR_JIT_STAGE_ARGS_TEXT                                                                                 \
+#define FR_JIT_STAGE_ARGS_TEXT_(...)                                                                           \
     struct JitInput { const float *data; unsigned long long base; unsigned long long len; };                   \
     struct JitStageProg { unsigned int shape, param_off, dst_ring; int out_row; };                            \
     struct JitStageArgs {                                                                                      \
@@ -73,8 +73,13 @@ FR_JIT_ARGS_TEXT
         unsigned long long n_times, idx, w0, w_len;                                                            \
         unsigned long long stride;      /* 0: thread wi computes frame w0 + wi; else frames w0 + wi + k * stride < w0 + w_len */ \
         unsigned int carry_only;        /* strided: every read of a ring this launch stores comes from the carry: no wait per stride */ \
+        __VA_ARGS__                                                                                            \
     };
-FR_JIT_STAGE_ARGS_TEXT
+// (a module generated without loop tiles declares the struct without its last field -- its text is the one it has always had, the
+//  hipRTC cache keys on it -- and reads the prefix of the same argument block)
+#define FR_JIT_STAGE_ARGS_TEXT FR_JIT_STAGE_ARGS_TEXT_()
+#define FR_JIT_STAGE_ARGS_TILE_TEXT FR_JIT_STAGE_ARGS_TEXT_(unsigned int tile; /* != 0: jit_stage_tile, frames per tile (callplan.hpp loop_tile) */)
+FR_JIT_STAGE_ARGS_TILE_TEXT
 static_assert(sizeof(JitInput) == sizeof(DevInput), "JitInput mirrors DevInput");
 
 struct StageJitPlan {
@@ -85,6 +90,7 @@ struct StageJitPlan {
     // the generated form: exactly the values of the source's #defines (fr_plan_json "stage_jit_form")
     bool deep = false, defer = false;
     uint32_t maxp = 0, maxld = 0, maxst = 0, blk = 1;
+    uint32_t tile = 0;                  // != 0: the module also holds jit_stage_tile (FR_LOOP_TILES) for launches of that many frames per tile
 };
 // Groups the programs by skeleton and writes the kernel source.  Returns false when specialisation is not worth a
 // compile: more than `max_shapes` skeletons, or (unless `force`) fewer than 4 programs per skeleton on average.
@@ -94,7 +100,11 @@ struct StageJitPlan {
 // every extra instruction counts, and the 2-stride launches of effects chains measured the same at 1, 2 and 4
 // (profiles/r03_feedback.txt; FR_STAGE_BLOCK overrides).
 bool plan_stage_jit(const std::vector<StageProg> &progs, const std::vector<StageInstr> &instrs, uint32_t max_shapes, bool force,
-                    StageJitPlan &out, bool sparkle = false, uint32_t block = 1, bool defer_stores = false);
+                    StageJitPlan &out, bool sparkle = false, uint32_t block = 1, bool defer_stores = false, uint32_t tile = 0);
+// `tile` (callplan.hpp loop_tile; 0: none, and the source is what it is without the feature): the module gains a second entry
+// point, jit_stage_tile, for the plan's strided launches -- one wave per program, the window in tiles of `tile` frames: frame-only
+// loads with their range tests into LDS by all lanes, each shape's loop over its residue's frames on LDS operands and the register
+// carry, the tile's stores by all lanes.  jit_stage itself stays for the plan's other launches (row copies).
 // `defer_stores`: a block's ring and output stores are issued after its iterations (only for plans whose strided threads read their
 // own rings through the carry alone, StagedPlan::fused_carry_only: nothing inside a block then reads what the block stores).
 
@@ -118,6 +128,7 @@ struct JitKernel {
     hipModule_t module = nullptr;
     hipFunction_t fn = nullptr;
     hipFunction_t fn_multi = nullptr;   // bank modules: the whole-voices-per-wave kernel for many small voices
+    hipFunction_t fn_tile = nullptr;    // stage modules generated with loop tiles: jit_stage_tile
     uint32_t k = 0;                     // varying constants per leaf
     ~JitKernel();
 };

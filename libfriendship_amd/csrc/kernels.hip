@@ -1675,9 +1675,129 @@ __global__ void __launch_bounds__(256) stage_kernel(StageArgs a) {
     }
 }
 
+// Loop tiles (kernels.hpp StageArgs::tile, callplan.hpp loop_tile): the strided launch of a feedback plan whose stride is at most
+// 64 frames, ONE wave per program, the window rendered in tiles of a.tile frames (a multiple of the stride, so lane r < stride
+// owns residue r in every tile).  stage_kernel keeps global memory inside its serial loop -- every operand a load from one
+// active lane, every ring and row store a dword of its own, the range tests and ring addresses in 64-bit arithmetic per frame --
+// and leaves the lanes >= stride idle.  Here a tile goes through three phases:
+//   1. all 64 lanes, lane = frame: the loads that depend on the frame alone (S_INPUT, S_READ_INPUT, S_READ of a ring the
+//      program does not store: imm == 0), range test applied, coalesced, into ldt[load slot][frame];
+//   2. lanes < stride: the residue's frames in order, operands from ldt, own rings from the carry, everything stage_kernel
+//      stores to a ring or a row into stt[store slot][frame] -- no global memory access but the instruction fetch;
+//   3. all 64 lanes: stt to the rings and the output row, coalesced, under stage_kernel's conditions.
+// Load slots number the frame-only loads in program order, store slots the S_STOREs in program order, then dst_ring, then
+// out_row (tile_is_load; the walk of phase 2 counts as the set-up walk does, and clamps the slot: the rule admits programs of
+// at most STAGE_TILE_LOADS loads and STAGE_TILE_STORES stores, the kernel stays in bounds without it).  No lane returns before
+// the last barrier; every loop is bounded by w_len.
+__device__ __forceinline__ bool tile_is_load(const StageInstr &in) {
+    return in.op == S_INPUT || in.op == S_READ_INPUT || (in.op == S_READ && in.imm == 0u);
+}
+
+__global__ void __launch_bounds__(64) stage_tile_kernel(StageArgs a) {
+    __shared__ float tmp[STAGE_REGS][64];
+    __shared__ float ldt[STAGE_TILE_LOADS][STAGE_TILE_FRAMES];
+    __shared__ float stt[STAGE_TILE_STORES][STAGE_TILE_FRAMES];
+    __shared__ float cyt[2][STAGE_CARRY][64];
+    __shared__ uint32_t ld_at[STAGE_TILE_LOADS];    // load slot -> instruction
+    __shared__ uint32_t st_ring[STAGE_TILE_STORES]; // store slot -> ring
+    const uint32_t lane = threadIdx.x;
+    const StageProg pg = a.progs[blockIdx.y];
+    const StageInstr *gins = a.instrs + pg.first_instr;
+    const uint32_t stride = (uint32_t)a.stride, tile = a.tile;
+    const size_t ring_cap = (size_t)a.ring_mask + 1;
+    // set-up: the slot tables (every lane counts -- the counts are uniform --, lane 0 writes), and the carry's first values: what
+    // an earlier launch left in the rings `stride` frames before the lane's first frame, or +0
+    uint32_t n_ld = 0, n_st = 0;
+    for (uint32_t i = 0; i < pg.n_instr; ++i) {
+        const StageInstr in = gins[i];
+        if (tile_is_load(in)) {
+            if (lane == 0 && n_ld < STAGE_TILE_LOADS) ld_at[n_ld] = i;
+            ++n_ld;
+        } else if (in.op == S_STORE) {
+            if (lane == 0 && n_st < STAGE_TILE_STORES) st_ring[n_st] = in.buf;
+            ++n_st;
+        } else if (in.op == S_READ && in.imm <= STAGE_CARRY && lane < stride && lane < a.w_len) {
+            cyt[1][in.imm - 1u][lane] = stage_load(a, in, a.w0 + lane);
+        }
+    }
+    if (pg.dst_ring != 0xFFFFFFFFu) {
+        if (lane == 0 && n_st < STAGE_TILE_STORES) st_ring[n_st] = pg.dst_ring;
+        ++n_st;
+    }
+    n_ld = n_ld < STAGE_TILE_LOADS ? n_ld : STAGE_TILE_LOADS;
+    n_st = n_st < STAGE_TILE_STORES ? n_st : STAGE_TILE_STORES;                 // ring stores; the row's slot follows them
+    const uint32_t row_slot = n_st < STAGE_TILE_STORES ? n_st : STAGE_TILE_STORES - 1u;
+    __syncthreads();
+    uint32_t par = 0;
+    for (uint64_t base = 0; base < a.w_len; base += tile) {
+        const uint32_t n = (uint32_t)(a.w_len - base < tile ? a.w_len - base : tile);   // frames of this tile
+        // 1. the tile's frame-only loads, a frame's in flight together
+        for (uint32_t f = lane; f < n; f += 64u) {
+            const uint64_t t = a.w0 + base + f;
+            float ld[STAGE_TILE_LOADS];
+#pragma unroll
+            for (uint32_t k = 0; k < STAGE_TILE_LOADS; ++k)
+                if (k < n_ld) ld[k] = stage_load(a, gins[ld_at[k]], t);
+#pragma unroll
+            for (uint32_t k = 0; k < STAGE_TILE_LOADS; ++k)
+                if (k < n_ld) ldt[k][f] = ld[k];
+        }
+        __syncthreads();
+        // 2. the loops, a lane per residue
+        if (lane < stride) {
+            for (uint32_t f = lane; f < n; f += stride, par ^= 1u) {
+                uint32_t k = 0, s = 0;
+                for (uint32_t i = 0; i < pg.n_instr; ++i) {
+                    const StageInstr in = gins[i];
+                    float v;
+                    switch (in.op) {
+                    case S_CONST: v = __uint_as_float(in.imm); break;
+                    case S_INPUT: case S_READ_INPUT: v = ldt[k++ & (STAGE_TILE_LOADS - 1u)][f]; break;
+                    case S_READ:
+                        if (in.imm == 0u) v = ldt[k++ & (STAGE_TILE_LOADS - 1u)][f];
+                        else v = cyt[par ^ 1u][(in.imm - 1u) & (STAGE_CARRY - 1u)][lane];
+                        break;
+                    case S_STEP: v = a.w0 + base + f >= in.d_lo ? __uint_as_float(in.imm) : 0.0f; break;
+                    case S_SUM2: v = tmp[in.a][lane] + tmp[in.b][lane]; break;
+                    case S_MUL: v = tmp[in.a][lane] * tmp[in.b][lane]; break;
+                    case S_DIV: v = tmp[in.a][lane] / tmp[in.b][lane]; break;
+                    case S_MOD: v = prim_mod(tmp[in.a][lane], tmp[in.b][lane]); break;
+                    case S_MIN: v = prim_min(tmp[in.a][lane], tmp[in.b][lane], a.sparkle != 0u); break;
+                    case S_STORE:
+                        stt[s < STAGE_TILE_STORES ? s : STAGE_TILE_STORES - 1u][f] = tmp[in.a][lane];
+                        ++s;
+                        if (in.imm != 0u && in.imm <= STAGE_CARRY) cyt[par][in.imm - 1u][lane] = tmp[in.a][lane];
+                        continue;
+                    default: v = 0.0f; break;   // (a Delay of a signal amount: the rule tiles no such program)
+                    }
+                    tmp[in.dst][lane] = v;
+                }
+                const float r = tmp[pg.result_reg][lane];
+                if (pg.dst_ring != 0xFFFFFFFFu) stt[n_st - 1u][f] = r;
+                if (pg.out_row >= 0) stt[row_slot][f] = r;
+            }
+        }
+        __syncthreads();   // (also: phase 2 has read ldt before the next tile's phase 1 overwrites it)
+        // 3. the tile's stores
+        for (uint32_t f = lane; f < n; f += 64u) {
+            const uint64_t t = a.w0 + base + f;
+#pragma unroll
+            for (uint32_t k = 0; k < STAGE_TILE_STORES; ++k)
+                if (k < n_st) a.rings[(size_t)st_ring[k] * ring_cap + (t & a.ring_mask)] = stt[k][f];
+            if (pg.out_row >= 0 && t >= a.idx) a.out[(size_t)pg.out_row * a.n_times + (t - a.idx)] = stt[row_slot][f];
+        }
+        // (phase 3 reads stt, the next tile's phase 2 writes it: the barrier after its phase 1 stands between them)
+    }
+}
+
 hipError_t launch_stage(const StageArgs &a, hipStream_t s) {
     if (a.n_progs == 0 || a.w_len == 0) return hipSuccess;
     if (a.n_progs > 65535u) return hipErrorInvalidValue;
+    if (a.tile) {
+        if (a.stride == 0 || a.stride > 64 || a.tile > STAGE_TILE_FRAMES || a.tile % a.stride != 0) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(stage_tile_kernel, dim3(1, a.n_progs), dim3(64), 0, s, a);
+        return hipGetLastError();
+    }
     uint64_t bx = ((a.stride ? std::min(a.stride, a.w_len) : a.w_len) + 255) / 256;
     if (bx > 0x7FFFFFFFull) return hipErrorInvalidValue;
     const size_t carry_bytes = a.use_carry ? (size_t)2 * STAGE_CARRY * 256 * sizeof(float) : 0;

@@ -179,7 +179,11 @@ struct StageArgs {
     uint32_t carry_only;       // strided launches: every read of a ring that this launch stores comes from the carry (below), so
                                // a stride's stores need not be in memory before the next stride starts
     uint32_t use_carry;        // the programs carry annotations (feedback plans): the launch gets the carry's LDS
+    uint32_t tile;             // 0: stage_kernel.  Else (callplan.hpp loop_tile, FR_LOOP_TILES) stage_tile_kernel: one wave per program
+                               // renders the window in tiles of this many frames -- a multiple of `stride`, at most STAGE_TILE_FRAMES
 };
+// stage_tile_kernel's LDS: the tile's frame-only loads and its stores as [slot][frame in tile]
+constexpr uint32_t STAGE_TILE_FRAMES = 256, STAGE_TILE_LOADS = 16, STAGE_TILE_STORES = 12;
 // Carry (feedback plans, stage.cpp): a strided thread that reads back, `stride` frames later, what it stored to a ring in its
 // previous iteration need not go through memory for it -- a dependent L2 round trip per iteration, all there is to a one-sample
 // loop.  S_STORE.imm = carry slot + 1 keeps the stored value (double-buffered by iteration parity, so that the order of stores

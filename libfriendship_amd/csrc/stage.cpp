@@ -556,7 +556,8 @@ void note_observed(const FlatGraph &g, const Planner &P, StagedPlan &sp) {
 }  // namespace
 
 StagedPlan plan_stages(const FlatGraph &g, bool allow_banks, bool allow_programs, uint32_t max_log2_p, bool allow_jit, bool allow_template,
-                       BankMatcher *reuse, const ShardSpec *shard, uint32_t track_from, const ObservedInputs *observed, uint64_t track_history) {
+                       BankMatcher *reuse, const ShardSpec *shard, uint32_t track_from, const ObservedInputs *observed, uint64_t track_history,
+                       bool loop_stride) {
     StagedPlan sp;
     PlanTrace plan_trace;
     const uint32_t n_rows = (uint32_t)g.outputs.size();
@@ -1107,8 +1108,26 @@ StagedPlan plan_stages(const FlatGraph &g, bool allow_banks, bool allow_programs
                 }
                 mp.n_instr = (uint32_t)(fbase + minstrs.size()) - mp.first_instr;
                 if (mp.n_instr > MAX_PROG_INSTR) throw Error(FR_ERR_UNSUPPORTED, "a feedback loop's expression exceeds the stage programs' budget");
+                mprogs.push_back(mp);
+            }
+            // The launches' stride: the gcd of the delays of every read of a program's ring.  `loop_stride` (FR_LOOP_TILES): of the
+            // reads of rings the reading program stores itself only -- the loops.  A ring another program stores belongs to an
+            // earlier level, whose launch has stored the whole window before this one starts: its delay binds no thread to a
+            // residue (x = in + Delay(0.75 * x, 5) read at delay 2 by a later level strides by 5, not by 1).
+            uint64_t stride = min_delay == ~0ull ? 0 : gcd_delay;
+            if (loop_stride) {
+                uint64_t own = 0;
+                for (const StageProg &mp : mprogs) {
+                    const StageInstr *ins = minstrs.data() + (mp.first_instr - fbase);
+                    std::unordered_set<uint32_t> mine;
+                    for (uint32_t k = 0; k < mp.n_instr; ++k) if (ins[k].op == S_STORE) mine.insert(ins[k].buf);
+                    for (uint32_t k = 0; k < mp.n_instr; ++k)
+                        if (ins[k].op == S_READ && mine.count(ins[k].buf)) { uint64_t a_ = own, b_ = ins[k].d_lo; while (b_) { const uint64_t r_ = a_ % b_; a_ = b_; b_ = r_; } own = a_; }
+                }
+                if (own != 0) stride = own;
+            }
+            for (const StageProg &mp : mprogs) {
                 {
-                    const uint64_t stride = min_delay == ~0ull ? 0 : gcd_delay;
                     std::unordered_map<uint32_t, uint32_t> slot_of;   // ring -> carry slot + 1 (0: it has none)
                     StageInstr *ins = minstrs.data() + (mp.first_instr - fbase);
                     for (uint32_t k = 0; k < mp.n_instr; ++k)
@@ -1125,7 +1144,6 @@ StagedPlan plan_stages(const FlatGraph &g, bool allow_banks, bool allow_programs
                         else { ins[k].imm = 0xFFu; carry_only = false; }        // further back than one iteration: through memory, in order
                     }
                 }
-                mprogs.push_back(mp);
             }
             std::vector<size_t> order(mprogs.size());
             for (size_t i = 0; i < order.size(); ++i) order[i] = i;
@@ -1133,7 +1151,7 @@ StagedPlan plan_stages(const FlatGraph &g, bool allow_banks, bool allow_programs
             sp.fused_first = (uint32_t)sp.progs.size();
             sp.fused_count = (uint32_t)mprogs.size();
             sp.fused_max_frames = 0;
-            sp.fused_stride = min_delay == ~0ull ? 0 : gcd_delay;
+            sp.fused_stride = stride;
             sp.feedback = true;
             sp.fused_carry_only = carry_only;
             sp.instrs.insert(sp.instrs.end(), minstrs.begin(), minstrs.end());

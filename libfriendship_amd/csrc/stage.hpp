@@ -141,7 +141,9 @@ class BankMatcher;
 // interpreter, template voices and voices that feed delay lines may read tracks too, as far back as that.
 StagedPlan plan_stages(const FlatGraph &g, bool allow_banks, bool allow_programs, uint32_t max_log2_p, bool allow_jit = false,
                        bool allow_template = true, BankMatcher *reuse = nullptr, const ShardSpec *shard = nullptr, uint32_t track_from = 0xFFFFFFFFu,
-                       const ObservedInputs *observed = nullptr, uint64_t track_history = 0);
+                       const ObservedInputs *observed = nullptr, uint64_t track_history = 0, bool loop_stride = false);
+// `loop_stride` (FR_LOOP_TILES): a feedback plan's fused_stride is the gcd of the delays with which its programs read rings they
+// store themselves -- its loops -- and not also of their reads of rings that earlier levels have finished.
 
 // Do the observed Delays of `sp` (planned from `g` with observed ranges) still fit their planned look-backs under the ranges
 // `obs` gives now?  False: some bound grew past its plan, or has none any more.

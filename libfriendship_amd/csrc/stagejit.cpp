@@ -223,6 +223,86 @@ STORE_CASES
 }
 )JIT";
 
+// Loop tiles (jit.hpp plan_stage_jit `tile`, callplan.hpp loop_tile): appended to the module of a tiled feedback plan.  One wave
+// per program; per tile: (1) all lanes, lane = frame: the shape's frame-only loads (shapeN_ld, as jit_stage issues them), then
+// their range tests (shapeN_tt), into t_ld[load][frame]; (2) lanes < stride: the shape's loop over the residue's frames --
+// shapeN_t: shapeN's text with LDS operands, no range test of a load, every ring store into t_st[store][frame], the carry in
+// registers as in jit_stage -- inside the shape's case; (3) all lanes: t_st to the rings (shapeN_st) and the row.  Inside (2)
+// there is no global memory access and no 64-bit address arithmetic.  No lane returns before the last barrier.
+static const char *kStageTileSkeleton = R"JIT(
+#define TILE_MAX 256
+TILE_FUNCTIONS
+extern "C" __global__ void __launch_bounds__(64) jit_stage_tile(JitStageArgs a) {
+    __shared__ float t_ld[MAXLD][TILE_MAX];
+    __shared__ float t_st[MAXST + 1][TILE_MAX];   // (the last: the program's result, for dst_ring and the output row)
+    const unsigned int lane = threadIdx.x;
+    const unsigned int stride = (unsigned int)a.stride;
+    const JitStageProg pg = a.progs[blockIdx.y];
+#if MAXP > 0
+    unsigned int P[MAXP];
+    {
+        cu32 prow = (cu32)(a.ptab + pg.param_off);
+#pragma unroll
+        for (int i = 0; i < MAXP; ++i) P[i] = prow[i];
+    }
+#else
+    cu32 P = (cu32)(a.ptab + pg.param_off);
+#endif
+    float cy[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, ny[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    if (lane < stride && lane < a.w_len) {   // the carry's first values: the rings `stride` frames before the lane's first frame
+        const u64 t = a.w0 + lane;
+        switch (pg.shape) {
+CARRY_CASES
+        default: break;
+        }
+    }
+    for (u64 base = 0; base < a.w_len; base += a.tile) {
+        const unsigned int n = (unsigned int)(a.w_len - base < a.tile ? a.w_len - base : a.tile);   // frames of this tile
+        const u64 t0 = a.w0 + base;
+        for (unsigned int f = lane; f < n; f += 64u) {
+            const u64 t = t0 + f;
+            float ldn[MAXLD];
+#pragma unroll
+            for (int i = 0; i < MAXLD; ++i) ldn[i] = 0.0f;
+            switch (pg.shape) {
+LOAD_CASES
+            default: break;
+            }
+#if defined(__AMDGCN__)
+#pragma unroll
+            for (int i = 0; i < MAXLD; ++i) asm volatile("" : "+v"(ldn[i]));   // every load issued before the first test
+#endif
+            switch (pg.shape) {
+TTEST_CASES
+            default: break;
+            }
+        }
+        __syncthreads();
+        if (lane < stride) {
+            switch (pg.shape) {
+TSERIAL_CASES
+            default: break;
+            }
+        }
+        __syncthreads();   // (also: the loops have read t_ld before the next tile's loads overwrite it)
+        for (unsigned int f = lane; f < n; f += 64u) {
+            const u64 t = t0 + f;
+            float sv[MAXST];
+#pragma unroll
+            for (int i = 0; i < MAXST; ++i) sv[i] = t_st[i][f];
+            switch (pg.shape) {
+STORE_CASES
+            default: break;
+            }
+            const float r = t_st[MAXST][f];
+            if (pg.dst_ring != 0xFFFFFFFFu) ring_store(a, pg.dst_ring, t, r);
+            if (pg.out_row >= 0 && t >= a.idx) a.out[(size_t)pg.out_row * a.n_times + (t - a.idx)] = r;
+        }
+        // (the stores read t_st, the next tile's loops write it: the barrier after its loads stands between them)
+    }
+}
+)JIT";
+
 namespace {
 // constants worth baking into the source: they enable peepholes (x mod 1.0, sign flips) and never come from a knob
 bool literal_worthy(uint32_t bits) {
@@ -234,12 +314,12 @@ bool literal_worthy(uint32_t bits) {
 }  // namespace
 
 bool plan_stage_jit(const std::vector<StageProg> &progs, const std::vector<StageInstr> &instrs, uint32_t max_shapes, bool force,
-                    StageJitPlan &out, bool sparkle, uint32_t block, bool defer_stores) {
+                    StageJitPlan &out, bool sparkle, uint32_t block, bool defer_stores, uint32_t tile) {
     // Plans without feedback keep the plain form -- every load where it is used, parameters through the scalar cache: their
     // launches compute one frame per thread (or a handful of strides) and the extra set-up of the deep form only costs (config
     // D's launch 8.9 -> 10.5 us with it).
     const bool deep = block > 1 || defer_stores;
-    if (progs.empty()) return false;
+    if (progs.empty() || (tile && !deep)) return false;
     struct Shape { uint32_t first; std::vector<uint32_t> members; std::vector<bool> literal; };
     std::map<std::string, uint32_t> ids;
     std::vector<Shape> shapes;
@@ -280,7 +360,9 @@ bool plan_stage_jit(const std::vector<StageProg> &progs, const std::vector<Stage
     // source
     constexpr uint32_t MAXLD = 16;   // loads per program fetched ahead, a block of iterations at a time (the rest where they are used)
     uint32_t max_nld = 1, max_nst = 1, max_np = 1;
-    std::ostringstream fns, cases, load_cases, store_cases, carry_cases;
+    std::ostringstream fns_, cases, load_cases, store_cases, carry_cases;
+    std::ostringstream &fns = fns_;
+    std::ostringstream tile_fns, test_cases, serial_cases;   // loop tiles (kStageTileSkeleton)
     for (size_t si = 0; si < shapes.size(); ++si) {
         const Shape &s = shapes[si];
         const StageProg &p0 = progs[s.first];
@@ -351,6 +433,13 @@ bool plan_stage_jit(const std::vector<StageProg> &progs, const std::vector<Stage
             fns << sf.str();
             max_nst = std::max(max_nst, nst);
         }
+        // the shape's function; loop tiles: and once more as shapeN_t, whose fetched-ahead loads (already range-tested) and ring stores
+        // are LDS columns [slot][frame] addressed from the frame's element
+        for (int tl = 0; tl <= (tile ? 1 : 0); ++tl) {
+        std::ostringstream &fns = tl ? tile_fns : fns_;   // (shadows the stream of the module's other functions)
+        if (tl) fns << "__device__ __forceinline__ float shape" << si << "_t(const JitStageArgs &a, PRM P, u64 t, const float *ld, const float *cy, float *ny, float *sv) {\n"
+                       "    (void)a; (void)P; (void)t; (void)ld; (void)cy; (void)ny; (void)sv;\n";
+        else
         fns << "__device__ __forceinline__ float shape" << si << "(const JitStageArgs &a, PRM P, u64 t, const float *ld, const float *cy, float *ny, bool carried, float *sv) {\n"
                "    (void)a; (void)P; (void)t; (void)ld; (void)cy; (void)ny; (void)carried; (void)sv;\n";
         uint32_t n_st = 0;
@@ -361,6 +450,12 @@ bool plan_stage_jit(const std::vector<StageProg> &progs, const std::vector<Stage
         for (uint32_t i = 0; i < p0.n_instr; ++i) {
             const StageInstr &in = instrs[p0.first_instr + i];
             char buf[96];
+            if (ld_of[i] >= 0 && tl) {
+                fns << "    float v" << i << " = ld[" << ld_of[i] << " * TILE_MAX];\n";
+                k += in.op == S_INPUT ? 1 : 2;
+                var_of[in.dst] = (int)i;
+                continue;
+            }
             if (ld_of[i] >= 0) {   // fetched ahead (raw): the range test decides between it and +0 here, on registers
                 fns << "    float v" << i << " = (";
                 if (in.op == S_INPUT) fns << "in_ok(a, P[" << k << "], t)";
@@ -369,6 +464,12 @@ bool plan_stage_jit(const std::vector<StageProg> &progs, const std::vector<Stage
                 fns << ") ? ld[" << ld_of[i] << "] : jit_opaque(0.0f);\n";
                 k += in.op == S_INPUT ? 1 : 2;
                 var_of[in.dst] = (int)i;
+                continue;
+            }
+            if (in.op == S_STORE && tl) {
+                fns << "    sv[" << n_st++ << " * TILE_MAX] = v" << var_of[in.a] << ";\n";
+                if (in.imm != 0 && in.imm <= 8) fns << "    ny[" << in.imm - 1 << "] = v" << var_of[in.a] << ";\n";
+                k += 1;
                 continue;
             }
             if (in.op == S_STORE) {
@@ -410,6 +511,37 @@ bool plan_stage_jit(const std::vector<StageProg> &progs, const std::vector<Stage
             var_of[in.dst] = (int)i;
         }
         fns << "    return v" << var_of[p0.result_reg] << ";\n}\n";
+        }
+        if (tile) {   // the range tests of the fetched-ahead loads, applied where they are fetched: the value, or +0 exactly as shapeN does
+            tile_fns << "__device__ __forceinline__ void shape" << si << "_tt(const JitStageArgs &a, PRM P, u64 t, const float *raw, float *ld) {\n    (void)a; (void)P; (void)t; (void)raw; (void)ld;\n";
+            uint32_t kk = 0;
+            for (uint32_t i = 0; i < p0.n_instr; ++i) {
+                const StageInstr &in = instrs[p0.first_instr + i];
+                if (ld_of[i] >= 0) {
+                    tile_fns << "    ld[" << ld_of[i] << " * TILE_MAX] = (";
+                    if (in.op == S_INPUT) tile_fns << "in_ok(a, P[" << kk << "], t)";
+                    else if (in.op == S_READ) tile_fns << "t >= P[" << kk + 1 << "]";
+                    else tile_fns << "t >= P[" << kk + 1 << "] && in_ok(a, P[" << kk << "], t - P[" << kk + 1 << "])";
+                    tile_fns << ") ? raw[" << ld_of[i] << "] : jit_opaque(0.0f);\n";
+                }
+                switch (in.op) {
+                case S_CONST: if (!s.literal[i]) kk += 1; break;
+                case S_INPUT: case S_STORE: case S_READ_DYN: case S_READ_INPUT_DYN: case S_STEP_DYN: kk += 1; break;
+                case S_READ: case S_READ_INPUT: case S_STEP: kk += 2; break;
+                default: break;
+                }
+            }
+            tile_fns << "}\n";
+            test_cases << "            case " << si << ": shape" << si << "_tt(a, P, t, ldn, &t_ld[0][f]); break;\n";
+            serial_cases << "            case " << si << ":\n"
+                            "                for (unsigned int f = lane; f < n; f += stride) {\n"
+                            "                    const float r = shape" << si << "_t(a, P, t0 + f, &t_ld[0][f], cy, ny, &t_st[0][f]);\n"
+                            "#pragma unroll\n"
+                            "                    for (int i = 0; i < 8; ++i) cy[i] = ny[i];\n"
+                            "                    t_st[MAXST][f] = r;\n"
+                            "                }\n"
+                            "                break;\n";
+        }
         cases << "        case " << si << ": r = shape" << si << "(a, P, t, ld, cy, ny, carried, sv); break;\n";
         store_cases << "                case " << si << ": shape" << si << "_st(a, P, t, sv); break;\n";
         load_cases << "        case " << si << ": shape" << si << "_ld(a, P, t, ldn); break;\n";
@@ -422,7 +554,8 @@ bool plan_stage_jit(const std::vector<StageProg> &progs, const std::vector<Stage
     out.blk = std::max(1u, std::min(block, std::max(1u, 32u / (max_nld + (out.defer ? max_nst + 1 : 0)))));
     std::ostringstream src;
     src << "#pragma clang fp contract(off)\n#define FR_SPARKLE " << (sparkle ? 1 : 0) << "\n#define MAXLD " << out.maxld << "\n#define MAXP " << out.maxp << "\n#define MAXST " << out.maxst << "\n#define DEFER " << (out.defer ? 1 : 0)
-        << "\n#define BLK " << out.blk << "\n" << FR_STR(FR_JIT_STAGE_ARGS_TEXT) << "\n";
+        << "\n#define BLK " << out.blk << "\n" << (tile ? FR_STR(FR_JIT_STAGE_ARGS_TILE_TEXT) : FR_STR(FR_JIT_STAGE_ARGS_TEXT)) << "\n";
+    out.tile = tile;
     std::string body = kStageSkeleton;
     auto put = [&](const std::string &tag, const std::string &text) { body.replace(body.find(tag), tag.size(), text); };
     put("SHAPE_FUNCTIONS", fns.str());
@@ -431,6 +564,16 @@ bool plan_stage_jit(const std::vector<StageProg> &progs, const std::vector<Stage
     put("STORE_CASES", store_cases.str());
     put("CARRY_CASES", carry_cases.str());
     src << body;
+    if (tile) {
+        body = kStageTileSkeleton;
+        put("TILE_FUNCTIONS", tile_fns.str());
+        put("CARRY_CASES", carry_cases.str());
+        put("LOAD_CASES", load_cases.str());
+        put("TTEST_CASES", test_cases.str());
+        put("TSERIAL_CASES", serial_cases.str());
+        put("STORE_CASES", store_cases.str());
+        src << body;
+    }
     out.source = src.str();
     out.n_shapes = (uint32_t)shapes.size();
 
