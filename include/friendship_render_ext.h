@@ -87,6 +87,21 @@ extern "C" {
  * reason when the plan is not tiled: a stride above max_stride, a loop that reads its own ring further back than one stride
  * (taps at d and 2d), a program of more than 16 frame-only loads or 12 stores, a Delay of a signal amount -- the tiled
  * launches' "variant" carries +tile, and "stage_jit_form" gains "tile".  With the option unset nothing changes.
+ *
+ * FR_STREAM_LOOPS = 0 / 1 (default 0; read strictly from the environment too; does nothing unless FR_STREAM_PROGRAMS=1):
+ * block streaming also serves feedback loops shorter than a block -- y = a x + b Delay(y, 1), a comb or plucked string
+ * x = voice + g Delay(x, d) with d < 64, a master filter or a 32-frame echo on a bus (with FR_STREAM_BUS) -- and what reads a
+ * loop's output behind it on the same voice (a tap Delay(x, 2), a second row).  A program that reads, less than 64 frames
+ * back, a delay line it stores itself is a loop program; its stride is the gcd of those delays.  A sixth resident kernel
+ * (bank_stream_loops_kernel) runs it in the wave that finishes its voice: all lanes fetch the block's inputs into on-chip
+ * memory, one lane per residue of the stride computes the frames from there in order, all lanes store the block.  It composes
+ * with FR_STREAM_BUS, FR_STREAM_INPUTS and FR_STREAM_BANKS and does not depend on FR_LOOP_TILES.  With 0 nothing changes: the
+ * same plans are served and refused, with the same reasons, by the same kernels.  "stream" gains "loop_programs" (the stride
+ * of every streamed program in the order they run, voice by voice, then the bus programs; 0 for a program that is no loop),
+ * "loop_loads" and "loop_stores" (the limits below); "kernel" is "bank_stream_loops_kernel" exactly when a program is a loop
+ * program.  Still refused: a loop program of more than 32 loads (input rows and delay-line reads) or 16 stored delay lines
+ * (the reason names the count and the limit), a Delay shorter than 64 frames of a computed value in a plan without a loop,
+ * delayed reads of an input row, signal-amount delays, and everything else of the lists above.
  */
 typedef struct fr_option {
     const char *name;              /* e.g. "FR_BANK_SHORT" */

@@ -197,7 +197,7 @@ static std::string stage_variant(const StageLaunchNote &n, const Plan &p) {
     return k;
 }
 
-constexpr size_t N_OPTIONS = 35;         // per-renderer options (friendship_render_ext.h; the table below fr_renderer)
+constexpr size_t N_OPTIONS = 36;         // per-renderer options (friendship_render_ext.h; the table below fr_renderer)
 
 struct TimerClass {
     double ms = 0;
@@ -253,6 +253,10 @@ __attribute__((weak)) hipError_t launch_bank_stream_in(const BankArgs &, const S
 }
 __attribute__((weak)) hipError_t launch_bank_stream_banks(const StreamBanksArgs &, const BankArgs &, const StreamProgArgs &, uint32_t, BankStreamInCtl *, BankStreamInDev *, uint32_t,
                                                           hipStream_t) {
+    return hipErrorNotSupported;
+}
+__attribute__((weak)) hipError_t launch_bank_stream_loops(const StreamBanksArgs &, const BankArgs &, const StreamProgArgs &, uint32_t, uint32_t, uint32_t, uint32_t, BankStreamInCtl *,
+                                                          BankStreamInDev *, uint32_t, hipStream_t) {
     return hipErrorNotSupported;
 }
 __attribute__((weak)) hipError_t launch_track_window(const TrackWindowArgs &a, hipStream_t) {
@@ -555,6 +559,7 @@ struct fr_renderer {
     bool stream_programs = false;        // the option
     bool stream_bus = false;             // FR_STREAM_BUS: mix-bus programs run after the block's last voice (bank_stream_bus_kernel)
     bool stream_inputs = false;          // FR_STREAM_INPUTS: programs read control rows, up to STREAM_MAX_INPUTS slots (bank_stream_in_kernel)
+    bool stream_loops = false;           // FR_STREAM_LOOPS: feedback loops shorter than a block (bank_stream_loops_kernel)
     bool stream_banks = false;           // FR_STREAM_BANKS: 2..STREAM_MAX_BANKS bank launches in one resident launch (bank_stream_banks_kernel)
     bool stream_prog = false;            // the open stream is of that kind
     bool stream_in = false;              // ... and its doorbell is the rows of stream_plan.input_slots (BankStreamInCtl / BankStreamInDev)
@@ -577,6 +582,7 @@ struct fr_renderer {
         env.bus = stream_bus;
         env.inputs = stream_inputs;
         env.banks = stream_banks;
+        env.loops = stream_loops;
         return plan_stream(plan.sp, banks, env);
     }
     // Rings the stop and waits for the resident launch to end.  `clean`: the launch was answering when the stop was rung
@@ -2180,12 +2186,14 @@ void fr_renderer::begin_program_stream(uint32_t n_slots) {
     // programs that read control rows (FR_STREAM_INPUTS): the stream's own copy of their instructions, S_INPUT's operand the
     // streamed row (the position of its slot in input_slots) instead of the plan's input index
     // (several banks: bank_stream_banks_kernel, whose control words and S_INPUT are those of the kernel with control rows)
-    const bool rows_in = s.input_slots.size() > 1 || s.banks.size() > 1;
+    // (loop programs, FR_STREAM_LOOPS: bank_stream_loops_kernel, the same control words; the copy also carries their store slots)
+    const bool rows_in = s.input_slots.size() > 1 || s.banks.size() > 1 || s.has_loops();
     std::vector<StageInstr> instrs;
     if (rows_in) {
         if (s.input_slots.size() > BANK_STREAM_ROWS) throw Error(FR_ERR_DEVICE, "internal: more streamed rows than the kernel takes");
-        for (StageProg &pg : progs) {
-            const uint32_t first = (uint32_t)instrs.size();
+        for (size_t i = 0; i < progs.size(); ++i) {
+            StageProg &pg = progs[i];
+            std::vector<StageInstr> own;
             for (uint32_t k = 0; k < pg.n_instr; ++k) {
                 StageInstr in = sp.instrs[pg.first_instr + k];
                 if (in.op == S_INPUT) {
@@ -2193,9 +2201,12 @@ void fr_renderer::begin_program_stream(uint32_t n_slots) {
                     if (it == s.input_slots.end()) throw Error(FR_ERR_DEVICE, "internal: a streamed program reads a slot the stream does not feed");
                     in.imm = (uint32_t)(it - s.input_slots.begin());
                 }
-                instrs.push_back(in);
+                own.push_back(in);
             }
-            pg.first_instr = first;
+            if (s.loop_stride[i] != 0 && (!stream_loop_prepare(pg, own) || pg.pad[0] != s.loop_stride[i]))
+                throw Error(FR_ERR_DEVICE, "internal: a loop program the stream cannot prepare");
+            pg.first_instr = (uint32_t)instrs.size();
+            instrs.insert(instrs.end(), own.begin(), own.end());
         }
         d_stream_instrs.ensure(std::max<size_t>(instrs.size(), 1) * sizeof(StageInstr));
         if (!instrs.empty()) HIP_CHECK(hipMemcpyAsync(d_stream_instrs.p, instrs.data(), instrs.size() * sizeof(StageInstr), hipMemcpyHostToDevice, stream));
@@ -2296,9 +2307,9 @@ void fr_renderer::seek_program_stream(uint64_t idx) {
     HIP_CHECK(hipMemsetAsync(d_stream_dev.p, 0, stream_in ? sizeof(BankStreamInDev) : sizeof(BankStreamDev), stream));
     // a plan whose programs read control rows (FR_STREAM_INPUTS): the kernel with a doorbell of rows; a plan with bus programs
     // (FR_STREAM_BUS): the kernel whose last arriver of a block runs them; every other plan: as before
-    if (s.banks.size() > 1) {
-        // voices of several banks (FR_STREAM_BANKS): the bank table travels in the kernel arguments; chunk sums and tickets
-        // are laid out by global voice
+    if (s.banks.size() > 1 || s.has_loops()) {
+        // voices of several banks (FR_STREAM_BANKS), loop programs (FR_STREAM_LOOPS: also for one bank): the bank table travels
+        // in the kernel arguments; chunk sums and tickets are laid out by global voice
         StreamBanksArgs t{};
         t.n_banks = (uint32_t)s.banks.size();
         for (size_t i = 0; i < s.banks.size(); ++i) {
@@ -2322,9 +2333,24 @@ void fr_renderer::seek_program_stream(uint64_t idx) {
         a.fast_ok = 0;
         p.bank_to_ring = 0;
         p.instrs = d_stream_instrs.as<StageInstr>();
-        HIP_CHECK(launch_bank_stream_banks(t, a, p, (uint32_t)s.input_slots.size(), h_stream_ctl.as_dev<BankStreamInCtl>(), d_stream_dev.as<BankStreamInDev>(), stream_idle_ms,
-                                           stream));
-        stream_kernel = "bank_stream_banks_kernel";
+        if (s.has_loops()) {
+            // (the tiles' fill is re-counted from the plan's instructions; the store slots are the stored rings)
+            uint32_t max_stride = 0, max_loads = 0, max_stores = 0;
+            for (size_t i = 0; i < s.progs.size(); ++i) {
+                if (!s.loop_stride[i]) continue;
+                const StageProg &pg = sp.progs[s.progs[i]];
+                max_stride = std::max(max_stride, s.loop_stride[i]);
+                max_loads = std::max(max_loads, stream_loop_loads(pg, sp.instrs.data() + pg.first_instr));
+                max_stores = std::max<uint32_t>(max_stores, (uint32_t)stream_stored_rings(pg, sp.instrs.data() + pg.first_instr).size());
+            }
+            HIP_CHECK(launch_bank_stream_loops(t, a, p, (uint32_t)s.input_slots.size(), max_stride, max_loads, max_stores, h_stream_ctl.as_dev<BankStreamInCtl>(),
+                                               d_stream_dev.as<BankStreamInDev>(), stream_idle_ms, stream));
+            stream_kernel = "bank_stream_loops_kernel";
+        } else {
+            HIP_CHECK(launch_bank_stream_banks(t, a, p, (uint32_t)s.input_slots.size(), h_stream_ctl.as_dev<BankStreamInCtl>(), d_stream_dev.as<BankStreamInDev>(), stream_idle_ms,
+                                               stream));
+            stream_kernel = "bank_stream_banks_kernel";
+        }
     } else if (stream_in) {
         p.instrs = d_stream_instrs.as<StageInstr>();
         HIP_CHECK(launch_bank_stream_in(a, p, (uint32_t)s.input_slots.size(), h_stream_ctl.as_dev<BankStreamInCtl>(), d_stream_dev.as<BankStreamInDev>(), stream_idle_ms, stream));
@@ -2401,6 +2427,7 @@ int64_t env_strict_stream_bus(const char *e);
 int64_t env_strict_stream_inputs(const char *e);
 int64_t env_strict_stream_banks(const char *e);
 int64_t env_strict_loop_tiles(const char *e);
+int64_t env_strict_stream_loops(const char *e);
 bool parse_option(const Knob &k, const char *s, int64_t &v);
 
 const Knob kKnobs[] = {
@@ -2489,6 +2516,10 @@ const Knob kKnobs[] = {
          r.loop_tiles = v != 0;
          r.loop_tiles_given = given;
      }, LISTED_WHEN_SET},
+    // Feedback loops shorter than a block in block streaming -- a one-pole filter, a short comb, a 32-frame bus echo -- and the
+    // taps behind them (streamplan.hpp StreamEnv::loops; fr_plan_json: stream.loop_programs).  Inert without FR_STREAM_PROGRAMS.
+    // Strict and listed once set.
+    {"FR_STREAM_LOOPS", 0, 0, 1, 0, nullptr, 0, env_strict_stream_loops, [](fr_renderer &r, int64_t v, bool) { r.stream_loops = v != 0; }, LISTED_WHEN_SET},
 };
 static_assert(sizeof kKnobs / sizeof kKnobs[0] == N_OPTIONS, "N_OPTIONS counts the rows of kKnobs");
 
@@ -2505,6 +2536,7 @@ int64_t env_strict_stream_bus(const char *e) { return env_strict("FR_STREAM_BUS"
 int64_t env_strict_stream_inputs(const char *e) { return env_strict("FR_STREAM_INPUTS", e); }
 int64_t env_strict_stream_banks(const char *e) { return env_strict("FR_STREAM_BANKS", e); }
 int64_t env_strict_loop_tiles(const char *e) { return env_strict("FR_LOOP_TILES", e); }
+int64_t env_strict_stream_loops(const char *e) { return env_strict("FR_STREAM_LOOPS", e); }
 
 bool parse_option(const Knob &k, const char *s, int64_t &v) {
     if (k.word && std::strcmp(s, k.word) == 0) {
@@ -3158,9 +3190,16 @@ const char *fr_plan_json(fr_renderer *r) {
                                   "\",\"voices\":" + std::to_string(s.voices) + ",\"chunks\":" + std::to_string(s.chunks) + ",\"programs_per_voice\":[" + per +
                                   "],\"bus_programs\":" + std::to_string(s.bus_programs()) + ",\"min_ring_delay\":" + std::to_string(s.min_ring_delay) + ",\"rings\":" + std::to_string(r->plan.sp.n_rings) +
                                   ",\"input_slots\":[" + ins + "]";
+            if (r->stream_loops) {                               // FR_STREAM_LOOPS: the stride of each streamed program, in the order they run
+                std::string lp;
+                for (uint32_t l : s.loop_stride) lp += (lp.empty() ? "" : ",") + std::to_string(l);
+                r->plan_json_cache += ",\"loop_programs\":[" + lp + "],\"loop_loads\":" + std::to_string(STREAM_LOOP_LOADS) + ",\"loop_stores\":" + std::to_string(STREAM_LOOP_STORES);
+            }
             // (the kernel a servable plan will get where the plan decides it; else the last resident launch's, unless that was one of those)
-            const bool last_stands = std::strcmp(r->stream_kernel, "bank_stream_in_kernel") && std::strcmp(r->stream_kernel, "bank_stream_banks_kernel");
-            const char *kernel = s.servable && s.banks.size() > 1 ? "bank_stream_banks_kernel"
+            const bool last_stands = std::strcmp(r->stream_kernel, "bank_stream_in_kernel") && std::strcmp(r->stream_kernel, "bank_stream_banks_kernel") &&
+                                     std::strcmp(r->stream_kernel, "bank_stream_loops_kernel");
+            const char *kernel = s.servable && s.has_loops() ? "bank_stream_loops_kernel"
+                                 : s.servable && s.banks.size() > 1 ? "bank_stream_banks_kernel"
                                  : s.servable && s.input_slots.size() > 1 ? "bank_stream_in_kernel" : last_stands ? r->stream_kernel : "";
             if (r->stream_banks) {                               // FR_STREAM_BANKS: the banks of the launch, in plan order
                 std::string bl;

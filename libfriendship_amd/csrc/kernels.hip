@@ -787,8 +787,8 @@ static hipError_t launch_bank_short(const BankArgs &a, hipStream_t s) {
 }
 
 // ---------------------------------------------------------------------------------------------------
-// Block streaming: the short-call kernel as ONE resident launch (kernels.hpp, BankStreamCtl).  Five kernels -- bank_stream_kernel
-// below, the four that also run programs after stage_kernel -- are compositions of the pieces in this section; each step of the
+// Block streaming: the short-call kernel as ONE resident launch (kernels.hpp, BankStreamCtl).  Six kernels -- bank_stream_kernel
+// below, the five that also run programs after stage_kernel -- are compositions of the pieces in this section; each step of the
 // protocol is written once, here.
 //
 // A block.  The host rings a doorbell in mapped pinned memory: every word carries a sample and the block's tag.  Wave 0 of
@@ -1099,6 +1099,129 @@ __device__ __forceinline__ void stream_run_programs(float *out, const StreamProg
         if (live && pg.dst_ring != 0xFFFFFFFFu)
             __hip_atomic_store(p.rings + (size_t)pg.dst_ring * ring_cap + (frame & p.ring_mask), res, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (live && pg.out_row >= 0) __hip_atomic_store(out + (size_t)pg.out_row * 64u + lane, res, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+}
+
+// A loop program (FR_STREAM_LOOPS; kernels.hpp bank_stream_loops_kernel): StageProg::pad[0] = its stride, 1..63.  The block's
+// n frames start at `head`; `ldt` and `stt` are the load and the store tile.  One wave runs this, so the phases are ordered by
+// the wave's own program order (LDS accesses of a wave complete in order); the wavefront-scope fences keep the compiler from
+// moving an access across a phase boundary and emit nothing.
+__device__ __forceinline__ void stream_wave_phase() {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+// Instruction i of a loop program: from the wave's LDS copy of its first BANK_STREAM_LOOP_INSTRS instructions (phase 2 fetches
+// every instruction once per FRAME: from global memory that is a dependent trip to L2 each), the rest from memory.  Uniform: the
+// words go to scalar registers.
+__device__ __forceinline__ StageInstr stream_loop_instr(const uint4 (&lins)[BANK_STREAM_LOOP_INSTRS], const StageInstr *ins, uint32_t i) {
+    uint4 w = i < BANK_STREAM_LOOP_INSTRS ? lins[i] : *reinterpret_cast<const uint4 *>(ins + i);
+    w.x = __builtin_amdgcn_readfirstlane(w.x);
+    w.y = __builtin_amdgcn_readfirstlane(w.y);
+    w.z = __builtin_amdgcn_readfirstlane(w.z);
+    w.w = __builtin_amdgcn_readfirstlane(w.w);
+    StageInstr in;
+    static_assert(sizeof(StageInstr) == sizeof(uint4), "an instruction is four words");
+    __builtin_memcpy(&in, &w, sizeof in);
+    return in;
+}
+
+template <class Input>
+__device__ __forceinline__ void stream_run_loop_program(float *out, const StreamProgArgs &p, float (&regs)[STAGE_REGS][64], float (&ldt)[BANK_STREAM_LOOP_LOADS][64],
+                                                        float (&stt)[BANK_STREAM_LOOP_STORES][64], uint4 (&lins)[BANK_STREAM_LOOP_INSTRS], const StageProg &pg, uint64_t head,
+                                                        uint32_t n, uint32_t lane, bool live, Input &&input) {
+    constexpr uint32_t LM = BANK_STREAM_LOOP_LOADS - 1u, SM = BANK_STREAM_LOOP_STORES - 1u;
+    const uint64_t ring_cap = p.ring_mask + 1;
+    const uint64_t frame = head + lane;
+    const StageInstr *ins = p.instrs + pg.first_instr;
+    const uint32_t stride = pg.pad[0] < BANK_STREAM_LOOP_MAX_STRIDE ? pg.pad[0] : BANK_STREAM_LOOP_MAX_STRIDE;
+    n = n < 64u ? n : 64u;
+    // 0. the program's instructions to LDS, a lane each
+    for (uint32_t i = lane; i < pg.n_instr && i < BANK_STREAM_LOOP_INSTRS; i += 64u) lins[i] = *reinterpret_cast<const uint4 *>(ins + i);
+    stream_wave_phase();
+    auto fetch = [&](uint32_t i) { return stream_loop_instr(lins, ins, i); };
+    // 1. the loads that depend on the frame alone, lane = frame: four round trips to L2 in flight together
+    {
+        uint32_t k = 0;
+        for (uint32_t i = 0; i < pg.n_instr;) {
+            uint32_t at0 = 0, at1 = 0, at2 = 0, at3 = 0, m = 0;   // the next (up to) four loads: the last m of at0..at3
+            for (; i < pg.n_instr && m < 4u; ++i) {
+                const uint32_t op = fetch(i).op;
+                if (op == S_INPUT || op == S_READ) { at0 = at1; at1 = at2; at2 = at3; at3 = i; ++m; }
+            }
+            const uint32_t at[4] = {at0, at1, at2, at3};
+            float ld[4];
+#pragma unroll
+            for (uint32_t j = 0; j < 4u; ++j) {
+                ld[j] = 0.0f;
+                if (j + m >= 4u) {
+                    const StageInstr in = fetch(at[j]);
+                    const bool inside = in.op == S_READ && in.imm != 0u && lane >= in.d_lo;   // phase 2 takes it from the store tile
+                    if (live && !inside) ld[j] = stream_prog_load(p, in, frame, input);
+                }
+            }
+#pragma unroll
+            for (uint32_t j = 0; j < 4u; ++j)
+                if (j + m >= 4u) ldt[(k + j + m - 4u) & LM][lane] = ld[j];
+            k += m;
+        }
+    }
+    stream_wave_phase();
+    // 2. the loops, a lane per residue, every frame on its own register column
+    if (lane < stride) {
+        for (uint32_t f = lane; f < n; f += stride) {
+            uint32_t k = 0;
+            for (uint32_t i = 0; i < pg.n_instr; ++i) {
+                const StageInstr in = fetch(i);
+                float v;
+                switch (in.op) {
+                case S_CONST: v = __uint_as_float(in.imm); break;
+                case S_STEP: v = head + f >= in.d_lo ? __uint_as_float(in.imm) : 0.0f; break;
+                case S_INPUT: v = ldt[k++ & LM][f]; break;
+                case S_READ: {
+                    const uint32_t slot = k++ & LM;
+                    v = in.imm != 0u && f >= in.d_lo ? stt[(in.imm - 1u) & SM][(f - in.d_lo) & 63u] : ldt[slot][f];
+                    break;
+                }
+                case S_SUM2: v = regs[in.a][f] + regs[in.b][f]; break;
+                case S_MUL: v = regs[in.a][f] * regs[in.b][f]; break;
+                case S_DIV: v = regs[in.a][f] / regs[in.b][f]; break;
+                case S_MOD: v = prim_mod(regs[in.a][f], regs[in.b][f]); break;
+                case S_MIN: v = prim_min(regs[in.a][f], regs[in.b][f], p.sparkle != 0u); break;
+                case S_STORE: stt[(in.imm - 1u) & SM][f] = regs[in.a][f]; continue;
+                default: v = 0.0f; break;   // (a Delay of a signal amount, a delayed input: the rule serves no such program)
+                }
+                regs[in.dst][f] = v;
+            }
+        }
+    }
+    stream_wave_phase();
+    // 3. the block's stores, lane = frame
+    for (uint32_t i = 0; i < pg.n_instr; ++i) {
+        const StageInstr in = fetch(i);
+        if (in.op == S_STORE && live)
+            __hip_atomic_store(p.rings + (size_t)in.buf * ring_cap + (frame & p.ring_mask), stt[(in.imm - 1u) & SM][lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    const float res = regs[pg.result_reg][lane];
+    if (live && pg.dst_ring != 0xFFFFFFFFu)
+        __hip_atomic_store(p.rings + (size_t)pg.dst_ring * ring_cap + (frame & p.ring_mask), res, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (live && pg.out_row >= 0) __hip_atomic_store(out + (size_t)pg.out_row * 64u + lane, res, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    stream_wave_phase();   // (the next program's phases write the tiles this one has read)
+}
+
+// stream_run_programs where a program may be a loop program; one of stride 0 is a range of one program of stream_run_programs.
+template <class Input>
+__device__ __forceinline__ void stream_run_programs_loops(float *out, const StreamProgArgs &p, float (&regs)[STAGE_REGS][64], float (&ldt)[BANK_STREAM_LOOP_LOADS][64],
+                                                          float (&stt)[BANK_STREAM_LOOP_STORES][64], uint4 (&lins)[BANK_STREAM_LOOP_INSTRS], uint32_t p_first,
+                                                          uint32_t p_end, uint64_t head, uint32_t n, uint32_t lane, bool live, Input &&input) {
+    for (uint32_t pi = p_first; pi < p_end; ++pi) {
+        if (p.progs[pi].pad[0] == 0u) {
+            stream_run_programs(out, p, regs, pi, pi + 1u, head + lane, lane, live, input);
+            continue;
+        }
+        // what this wave has stored so far (the voice's ring, an earlier program's rings) is in L2 before it is read back
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        const StageProg pg = p.progs[pi];
+        stream_run_loop_program(out, p, regs, ldt, stt, lins, pg, head, n, lane, live, input);
     }
 }
 
@@ -1806,8 +1929,8 @@ hipError_t launch_stage(const StageArgs &a, hipStream_t s) {
 }
 
 // ---------------------------------------------------------------------------------------------------
-// Block streaming of plans with programs (kernels.hpp StreamProgArgs, streamplan.hpp): four more compositions of the pieces
-// above bank_stream_kernel, where the protocol is described.  All four keep the interpreter's registers in LDS, advance `head`
+// Block streaming of plans with programs (kernels.hpp StreamProgArgs, streamplan.hpp): five more compositions of the pieces
+// above bank_stream_kernel, where the protocol is described.  All five keep the interpreter's registers in LDS, advance `head`
 // (the first frame of the block, the same in every workgroup) by each block's length, and in the wave that finishes a voice
 // store the voice and run its programs (stream_voice_programs).  They differ in the doorbell, in where S_INPUT comes from, in
 // whether the block's last arriver runs a bus segment, and in how a workgroup finds its work:
@@ -1817,6 +1940,8 @@ hipError_t launch_stage(const StageArgs &a, hipStream_t s) {
 //   bank_stream_bus_kernel     one row         the block's row         yes           BankArgs
 //   bank_stream_in_kernel      n_rows rows     the row the host named  yes           BankArgs
 //   bank_stream_banks_kernel   n_rows rows     the row the host named  yes           its entry of the bank table
+//   bank_stream_loops_kernel   n_rows rows     the row the host named  yes           its entry of the bank table; loop programs
+//                                                                                    in three phases (stream_run_loop_program)
 //
 // The bus segment is progs[voice_first[n_voices] .. voice_first[n_voices + 1]) and may be empty.  Which kernel a plan launches
 // is the host's rule (streamplan.hpp; fr_plan_json["stream"]["kernel"]).  The compiled kernels against their earlier,
@@ -2019,25 +2144,86 @@ __global__ void __launch_bounds__(1024) bank_stream_banks_kernel(StreamBanksArgs
     if (blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store(&ctl->alive, 0u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-hipError_t launch_bank_stream_banks(const StreamBanksArgs &t, const BankArgs &a, const StreamProgArgs &p, uint32_t n_rows, BankStreamInCtl *ctl_dev, BankStreamInDev *dev,
-                                    uint32_t idle_ms, hipStream_t s) {
-    if (t.n_banks == 0 || t.n_banks > BANK_STREAM_BANKS) return hipErrorInvalidValue;
-    // every bank as the one-bank launchers check theirs; the banks' workgroups and voices follow one another without a gap
-    uint64_t wgs = 0, voices = 0;
+// What the launches with a bank table check: every bank as the one-bank launchers check theirs; the banks' workgroups and
+// voices follow one another without a gap.  `wgs`: the launch's workgroups.
+static bool stream_table_ok(const StreamBanksArgs &t, const BankArgs &a, const StreamProgArgs &p, uint32_t n_rows, uint64_t &wgs) {
+    if (t.n_banks == 0 || t.n_banks > BANK_STREAM_BANKS) return false;
+    uint64_t voices = 0;
     bool to_ring = false;
+    wgs = 0;
     for (uint32_t i = 0; i < t.n_banks; ++i) {
         const StreamBanksArgs::Bank &b = t.bank[i];
-        if (!stream_bank_ok(b.log2_p, b.chunk_log2, b.n_voices, a.ws, a.tickets) || !b.params || !b.rows) return hipErrorInvalidValue;
-        if (b.first_wg != wgs || b.first_voice != voices) return hipErrorInvalidValue;
+        if (!stream_bank_ok(b.log2_p, b.chunk_log2, b.n_voices, a.ws, a.tickets) || !b.params || !b.rows) return false;
+        if (b.first_wg != wgs || b.first_voice != voices) return false;
         wgs += (uint64_t)b.n_voices << (b.log2_p - b.chunk_log2);
         voices += b.n_voices;
-        if (wgs > BANK_STREAM_WGS) return hipErrorInvalidValue;   // all workgroups must be resident
+        if (wgs > BANK_STREAM_WGS) return false;   // all workgroups must be resident
         to_ring = to_ring || b.to_ring != 0;
     }
-    if (voices != a.n_voices || !stream_progs_ok(p, to_ring)) return hipErrorInvalidValue;
-    if (a.leaf_variant != 1 || !a.out || !ctl_dev || !dev) return hipErrorInvalidValue;
-    if (n_rows == 0 || n_rows > BANK_STREAM_ROWS) return hipErrorInvalidValue;
+    if (voices != a.n_voices || !stream_progs_ok(p, to_ring)) return false;
+    if (a.leaf_variant != 1 || !a.out) return false;
+    return n_rows != 0 && n_rows <= BANK_STREAM_ROWS;
+}
+
+hipError_t launch_bank_stream_banks(const StreamBanksArgs &t, const BankArgs &a, const StreamProgArgs &p, uint32_t n_rows, BankStreamInCtl *ctl_dev, BankStreamInDev *dev,
+                                    uint32_t idle_ms, hipStream_t s) {
+    uint64_t wgs = 0;
+    if (!stream_table_ok(t, a, p, n_rows, wgs) || !ctl_dev || !dev) return hipErrorInvalidValue;
     hipLaunchKernelGGL(bank_stream_banks_kernel, dim3((uint32_t)wgs), dim3(1024), 0, s, t, a, p, n_rows, ctl_dev, dev, idle_ms ? idle_ms : BANK_STREAM_IDLE_MS);
+    return hipGetLastError();
+}
+
+// bank_stream_banks_kernel for plans with loop programs (FR_STREAM_LOOPS, kernels.hpp): the bank table also for one bank, the
+// same doorbell, hand-overs and bus segment; the programs go through stream_run_programs_loops with a load and a store tile.
+__global__ void __launch_bounds__(1024) bank_stream_loops_kernel(StreamBanksArgs t, BankArgs a, StreamProgArgs p, uint32_t n_rows, BankStreamInCtl *ctl,
+                                                                 BankStreamInDev *dev, uint32_t idle_ms) {
+    __shared__ float sm[STREAM_NW][64];
+    __shared__ float regs[STAGE_REGS][64];                   // the interpreter's registers: [register][frame] of wave 0
+    __shared__ float ldt[BANK_STREAM_LOOP_LOADS][64];        // a loop program's loads, [load slot][frame]
+    __shared__ float stt[BANK_STREAM_LOOP_STORES][64];       // ... and what it stores to its rings, [store slot][frame]
+    __shared__ uint4 lins[BANK_STREAM_LOOP_INSTRS];          // ... and its (first) instructions
+    __shared__ unsigned long long zshared;
+    __shared__ uint32_t s_seq, s_T;
+    StreamBanksArgs::Bank bk = t.bank[0];
+    static_for<1, (int)BANK_STREAM_BANKS>([&](auto j) {
+        if ((uint32_t)j < t.n_banks && blockIdx.x >= t.bank[j].first_wg) bk = t.bank[j];
+    });
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const StreamWork w = stream_work(bk.params, bk.rows, bk.log2_p, bk.chunk_log2, bk.fast_ok, bk.to_ring, bk.first_voice, blockIdx.x - bk.first_wg, wave);
+    const uint32_t n_voices = a.n_voices;                    // of all banks
+    const unsigned long long idle_ticks = (unsigned long long)idle_ms * 100000ull;
+    uint64_t head = p.head;
+    uint32_t seen = 0;
+    if (blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store(&ctl->alive, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    for (;;) {
+        uint32_t T;
+        const uint32_t seq = stream_next_block(dev, wave, lane, seen, idle_ticks, s_seq, s_T, T, [&](uint32_t &T0) { return stream_rows_wait(n_rows, ctl, dev, lane, seen, idle_ticks, T0); });
+        if (seq == BANK_STREAM_STOP) break;
+        seen = seq;
+        const bool live = lane < T;
+        float t_in, result;
+        const float r = stream_render_chunk(w, dev->rows[0], live, wave, lane, sm, zshared, t_in);
+        if (wave == 0u && stream_hand_over(w, a.ws, a.tickets, n_voices, lane, r, result)) {
+            const StreamRowsInput input{dev, lane, t_in};
+            stream_store_voice(w, a.out, p, head + lane, lane, live, result);
+            stream_run_programs_loops(a.out, p, regs, ldt, stt, lins, p.voice_first[w.voice], p.voice_first[w.voice + 1], head, T, lane, live, input);
+            stream_finish_bus(ctl, dev, n_voices, lane, seq, [&] {
+                stream_run_programs_loops(a.out, p, regs, ldt, stt, lins, p.voice_first[n_voices], p.voice_first[n_voices + 1], head, T, lane, live, input);
+            });
+        }
+        head += T;
+        __syncthreads();   // LDS is reused by the next block
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store(&ctl->alive, 0u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+hipError_t launch_bank_stream_loops(const StreamBanksArgs &t, const BankArgs &a, const StreamProgArgs &p, uint32_t n_rows, uint32_t max_stride, uint32_t max_loads,
+                                    uint32_t max_stores, BankStreamInCtl *ctl_dev, BankStreamInDev *dev, uint32_t idle_ms, hipStream_t s) {
+    if (max_stride > BANK_STREAM_LOOP_MAX_STRIDE || max_loads > BANK_STREAM_LOOP_LOADS || max_stores > BANK_STREAM_LOOP_STORES) return hipErrorInvalidValue;
+    uint64_t wgs = 0;
+    if (!stream_table_ok(t, a, p, n_rows, wgs) || !p.n_rings || !ctl_dev || !dev) return hipErrorInvalidValue;   // (a loop lives in a ring)
+    hipLaunchKernelGGL(bank_stream_loops_kernel, dim3((uint32_t)wgs), dim3(1024), 0, s, t, a, p, n_rows, ctl_dev, dev, idle_ms ? idle_ms : BANK_STREAM_IDLE_MS);
     return hipGetLastError();
 }
 

@@ -266,6 +266,31 @@ struct StreamBanksArgs {
 hipError_t launch_bank_stream_banks(const StreamBanksArgs &t, const BankArgs &a, const StreamProgArgs &p, uint32_t n_rows, BankStreamInCtl *ctl_dev, BankStreamInDev *dev,
                                     uint32_t idle_ms, hipStream_t s);
 
+// bank_stream_loops_kernel (FR_STREAM_LOOPS): bank_stream_banks_kernel's work -- the bank table also for one bank -- for plans
+// whose streamed programs hold feedback loops shorter than a block.  StageProg::pad[0] of a streamed program is its STRIDE
+// (streamplan.hpp stream_loop_prepare): 0 = the program runs lane = frame, as in the other kernels; 1..BANK_STREAM_LOOP_MAX_STRIDE
+// = a loop program, which the finishing wave runs in three phases on a block of n frames at `head`:
+//   1. all lanes, lane = frame: the program's S_INPUTs and S_READs, numbered in program order, go to a load tile
+//      [load slot][frame] in LDS, range test applied, four in flight together -- except a read of a ring the program stores
+//      itself (S_READ.imm = store slot + 1) whose source frame lies inside the block (lane >= d_lo);
+//   2. lanes < stride: lane r walks the frames r, r + stride, ... < n in order, every frame on its own column of the
+//      interpreter's registers, operands from the load tile, an own-ring read with f >= d_lo from the store tile
+//      [store slot][f - d_lo] -- the same lane wrote it, the stride divides d_lo --, every S_STORE (imm = store slot + 1) into
+//      the store tile: no global memory access but the instruction fetch;
+//   3. all lanes, lane = frame, live lanes only: the store tile to the rings, the result to its row.
+// Before phase 1 the wave copies the program's first BANK_STREAM_LOOP_INSTRS instructions to LDS: phase 2 fetches every
+// instruction once per frame, and from global memory each fetch is a dependent trip to L2 (measured: 106 us per block of a
+// one-sample comb without the copy, 100 with it; profiles/stream_loops.txt); instructions beyond the copy come from memory.
+// The stream's copy of a loop program has no dst_ring (the helper turns it into an S_STORE).  Slots are masked, frame loops
+// are bounded by n <= 64.  LDS: the other program kernels' 16 400 bytes + BANK_STREAM_LOOP_LOADS * 256 + BANK_STREAM_LOOP_STORES * 256
+// + BANK_STREAM_LOOP_INSTRS * 16 = 36 880.
+constexpr uint32_t BANK_STREAM_LOOP_LOADS = 32, BANK_STREAM_LOOP_STORES = 16, BANK_STREAM_LOOP_MAX_STRIDE = 63;   // (powers of two: slots are masked)
+constexpr uint32_t BANK_STREAM_LOOP_INSTRS = 512;
+// `max_stride`, `max_loads`, `max_stores`: the largest stride, load count and store-slot count of the streamed programs, as
+// the host prepared them; the launch refuses what the kernel's tiles do not hold.
+hipError_t launch_bank_stream_loops(const StreamBanksArgs &t, const BankArgs &a, const StreamProgArgs &p, uint32_t n_rows, uint32_t max_stride, uint32_t max_loads,
+                                    uint32_t max_stores, BankStreamInCtl *ctl_dev, BankStreamInDev *dev, uint32_t idle_ms, hipStream_t s);
+
 // One step of the partial-block exchange (friendship_render.h FR_SHARD_PARTIALS): row i, window frame t:
 //   v = lo[i][t] + hi[i][t]         the Sum2 node one level up: left sub-tree + right sub-tree, one f32 add
 // stored to dst_ws[i][t] (steps before the last; may alias lo or hi), or -- the last step, dst_ws == null -- where the

@@ -19,6 +19,11 @@
 // that write rows next to voices that feed programs -- is one resident launch too (kernels.hip bank_stream_banks_kernel).
 // Voices are numbered GLOBALLY, banks in plan order, then voices in bank order: everything below that says "voice" means that
 // number.  Each bank has its own chunk size (deal_stream_chunks).
+// With FR_STREAM_LOOPS=1 (StreamEnv::loops) a feedback plan's program may also read, below 64 frames, a ring that it stores
+// ITSELF -- a loop shorter than a block: a one-pole filter, a comb above 750 Hz, a 32-frame bus echo.  Such a LOOP PROGRAM has a
+// stride, the gcd of those delays (stream_loop_stride), and the one wave that runs it walks the residues of the stride in its
+// lanes (kernels.hip bank_stream_loops_kernel): still nobody waits for anybody.  A read below 64 frames of a ring that an
+// EARLIER program of the block stores -- the level behind a loop -- is served too: the reader follows the storer's voice.
 #pragma once
 
 #include <algorithm>
@@ -35,6 +40,14 @@ constexpr uint32_t STREAM_BLOCK = 64;        // the longest block a stream accep
 constexpr uint32_t STREAM_MAX_WGS = 256;     // (= kernels.hpp BANK_STREAM_WGS)
 constexpr uint32_t STREAM_MAX_INPUTS = 8;    // most distinct input slots the streamed programs may read, slot 0 included (= kernels.hpp BANK_STREAM_ROWS)
 constexpr uint32_t STREAM_MAX_BANKS = 8;     // most bank launches one resident launch serves (= kernels.hpp BANK_STREAM_BANKS)
+// A loop program's S_INPUTs and S_READs are numbered into the kernel's load tile, the rings it stores into its store tile
+// (= kernels.hpp BANK_STREAM_LOOP_LOADS / _STORES: 256 bytes of LDS per slot, 12 KiB in all next to the interpreter's 12 KiB of
+// registers and the 8 KiB copy of the program's instructions: 36 880 bytes for the kernel -- one workgroup per CU is
+// resident and may declare 160 KiB, so LDS is not what limits anything; the numbers are twice and 4/3 of the loop-tile
+// rule's 16 and 12, and powers of two because the kernel masks its slots)
+constexpr uint32_t STREAM_LOOP_LOADS = 32, STREAM_LOOP_STORES = 16;
+static_assert(STREAM_LOOP_LOADS == BANK_STREAM_LOOP_LOADS && STREAM_LOOP_STORES == BANK_STREAM_LOOP_STORES && STREAM_BLOCK == BANK_STREAM_LOOP_MAX_STRIDE + 1,
+              "the rule's limits are the kernel's");
 
 // What the rule needs to know besides the plan.
 struct StreamEnv {
@@ -47,6 +60,7 @@ struct StreamEnv {
     bool bus = false;                // FR_STREAM_BUS: programs that read several voices of a block run after the last voice
     bool inputs = false;             // FR_STREAM_INPUTS: programs may read input slots other than 0 at the current frame
     bool banks = false;              // FR_STREAM_BANKS: 2..STREAM_MAX_BANKS bank launches in one resident launch
+    bool loops = false;              // FR_STREAM_LOOPS: feedback loops shorter than a block, and the taps behind them
 };
 
 // One bank of a streamed plan.  Voices [first_voice, first_voice + voices) of the global numbering; workgroups
@@ -104,6 +118,8 @@ struct StreamPlan {
         return n;
     }
     std::vector<uint32_t> progs;         // indices into StagedPlan::progs, voice by voice, then the bus programs, in the order they run
+    std::vector<uint32_t> loop_stride;   // per entry of `progs`: the stride of a loop program (1..63), 0 for any other (StreamEnv::loops)
+    bool has_loops() const { return std::any_of(loop_stride.begin(), loop_stride.end(), [](uint32_t l) { return l != 0; }); }
     std::vector<uint32_t> voice_first;   // [voices + 2] into `progs`: [voice_first[voices], voice_first[voices + 1]) is the bus segment
     uint64_t min_ring_delay = 0;         // shortest delayed read of a ring that a program stores (0: there is none)
     uint64_t lookback = 0;               // deepest ring read of the assigned programs
@@ -121,6 +137,64 @@ inline const char *stage_op_name(uint8_t op) {
     static const char *const names[] = {"S_CONST", "S_INPUT", "S_READ", "S_READ_INPUT", "S_STEP", "S_SUM2", "S_MUL", "S_DIV", "S_MOD", "S_MIN",
                                         "S_STORE", "S_READ_DYN", "S_READ_INPUT_DYN", "S_STEP_DYN"};
     return op < sizeof names / sizeof names[0] ? names[op] : "an unknown op";
+}
+
+// The rings a program stores: its S_STOREs' in program order, then its dst_ring; each once.  A ring's position is its STORE SLOT.
+inline std::vector<uint32_t> stream_stored_rings(const StageProg &pg, const StageInstr *ins) {
+    std::vector<uint32_t> rings;
+    auto add = [&](uint32_t ring) { if (std::find(rings.begin(), rings.end(), ring) == rings.end()) rings.push_back(ring); };
+    for (uint32_t i = 0; i < pg.n_instr; ++i)
+        if (ins[i].op == S_STORE) add(ins[i].buf);
+    if (pg.dst_ring != 0xFFFFFFFFu) add(pg.dst_ring);
+    return rings;
+}
+
+// A program's stride: the gcd of the delays, below a block, with which it reads rings it stores itself (0: it has no such
+// read, it is no loop program).  Own-ring reads of a block or more bind no lane: an earlier block stored those frames.
+inline uint32_t stream_loop_stride(const StageProg &pg, const StageInstr *ins) {
+    const std::vector<uint32_t> mine = stream_stored_rings(pg, ins);
+    uint32_t stride = 0;
+    for (uint32_t i = 0; i < pg.n_instr; ++i) {
+        const StageInstr &in = ins[i];
+        if (in.op != S_READ || in.d_lo == 0 || in.d_lo >= STREAM_BLOCK || std::find(mine.begin(), mine.end(), in.buf) == mine.end()) continue;
+        uint32_t a = stride, b = in.d_lo;
+        while (b) { const uint32_t r = a % b; a = b; b = r; }
+        stride = a;
+    }
+    return stride;
+}
+
+// A loop program's loads as the kernel numbers them into its load tile: every S_INPUT and S_READ, in program order.
+inline uint32_t stream_loop_loads(const StageProg &pg, const StageInstr *ins) {
+    uint32_t n = 0;
+    for (uint32_t i = 0; i < pg.n_instr; ++i) n += ins[i].op == S_INPUT || ins[i].op == S_READ ? 1u : 0u;
+    return n;
+}
+
+// The stream's own copy of a loop program (`ins`: its pg.n_instr instructions, copied; `pg`: its streamed StageProg).  Every
+// ring the program stores gets a store slot, S_STORE.imm = slot + 1; every read of one of them is marked with it, S_READ.imm =
+// slot + 1, every other S_READ gets imm = 0 -- the plan's carry annotations (kernels.hpp STAGE_CARRY), which depend on
+// FR_LOOP_TILES, are overwritten here and only here --; a dst_ring becomes an S_STORE of the result at the end; the stride goes
+// to pg.pad[0].  False (nothing the kernel may run) when the program is no loop program or exceeds the tiles.
+inline bool stream_loop_prepare(StageProg &pg, std::vector<StageInstr> &ins) {
+    if (ins.size() != pg.n_instr) return false;
+    const uint32_t stride = stream_loop_stride(pg, ins.data());
+    const std::vector<uint32_t> mine = stream_stored_rings(pg, ins.data());
+    if (stride == 0 || mine.size() > STREAM_LOOP_STORES || stream_loop_loads(pg, ins.data()) > STREAM_LOOP_LOADS) return false;
+    auto slot = [&](uint32_t ring) { return (uint32_t)(std::find(mine.begin(), mine.end(), ring) - mine.begin()); };
+    for (StageInstr &in : ins) {
+        if (in.op == S_STORE) in.imm = slot(in.buf) + 1u;
+        if (in.op == S_READ) in.imm = slot(in.buf) < mine.size() ? slot(in.buf) + 1u : 0u;
+    }
+    if (pg.dst_ring != 0xFFFFFFFFu) {
+        StageInstr st{};
+        st.op = S_STORE; st.a = (uint8_t)pg.result_reg; st.buf = pg.dst_ring; st.imm = slot(pg.dst_ring) + 1u;
+        ins.push_back(st);
+        pg.dst_ring = 0xFFFFFFFFu;
+        ++pg.n_instr;
+    }
+    pg.pad[0] = stride;
+    return true;
 }
 
 // `banks`: the plan's bank launches (the engine moves them out of StagedPlan::banks when it uploads them).
@@ -204,6 +278,8 @@ inline StreamPlan plan_stream(const StagedPlan &sp, const std::vector<const Bank
     constexpr uint32_t NONE = UINT32_MAX;
     const uint32_t BUS = V;                                   // "voice" of a bus program: the segment after the last voice's
     std::vector<uint32_t> voice_of(run.size(), NONE);
+    const bool loops = env.loops && sp.feedback;              // FR_STREAM_LOOPS concerns a feedback plan's one-launch form
+    std::vector<uint32_t> stride_of(run.size(), 0);
     // FR_STREAM_BUS: a program is a bus program when, at a delay below a block, it reads the bank rings of two or more voices
     // or a ring that an earlier bus program stores (a feedback plan's row copy of such a ring included)
     auto is_bus = [&](uint32_t k) {
@@ -221,6 +297,10 @@ inline StreamPlan plan_stream(const StagedPlan &sp, const std::vector<const Bank
             }
             auto st = stored_by.find(in.buf);
             if (st != stored_by.end() && st->second < k && voice_of[st->second] == BUS) return true;
+            if (loops && st != stored_by.end() && st->second < k) {   // a tap behind a loop: it follows the storer's voice
+                if (one != NONE && one != voice_of[st->second]) return true;
+                one = voice_of[st->second];
+            }
         }
         return false;
     };
@@ -255,6 +335,13 @@ inline StreamPlan plan_stream(const StagedPlan &sp, const std::vector<const Bank
                     mine = bv->second;
                     break;
                 }
+                if (loops && in.d_lo != 0 && in.d_lo < STREAM_BLOCK) {   // a ring the program stores itself: a loop shorter than a block
+                    auto st = stored_by.find(in.buf);
+                    if (st != stored_by.end() && st->second == k) {
+                        min_delay = std::min<uint64_t>(min_delay, in.d_lo);
+                        break;                                       // (its stride: stream_loop_stride, below)
+                    }
+                }
                 if (bus && in.d_lo < STREAM_BLOCK) {                 // a ring an EARLIER program of the block stores: it has finished
                     auto st = stored_by.find(in.buf);
                     if (st != stored_by.end() && st->second < k) break;
@@ -266,6 +353,18 @@ inline StreamPlan plan_stream(const StagedPlan &sp, const std::vector<const Bank
                     if (st == stored_by.end() || voice_of[st->second] == NONE) return refuse("internal: a row copy of a ring no streamed program stores");
                     mine = voice_of[st->second];
                     break;
+                }
+                if (loops && in.d_lo < STREAM_BLOCK) {               // a ring an EARLIER program stores, on one voice: the level behind a loop
+                    auto st = stored_by.find(in.buf);
+                    if (st != stored_by.end() && st->second < k) {
+                        const uint32_t theirs = voice_of[st->second];
+                        if (mine != NONE && mine != theirs)
+                            return refuse("a program reads voices " + std::to_string(mine) + " and " + std::to_string(theirs) +
+                                          " in the same block (a mix bus across voices); each streamed program follows one voice");
+                        mine = theirs;
+                        min_delay = std::min<uint64_t>(min_delay, in.d_lo);
+                        break;
+                    }
                 }
                 if (in.d_lo < STREAM_BLOCK)
                     return refuse("a program's ring is read " + std::to_string(in.d_lo) + " frames back; a streamed block needs delays of at least " +
@@ -280,6 +379,14 @@ inline StreamPlan plan_stream(const StagedPlan &sp, const std::vector<const Bank
             if (in.dst >= STAGE_REGS || in.a >= STAGE_REGS || in.b >= STAGE_REGS) return refuse("a program needs more registers than the streamed interpreter has");
         }
         if (pg.result_reg >= STAGE_REGS) return refuse("a program needs more registers than the streamed interpreter has");
+        if (loops && (stride_of[k] = stream_loop_stride(pg, sp.instrs.data() + pg.first_instr)) != 0) {
+            const uint32_t n_ld = stream_loop_loads(pg, sp.instrs.data() + pg.first_instr);
+            const size_t n_st = stream_stored_rings(pg, sp.instrs.data() + pg.first_instr).size();
+            if (n_ld > STREAM_LOOP_LOADS)
+                return refuse("a loop program has " + std::to_string(n_ld) + " frame-only loads; block streaming serves at most " + std::to_string(STREAM_LOOP_LOADS));
+            if (n_st > STREAM_LOOP_STORES)
+                return refuse("a loop program stores " + std::to_string(n_st) + " rings; block streaming serves at most " + std::to_string(STREAM_LOOP_STORES));
+        }
         voice_of[k] = bus ? BUS : mine != NONE ? mine : run[k] % V;   // (reads no voice at a short delay: any one voice, the same every time)
     }
     std::sort(others.begin(), others.end());
@@ -303,8 +410,12 @@ inline StreamPlan plan_stream(const StagedPlan &sp, const std::vector<const Bank
     for (uint32_t k = 0; k < run.size(); ++k) ++s.voice_first[voice_of[k] + 1];
     for (uint32_t v = 0; v <= V; ++v) s.voice_first[v + 1] += s.voice_first[v];
     s.progs.resize(run.size());
+    s.loop_stride.resize(run.size());
     std::vector<uint32_t> at(s.voice_first.begin(), s.voice_first.end() - 1);
-    for (uint32_t k = 0; k < run.size(); ++k) s.progs[at[voice_of[k]]++] = run[k];   // (stable: the order of `run` inside a voice)
+    for (uint32_t k = 0; k < run.size(); ++k) {                                      // (stable: the order of `run` inside a voice)
+        s.loop_stride[at[voice_of[k]]] = stride_of[k];
+        s.progs[at[voice_of[k]]++] = run[k];
+    }
     s.min_ring_delay = min_delay == UINT64_MAX ? 0 : min_delay;
     s.input_slots.insert(s.input_slots.end(), others.begin(), others.end());
     s.servable = true;
