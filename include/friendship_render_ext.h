@@ -102,6 +102,20 @@ extern "C" {
  * program.  Still refused: a loop program of more than 32 loads (input rows and delay-line reads) or 16 stored delay lines
  * (the reason names the count and the limit), a Delay shorter than 64 frames of a computed value in a plan without a loop,
  * delayed reads of an input row, signal-amount delays, and everything else of the lists above.
+ *
+ * FR_STREAM_GENERAL = 0 / 1 (default 0; read strictly from the environment too; does nothing unless FR_STREAM_PROGRAMS=1):
+ * block streaming also serves voices of ANY partial count and any tree of sums -- 24, 100, 300, 1000 partials, a chain, a
+ * lopsided tree: what fr_fill_buffer renders as general voices -- and balanced voices of 32 or 64 partials.  Such a voice is
+ * rendered by one workgroup of a seventh resident kernel (bank_stream_general_kernel), which runs the voice's schedule -- its
+ * complete sub-trees of up to 2048 leaves, each split over up to 16 waves, then the sums above them -- exactly as the
+ * ordinary path does: same bits.  Everything behind the voices (programs, FR_STREAM_BUS, FR_STREAM_INPUTS, FR_STREAM_LOOPS)
+ * applies to such voices as to any other; next to voices of other sizes they need FR_STREAM_BANKS like any second bank.  With
+ * 0 nothing changes: the same plans are served and refused, with the same reasons, by the same kernels.  "stream" gains
+ * "general_voices" (the leaf count of every voice served this way, in voice order; [] when there is none) and
+ * "general_max_leaves"; with FR_STREAM_BANKS the "banks" entries gain "general" (such a bank reports its largest voice as
+ * "partials" and 1 chunk); "kernel" is "bank_stream_general_kernel" exactly when a voice is served this way.  Still refused:
+ * a voice of more than 32768 leaves (one workgroup renders it; the reason names the count and the limit), more voices than
+ * the device has compute units, compiled and track voices.
  */
 typedef struct fr_option {
     const char *name;              /* e.g. "FR_BANK_SHORT" */

@@ -197,7 +197,7 @@ static std::string stage_variant(const StageLaunchNote &n, const Plan &p) {
     return k;
 }
 
-constexpr size_t N_OPTIONS = 36;         // per-renderer options (friendship_render_ext.h; the table below fr_renderer)
+constexpr size_t N_OPTIONS = 37;         // per-renderer options (friendship_render_ext.h; the table below fr_renderer)
 
 struct TimerClass {
     double ms = 0;
@@ -257,6 +257,10 @@ __attribute__((weak)) hipError_t launch_bank_stream_banks(const StreamBanksArgs 
 }
 __attribute__((weak)) hipError_t launch_bank_stream_loops(const StreamBanksArgs &, const BankArgs &, const StreamProgArgs &, uint32_t, uint32_t, uint32_t, uint32_t, BankStreamInCtl *,
                                                           BankStreamInDev *, uint32_t, hipStream_t) {
+    return hipErrorNotSupported;
+}
+__attribute__((weak)) hipError_t launch_bank_stream_general(const StreamBanksArgs &, const StreamGeneralArgs &, const BankArgs &, const StreamProgArgs &, uint32_t, uint32_t, uint32_t,
+                                                            uint32_t, BankStreamInCtl *, BankStreamInDev *, uint32_t, hipStream_t) {
     return hipErrorNotSupported;
 }
 __attribute__((weak)) hipError_t launch_track_window(const TrackWindowArgs &a, hipStream_t) {
@@ -561,6 +565,7 @@ struct fr_renderer {
     bool stream_inputs = false;          // FR_STREAM_INPUTS: programs read control rows, up to STREAM_MAX_INPUTS slots (bank_stream_in_kernel)
     bool stream_loops = false;           // FR_STREAM_LOOPS: feedback loops shorter than a block (bank_stream_loops_kernel)
     bool stream_banks = false;           // FR_STREAM_BANKS: 2..STREAM_MAX_BANKS bank launches in one resident launch (bank_stream_banks_kernel)
+    bool stream_general = false;         // FR_STREAM_GENERAL: schedule banks -- voices of any partial count (bank_stream_general_kernel)
     bool stream_prog = false;            // the open stream is of that kind
     bool stream_in = false;              // ... and its doorbell is the rows of stream_plan.input_slots (BankStreamInCtl / BankStreamInDev)
     StreamRows stream_rows;              // the input store's rules for the open stream's rows, without the samples (streamrows.hpp)
@@ -569,6 +574,10 @@ struct fr_renderer {
     const char *stream_kernel = "";      // the last resident launch's kernel (fr_plan_json "stream")
     StreamPlan stream_plan;
     DevBuf d_stream_progs, d_stream_vfirst;
+    // FR_STREAM_GENERAL: the one-item schedules of the open stream's balanced 32- and 64-partial banks, built at stream begin;
+    // per plan bank the word offsets of its groups and group_off in d_stream_sched (SIZE_MAX: the bank has none of its own here)
+    DevBuf d_stream_sched;
+    std::vector<std::pair<size_t, size_t>> stream_sched_at;
     StreamPlan plan_stream_now() const {
         std::vector<const BankLaunch *> banks;
         for (const BankStage &bs : plan.banks) banks.push_back(&bs.grp);
@@ -583,6 +592,7 @@ struct fr_renderer {
         env.inputs = stream_inputs;
         env.banks = stream_banks;
         env.loops = stream_loops;
+        env.general = stream_general;
         return plan_stream(plan.sp, banks, env);
     }
     // Rings the stop and waits for the resident launch to end.  `clean`: the launch was answering when the stop was rung
@@ -2183,11 +2193,42 @@ void fr_renderer::begin_program_stream(uint32_t n_slots) {
         for (uint32_t row : grp.rows)
             if (row >= (grp.to_ring ? sp.n_rings : n_slots)) throw Error(FR_ERR_DEVICE, "internal: a streamed voice's row out of bounds");
     }
+    // schedule banks (FR_STREAM_GENERAL): every voice's schedule stays inside the bank's items and parameters (the rule has
+    // validated its stack); the one-item schedules of balanced 32- and 64-partial banks are built and uploaded here, once
+    stream_sched_at.assign(plan.banks.size(), {SIZE_MAX, SIZE_MAX});
+    if (s.has_general()) {
+        std::vector<uint32_t> words;
+        for (size_t i = 0; i < plan.banks.size(); ++i) {
+            if (!s.banks[i].general) continue;
+            const BankLaunch &grp = plan.banks[i].grp;
+            std::vector<uint32_t> own_groups, own_off;
+            if (!grp.general) stream_balanced_schedule(s.banks[i].voices, grp.log2_p, own_groups, own_off);
+            const std::vector<uint32_t> &groups = grp.general ? grp.groups : own_groups, &group_off = grp.general ? grp.group_off : own_off;
+            for (uint32_t v = 0; v < s.banks[i].voices; ++v)
+                if (!stream_schedule_ok(groups, group_off, v) ||
+                    (uint64_t)group_off[2 * v + 1] * 8u + stream_schedule_pairs(groups, group_off, v) > grp.params.size() / 2)
+                    throw Error(FR_ERR_DEVICE, "internal: a streamed voice's schedule out of the bank's bounds");
+            if (grp.general) {
+                if (plan.banks[i].d_groups.bytes < groups.size() * sizeof(uint32_t) || plan.banks[i].d_group_off.bytes < group_off.size() * sizeof(uint32_t))
+                    throw Error(FR_ERR_DEVICE, "internal: a general bank without its device schedule");
+                continue;
+            }
+            stream_sched_at[i] = {words.size(), words.size() + own_groups.size()};
+            words.insert(words.end(), own_groups.begin(), own_groups.end());
+            words.insert(words.end(), own_off.begin(), own_off.end());
+        }
+        d_stream_sched.ensure(std::max<size_t>(words.size(), 1) * sizeof(uint32_t));
+        if (!words.empty()) {
+            HIP_CHECK(hipMemcpyAsync(d_stream_sched.p, words.data(), words.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+            HIP_CHECK(hipStreamSynchronize(stream));   // (`words` goes out of scope)
+        }
+    }
     // programs that read control rows (FR_STREAM_INPUTS): the stream's own copy of their instructions, S_INPUT's operand the
     // streamed row (the position of its slot in input_slots) instead of the plan's input index
     // (several banks: bank_stream_banks_kernel, whose control words and S_INPUT are those of the kernel with control rows)
     // (loop programs, FR_STREAM_LOOPS: bank_stream_loops_kernel, the same control words; the copy also carries their store slots)
-    const bool rows_in = s.input_slots.size() > 1 || s.banks.size() > 1 || s.has_loops();
+    // (schedule banks, FR_STREAM_GENERAL: bank_stream_general_kernel, the same control words)
+    const bool rows_in = s.input_slots.size() > 1 || s.banks.size() > 1 || s.has_loops() || s.has_general();
     std::vector<StageInstr> instrs;
     if (rows_in) {
         if (s.input_slots.size() > BANK_STREAM_ROWS) throw Error(FR_ERR_DEVICE, "internal: more streamed rows than the kernel takes");
@@ -2307,15 +2348,29 @@ void fr_renderer::seek_program_stream(uint64_t idx) {
     HIP_CHECK(hipMemsetAsync(d_stream_dev.p, 0, stream_in ? sizeof(BankStreamInDev) : sizeof(BankStreamDev), stream));
     // a plan whose programs read control rows (FR_STREAM_INPUTS): the kernel with a doorbell of rows; a plan with bus programs
     // (FR_STREAM_BUS): the kernel whose last arriver of a block runs them; every other plan: as before
-    if (s.banks.size() > 1 || s.has_loops()) {
-        // voices of several banks (FR_STREAM_BANKS), loop programs (FR_STREAM_LOOPS: also for one bank): the bank table travels
-        // in the kernel arguments; chunk sums and tickets are laid out by global voice
+    if (s.banks.size() > 1 || s.has_loops() || s.has_general()) {
+        // voices of several banks (FR_STREAM_BANKS), loop programs (FR_STREAM_LOOPS: also for one bank), schedule banks
+        // (FR_STREAM_GENERAL: also for one bank, and a second table of their schedules): the bank table travels in the kernel
+        // arguments; chunk sums and tickets are laid out by global voice
         StreamBanksArgs t{};
+        StreamGeneralArgs g{};
         t.n_banks = (uint32_t)s.banks.size();
         for (size_t i = 0; i < s.banks.size(); ++i) {
             const BankStage &b = plan.banks[i];
             const StreamBank &sb = s.banks[i];
-            if (b.grp.rows.size() != sb.voices || b.grp.log2_p != sb.log2_p) throw Error(FR_ERR_DEVICE, "internal: the stream's banks are not the plan's");
+            if (b.grp.rows.size() != sb.voices || (!b.grp.general && b.grp.log2_p != sb.log2_p) || (b.grp.general && !sb.general))
+                throw Error(FR_ERR_DEVICE, "internal: the stream's banks are not the plan's");
+            if (sb.general) {                                    // its schedule: the ordinary launch's device copy, or the stream's own
+                g.mask |= 1u << i;
+                if (b.grp.general) {
+                    g.bank[i].groups = b.d_groups.as<uint32_t>();
+                    g.bank[i].group_off = b.d_group_off.as<uint32_t>();
+                } else {
+                    if (i >= stream_sched_at.size() || stream_sched_at[i].first == SIZE_MAX) throw Error(FR_ERR_DEVICE, "internal: a schedule bank without its schedule");
+                    g.bank[i].groups = d_stream_sched.as<uint32_t>() + stream_sched_at[i].first;
+                    g.bank[i].group_off = d_stream_sched.as<uint32_t>() + stream_sched_at[i].second;
+                }
+            }
             t.bank[i].params = b.d_params.as<float2>();
             t.bank[i].rows = b.d_rows.as<uint32_t>();
             t.bank[i].first_wg = sb.first_wg;
@@ -2333,16 +2388,20 @@ void fr_renderer::seek_program_stream(uint64_t idx) {
         a.fast_ok = 0;
         p.bank_to_ring = 0;
         p.instrs = d_stream_instrs.as<StageInstr>();
-        if (s.has_loops()) {
-            // (the tiles' fill is re-counted from the plan's instructions; the store slots are the stored rings)
-            uint32_t max_stride = 0, max_loads = 0, max_stores = 0;
-            for (size_t i = 0; i < s.progs.size(); ++i) {
-                if (!s.loop_stride[i]) continue;
-                const StageProg &pg = sp.progs[s.progs[i]];
-                max_stride = std::max(max_stride, s.loop_stride[i]);
-                max_loads = std::max(max_loads, stream_loop_loads(pg, sp.instrs.data() + pg.first_instr));
-                max_stores = std::max<uint32_t>(max_stores, (uint32_t)stream_stored_rings(pg, sp.instrs.data() + pg.first_instr).size());
-            }
+        // (the tiles' fill is re-counted from the plan's instructions; the store slots are the stored rings)
+        uint32_t max_stride = 0, max_loads = 0, max_stores = 0;
+        for (size_t i = 0; i < s.progs.size(); ++i) {
+            if (!s.loop_stride[i]) continue;
+            const StageProg &pg = sp.progs[s.progs[i]];
+            max_stride = std::max(max_stride, s.loop_stride[i]);
+            max_loads = std::max(max_loads, stream_loop_loads(pg, sp.instrs.data() + pg.first_instr));
+            max_stores = std::max<uint32_t>(max_stores, (uint32_t)stream_stored_rings(pg, sp.instrs.data() + pg.first_instr).size());
+        }
+        if (s.has_general()) {
+            HIP_CHECK(launch_bank_stream_general(t, g, a, p, (uint32_t)s.input_slots.size(), max_stride, max_loads, max_stores, h_stream_ctl.as_dev<BankStreamInCtl>(),
+                                                 d_stream_dev.as<BankStreamInDev>(), stream_idle_ms, stream));
+            stream_kernel = "bank_stream_general_kernel";
+        } else if (s.has_loops()) {
             HIP_CHECK(launch_bank_stream_loops(t, a, p, (uint32_t)s.input_slots.size(), max_stride, max_loads, max_stores, h_stream_ctl.as_dev<BankStreamInCtl>(),
                                                d_stream_dev.as<BankStreamInDev>(), stream_idle_ms, stream));
             stream_kernel = "bank_stream_loops_kernel";
@@ -2428,6 +2487,7 @@ int64_t env_strict_stream_inputs(const char *e);
 int64_t env_strict_stream_banks(const char *e);
 int64_t env_strict_loop_tiles(const char *e);
 int64_t env_strict_stream_loops(const char *e);
+int64_t env_strict_stream_general(const char *e);
 bool parse_option(const Knob &k, const char *s, int64_t &v);
 
 const Knob kKnobs[] = {
@@ -2520,6 +2580,10 @@ const Knob kKnobs[] = {
     // taps behind them (streamplan.hpp StreamEnv::loops; fr_plan_json: stream.loop_programs).  Inert without FR_STREAM_PROGRAMS.
     // Strict and listed once set.
     {"FR_STREAM_LOOPS", 0, 0, 1, 0, nullptr, 0, env_strict_stream_loops, [](fr_renderer &r, int64_t v, bool) { r.stream_loops = v != 0; }, LISTED_WHEN_SET},
+    // Voices of any partial count in block streaming: general voices (items plus a merge schedule) and balanced voices of 32 or
+    // 64 partials, one workgroup per voice (streamplan.hpp StreamEnv::general; fr_plan_json: stream.general_voices).  Inert
+    // without FR_STREAM_PROGRAMS.  Strict and listed once set.
+    {"FR_STREAM_GENERAL", 0, 0, 1, 0, nullptr, 0, env_strict_stream_general, [](fr_renderer &r, int64_t v, bool) { r.stream_general = v != 0; }, LISTED_WHEN_SET},
 };
 static_assert(sizeof kKnobs / sizeof kKnobs[0] == N_OPTIONS, "N_OPTIONS counts the rows of kKnobs");
 
@@ -2537,6 +2601,7 @@ int64_t env_strict_stream_inputs(const char *e) { return env_strict("FR_STREAM_I
 int64_t env_strict_stream_banks(const char *e) { return env_strict("FR_STREAM_BANKS", e); }
 int64_t env_strict_loop_tiles(const char *e) { return env_strict("FR_LOOP_TILES", e); }
 int64_t env_strict_stream_loops(const char *e) { return env_strict("FR_STREAM_LOOPS", e); }
+int64_t env_strict_stream_general(const char *e) { return env_strict("FR_STREAM_GENERAL", e); }
 
 bool parse_option(const Knob &k, const char *s, int64_t &v) {
     if (k.word && std::strcmp(s, k.word) == 0) {
@@ -2912,8 +2977,11 @@ fr_status fr_stream_begin(fr_renderer *r, uint32_t n_slots) {
         r->order_after_previous(r->stream);
         r->ensure_plan(n_slots, r->stream);
         const StagedPlan &sp = r->plan.sp;
-        // (FR_STREAM_BANKS: a plan of several banks takes this path even when it has no programs and no rings)
-        if (r->stream_programs && (!sp.progs.empty() || sp.uses_rings() || (r->stream_banks && r->plan.banks.size() > 1))) {
+        // (FR_STREAM_BANKS: a plan of several banks takes this path even when it has no programs and no rings; FR_STREAM_GENERAL: so
+        // does a plan with a bank that the option may serve by schedule -- general voices, voices below 128 partials)
+        const bool by_schedule = r->stream_general && std::any_of(r->plan.banks.begin(), r->plan.banks.end(),
+                                                                  [](const BankStage &b) { return b.grp.general || b.grp.log2_p < 7; });
+        if (r->stream_programs && (!sp.progs.empty() || sp.uses_rings() || (r->stream_banks && r->plan.banks.size() > 1) || by_schedule)) {
             r->begin_program_stream(n_slots);
             return;
         }
@@ -3196,16 +3264,23 @@ const char *fr_plan_json(fr_renderer *r) {
                 r->plan_json_cache += ",\"loop_programs\":[" + lp + "],\"loop_loads\":" + std::to_string(STREAM_LOOP_LOADS) + ",\"loop_stores\":" + std::to_string(STREAM_LOOP_STORES);
             }
             // (the kernel a servable plan will get where the plan decides it; else the last resident launch's, unless that was one of those)
+            if (r->stream_general) {                             // FR_STREAM_GENERAL: the leaves of every voice served by schedule, by global voice
+                std::string gv;
+                for (uint32_t n : s.general_voices) gv += (gv.empty() ? "" : ",") + std::to_string(n);
+                r->plan_json_cache += ",\"general_voices\":[" + gv + "],\"general_max_leaves\":" + std::to_string(STREAM_GENERAL_MAX_LEAVES);
+            }
             const bool last_stands = std::strcmp(r->stream_kernel, "bank_stream_in_kernel") && std::strcmp(r->stream_kernel, "bank_stream_banks_kernel") &&
-                                     std::strcmp(r->stream_kernel, "bank_stream_loops_kernel");
-            const char *kernel = s.servable && s.has_loops() ? "bank_stream_loops_kernel"
+                                     std::strcmp(r->stream_kernel, "bank_stream_loops_kernel") && std::strcmp(r->stream_kernel, "bank_stream_general_kernel");
+            const char *kernel = s.servable && s.has_general() ? "bank_stream_general_kernel"
+                                 : s.servable && s.has_loops() ? "bank_stream_loops_kernel"
                                  : s.servable && s.banks.size() > 1 ? "bank_stream_banks_kernel"
                                  : s.servable && s.input_slots.size() > 1 ? "bank_stream_in_kernel" : last_stands ? r->stream_kernel : "";
             if (r->stream_banks) {                               // FR_STREAM_BANKS: the banks of the launch, in plan order
                 std::string bl;
                 for (const StreamBank &b : s.banks)
-                    bl += std::string(bl.empty() ? "" : ",") + "{\"voices\":" + std::to_string(b.voices) + ",\"partials\":" + std::to_string(1u << b.log2_p) +
-                          ",\"chunks\":" + std::to_string(1u << (b.log2_p - b.chunk_log2)) + ",\"to_ring\":" + (b.to_ring ? "true" : "false") + "}";
+                    bl += std::string(bl.empty() ? "" : ",") + "{\"voices\":" + std::to_string(b.voices) + ",\"partials\":" + std::to_string(b.general ? b.max_leaves : 1u << b.log2_p) +
+                          ",\"chunks\":" + std::to_string(1u << (b.log2_p - b.chunk_log2)) + ",\"to_ring\":" + (b.to_ring ? "true" : "false") +
+                          (r->stream_general ? std::string(",\"general\":") + (b.general ? "true" : "false") : std::string()) + "}";
                 r->plan_json_cache += ",\"banks\":[" + bl + "],\"workgroups\":" + std::to_string(s.workgroups()) +
                                       ",\"max_workgroups\":" + std::to_string(stream_max_wgs((uint32_t)std::max(r->device_cus, 0)));
             }

@@ -1005,6 +1005,146 @@ __device__ __forceinline__ float stream_render_chunk(const StreamWork &w, const 
     return r;
 }
 
+// A SCHEDULE voice (FR_STREAM_GENERAL, kernels.hpp StreamGeneralArgs): gbank_tile for 16 waves.  gbank_group and the depth of
+// the evaluation stack are the general voices' own, further down (GB_MAX_DEPTH).
+template <bool FAST>
+__device__ __forceinline__ float gbank_group(const ParamGroup &pg, uint32_t j, float t);
+constexpr uint32_t STREAM_STACK_DEPTH = 16;
+
+// The items of the voice in schedule order, lane = frame.  An item of 2^k >= 16 leaves is a complete sub-tree: the first
+// min(16, 2^(k-3)) waves each sum 2^(k-7) groups of 8 (one group below 128 leaves) with the balanced kernel's inner loop, the
+// wave sums meet in `sm` and wave 0 adds them in tree order -- adjacent pairs, the ladder of stream_render_chunk, of which an
+// item of fewer than 128 leaves takes a lower rung.  One barrier per such item: its condition is the schedule word, uniform
+// for the workgroup, and every wave of the workgroup walks every item.  The hand-over is double-buffered as in gbank_tile (item
+// i + 2 reuses item i's buffer only after the barrier of item i + 1, which wave 0 reaches after it has read item i's).  Items
+// of at most 8 leaves and every merge (v = pop() + v, the tree's own add, left operand on the left) run on wave 0, on its LDS
+// stack.  Returns the root in wave 0.
+template <bool FAST>
+__device__ __forceinline__ float stream_schedule_sum(const float *params, const uint32_t *gmeta, uint32_t nitems, float t, uint32_t wave, uint32_t lane,
+                                                     float *stack /* wave 0: [STREAM_STACK_DEPTH][64] + lane */, float (&sm)[2][STREAM_NW][64]) {
+    constexpr int NW = STREAM_NW;
+    uint32_t sp = 0;
+    const_f32_ptr p = (const_f32_ptr)params;
+    typedef uint32_t __attribute__((address_space(4))) const *const_u32_ptr;
+    const_u32_ptr gm = (const_u32_ptr)gmeta;
+    auto finish = [&](float v, uint32_t meta) {        // wave 0 only; (the host validated the schedule: the masks never bite)
+        for (uint32_t m = meta >> 4; m != 0u; --m) {   // v = pop() + v
+            --sp;
+            v = stack[(sp & (STREAM_STACK_DEPTH - 1u)) * 64u] + v;
+        }
+        stack[(sp & (STREAM_STACK_DEPTH - 1u)) * 64u] = v;
+        ++sp;
+    };
+    uint32_t goff = 0;          // parameter group (8 pairs) the current item starts at
+    uint32_t nbig = 0;
+    for (uint32_t i = 0; i < nitems; ++i) {
+        const uint32_t meta = gm[i];
+        const uint32_t k = meta & 15u;
+        if (k >= 4u) {          // 16..2048 leaves
+            const uint32_t wl = k >= 7u ? 4u : k - 3u;   // log2 of the waves that work on it
+            const uint32_t lv = k - 3u - wl;             // ... and of the groups each of them sums
+            float(&buf)[NW][64] = sm[nbig & 1u];
+            ++nbig;
+            if (wave < (1u << wl)) {
+                const float tt[1] = {t};
+                float res[1];
+                bank_wave_sum<1, FAST, false>(params + ((size_t)goff + ((size_t)wave << lv)) * 16u, 1u << lv, lv, tt, res);
+                buf[wave][lane] = res[0];
+            }
+            __syncthreads();    // (uniform: k is the schedule's)
+            if (wave == 0u) {   // the ladder; rows of waves that did not work hold whatever they held and reach no rung that is taken
+                float s[NW];
+                static_for<0, NW>([&](auto j) { s[j] = buf[j][lane]; });
+                static_for<0, NW / 2>([&](auto j) { s[j] = s[2 * j] + s[2 * j + 1]; });
+                const float a1 = s[0];
+                static_for<0, NW / 4>([&](auto j) { s[j] = s[2 * j] + s[2 * j + 1]; });
+                const float a2 = s[0];
+                static_for<0, NW / 8>([&](auto j) { s[j] = s[2 * j] + s[2 * j + 1]; });
+                const float a3 = s[0];
+                static_for<0, NW / 16>([&](auto j) { s[j] = s[2 * j] + s[2 * j + 1]; });
+                float v = s[0];
+                v = wl == 3u ? a3 : v;
+                v = wl == 2u ? a2 : v;
+                v = wl == 1u ? a1 : v;
+                finish(v, meta);
+            }
+            goff += 1u << (k - 3u);
+        } else {
+            if (wave == 0u) {   // 1..8 leaves: one group, padding pairs are not leaves
+                ParamGroup cur;
+                load_group(cur, p, goff);
+                __builtin_amdgcn_s_waitcnt(0xC07F);
+                finish(gbank_group<FAST>(cur, k, t), meta);
+            }
+            goff += 1u;
+        }
+    }
+    return wave == 0u ? stack[0] : 0.0f;   // a validated schedule leaves exactly the root
+}
+
+// Whether every leaf of this wave's share of the voice is -0 at the lanes `zm`, shaped like the sum: the waves that summed an
+// item scan it, wave 0 the leaves of the small items; a wave without a share answers true.
+template <bool FAST>
+__device__ __forceinline__ bool stream_schedule_negzero(const float *params, const uint32_t *gmeta, uint32_t nitems, float t, uint32_t wave, unsigned long long zm) {
+    typedef uint32_t __attribute__((address_space(4))) const *const_u32_ptr;
+    const_u32_ptr gm = (const_u32_ptr)gmeta;
+    bool ok = true;
+    uint32_t goff = 0;
+    for (uint32_t i = 0; i < nitems; ++i) {
+        const uint32_t k = gm[i] & 15u;
+        if (k >= 4u) {
+            const uint32_t wl = k >= 7u ? 4u : k - 3u;
+            const uint32_t lv = k - 3u - wl;
+            if (wave < (1u << wl)) {
+                const bool item = wave_leaves_all_negzero<FAST>(params + ((size_t)goff + ((size_t)wave << lv)) * 16u, 1u << lv, t, zm);
+                ok = ok && item;
+            }
+            goff += 1u << (k - 3u);
+        } else {
+            if (wave == 0u) {
+                for (uint32_t j = 0; j < (1u << k); ++j) {
+                    const float2 pr = ((const float2 *)params)[(size_t)goff * 8u + j];   // wave-uniform address
+                    ok = ok && __float_as_uint(bank_leaf<FAST, true>(t, pr.x, pr.y)) == 0x80000000u;
+                }
+            }
+            goff += 1u;
+        }
+    }
+    return ok;
+}
+
+// One schedule voice of one block: the time row as stream_render_chunk reads it, the fast path per workgroup (every wave holds
+// the same 64 frames), the sum, and where a live lane's root is zero its sign: -0 iff every leaf of the voice is -0 in the
+// graph's arithmetic, the 16 waves' answers ANDed through LDS.  Returns the root in wave 0; `t` is the lane's time in every wave.
+// Barriers: one per item of >= 16 leaves, one for the zero mask, a last one when a root is zero -- all under conditions that are
+// uniform for the workgroup.
+__device__ __forceinline__ float stream_render_schedule(const float *params, const uint32_t *gmeta, uint32_t nitems, uint32_t fast_ok, const float *trow, bool live, uint32_t wave,
+                                                        uint32_t lane, float (&sm)[2][STREAM_NW][64], float (&stack_mem)[STREAM_STACK_DEPTH][64], unsigned long long &zshared,
+                                                        float &t) {
+    constexpr int NW = STREAM_NW;
+    t = live ? __hip_atomic_load(&trow[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0f;
+    const bool fast = fast_ok && __all(t >= 0.0f && t <= 4294967296.0f);
+    float *stack = &stack_mem[0][lane];
+    float r = fast ? stream_schedule_sum<true>(params, gmeta, nitems, t, wave, lane, stack, sm) : stream_schedule_sum<false>(params, gmeta, nitems, t, wave, lane, stack, sm);
+    if (wave == 0u) {
+        const unsigned long long z = __ballot(live && r == 0.0f);
+        if (lane == 0u) zshared = z;
+    }
+    __syncthreads();
+    const unsigned long long zm = zshared;                // workgroup-uniform
+    if (zm != 0ull) {
+        const bool ok = fast ? stream_schedule_negzero<true>(params, gmeta, nitems, t, wave, zm) : stream_schedule_negzero<false>(params, gmeta, nitems, t, wave, zm);
+        sm[0][wave][lane] = ok ? 1.0f : 0.0f;             // (every wave is past the last hand-over of the sum: zshared's barrier)
+        __syncthreads();
+        if (wave == 0u && ((zm >> lane) & 1ull)) {
+            bool all = true;
+            static_for<0, NW>([&](auto i) { all = all && sm[0][i][lane] != 0.0f; });
+            r = all ? -0.0f : 0.0f;
+        }
+    }
+    return r;
+}
+
 // Wave 0 hands its chunk sum `r` over: store, acknowledged, then a ticket; the wave whose ticket is the voice's last reads all
 // chunks back and adds them in tree order, takes the top of the ladder for this voice's chunk count and resets the ticket for
 // the next block.  The chunk sums of all voices share one workspace, [chunk][n_voices][64] by global voice; one ticket per
@@ -2145,17 +2285,19 @@ __global__ void __launch_bounds__(1024) bank_stream_banks_kernel(StreamBanksArgs
 }
 
 // What the launches with a bank table check: every bank as the one-bank launchers check theirs; the banks' workgroups and
-// voices follow one another without a gap.  `wgs`: the launch's workgroups.
-static bool stream_table_ok(const StreamBanksArgs &t, const BankArgs &a, const StreamProgArgs &p, uint32_t n_rows, uint64_t &wgs) {
+// voices follow one another without a gap.  `wgs`: the launch's workgroups.  `schedule_mask`: the banks that are schedule banks
+// (StreamGeneralArgs::mask): one workgroup per voice, whatever their log2_p and chunk_log2 say.
+static bool stream_table_ok(const StreamBanksArgs &t, const BankArgs &a, const StreamProgArgs &p, uint32_t n_rows, uint64_t &wgs, uint32_t schedule_mask = 0) {
     if (t.n_banks == 0 || t.n_banks > BANK_STREAM_BANKS) return false;
     uint64_t voices = 0;
     bool to_ring = false;
     wgs = 0;
     for (uint32_t i = 0; i < t.n_banks; ++i) {
         const StreamBanksArgs::Bank &b = t.bank[i];
-        if (!stream_bank_ok(b.log2_p, b.chunk_log2, b.n_voices, a.ws, a.tickets) || !b.params || !b.rows) return false;
-        if (b.first_wg != wgs || b.first_voice != voices) return false;
-        wgs += (uint64_t)b.n_voices << (b.log2_p - b.chunk_log2);
+        const bool schedule = (schedule_mask >> i) & 1u;
+        if (schedule ? b.n_voices == 0 : !stream_bank_ok(b.log2_p, b.chunk_log2, b.n_voices, a.ws, a.tickets)) return false;
+        if (!b.params || !b.rows || b.first_wg != wgs || b.first_voice != voices) return false;
+        wgs += schedule ? (uint64_t)b.n_voices : (uint64_t)b.n_voices << (b.log2_p - b.chunk_log2);
         voices += b.n_voices;
         if (wgs > BANK_STREAM_WGS) return false;   // all workgroups must be resident
         to_ring = to_ring || b.to_ring != 0;
@@ -2224,6 +2366,89 @@ hipError_t launch_bank_stream_loops(const StreamBanksArgs &t, const BankArgs &a,
     uint64_t wgs = 0;
     if (!stream_table_ok(t, a, p, n_rows, wgs) || !p.n_rings || !ctl_dev || !dev) return hipErrorInvalidValue;   // (a loop lives in a ring)
     hipLaunchKernelGGL(bank_stream_loops_kernel, dim3((uint32_t)wgs), dim3(1024), 0, s, t, a, p, n_rows, ctl_dev, dev, idle_ms ? idle_ms : BANK_STREAM_IDLE_MS);
+    return hipGetLastError();
+}
+
+// bank_stream_loops_kernel for plans with schedule banks (FR_STREAM_GENERAL, kernels.hpp StreamGeneralArgs): the same bank table,
+// doorbell, hand-over, programs and bus segment.  What differs is what a workgroup of a schedule bank renders: it learns before
+// the block loop, uniformly, that its bank is one; its voice is first_voice + (blockIdx.x - first_wg), its chunk count 1 (so
+// stream_hand_over returns at once), and stream_render_schedule runs the voice's items and merges.
+static_assert(STREAM_STACK_DEPTH == GB_MAX_DEPTH, "a schedule voice's stack is the general voices'");
+__global__ void __launch_bounds__(1024) bank_stream_general_kernel(StreamBanksArgs t, StreamGeneralArgs g, BankArgs a, StreamProgArgs p, uint32_t n_rows, BankStreamInCtl *ctl,
+                                                                   BankStreamInDev *dev, uint32_t idle_ms) {
+    __shared__ float sm[2][STREAM_NW][64];                   // the waves' sums: a chunk's in [0], a schedule's items alternate
+    __shared__ float stack_mem[STREAM_STACK_DEPTH][64];      // a schedule voice's evaluation stack: [level][frame] of wave 0
+    __shared__ float regs[STAGE_REGS][64];                   // the interpreter's registers: [register][frame] of wave 0
+    __shared__ float ldt[BANK_STREAM_LOOP_LOADS][64];        // a loop program's loads, [load slot][frame]
+    __shared__ float stt[BANK_STREAM_LOOP_STORES][64];       // ... and what it stores to its rings, [store slot][frame]
+    __shared__ uint4 lins[BANK_STREAM_LOOP_INSTRS];          // ... and its (first) instructions
+    __shared__ unsigned long long zshared;
+    __shared__ uint32_t s_seq, s_T;
+    StreamBanksArgs::Bank bk = t.bank[0];
+    const uint32_t *groups = g.bank[0].groups, *group_off = g.bank[0].group_off;
+    uint32_t bi = 0;
+    static_for<1, (int)BANK_STREAM_BANKS>([&](auto j) {
+        if ((uint32_t)j < t.n_banks && blockIdx.x >= t.bank[j].first_wg) {
+            bk = t.bank[j];
+            groups = g.bank[j].groups;
+            group_off = g.bank[j].group_off;
+            bi = (uint32_t)j;
+        }
+    });
+    const bool schedule = (g.mask >> bi) & 1u;               // uniform: the workgroup's bank is a schedule bank
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t local = blockIdx.x - bk.first_wg;
+    // (a schedule bank: log2_p = chunk_log2 = 0 makes `local` the voice of the bank and its chunk count 1)
+    const StreamWork w = stream_work(bk.params, bk.rows, schedule ? 0u : bk.log2_p, schedule ? 0u : bk.chunk_log2, bk.fast_ok, bk.to_ring, bk.first_voice, local, wave);
+    const uint32_t *items = nullptr;
+    const float *vparams = nullptr;
+    uint32_t nitems = 0;
+    if (schedule) {
+        typedef uint32_t __attribute__((address_space(4))) const *const_u32_ptr;
+        const_u32_ptr go = (const_u32_ptr)group_off;
+        const uint32_t i0 = go[2u * local];
+        nitems = go[2u * local + 2u] - i0;
+        items = groups + i0;
+        vparams = (const float *)(bk.params + (size_t)go[2u * local + 1u] * 8u);
+    }
+    const uint32_t n_voices = a.n_voices;                    // of all banks
+    const unsigned long long idle_ticks = (unsigned long long)idle_ms * 100000ull;
+    uint64_t head = p.head;
+    uint32_t seen = 0;
+    if (blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store(&ctl->alive, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    for (;;) {
+        uint32_t T;
+        const uint32_t seq = stream_next_block(dev, wave, lane, seen, idle_ticks, s_seq, s_T, T, [&](uint32_t &T0) { return stream_rows_wait(n_rows, ctl, dev, lane, seen, idle_ticks, T0); });
+        if (seq == BANK_STREAM_STOP) break;
+        seen = seq;
+        const bool live = lane < T;
+        float t_in, result;
+        const float r = schedule ? stream_render_schedule(vparams, items, nitems, bk.fast_ok, dev->rows[0], live, wave, lane, sm, stack_mem, zshared, t_in)
+                                 : stream_render_chunk(w, dev->rows[0], live, wave, lane, sm[0], zshared, t_in);
+        if (wave == 0u && stream_hand_over(w, a.ws, a.tickets, n_voices, lane, r, result)) {
+            const StreamRowsInput input{dev, lane, t_in};
+            stream_store_voice(w, a.out, p, head + lane, lane, live, result);
+            stream_run_programs_loops(a.out, p, regs, ldt, stt, lins, p.voice_first[w.voice], p.voice_first[w.voice + 1], head, T, lane, live, input);
+            stream_finish_bus(ctl, dev, n_voices, lane, seq, [&] {
+                stream_run_programs_loops(a.out, p, regs, ldt, stt, lins, p.voice_first[n_voices], p.voice_first[n_voices + 1], head, T, lane, live, input);
+            });
+        }
+        head += T;
+        __syncthreads();   // LDS is reused by the next block
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store(&ctl->alive, 0u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+hipError_t launch_bank_stream_general(const StreamBanksArgs &t, const StreamGeneralArgs &g, const BankArgs &a, const StreamProgArgs &p, uint32_t n_rows, uint32_t max_stride,
+                                      uint32_t max_loads, uint32_t max_stores, BankStreamInCtl *ctl_dev, BankStreamInDev *dev, uint32_t idle_ms, hipStream_t s) {
+    if (max_stride > BANK_STREAM_LOOP_MAX_STRIDE || max_loads > BANK_STREAM_LOOP_LOADS || max_stores > BANK_STREAM_LOOP_STORES) return hipErrorInvalidValue;
+    if (g.mask == 0 || t.n_banks == 0 || t.n_banks > BANK_STREAM_BANKS || (g.mask >> t.n_banks) != 0) return hipErrorInvalidValue;
+    for (uint32_t i = 0; i < t.n_banks; ++i)
+        if (((g.mask >> i) & 1u) && (!g.bank[i].groups || !g.bank[i].group_off)) return hipErrorInvalidValue;
+    uint64_t wgs = 0;                                         // (a schedule bank: one workgroup per voice; the total within BANK_STREAM_WGS)
+    if (!stream_table_ok(t, a, p, n_rows, wgs, g.mask) || (max_stride && !p.n_rings) || !ctl_dev || !dev) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(bank_stream_general_kernel, dim3((uint32_t)wgs), dim3(1024), 0, s, t, g, a, p, n_rows, ctl_dev, dev, idle_ms ? idle_ms : BANK_STREAM_IDLE_MS);
     return hipGetLastError();
 }
 

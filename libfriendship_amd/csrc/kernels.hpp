@@ -291,6 +291,26 @@ constexpr uint32_t BANK_STREAM_LOOP_INSTRS = 512;
 hipError_t launch_bank_stream_loops(const StreamBanksArgs &t, const BankArgs &a, const StreamProgArgs &p, uint32_t n_rows, uint32_t max_stride, uint32_t max_loads,
                                     uint32_t max_stores, BankStreamInCtl *ctl_dev, BankStreamInDev *dev, uint32_t idle_ms, hipStream_t s);
 
+// bank_stream_general_kernel (FR_STREAM_GENERAL): bank_stream_loops_kernel's work for plans with SCHEDULE BANKS -- voices of any
+// partial count and any Sum2 tree, in the general form of launch_gbank (BankArgs::groups / group_off above), and balanced
+// voices of 32 or 64 partials as one-item schedules.  Bit `i` of `mask` says that bank i of the StreamBanksArgs table is a
+// schedule bank: its Bank::params are the items' pairs, its log2_p and chunk_log2 are not read, and it has ONE workgroup per
+// voice (workgroup first_wg + v renders voice first_voice + v) with one chunk, so nothing of it goes through the workspace
+// or the tickets.  That workgroup runs the voice's schedule on its 16 waves (kernels.hip stream_render_schedule): an item of
+// >= 128 leaves is split over the 16 waves, one of 16 .. 64 leaves over 2 .. 8 waves with a group of 8 each, the sums meet in LDS
+// in the tree's own association, one barrier per such item; smaller items and the merges run on wave 0, on an LDS stack.  Every
+// barrier's condition comes from the schedule words, which are uniform for the workgroup.  The other banks of the table are
+// rendered in chunks as before.  The host validates every schedule before it uploads it (streamplan.hpp stream_schedule_ok).
+// LDS: the loops kernel's 36 880 bytes + the stack's 4096 + a second hand-over buffer of 4096 = 45 072.
+struct StreamGeneralArgs {
+    uint32_t mask;
+    struct {
+        const uint32_t *groups, *group_off;
+    } bank[BANK_STREAM_BANKS];
+};
+hipError_t launch_bank_stream_general(const StreamBanksArgs &t, const StreamGeneralArgs &g, const BankArgs &a, const StreamProgArgs &p, uint32_t n_rows, uint32_t max_stride,
+                                      uint32_t max_loads, uint32_t max_stores, BankStreamInCtl *ctl_dev, BankStreamInDev *dev, uint32_t idle_ms, hipStream_t s);
+
 // One step of the partial-block exchange (friendship_render.h FR_SHARD_PARTIALS): row i, window frame t:
 //   v = lo[i][t] + hi[i][t]         the Sum2 node one level up: left sub-tree + right sub-tree, one f32 add
 // stored to dst_ws[i][t] (steps before the last; may alias lo or hi), or -- the last step, dst_ws == null -- where the

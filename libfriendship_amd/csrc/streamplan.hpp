@@ -24,6 +24,10 @@
 // stride, the gcd of those delays (stream_loop_stride), and the one wave that runs it walks the residues of the stride in its
 // lanes (kernels.hip bank_stream_loops_kernel): still nobody waits for anybody.  A read below 64 frames of a ring that an
 // EARLIER program of the block stores -- the level behind a loop -- is served too: the reader follows the storer's voice.
+// With FR_STREAM_GENERAL=1 (StreamEnv::general) a voice may have any partial count and any Sum2 tree: a SCHEDULE BANK -- a bank
+// of general voices (items plus a merge schedule, match.hpp), or a balanced bank of 32 or 64 partials, each voice a one-item
+// schedule -- gets one workgroup per voice, no chunks, and that workgroup runs the voice's schedule on its 16 waves
+// (kernels.hip bank_stream_general_kernel).  Everything about programs applies to such a voice as to any other.
 #pragma once
 
 #include <algorithm>
@@ -46,6 +50,11 @@ constexpr uint32_t STREAM_MAX_BANKS = 8;     // most bank launches one resident 
 // resident and may declare 160 KiB, so LDS is not what limits anything; the numbers are twice and 4/3 of the loop-tile
 // rule's 16 and 12, and powers of two because the kernel masks its slots)
 constexpr uint32_t STREAM_LOOP_LOADS = 32, STREAM_LOOP_STORES = 16;
+// A schedule voice is rendered by ONE workgroup, and a block is only as fast as its slowest workgroup: the limit is four times
+// the largest chunk a workgroup of a chunked bank renders (8192 partials), 16 waves x one full item of 2048 leaves.  Dealing the
+// items of one voice over several workgroups is not built.
+constexpr uint32_t STREAM_GENERAL_MAX_LEAVES = 32768;
+constexpr uint32_t STREAM_SCHEDULE_MAX_DEPTH = 16;   // (= kernels.hip GB_MAX_DEPTH: the evaluation stack's columns in LDS)
 static_assert(STREAM_LOOP_LOADS == BANK_STREAM_LOOP_LOADS && STREAM_LOOP_STORES == BANK_STREAM_LOOP_STORES && STREAM_BLOCK == BANK_STREAM_LOOP_MAX_STRIDE + 1,
               "the rule's limits are the kernel's");
 
@@ -61,6 +70,7 @@ struct StreamEnv {
     bool inputs = false;             // FR_STREAM_INPUTS: programs may read input slots other than 0 at the current frame
     bool banks = false;              // FR_STREAM_BANKS: 2..STREAM_MAX_BANKS bank launches in one resident launch
     bool loops = false;              // FR_STREAM_LOOPS: feedback loops shorter than a block, and the taps behind them
+    bool general = false;            // FR_STREAM_GENERAL: schedule banks -- general voices, balanced voices of 32 or 64 partials
 };
 
 // One bank of a streamed plan.  Voices [first_voice, first_voice + voices) of the global numbering; workgroups
@@ -69,6 +79,8 @@ struct StreamBank {
     uint32_t first_voice = 0, voices = 0, log2_p = 0, chunk_log2 = 0;
     bool to_ring = false;
     uint32_t first_wg = 0;
+    bool general = false;            // a schedule bank (StreamEnv::general): one workgroup per voice, log2_p == chunk_log2
+    uint32_t max_leaves = 0;         // ... and its largest voice
 };
 
 // Every workgroup of the launch must be resident at once, one per CU: as many as the device has CUs (0: unknown, the kernel's
@@ -80,6 +92,7 @@ inline uint64_t stream_max_wgs(uint32_t device_cus) { return std::min<uint64_t>(
 // (on a tie the lower index) among those whose chunk is above 128 partials (a wave needs a group of 8), that have fewer than
 // 256 chunks per voice and whose halving keeps the total within max_wgs, has its chunk halved.  A block is only as fast as its
 // largest chunk, so this evens out the partials per workgroup; for one bank it is the short-call kernel's loop.
+// A schedule bank (StreamBank::general) counts as `voices` workgroups and is never halved.
 inline bool deal_stream_chunks(std::vector<StreamBank> &banks, uint64_t max_wgs) {
     uint64_t total = 0;
     for (StreamBank &b : banks) { b.chunk_log2 = b.log2_p; total += b.voices; }
@@ -87,7 +100,7 @@ inline bool deal_stream_chunks(std::vector<StreamBank> &banks, uint64_t max_wgs)
     for (;;) {
         StreamBank *pick = nullptr;
         for (StreamBank &b : banks) {
-            if (!(b.chunk_log2 > 7 && b.log2_p - b.chunk_log2 < 8)) continue;
+            if (b.general || !(b.chunk_log2 > 7 && b.log2_p - b.chunk_log2 < 8)) continue;
             if (total + ((uint64_t)b.voices << (b.log2_p - b.chunk_log2)) > max_wgs) continue;
             if (!pick || b.chunk_log2 > pick->chunk_log2) pick = &b;
         }
@@ -103,6 +116,51 @@ inline bool deal_stream_chunks(std::vector<StreamBank> &banks, uint64_t max_wgs)
         v += b.voices;
     }
     return true;
+}
+
+// The schedule of voice `voice` of a bank in the general form (kernels.hpp BankArgs::groups / group_off): at least one item,
+// every item of at most 2^11 leaves, an evaluation stack that never underflows, never holds more than
+// STREAM_SCHEDULE_MAX_DEPTH values and ends with exactly one.  Host only: every voice is checked before anything is uploaded.
+inline bool stream_schedule_ok(const std::vector<uint32_t> &groups, const std::vector<uint32_t> &group_off, uint32_t voice, std::string *why = nullptr) {
+    auto bad = [&](const std::string &w) { if (why) *why = w; return false; };
+    if ((size_t)2 * voice + 2 >= group_off.size()) return bad("a voice without a schedule");
+    const uint32_t i0 = group_off[2 * voice], i1 = group_off[2 * voice + 2];
+    if (i0 >= i1 || i1 > groups.size()) return bad("an empty schedule");
+    uint32_t depth = 0;
+    for (uint32_t i = i0; i < i1; ++i) {
+        const uint32_t k = groups[i] & 15u, merges = groups[i] >> 4;
+        if (k > 11u) return bad("an item of more than 2048 leaves");
+        if (merges > depth) return bad("the schedule's stack underflows");
+        depth -= merges;                  // v = pop() + v, `merges` times; then push(v)
+        if (++depth > STREAM_SCHEDULE_MAX_DEPTH) return bad("the schedule's stack is deeper than " + std::to_string(STREAM_SCHEDULE_MAX_DEPTH));
+    }
+    if (depth != 1) return bad("the schedule leaves " + std::to_string(depth) + " values");
+    return true;
+}
+
+// The leaves of that voice (padding pairs are not leaves).
+inline uint64_t stream_schedule_leaves(const std::vector<uint32_t> &groups, const std::vector<uint32_t> &group_off, uint32_t voice) {
+    uint64_t n = 0;
+    for (uint32_t i = group_off[2 * voice]; i < group_off[2 * voice + 2] && i < groups.size(); ++i) n += 1ull << (groups[i] & 15u);
+    return n;
+}
+
+// The parameter pairs that voice's items hold, from its first group on (an item of fewer than 8 leaves is padded to 8 pairs).
+inline uint64_t stream_schedule_pairs(const std::vector<uint32_t> &groups, const std::vector<uint32_t> &group_off, uint32_t voice) {
+    uint64_t n = 0;
+    for (uint32_t i = group_off[2 * voice]; i < group_off[2 * voice + 2] && i < groups.size(); ++i) n += std::max<uint64_t>(8, 1ull << (groups[i] & 15u));
+    return n;
+}
+
+// The one-item schedules of a balanced bank of `voices` voices of 1 << log2_p partials (log2_p <= 11), in the general form: voice
+// v is the item log2_p | 0 << 4, its parameters start at group v << (log2_p - 3) -- where the balanced layout has them.
+inline void stream_balanced_schedule(uint32_t voices, uint32_t log2_p, std::vector<uint32_t> &groups, std::vector<uint32_t> &group_off) {
+    groups.assign(voices, log2_p);
+    group_off.clear();
+    for (uint32_t v = 0; v <= voices; ++v) {
+        group_off.push_back(v);
+        group_off.push_back(v << (log2_p - 3u));
+    }
 }
 
 struct StreamPlan {
@@ -125,6 +183,8 @@ struct StreamPlan {
     uint64_t lookback = 0;               // deepest ring read of the assigned programs
     std::vector<uint32_t> input_slots{0};   // the distinct input slots the voices and the assigned programs read: slot 0 (the voices' time)
                                          // first, the others ascending -- the order of a block's streamed rows
+    std::vector<uint32_t> general_voices;   // the leaf count of every voice served by schedule, in global voice order (StreamEnv::general)
+    bool has_general() const { return std::any_of(banks.begin(), banks.end(), [](const StreamBank &b) { return b.general; }); }
     std::vector<uint32_t> programs_per_voice() const {
         std::vector<uint32_t> n;
         for (size_t v = 0; v + 2 < voice_first.size(); ++v) n.push_back(voice_first[v + 1] - voice_first[v]);
@@ -203,7 +263,7 @@ inline StreamPlan plan_stream(const StagedPlan &sp, const std::vector<const Bank
     auto refuse = [&](const std::string &why) {
         s.servable = false;
         s.reason = why;
-        if (!s.voices) s.banks.clear();              // (refused before the banks were dealt)
+        if (!s.voices) { s.banks.clear(); s.general_voices.clear(); }   // (refused before the banks were dealt)
         return s;
     };
     if (env.n_slots == 0) return refuse("no output slots");
@@ -219,20 +279,44 @@ inline StreamPlan plan_stream(const StagedPlan &sp, const std::vector<const Bank
     }
     for (const BankLaunch *bp : banks) {             // (one bank: the checks and their order are what they have always been)
         const BankLaunch &b = *bp;
-        if (b.general || b.jit || b.tracks || b.to_ws) return refuse("block streaming needs balanced template voices (these are general, compiled or track voices)");
+        if (env.general) {
+            if (b.jit || b.tracks || b.to_ws) return refuse("block streaming needs template voices (these are compiled or track voices)");
+        } else if (b.general || b.jit || b.tracks || b.to_ws) {
+            return refuse("block streaming needs balanced template voices (these are general, compiled or track voices)");
+        }
         if (env.leaf_variant != 1) return refuse("block streaming with FR_BANK_LEAF=0");
         if (b.input_slot != 0) return refuse("block streaming feeds input slot 0; these voices read another slot");
-        if (b.log2_p < 7) return refuse("block streaming needs voices of at least 128 partials (16 waves x one group of 8)");
+        // FR_STREAM_GENERAL: a schedule bank -- general voices as the matcher cut them, balanced voices of 32 or 64 partials
+        const bool schedule = env.general && (b.general || b.log2_p == 5 || b.log2_p == 6);
+        if (!schedule && b.log2_p < 7) return refuse("block streaming needs voices of at least 128 partials (16 waves x one group of 8)");
         if (b.rows.empty()) return refuse("block streaming needs a plan with one voice bank (this one has no voices)");
         StreamBank sb;
         sb.voices = (uint32_t)b.rows.size();
-        sb.log2_p = b.log2_p;
+        sb.log2_p = b.general ? 0 : b.log2_p;
         sb.to_ring = b.to_ring;
+        sb.general = schedule;
+        if (schedule) {
+            for (uint32_t v = 0; v < sb.voices; ++v) {
+                uint64_t leaves = 1ull << b.log2_p;
+                if (b.general) {
+                    std::string why;
+                    if (!stream_schedule_ok(b.groups, b.group_off, v, &why)) return refuse("internal: a voice's schedule is malformed (" + why + ")");
+                    leaves = stream_schedule_leaves(b.groups, b.group_off, v);
+                }
+                leaves = std::min<uint64_t>(leaves, UINT32_MAX);
+                sb.max_leaves = std::max(sb.max_leaves, (uint32_t)leaves);
+                s.general_voices.push_back((uint32_t)leaves);
+            }
+        }
         s.banks.push_back(sb);
     }
     // every workgroup of the launch must be resident at once, one per CU: chunks of >= 128 partials until the CUs are used
     const uint64_t max_wgs = stream_max_wgs(env.device_cus);
     if (!deal_stream_chunks(s.banks, max_wgs)) return refuse("block streaming serves at most one voice per CU (" + std::to_string(max_wgs) + " here)");
+    for (uint32_t leaves : s.general_voices)         // one workgroup renders a schedule voice
+        if (leaves > STREAM_GENERAL_MAX_LEAVES)
+            return refuse("a voice of " + std::to_string(leaves) + " leaves; block streaming renders a voice of any partial count in one workgroup, at most " +
+                          std::to_string(STREAM_GENERAL_MAX_LEAVES) + " leaves");
     uint32_t V = 0;
     for (const StreamBank &sb : s.banks) {
         V += sb.voices;
