@@ -242,27 +242,7 @@ __attribute__((weak)) hipError_t launch_ring_move(const RingMoveArgs &a, hipStre
     return hipSuccess;
 }
 // (no resident launches on the simulator: the serving rule and the tables are what it tests, through fr_plan_json)
-__attribute__((weak)) hipError_t launch_bank_stream_prog(const BankArgs &, const StreamProgArgs &, BankStreamCtl *, BankStreamDev *, uint32_t, hipStream_t) {
-    return hipErrorNotSupported;
-}
-__attribute__((weak)) hipError_t launch_bank_stream_bus(const BankArgs &, const StreamProgArgs &, BankStreamCtl *, BankStreamDev *, uint32_t, hipStream_t) {
-    return hipErrorNotSupported;
-}
-__attribute__((weak)) hipError_t launch_bank_stream_in(const BankArgs &, const StreamProgArgs &, uint32_t, BankStreamInCtl *, BankStreamInDev *, uint32_t, hipStream_t) {
-    return hipErrorNotSupported;
-}
-__attribute__((weak)) hipError_t launch_bank_stream_banks(const StreamBanksArgs &, const BankArgs &, const StreamProgArgs &, uint32_t, BankStreamInCtl *, BankStreamInDev *, uint32_t,
-                                                          hipStream_t) {
-    return hipErrorNotSupported;
-}
-__attribute__((weak)) hipError_t launch_bank_stream_loops(const StreamBanksArgs &, const BankArgs &, const StreamProgArgs &, uint32_t, uint32_t, uint32_t, uint32_t, BankStreamInCtl *,
-                                                          BankStreamInDev *, uint32_t, hipStream_t) {
-    return hipErrorNotSupported;
-}
-__attribute__((weak)) hipError_t launch_bank_stream_general(const StreamBanksArgs &, const StreamGeneralArgs &, const BankArgs &, const StreamProgArgs &, uint32_t, uint32_t, uint32_t,
-                                                            uint32_t, BankStreamInCtl *, BankStreamInDev *, uint32_t, hipStream_t) {
-    return hipErrorNotSupported;
-}
+__attribute__((weak)) hipError_t launch_bank_stream(StreamKernel, const StreamLaunchArgs &, hipStream_t) { return hipErrorNotSupported; }
 __attribute__((weak)) hipError_t launch_track_window(const TrackWindowArgs &a, hipStream_t) {
     for (uint32_t r = 0; r < a.n_rows; ++r)
         for (uint64_t i = 0; i < a.back + a.n; ++i)
@@ -526,13 +506,31 @@ struct fr_renderer {
         if (bank_launches.size() < 256)
             bank_launches.push_back({bp, voices, partials, frames, bs.grp.log2_p, bank_tune.leaf_variant, row_flags, bank_form});
     }
-    // Block streaming (fr_stream_*): one resident launch renders 64-frame blocks on a doorbell (kernels.hpp BankStreamCtl)
-    bool streaming = false;
-    double stream_trace_us[2] = {0, 0};
-    uint64_t stream_trace_n = 0;
-    uint32_t stream_seq = 0, stream_slots = 0;
-    uint64_t stream_head = 0;            // first frame after the last streamed block
-    bool stream_have_last = false;
+    // Block streaming (fr_stream_*): one resident launch renders 64-frame blocks on a doorbell (kernels.hpp BankStreamCtl).
+    // A plan with programs (FR_STREAM_PROGRAMS, streamplan.hpp) is launched with its first block and again with every block
+    // that does not continue the previous one, after the rings were brought up to that block's first frame.
+    struct Stream {
+        struct Open {                    // the open stream: opening and closing one replaces the whole object
+            bool prog = false;           // it is of the program path
+            bool launched = false;       // its resident launch is running
+            bool have_last = false;
+            uint32_t seq = 0, slots = 0;
+            uint64_t head = 0;           // first frame after the last streamed block
+            StreamLaunch launch;         // how it is launched (streamplan.hpp): everyone reads this and decides nothing
+            StreamPlan plan;
+            StreamRows rows;             // the input store's rules for its rows, without the samples (streamrows.hpp)
+            // FR_STREAM_GENERAL: per plan bank the word offsets in d_sched of the one-item schedule (groups, group_off) built for a
+            // balanced 32- or 64-partial bank (SIZE_MAX: the bank has none of its own here)
+            std::vector<std::pair<size_t, size_t>> sched_at;
+        } now;
+        bool open = false;
+        // what outlives a stream: the buffers (they only grow), the last resident launch's kernel (fr_plan_json "stream"), the trace
+        PinnedBuf h_ctl, h_out;
+        DevBuf d_dev, d_progs, d_vfirst, d_sched, d_instrs;   // (d_instrs: StreamLaunch::own_instrs)
+        StreamKernel last_kernel = StreamKernel::none;
+        double trace_us[2] = {0, 0};
+        uint64_t trace_n = 0;
+    } strm;
     uint32_t stream_idle_ms = BANK_STREAM_IDLE_MS;   // FR_STREAM_IDLE_MS (tests shorten it)
     int device_cus = 0;
     // The in-launch combine's arrival counters (d_tickets) and the row-completion counters (d_row_done) are "all zero
@@ -555,32 +553,14 @@ struct fr_renderer {
         }
         return d_tickets.as<uint32_t>();
     }
-    PinnedBuf h_stream_ctl, h_stream_out;
-    DevBuf d_stream_dev;
-    // Plans with programs (FR_STREAM_PROGRAMS, streamplan.hpp): fr_stream_begin deals the programs to the voices and uploads
-    // the tables; the resident launch (bank_stream_prog_kernel) starts with the first block and again with every block that
-    // does not continue the previous one, after the rings were brought up to that block's first frame.
-    bool stream_programs = false;        // the option
-    bool stream_bus = false;             // FR_STREAM_BUS: mix-bus programs run after the block's last voice (bank_stream_bus_kernel)
-    bool stream_inputs = false;          // FR_STREAM_INPUTS: programs read control rows, up to STREAM_MAX_INPUTS slots (bank_stream_in_kernel)
-    bool stream_loops = false;           // FR_STREAM_LOOPS: feedback loops shorter than a block (bank_stream_loops_kernel)
-    bool stream_banks = false;           // FR_STREAM_BANKS: 2..STREAM_MAX_BANKS bank launches in one resident launch (bank_stream_banks_kernel)
-    bool stream_general = false;         // FR_STREAM_GENERAL: schedule banks -- voices of any partial count (bank_stream_general_kernel)
-    bool stream_prog = false;            // the open stream is of that kind
-    bool stream_in = false;              // ... and its doorbell is the rows of stream_plan.input_slots (BankStreamInCtl / BankStreamInDev)
-    StreamRows stream_rows;              // the input store's rules for the open stream's rows, without the samples (streamrows.hpp)
-    DevBuf d_stream_instrs;              // bank_stream_in_kernel: the programs' instructions with S_INPUT's operand rewritten to the streamed row
-    bool stream_launched = false;        // its resident launch is running
-    const char *stream_kernel = "";      // the last resident launch's kernel (fr_plan_json "stream")
-    StreamPlan stream_plan;
-    DevBuf d_stream_progs, d_stream_vfirst;
-    // FR_STREAM_GENERAL: the one-item schedules of the open stream's balanced 32- and 64-partial banks, built at stream begin;
-    // per plan bank the word offsets of its groups and group_off in d_stream_sched (SIZE_MAX: the bank has none of its own here)
-    DevBuf d_stream_sched;
-    std::vector<std::pair<size_t, size_t>> stream_sched_at;
-    StreamPlan plan_stream_now() const {
+    // FR_STREAM_PROGRAMS, _BUS, _INPUTS, _LOOPS, _BANKS, _GENERAL (the options table says what each serves; streamplan.hpp StreamEnv)
+    bool stream_programs = false, stream_bus = false, stream_inputs = false, stream_loops = false, stream_banks = false, stream_general = false;
+    std::vector<const BankLaunch *> stream_bank_list() const {
         std::vector<const BankLaunch *> banks;
         for (const BankStage &bs : plan.banks) banks.push_back(&bs.grp);
+        return banks;
+    }
+    StreamEnv stream_env() const {
         StreamEnv env;
         env.n_slots = plan.n_slots;
         env.device_cus = (uint32_t)std::max(device_cus, 0);
@@ -588,38 +568,83 @@ struct fr_renderer {
         env.pull_mode = mode == FR_MODE_PULL;
         env.sharded = sharded();
         env.track_history = tail_on();
-        env.bus = stream_bus;
-        env.inputs = stream_inputs;
-        env.banks = stream_banks;
-        env.loops = stream_loops;
-        env.general = stream_general;
-        return plan_stream(plan.sp, banks, env);
+        env.programs = stream_programs; env.bus = stream_bus; env.inputs = stream_inputs;
+        env.banks = stream_banks; env.loops = stream_loops; env.general = stream_general;
+        return env;
     }
+    StreamPlan plan_stream_now() const { return plan_stream(plan.sp, stream_bank_list(), stream_env()); }
     // Rings the stop and waits for the resident launch to end.  `clean`: the launch was answering when the stop was rung
     // (every block it took was finished).  Otherwise some chunks of a voice may have taken their ticket and others never
     // run: the counters are cleared before anyone uses them again.
     void stop_resident(bool clean) {
-        if (stream_launched) {
-            // (BankStreamCtl::row is BankStreamInCtl::rows[0]: the stop goes to every row the launch looks at)
-            unsigned long long *words = (unsigned long long *)h_stream_ctl.p;
-            const size_t n_words = stream_in ? (size_t)BANK_STREAM_ROWS * 64 : 64;
-            for (size_t i = 0; i < n_words; ++i) __atomic_store_n(&words[i], (unsigned long long)BANK_STREAM_STOP << 32, __ATOMIC_RELEASE);
+        if (strm.now.launched) {
+            const StreamDoorbell bell = stream_doorbell(strm.h_ctl.p, strm.now.launch.rows_doorbell);   // (the stop goes to every row)
+            for (size_t i = 0; i < bell.n_words; ++i) __atomic_store_n(&bell.words[i], (unsigned long long)BANK_STREAM_STOP << 32, __ATOMIC_RELEASE);
             if (hipStreamSynchronize(stream) != hipSuccess) { (void)hipGetLastError(); clean = false; }   // the kernel sees the stop within a poll, or ends itself after its bound
         }
-        stream_launched = false;
-        stream_have_last = false;
+        strm.now.launched = false;
+        strm.now.have_last = false;
         if (!clean) counters_dirty = true;
     }
     void end_stream(bool clean = true) {
-        if (!streaming) return;
+        if (!strm.open) return;
         stop_resident(clean);
-        streaming = false;
-        if (stream_prog) {                       // the rings moved on with frames the input store never saw
+        if (strm.now.prog) {                     // the rings moved on with frames the input store never saw
             plan.stage_valid = false;
             ring_table.valid = false;
         }
-        stream_prog = false;
+        strm.open = false;
+        strm.now = Stream::Open{};
         head = UINT64_MAX;                       // the streamed frames were not stored: whatever comes next is a seek
+    }
+    void ensure_stream_buffers(const StreamLaunch &l, uint32_t n_slots) {
+        const StreamDoorbell bell = stream_doorbell(nullptr, l.rows_doorbell);
+        strm.h_ctl.ensure(bell.ctl_bytes);
+        strm.h_out.ensure((size_t)n_slots * 64 * sizeof(float));
+        strm.d_dev.ensure(bell.dev_bytes);
+    }
+    void open_stream(Stream::Open &&o, uint32_t n_slots) {
+        o.slots = n_slots;
+        o.rows.open(n_vecs);
+        strm.now = std::move(o);
+        strm.open = true;
+        last_pending = false;
+    }
+    // The BankArgs of a resident launch over the one bank `bs`; null: the banks travel as a table, and what BankArgs says of one
+    // bank (params, rows, log2_p, chunk_log2, fast_ok) is not read and stays zero.
+    BankArgs stream_bank_args(const BankStage *bs, uint32_t voices, uint32_t chunk_log2, uint32_t chunks) {
+        BankArgs a{};
+        if (bs) {
+            a.params = bs->d_params.as<float2>();
+            a.rows = bs->d_rows.as<uint32_t>();
+            a.log2_p = bs->grp.log2_p;
+            a.fast_ok = bs->grp.fast_ok ? 1u : 0u;
+            a.chunk_log2 = chunk_log2;
+        }
+        a.n_voices = voices; a.n_times = 64; a.leaf_variant = 1;
+        a.small_call = 2; a.waves_per_group = 16; a.frames_per_lane = 1;   // (the short-call kernel's shape)
+        if (chunks > 1) {
+            d_bank_ws.ensure((size_t)voices * chunks * 64 * sizeof(float));
+            a.ws = d_bank_ws.as<float>();
+            a.tickets = ticket_counters((size_t)voices * BANK_TICKET_STRIDE, stream);
+        }
+        a.out = strm.h_out.as_dev<float>(); a.out_stride = 64;
+        return a;
+    }
+    // The resident launch of stream `o` from a clean control block (the previous launch's doorbell and stop are still in the words);
+    // `x`: the kernel's arguments, without what is filled in here.
+    void launch_resident(Stream::Open &o, StreamLaunchArgs &x) {
+        const StreamLaunch &l = o.launch;
+        const StreamDoorbell bell = stream_doorbell(strm.h_ctl.p, l.rows_doorbell);
+        std::memset(strm.h_ctl.p, 0, bell.ctl_bytes);
+        HIP_CHECK(hipMemsetAsync(strm.d_dev.p, 0, bell.dev_bytes, stream));
+        x.n_rows = l.n_rows;
+        x.max_stride = l.max_stride; x.max_loads = l.max_loads; x.max_stores = l.max_stores;
+        x.ctl_dev = strm.h_ctl.dev; x.dev = strm.d_dev.p; x.idle_ms = stream_idle_ms;
+        HIP_CHECK(launch_bank_stream(l.kernel, x, stream));
+        strm.last_kernel = l.kernel;
+        o.launched = true;
+        last_pending = false;
     }
     void begin_program_stream(uint32_t n_slots);
     void seek_program_stream(uint64_t idx);
@@ -931,9 +956,9 @@ struct fr_renderer {
         // another renderer would otherwise meet a stale one)
         if (!registered.empty()) (void)hipStreamSynchronize(stream);
         for (auto &rg : registered) { if (hipHostUnregister(rg.first) != hipSuccess) (void)hipGetLastError(); }
-        if (host_trace && stream_trace_n)
-            std::fprintf(stderr, "fr_stream_block over %llu blocks: ring + wait %.1f us, copy out %.1f us\n", (unsigned long long)stream_trace_n,
-                         stream_trace_us[0] / stream_trace_n, stream_trace_us[1] / stream_trace_n);
+        if (host_trace && strm.trace_n)
+            std::fprintf(stderr, "fr_stream_block over %llu blocks: ring + wait %.1f us, copy out %.1f us\n", (unsigned long long)strm.trace_n,
+                         strm.trace_us[0] / strm.trace_n, strm.trace_us[1] / strm.trace_n);
         if (host_trace && trace_n)
             std::fprintf(stderr, "fr_fill_buffer phases over %llu calls (mapped out %d, mapped in %d): issue %.1f us, %s %.1f us, %s %.1f us\n",
                          (unsigned long long)trace_n, (int)host_out_mapped, (int)host_rows_mapped, trace_us[0] / trace_n,
@@ -2193,10 +2218,13 @@ void fr_renderer::begin_program_stream(uint32_t n_slots) {
         for (uint32_t row : grp.rows)
             if (row >= (grp.to_ring ? sp.n_rings : n_slots)) throw Error(FR_ERR_DEVICE, "internal: a streamed voice's row out of bounds");
     }
+    Stream::Open o;
+    o.launch = stream_launch(sp, s);
+    const StreamLaunch &l = o.launch;
     // schedule banks (FR_STREAM_GENERAL): every voice's schedule stays inside the bank's items and parameters (the rule has
     // validated its stack); the one-item schedules of balanced 32- and 64-partial banks are built and uploaded here, once
-    stream_sched_at.assign(plan.banks.size(), {SIZE_MAX, SIZE_MAX});
-    if (s.has_general()) {
+    o.sched_at.assign(plan.banks.size(), {SIZE_MAX, SIZE_MAX});
+    if (l.schedule_table) {
         std::vector<uint32_t> words;
         for (size_t i = 0; i < plan.banks.size(); ++i) {
             if (!s.banks[i].general) continue;
@@ -2213,24 +2241,20 @@ void fr_renderer::begin_program_stream(uint32_t n_slots) {
                     throw Error(FR_ERR_DEVICE, "internal: a general bank without its device schedule");
                 continue;
             }
-            stream_sched_at[i] = {words.size(), words.size() + own_groups.size()};
+            o.sched_at[i] = {words.size(), words.size() + own_groups.size()};
             words.insert(words.end(), own_groups.begin(), own_groups.end());
             words.insert(words.end(), own_off.begin(), own_off.end());
         }
-        d_stream_sched.ensure(std::max<size_t>(words.size(), 1) * sizeof(uint32_t));
+        strm.d_sched.ensure(std::max<size_t>(words.size(), 1) * sizeof(uint32_t));
         if (!words.empty()) {
-            HIP_CHECK(hipMemcpyAsync(d_stream_sched.p, words.data(), words.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+            HIP_CHECK(hipMemcpyAsync(strm.d_sched.p, words.data(), words.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
             HIP_CHECK(hipStreamSynchronize(stream));   // (`words` goes out of scope)
         }
     }
-    // programs that read control rows (FR_STREAM_INPUTS): the stream's own copy of their instructions, S_INPUT's operand the
-    // streamed row (the position of its slot in input_slots) instead of the plan's input index
-    // (several banks: bank_stream_banks_kernel, whose control words and S_INPUT are those of the kernel with control rows)
-    // (loop programs, FR_STREAM_LOOPS: bank_stream_loops_kernel, the same control words; the copy also carries their store slots)
-    // (schedule banks, FR_STREAM_GENERAL: bank_stream_general_kernel, the same control words)
-    const bool rows_in = s.input_slots.size() > 1 || s.banks.size() > 1 || s.has_loops() || s.has_general();
+    // the stream's own copy of the programs' instructions (StreamLaunch::own_instrs): S_INPUT's operand the streamed row (the
+    // position of its slot in input_slots) instead of the plan's input index; a loop program's store slots
     std::vector<StageInstr> instrs;
-    if (rows_in) {
+    if (l.own_instrs) {
         if (s.input_slots.size() > BANK_STREAM_ROWS) throw Error(FR_ERR_DEVICE, "internal: more streamed rows than the kernel takes");
         for (size_t i = 0; i < progs.size(); ++i) {
             StageProg &pg = progs[i];
@@ -2249,30 +2273,20 @@ void fr_renderer::begin_program_stream(uint32_t n_slots) {
             pg.first_instr = (uint32_t)instrs.size();
             instrs.insert(instrs.end(), own.begin(), own.end());
         }
-        d_stream_instrs.ensure(std::max<size_t>(instrs.size(), 1) * sizeof(StageInstr));
-        if (!instrs.empty()) HIP_CHECK(hipMemcpyAsync(d_stream_instrs.p, instrs.data(), instrs.size() * sizeof(StageInstr), hipMemcpyHostToDevice, stream));
+        strm.d_instrs.ensure(std::max<size_t>(instrs.size(), 1) * sizeof(StageInstr));
+        if (!instrs.empty()) HIP_CHECK(hipMemcpyAsync(strm.d_instrs.p, instrs.data(), instrs.size() * sizeof(StageInstr), hipMemcpyHostToDevice, stream));
     }
-    d_stream_progs.ensure(std::max<size_t>(progs.size(), 1) * sizeof(StageProg));
-    d_stream_vfirst.ensure(s.voice_first.size() * sizeof(uint32_t));
-    if (!progs.empty()) HIP_CHECK(hipMemcpyAsync(d_stream_progs.p, progs.data(), progs.size() * sizeof(StageProg), hipMemcpyHostToDevice, stream));
-    HIP_CHECK(hipMemcpyAsync(d_stream_vfirst.p, s.voice_first.data(), s.voice_first.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    strm.d_progs.ensure(std::max<size_t>(progs.size(), 1) * sizeof(StageProg));
+    strm.d_vfirst.ensure(s.voice_first.size() * sizeof(uint32_t));
+    if (!progs.empty()) HIP_CHECK(hipMemcpyAsync(strm.d_progs.p, progs.data(), progs.size() * sizeof(StageProg), hipMemcpyHostToDevice, stream));
+    HIP_CHECK(hipMemcpyAsync(strm.d_vfirst.p, s.voice_first.data(), s.voice_first.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
     HIP_CHECK(hipStreamSynchronize(stream));   // (host vectors go out of scope)
     // rings: the deepest look-back and a block, as execute() sizes them for a 64-frame call (which the seek then finds in place)
     if (sp.uses_rings()) grow_rings(ring_capacity(sp, STREAM_BLOCK));
-    h_stream_ctl.ensure(rows_in ? sizeof(BankStreamInCtl) : sizeof(BankStreamCtl));
-    h_stream_out.ensure((size_t)n_slots * 64 * sizeof(float));
-    d_stream_dev.ensure(rows_in ? sizeof(BankStreamInDev) : sizeof(BankStreamDev));
-    std::memset(h_stream_ctl.p, 0, rows_in ? sizeof(BankStreamInCtl) : sizeof(BankStreamCtl));
-    stream_plan = std::move(s);
-    stream_rows.open(n_vecs);
-    streaming = true;
-    stream_prog = true;
-    stream_in = rows_in;
-    stream_launched = false;
-    stream_seq = 0;
-    stream_slots = n_slots;
-    stream_have_last = false;
-    last_pending = false;
+    ensure_stream_buffers(l, n_slots);
+    o.prog = true;
+    o.plan = std::move(s);
+    open_stream(std::move(o), n_slots);
 }
 
 // A block that does not continue the previous one (the first block included): the running launch is retired, the rings are
@@ -2282,7 +2296,7 @@ void fr_renderer::begin_program_stream(uint32_t n_slots) {
 void fr_renderer::seek_program_stream(uint64_t idx) {
     HIP_CHECK(hipSetDevice(device));
     stop_resident(true);
-    const uint32_t n_slots = stream_slots;
+    const uint32_t n_slots = strm.now.slots;
     const StagedPlan &sp = plan.sp;
     if (!plan_current(n_slots)) throw Error(FR_ERR_DEVICE, "internal: a stream outlived its plan");
     const uint64_t warm = sp.uses_rings() ? std::min<uint64_t>(idx, STREAM_BLOCK) : 0;
@@ -2306,54 +2320,30 @@ void fr_renderer::seek_program_stream(uint64_t idx) {
     }
     plan.stage_valid = false;                    // from here on the rings run ahead of the input store
     ring_table.valid = false;
-    const BankStage &bs = plan.banks[0];
-    const StreamPlan &s = stream_plan;
+    const StreamPlan &s = strm.now.plan;
+    const StreamLaunch &l = strm.now.launch;
     size_t plan_voices = 0;
     for (const BankStage &b : plan.banks) plan_voices += b.grp.rows.size();
     if ((sp.uses_rings() && (ring_cap < sp.lmax + STREAM_BLOCK || (size_t)sp.n_rings * ring_cap * sizeof(float) > d_rings.bytes)) || s.voices != plan_voices ||
         s.banks.size() != plan.banks.size())
         throw Error(FR_ERR_DEVICE, "internal: the rings do not hold a streamed block's look-back");
-    BankArgs a{};
-    a.params = bs.d_params.as<float2>();
-    a.rows = bs.d_rows.as<uint32_t>();
-    a.n_voices = s.voices;
-    a.log2_p = bs.grp.log2_p;
-    a.n_times = 64;
-    a.fast_ok = bs.grp.fast_ok ? 1u : 0u;
-    a.leaf_variant = 1;
-    a.small_call = 2;
-    a.waves_per_group = 16;
-    a.frames_per_lane = 1;
-    a.chunk_log2 = s.chunk_log2;
-    if (s.chunks > 1) {
-        d_bank_ws.ensure((size_t)s.voices * s.chunks * 64 * sizeof(float));
-        a.ws = d_bank_ws.as<float>();
-        a.tickets = ticket_counters((size_t)s.voices * BANK_TICKET_STRIDE, stream);
-    }
-    a.out = h_stream_out.as_dev<float>();
-    a.out_stride = 64;
-    StreamProgArgs p{};
-    p.instrs = plan.d_instrs.as<StageInstr>();
-    p.progs = d_stream_progs.as<StageProg>();
-    p.voice_first = d_stream_vfirst.as<uint32_t>();
+    StreamLaunchArgs x{};
+    x.a = stream_bank_args(l.bank_table ? nullptr : &plan.banks[0], s.voices, s.chunk_log2, s.chunks);
+    StreamProgArgs &p = x.p;
+    p.instrs = l.own_instrs ? strm.d_instrs.as<StageInstr>() : plan.d_instrs.as<StageInstr>();
+    p.progs = strm.d_progs.as<StageProg>();
+    p.voice_first = strm.d_vfirst.as<uint32_t>();
     p.rings = sp.uses_rings() ? d_rings.as<float>() : nullptr;
     p.ring_mask = sp.uses_rings() ? ring_cap - 1 : 0;
     p.n_rings = sp.n_rings;
     p.n_rows = n_slots;
     p.head = idx;
-    p.bank_to_ring = bs.grp.to_ring ? 1u : 0u;
+    p.bank_to_ring = !l.bank_table && plan.banks[0].grp.to_ring ? 1u : 0u;   // (a bank table: each bank has its own)
     p.sparkle = mirror.sparkle ? 1u : 0u;
-    // (the previous launch's last doorbell and stop are still in the control words: a new launch starts from a clean slate)
-    std::memset(h_stream_ctl.p, 0, stream_in ? sizeof(BankStreamInCtl) : sizeof(BankStreamCtl));
-    HIP_CHECK(hipMemsetAsync(d_stream_dev.p, 0, stream_in ? sizeof(BankStreamInDev) : sizeof(BankStreamDev), stream));
-    // a plan whose programs read control rows (FR_STREAM_INPUTS): the kernel with a doorbell of rows; a plan with bus programs
-    // (FR_STREAM_BUS): the kernel whose last arriver of a block runs them; every other plan: as before
-    if (s.banks.size() > 1 || s.has_loops() || s.has_general()) {
-        // voices of several banks (FR_STREAM_BANKS), loop programs (FR_STREAM_LOOPS: also for one bank), schedule banks
-        // (FR_STREAM_GENERAL: also for one bank, and a second table of their schedules): the bank table travels in the kernel
-        // arguments; chunk sums and tickets are laid out by global voice
-        StreamBanksArgs t{};
-        StreamGeneralArgs g{};
+    if (l.bank_table) {
+        // the bank table travels in the kernel arguments (and, for schedule banks, a second table of their schedules); chunk
+        // sums and tickets are laid out by global voice
+        StreamBanksArgs &t = x.t;
         t.n_banks = (uint32_t)s.banks.size();
         for (size_t i = 0; i < s.banks.size(); ++i) {
             const BankStage &b = plan.banks[i];
@@ -2361,69 +2351,22 @@ void fr_renderer::seek_program_stream(uint64_t idx) {
             if (b.grp.rows.size() != sb.voices || (!b.grp.general && b.grp.log2_p != sb.log2_p) || (b.grp.general && !sb.general))
                 throw Error(FR_ERR_DEVICE, "internal: the stream's banks are not the plan's");
             if (sb.general) {                                    // its schedule: the ordinary launch's device copy, or the stream's own
-                g.mask |= 1u << i;
+                const auto &sched_at = strm.now.sched_at;
+                x.g.mask |= 1u << i;
                 if (b.grp.general) {
-                    g.bank[i].groups = b.d_groups.as<uint32_t>();
-                    g.bank[i].group_off = b.d_group_off.as<uint32_t>();
+                    x.g.bank[i].groups = b.d_groups.as<uint32_t>();
+                    x.g.bank[i].group_off = b.d_group_off.as<uint32_t>();
                 } else {
-                    if (i >= stream_sched_at.size() || stream_sched_at[i].first == SIZE_MAX) throw Error(FR_ERR_DEVICE, "internal: a schedule bank without its schedule");
-                    g.bank[i].groups = d_stream_sched.as<uint32_t>() + stream_sched_at[i].first;
-                    g.bank[i].group_off = d_stream_sched.as<uint32_t>() + stream_sched_at[i].second;
+                    if (i >= sched_at.size() || sched_at[i].first == SIZE_MAX) throw Error(FR_ERR_DEVICE, "internal: a schedule bank without its schedule");
+                    x.g.bank[i].groups = strm.d_sched.as<uint32_t>() + sched_at[i].first;
+                    x.g.bank[i].group_off = strm.d_sched.as<uint32_t>() + sched_at[i].second;
                 }
             }
-            t.bank[i].params = b.d_params.as<float2>();
-            t.bank[i].rows = b.d_rows.as<uint32_t>();
-            t.bank[i].first_wg = sb.first_wg;
-            t.bank[i].first_voice = sb.first_voice;
-            t.bank[i].n_voices = sb.voices;
-            t.bank[i].log2_p = sb.log2_p;
-            t.bank[i].chunk_log2 = sb.chunk_log2;
-            t.bank[i].fast_ok = b.grp.fast_ok ? 1u : 0u;
-            t.bank[i].to_ring = b.grp.to_ring ? 1u : 0u;
+            t.bank[i] = {b.d_params.as<float2>(), b.d_rows.as<uint32_t>(), sb.first_wg, sb.first_voice, sb.voices, sb.log2_p, sb.chunk_log2,
+                         b.grp.fast_ok ? 1u : 0u, b.grp.to_ring ? 1u : 0u};
         }
-        a.params = nullptr;
-        a.rows = nullptr;
-        a.chunk_log2 = 0;
-        a.log2_p = 0;
-        a.fast_ok = 0;
-        p.bank_to_ring = 0;
-        p.instrs = d_stream_instrs.as<StageInstr>();
-        // (the tiles' fill is re-counted from the plan's instructions; the store slots are the stored rings)
-        uint32_t max_stride = 0, max_loads = 0, max_stores = 0;
-        for (size_t i = 0; i < s.progs.size(); ++i) {
-            if (!s.loop_stride[i]) continue;
-            const StageProg &pg = sp.progs[s.progs[i]];
-            max_stride = std::max(max_stride, s.loop_stride[i]);
-            max_loads = std::max(max_loads, stream_loop_loads(pg, sp.instrs.data() + pg.first_instr));
-            max_stores = std::max<uint32_t>(max_stores, (uint32_t)stream_stored_rings(pg, sp.instrs.data() + pg.first_instr).size());
-        }
-        if (s.has_general()) {
-            HIP_CHECK(launch_bank_stream_general(t, g, a, p, (uint32_t)s.input_slots.size(), max_stride, max_loads, max_stores, h_stream_ctl.as_dev<BankStreamInCtl>(),
-                                                 d_stream_dev.as<BankStreamInDev>(), stream_idle_ms, stream));
-            stream_kernel = "bank_stream_general_kernel";
-        } else if (s.has_loops()) {
-            HIP_CHECK(launch_bank_stream_loops(t, a, p, (uint32_t)s.input_slots.size(), max_stride, max_loads, max_stores, h_stream_ctl.as_dev<BankStreamInCtl>(),
-                                               d_stream_dev.as<BankStreamInDev>(), stream_idle_ms, stream));
-            stream_kernel = "bank_stream_loops_kernel";
-        } else {
-            HIP_CHECK(launch_bank_stream_banks(t, a, p, (uint32_t)s.input_slots.size(), h_stream_ctl.as_dev<BankStreamInCtl>(), d_stream_dev.as<BankStreamInDev>(), stream_idle_ms,
-                                               stream));
-            stream_kernel = "bank_stream_banks_kernel";
-        }
-    } else if (stream_in) {
-        p.instrs = d_stream_instrs.as<StageInstr>();
-        HIP_CHECK(launch_bank_stream_in(a, p, (uint32_t)s.input_slots.size(), h_stream_ctl.as_dev<BankStreamInCtl>(), d_stream_dev.as<BankStreamInDev>(), stream_idle_ms, stream));
-        stream_kernel = "bank_stream_in_kernel";
-    } else if (s.bus_programs()) {
-        HIP_CHECK(launch_bank_stream_bus(a, p, h_stream_ctl.as_dev<BankStreamCtl>(), d_stream_dev.as<BankStreamDev>(), stream_idle_ms, stream));
-        stream_kernel = "bank_stream_bus_kernel";
-    } else {
-        HIP_CHECK(launch_bank_stream_prog(a, p, h_stream_ctl.as_dev<BankStreamCtl>(), d_stream_dev.as<BankStreamDev>(), stream_idle_ms, stream));
-        stream_kernel = "bank_stream_prog_kernel";
     }
-    stream_launched = true;
-    stream_have_last = false;
-    last_pending = false;
+    launch_resident(strm.now, x);
 }
 
 namespace {
@@ -2432,7 +2375,7 @@ template <class F>
 fr_status guarded(fr_renderer *r, F &&f, bool keeps_stream = false) {
     if (!r) return FR_ERR_INVALID_ARG;
     try {
-        if (r->streaming && !keeps_stream) r->end_stream();   // any other call first retires the resident launch
+        if (r->strm.open && !keeps_stream) r->end_stream();   // any other call first retires the resident launch
         f();
         r->last_error.clear();
         return FR_OK;
@@ -2977,11 +2920,7 @@ fr_status fr_stream_begin(fr_renderer *r, uint32_t n_slots) {
         r->order_after_previous(r->stream);
         r->ensure_plan(n_slots, r->stream);
         const StagedPlan &sp = r->plan.sp;
-        // (FR_STREAM_BANKS: a plan of several banks takes this path even when it has no programs and no rings; FR_STREAM_GENERAL: so
-        // does a plan with a bank that the option may serve by schedule -- general voices, voices below 128 partials)
-        const bool by_schedule = r->stream_general && std::any_of(r->plan.banks.begin(), r->plan.banks.end(),
-                                                                  [](const BankStage &b) { return b.grp.general || b.grp.log2_p < 7; });
-        if (r->stream_programs && (!sp.progs.empty() || sp.uses_rings() || (r->stream_banks && r->plan.banks.size() > 1) || by_schedule)) {
+        if (stream_path(sp, r->stream_bank_list(), r->stream_env())) {
             r->begin_program_stream(n_slots);
             return;
         }
@@ -2996,48 +2935,18 @@ fr_status fr_stream_begin(fr_renderer *r, uint32_t n_slots) {
         if (r->bank_tune.leaf_variant != 1) throw Error(FR_ERR_UNSUPPORTED, "block streaming with FR_BANK_LEAF=0");
         if (bs.grp.input_slot != 0) throw Error(FR_ERR_UNSUPPORTED, "block streaming feeds input slot 0; these voices read another slot");
         if (bs.grp.log2_p < 7) throw Error(FR_ERR_UNSUPPORTED, "block streaming needs voices of at least 128 partials (16 waves x one group of 8)");
-        BankArgs a{};
-        a.params = bs.d_params.as<float2>();
-        a.rows = bs.d_rows.as<uint32_t>();
-        a.n_voices = n_slots;
-        a.log2_p = bs.grp.log2_p;
-        a.n_times = 64;
-        a.fast_ok = bs.grp.fast_ok ? 1u : 0u;
-        a.leaf_variant = 1;
-        a.small_call = 2;
-        a.waves_per_group = 16;
-        a.frames_per_lane = 1;
         // Every workgroup of the launch must be resident at once (a workgroup that never starts never counts its voice in), one
         // per CU: as many as the device has CUs (a partitioned gfx950 has fewer than 256), and no more than the kernel's limit.
         const uint64_t max_wgs = std::min<uint64_t>(BANK_STREAM_WGS, (uint64_t)std::max(r->device_cus, 1));
-        uint32_t c = a.log2_p;                    // chunks of >= 128 partials (a wave needs a group of 8) until the CUs are used
-        while (c > 7 && ((uint64_t)n_slots << (a.log2_p - c + 1)) <= max_wgs && a.log2_p - c < 8) --c;
-        a.chunk_log2 = c;
-        if (((uint64_t)n_slots << (a.log2_p - c)) > max_wgs)
+        fr_renderer::Stream::Open o;
+        StreamBank sb;
+        if (!plain_stream_launch(n_slots, bs.grp.log2_p, max_wgs, sb, o.launch))
             throw Error(FR_ERR_UNSUPPORTED, "block streaming serves at most one voice per CU (" + std::to_string(max_wgs) + " here)");
-        if (c != a.log2_p) {
-            r->d_bank_ws.ensure(((size_t)n_slots << (a.log2_p - c)) * 64 * sizeof(float));
-            a.ws = r->d_bank_ws.as<float>();
-            a.tickets = r->ticket_counters((size_t)n_slots * BANK_TICKET_STRIDE, r->stream);
-        }
-        r->h_stream_ctl.ensure(sizeof(BankStreamCtl));
-        r->h_stream_out.ensure((size_t)n_slots * 64 * sizeof(float));
-        r->d_stream_dev.ensure(sizeof(BankStreamDev));
-        std::memset(r->h_stream_ctl.p, 0, sizeof(BankStreamCtl));
-        HIP_CHECK(hipMemsetAsync(r->d_stream_dev.p, 0, sizeof(BankStreamDev), r->stream));
-        a.out = r->h_stream_out.as_dev<float>();
-        a.out_stride = 64;
-        HIP_CHECK(launch_bank_stream(a, r->h_stream_ctl.as_dev<BankStreamCtl>(), r->d_stream_dev.as<BankStreamDev>(), r->stream_idle_ms, r->stream));
-        r->stream_kernel = "bank_stream_kernel";
-        r->streaming = true;
-        r->stream_launched = true;
-        r->stream_prog = false;
-        r->stream_in = false;
-        r->stream_rows.open(r->n_vecs);
-        r->stream_seq = 0;
-        r->stream_slots = n_slots;
-        r->stream_have_last = false;
-        r->last_pending = false;
+        r->ensure_stream_buffers(o.launch, n_slots);
+        StreamLaunchArgs x{};
+        x.a = r->stream_bank_args(&bs, n_slots, sb.chunk_log2, 1u << (sb.log2_p - sb.chunk_log2));
+        r->launch_resident(o, x);
+        r->open_stream(std::move(o), n_slots);
     });
 }
 
@@ -3051,41 +2960,40 @@ static void stream_block_rows(fr_renderer *r, float *out, uint64_t n_times, uint
     if (r->track_from != 0xFFFFFFFFu && n_rows > r->track_from) throw Error(FR_ERR_UNSUPPORTED, "block streaming takes no rows of track slots");
     // the first block of a stream, and a block that does not continue the previous one, is a seek: every slot unfed, every
     // input before idx 0.0.  A refused block changes nothing: the next one may follow as if it had not been made.
-    const bool seek = !r->stream_have_last || idx != r->stream_head || (r->stream_prog && !r->stream_launched);
+    fr_renderer::Stream::Open &o = r->strm.now;
+    const bool seek = !o.have_last || idx != o.head || (o.prog && !o.launched);
     {
         std::string why;
-        const StreamRowsStatus rs = r->stream_rows.check(r->stream_slots, n_times, idx, seek, offs, n_rows, &why);
+        const StreamRowsStatus rs = o.rows.check(o.slots, n_times, idx, seek, offs, n_rows, &why);
         if (rs != STREAM_ROWS_OK) throw Error(rs == STREAM_ROWS_HISTORY ? FR_ERR_INPUT_HISTORY : FR_ERR_INPUT_TOO_LONG, why);
     }
     // a plan with programs: the rings are brought up to idx and the resident launch starts there
-    if (r->stream_prog && seek) r->seek_program_stream(idx);
+    if (o.prog && seek) r->seek_program_stream(idx);
     const auto t_in = std::chrono::steady_clock::now();
     // the rows of the slots the plan reads, padded like short rows of fill_buffer (reference.rs:72-73); a slot without a row: +0.0
-    static const uint32_t kSlot0[1] = {0};
-    const uint32_t K = r->stream_in ? (uint32_t)r->stream_plan.input_slots.size() : 1u;
-    const uint32_t *want = r->stream_in ? r->stream_plan.input_slots.data() : kSlot0;
+    // (a one-row doorbell: StreamPlan::input_slots is {0}, also in a stream of the plain path, which has no plan)
+    const uint32_t K = o.launch.n_rows;
     float rows[BANK_STREAM_ROWS][STREAM_ROW_FRAMES];
-    r->stream_rows.accept(r->stream_slots, n_times, idx, seek, in_data, offs, n_rows, want, K, rows);
-    r->n_vecs = std::max(r->n_vecs, r->stream_rows.n_vecs);   // (the count the stream reached stays with the renderer)
+    o.rows.accept(o.slots, n_times, idx, seek, in_data, offs, n_rows, o.plan.input_slots.data(), K, rows);
+    r->n_vecs = std::max(r->n_vecs, o.rows.n_vecs);   // (the count the stream reached stays with the renderer)
     // every word is tagged with the block's number and length: the words are the doorbell (kernels.hpp BankStreamCtl, BankStreamInCtl)
-    r->stream_seq = (r->stream_seq + 1u) & 0xFFFFFFu;
-    if (r->stream_seq == 0 || r->stream_seq == 0xFFFFFFu) r->stream_seq = 1;
-    const uint32_t seq = r->stream_seq << 8 | (uint32_t)n_times;
-    unsigned long long *words = (unsigned long long *)r->h_stream_ctl.p;   // (BankStreamCtl::row is BankStreamInCtl::rows[0])
+    o.seq = (o.seq + 1u) & 0xFFFFFFu;
+    if (o.seq == 0 || o.seq == 0xFFFFFFu) o.seq = 1;
+    const uint32_t seq = o.seq << 8 | (uint32_t)n_times;
+    const StreamDoorbell bell = stream_doorbell(r->strm.h_ctl.p, o.launch.rows_doorbell);
     for (uint32_t j = 0; j < K; ++j)
         for (uint64_t i = 0; i < 64; ++i) {
             uint32_t bits;
             std::memcpy(&bits, &rows[j][i], 4);
-            __atomic_store_n(&words[(size_t)j * 64 + i], (unsigned long long)seq << 32 | bits, __ATOMIC_RELAXED);
+            __atomic_store_n(&bell.words[(size_t)j * 64 + i], (unsigned long long)seq << 32 | bits, __ATOMIC_RELAXED);
         }
-    uint32_t *done = r->stream_in ? &((BankStreamInCtl *)r->h_stream_ctl.p)->done : &((BankStreamCtl *)r->h_stream_ctl.p)->done;
     uint64_t spins = 0;
     const auto t_ring = std::chrono::steady_clock::now();
-    while (__atomic_load_n(done, __ATOMIC_ACQUIRE) != seq) {
+    while (__atomic_load_n(bell.done, __ATOMIC_ACQUIRE) != seq) {
         if ((++spins & 0xFFFFFu) != 0) continue;
         if (hipStreamQuery(r->stream) != hipErrorNotReady) {   // the launch is gone (its own bound, or a fault)
             (void)hipStreamSynchronize(r->stream);
-            r->stream_launched = false;
+            o.launched = false;
             r->end_stream(false);                              // (it may have ended between two chunks of a voice)
             throw Error(FR_ERR_DEVICE, "the resident launch ended before the block was rendered");
         }
@@ -3097,20 +3005,20 @@ static void stream_block_rows(fr_renderer *r, float *out, uint64_t n_times, uint
         }
     }
     const auto t_done = std::chrono::steady_clock::now();
-    const float *res = r->h_stream_out.as<float>();
-    for (uint32_t v = 0; v < r->stream_slots; ++v) std::memcpy(out + (size_t)v * n_times, res + (size_t)v * 64, n_times * sizeof(float));
-    r->stream_head = idx + n_times;
-    r->stream_have_last = true;
+    const float *res = r->strm.h_out.as<float>();
+    for (uint32_t v = 0; v < o.slots; ++v) std::memcpy(out + (size_t)v * n_times, res + (size_t)v * 64, n_times * sizeof(float));
+    o.head = idx + n_times;
+    o.have_last = true;
     if (r->host_trace) {   // FR_HOST_TRACE=1: inside the call, without the caller's wrapper
-        r->stream_trace_us[0] += std::chrono::duration<double, std::micro>(t_done - t_in).count();
-        r->stream_trace_us[1] += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_done).count();
-        ++r->stream_trace_n;
+        r->strm.trace_us[0] += std::chrono::duration<double, std::micro>(t_done - t_in).count();
+        r->strm.trace_us[1] += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_done).count();
+        ++r->strm.trace_n;
     }
 }
 
 fr_status fr_stream_block_rows(fr_renderer *r, float *out, uint64_t n_times, uint64_t idx, const float *in_data, const uint64_t *in_row_offsets, uint32_t n_in_rows) {
     return guarded(r, [&] {
-        if (!r->streaming) throw Error(FR_ERR_INVALID_ARG, "no stream is open (fr_stream_begin; any other call on the renderer closes it)");
+        if (!r->strm.open) throw Error(FR_ERR_INVALID_ARG, "no stream is open (fr_stream_begin; any other call on the renderer closes it)");
         if (!out || n_times == 0 || n_times > 64) throw Error(FR_ERR_INVALID_ARG, "a streamed block is 1..64 frames");
         stream_block_rows(r, out, n_times, idx, in_data, in_row_offsets, n_in_rows);
     }, true);
@@ -3119,7 +3027,7 @@ fr_status fr_stream_block_rows(fr_renderer *r, float *out, uint64_t n_times, uin
 // (one row, for input slot 0: fr_stream_block_rows with that row)
 fr_status fr_stream_block(fr_renderer *r, float *out, uint64_t n_times, uint64_t idx, const float *row, uint64_t row_len) {
     return guarded(r, [&] {
-        if (!r->streaming) throw Error(FR_ERR_INVALID_ARG, "no stream is open (fr_stream_begin; any other call on the renderer closes it)");
+        if (!r->strm.open) throw Error(FR_ERR_INVALID_ARG, "no stream is open (fr_stream_begin; any other call on the renderer closes it)");
         if (!out || n_times == 0 || n_times > 64 || row_len > n_times || (row_len && !row)) throw Error(FR_ERR_INVALID_ARG, "a streamed block is 1..64 frames");
         const uint64_t offs[2] = {0, row_len};
         stream_block_rows(r, out, n_times, idx, row, offs, 1);
@@ -3269,12 +3177,8 @@ const char *fr_plan_json(fr_renderer *r) {
                 for (uint32_t n : s.general_voices) gv += (gv.empty() ? "" : ",") + std::to_string(n);
                 r->plan_json_cache += ",\"general_voices\":[" + gv + "],\"general_max_leaves\":" + std::to_string(STREAM_GENERAL_MAX_LEAVES);
             }
-            const bool last_stands = std::strcmp(r->stream_kernel, "bank_stream_in_kernel") && std::strcmp(r->stream_kernel, "bank_stream_banks_kernel") &&
-                                     std::strcmp(r->stream_kernel, "bank_stream_loops_kernel") && std::strcmp(r->stream_kernel, "bank_stream_general_kernel");
-            const char *kernel = s.servable && s.has_general() ? "bank_stream_general_kernel"
-                                 : s.servable && s.has_loops() ? "bank_stream_loops_kernel"
-                                 : s.servable && s.banks.size() > 1 ? "bank_stream_banks_kernel"
-                                 : s.servable && s.input_slots.size() > 1 ? "bank_stream_in_kernel" : last_stands ? r->stream_kernel : "";
+            const StreamLaunch l = s.servable ? stream_launch(r->plan.sp, s) : StreamLaunch{};
+            const char *kernel = stream_kernel_name(l.by_plan ? l.kernel : stream_kernel_by_plan(r->strm.last_kernel) ? StreamKernel::none : r->strm.last_kernel);
             if (r->stream_banks) {                               // FR_STREAM_BANKS: the banks of the launch, in plan order
                 std::string bl;
                 for (const StreamBank &b : s.banks)

@@ -1448,7 +1448,7 @@ __global__ void __launch_bounds__(1024) bank_stream_kernel(BankArgs a, BankStrea
     if (blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store(&ctl->alive, 0u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-hipError_t launch_bank_stream(const BankArgs &a, BankStreamCtl *ctl_dev, BankStreamDev *dev, uint32_t idle_ms, hipStream_t s) {
+static hipError_t launch_bank_stream_plain(const BankArgs &a, BankStreamCtl *ctl_dev, BankStreamDev *dev, uint32_t idle_ms, hipStream_t s) {
     if (!stream_bank_ok(a.log2_p, a.chunk_log2, a.n_voices, a.ws, a.tickets)) return hipErrorInvalidValue;
     if ((1u << a.chunk_log2) / 16u < 8u) return hipErrorInvalidValue;          // a wave needs a whole group of 8 partials
     if (a.leaf_variant != 1 || !a.out || !a.rows || !ctl_dev || !dev) return hipErrorInvalidValue;
@@ -2144,14 +2144,6 @@ __global__ void __launch_bounds__(1024) bank_stream_prog_kernel(BankArgs a, Stre
     if (blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store(&ctl->alive, 0u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-hipError_t launch_bank_stream_prog(const BankArgs &a, const StreamProgArgs &p, BankStreamCtl *ctl_dev, BankStreamDev *dev, uint32_t idle_ms, hipStream_t s) {
-    if (!stream_bank_ok(a.log2_p, a.chunk_log2, a.n_voices, a.ws, a.tickets) || !stream_progs_ok(p, p.bank_to_ring != 0)) return hipErrorInvalidValue;
-    if (a.leaf_variant != 1 || !a.out || !a.rows || !ctl_dev || !dev) return hipErrorInvalidValue;
-    const uint32_t wgs = a.n_voices << (a.log2_p - a.chunk_log2);
-    hipLaunchKernelGGL(bank_stream_prog_kernel, dim3(wgs), dim3(1024), 0, s, a, p, ctl_dev, dev, idle_ms ? idle_ms : BANK_STREAM_IDLE_MS);
-    return hipGetLastError();
-}
-
 // bank_stream_prog_kernel with the bus segment (FR_STREAM_BUS): the voices_done ticket goes to the whole wave.
 __global__ void __launch_bounds__(1024) bank_stream_bus_kernel(BankArgs a, StreamProgArgs p, BankStreamCtl *ctl, BankStreamDev *dev, uint32_t idle_ms) {
     __shared__ float sm[STREAM_NW][64];
@@ -2186,11 +2178,12 @@ __global__ void __launch_bounds__(1024) bank_stream_bus_kernel(BankArgs a, Strea
     if (blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store(&ctl->alive, 0u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-hipError_t launch_bank_stream_bus(const BankArgs &a, const StreamProgArgs &p, BankStreamCtl *ctl_dev, BankStreamDev *dev, uint32_t idle_ms, hipStream_t s) {
+// (bank_stream_prog_kernel and bank_stream_bus_kernel: the same arguments, the same checks)
+static hipError_t launch_bank_stream_prog(bool bus, const BankArgs &a, const StreamProgArgs &p, BankStreamCtl *ctl_dev, BankStreamDev *dev, uint32_t idle_ms, hipStream_t s) {
     if (!stream_bank_ok(a.log2_p, a.chunk_log2, a.n_voices, a.ws, a.tickets) || !stream_progs_ok(p, p.bank_to_ring != 0)) return hipErrorInvalidValue;
     if (a.leaf_variant != 1 || !a.out || !a.rows || !ctl_dev || !dev) return hipErrorInvalidValue;
     const uint32_t wgs = a.n_voices << (a.log2_p - a.chunk_log2);
-    hipLaunchKernelGGL(bank_stream_bus_kernel, dim3(wgs), dim3(1024), 0, s, a, p, ctl_dev, dev, idle_ms ? idle_ms : BANK_STREAM_IDLE_MS);
+    hipLaunchKernelGGL(bus ? bank_stream_bus_kernel : bank_stream_prog_kernel, dim3(wgs), dim3(1024), 0, s, a, p, ctl_dev, dev, idle_ms ? idle_ms : BANK_STREAM_IDLE_MS);
     return hipGetLastError();
 }
 
@@ -2228,7 +2221,7 @@ __global__ void __launch_bounds__(1024) bank_stream_in_kernel(BankArgs a, Stream
     if (blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store(&ctl->alive, 0u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-hipError_t launch_bank_stream_in(const BankArgs &a, const StreamProgArgs &p, uint32_t n_rows, BankStreamInCtl *ctl_dev, BankStreamInDev *dev, uint32_t idle_ms,
+static hipError_t launch_bank_stream_in(const BankArgs &a, const StreamProgArgs &p, uint32_t n_rows, BankStreamInCtl *ctl_dev, BankStreamInDev *dev, uint32_t idle_ms,
                                  hipStream_t s) {
     if (!stream_bank_ok(a.log2_p, a.chunk_log2, a.n_voices, a.ws, a.tickets) || !stream_progs_ok(p, p.bank_to_ring != 0)) return hipErrorInvalidValue;
     if (a.leaf_variant != 1 || !a.out || !a.rows || !ctl_dev || !dev) return hipErrorInvalidValue;
@@ -2307,14 +2300,6 @@ static bool stream_table_ok(const StreamBanksArgs &t, const BankArgs &a, const S
     return n_rows != 0 && n_rows <= BANK_STREAM_ROWS;
 }
 
-hipError_t launch_bank_stream_banks(const StreamBanksArgs &t, const BankArgs &a, const StreamProgArgs &p, uint32_t n_rows, BankStreamInCtl *ctl_dev, BankStreamInDev *dev,
-                                    uint32_t idle_ms, hipStream_t s) {
-    uint64_t wgs = 0;
-    if (!stream_table_ok(t, a, p, n_rows, wgs) || !ctl_dev || !dev) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(bank_stream_banks_kernel, dim3((uint32_t)wgs), dim3(1024), 0, s, t, a, p, n_rows, ctl_dev, dev, idle_ms ? idle_ms : BANK_STREAM_IDLE_MS);
-    return hipGetLastError();
-}
-
 // bank_stream_banks_kernel for plans with loop programs (FR_STREAM_LOOPS, kernels.hpp): the bank table also for one bank, the
 // same doorbell, hand-overs and bus segment; the programs go through stream_run_programs_loops with a load and a store tile.
 __global__ void __launch_bounds__(1024) bank_stream_loops_kernel(StreamBanksArgs t, BankArgs a, StreamProgArgs p, uint32_t n_rows, BankStreamInCtl *ctl,
@@ -2360,12 +2345,14 @@ __global__ void __launch_bounds__(1024) bank_stream_loops_kernel(StreamBanksArgs
     if (blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store(&ctl->alive, 0u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-hipError_t launch_bank_stream_loops(const StreamBanksArgs &t, const BankArgs &a, const StreamProgArgs &p, uint32_t n_rows, uint32_t max_stride, uint32_t max_loads,
-                                    uint32_t max_stores, BankStreamInCtl *ctl_dev, BankStreamInDev *dev, uint32_t idle_ms, hipStream_t s) {
-    if (max_stride > BANK_STREAM_LOOP_MAX_STRIDE || max_loads > BANK_STREAM_LOOP_LOADS || max_stores > BANK_STREAM_LOOP_STORES) return hipErrorInvalidValue;
+// (bank_stream_banks_kernel and bank_stream_loops_kernel: the same arguments; the limits concern loop programs only)
+static hipError_t launch_bank_stream_banks(bool loops, const StreamBanksArgs &t, const BankArgs &a, const StreamProgArgs &p, uint32_t n_rows, uint32_t max_stride,
+                                           uint32_t max_loads, uint32_t max_stores, BankStreamInCtl *ctl_dev, BankStreamInDev *dev, uint32_t idle_ms, hipStream_t s) {
+    if (loops && (max_stride > BANK_STREAM_LOOP_MAX_STRIDE || max_loads > BANK_STREAM_LOOP_LOADS || max_stores > BANK_STREAM_LOOP_STORES)) return hipErrorInvalidValue;
     uint64_t wgs = 0;
-    if (!stream_table_ok(t, a, p, n_rows, wgs) || !p.n_rings || !ctl_dev || !dev) return hipErrorInvalidValue;   // (a loop lives in a ring)
-    hipLaunchKernelGGL(bank_stream_loops_kernel, dim3((uint32_t)wgs), dim3(1024), 0, s, t, a, p, n_rows, ctl_dev, dev, idle_ms ? idle_ms : BANK_STREAM_IDLE_MS);
+    if (!stream_table_ok(t, a, p, n_rows, wgs) || (loops && !p.n_rings) || !ctl_dev || !dev) return hipErrorInvalidValue;   // (a loop lives in a ring)
+    hipLaunchKernelGGL(loops ? bank_stream_loops_kernel : bank_stream_banks_kernel, dim3((uint32_t)wgs), dim3(1024), 0, s, t, a, p, n_rows, ctl_dev, dev,
+                       idle_ms ? idle_ms : BANK_STREAM_IDLE_MS);
     return hipGetLastError();
 }
 
@@ -2440,7 +2427,7 @@ __global__ void __launch_bounds__(1024) bank_stream_general_kernel(StreamBanksAr
     if (blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store(&ctl->alive, 0u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-hipError_t launch_bank_stream_general(const StreamBanksArgs &t, const StreamGeneralArgs &g, const BankArgs &a, const StreamProgArgs &p, uint32_t n_rows, uint32_t max_stride,
+static hipError_t launch_bank_stream_general(const StreamBanksArgs &t, const StreamGeneralArgs &g, const BankArgs &a, const StreamProgArgs &p, uint32_t n_rows, uint32_t max_stride,
                                       uint32_t max_loads, uint32_t max_stores, BankStreamInCtl *ctl_dev, BankStreamInDev *dev, uint32_t idle_ms, hipStream_t s) {
     if (max_stride > BANK_STREAM_LOOP_MAX_STRIDE || max_loads > BANK_STREAM_LOOP_LOADS || max_stores > BANK_STREAM_LOOP_STORES) return hipErrorInvalidValue;
     if (g.mask == 0 || t.n_banks == 0 || t.n_banks > BANK_STREAM_BANKS || (g.mask >> t.n_banks) != 0) return hipErrorInvalidValue;
@@ -2450,6 +2437,23 @@ hipError_t launch_bank_stream_general(const StreamBanksArgs &t, const StreamGene
     if (!stream_table_ok(t, a, p, n_rows, wgs, g.mask) || (max_stride && !p.n_rings) || !ctl_dev || !dev) return hipErrorInvalidValue;
     hipLaunchKernelGGL(bank_stream_general_kernel, dim3((uint32_t)wgs), dim3(1024), 0, s, t, g, a, p, n_rows, ctl_dev, dev, idle_ms ? idle_ms : BANK_STREAM_IDLE_MS);
     return hipGetLastError();
+}
+
+// The one entry of the resident launches (kernels.hpp StreamLaunchArgs): each launcher above takes what its kernel takes.
+hipError_t launch_bank_stream(StreamKernel k, const StreamLaunchArgs &x, hipStream_t s) {
+    BankStreamCtl *const ctl = static_cast<BankStreamCtl *>(x.ctl_dev);          // (the form is the kernel's: kernels.hpp StreamKernel)
+    BankStreamDev *const dev = static_cast<BankStreamDev *>(x.dev);
+    BankStreamInCtl *const ctl_in = static_cast<BankStreamInCtl *>(x.ctl_dev);
+    BankStreamInDev *const dev_in = static_cast<BankStreamInDev *>(x.dev);
+    switch (k) {
+    case StreamKernel::plain: return launch_bank_stream_plain(x.a, ctl, dev, x.idle_ms, s);
+    case StreamKernel::prog: case StreamKernel::bus: return launch_bank_stream_prog(k == StreamKernel::bus, x.a, x.p, ctl, dev, x.idle_ms, s);
+    case StreamKernel::in: return launch_bank_stream_in(x.a, x.p, x.n_rows, ctl_in, dev_in, x.idle_ms, s);
+    case StreamKernel::banks: case StreamKernel::loops:
+        return launch_bank_stream_banks(k == StreamKernel::loops, x.t, x.a, x.p, x.n_rows, x.max_stride, x.max_loads, x.max_stores, ctl_in, dev_in, x.idle_ms, s);
+    case StreamKernel::general: return launch_bank_stream_general(x.t, x.g, x.a, x.p, x.n_rows, x.max_stride, x.max_loads, x.max_stores, ctl_in, dev_in, x.idle_ms, s);
+    default: return hipErrorInvalidValue;
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------

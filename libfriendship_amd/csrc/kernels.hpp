@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime_api.h>
 
+#include <cstddef>
 #include <cstdint>
 
 namespace fr {
@@ -118,8 +119,7 @@ constexpr uint32_t BANK_STREAM_WGS = 256;      // most workgroups a stream may u
 constexpr uint32_t BANK_STREAM_IDLE_MS = 2000; // the resident launch ends itself after this long without a block
 // `a`: as for the short-call kernel (small_call == 2, 16 waves, chunk_log2 chosen so that voices * chunks <= the CUs of the device),
 // out = device pointer of the mapped [n_voices][64] host result (out_stride = 64), ws / tickets allocated for 64 frames.
-// Launches exactly n_voices * chunks workgroups.  idle_ms: 0 = BANK_STREAM_IDLE_MS.
-hipError_t launch_bank_stream(const BankArgs &a, BankStreamCtl *ctl_dev, BankStreamDev *dev, uint32_t idle_ms, hipStream_t s);
+// Launches exactly n_voices * chunks workgroups.  idle_ms: 0 = BANK_STREAM_IDLE_MS.  (The entry: launch_bank_stream, below.)
 uint64_t bank_blocks(const BankArgs &a);
 hipError_t launch_bank(const BankArgs &a, hipStream_t s);
 hipError_t launch_gbank(const BankArgs &a, hipStream_t s);   // voices that are arbitrary Sum2 trees (schedule form)
@@ -212,12 +212,10 @@ struct StreamProgArgs {
     uint32_t bank_to_ring;         // BankArgs::rows are ring indices
     uint32_t sparkle;              // FR_SEMANTICS_SPARKLE
 };
-hipError_t launch_bank_stream_prog(const BankArgs &a, const StreamProgArgs &p, BankStreamCtl *ctl_dev, BankStreamDev *dev, uint32_t idle_ms, hipStream_t s);
 // bank_stream_bus_kernel (FR_STREAM_BUS): bank_stream_prog_kernel, and the wave whose voices_done ticket is the block's last
 // (n_voices - 1) interprets progs[voice_first[n_voices] .. voice_first[n_voices + 1]) -- the bus programs, which read several
 // voices of the same block -- before it resets the counter and stores the done tag.  Every voice acknowledged its ring and
 // row stores before its ticket, the last arriver loads after its own: no wait, no acquire or release, no new polling loop.
-hipError_t launch_bank_stream_bus(const BankArgs &a, const StreamProgArgs &p, BankStreamCtl *ctl_dev, BankStreamDev *dev, uint32_t idle_ms, hipStream_t s);
 
 // bank_stream_in_kernel (FR_STREAM_INPUTS): bank_stream_bus_kernel's work -- per-voice programs, then the bus programs in the
 // block's last arriver, a segment that may be empty -- for programs that read control rows: up to BANK_STREAM_ROWS input slots
@@ -242,8 +240,6 @@ struct BankStreamInDev {      // device memory
     uint32_t pad[13];
     float rows[BANK_STREAM_ROWS][64];
 };
-hipError_t launch_bank_stream_in(const BankArgs &a, const StreamProgArgs &p, uint32_t n_rows, BankStreamInCtl *ctl_dev, BankStreamInDev *dev,
-                                 uint32_t idle_ms, hipStream_t s);
 
 // bank_stream_banks_kernel (FR_STREAM_BANKS): bank_stream_in_kernel's work for a plan of 2..BANK_STREAM_BANKS bank launches --
 // voices of several partial counts, voices that write rows next to voices that feed rings -- in ONE resident launch.  The bank
@@ -263,8 +259,6 @@ struct StreamBanksArgs {
         uint32_t first_wg, first_voice, n_voices, log2_p, chunk_log2, fast_ok, to_ring;
     } bank[BANK_STREAM_BANKS];
 };
-hipError_t launch_bank_stream_banks(const StreamBanksArgs &t, const BankArgs &a, const StreamProgArgs &p, uint32_t n_rows, BankStreamInCtl *ctl_dev, BankStreamInDev *dev,
-                                    uint32_t idle_ms, hipStream_t s);
 
 // bank_stream_loops_kernel (FR_STREAM_LOOPS): bank_stream_banks_kernel's work -- the bank table also for one bank -- for plans
 // whose streamed programs hold feedback loops shorter than a block.  StageProg::pad[0] of a streamed program is its STRIDE
@@ -286,10 +280,8 @@ hipError_t launch_bank_stream_banks(const StreamBanksArgs &t, const BankArgs &a,
 // + BANK_STREAM_LOOP_INSTRS * 16 = 36 880.
 constexpr uint32_t BANK_STREAM_LOOP_LOADS = 32, BANK_STREAM_LOOP_STORES = 16, BANK_STREAM_LOOP_MAX_STRIDE = 63;   // (powers of two: slots are masked)
 constexpr uint32_t BANK_STREAM_LOOP_INSTRS = 512;
-// `max_stride`, `max_loads`, `max_stores`: the largest stride, load count and store-slot count of the streamed programs, as
-// the host prepared them; the launch refuses what the kernel's tiles do not hold.
-hipError_t launch_bank_stream_loops(const StreamBanksArgs &t, const BankArgs &a, const StreamProgArgs &p, uint32_t n_rows, uint32_t max_stride, uint32_t max_loads,
-                                    uint32_t max_stores, BankStreamInCtl *ctl_dev, BankStreamInDev *dev, uint32_t idle_ms, hipStream_t s);
+// StreamLaunchArgs::max_stride, max_loads, max_stores: the largest stride, load count and store-slot count of the streamed
+// programs, as the host prepared them; the launch refuses what the kernel's tiles do not hold.
 
 // bank_stream_general_kernel (FR_STREAM_GENERAL): bank_stream_loops_kernel's work for plans with SCHEDULE BANKS -- voices of any
 // partial count and any Sum2 tree, in the general form of launch_gbank (BankArgs::groups / group_off above), and balanced
@@ -308,8 +300,40 @@ struct StreamGeneralArgs {
         const uint32_t *groups, *group_off;
     } bank[BANK_STREAM_BANKS];
 };
-hipError_t launch_bank_stream_general(const StreamBanksArgs &t, const StreamGeneralArgs &g, const BankArgs &a, const StreamProgArgs &p, uint32_t n_rows, uint32_t max_stride,
-                                      uint32_t max_loads, uint32_t max_stores, BankStreamInCtl *ctl_dev, BankStreamInDev *dev, uint32_t idle_ms, hipStream_t s);
+
+// The seven resident kernels (streamplan.hpp stream_launch chooses; `none`: no resident launch yet) and their one launch entry.
+// plain, prog and bus have the one-row doorbell (BankStreamCtl / BankStreamDev), the others the doorbell of rows (BankStreamIn*).
+enum class StreamKernel : uint32_t { none, plain, prog, bus, in, banks, loops, general };
+// Everything a resident launch may need; each kernel's launcher (kernels.hip) reads and checks what its kernel takes.
+struct StreamLaunchArgs {
+    BankArgs a;
+    StreamProgArgs p;
+    StreamBanksArgs t;
+    StreamGeneralArgs g;
+    uint32_t n_rows, max_stride, max_loads, max_stores;
+    void *ctl_dev, *dev;                        // the control block as the device addresses it and the device block, of the kernel's doorbell form
+    uint32_t idle_ms;                           // 0 = BANK_STREAM_IDLE_MS
+};
+hipError_t launch_bank_stream(StreamKernel k, const StreamLaunchArgs &x, hipStream_t s);
+
+// The host's side of a doorbell by its form: all its words (the stop goes to every one), the done tag, the two blocks' sizes.
+static_assert(offsetof(BankStreamCtl, row) == offsetof(BankStreamInCtl, rows), "a one-row doorbell is the first row of a doorbell of rows");
+static_assert(offsetof(BankStreamCtl, done) == sizeof(BankStreamCtl::row) && offsetof(BankStreamCtl, alive) == offsetof(BankStreamCtl, done) + 4 &&
+              offsetof(BankStreamInCtl, done) == sizeof(BankStreamInCtl::rows) && offsetof(BankStreamInCtl, alive) == offsetof(BankStreamInCtl, done) + 4, "done and alive follow the rows");
+struct StreamDoorbell {
+    unsigned long long *words;
+    size_t n_words;
+    uint32_t *done;
+    size_t ctl_bytes, dev_bytes;
+};
+inline StreamDoorbell stream_doorbell(void *ctl, bool rows) {
+    if (rows) {
+        BankStreamInCtl *c = static_cast<BankStreamInCtl *>(ctl);
+        return {c ? c->rows[0] : nullptr, (size_t)BANK_STREAM_ROWS * 64, c ? &c->done : nullptr, sizeof(BankStreamInCtl), sizeof(BankStreamInDev)};
+    }
+    BankStreamCtl *c = static_cast<BankStreamCtl *>(ctl);
+    return {c ? c->row : nullptr, 64, c ? &c->done : nullptr, sizeof(BankStreamCtl), sizeof(BankStreamDev)};
+}
 
 // One step of the partial-block exchange (friendship_render.h FR_SHARD_PARTIALS): row i, window frame t:
 //   v = lo[i][t] + hi[i][t]         the Sum2 node one level up: left sub-tree + right sub-tree, one f32 add

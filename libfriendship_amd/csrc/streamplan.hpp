@@ -28,6 +28,9 @@
 // of general voices (items plus a merge schedule, match.hpp), or a balanced bank of 32 or 64 partials, each voice a one-item
 // schedule -- gets one workgroup per voice, no chunks, and that workgroup runs the voice's schedule on its 16 waves
 // (kernels.hip bank_stream_general_kernel).  Everything about programs applies to such a voice as to any other.
+// HOW a served plan is launched is one rule as well (stream_path, stream_launch, plain_stream_launch, at the end): the path, the
+// kernel, its doorbell form, its tables, the loop limits, the workgroups.  fr_stream_begin, the seek, the block, the stop and
+// fr_plan_json's "kernel" read the StreamLaunch it returns and decide nothing themselves.
 #pragma once
 
 #include <algorithm>
@@ -71,6 +74,7 @@ struct StreamEnv {
     bool banks = false;              // FR_STREAM_BANKS: 2..STREAM_MAX_BANKS bank launches in one resident launch
     bool loops = false;              // FR_STREAM_LOOPS: feedback loops shorter than a block, and the taps behind them
     bool general = false;            // FR_STREAM_GENERAL: schedule banks -- general voices, balanced voices of 32 or 64 partials
+    bool programs = false;           // FR_STREAM_PROGRAMS: the program path exists (stream_path; plan_stream does not ask)
 };
 
 // One bank of a streamed plan.  Voices [first_voice, first_voice + voices) of the global numbering; workgroups
@@ -504,6 +508,69 @@ inline StreamPlan plan_stream(const StagedPlan &sp, const std::vector<const Bank
     s.input_slots.insert(s.input_slots.end(), others.begin(), others.end());
     s.servable = true;
     return s;
+}
+
+// ---- the launch rule ----------------------------------------------------------------------------------------------------------
+inline const char *stream_kernel_name(StreamKernel k) {
+    static const char *const names[] = {"", "bank_stream_kernel", "bank_stream_prog_kernel", "bank_stream_bus_kernel", "bank_stream_in_kernel",
+                                        "bank_stream_banks_kernel", "bank_stream_loops_kernel", "bank_stream_general_kernel"};
+    return names[(uint32_t)k < sizeof names / sizeof names[0] ? (uint32_t)k : 0];
+}
+
+inline bool stream_kernel_by_plan(StreamKernel k) { return k >= StreamKernel::in; }
+
+struct StreamLaunch {
+    StreamKernel kernel = StreamKernel::none;
+    bool rows_doorbell = false;      // the doorbell is n_rows rows (BankStreamInCtl / BankStreamInDev); else one row (BankStreamCtl / BankStreamDev)
+    uint32_t n_rows = 1;             // the rows a block brings: StreamPlan::input_slots, in that order (one row: slot 0)
+    bool own_instrs = false;         // the programs run from the stream's own copy of their instructions (S_INPUT by row, store slots)
+    bool bank_table = false;         // the banks travel as a table (StreamBanksArgs), voices numbered globally
+    bool schedule_table = false;     // ... and the schedule banks' schedules next to it (StreamGeneralArgs)
+    uint32_t max_stride = 0, max_loads = 0, max_stores = 0;   // the loop programs' largest stride, load count and store-slot count
+    uint32_t workgroups = 0;
+    bool by_plan = false;            // the plan alone decides the kernel: fr_plan_json names it before any launch (stream_kernel_by_plan)
+};
+
+// The path fr_stream_begin takes: true = the program path (plan_stream, stream_launch), false = the plain path (one balanced bank
+// that writes the rows: plain_stream_launch).  FR_STREAM_BANKS: several banks take the program path even without programs and
+// rings; FR_STREAM_GENERAL: so does a bank that the option may serve by schedule -- general voices, voices below 128 partials.
+inline bool stream_path(const StagedPlan &sp, const std::vector<const BankLaunch *> &banks, const StreamEnv &env) {
+    const bool by_schedule = env.general && std::any_of(banks.begin(), banks.end(), [](const BankLaunch *b) { return b->general || b->log2_p < 7; });
+    return env.programs && (!sp.progs.empty() || sp.uses_rings() || (env.banks && banks.size() > 1) || by_schedule);
+}
+
+// The launch of a servable plan of the program path.  The one cascade: general > loops > banks > in > bus > prog.
+inline StreamLaunch stream_launch(const StagedPlan &sp, const StreamPlan &s) {
+    StreamLaunch l;
+    l.kernel = s.has_general() ? StreamKernel::general : s.has_loops() ? StreamKernel::loops : s.banks.size() > 1 ? StreamKernel::banks
+               : s.input_slots.size() > 1 ? StreamKernel::in : s.bus_programs() ? StreamKernel::bus : StreamKernel::prog;
+    l.rows_doorbell = l.own_instrs = l.by_plan = stream_kernel_by_plan(l.kernel);
+    l.bank_table = l.kernel >= StreamKernel::banks;
+    l.schedule_table = l.kernel == StreamKernel::general;
+    l.n_rows = l.rows_doorbell ? (uint32_t)s.input_slots.size() : 1u;
+    for (size_t i = 0; i < s.progs.size(); ++i) {    // (the tiles' fill is counted from the plan's instructions; the store slots are the stored rings)
+        if (!s.loop_stride[i]) continue;
+        const StageProg &pg = sp.progs[s.progs[i]];
+        l.max_stride = std::max(l.max_stride, s.loop_stride[i]);
+        l.max_loads = std::max(l.max_loads, stream_loop_loads(pg, sp.instrs.data() + pg.first_instr));
+        l.max_stores = std::max(l.max_stores, (uint32_t)stream_stored_rings(pg, sp.instrs.data() + pg.first_instr).size());
+    }
+    l.workgroups = s.workgroups();
+    return l;
+}
+
+// The plain path's launch: one bank of `voices` balanced voices of 1 << log2_p partials (log2_p >= 7), a one-row doorbell, no
+// tables; `bank` gets the chunks.  False: more than max_wgs workgroups (the caller's limit: the plain path counts an unknown CU
+// count as one CU, stream_max_wgs() as the kernel's limit).
+inline bool plain_stream_launch(uint32_t voices, uint32_t log2_p, uint64_t max_wgs, StreamBank &bank, StreamLaunch &l) {
+    std::vector<StreamBank> one(1);
+    one[0].voices = voices; one[0].log2_p = log2_p;
+    if (!deal_stream_chunks(one, max_wgs)) return false;
+    bank = one[0];
+    l = StreamLaunch{};
+    l.kernel = StreamKernel::plain;
+    l.workgroups = voices << (log2_p - bank.chunk_log2);
+    return true;
 }
 
 }  // namespace fr

@@ -93,7 +93,7 @@ hipError_t launch_pull(const PullArgs &a, hipStream_t) {
     return hipSuccess;
 }
 
-hipError_t launch_bank_stream(const BankArgs &, BankStreamCtl *, BankStreamDev *, uint32_t, hipStream_t) { return hipErrorNotSupported; }   // (no resident launches on the simulator)
+hipError_t launch_bank_stream(StreamKernel, const StreamLaunchArgs &, hipStream_t) { return hipErrorNotSupported; }   // (no resident launches on the simulator)
 hipError_t launch_bank(const BankArgs &a, hipStream_t) {
     ++fr_sim_launches[C_BANK];
     const size_t P = (size_t)1 << a.log2_p;
