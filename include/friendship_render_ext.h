@@ -116,6 +116,19 @@ extern "C" {
  * "partials" and 1 chunk); "kernel" is "bank_stream_general_kernel" exactly when a voice is served this way.  Still refused:
  * a voice of more than 32768 leaves (one workgroup renders it; the reason names the count and the limit), more voices than
  * the device has compute units, compiled and track voices.
+ *
+ * FR_STREAM_DYN = 0 / 1 (default 0; read strictly from the environment too; does nothing unless FR_STREAM_PROGRAMS=1):
+ * block streaming also serves a voice delayed by a SIGNAL amount -- a chorus, a flanger, a vibrato
+ * (Delay(voice, base + depth * lfo(t))), a delay time on a knob (Delay(voice, Minimum(In(1), 48)), with FR_STREAM_INPUTS) --
+ * and a constant delayed by a signal amount.  The planner's proven bound for the amount sizes the voice's delay line as in
+ * fr_fill_buffer; an eighth resident kernel (bank_stream_dyn_kernel: the seventh's work with an interpreter that knows the
+ * two ops) reads it with the reference's cast of the amount: same bits, in both semantics.  A delayed voice other than the
+ * row's own makes the row a mix bus (FR_STREAM_BUS).  It composes with every option above.  With 0 nothing changes: the same
+ * plans are served and refused, with the same reasons, by the same kernels.  "stream" gains "dyn_reads" and "dyn_steps" (the
+ * streamed programs' signal delays of a voice and of a constant) and "lookback" (the deepest delay-line read, the bound
+ * included); "kernel" is "bank_stream_dyn_kernel" exactly when there is such a delay.  Still refused, each with its reason: a
+ * signal delay inside a feedback loop shorter than a block, of a computed value (a ring that a program stores), of an input
+ * row (a stream keeps no input history), and one whose bound was observed from input rows (FR_DELAY_OBSERVED).
  */
 typedef struct fr_option {
     const char *name;              /* e.g. "FR_BANK_SHORT" */

@@ -197,7 +197,7 @@ static std::string stage_variant(const StageLaunchNote &n, const Plan &p) {
     return k;
 }
 
-constexpr size_t N_OPTIONS = 37;         // per-renderer options (friendship_render_ext.h; the table below fr_renderer)
+constexpr size_t N_OPTIONS = 38;        // per-renderer options (friendship_render_ext.h; the table below fr_renderer)
 
 struct TimerClass {
     double ms = 0;
@@ -553,8 +553,8 @@ struct fr_renderer {
         }
         return d_tickets.as<uint32_t>();
     }
-    // FR_STREAM_PROGRAMS, _BUS, _INPUTS, _LOOPS, _BANKS, _GENERAL (the options table says what each serves; streamplan.hpp StreamEnv)
-    bool stream_programs = false, stream_bus = false, stream_inputs = false, stream_loops = false, stream_banks = false, stream_general = false;
+    // FR_STREAM_PROGRAMS, _BUS, _INPUTS, _LOOPS, _BANKS, _GENERAL, _DYN (the options table says what each serves; streamplan.hpp StreamEnv)
+    bool stream_programs = false, stream_bus = false, stream_inputs = false, stream_loops = false, stream_banks = false, stream_general = false, stream_dyn = false;
     std::vector<const BankLaunch *> stream_bank_list() const {
         std::vector<const BankLaunch *> banks;
         for (const BankStage &bs : plan.banks) banks.push_back(&bs.grp);
@@ -569,7 +569,7 @@ struct fr_renderer {
         env.sharded = sharded();
         env.track_history = tail_on();
         env.programs = stream_programs; env.bus = stream_bus; env.inputs = stream_inputs;
-        env.banks = stream_banks; env.loops = stream_loops; env.general = stream_general;
+        env.banks = stream_banks; env.loops = stream_loops; env.general = stream_general; env.dyn = stream_dyn;
         return env;
     }
     StreamPlan plan_stream_now() const { return plan_stream(plan.sp, stream_bank_list(), stream_env()); }
@@ -2208,7 +2208,7 @@ void fr_renderer::begin_program_stream(uint32_t n_slots) {
             throw Error(FR_ERR_DEVICE, "internal: a streamed program out of the plan's bounds");
         for (uint32_t k = 0; k < pg.n_instr; ++k) {
             const StageInstr &in = sp.instrs[pg.first_instr + k];
-            if ((in.op == S_READ || in.op == S_STORE) && in.buf >= sp.n_rings) throw Error(FR_ERR_DEVICE, "internal: a streamed program reads a ring the plan does not have");
+            if ((in.op == S_READ || in.op == S_READ_DYN || in.op == S_STORE) && in.buf >= sp.n_rings) throw Error(FR_ERR_DEVICE, "internal: a streamed program reads a ring the plan does not have");
         }
     }
     if (s.banks.size() != plan.banks.size() || s.banks.size() > BANK_STREAM_BANKS) throw Error(FR_ERR_DEVICE, "internal: the stream's banks are not the plan's");
@@ -2431,6 +2431,7 @@ int64_t env_strict_stream_banks(const char *e);
 int64_t env_strict_loop_tiles(const char *e);
 int64_t env_strict_stream_loops(const char *e);
 int64_t env_strict_stream_general(const char *e);
+int64_t env_strict_stream_dyn(const char *e);
 bool parse_option(const Knob &k, const char *s, int64_t &v);
 
 const Knob kKnobs[] = {
@@ -2527,6 +2528,9 @@ const Knob kKnobs[] = {
     // 64 partials, one workgroup per voice (streamplan.hpp StreamEnv::general; fr_plan_json: stream.general_voices).  Inert
     // without FR_STREAM_PROGRAMS.  Strict and listed once set.
     {"FR_STREAM_GENERAL", 0, 0, 1, 0, nullptr, 0, env_strict_stream_general, [](fr_renderer &r, int64_t v, bool) { r.stream_general = v != 0; }, LISTED_WHEN_SET},
+    // Delays of a voice by a signal amount in block streaming -- a chorus, a flanger, a vibrato, a delay time on a knob
+    // (streamplan.hpp StreamEnv::dyn; fr_plan_json: stream.dyn_reads).  Inert without FR_STREAM_PROGRAMS.  Strict and listed once set.
+    {"FR_STREAM_DYN", 0, 0, 1, 0, nullptr, 0, env_strict_stream_dyn, [](fr_renderer &r, int64_t v, bool) { r.stream_dyn = v != 0; }, LISTED_WHEN_SET},
 };
 static_assert(sizeof kKnobs / sizeof kKnobs[0] == N_OPTIONS, "N_OPTIONS counts the rows of kKnobs");
 
@@ -2545,6 +2549,7 @@ int64_t env_strict_stream_banks(const char *e) { return env_strict("FR_STREAM_BA
 int64_t env_strict_loop_tiles(const char *e) { return env_strict("FR_LOOP_TILES", e); }
 int64_t env_strict_stream_loops(const char *e) { return env_strict("FR_STREAM_LOOPS", e); }
 int64_t env_strict_stream_general(const char *e) { return env_strict("FR_STREAM_GENERAL", e); }
+int64_t env_strict_stream_dyn(const char *e) { return env_strict("FR_STREAM_DYN", e); }
 
 bool parse_option(const Knob &k, const char *s, int64_t &v) {
     if (k.word && std::strcmp(s, k.word) == 0) {
@@ -3177,6 +3182,9 @@ const char *fr_plan_json(fr_renderer *r) {
                 for (uint32_t n : s.general_voices) gv += (gv.empty() ? "" : ",") + std::to_string(n);
                 r->plan_json_cache += ",\"general_voices\":[" + gv + "],\"general_max_leaves\":" + std::to_string(STREAM_GENERAL_MAX_LEAVES);
             }
+            if (r->stream_dyn)                                   // FR_STREAM_DYN: the assigned programs' Delays by a signal amount, and the deepest ring read
+                r->plan_json_cache += ",\"dyn_reads\":" + std::to_string(s.dyn_reads) + ",\"dyn_steps\":" + std::to_string(s.dyn_steps) +
+                                      ",\"lookback\":" + std::to_string(s.lookback);
             const StreamLaunch l = s.servable ? stream_launch(r->plan.sp, s) : StreamLaunch{};
             const char *kernel = stream_kernel_name(l.by_plan ? l.kernel : stream_kernel_by_plan(r->strm.last_kernel) ? StreamKernel::none : r->strm.last_kernel);
             if (r->stream_banks) {                               // FR_STREAM_BANKS: the banks of the launch, in plan order

@@ -1200,9 +1200,23 @@ __device__ __forceinline__ float stream_prog_load(const StreamProgArgs &p, const
     }
 }
 
+// A Delay by a signal amount (FR_STREAM_DYN; kernels.hpp bank_stream_dyn_kernel), lane = frame: the reference's cast of the
+// amount (delay_frames, as pull_kernel and stage_kernel), then S_READ_DYN reads the ring `frames` back and S_STEP_DYN yields its
+// constant; 0.0 where the cast fails or the source frame lies before frame 0.  The rule admits bank rings only: this wave (a bus
+// program: every voice) has stored and acknowledged the block's frames, earlier blocks everything older, so the load -- L2's,
+// never a CU's L1: the finisher of a voice changes CU from block to block -- finds any offset in [0, bound].  The index is
+// masked.
+__device__ __forceinline__ float stream_prog_dyn(const float *rings, uint64_t ring_mask, uint32_t sparkle, uint32_t op, uint32_t imm, uint32_t buf, float amount,
+                                                 uint64_t frame) {
+    uint64_t fr;
+    if (!delay_frames(amount, fr, sparkle != 0u) || frame < fr) return 0.0f;
+    if (op == S_STEP_DYN) return __uint_as_float(imm);
+    return __hip_atomic_load(rings + (size_t)buf * (ring_mask + 1) + ((frame - fr) & ring_mask), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 // The interpreter: programs [p_first, p_end) in order, lane = frame, in wave 0 of a finishing workgroup; `regs` are its
-// registers, [register][lane] in LDS; `out` the mapped host rows.
-template <class Input>
+// registers, [register][lane] in LDS; `out` the mapped host rows.  DYN: it also knows S_READ_DYN and S_STEP_DYN.
+template <bool DYN = false, class Input>
 __device__ __forceinline__ void stream_run_programs(float *out, const StreamProgArgs &p, float (&regs)[STAGE_REGS][64], uint32_t p_first, uint32_t p_end, uint64_t frame,
                                                     uint32_t lane, bool live, Input &&input) {
     const uint64_t ring_cap = p.ring_mask + 1;
@@ -1231,6 +1245,12 @@ __device__ __forceinline__ void stream_run_programs(float *out, const StreamProg
             case S_STORE:
                 if (live) __hip_atomic_store(p.rings + (size_t)in.buf * ring_cap + (frame & p.ring_mask), regs[in.a][lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 continue;
+            case S_READ_DYN: case S_STEP_DYN:
+                if constexpr (DYN) {
+                    v = stream_prog_dyn(p.rings, p.ring_mask, p.sparkle, in.op, in.imm, in.buf, regs[in.a][lane], frame);
+                    break;
+                }
+                [[fallthrough]];
             default: v = stream_prog_load(p, in, frame, input); break;
             }
             regs[in.dst][lane] = v;
@@ -1349,13 +1369,14 @@ __device__ __forceinline__ void stream_run_loop_program(float *out, const Stream
 }
 
 // stream_run_programs where a program may be a loop program; one of stride 0 is a range of one program of stream_run_programs.
-template <class Input>
+// (DYN concerns those alone: the rule serves no loop program with a Delay by a signal amount.)
+template <bool DYN = false, class Input>
 __device__ __forceinline__ void stream_run_programs_loops(float *out, const StreamProgArgs &p, float (&regs)[STAGE_REGS][64], float (&ldt)[BANK_STREAM_LOOP_LOADS][64],
                                                           float (&stt)[BANK_STREAM_LOOP_STORES][64], uint4 (&lins)[BANK_STREAM_LOOP_INSTRS], uint32_t p_first,
                                                           uint32_t p_end, uint64_t head, uint32_t n, uint32_t lane, bool live, Input &&input) {
     for (uint32_t pi = p_first; pi < p_end; ++pi) {
         if (p.progs[pi].pad[0] == 0u) {
-            stream_run_programs(out, p, regs, pi, pi + 1u, head + lane, lane, live, input);
+            stream_run_programs<DYN>(out, p, regs, pi, pi + 1u, head + lane, lane, live, input);
             continue;
         }
         // what this wave has stored so far (the voice's ring, an earlier program's rings) is in L2 before it is read back
@@ -2360,9 +2381,12 @@ static hipError_t launch_bank_stream_banks(bool loops, const StreamBanksArgs &t,
 // doorbell, hand-over, programs and bus segment.  What differs is what a workgroup of a schedule bank renders: it learns before
 // the block loop, uniformly, that its bank is one; its voice is first_voice + (blockIdx.x - first_wg), its chunk count 1 (so
 // stream_hand_over returns at once), and stream_render_schedule runs the voice's items and merges.
+// The body is shared with bank_stream_dyn_kernel (FR_STREAM_DYN, kernels.hpp): DYN = the interpreter also knows the Delays by a
+// signal amount (stream_prog_dyn); a plan of that kernel need not have a schedule bank (g.mask == 0).
 static_assert(STREAM_STACK_DEPTH == GB_MAX_DEPTH, "a schedule voice's stack is the general voices'");
-__global__ void __launch_bounds__(1024) bank_stream_general_kernel(StreamBanksArgs t, StreamGeneralArgs g, BankArgs a, StreamProgArgs p, uint32_t n_rows, BankStreamInCtl *ctl,
-                                                                   BankStreamInDev *dev, uint32_t idle_ms) {
+template <bool DYN>
+__device__ __forceinline__ void bank_stream_general_body(StreamBanksArgs t, StreamGeneralArgs g, BankArgs a, StreamProgArgs p, uint32_t n_rows, BankStreamInCtl *ctl,
+                                                         BankStreamInDev *dev, uint32_t idle_ms) {
     __shared__ float sm[2][STREAM_NW][64];                   // the waves' sums: a chunk's in [0], a schedule's items alternate
     __shared__ float stack_mem[STREAM_STACK_DEPTH][64];      // a schedule voice's evaluation stack: [level][frame] of wave 0
     __shared__ float regs[STAGE_REGS][64];                   // the interpreter's registers: [register][frame] of wave 0
@@ -2416,9 +2440,9 @@ __global__ void __launch_bounds__(1024) bank_stream_general_kernel(StreamBanksAr
         if (wave == 0u && stream_hand_over(w, a.ws, a.tickets, n_voices, lane, r, result)) {
             const StreamRowsInput input{dev, lane, t_in};
             stream_store_voice(w, a.out, p, head + lane, lane, live, result);
-            stream_run_programs_loops(a.out, p, regs, ldt, stt, lins, p.voice_first[w.voice], p.voice_first[w.voice + 1], head, T, lane, live, input);
+            stream_run_programs_loops<DYN>(a.out, p, regs, ldt, stt, lins, p.voice_first[w.voice], p.voice_first[w.voice + 1], head, T, lane, live, input);
             stream_finish_bus(ctl, dev, n_voices, lane, seq, [&] {
-                stream_run_programs_loops(a.out, p, regs, ldt, stt, lins, p.voice_first[n_voices], p.voice_first[n_voices + 1], head, T, lane, live, input);
+                stream_run_programs_loops<DYN>(a.out, p, regs, ldt, stt, lins, p.voice_first[n_voices], p.voice_first[n_voices + 1], head, T, lane, live, input);
             });
         }
         head += T;
@@ -2427,15 +2451,27 @@ __global__ void __launch_bounds__(1024) bank_stream_general_kernel(StreamBanksAr
     if (blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store(&ctl->alive, 0u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-static hipError_t launch_bank_stream_general(const StreamBanksArgs &t, const StreamGeneralArgs &g, const BankArgs &a, const StreamProgArgs &p, uint32_t n_rows, uint32_t max_stride,
-                                      uint32_t max_loads, uint32_t max_stores, BankStreamInCtl *ctl_dev, BankStreamInDev *dev, uint32_t idle_ms, hipStream_t s) {
+__global__ void __launch_bounds__(1024) bank_stream_general_kernel(StreamBanksArgs t, StreamGeneralArgs g, BankArgs a, StreamProgArgs p, uint32_t n_rows, BankStreamInCtl *ctl,
+                                                                   BankStreamInDev *dev, uint32_t idle_ms) {
+    bank_stream_general_body<false>(t, g, a, p, n_rows, ctl, dev, idle_ms);
+}
+__global__ void __launch_bounds__(1024) bank_stream_dyn_kernel(StreamBanksArgs t, StreamGeneralArgs g, BankArgs a, StreamProgArgs p, uint32_t n_rows, BankStreamInCtl *ctl,
+                                                               BankStreamInDev *dev, uint32_t idle_ms) {
+    bank_stream_general_body<true>(t, g, a, p, n_rows, ctl, dev, idle_ms);
+}
+
+// (bank_stream_general_kernel and bank_stream_dyn_kernel: the same arguments; only the latter takes a plan without a schedule bank)
+static hipError_t launch_bank_stream_general(bool dyn, const StreamBanksArgs &t, const StreamGeneralArgs &g, const BankArgs &a, const StreamProgArgs &p, uint32_t n_rows,
+                                             uint32_t max_stride, uint32_t max_loads, uint32_t max_stores, BankStreamInCtl *ctl_dev, BankStreamInDev *dev, uint32_t idle_ms,
+                                             hipStream_t s) {
     if (max_stride > BANK_STREAM_LOOP_MAX_STRIDE || max_loads > BANK_STREAM_LOOP_LOADS || max_stores > BANK_STREAM_LOOP_STORES) return hipErrorInvalidValue;
-    if (g.mask == 0 || t.n_banks == 0 || t.n_banks > BANK_STREAM_BANKS || (g.mask >> t.n_banks) != 0) return hipErrorInvalidValue;
+    if ((g.mask == 0 && !dyn) || t.n_banks == 0 || t.n_banks > BANK_STREAM_BANKS || (g.mask >> t.n_banks) != 0) return hipErrorInvalidValue;
     for (uint32_t i = 0; i < t.n_banks; ++i)
         if (((g.mask >> i) & 1u) && (!g.bank[i].groups || !g.bank[i].group_off)) return hipErrorInvalidValue;
     uint64_t wgs = 0;                                         // (a schedule bank: one workgroup per voice; the total within BANK_STREAM_WGS)
     if (!stream_table_ok(t, a, p, n_rows, wgs, g.mask) || (max_stride && !p.n_rings) || !ctl_dev || !dev) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(bank_stream_general_kernel, dim3((uint32_t)wgs), dim3(1024), 0, s, t, g, a, p, n_rows, ctl_dev, dev, idle_ms ? idle_ms : BANK_STREAM_IDLE_MS);
+    hipLaunchKernelGGL(dyn ? bank_stream_dyn_kernel : bank_stream_general_kernel, dim3((uint32_t)wgs), dim3(1024), 0, s, t, g, a, p, n_rows, ctl_dev, dev,
+                       idle_ms ? idle_ms : BANK_STREAM_IDLE_MS);
     return hipGetLastError();
 }
 
@@ -2451,7 +2487,8 @@ hipError_t launch_bank_stream(StreamKernel k, const StreamLaunchArgs &x, hipStre
     case StreamKernel::in: return launch_bank_stream_in(x.a, x.p, x.n_rows, ctl_in, dev_in, x.idle_ms, s);
     case StreamKernel::banks: case StreamKernel::loops:
         return launch_bank_stream_banks(k == StreamKernel::loops, x.t, x.a, x.p, x.n_rows, x.max_stride, x.max_loads, x.max_stores, ctl_in, dev_in, x.idle_ms, s);
-    case StreamKernel::general: return launch_bank_stream_general(x.t, x.g, x.a, x.p, x.n_rows, x.max_stride, x.max_loads, x.max_stores, ctl_in, dev_in, x.idle_ms, s);
+    case StreamKernel::general: case StreamKernel::dyn:
+        return launch_bank_stream_general(k == StreamKernel::dyn, x.t, x.g, x.a, x.p, x.n_rows, x.max_stride, x.max_loads, x.max_stores, ctl_in, dev_in, x.idle_ms, s);
     default: return hipErrorInvalidValue;
     }
 }

@@ -301,9 +301,19 @@ struct StreamGeneralArgs {
     } bank[BANK_STREAM_BANKS];
 };
 
-// The seven resident kernels (streamplan.hpp stream_launch chooses; `none`: no resident launch yet) and their one launch entry.
+// bank_stream_dyn_kernel (FR_STREAM_DYN): bank_stream_general_kernel's composition -- the same body, one template on a bool -- for
+// plans whose streamed programs delay a voice by a SIGNAL amount: its interpreter also knows S_READ_DYN and S_STEP_DYN, lane =
+// frame.  frames = delay_frames(regs[a][lane]) is the reference's cast (shared with pull_kernel and stage_kernel); S_READ_DYN
+// yields ring[buf][(frame - frames) & ring_mask] when the cast succeeds and frame >= frames, else 0.0; S_STEP_DYN yields
+// bits(imm) under the same condition.  The read is a relaxed agent-scope atomic load like every ring access here: the rule
+// admits only bank rings, whose frames of this block the wave itself (a bus program: every voice) has stored and acknowledged,
+// so no acquire, release, poll or wait is added.  The index is masked: an address is inside the rings whatever the amount.
+// A plan without schedule banks is launched with mask == 0 (no schedule table).  The loop phases know no _DYN op: the rule
+// refuses one inside a loop program.  LDS: the general kernel's 45 072 bytes.
+
+// The eight resident kernels (streamplan.hpp stream_launch chooses; `none`: no resident launch yet) and their one launch entry.
 // plain, prog and bus have the one-row doorbell (BankStreamCtl / BankStreamDev), the others the doorbell of rows (BankStreamIn*).
-enum class StreamKernel : uint32_t { none, plain, prog, bus, in, banks, loops, general };
+enum class StreamKernel : uint32_t { none, plain, prog, bus, in, banks, loops, general, dyn };
 // Everything a resident launch may need; each kernel's launcher (kernels.hip) reads and checks what its kernel takes.
 struct StreamLaunchArgs {
     BankArgs a;

@@ -28,6 +28,12 @@
 // of general voices (items plus a merge schedule, match.hpp), or a balanced bank of 32 or 64 partials, each voice a one-item
 // schedule -- gets one workgroup per voice, no chunks, and that workgroup runs the voice's schedule on its 16 waves
 // (kernels.hip bank_stream_general_kernel).  Everything about programs applies to such a voice as to any other.
+// With FR_STREAM_DYN=1 (StreamEnv::dyn) a program may delay a VOICE by a signal amount -- a chorus, a flanger, a delay time on a
+// knob: S_READ_DYN of a bank's ring, whose offset is anything in [0, d_lo], so whatever the bound it counts as a read below a
+// block and binds the program to that voice (or, with FR_STREAM_BUS, makes it a bus program); and S_STEP_DYN, which touches no
+// memory.  The finishing wave has just stored the voice's frames of this block and earlier blocks stored everything older, so
+// every such offset is readable and still nobody waits (kernels.hip bank_stream_dyn_kernel).  A signal delay of a ring that a
+// program stores, one inside a loop program, a delayed read of an input row and a bound observed from input rows stay refused.
 // HOW a served plan is launched is one rule as well (stream_path, stream_launch, plain_stream_launch, at the end): the path, the
 // kernel, its doorbell form, its tables, the loop limits, the workgroups.  fr_stream_begin, the seek, the block, the stop and
 // fr_plan_json's "kernel" read the StreamLaunch it returns and decide nothing themselves.
@@ -74,6 +80,7 @@ struct StreamEnv {
     bool banks = false;              // FR_STREAM_BANKS: 2..STREAM_MAX_BANKS bank launches in one resident launch
     bool loops = false;              // FR_STREAM_LOOPS: feedback loops shorter than a block, and the taps behind them
     bool general = false;            // FR_STREAM_GENERAL: schedule banks -- general voices, balanced voices of 32 or 64 partials
+    bool dyn = false;                // FR_STREAM_DYN: Delays of a voice by a signal amount (S_READ_DYN of a bank's ring, S_STEP_DYN)
     bool programs = false;           // FR_STREAM_PROGRAMS: the program path exists (stream_path; plan_stream does not ask)
 };
 
@@ -185,6 +192,9 @@ struct StreamPlan {
     std::vector<uint32_t> voice_first;   // [voices + 2] into `progs`: [voice_first[voices], voice_first[voices + 1]) is the bus segment
     uint64_t min_ring_delay = 0;         // shortest delayed read of a ring that a program stores (0: there is none)
     uint64_t lookback = 0;               // deepest ring read of the assigned programs
+    uint32_t dyn_reads = 0;              // the assigned programs' S_READ_DYNs (StreamEnv::dyn) ...
+    uint32_t dyn_steps = 0;              // ... and their S_STEP_DYNs
+    bool has_dyn() const { return dyn_reads + dyn_steps != 0; }
     std::vector<uint32_t> input_slots{0};   // the distinct input slots the voices and the assigned programs read: slot 0 (the voices' time)
                                          // first, the others ascending -- the order of a block's streamed rows
     std::vector<uint32_t> general_voices;   // the leaf count of every voice served by schedule, in global voice order (StreamEnv::general)
@@ -376,7 +386,9 @@ inline StreamPlan plan_stream(const StagedPlan &sp, const std::vector<const Bank
         uint32_t one = NONE;
         for (uint32_t i = 0; i < pg.n_instr; ++i) {
             const StageInstr &in = sp.instrs[pg.first_instr + i];
-            if (in.op != S_READ || in.d_lo >= STREAM_BLOCK) continue;
+            const bool dyn_read = env.dyn && in.op == S_READ_DYN;   // (of a bank's ring: its offset may be below a block whatever its bound)
+            if (dyn_read && bank_ring_voice.find(in.buf) == bank_ring_voice.end()) continue;
+            if (!dyn_read && (in.op != S_READ || in.d_lo >= STREAM_BLOCK)) continue;
             auto bv = bank_ring_voice.find(in.buf);
             if (bv != bank_ring_voice.end()) {
                 if (one != NONE && one != bv->second) return true;
@@ -393,11 +405,19 @@ inline StreamPlan plan_stream(const StagedPlan &sp, const std::vector<const Bank
         return false;
     };
     uint64_t min_delay = UINT64_MAX;
+    uint32_t n_dyn_reads = 0, n_dyn_steps = 0;
     for (uint32_t k = 0; k < run.size(); ++k) {
         const StageProg &pg = sp.progs[run[k]];
         const bool copy = k >= first_copy;
         const bool bus = is_bus(k);
         uint32_t mine = NONE;
+        if (env.dyn && loops && stream_loop_stride(pg, sp.instrs.data() + pg.first_instr) != 0)   // the loop kernel's phases hoist frame-only loads
+            for (uint32_t i = 0; i < pg.n_instr; ++i) {
+                const uint8_t op = sp.instrs[pg.first_instr + i].op;
+                if (op == S_READ_DYN || op == S_STEP_DYN)
+                    return refuse(std::string("a loop program uses ") + stage_op_name(op) +
+                                  " (a Delay by a signal amount inside a feedback loop shorter than a block), which block streaming does not serve yet");
+            }
         for (uint32_t i = 0; i < pg.n_instr; ++i) {
             const StageInstr &in = sp.instrs[pg.first_instr + i];
             switch (in.op) {
@@ -460,7 +480,29 @@ inline StreamPlan plan_stream(const StagedPlan &sp, const std::vector<const Bank
                 min_delay = std::min<uint64_t>(min_delay, in.d_lo);
                 break;
             }
+            case S_READ_DYN: case S_STEP_DYN: {
+                if (!env.dyn)
+                    return refuse(std::string("a program uses ") + stage_op_name(in.op) + " (a Delay by a signal amount), which block streaming does not serve yet");
+                if (!sp.observed.empty())
+                    return refuse("a Delay's bound was observed from input rows (FR_DELAY_OBSERVED); a stream stores no rows, so block streaming does not serve it");
+                if (in.op == S_STEP_DYN) { ++n_dyn_steps; break; }  // touches no memory
+                auto bv = bank_ring_voice.find(in.buf);
+                if (bv == bank_ring_voice.end())
+                    return refuse("a program uses S_READ_DYN of a ring that a program stores (a Delay of a computed value by a signal amount, which may be 0 "
+                                  "frames); block streaming serves signal delays of voices only");
+                s.lookback = std::max<uint64_t>(s.lookback, in.d_lo);
+                ++n_dyn_reads;
+                if (bus) break;                                     // every voice of the block has finished
+                if (mine != NONE && mine != bv->second)
+                    return refuse("a program reads voices " + std::to_string(mine) + " and " + std::to_string(bv->second) +
+                                  " in the same block (a mix bus across voices); each streamed program follows one voice");
+                mine = bv->second;
+                break;
+            }
             default:
+                if (env.dyn)                                        // (S_READ_INPUT, S_READ_INPUT_DYN: a stream keeps no input history)
+                    return refuse(std::string("a program uses ") + stage_op_name(in.op) +
+                                  " (a delayed read of an input row), which block streaming does not serve yet: a stream keeps no input history");
                 return refuse(std::string("a program uses ") + stage_op_name(in.op) +
                               (in.op == S_READ_INPUT ? " (a delayed read of the input row)" : " (a Delay by a signal amount)") + ", which block streaming does not serve yet");
             }
@@ -505,6 +547,8 @@ inline StreamPlan plan_stream(const StagedPlan &sp, const std::vector<const Bank
         s.progs[at[voice_of[k]]++] = run[k];
     }
     s.min_ring_delay = min_delay == UINT64_MAX ? 0 : min_delay;
+    s.dyn_reads = n_dyn_reads;
+    s.dyn_steps = n_dyn_steps;
     s.input_slots.insert(s.input_slots.end(), others.begin(), others.end());
     s.servable = true;
     return s;
@@ -513,7 +557,7 @@ inline StreamPlan plan_stream(const StagedPlan &sp, const std::vector<const Bank
 // ---- the launch rule ----------------------------------------------------------------------------------------------------------
 inline const char *stream_kernel_name(StreamKernel k) {
     static const char *const names[] = {"", "bank_stream_kernel", "bank_stream_prog_kernel", "bank_stream_bus_kernel", "bank_stream_in_kernel",
-                                        "bank_stream_banks_kernel", "bank_stream_loops_kernel", "bank_stream_general_kernel"};
+                                        "bank_stream_banks_kernel", "bank_stream_loops_kernel", "bank_stream_general_kernel", "bank_stream_dyn_kernel"};
     return names[(uint32_t)k < sizeof names / sizeof names[0] ? (uint32_t)k : 0];
 }
 
@@ -539,14 +583,16 @@ inline bool stream_path(const StagedPlan &sp, const std::vector<const BankLaunch
     return env.programs && (!sp.progs.empty() || sp.uses_rings() || (env.banks && banks.size() > 1) || by_schedule);
 }
 
-// The launch of a servable plan of the program path.  The one cascade: general > loops > banks > in > bus > prog.
+// The launch of a servable plan of the program path.  The one cascade: dyn > general > loops > banks > in > bus > prog.  dyn -- a
+// plan with a Delay by a signal amount (StreamPlan::has_dyn) -- is the general kernel's composition and takes the schedule table
+// only when the plan has schedule banks.
 inline StreamLaunch stream_launch(const StagedPlan &sp, const StreamPlan &s) {
     StreamLaunch l;
-    l.kernel = s.has_general() ? StreamKernel::general : s.has_loops() ? StreamKernel::loops : s.banks.size() > 1 ? StreamKernel::banks
+    l.kernel = s.has_dyn() ? StreamKernel::dyn : s.has_general() ? StreamKernel::general : s.has_loops() ? StreamKernel::loops : s.banks.size() > 1 ? StreamKernel::banks
                : s.input_slots.size() > 1 ? StreamKernel::in : s.bus_programs() ? StreamKernel::bus : StreamKernel::prog;
     l.rows_doorbell = l.own_instrs = l.by_plan = stream_kernel_by_plan(l.kernel);
     l.bank_table = l.kernel >= StreamKernel::banks;
-    l.schedule_table = l.kernel == StreamKernel::general;
+    l.schedule_table = l.kernel == StreamKernel::general || (l.kernel == StreamKernel::dyn && s.has_general());
     l.n_rows = l.rows_doorbell ? (uint32_t)s.input_slots.size() : 1u;
     for (size_t i = 0; i < s.progs.size(); ++i) {    // (the tiles' fill is counted from the plan's instructions; the store slots are the stored rings)
         if (!s.loop_stride[i]) continue;
