@@ -787,9 +787,9 @@ static hipError_t launch_bank_short(const BankArgs &a, hipStream_t s) {
 }
 
 // ---------------------------------------------------------------------------------------------------
-// Block streaming: the short-call kernel as ONE resident launch (kernels.hpp, BankStreamCtl).  Six kernels -- bank_stream_kernel
-// below, the five that also run programs after stage_kernel -- are compositions of the pieces in this section; each step of the
-// protocol is written once, here.
+// Block streaming: the short-call kernel as ONE resident launch (kernels.hpp, BankStreamCtl).  Each step of the protocol is
+// written once, in this section; the skeleton that calls the steps -- stream_resident_body, of which the eight resident
+// kernels are instantiations -- follows stage_kernel, whose interpreter's types it uses.
 //
 // A block.  The host rings a doorbell in mapped pinned memory: every word carries a sample and the block's tag.  Wave 0 of
 // workgroup 0 polls it (stream_row_wait: one row; stream_in_wait: K rows), republishes the rows to device memory, has them
@@ -815,8 +815,8 @@ static hipError_t launch_bank_short(const BankArgs &a, hipStream_t s) {
 //
 // 1024 threads per workgroup: at most 128 VGPRs and no scratch -- the interpreter's registers are LDS columns.  The pieces are
 // __forceinline__; what they compile to inside each kernel is compared with the kernels' earlier, separately written text in
-// profiles/stream_shared_text.txt (registers, LDS, scratch, and the count of every barrier, sleep, clock read, vmcnt(0) and
-// atomic), which is where a change to a piece is checked.
+// profiles/stream_shared_text.txt and profiles/stream_resident_body.txt (registers, LDS, scratch, and the count of every
+// barrier, sleep, clock read, vmcnt(0) and atomic), which is where a change to a piece is checked.
 // ---------------------------------------------------------------------------------------------------
 constexpr int STREAM_NW = 16;   // waves of a streaming workgroup
 
@@ -1426,57 +1426,6 @@ __device__ __forceinline__ void stream_finish_bus(Ctl *ctl, Dev *dev, uint32_t n
             __hip_atomic_store(&ctl->done, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         }
     }
-}
-
-// What every streaming launch checks of a bank's shape, and of the programs' arguments.
-static bool stream_bank_ok(uint32_t log2_p, uint32_t chunk_log2, uint32_t n_voices, const float *ws, const uint32_t *tickets) {
-    if (chunk_log2 < 7 || chunk_log2 > 13 || chunk_log2 > log2_p || log2_p - chunk_log2 > 8) return false;
-    if (((uint64_t)n_voices << (log2_p - chunk_log2)) > BANK_STREAM_WGS || n_voices == 0) return false;   // all workgroups must be resident
-    return chunk_log2 == log2_p || (ws && tickets);
-}
-static bool stream_progs_ok(const StreamProgArgs &p, bool to_ring) {
-    if (!p.voice_first || (p.ring_mask & (p.ring_mask + 1)) != 0) return false;
-    return !(p.n_rings && (!p.rings || p.ring_mask + 1 < 64u)) && !(to_ring && !p.n_rings);
-}
-
-// bank_stream_kernel: banks alone.  One-row doorbell, render, hand-over; the finished voice goes to its row of the mapped host
-// result (system scope) and is counted in by lane 0.  No programs, no interpreter registers in LDS.
-__global__ void __launch_bounds__(1024) bank_stream_kernel(BankArgs a, BankStreamCtl *ctl, BankStreamDev *dev, uint32_t idle_ms) {
-    __shared__ float sm[STREAM_NW][64];
-    __shared__ unsigned long long zshared;
-    __shared__ uint32_t s_seq, s_T;
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const StreamWork w = stream_work(a.params, a.rows, a.log2_p, a.chunk_log2, a.fast_ok, 0u, 0u, blockIdx.x, wave);   // (the grid is exactly n_voices * nchunks workgroups)
-    const unsigned long long idle_ticks = (unsigned long long)idle_ms * 100000ull;
-    uint32_t seen = 0;
-    if (blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store(&ctl->alive, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    for (;;) {
-        uint32_t T;
-        const uint32_t seq = stream_next_block(dev, wave, lane, seen, idle_ticks, s_seq, s_T, T, [&](uint32_t &T0) { return stream_row_wait(ctl, dev, lane, seen, idle_ticks, T0); });
-        if (seq == BANK_STREAM_STOP) break;
-        seen = seq;
-        const bool live = lane < T;
-        float t, result;
-        const float r = stream_render_chunk(w, dev->row, live, wave, lane, sm, zshared, t);
-        if (wave == 0u && stream_hand_over(w, a.ws, a.tickets, a.n_voices, lane, r, result)) {
-            // the row goes to the host: system-scope stores, acknowledged before the voice is counted in
-            if (live) __hip_atomic_store(a.out + (size_t)w.rows[w.bank_voice] * 64u + lane, result, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            stream_finish(ctl, dev, a.n_voices, lane, seq);
-        }
-        __syncthreads();   // LDS is reused by the next block
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store(&ctl->alive, 0u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
-static hipError_t launch_bank_stream_plain(const BankArgs &a, BankStreamCtl *ctl_dev, BankStreamDev *dev, uint32_t idle_ms, hipStream_t s) {
-    if (!stream_bank_ok(a.log2_p, a.chunk_log2, a.n_voices, a.ws, a.tickets)) return hipErrorInvalidValue;
-    if ((1u << a.chunk_log2) / 16u < 8u) return hipErrorInvalidValue;          // a wave needs a whole group of 8 partials
-    if (a.leaf_variant != 1 || !a.out || !a.rows || !ctl_dev || !dev) return hipErrorInvalidValue;
-    // exactly the workgroups that render: a small patch leaves the other CUs to whatever else wants the device
-    const uint32_t wgs = a.n_voices << (a.log2_p - a.chunk_log2);
-    hipLaunchKernelGGL(bank_stream_kernel, dim3(wgs), dim3(1024), 0, s, a, ctl_dev, dev, idle_ms ? idle_ms : BANK_STREAM_IDLE_MS);
-    return hipGetLastError();
 }
 
 // Workgroups launch_bank uses for this shape.
@@ -2090,23 +2039,24 @@ hipError_t launch_stage(const StageArgs &a, hipStream_t s) {
 }
 
 // ---------------------------------------------------------------------------------------------------
-// Block streaming of plans with programs (kernels.hpp StreamProgArgs, streamplan.hpp): five more compositions of the pieces
-// above bank_stream_kernel, where the protocol is described.  All five keep the interpreter's registers in LDS, advance `head`
-// (the first frame of the block, the same in every workgroup) by each block's length, and in the wave that finishes a voice
-// store the voice and run its programs (stream_voice_programs).  They differ in the doorbell, in where S_INPUT comes from, in
-// whether the block's last arriver runs a bus segment, and in how a workgroup finds its work:
+// The eight resident kernels (kernels.hpp StreamKernel; the pieces and the protocol: above, "Block streaming"): ONE body,
+// stream_resident_body, instantiated by the kernel's form (kernels.hpp StreamForm).  The body is the protocol's skeleton -- when
+// `alive` is published, the block loop and its stop test, which wave counts a voice in, when LDS may be reused -- and every
+// kernel is the one before it and one thing more:
 //
-//   kernel                     doorbell        S_INPUT                 bus segment   work
-//   bank_stream_prog_kernel    one row         the block's row         no            BankArgs
-//   bank_stream_bus_kernel     one row         the block's row         yes           BankArgs
-//   bank_stream_in_kernel      n_rows rows     the row the host named  yes           BankArgs
-//   bank_stream_banks_kernel   n_rows rows     the row the host named  yes           its entry of the bank table
-//   bank_stream_loops_kernel   n_rows rows     the row the host named  yes           its entry of the bank table; loop programs
-//                                                                                    in three phases (stream_run_loop_program)
+//   kernel                       adds                                                              LDS bytes
+//   bank_stream_kernel           banks alone: one-row doorbell, the finished voice to its host row     4 112
+//   bank_stream_prog_kernel      the voices' programs (StreamProgArgs), `head`; registers in LDS      16 400
+//   bank_stream_bus_kernel       the bus segment in the block's last arriver                          16 400
+//   bank_stream_in_kernel        a doorbell of n_rows rows, S_INPUT by row                            16 400
+//   bank_stream_banks_kernel     a workgroup finds its bank in the bank table                         16 400
+//   bank_stream_loops_kernel     loop programs in three phases (stream_run_loop_program)              36 880
+//   bank_stream_general_kernel   schedule banks (stream_render_schedule)                              45 072
+//   bank_stream_dyn_kernel       Delays by a signal amount (stream_prog_dyn)                          45 072
 //
 // The bus segment is progs[voice_first[n_voices] .. voice_first[n_voices + 1]) and may be empty.  Which kernel a plan launches
 // is the host's rule (streamplan.hpp; fr_plan_json["stream"]["kernel"]).  The compiled kernels against their earlier,
-// separately written text: profiles/stream_shared_text.txt.
+// separately written text: profiles/stream_resident_body.txt.
 // ---------------------------------------------------------------------------------------------------
 
 // S_INPUT of the one-row kernels: the block's row, which the finishing wave holds as `t`.
@@ -2126,268 +2076,34 @@ struct StreamRowsInput {
     }
 };
 
-// The finishing wave: the voice's frames head + lane to its ring or row, then its programs, lane = frame.
-template <class Input>
-__device__ __forceinline__ void stream_voice_programs(const StreamWork &w, float *out, const StreamProgArgs &p, float (&regs)[STAGE_REGS][64], uint64_t frame, uint32_t lane,
-                                                      bool live, float result, const Input &input) {
-    stream_store_voice(w, out, p, frame, lane, live, result);
-    stream_run_programs(out, p, regs, p.voice_first[w.voice], p.voice_first[w.voice + 1], frame, lane, live, input);
+// What the doorbell's form decides, by overload on its device block: workgroup 0's wait, the block's time row, S_INPUT.
+__device__ __forceinline__ uint32_t stream_doorbell_wait(uint32_t, BankStreamCtl *ctl, BankStreamDev *dev, uint32_t lane, uint32_t seen, unsigned long long idle_ticks,
+                                                         uint32_t &T) {
+    return stream_row_wait(ctl, dev, lane, seen, idle_ticks, T);
 }
-
-// One-row doorbell; per-voice programs; lane 0 counts the voice in.
-__global__ void __launch_bounds__(1024) bank_stream_prog_kernel(BankArgs a, StreamProgArgs p, BankStreamCtl *ctl, BankStreamDev *dev, uint32_t idle_ms) {
-    __shared__ float sm[STREAM_NW][64];
-    __shared__ float regs[STAGE_REGS][64];                   // the interpreter's registers: [register][lane] of wave 0
-    __shared__ unsigned long long zshared;
-    __shared__ uint32_t s_seq, s_T;
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const StreamWork w = stream_work(a.params, a.rows, a.log2_p, a.chunk_log2, a.fast_ok, p.bank_to_ring, 0u, blockIdx.x, wave);   // (the grid is exactly n_voices * nchunks workgroups)
-    const unsigned long long idle_ticks = (unsigned long long)idle_ms * 100000ull;
-    uint64_t head = p.head;
-    uint32_t seen = 0;
-    if (blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store(&ctl->alive, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    for (;;) {
-        uint32_t T;
-        const uint32_t seq = stream_next_block(dev, wave, lane, seen, idle_ticks, s_seq, s_T, T, [&](uint32_t &T0) { return stream_row_wait(ctl, dev, lane, seen, idle_ticks, T0); });
-        if (seq == BANK_STREAM_STOP) break;
-        seen = seq;
-        const bool live = lane < T;
-        float t, result;
-        const float r = stream_render_chunk(w, dev->row, live, wave, lane, sm, zshared, t);
-        if (wave == 0u && stream_hand_over(w, a.ws, a.tickets, a.n_voices, lane, r, result)) {
-            stream_voice_programs(w, a.out, p, regs, head + lane, lane, live, result, StreamRowInput{t});
-            stream_finish(ctl, dev, a.n_voices, lane, seq);
-        }
-        head += T;
-        __syncthreads();   // LDS is reused by the next block
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store(&ctl->alive, 0u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+__device__ __forceinline__ uint32_t stream_doorbell_wait(uint32_t n_rows, BankStreamInCtl *ctl, BankStreamInDev *dev, uint32_t lane, uint32_t seen,
+                                                         unsigned long long idle_ticks, uint32_t &T) {
+    return stream_rows_wait(n_rows, ctl, dev, lane, seen, idle_ticks, T);
 }
+__device__ __forceinline__ const float *stream_time_row(const BankStreamDev *dev) { return dev->row; }
+__device__ __forceinline__ const float *stream_time_row(const BankStreamInDev *dev) { return dev->rows[0]; }
+__device__ __forceinline__ StreamRowInput stream_input(const BankStreamDev *, uint32_t, float t) { return {t}; }
+__device__ __forceinline__ StreamRowsInput stream_input(const BankStreamInDev *dev, uint32_t lane, float t) { return {dev, lane, t}; }
 
-// bank_stream_prog_kernel with the bus segment (FR_STREAM_BUS): the voices_done ticket goes to the whole wave.
-__global__ void __launch_bounds__(1024) bank_stream_bus_kernel(BankArgs a, StreamProgArgs p, BankStreamCtl *ctl, BankStreamDev *dev, uint32_t idle_ms) {
-    __shared__ float sm[STREAM_NW][64];
-    __shared__ float regs[STAGE_REGS][64];                   // the interpreter's registers: [register][lane] of wave 0
-    __shared__ unsigned long long zshared;
-    __shared__ uint32_t s_seq, s_T;
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const StreamWork w = stream_work(a.params, a.rows, a.log2_p, a.chunk_log2, a.fast_ok, p.bank_to_ring, 0u, blockIdx.x, wave);   // (the grid is exactly n_voices * nchunks workgroups)
-    const unsigned long long idle_ticks = (unsigned long long)idle_ms * 100000ull;
-    uint64_t head = p.head;
-    uint32_t seen = 0;
-    if (blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store(&ctl->alive, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    for (;;) {
-        uint32_t T;
-        const uint32_t seq = stream_next_block(dev, wave, lane, seen, idle_ticks, s_seq, s_T, T, [&](uint32_t &T0) { return stream_row_wait(ctl, dev, lane, seen, idle_ticks, T0); });
-        if (seq == BANK_STREAM_STOP) break;
-        seen = seq;
-        const bool live = lane < T;
-        float t, result;
-        const float r = stream_render_chunk(w, dev->row, live, wave, lane, sm, zshared, t);
-        if (wave == 0u && stream_hand_over(w, a.ws, a.tickets, a.n_voices, lane, r, result)) {
-            const uint64_t frame = head + lane;
-            const StreamRowInput input{t};
-            stream_voice_programs(w, a.out, p, regs, frame, lane, live, result, input);
-            stream_finish_bus(ctl, dev, a.n_voices, lane, seq,
-                              [&] { stream_run_programs(a.out, p, regs, p.voice_first[a.n_voices], p.voice_first[a.n_voices + 1], frame, lane, live, input); });
-        }
-        head += T;
-        __syncthreads();   // LDS is reused by the next block
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store(&ctl->alive, 0u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
-// (bank_stream_prog_kernel and bank_stream_bus_kernel: the same arguments, the same checks)
-static hipError_t launch_bank_stream_prog(bool bus, const BankArgs &a, const StreamProgArgs &p, BankStreamCtl *ctl_dev, BankStreamDev *dev, uint32_t idle_ms, hipStream_t s) {
-    if (!stream_bank_ok(a.log2_p, a.chunk_log2, a.n_voices, a.ws, a.tickets) || !stream_progs_ok(p, p.bank_to_ring != 0)) return hipErrorInvalidValue;
-    if (a.leaf_variant != 1 || !a.out || !a.rows || !ctl_dev || !dev) return hipErrorInvalidValue;
-    const uint32_t wgs = a.n_voices << (a.log2_p - a.chunk_log2);
-    hipLaunchKernelGGL(bus ? bank_stream_bus_kernel : bank_stream_prog_kernel, dim3(wgs), dim3(1024), 0, s, a, p, ctl_dev, dev, idle_ms ? idle_ms : BANK_STREAM_IDLE_MS);
-    return hipGetLastError();
-}
-
-// bank_stream_bus_kernel with control rows (FR_STREAM_INPUTS, kernels.hpp BankStreamInCtl): a doorbell of n_rows rows, S_INPUT by row.
-__global__ void __launch_bounds__(1024) bank_stream_in_kernel(BankArgs a, StreamProgArgs p, uint32_t n_rows, BankStreamInCtl *ctl, BankStreamInDev *dev, uint32_t idle_ms) {
-    __shared__ float sm[STREAM_NW][64];
-    __shared__ float regs[STAGE_REGS][64];                   // the interpreter's registers: [register][lane] of wave 0
-    __shared__ unsigned long long zshared;
-    __shared__ uint32_t s_seq, s_T;
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const StreamWork w = stream_work(a.params, a.rows, a.log2_p, a.chunk_log2, a.fast_ok, p.bank_to_ring, 0u, blockIdx.x, wave);   // (the grid is exactly n_voices * nchunks workgroups)
-    const unsigned long long idle_ticks = (unsigned long long)idle_ms * 100000ull;
-    uint64_t head = p.head;
-    uint32_t seen = 0;
-    if (blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store(&ctl->alive, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    for (;;) {
-        uint32_t T;
-        const uint32_t seq = stream_next_block(dev, wave, lane, seen, idle_ticks, s_seq, s_T, T, [&](uint32_t &T0) { return stream_rows_wait(n_rows, ctl, dev, lane, seen, idle_ticks, T0); });
-        if (seq == BANK_STREAM_STOP) break;
-        seen = seq;
-        const bool live = lane < T;
-        float t, result;
-        const float r = stream_render_chunk(w, dev->rows[0], live, wave, lane, sm, zshared, t);
-        if (wave == 0u && stream_hand_over(w, a.ws, a.tickets, a.n_voices, lane, r, result)) {
-            const uint64_t frame = head + lane;
-            const StreamRowsInput input{dev, lane, t};
-            stream_voice_programs(w, a.out, p, regs, frame, lane, live, result, input);
-            stream_finish_bus(ctl, dev, a.n_voices, lane, seq,
-                              [&] { stream_run_programs(a.out, p, regs, p.voice_first[a.n_voices], p.voice_first[a.n_voices + 1], frame, lane, live, input); });
-        }
-        head += T;
-        __syncthreads();   // LDS is reused by the next block
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store(&ctl->alive, 0u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
-static hipError_t launch_bank_stream_in(const BankArgs &a, const StreamProgArgs &p, uint32_t n_rows, BankStreamInCtl *ctl_dev, BankStreamInDev *dev, uint32_t idle_ms,
-                                 hipStream_t s) {
-    if (!stream_bank_ok(a.log2_p, a.chunk_log2, a.n_voices, a.ws, a.tickets) || !stream_progs_ok(p, p.bank_to_ring != 0)) return hipErrorInvalidValue;
-    if (a.leaf_variant != 1 || !a.out || !a.rows || !ctl_dev || !dev) return hipErrorInvalidValue;
-    if (n_rows == 0 || n_rows > BANK_STREAM_ROWS) return hipErrorInvalidValue;
-    const uint32_t wgs = a.n_voices << (a.log2_p - a.chunk_log2);
-    hipLaunchKernelGGL(bank_stream_in_kernel, dim3(wgs), dim3(1024), 0, s, a, p, n_rows, ctl_dev, dev, idle_ms ? idle_ms : BANK_STREAM_IDLE_MS);
-    return hipGetLastError();
-}
-
-// bank_stream_in_kernel for voices of 2..8 banks (FR_STREAM_BANKS, kernels.hpp StreamBanksArgs), each with its own partial
-// count, chunk size, fast path and destination kind.  What differs is how a workgroup finds its work: the bank table is a
-// launch argument, the workgroup compares its index with the banks' first workgroups (uniform, once, before the block loop)
-// and keeps that bank's fields in scalar registers.  Voices are numbered globally: chunk sums, tickets, voice_first and the
-// voices_done count -- whichever bank the block's last arriver is of -- all go by that number.
-__global__ void __launch_bounds__(1024) bank_stream_banks_kernel(StreamBanksArgs t, BankArgs a, StreamProgArgs p, uint32_t n_rows, BankStreamInCtl *ctl,
-                                                                 BankStreamInDev *dev, uint32_t idle_ms) {
-    __shared__ float sm[STREAM_NW][64];
-    __shared__ float regs[STAGE_REGS][64];                   // the interpreter's registers: [register][lane] of wave 0
-    __shared__ unsigned long long zshared;
-    __shared__ uint32_t s_seq, s_T;
-    // ---- this workgroup's bank: the last one whose first workgroup is not after it (the table is in ascending order) ----
-    StreamBanksArgs::Bank bk = t.bank[0];
-    static_for<1, (int)BANK_STREAM_BANKS>([&](auto j) {
-        if ((uint32_t)j < t.n_banks && blockIdx.x >= t.bank[j].first_wg) bk = t.bank[j];
-    });
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    // (the grid is exactly the sum of the banks' n_voices * nchunks workgroups)
-    const StreamWork w = stream_work(bk.params, bk.rows, bk.log2_p, bk.chunk_log2, bk.fast_ok, bk.to_ring, bk.first_voice, blockIdx.x - bk.first_wg, wave);
-    const uint32_t n_voices = a.n_voices;                    // of all banks
-    const unsigned long long idle_ticks = (unsigned long long)idle_ms * 100000ull;
-    uint64_t head = p.head;
-    uint32_t seen = 0;
-    if (blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store(&ctl->alive, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    for (;;) {
-        uint32_t T;
-        const uint32_t seq = stream_next_block(dev, wave, lane, seen, idle_ticks, s_seq, s_T, T, [&](uint32_t &T0) { return stream_rows_wait(n_rows, ctl, dev, lane, seen, idle_ticks, T0); });
-        if (seq == BANK_STREAM_STOP) break;
-        seen = seq;
-        const bool live = lane < T;
-        float t_in, result;
-        const float r = stream_render_chunk(w, dev->rows[0], live, wave, lane, sm, zshared, t_in);
-        if (wave == 0u && stream_hand_over(w, a.ws, a.tickets, n_voices, lane, r, result)) {
-            const uint64_t frame = head + lane;
-            const StreamRowsInput input{dev, lane, t_in};
-            stream_voice_programs(w, a.out, p, regs, frame, lane, live, result, input);
-            stream_finish_bus(ctl, dev, n_voices, lane, seq,
-                              [&] { stream_run_programs(a.out, p, regs, p.voice_first[n_voices], p.voice_first[n_voices + 1], frame, lane, live, input); });
-        }
-        head += T;
-        __syncthreads();   // LDS is reused by the next block
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store(&ctl->alive, 0u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
-// What the launches with a bank table check: every bank as the one-bank launchers check theirs; the banks' workgroups and
-// voices follow one another without a gap.  `wgs`: the launch's workgroups.  `schedule_mask`: the banks that are schedule banks
-// (StreamGeneralArgs::mask): one workgroup per voice, whatever their log2_p and chunk_log2 say.
-static bool stream_table_ok(const StreamBanksArgs &t, const BankArgs &a, const StreamProgArgs &p, uint32_t n_rows, uint64_t &wgs, uint32_t schedule_mask = 0) {
-    if (t.n_banks == 0 || t.n_banks > BANK_STREAM_BANKS) return false;
-    uint64_t voices = 0;
-    bool to_ring = false;
-    wgs = 0;
-    for (uint32_t i = 0; i < t.n_banks; ++i) {
-        const StreamBanksArgs::Bank &b = t.bank[i];
-        const bool schedule = (schedule_mask >> i) & 1u;
-        if (schedule ? b.n_voices == 0 : !stream_bank_ok(b.log2_p, b.chunk_log2, b.n_voices, a.ws, a.tickets)) return false;
-        if (!b.params || !b.rows || b.first_wg != wgs || b.first_voice != voices) return false;
-        wgs += schedule ? (uint64_t)b.n_voices : (uint64_t)b.n_voices << (b.log2_p - b.chunk_log2);
-        voices += b.n_voices;
-        if (wgs > BANK_STREAM_WGS) return false;   // all workgroups must be resident
-        to_ring = to_ring || b.to_ring != 0;
-    }
-    if (voices != a.n_voices || !stream_progs_ok(p, to_ring)) return false;
-    if (a.leaf_variant != 1 || !a.out) return false;
-    return n_rows != 0 && n_rows <= BANK_STREAM_ROWS;
-}
-
-// bank_stream_banks_kernel for plans with loop programs (FR_STREAM_LOOPS, kernels.hpp): the bank table also for one bank, the
-// same doorbell, hand-overs and bus segment; the programs go through stream_run_programs_loops with a load and a store tile.
-__global__ void __launch_bounds__(1024) bank_stream_loops_kernel(StreamBanksArgs t, BankArgs a, StreamProgArgs p, uint32_t n_rows, BankStreamInCtl *ctl,
-                                                                 BankStreamInDev *dev, uint32_t idle_ms) {
-    __shared__ float sm[STREAM_NW][64];
-    __shared__ float regs[STAGE_REGS][64];                   // the interpreter's registers: [register][frame] of wave 0
-    __shared__ float ldt[BANK_STREAM_LOOP_LOADS][64];        // a loop program's loads, [load slot][frame]
-    __shared__ float stt[BANK_STREAM_LOOP_STORES][64];       // ... and what it stores to its rings, [store slot][frame]
-    __shared__ uint4 lins[BANK_STREAM_LOOP_INSTRS];          // ... and its (first) instructions
-    __shared__ unsigned long long zshared;
-    __shared__ uint32_t s_seq, s_T;
-    StreamBanksArgs::Bank bk = t.bank[0];
-    static_for<1, (int)BANK_STREAM_BANKS>([&](auto j) {
-        if ((uint32_t)j < t.n_banks && blockIdx.x >= t.bank[j].first_wg) bk = t.bank[j];
-    });
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const StreamWork w = stream_work(bk.params, bk.rows, bk.log2_p, bk.chunk_log2, bk.fast_ok, bk.to_ring, bk.first_voice, blockIdx.x - bk.first_wg, wave);
-    const uint32_t n_voices = a.n_voices;                    // of all banks
-    const unsigned long long idle_ticks = (unsigned long long)idle_ms * 100000ull;
-    uint64_t head = p.head;
-    uint32_t seen = 0;
-    if (blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store(&ctl->alive, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    for (;;) {
-        uint32_t T;
-        const uint32_t seq = stream_next_block(dev, wave, lane, seen, idle_ticks, s_seq, s_T, T, [&](uint32_t &T0) { return stream_rows_wait(n_rows, ctl, dev, lane, seen, idle_ticks, T0); });
-        if (seq == BANK_STREAM_STOP) break;
-        seen = seq;
-        const bool live = lane < T;
-        float t_in, result;
-        const float r = stream_render_chunk(w, dev->rows[0], live, wave, lane, sm, zshared, t_in);
-        if (wave == 0u && stream_hand_over(w, a.ws, a.tickets, n_voices, lane, r, result)) {
-            const StreamRowsInput input{dev, lane, t_in};
-            stream_store_voice(w, a.out, p, head + lane, lane, live, result);
-            stream_run_programs_loops(a.out, p, regs, ldt, stt, lins, p.voice_first[w.voice], p.voice_first[w.voice + 1], head, T, lane, live, input);
-            stream_finish_bus(ctl, dev, n_voices, lane, seq, [&] {
-                stream_run_programs_loops(a.out, p, regs, ldt, stt, lins, p.voice_first[n_voices], p.voice_first[n_voices + 1], head, T, lane, live, input);
-            });
-        }
-        head += T;
-        __syncthreads();   // LDS is reused by the next block
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store(&ctl->alive, 0u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
-// (bank_stream_banks_kernel and bank_stream_loops_kernel: the same arguments; the limits concern loop programs only)
-static hipError_t launch_bank_stream_banks(bool loops, const StreamBanksArgs &t, const BankArgs &a, const StreamProgArgs &p, uint32_t n_rows, uint32_t max_stride,
-                                           uint32_t max_loads, uint32_t max_stores, BankStreamInCtl *ctl_dev, BankStreamInDev *dev, uint32_t idle_ms, hipStream_t s) {
-    if (loops && (max_stride > BANK_STREAM_LOOP_MAX_STRIDE || max_loads > BANK_STREAM_LOOP_LOADS || max_stores > BANK_STREAM_LOOP_STORES)) return hipErrorInvalidValue;
-    uint64_t wgs = 0;
-    if (!stream_table_ok(t, a, p, n_rows, wgs) || (loops && !p.n_rings) || !ctl_dev || !dev) return hipErrorInvalidValue;   // (a loop lives in a ring)
-    hipLaunchKernelGGL(loops ? bank_stream_loops_kernel : bank_stream_banks_kernel, dim3((uint32_t)wgs), dim3(1024), 0, s, t, a, p, n_rows, ctl_dev, dev,
-                       idle_ms ? idle_ms : BANK_STREAM_IDLE_MS);
-    return hipGetLastError();
-}
-
-// bank_stream_loops_kernel for plans with schedule banks (FR_STREAM_GENERAL, kernels.hpp StreamGeneralArgs): the same bank table,
-// doorbell, hand-over, programs and bus segment.  What differs is what a workgroup of a schedule bank renders: it learns before
-// the block loop, uniformly, that its bank is one; its voice is first_voice + (blockIdx.x - first_wg), its chunk count 1 (so
-// stream_hand_over returns at once), and stream_render_schedule runs the voice's items and merges.
-// The body is shared with bank_stream_dyn_kernel (FR_STREAM_DYN, kernels.hpp): DYN = the interpreter also knows the Delays by a
-// signal amount (stream_prog_dyn); a plan of that kernel need not have a schedule bank (g.mask == 0).
+// The resident kernel of form K.  The argument structs come BY VALUE (by reference the bank table goes to scratch); what a form
+// does not have is passed empty and never read, and a __shared__ array it does not use takes no LDS.
+//
+// A workgroup's bank is the last one of the table whose first workgroup is not after it (the table is in ascending order; the
+// grid is exactly the sum of the banks' workgroups), found once, uniformly, before the block loop; without a table it is the
+// one bank of BankArgs.  Voices are numbered globally: chunk sums, tickets, voice_first and the voices_done count -- whichever
+// bank the block's last arriver is of -- all go by that number.  A workgroup of a schedule bank renders the voice first_voice +
+// (blockIdx.x - first_wg) whole: its chunk count is 1, so stream_hand_over returns at once.
 static_assert(STREAM_STACK_DEPTH == GB_MAX_DEPTH, "a schedule voice's stack is the general voices'");
-template <bool DYN>
-__device__ __forceinline__ void bank_stream_general_body(StreamBanksArgs t, StreamGeneralArgs g, BankArgs a, StreamProgArgs p, uint32_t n_rows, BankStreamInCtl *ctl,
-                                                         BankStreamInDev *dev, uint32_t idle_ms) {
-    __shared__ float sm[2][STREAM_NW][64];                   // the waves' sums: a chunk's in [0], a schedule's items alternate
+template <StreamKernel K, class Ctl, class Dev>
+__device__ __forceinline__ void stream_resident_body(StreamBanksArgs t, StreamGeneralArgs g, BankArgs a, StreamProgArgs p, uint32_t n_rows, Ctl *ctl, Dev *dev,
+                                                     uint32_t idle_ms) {
+    constexpr StreamForm F = stream_form(K);
+    __shared__ float sm[F.schedule ? 2 : 1][STREAM_NW][64];  // the waves' sums: a chunk's in [0], a schedule's items alternate
     __shared__ float stack_mem[STREAM_STACK_DEPTH][64];      // a schedule voice's evaluation stack: [level][frame] of wave 0
     __shared__ float regs[STAGE_REGS][64];                   // the interpreter's registers: [register][frame] of wave 0
     __shared__ float ldt[BANK_STREAM_LOOP_LOADS][64];        // a loop program's loads, [load slot][frame]
@@ -2395,18 +2111,23 @@ __device__ __forceinline__ void bank_stream_general_body(StreamBanksArgs t, Stre
     __shared__ uint4 lins[BANK_STREAM_LOOP_INSTRS];          // ... and its (first) instructions
     __shared__ unsigned long long zshared;
     __shared__ uint32_t s_seq, s_T;
-    StreamBanksArgs::Bank bk = t.bank[0];
-    const uint32_t *groups = g.bank[0].groups, *group_off = g.bank[0].group_off;
+    StreamBanksArgs::Bank bk = {a.params, a.rows, 0u, 0u, a.n_voices, a.log2_p, a.chunk_log2, a.fast_ok, p.bank_to_ring};
+    const uint32_t *groups = nullptr, *group_off = nullptr;
     uint32_t bi = 0;
-    static_for<1, (int)BANK_STREAM_BANKS>([&](auto j) {
-        if ((uint32_t)j < t.n_banks && blockIdx.x >= t.bank[j].first_wg) {
-            bk = t.bank[j];
-            groups = g.bank[j].groups;
-            group_off = g.bank[j].group_off;
-            bi = (uint32_t)j;
-        }
-    });
-    const bool schedule = (g.mask >> bi) & 1u;               // uniform: the workgroup's bank is a schedule bank
+    if constexpr (F.table) {
+        bk = t.bank[0];
+        groups = g.bank[0].groups;
+        group_off = g.bank[0].group_off;
+        static_for<1, (int)BANK_STREAM_BANKS>([&](auto j) {
+            if ((uint32_t)j < t.n_banks && blockIdx.x >= t.bank[j].first_wg) {
+                bk = t.bank[j];
+                groups = g.bank[j].groups;
+                group_off = g.bank[j].group_off;
+                bi = (uint32_t)j;
+            }
+        });
+    }
+    const bool schedule = F.schedule && ((g.mask >> bi) & 1u);   // uniform: the workgroup's bank is a schedule bank
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t local = blockIdx.x - bk.first_wg;
@@ -2425,25 +2146,32 @@ __device__ __forceinline__ void bank_stream_general_body(StreamBanksArgs t, Stre
     }
     const uint32_t n_voices = a.n_voices;                    // of all banks
     const unsigned long long idle_ticks = (unsigned long long)idle_ms * 100000ull;
-    uint64_t head = p.head;
+    uint64_t head = p.head;                                  // the first frame of the block, the same in every workgroup
     uint32_t seen = 0;
     if (blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store(&ctl->alive, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     for (;;) {
         uint32_t T;
-        const uint32_t seq = stream_next_block(dev, wave, lane, seen, idle_ticks, s_seq, s_T, T, [&](uint32_t &T0) { return stream_rows_wait(n_rows, ctl, dev, lane, seen, idle_ticks, T0); });
+        const uint32_t seq = stream_next_block(dev, wave, lane, seen, idle_ticks, s_seq, s_T, T, [&](uint32_t &T0) { return stream_doorbell_wait(n_rows, ctl, dev, lane, seen, idle_ticks, T0); });
         if (seq == BANK_STREAM_STOP) break;
         seen = seq;
         const bool live = lane < T;
-        float t_in, result;
-        const float r = schedule ? stream_render_schedule(vparams, items, nitems, bk.fast_ok, dev->rows[0], live, wave, lane, sm, stack_mem, zshared, t_in)
-                                 : stream_render_chunk(w, dev->rows[0], live, wave, lane, sm[0], zshared, t_in);
+        float t_in, result, r;
+        // (the conditional expression the general kernel has always had: as an if / else its compiled loop comes out another)
+        if constexpr (F.schedule)
+            r = schedule ? stream_render_schedule(vparams, items, nitems, bk.fast_ok, stream_time_row(dev), live, wave, lane, sm, stack_mem, zshared, t_in)
+                         : stream_render_chunk(w, stream_time_row(dev), live, wave, lane, sm[0], zshared, t_in);
+        else r = stream_render_chunk(w, stream_time_row(dev), live, wave, lane, sm[0], zshared, t_in);
         if (wave == 0u && stream_hand_over(w, a.ws, a.tickets, n_voices, lane, r, result)) {
-            const StreamRowsInput input{dev, lane, t_in};
+            // the finishing wave: the voice's frames head + lane to its ring or row, then its programs, then it counts the voice in
+            const auto input = stream_input(dev, lane, t_in);
+            auto run = [&](uint32_t p_first, uint32_t p_end) {
+                if constexpr (F.loops) stream_run_programs_loops<F.dyn>(a.out, p, regs, ldt, stt, lins, p_first, p_end, head, T, lane, live, input);
+                else if constexpr (F.progs) stream_run_programs(a.out, p, regs, p_first, p_end, head + lane, lane, live, input);
+            };
             stream_store_voice(w, a.out, p, head + lane, lane, live, result);
-            stream_run_programs_loops<DYN>(a.out, p, regs, ldt, stt, lins, p.voice_first[w.voice], p.voice_first[w.voice + 1], head, T, lane, live, input);
-            stream_finish_bus(ctl, dev, n_voices, lane, seq, [&] {
-                stream_run_programs_loops<DYN>(a.out, p, regs, ldt, stt, lins, p.voice_first[n_voices], p.voice_first[n_voices + 1], head, T, lane, live, input);
-            });
+            if constexpr (F.progs) run(p.voice_first[w.voice], p.voice_first[w.voice + 1]);
+            if constexpr (F.bus) stream_finish_bus(ctl, dev, n_voices, lane, seq, [&] { run(p.voice_first[n_voices], p.voice_first[n_voices + 1]); });
+            else stream_finish(ctl, dev, n_voices, lane, seq);
         }
         head += T;
         __syncthreads();   // LDS is reused by the next block
@@ -2451,46 +2179,57 @@ __device__ __forceinline__ void bank_stream_general_body(StreamBanksArgs t, Stre
     if (blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store(&ctl->alive, 0u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
+__global__ void __launch_bounds__(1024) bank_stream_kernel(BankArgs a, BankStreamCtl *ctl, BankStreamDev *dev, uint32_t idle_ms) {
+    stream_resident_body<StreamKernel::plain>({}, {}, a, {}, 1u, ctl, dev, idle_ms);
+}
+__global__ void __launch_bounds__(1024) bank_stream_prog_kernel(BankArgs a, StreamProgArgs p, BankStreamCtl *ctl, BankStreamDev *dev, uint32_t idle_ms) {
+    stream_resident_body<StreamKernel::prog>({}, {}, a, p, 1u, ctl, dev, idle_ms);
+}
+__global__ void __launch_bounds__(1024) bank_stream_bus_kernel(BankArgs a, StreamProgArgs p, BankStreamCtl *ctl, BankStreamDev *dev, uint32_t idle_ms) {
+    stream_resident_body<StreamKernel::bus>({}, {}, a, p, 1u, ctl, dev, idle_ms);
+}
+__global__ void __launch_bounds__(1024) bank_stream_in_kernel(BankArgs a, StreamProgArgs p, uint32_t n_rows, BankStreamInCtl *ctl, BankStreamInDev *dev, uint32_t idle_ms) {
+    stream_resident_body<StreamKernel::in>({}, {}, a, p, n_rows, ctl, dev, idle_ms);
+}
+__global__ void __launch_bounds__(1024) bank_stream_banks_kernel(StreamBanksArgs t, BankArgs a, StreamProgArgs p, uint32_t n_rows, BankStreamInCtl *ctl,
+                                                                 BankStreamInDev *dev, uint32_t idle_ms) {
+    stream_resident_body<StreamKernel::banks>(t, {}, a, p, n_rows, ctl, dev, idle_ms);
+}
+__global__ void __launch_bounds__(1024) bank_stream_loops_kernel(StreamBanksArgs t, BankArgs a, StreamProgArgs p, uint32_t n_rows, BankStreamInCtl *ctl,
+                                                                 BankStreamInDev *dev, uint32_t idle_ms) {
+    stream_resident_body<StreamKernel::loops>(t, {}, a, p, n_rows, ctl, dev, idle_ms);
+}
 __global__ void __launch_bounds__(1024) bank_stream_general_kernel(StreamBanksArgs t, StreamGeneralArgs g, BankArgs a, StreamProgArgs p, uint32_t n_rows, BankStreamInCtl *ctl,
                                                                    BankStreamInDev *dev, uint32_t idle_ms) {
-    bank_stream_general_body<false>(t, g, a, p, n_rows, ctl, dev, idle_ms);
+    stream_resident_body<StreamKernel::general>(t, g, a, p, n_rows, ctl, dev, idle_ms);
 }
 __global__ void __launch_bounds__(1024) bank_stream_dyn_kernel(StreamBanksArgs t, StreamGeneralArgs g, BankArgs a, StreamProgArgs p, uint32_t n_rows, BankStreamInCtl *ctl,
                                                                BankStreamInDev *dev, uint32_t idle_ms) {
-    bank_stream_general_body<true>(t, g, a, p, n_rows, ctl, dev, idle_ms);
+    stream_resident_body<StreamKernel::dyn>(t, g, a, p, n_rows, ctl, dev, idle_ms);
 }
 
-// (bank_stream_general_kernel and bank_stream_dyn_kernel: the same arguments; only the latter takes a plan without a schedule bank)
-static hipError_t launch_bank_stream_general(bool dyn, const StreamBanksArgs &t, const StreamGeneralArgs &g, const BankArgs &a, const StreamProgArgs &p, uint32_t n_rows,
-                                             uint32_t max_stride, uint32_t max_loads, uint32_t max_stores, BankStreamInCtl *ctl_dev, BankStreamInDev *dev, uint32_t idle_ms,
-                                             hipStream_t s) {
-    if (max_stride > BANK_STREAM_LOOP_MAX_STRIDE || max_loads > BANK_STREAM_LOOP_LOADS || max_stores > BANK_STREAM_LOOP_STORES) return hipErrorInvalidValue;
-    if ((g.mask == 0 && !dyn) || t.n_banks == 0 || t.n_banks > BANK_STREAM_BANKS || (g.mask >> t.n_banks) != 0) return hipErrorInvalidValue;
-    for (uint32_t i = 0; i < t.n_banks; ++i)
-        if (((g.mask >> i) & 1u) && (!g.bank[i].groups || !g.bank[i].group_off)) return hipErrorInvalidValue;
-    uint64_t wgs = 0;                                         // (a schedule bank: one workgroup per voice; the total within BANK_STREAM_WGS)
-    if (!stream_table_ok(t, a, p, n_rows, wgs, g.mask) || (max_stride && !p.n_rings) || !ctl_dev || !dev) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(dyn ? bank_stream_dyn_kernel : bank_stream_general_kernel, dim3((uint32_t)wgs), dim3(1024), 0, s, t, g, a, p, n_rows, ctl_dev, dev,
-                       idle_ms ? idle_ms : BANK_STREAM_IDLE_MS);
-    return hipGetLastError();
-}
-
-// The one entry of the resident launches (kernels.hpp StreamLaunchArgs): each launcher above takes what its kernel takes.
+// The one entry of the resident launches (kernels.hpp StreamLaunchArgs): the check, then the kernel with what it takes.
 hipError_t launch_bank_stream(StreamKernel k, const StreamLaunchArgs &x, hipStream_t s) {
-    BankStreamCtl *const ctl = static_cast<BankStreamCtl *>(x.ctl_dev);          // (the form is the kernel's: kernels.hpp StreamKernel)
+    const uint32_t wgs = stream_launch_check(k, x);
+    if (!wgs) return hipErrorInvalidValue;
+    BankStreamCtl *const ctl = static_cast<BankStreamCtl *>(x.ctl_dev);          // (the doorbell's form is the kernel's: StreamForm::rows)
     BankStreamDev *const dev = static_cast<BankStreamDev *>(x.dev);
     BankStreamInCtl *const ctl_in = static_cast<BankStreamInCtl *>(x.ctl_dev);
     BankStreamInDev *const dev_in = static_cast<BankStreamInDev *>(x.dev);
+    const dim3 grid(wgs), block(1024);
+    const uint32_t idle_ms = x.idle_ms ? x.idle_ms : BANK_STREAM_IDLE_MS;
     switch (k) {
-    case StreamKernel::plain: return launch_bank_stream_plain(x.a, ctl, dev, x.idle_ms, s);
-    case StreamKernel::prog: case StreamKernel::bus: return launch_bank_stream_prog(k == StreamKernel::bus, x.a, x.p, ctl, dev, x.idle_ms, s);
-    case StreamKernel::in: return launch_bank_stream_in(x.a, x.p, x.n_rows, ctl_in, dev_in, x.idle_ms, s);
-    case StreamKernel::banks: case StreamKernel::loops:
-        return launch_bank_stream_banks(k == StreamKernel::loops, x.t, x.a, x.p, x.n_rows, x.max_stride, x.max_loads, x.max_stores, ctl_in, dev_in, x.idle_ms, s);
-    case StreamKernel::general: case StreamKernel::dyn:
-        return launch_bank_stream_general(k == StreamKernel::dyn, x.t, x.g, x.a, x.p, x.n_rows, x.max_stride, x.max_loads, x.max_stores, ctl_in, dev_in, x.idle_ms, s);
+    case StreamKernel::plain: hipLaunchKernelGGL(bank_stream_kernel, grid, block, 0, s, x.a, ctl, dev, idle_ms); break;
+    case StreamKernel::prog: hipLaunchKernelGGL(bank_stream_prog_kernel, grid, block, 0, s, x.a, x.p, ctl, dev, idle_ms); break;
+    case StreamKernel::bus: hipLaunchKernelGGL(bank_stream_bus_kernel, grid, block, 0, s, x.a, x.p, ctl, dev, idle_ms); break;
+    case StreamKernel::in: hipLaunchKernelGGL(bank_stream_in_kernel, grid, block, 0, s, x.a, x.p, x.n_rows, ctl_in, dev_in, idle_ms); break;
+    case StreamKernel::banks: hipLaunchKernelGGL(bank_stream_banks_kernel, grid, block, 0, s, x.t, x.a, x.p, x.n_rows, ctl_in, dev_in, idle_ms); break;
+    case StreamKernel::loops: hipLaunchKernelGGL(bank_stream_loops_kernel, grid, block, 0, s, x.t, x.a, x.p, x.n_rows, ctl_in, dev_in, idle_ms); break;
+    case StreamKernel::general: hipLaunchKernelGGL(bank_stream_general_kernel, grid, block, 0, s, x.t, x.g, x.a, x.p, x.n_rows, ctl_in, dev_in, idle_ms); break;
+    case StreamKernel::dyn: hipLaunchKernelGGL(bank_stream_dyn_kernel, grid, block, 0, s, x.t, x.g, x.a, x.p, x.n_rows, ctl_in, dev_in, idle_ms); break;
     default: return hipErrorInvalidValue;
     }
+    return hipGetLastError();
 }
 
 // ---------------------------------------------------------------------------------------------------

@@ -301,7 +301,7 @@ struct StreamGeneralArgs {
     } bank[BANK_STREAM_BANKS];
 };
 
-// bank_stream_dyn_kernel (FR_STREAM_DYN): bank_stream_general_kernel's composition -- the same body, one template on a bool -- for
+// bank_stream_dyn_kernel (FR_STREAM_DYN): bank_stream_general_kernel's composition -- the same body, one more flag of its form -- for
 // plans whose streamed programs delay a voice by a SIGNAL amount: its interpreter also knows S_READ_DYN and S_STEP_DYN, lane =
 // frame.  frames = delay_frames(regs[a][lane]) is the reference's cast (shared with pull_kernel and stage_kernel); S_READ_DYN
 // yields ring[buf][(frame - frames) & ring_mask] when the cast succeeds and frame >= frames, else 0.0; S_STEP_DYN yields
@@ -314,7 +314,23 @@ struct StreamGeneralArgs {
 // The eight resident kernels (streamplan.hpp stream_launch chooses; `none`: no resident launch yet) and their one launch entry.
 // plain, prog and bus have the one-row doorbell (BankStreamCtl / BankStreamDev), the others the doorbell of rows (BankStreamIn*).
 enum class StreamKernel : uint32_t { none, plain, prog, bus, in, banks, loops, general, dyn };
-// Everything a resident launch may need; each kernel's launcher (kernels.hip) reads and checks what its kernel takes.
+// A kernel's form: what it has on top of bank_stream_kernel.  The kernels are a cascade -- each is the one before it and one
+// thing more --, so the enum's order is the form.  kernels.hip's one resident body is instantiated by it, stream_launch_check
+// below reads it.
+struct StreamForm {
+    bool progs;      // runs the voices' programs (StreamProgArgs) and advances `head`
+    bool bus;        // ... and the bus segment in the block's last arriver
+    bool rows;       // the doorbell of n_rows rows, S_INPUT by row; else the one-row doorbell
+    bool table;      // a workgroup finds its bank in the table (StreamBanksArgs); else the one bank of BankArgs
+    bool loops;      // loop programs: the load and store tiles and the instruction copy
+    bool schedule;   // schedule banks (StreamGeneralArgs)
+    bool dyn;        // the interpreter knows the Delays by a signal amount; a plan need not have a schedule bank
+};
+constexpr StreamForm stream_form(StreamKernel k) {
+    return {k >= StreamKernel::prog,  k >= StreamKernel::bus,     k >= StreamKernel::in, k >= StreamKernel::banks,
+            k >= StreamKernel::loops, k >= StreamKernel::general, k == StreamKernel::dyn};
+}
+// Everything a resident launch may need; stream_launch_check reads and checks what the kernel takes.
 struct StreamLaunchArgs {
     BankArgs a;
     StreamProgArgs p;
@@ -325,6 +341,65 @@ struct StreamLaunchArgs {
     uint32_t idle_ms;                           // 0 = BANK_STREAM_IDLE_MS
 };
 hipError_t launch_bank_stream(StreamKernel k, const StreamLaunchArgs &x, hipStream_t s);
+
+// What every resident launch checks of a balanced bank's shape, and of the programs' arguments.  (chunk_log2 >= 7: each of
+// the 16 waves gets a whole group of 8 partials.)
+inline bool stream_bank_ok(uint32_t log2_p, uint32_t chunk_log2, uint32_t n_voices, const float *ws, const uint32_t *tickets) {
+    if (chunk_log2 < 7 || chunk_log2 > 13 || chunk_log2 > log2_p || log2_p - chunk_log2 > 8) return false;
+    if (((uint64_t)n_voices << (log2_p - chunk_log2)) > BANK_STREAM_WGS || n_voices == 0) return false;   // all workgroups must be resident
+    return chunk_log2 == log2_p || (ws && tickets);
+}
+inline bool stream_progs_ok(const StreamProgArgs &p, bool to_ring) {
+    if (!p.voice_first || (p.ring_mask & (p.ring_mask + 1)) != 0) return false;
+    return !(p.n_rings && (!p.rings || p.ring_mask + 1 < 64u)) && !(to_ring && !p.n_rings);
+}
+// The bank table: every bank as the one-bank kernels' bank; the banks' workgroups and voices follow one another without a
+// gap.  `schedule_mask`: the schedule banks (StreamGeneralArgs::mask), one workgroup per voice whatever their log2_p and
+// chunk_log2 say.  Returns the launch's workgroups (0: refused) and whether a bank feeds rings.
+inline uint32_t stream_table_ok(const StreamBanksArgs &t, const BankArgs &a, uint32_t schedule_mask, bool &to_ring) {
+    if (t.n_banks == 0 || t.n_banks > BANK_STREAM_BANKS || (schedule_mask >> t.n_banks) != 0) return 0;
+    uint64_t wgs = 0, voices = 0;
+    to_ring = false;
+    for (uint32_t i = 0; i < t.n_banks; ++i) {
+        const StreamBanksArgs::Bank &b = t.bank[i];
+        const bool schedule = (schedule_mask >> i) & 1u;
+        if (schedule ? b.n_voices == 0 : !stream_bank_ok(b.log2_p, b.chunk_log2, b.n_voices, a.ws, a.tickets)) return 0;
+        if (!b.params || !b.rows || b.first_wg != wgs || b.first_voice != voices) return 0;
+        wgs += schedule ? (uint64_t)b.n_voices : (uint64_t)b.n_voices << (b.log2_p - b.chunk_log2);
+        voices += b.n_voices;
+        if (wgs > BANK_STREAM_WGS) return 0;   // all workgroups must be resident
+        to_ring = to_ring || b.to_ring != 0;
+    }
+    return voices == a.n_voices ? (uint32_t)wgs : 0;
+}
+
+// What launch_bank_stream checks before it launches kernel `k`, by the kernel's form: plain host logic, so it is tested without
+// a device (tests/cpp/streamcheck_tests.cpp).  Returns the workgroups to launch -- exactly those that render: a small patch
+// leaves the other CUs to whatever else wants the device --, 0: refused.
+inline uint32_t stream_launch_check(StreamKernel k, const StreamLaunchArgs &x) {
+    if (k == StreamKernel::none || k > StreamKernel::dyn) return 0;
+    const StreamForm f = stream_form(k);
+    const BankArgs &a = x.a;
+    if (a.leaf_variant != 1 || !a.out || !x.ctl_dev || !x.dev) return 0;
+    if (f.rows && (x.n_rows == 0 || x.n_rows > BANK_STREAM_ROWS)) return 0;
+    // the tiles' limits concern loop programs; the general form takes a plan without one (max_stride == 0)
+    if (f.loops && (x.max_stride > BANK_STREAM_LOOP_MAX_STRIDE || x.max_loads > BANK_STREAM_LOOP_LOADS || x.max_stores > BANK_STREAM_LOOP_STORES)) return 0;
+    if ((f.schedule ? x.max_stride != 0 : f.loops) && !x.p.n_rings) return 0;   // a loop lives in a ring
+    uint32_t wgs = 0;
+    bool to_ring = f.progs && x.p.bank_to_ring != 0;
+    if (f.table) {
+        const uint32_t mask = f.schedule ? x.g.mask : 0u;
+        if (f.schedule && !f.dyn && mask == 0) return 0;   // (only dyn takes a plan without a schedule bank)
+        wgs = stream_table_ok(x.t, a, mask, to_ring);
+        if (!wgs) return 0;
+        for (uint32_t i = 0; i < x.t.n_banks; ++i)
+            if (((mask >> i) & 1u) && (!x.g.bank[i].groups || !x.g.bank[i].group_off)) return 0;
+    } else {
+        if (!stream_bank_ok(a.log2_p, a.chunk_log2, a.n_voices, a.ws, a.tickets) || !a.rows) return 0;
+        wgs = a.n_voices << (a.log2_p - a.chunk_log2);
+    }
+    return !f.progs || stream_progs_ok(x.p, to_ring) ? wgs : 0;
+}
 
 // The host's side of a doorbell by its form: all its words (the stop goes to every one), the done tag, the two blocks' sizes.
 static_assert(offsetof(BankStreamCtl, row) == offsetof(BankStreamInCtl, rows), "a one-row doorbell is the first row of a doorbell of rows");

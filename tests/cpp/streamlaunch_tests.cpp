@@ -1,85 +1,15 @@
 // streamlaunch_tests.cpp -- the launch rule of block streaming on the host (libfriendship_amd/csrc/streamplan.hpp stream_path,
-// stream_launch, plain_stream_launch): each of the seven resident kernels on a hand-built plan that calls for it, with its
+// stream_launch, plain_stream_launch): each of the resident kernels on a hand-built plan (streamplans.hpp) that calls for it, with its
 // doorbell form, rows, tables, limits and workgroups; the precedence general > loops > banks > in > bus > prog; the loop limits
 // against a direct count over the instructions; the plain path exactly where fr_stream_begin has always taken it; and the
 // one-bank chunk dealing against the loop fr_stream_begin used to have.  Stand-alone: built and run on the CPU with
 // -fsanitize=address,undefined by tests/test_stream_launch_host.py.
-#include <cstdio>
 #include <cstring>
 #include <set>
 #include <string>
 #include <vector>
 
-#include "../../libfriendship_amd/csrc/streamplan.hpp"
-
-using namespace fr;
-
-static int passed = 0, failed = 0;
-#define CHECK(cond)                                                                 \
-    do {                                                                            \
-        if (cond) ++passed;                                                         \
-        else { ++failed; std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); } \
-    } while (0)
-
-constexpr uint32_t NO_RING = 0xFFFFFFFFu;
-
-static StageInstr ins(uint8_t op, uint8_t dst, uint8_t a, uint8_t b, uint32_t imm, uint32_t buf, uint32_t d) {
-    StageInstr i{};
-    i.op = op; i.dst = dst; i.a = a; i.b = b; i.imm = imm; i.buf = buf; i.d_lo = d;
-    return i;
-}
-
-// ---- hand-built plans -------------------------------------------------------------------------------------------------------
-struct Built {
-    StagedPlan sp;
-    std::vector<BankLaunch> banks;
-    StreamEnv env;
-    Built() { env.programs = true; }
-    std::vector<const BankLaunch *> list() const {
-        std::vector<const BankLaunch *> l;
-        for (const BankLaunch &b : banks) l.push_back(&b);
-        return l;
-    }
-    void bank(uint32_t log2_p, bool to_ring, std::vector<uint32_t> rows) {
-        BankLaunch b;
-        b.log2_p = log2_p;
-        b.to_ring = to_ring;
-        b.rows = std::move(rows);
-        banks.push_back(b);
-    }
-    // a program of one level (a feedback plan: of the fused form)
-    void program(const std::vector<StageInstr> &p, uint32_t result, uint32_t dst_ring, int32_t out_row) {
-        StageProg pg{};
-        pg.first_instr = (uint32_t)sp.instrs.size();
-        pg.n_instr = (uint32_t)p.size();
-        pg.result_reg = result;
-        pg.dst_ring = dst_ring;
-        pg.out_row = out_row;
-        sp.instrs.insert(sp.instrs.end(), p.begin(), p.end());
-        sp.progs.push_back(pg);
-        sp.level_first = {0, (uint32_t)sp.progs.size()};
-        if (sp.feedback) { sp.fused_first = 0; sp.fused_count = (uint32_t)sp.progs.size(); sp.post_first = sp.fused_count; }
-    }
-    StreamPlan plan() const { return plan_stream(sp, list(), env); }
-};
-
-// voice ring `ring` at the current frame to output row `row`
-static std::vector<StageInstr> follow(uint32_t ring) { return {ins(S_READ, 0, 0, 0, 0, ring, 0)}; }
-// x = voice ring + Delay(x, d), x in `ring` (a loop of d frames)
-static std::vector<StageInstr> comb(uint32_t voice_ring, uint32_t ring, uint32_t d) {
-    return {ins(S_READ, 0, 0, 0, 0, voice_ring, 0), ins(S_READ, 1, 0, 0, 0, ring, d), ins(S_SUM2, 0, 0, 1, 0, 0, 0), ins(S_STORE, 0, 0, 0, 0, ring, 0)};
-}
-
-// two voices of 128 partials behind rings 0 and 1, a program per voice that copies its ring to its row
-static Built two_voices() {
-    Built b;
-    b.env.n_slots = 2;
-    b.bank(7, true, {0, 1});
-    b.sp.n_rings = 2;
-    b.program(follow(0), 0, NO_RING, 0);
-    b.program(follow(1), 0, NO_RING, 1);
-    return b;
-}
+#include "streamplans.hpp"
 
 static bool no_limits(const StreamLaunch &l) { return l.max_stride == 0 && l.max_loads == 0 && l.max_stores == 0; }
 static bool one_row(const StreamLaunch &l) { return !l.rows_doorbell && l.n_rows == 1 && !l.own_instrs && !l.bank_table && !l.schedule_table && !l.by_plan; }
@@ -114,7 +44,7 @@ static void test_each_kernel() {
         CHECK(!plain_stream_launch(9, 10, 8, sb, l));
     }
     {   // prog: a program per voice
-        const Built b = two_voices();
+        const Built b = kernel_plan(StreamKernel::prog);
         CHECK(stream_path(b.sp, b.list(), b.env));
         const StreamPlan s = b.plan();
         CHECK(s.servable && s.bus_programs() == 0);
@@ -122,10 +52,7 @@ static void test_each_kernel() {
         CHECK(l.kernel == StreamKernel::prog && one_row(l) && no_limits(l) && l.workgroups == 2);
     }
     {   // bus: and a program that reads both voices of the block
-        Built b = two_voices();
-        b.env.bus = true;
-        b.env.n_slots = 3;
-        b.program({ins(S_READ, 0, 0, 0, 0, 0, 0), ins(S_READ, 1, 0, 0, 0, 1, 0), ins(S_SUM2, 0, 0, 1, 0, 0, 0)}, 0, NO_RING, 2);
+        Built b = kernel_plan(StreamKernel::bus);
         const StreamPlan s = b.plan();
         CHECK(s.servable && s.bus_programs() == 1);
         const StreamLaunch l = stream_launch(b.sp, s);
@@ -134,24 +61,14 @@ static void test_each_kernel() {
         CHECK(!b.plan().servable);
     }
     {   // in: a program reads slot 3 next to the time slot
-        Built b = two_voices();
-        b.env.inputs = true;
-        b.env.n_slots = 3;
-        b.sp.input_slots = {0, 3};
-        b.program({ins(S_INPUT, 0, 0, 0, 1, 0, 0)}, 0, NO_RING, 2);
+        const Built b = kernel_plan(StreamKernel::in);
         const StreamPlan s = b.plan();
         CHECK(s.servable && s.input_slots == (std::vector<uint32_t>{0, 3}));
         const StreamLaunch l = stream_launch(b.sp, s);
         CHECK(l.kernel == StreamKernel::in && rows_of(l, 2, false, false) && no_limits(l) && l.workgroups == 2);
     }
     {   // banks: a voice of 128 partials behind a program next to a voice of 512 that writes its row
-        Built b;
-        b.env.n_slots = 2;
-        b.env.banks = true;
-        b.bank(7, true, {0});
-        b.bank(9, false, {1});
-        b.sp.n_rings = 1;
-        b.program(follow(0), 0, NO_RING, 0);
+        const Built b = kernel_plan(StreamKernel::banks);
         const StreamPlan s = b.plan();
         CHECK(s.servable && s.banks.size() == 2);
         const StreamLaunch l = stream_launch(b.sp, s);
@@ -164,24 +81,14 @@ static void test_each_kernel() {
         CHECK(t.servable && stream_launch(c.sp, t).kernel == StreamKernel::banks);
     }
     {   // loops: a comb of 5 frames on voice 0
-        Built b;
-        b.env.n_slots = 2;
-        b.env.loops = true;
-        b.bank(7, true, {0, 1});
-        b.sp.feedback = true;
-        b.sp.n_rings = 3;
-        b.program(comb(0, 2, 5), 0, NO_RING, 0);
-        b.program(follow(1), 0, NO_RING, 1);
+        const Built b = kernel_plan(StreamKernel::loops);
         const StreamPlan s = b.plan();
         CHECK(s.servable && s.has_loops());
         const StreamLaunch l = stream_launch(b.sp, s);
         CHECK(l.kernel == StreamKernel::loops && rows_of(l, 1, true, false) && l.max_stride == 5 && l.max_loads == 2 && l.max_stores == 1 && l.workgroups == 2);
     }
     {   // general: two voices of 32 partials that write their rows
-        Built b;
-        b.env.n_slots = 2;
-        b.env.general = true;
-        b.bank(5, false, {0, 1});
+        const Built b = kernel_plan(StreamKernel::general);
         CHECK(stream_path(b.sp, b.list(), b.env));
         const StreamPlan s = b.plan();
         CHECK(s.servable && s.has_general());
