@@ -103,6 +103,34 @@ def block_rows(rng, starts):
     return rows
 
 
+FIRST_LENGTHS = (64, 64, 1, 37, 64, 2, 63)      # full, full, one frame, ragged, full, two, one short of full
+FINITE_SPECIAL = SPECIAL[np.isfinite(SPECIAL)]  # every one of them gives a finite voice
+POISON = SPECIAL[~np.isfinite(SPECIAL)]
+
+
+def finite_block_rows(rng, starts):
+    """[(idx, row)] as block_rows gives them, for patches with feedback: in x = voice + g * Delay(x, d) a NaN never leaves, so
+    rows that poison a loop early leave NaN to be compared with NaN.  Per segment of `starts` = [(first frame, frames)]: the
+    first seven blocks have FIRST_LENGTHS, the later ones a random length 1..64, the last one is cut at the segment's end;
+    every fifth block (k % 5 == 4) carries hostile but FINITE time values in a quarter of its entries; the segment's last
+    block carries +-inf and NaN in a quarter of its entries -- what follows it is a seek (the engine rebuilds the loops from
+    frame 0 with every input 0.0) or the end."""
+    rows = []
+    for idx, frames in starts:
+        end, k = idx + frames, 0
+        while idx < end:
+            T = int(min(FIRST_LENGTHS[k] if k < len(FIRST_LENGTHS) else rng.integers(1, 65), end - idx))
+            row = synth.time_ramp(idx, idx + T)
+            values = POISON if idx + T == end else FINITE_SPECIAL if k % 5 == 4 else None
+            if values is not None:
+                row = row.copy()
+                row[rng.integers(T, size=max(1, T // 4))] = values[rng.integers(len(values), size=max(1, T // 4))]
+            rows.append((idx, row))
+            idx += T
+            k += 1
+    return rows
+
+
 def silence_voice(tree, V, P, v):
     """The tree with every amplitude of voice v of its bank of V voices x P partials (synth.voice_params: amp = 1 / (k + 1))
     replaced by +0.0: every leaf of the voice is +-0, every chunk sum of it is an exact zero, and the kernel has to find the

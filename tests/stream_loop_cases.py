@@ -23,7 +23,7 @@ import stream_bus_cases as B
 import stream_cases as K
 import stream_input_cases as I
 from libfriendship_amd import synth
-from stream_cases import block_rows, comb_tree, short_blocks, silence_voice   # noqa: F401  (the tests take them from here)
+from stream_cases import block_rows, comb_tree, finite_block_rows, short_blocks, silence_voice   # noqa: F401  (the tests take them from here)
 
 NEW_KERNEL = "bank_stream_loops_kernel"
 PROGRAMS = dict(K.OPTION)                                       # FR_STREAM_PROGRAMS alone
