@@ -128,7 +128,23 @@ extern "C" {
  * streamed programs' signal delays of a voice and of a constant) and "lookback" (the deepest delay-line read, the bound
  * included); "kernel" is "bank_stream_dyn_kernel" exactly when there is such a delay.  Still refused, each with its reason: a
  * signal delay inside a feedback loop shorter than a block, of a computed value (a ring that a program stores), of an input
- * row (a stream keeps no input history), and one whose bound was observed from input rows (FR_DELAY_OBSERVED).
+ * row (a stream keeps no input history; FR_STREAM_HISTORY below), and one whose bound was observed from input rows
+ * (FR_DELAY_OBSERVED).
+ *
+ * FR_STREAM_HISTORY = 0 / 1 (default 0; read strictly from the environment too; does nothing unless FR_STREAM_PROGRAMS=1):
+ * block streaming also serves a DELAYED READ OF AN INPUT ROW -- Delay(In(k), d): a pre-delay or a slap-back on a control or
+ * audio row, a delayed gate, an LFO row read a quarter period late, Delay(In(0), d) on the time row itself -- at any constant
+ * delay, 0..63 frames included, in per-voice programs, mix buses (FR_STREAM_BUS) and feedback loops shorter than a block
+ * (FR_STREAM_LOOPS); and, with FR_STREAM_DYN, by a signal amount for which the planner proves a bound (Delay(In(1),
+ * Minimum(In(2), 48))).  A slot other than 0 needs FR_STREAM_INPUTS as before and counts towards its 8 slots.  The stream
+ * keeps a history of the rows it is fed -- the power of two >= the deepest such read + 64 frames per streamed slot, at most
+ * 1 048 576 frames back (4 MiB per slot) -- in a ninth resident kernel (bank_stream_hist_kernel); a seek empties it, as a seek
+ * of fr_fill_buffer makes every earlier input read 0.0: same bits, in both semantics.  With 0 nothing changes: the same plans
+ * are served and refused, with the same reasons, by the same kernels.  "stream" gains "hist_reads" and "hist_dyn_reads" (the
+ * streamed programs' delayed reads of input rows by a constant and by a signal amount) and "input_lookback" (the deepest of
+ * them); "kernel" is "bank_stream_hist_kernel" exactly when there is such a read.  Still refused, each with its reason: a
+ * signal delay of an input row without FR_STREAM_DYN, without a proven bound, inside a feedback loop shorter than a block, or
+ * next to a bound observed from input rows; a read further back than the limit; a patch without a voice.
  */
 typedef struct fr_option {
     const char *name;              /* e.g. "FR_BANK_SHORT" */

@@ -197,7 +197,7 @@ static std::string stage_variant(const StageLaunchNote &n, const Plan &p) {
     return k;
 }
 
-constexpr size_t N_OPTIONS = 38;        // per-renderer options (friendship_render_ext.h; the table below fr_renderer)
+constexpr size_t N_OPTIONS = 39;        // per-renderer options (friendship_render_ext.h; the table below fr_renderer)
 
 struct TimerClass {
     double ms = 0;
@@ -526,7 +526,7 @@ struct fr_renderer {
         bool open = false;
         // what outlives a stream: the buffers (they only grow), the last resident launch's kernel (fr_plan_json "stream"), the trace
         PinnedBuf h_ctl, h_out;
-        DevBuf d_dev, d_progs, d_vfirst, d_sched, d_instrs;   // (d_instrs: StreamLaunch::own_instrs)
+        DevBuf d_dev, d_progs, d_vfirst, d_sched, d_instrs, d_hist;   // (d_instrs: StreamLaunch::own_instrs; d_hist: StreamLaunch::hist_cap)
         StreamKernel last_kernel = StreamKernel::none;
         double trace_us[2] = {0, 0};
         uint64_t trace_n = 0;
@@ -553,8 +553,9 @@ struct fr_renderer {
         }
         return d_tickets.as<uint32_t>();
     }
-    // FR_STREAM_PROGRAMS, _BUS, _INPUTS, _LOOPS, _BANKS, _GENERAL, _DYN (the options table says what each serves; streamplan.hpp StreamEnv)
-    bool stream_programs = false, stream_bus = false, stream_inputs = false, stream_loops = false, stream_banks = false, stream_general = false, stream_dyn = false;
+    // FR_STREAM_PROGRAMS, _BUS, _INPUTS, _LOOPS, _BANKS, _GENERAL, _DYN, _HISTORY (the options table says what each serves; streamplan.hpp StreamEnv)
+    bool stream_programs = false, stream_bus = false, stream_inputs = false, stream_loops = false, stream_banks = false, stream_general = false, stream_dyn = false,
+         stream_history = false;
     std::vector<const BankLaunch *> stream_bank_list() const {
         std::vector<const BankLaunch *> banks;
         for (const BankStage &bs : plan.banks) banks.push_back(&bs.grp);
@@ -570,6 +571,7 @@ struct fr_renderer {
         env.track_history = tail_on();
         env.programs = stream_programs; env.bus = stream_bus; env.inputs = stream_inputs;
         env.banks = stream_banks; env.loops = stream_loops; env.general = stream_general; env.dyn = stream_dyn;
+        env.history = stream_history;
         return env;
     }
     StreamPlan plan_stream_now() const { return plan_stream(plan.sp, stream_bank_list(), stream_env()); }
@@ -2251,8 +2253,9 @@ void fr_renderer::begin_program_stream(uint32_t n_slots) {
             HIP_CHECK(hipStreamSynchronize(stream));   // (`words` goes out of scope)
         }
     }
-    // the stream's own copy of the programs' instructions (StreamLaunch::own_instrs): S_INPUT's operand the streamed row (the
-    // position of its slot in input_slots) instead of the plan's input index; a loop program's store slots
+    // the stream's own copy of the programs' instructions (StreamLaunch::own_instrs): the operand of S_INPUT -- and of S_READ_INPUT
+    // and S_READ_INPUT_DYN, FR_STREAM_HISTORY -- the streamed row (the position of its slot in input_slots) instead of the plan's
+    // input index; a loop program's store slots.  (The plan's own instructions, which the ordinary path runs, are not touched.)
     std::vector<StageInstr> instrs;
     if (l.own_instrs) {
         if (s.input_slots.size() > BANK_STREAM_ROWS) throw Error(FR_ERR_DEVICE, "internal: more streamed rows than the kernel takes");
@@ -2261,7 +2264,7 @@ void fr_renderer::begin_program_stream(uint32_t n_slots) {
             std::vector<StageInstr> own;
             for (uint32_t k = 0; k < pg.n_instr; ++k) {
                 StageInstr in = sp.instrs[pg.first_instr + k];
-                if (in.op == S_INPUT) {
+                if (in.op == S_INPUT || in.op == S_READ_INPUT || in.op == S_READ_INPUT_DYN) {
                     const auto it = in.imm < sp.input_slots.size() ? std::find(s.input_slots.begin(), s.input_slots.end(), sp.input_slots[in.imm]) : s.input_slots.end();
                     if (it == s.input_slots.end()) throw Error(FR_ERR_DEVICE, "internal: a streamed program reads a slot the stream does not feed");
                     in.imm = (uint32_t)(it - s.input_slots.begin());
@@ -2283,6 +2286,15 @@ void fr_renderer::begin_program_stream(uint32_t n_slots) {
     HIP_CHECK(hipStreamSynchronize(stream));   // (host vectors go out of scope)
     // rings: the deepest look-back and a block, as execute() sizes them for a 64-frame call (which the seek then finds in place)
     if (sp.uses_rings()) grow_rings(ring_capacity(sp, STREAM_BLOCK));
+    // the history of the streamed rows (FR_STREAM_HISTORY): hist_cap frames for each of the n_rows rows, zeroed by every seek.  It
+    // needs no books of its own next to streamrows.hpp's: what accept() puts into a block's doorbell for a slot -- the row, its
+    // padding, +0.0 for a slot without a row or beyond the vector count -- is, frame for frame, what fr_fill_buffer's input store
+    // would answer for that frame ever after (a slot that lags can only be fed again after a seek), and workgroup 0 stores exactly
+    // those words.  After a seek the store answers 0.0 for every earlier frame: the zeroed history, and the kernel's frame >= d.
+    if (l.hist_cap) {
+        if (l.hist_cap < s.input_lookback + STREAM_BLOCK || (l.hist_cap & (l.hist_cap - 1)) != 0) throw Error(FR_ERR_DEVICE, "internal: the input history does not hold the stream's look-back");
+        strm.d_hist.ensure((size_t)l.n_rows * l.hist_cap * sizeof(float));
+    }
     ensure_stream_buffers(l, n_slots);
     o.prog = true;
     o.plan = std::move(s);
@@ -2340,6 +2352,13 @@ void fr_renderer::seek_program_stream(uint64_t idx) {
     p.head = idx;
     p.bank_to_ring = !l.bank_table && plan.banks[0].grp.to_ring ? 1u : 0u;   // (a bank table: each bank has its own)
     p.sparkle = mirror.sparkle ? 1u : 0u;
+    if (l.hist_cap) {                                            // every frame before idx reads 0.0 after a seek: an empty history, on the launch's stream
+        const size_t bytes = (size_t)l.n_rows * l.hist_cap * sizeof(float);
+        if (bytes > strm.d_hist.bytes) throw Error(FR_ERR_DEVICE, "internal: the input history does not hold the stream's look-back");
+        HIP_CHECK(hipMemsetAsync(strm.d_hist.p, 0, bytes, stream));
+        x.h.hist = strm.d_hist.as<float>();
+        x.h.mask = l.hist_cap - 1;
+    }
     if (l.bank_table) {
         // the bank table travels in the kernel arguments (and, for schedule banks, a second table of their schedules); chunk
         // sums and tickets are laid out by global voice
@@ -2432,6 +2451,7 @@ int64_t env_strict_loop_tiles(const char *e);
 int64_t env_strict_stream_loops(const char *e);
 int64_t env_strict_stream_general(const char *e);
 int64_t env_strict_stream_dyn(const char *e);
+int64_t env_strict_stream_history(const char *e);
 bool parse_option(const Knob &k, const char *s, int64_t &v);
 
 const Knob kKnobs[] = {
@@ -2531,6 +2551,10 @@ const Knob kKnobs[] = {
     // Delays of a voice by a signal amount in block streaming -- a chorus, a flanger, a vibrato, a delay time on a knob
     // (streamplan.hpp StreamEnv::dyn; fr_plan_json: stream.dyn_reads).  Inert without FR_STREAM_PROGRAMS.  Strict and listed once set.
     {"FR_STREAM_DYN", 0, 0, 1, 0, nullptr, 0, env_strict_stream_dyn, [](fr_renderer &r, int64_t v, bool) { r.stream_dyn = v != 0; }, LISTED_WHEN_SET},
+    // Delayed reads of input rows in block streaming -- a pre-delay on a control row, a delayed gate, Delay(In(0), d); with
+    // FR_STREAM_DYN by a signal amount -- from a history of the streamed rows (streamplan.hpp StreamEnv::history; fr_plan_json:
+    // stream.hist_reads, stream.input_lookback).  Inert without FR_STREAM_PROGRAMS.  Strict and listed once set.
+    {"FR_STREAM_HISTORY", 0, 0, 1, 0, nullptr, 0, env_strict_stream_history, [](fr_renderer &r, int64_t v, bool) { r.stream_history = v != 0; }, LISTED_WHEN_SET},
 };
 static_assert(sizeof kKnobs / sizeof kKnobs[0] == N_OPTIONS, "N_OPTIONS counts the rows of kKnobs");
 
@@ -2550,6 +2574,7 @@ int64_t env_strict_loop_tiles(const char *e) { return env_strict("FR_LOOP_TILES"
 int64_t env_strict_stream_loops(const char *e) { return env_strict("FR_STREAM_LOOPS", e); }
 int64_t env_strict_stream_general(const char *e) { return env_strict("FR_STREAM_GENERAL", e); }
 int64_t env_strict_stream_dyn(const char *e) { return env_strict("FR_STREAM_DYN", e); }
+int64_t env_strict_stream_history(const char *e) { return env_strict("FR_STREAM_HISTORY", e); }
 
 bool parse_option(const Knob &k, const char *s, int64_t &v) {
     if (k.word && std::strcmp(s, k.word) == 0) {
@@ -3185,6 +3210,9 @@ const char *fr_plan_json(fr_renderer *r) {
             if (r->stream_dyn)                                   // FR_STREAM_DYN: the assigned programs' Delays by a signal amount, and the deepest ring read
                 r->plan_json_cache += ",\"dyn_reads\":" + std::to_string(s.dyn_reads) + ",\"dyn_steps\":" + std::to_string(s.dyn_steps) +
                                       ",\"lookback\":" + std::to_string(s.lookback);
+            if (r->stream_history)                               // FR_STREAM_HISTORY: the assigned programs' delayed reads of input rows, and the deepest of them
+                r->plan_json_cache += ",\"hist_reads\":" + std::to_string(s.hist_reads) + ",\"hist_dyn_reads\":" + std::to_string(s.hist_dyn_reads) +
+                                      ",\"input_lookback\":" + std::to_string(s.input_lookback);
             const StreamLaunch l = s.servable ? stream_launch(r->plan.sp, s) : StreamLaunch{};
             const char *kernel = stream_kernel_name(l.by_plan ? l.kernel : stream_kernel_by_plan(r->strm.last_kernel) ? StreamKernel::none : r->strm.last_kernel);
             if (r->stream_banks) {                               // FR_STREAM_BANKS: the banks of the launch, in plan order

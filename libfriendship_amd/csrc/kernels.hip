@@ -788,7 +788,7 @@ static hipError_t launch_bank_short(const BankArgs &a, hipStream_t s) {
 
 // ---------------------------------------------------------------------------------------------------
 // Block streaming: the short-call kernel as ONE resident launch (kernels.hpp, BankStreamCtl).  Each step of the protocol is
-// written once, in this section; the skeleton that calls the steps -- stream_resident_body, of which the eight resident
+// written once, in this section; the skeleton that calls the steps -- stream_resident_body, of which the nine resident
 // kernels are instantiations -- follows stage_kernel, whose interpreter's types it uses.
 //
 // A block.  The host rings a doorbell in mapped pinned memory: every word carries a sample and the block's tag.  Wave 0 of
@@ -882,9 +882,14 @@ __device__ __forceinline__ uint32_t stream_row_wait(BankStreamCtl *ctl, BankStre
 
 // The same for a doorbell of K rows (BankStreamInCtl).  One look = the loads of all K rows in flight together, then one wait: a
 // word whose tag is new carries its sample with it, so however many rows there are the block costs one trip across PCIe.  The
-// block has arrived when every lane of every row holds the same new tag.
-template <uint32_t K>
-__device__ __forceinline__ uint32_t stream_in_wait(BankStreamInCtl *ctl, BankStreamInDev *dev, uint32_t lane, uint32_t seen, unsigned long long idle_ticks, uint32_t &T) {
+// block has arrived when every lane of every row holds the same new tag.  `keep(row, sample, T)`: what else workgroup 0 does
+// with a row's samples under the same acknowledgement (StreamNoHistory: nothing; StreamHistoryStore: the hist form's history).
+struct StreamNoHistory {
+    __device__ __forceinline__ void operator()(uint32_t, float, uint32_t) const {}
+};
+template <uint32_t K, class Keep>
+__device__ __forceinline__ uint32_t stream_in_wait(BankStreamInCtl *ctl, BankStreamInDev *dev, uint32_t lane, uint32_t seen, unsigned long long idle_ticks, uint32_t &T,
+                                                   const Keep &keep) {
     unsigned long long word[K];
     uint32_t tag = seen;
     bool fresh = false;
@@ -907,23 +912,25 @@ __device__ __forceinline__ uint32_t stream_in_wait(BankStreamInCtl *ctl, BankStr
         static_for<0, K>([&](auto j) {
             __hip_atomic_store(&dev->rows[j][lane], lane < T ? __uint_as_float((uint32_t)word[j]) : 0.0f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         });
+        static_for<0, K>([&](auto j) { keep((uint32_t)j, __uint_as_float((uint32_t)word[j]), T); });
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
     return seq;
 }
 
 // (launch-uniform row count: one jump, then a loop whose every look is straight-line code)
+template <class Keep>
 __device__ __forceinline__ uint32_t stream_rows_wait(uint32_t n_rows, BankStreamInCtl *ctl, BankStreamInDev *dev, uint32_t lane, uint32_t seen,
-                                                     unsigned long long idle_ticks, uint32_t &T) {
+                                                     unsigned long long idle_ticks, uint32_t &T, const Keep &keep) {
     switch (n_rows) {
-    case 1: return stream_in_wait<1>(ctl, dev, lane, seen, idle_ticks, T);
-    case 2: return stream_in_wait<2>(ctl, dev, lane, seen, idle_ticks, T);
-    case 3: return stream_in_wait<3>(ctl, dev, lane, seen, idle_ticks, T);
-    case 4: return stream_in_wait<4>(ctl, dev, lane, seen, idle_ticks, T);
-    case 5: return stream_in_wait<5>(ctl, dev, lane, seen, idle_ticks, T);
-    case 6: return stream_in_wait<6>(ctl, dev, lane, seen, idle_ticks, T);
-    case 7: return stream_in_wait<7>(ctl, dev, lane, seen, idle_ticks, T);
-    default: return stream_in_wait<8>(ctl, dev, lane, seen, idle_ticks, T);
+    case 1: return stream_in_wait<1>(ctl, dev, lane, seen, idle_ticks, T, keep);
+    case 2: return stream_in_wait<2>(ctl, dev, lane, seen, idle_ticks, T, keep);
+    case 3: return stream_in_wait<3>(ctl, dev, lane, seen, idle_ticks, T, keep);
+    case 4: return stream_in_wait<4>(ctl, dev, lane, seen, idle_ticks, T, keep);
+    case 5: return stream_in_wait<5>(ctl, dev, lane, seen, idle_ticks, T, keep);
+    case 6: return stream_in_wait<6>(ctl, dev, lane, seen, idle_ticks, T, keep);
+    case 7: return stream_in_wait<7>(ctl, dev, lane, seen, idle_ticks, T, keep);
+    default: return stream_in_wait<8>(ctl, dev, lane, seen, idle_ticks, T, keep);
     }
 }
 
@@ -1186,7 +1193,11 @@ __device__ __forceinline__ bool stream_hand_over(const StreamWork &w, float *ws,
     return true;
 }
 
-// A program's load.  `input(row)` is S_INPUT: the block's one row, or a republished control row.
+// A program's load.  `input(row)` is S_INPUT: the block's one row, or a republished control row.  An input with a history (the
+// hist form's StreamHistInput; kernels.hpp bank_stream_hist_kernel has the argument) also serves S_READ_INPUT: the streamed row
+// imm, d_lo frames back, 0.0 before frame 0 -- a frame-only load like the others, so it goes out with a program's leading loads.
+template <class Input>
+constexpr bool stream_has_history = std::remove_reference_t<Input>::history;
 template <class Input>
 __device__ __forceinline__ float stream_prog_load(const StreamProgArgs &p, const StageInstr &in, uint64_t frame, Input &&input) {
     switch (in.op) {
@@ -1196,6 +1207,9 @@ __device__ __forceinline__ float stream_prog_load(const StreamProgArgs &p, const
         return frame >= in.d_lo ? __hip_atomic_load(p.rings + (size_t)in.buf * (p.ring_mask + 1) + ((frame - in.d_lo) & p.ring_mask), __ATOMIC_RELAXED,
                                                     __HIP_MEMORY_SCOPE_AGENT)
                                 : 0.0f;
+    case S_READ_INPUT:
+        if constexpr (stream_has_history<Input>) return frame >= in.d_lo ? input.at(in.imm, frame - in.d_lo) : 0.0f;
+        [[fallthrough]];
     default: return frame >= in.d_lo ? __uint_as_float(in.imm) : 0.0f;   // S_STEP
     }
 }
@@ -1215,7 +1229,9 @@ __device__ __forceinline__ float stream_prog_dyn(const float *rings, uint64_t ri
 }
 
 // The interpreter: programs [p_first, p_end) in order, lane = frame, in wave 0 of a finishing workgroup; `regs` are its
-// registers, [register][lane] in LDS; `out` the mapped host rows.  DYN: it also knows S_READ_DYN and S_STEP_DYN.
+// registers, [register][lane] in LDS; `out` the mapped host rows.  DYN: it also knows S_READ_DYN and S_STEP_DYN; with an input that
+// has a history (stream_has_history) S_READ_INPUT_DYN too: stream_prog_dyn with the history as its rings and the streamed row as
+// the ring -- the same cast, the same range test, the same masked relaxed agent-scope load.
 template <bool DYN = false, class Input>
 __device__ __forceinline__ void stream_run_programs(float *out, const StreamProgArgs &p, float (&regs)[STAGE_REGS][64], uint32_t p_first, uint32_t p_end, uint64_t frame,
                                                     uint32_t lane, bool live, Input &&input) {
@@ -1248,6 +1264,12 @@ __device__ __forceinline__ void stream_run_programs(float *out, const StreamProg
             case S_READ_DYN: case S_STEP_DYN:
                 if constexpr (DYN) {
                     v = stream_prog_dyn(p.rings, p.ring_mask, p.sparkle, in.op, in.imm, in.buf, regs[in.a][lane], frame);
+                    break;
+                }
+                [[fallthrough]];
+            case S_READ_INPUT_DYN:
+                if constexpr (DYN && stream_has_history<Input>) {
+                    v = stream_prog_dyn(input.hist, input.hmask, p.sparkle, S_READ_DYN, 0u, in.imm & (BANK_STREAM_ROWS - 1u), regs[in.a][lane], frame);
                     break;
                 }
                 [[fallthrough]];
@@ -1306,7 +1328,7 @@ __device__ __forceinline__ void stream_run_loop_program(float *out, const Stream
             uint32_t at0 = 0, at1 = 0, at2 = 0, at3 = 0, m = 0;   // the next (up to) four loads: the last m of at0..at3
             for (; i < pg.n_instr && m < 4u; ++i) {
                 const uint32_t op = fetch(i).op;
-                if (op == S_INPUT || op == S_READ) { at0 = at1; at1 = at2; at2 = at3; at3 = i; ++m; }
+                if (op == S_INPUT || op == S_READ || (stream_has_history<Input> && op == S_READ_INPUT)) { at0 = at1; at1 = at2; at2 = at3; at3 = i; ++m; }
             }
             const uint32_t at[4] = {at0, at1, at2, at3};
             float ld[4];
@@ -1348,7 +1370,13 @@ __device__ __forceinline__ void stream_run_loop_program(float *out, const Stream
                 case S_MOD: v = prim_mod(regs[in.a][f], regs[in.b][f]); break;
                 case S_MIN: v = prim_min(regs[in.a][f], regs[in.b][f], p.sparkle != 0u); break;
                 case S_STORE: stt[(in.imm - 1u) & SM][f] = regs[in.a][f]; continue;
-                default: v = 0.0f; break;   // (a Delay of a signal amount, a delayed input: the rule serves no such program)
+                case S_READ_INPUT:          // (an input with a history: phase 1 loaded it like an S_INPUT)
+                    if constexpr (stream_has_history<Input>) {
+                        v = ldt[k++ & LM][f];
+                        break;
+                    }
+                    [[fallthrough]];
+                default: v = 0.0f; break;   // (a Delay of a signal amount; without a history a delayed input: the rule serves no such program)
                 }
                 regs[in.dst][f] = v;
             }
@@ -2039,7 +2067,7 @@ hipError_t launch_stage(const StageArgs &a, hipStream_t s) {
 }
 
 // ---------------------------------------------------------------------------------------------------
-// The eight resident kernels (kernels.hpp StreamKernel; the pieces and the protocol: above, "Block streaming"): ONE body,
+// The nine resident kernels (kernels.hpp StreamKernel; the pieces and the protocol: above, "Block streaming"): ONE body,
 // stream_resident_body, instantiated by the kernel's form (kernels.hpp StreamForm).  The body is the protocol's skeleton -- when
 // `alive` is published, the block loop and its stop test, which wave counts a voice in, when LDS may be reused -- and every
 // kernel is the one before it and one thing more:
@@ -2053,6 +2081,7 @@ hipError_t launch_stage(const StageArgs &a, hipStream_t s) {
 //   bank_stream_loops_kernel     loop programs in three phases (stream_run_loop_program)              36 880
 //   bank_stream_general_kernel   schedule banks (stream_render_schedule)                              45 072
 //   bank_stream_dyn_kernel       Delays by a signal amount (stream_prog_dyn)                          45 072
+//   bank_stream_hist_kernel      delayed reads of input rows: the rows' history (StreamHistArgs)      45 072
 //
 // The bus segment is progs[voice_first[n_voices] .. voice_first[n_voices + 1]) and may be empty.  Which kernel a plan launches
 // is the host's rule (streamplan.hpp; fr_plan_json["stream"]["kernel"]).  The compiled kernels against their earlier,
@@ -2061,6 +2090,7 @@ hipError_t launch_stage(const StageArgs &a, hipStream_t s) {
 
 // S_INPUT of the one-row kernels: the block's row, which the finishing wave holds as `t`.
 struct StreamRowInput {
+    static constexpr bool history = false;
     float t;
     __device__ __forceinline__ float operator()(uint32_t) const { return t; }
 };
@@ -2068,6 +2098,7 @@ struct StreamRowInput {
 // Row 0 is `t`; the others were republished before this workgroup saw the block's seq: a relaxed agent-scope load, in flight
 // with the program's other leading loads.
 struct StreamRowsInput {
+    static constexpr bool history = false;
     const BankStreamInDev *dev;
     uint32_t lane;
     float t;
@@ -2076,14 +2107,41 @@ struct StreamRowsInput {
     }
 };
 
+// The hist form (kernels.hpp bank_stream_hist_kernel, where the argument for all of this stands).  The history of the streamed
+// rows is hist[row][frame & hmask].  StreamHistoryStore is workgroup 0's side: wave 0 stores the live lanes of every row of the
+// block at `head` right after it has republished them -- relaxed agent-scope VECTOR stores, acknowledged by the wait's one
+// s_waitcnt vmcnt(0) together with the rows, so before n_times and seq.  StreamHistInput is the readers' side: S_INPUT as
+// StreamRowsInput, `at` a row's sample of an absolute frame -- a relaxed agent-scope load (L2's copy, never a CU's L1: the
+// storer is another CU), row and index masked.
+struct StreamHistoryStore {
+    float *hist;
+    uint64_t hmask, head;
+    uint32_t lane;
+    __device__ __forceinline__ void operator()(uint32_t row, float v, uint32_t T) const {
+        if (lane < T) __hip_atomic_store(hist + (size_t)row * (hmask + 1) + ((head + lane) & hmask), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+};
+struct StreamHistInput {
+    static constexpr bool history = true;
+    StreamRowsInput rows;
+    const float *hist;
+    uint64_t hmask;
+    __device__ __forceinline__ float operator()(uint32_t row) const { return rows(row); }
+    __device__ __forceinline__ float at(uint32_t row, uint64_t frame) const {
+        return __hip_atomic_load(hist + (size_t)(row & (BANK_STREAM_ROWS - 1u)) * (hmask + 1) + (frame & hmask), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+};
+
 // What the doorbell's form decides, by overload on its device block: workgroup 0's wait, the block's time row, S_INPUT.
+template <class Keep>
 __device__ __forceinline__ uint32_t stream_doorbell_wait(uint32_t, BankStreamCtl *ctl, BankStreamDev *dev, uint32_t lane, uint32_t seen, unsigned long long idle_ticks,
-                                                         uint32_t &T) {
+                                                         uint32_t &T, const Keep &) {
     return stream_row_wait(ctl, dev, lane, seen, idle_ticks, T);
 }
+template <class Keep>
 __device__ __forceinline__ uint32_t stream_doorbell_wait(uint32_t n_rows, BankStreamInCtl *ctl, BankStreamInDev *dev, uint32_t lane, uint32_t seen,
-                                                         unsigned long long idle_ticks, uint32_t &T) {
-    return stream_rows_wait(n_rows, ctl, dev, lane, seen, idle_ticks, T);
+                                                         unsigned long long idle_ticks, uint32_t &T, const Keep &keep) {
+    return stream_rows_wait(n_rows, ctl, dev, lane, seen, idle_ticks, T, keep);
 }
 __device__ __forceinline__ const float *stream_time_row(const BankStreamDev *dev) { return dev->row; }
 __device__ __forceinline__ const float *stream_time_row(const BankStreamInDev *dev) { return dev->rows[0]; }
@@ -2100,8 +2158,8 @@ __device__ __forceinline__ StreamRowsInput stream_input(const BankStreamInDev *d
 // (blockIdx.x - first_wg) whole: its chunk count is 1, so stream_hand_over returns at once.
 static_assert(STREAM_STACK_DEPTH == GB_MAX_DEPTH, "a schedule voice's stack is the general voices'");
 template <StreamKernel K, class Ctl, class Dev>
-__device__ __forceinline__ void stream_resident_body(StreamBanksArgs t, StreamGeneralArgs g, BankArgs a, StreamProgArgs p, uint32_t n_rows, Ctl *ctl, Dev *dev,
-                                                     uint32_t idle_ms) {
+__device__ __forceinline__ void stream_resident_body(StreamBanksArgs t, StreamGeneralArgs g, StreamHistArgs h, BankArgs a, StreamProgArgs p, uint32_t n_rows, Ctl *ctl,
+                                                     Dev *dev, uint32_t idle_ms) {
     constexpr StreamForm F = stream_form(K);
     __shared__ float sm[F.schedule ? 2 : 1][STREAM_NW][64];  // the waves' sums: a chunk's in [0], a schedule's items alternate
     __shared__ float stack_mem[STREAM_STACK_DEPTH][64];      // a schedule voice's evaluation stack: [level][frame] of wave 0
@@ -2151,7 +2209,11 @@ __device__ __forceinline__ void stream_resident_body(StreamBanksArgs t, StreamGe
     if (blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store(&ctl->alive, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     for (;;) {
         uint32_t T;
-        const uint32_t seq = stream_next_block(dev, wave, lane, seen, idle_ticks, s_seq, s_T, T, [&](uint32_t &T0) { return stream_doorbell_wait(n_rows, ctl, dev, lane, seen, idle_ticks, T0); });
+        const uint32_t seq = stream_next_block(dev, wave, lane, seen, idle_ticks, s_seq, s_T, T, [&](uint32_t &T0) {
+            // (the hist form: workgroup 0 keeps the block's rows, at the `head` every workgroup of a progs form carries)
+            if constexpr (F.hist) return stream_doorbell_wait(n_rows, ctl, dev, lane, seen, idle_ticks, T0, StreamHistoryStore{h.hist, h.mask, head, lane});
+            else return stream_doorbell_wait(n_rows, ctl, dev, lane, seen, idle_ticks, T0, StreamNoHistory{});
+        });
         if (seq == BANK_STREAM_STOP) break;
         seen = seq;
         const bool live = lane < T;
@@ -2163,7 +2225,10 @@ __device__ __forceinline__ void stream_resident_body(StreamBanksArgs t, StreamGe
         else r = stream_render_chunk(w, stream_time_row(dev), live, wave, lane, sm[0], zshared, t_in);
         if (wave == 0u && stream_hand_over(w, a.ws, a.tickets, n_voices, lane, r, result)) {
             // the finishing wave: the voice's frames head + lane to its ring or row, then its programs, then it counts the voice in
-            const auto input = stream_input(dev, lane, t_in);
+            const auto input = [&] {
+                if constexpr (F.hist) return StreamHistInput{stream_input(dev, lane, t_in), h.hist, h.mask};
+                else return stream_input(dev, lane, t_in);
+            }();
             auto run = [&](uint32_t p_first, uint32_t p_end) {
                 if constexpr (F.loops) stream_run_programs_loops<F.dyn>(a.out, p, regs, ldt, stt, lins, p_first, p_end, head, T, lane, live, input);
                 else if constexpr (F.progs) stream_run_programs(a.out, p, regs, p_first, p_end, head + lane, lane, live, input);
@@ -2180,32 +2245,36 @@ __device__ __forceinline__ void stream_resident_body(StreamBanksArgs t, StreamGe
 }
 
 __global__ void __launch_bounds__(1024) bank_stream_kernel(BankArgs a, BankStreamCtl *ctl, BankStreamDev *dev, uint32_t idle_ms) {
-    stream_resident_body<StreamKernel::plain>({}, {}, a, {}, 1u, ctl, dev, idle_ms);
+    stream_resident_body<StreamKernel::plain>({}, {}, {}, a, {}, 1u, ctl, dev, idle_ms);
 }
 __global__ void __launch_bounds__(1024) bank_stream_prog_kernel(BankArgs a, StreamProgArgs p, BankStreamCtl *ctl, BankStreamDev *dev, uint32_t idle_ms) {
-    stream_resident_body<StreamKernel::prog>({}, {}, a, p, 1u, ctl, dev, idle_ms);
+    stream_resident_body<StreamKernel::prog>({}, {}, {}, a, p, 1u, ctl, dev, idle_ms);
 }
 __global__ void __launch_bounds__(1024) bank_stream_bus_kernel(BankArgs a, StreamProgArgs p, BankStreamCtl *ctl, BankStreamDev *dev, uint32_t idle_ms) {
-    stream_resident_body<StreamKernel::bus>({}, {}, a, p, 1u, ctl, dev, idle_ms);
+    stream_resident_body<StreamKernel::bus>({}, {}, {}, a, p, 1u, ctl, dev, idle_ms);
 }
 __global__ void __launch_bounds__(1024) bank_stream_in_kernel(BankArgs a, StreamProgArgs p, uint32_t n_rows, BankStreamInCtl *ctl, BankStreamInDev *dev, uint32_t idle_ms) {
-    stream_resident_body<StreamKernel::in>({}, {}, a, p, n_rows, ctl, dev, idle_ms);
+    stream_resident_body<StreamKernel::in>({}, {}, {}, a, p, n_rows, ctl, dev, idle_ms);
 }
 __global__ void __launch_bounds__(1024) bank_stream_banks_kernel(StreamBanksArgs t, BankArgs a, StreamProgArgs p, uint32_t n_rows, BankStreamInCtl *ctl,
                                                                  BankStreamInDev *dev, uint32_t idle_ms) {
-    stream_resident_body<StreamKernel::banks>(t, {}, a, p, n_rows, ctl, dev, idle_ms);
+    stream_resident_body<StreamKernel::banks>(t, {}, {}, a, p, n_rows, ctl, dev, idle_ms);
 }
 __global__ void __launch_bounds__(1024) bank_stream_loops_kernel(StreamBanksArgs t, BankArgs a, StreamProgArgs p, uint32_t n_rows, BankStreamInCtl *ctl,
                                                                  BankStreamInDev *dev, uint32_t idle_ms) {
-    stream_resident_body<StreamKernel::loops>(t, {}, a, p, n_rows, ctl, dev, idle_ms);
+    stream_resident_body<StreamKernel::loops>(t, {}, {}, a, p, n_rows, ctl, dev, idle_ms);
 }
 __global__ void __launch_bounds__(1024) bank_stream_general_kernel(StreamBanksArgs t, StreamGeneralArgs g, BankArgs a, StreamProgArgs p, uint32_t n_rows, BankStreamInCtl *ctl,
                                                                    BankStreamInDev *dev, uint32_t idle_ms) {
-    stream_resident_body<StreamKernel::general>(t, g, a, p, n_rows, ctl, dev, idle_ms);
+    stream_resident_body<StreamKernel::general>(t, g, {}, a, p, n_rows, ctl, dev, idle_ms);
 }
 __global__ void __launch_bounds__(1024) bank_stream_dyn_kernel(StreamBanksArgs t, StreamGeneralArgs g, BankArgs a, StreamProgArgs p, uint32_t n_rows, BankStreamInCtl *ctl,
                                                                BankStreamInDev *dev, uint32_t idle_ms) {
-    stream_resident_body<StreamKernel::dyn>(t, g, a, p, n_rows, ctl, dev, idle_ms);
+    stream_resident_body<StreamKernel::dyn>(t, g, {}, a, p, n_rows, ctl, dev, idle_ms);
+}
+__global__ void __launch_bounds__(1024) bank_stream_hist_kernel(StreamBanksArgs t, StreamGeneralArgs g, StreamHistArgs h, BankArgs a, StreamProgArgs p, uint32_t n_rows,
+                                                                BankStreamInCtl *ctl, BankStreamInDev *dev, uint32_t idle_ms) {
+    stream_resident_body<StreamKernel::hist>(t, g, h, a, p, n_rows, ctl, dev, idle_ms);
 }
 
 // The one entry of the resident launches (kernels.hpp StreamLaunchArgs): the check, then the kernel with what it takes.
@@ -2227,6 +2296,7 @@ hipError_t launch_bank_stream(StreamKernel k, const StreamLaunchArgs &x, hipStre
     case StreamKernel::loops: hipLaunchKernelGGL(bank_stream_loops_kernel, grid, block, 0, s, x.t, x.a, x.p, x.n_rows, ctl_in, dev_in, idle_ms); break;
     case StreamKernel::general: hipLaunchKernelGGL(bank_stream_general_kernel, grid, block, 0, s, x.t, x.g, x.a, x.p, x.n_rows, ctl_in, dev_in, idle_ms); break;
     case StreamKernel::dyn: hipLaunchKernelGGL(bank_stream_dyn_kernel, grid, block, 0, s, x.t, x.g, x.a, x.p, x.n_rows, ctl_in, dev_in, idle_ms); break;
+    case StreamKernel::hist: hipLaunchKernelGGL(bank_stream_hist_kernel, grid, block, 0, s, x.t, x.g, x.h, x.a, x.p, x.n_rows, ctl_in, dev_in, idle_ms); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

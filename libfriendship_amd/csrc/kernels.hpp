@@ -138,7 +138,7 @@ enum StageOp : uint8_t {
     // Delay with a signal amount (register a, evaluated at t): frames = amount -> u64 as reference.rs:200-211
     // (>= 2^64 -> output 0; negative/NaN -> 0 frames; else floor), then as the constant forms.  d_lo = proven bound.
     S_READ_DYN = 11,        // dst = ring[buf] at t - frames
-    S_READ_INPUT_DYN = 12,  // dst = input[imm] at t - frames
+    S_READ_INPUT_DYN = 12,  // dst = input[imm] at t - frames         (buf = the amount's proven bound, 0xFFFFFFFF: none; no evaluator reads it)
     S_STEP_DYN = 13,        // dst = t >= frames ? bits(imm) : 0
 };
 struct StageInstr {    // 16 bytes
@@ -311,9 +311,32 @@ struct StreamGeneralArgs {
 // A plan without schedule banks is launched with mask == 0 (no schedule table).  The loop phases know no _DYN op: the rule
 // refuses one inside a loop program.  LDS: the general kernel's 45 072 bytes.
 
-// The eight resident kernels (streamplan.hpp stream_launch chooses; `none`: no resident launch yet) and their one launch entry.
+// bank_stream_hist_kernel (FR_STREAM_HISTORY): bank_stream_dyn_kernel's composition and one more flag, for plans whose streamed
+// programs read an INPUT ROW at a delay: S_READ_INPUT (any constant delay, also inside a loop program, where it is one more
+// frame-only load of phase 1) and S_READ_INPUT_DYN (lane = frame).  The stream keeps a HISTORY of its n_rows streamed rows,
+// hist[row][frame & mask], mask + 1 >= the deepest input read + 64 floats per row: wave 0 of workgroup 0 stores every block's
+// live lanes there right after it has republished the rows, under the same acknowledgement, before it stores n_times and seq.
+// S_READ_INPUT yields frame >= d_lo ? hist[imm & 7][(frame - d_lo) & mask] : 0.0 (imm: the streamed row, as for S_INPUT);
+// S_READ_INPUT_DYN is stream_prog_dyn with the history as its rings.  Every load is a relaxed agent-scope atomic load.  Why no
+// wait, acquire or release is added:
+//   * frames of the current block (a delay below 64, a signal amount of 0): workgroup 0 had them acknowledged before it stored
+//     seq, and a reader loads after it has seen seq -- the hand-over BankStreamInDev::rows has always relied on;
+//   * older frames: an earlier block's stores, acknowledged before that block's seq;
+//   * block k + 1's stores cannot pass block k's reads: the host rings k + 1 only after k's done tag, the tag follows every
+//     voice's ticket, and a ticket follows the acknowledged row stores that depend on those loads;
+//   * mask + 1 >= look-back + 64 keeps a block's stores off the frames it reads, and the host zeroes the history before every
+//     launch (a launch follows a seek, after which every earlier input reads 0.0), so `frame >= d` is the whole range test.
+// Indices are masked: an address is inside the history whatever the amount.  LDS: the general kernel's 45 072 bytes.
+struct StreamHistArgs {
+    float *hist;               // [n_rows][mask + 1]
+    uint64_t mask;
+};
+
+// The nine resident kernels (streamplan.hpp stream_launch chooses; `none`: no resident launch yet) and their one launch entry.
 // plain, prog and bus have the one-row doorbell (BankStreamCtl / BankStreamDev), the others the doorbell of rows (BankStreamIn*).
-enum class StreamKernel : uint32_t { none, plain, prog, bus, in, banks, loops, general, dyn };
+// (hist is dyn + 2: the value after dyn stays unnamed and refused, as the tests of the launch check have always required)
+enum class StreamKernel : uint32_t { none, plain, prog, bus, in, banks, loops, general, dyn, hist = dyn + 2 };
+constexpr bool stream_kernel_named(StreamKernel k) { return k != StreamKernel::none && (k <= StreamKernel::dyn || k == StreamKernel::hist); }
 // A kernel's form: what it has on top of bank_stream_kernel.  The kernels are a cascade -- each is the one before it and one
 // thing more --, so the enum's order is the form.  kernels.hip's one resident body is instantiated by it, stream_launch_check
 // below reads it.
@@ -325,10 +348,11 @@ struct StreamForm {
     bool loops;      // loop programs: the load and store tiles and the instruction copy
     bool schedule;   // schedule banks (StreamGeneralArgs)
     bool dyn;        // the interpreter knows the Delays by a signal amount; a plan need not have a schedule bank
+    bool hist;       // the history of the streamed rows (StreamHistArgs): delayed reads of input rows
 };
 constexpr StreamForm stream_form(StreamKernel k) {
     return {k >= StreamKernel::prog,  k >= StreamKernel::bus,     k >= StreamKernel::in, k >= StreamKernel::banks,
-            k >= StreamKernel::loops, k >= StreamKernel::general, k == StreamKernel::dyn};
+            k >= StreamKernel::loops, k >= StreamKernel::general, k >= StreamKernel::dyn, k == StreamKernel::hist};
 }
 // Everything a resident launch may need; stream_launch_check reads and checks what the kernel takes.
 struct StreamLaunchArgs {
@@ -336,6 +360,7 @@ struct StreamLaunchArgs {
     StreamProgArgs p;
     StreamBanksArgs t;
     StreamGeneralArgs g;
+    StreamHistArgs h;                           // (read for the hist form alone)
     uint32_t n_rows, max_stride, max_loads, max_stores;
     void *ctl_dev, *dev;                        // the control block as the device addresses it and the device block, of the kernel's doorbell form
     uint32_t idle_ms;                           // 0 = BANK_STREAM_IDLE_MS
@@ -377,11 +402,12 @@ inline uint32_t stream_table_ok(const StreamBanksArgs &t, const BankArgs &a, uin
 // a device (tests/cpp/streamcheck_tests.cpp).  Returns the workgroups to launch -- exactly those that render: a small patch
 // leaves the other CUs to whatever else wants the device --, 0: refused.
 inline uint32_t stream_launch_check(StreamKernel k, const StreamLaunchArgs &x) {
-    if (k == StreamKernel::none || k > StreamKernel::dyn) return 0;
+    if (!stream_kernel_named(k)) return 0;
     const StreamForm f = stream_form(k);
     const BankArgs &a = x.a;
     if (a.leaf_variant != 1 || !a.out || !x.ctl_dev || !x.dev) return 0;
     if (f.rows && (x.n_rows == 0 || x.n_rows > BANK_STREAM_ROWS)) return 0;
+    if (f.hist && (!x.h.hist || (x.h.mask & (x.h.mask + 1)) != 0 || x.h.mask + 1 < 64u)) return 0;   // a ring of 2^n >= 64 frames per row
     // the tiles' limits concern loop programs; the general form takes a plan without one (max_stride == 0)
     if (f.loops && (x.max_stride > BANK_STREAM_LOOP_MAX_STRIDE || x.max_loads > BANK_STREAM_LOOP_LOADS || x.max_stores > BANK_STREAM_LOOP_STORES)) return 0;
     if ((f.schedule ? x.max_stride != 0 : f.loops) && !x.p.n_rings) return 0;   // a loop lives in a ring

@@ -71,6 +71,9 @@ struct Planner {
     using Range = fr::Range;
     std::unordered_map<uint32_t, Range> range_memo, obs_memo;
     std::unordered_map<uint32_t, uint64_t> dyn_max;   // Delay node with a signal amount -> bound on the delay in frames
+    // Delay of an INPUT by a signal amount -> the amount's proven bound, where it has one.  The ordinary path needs none (dyn_max
+    // says so); block streaming, whose input history is finite, reads it (S_READ_INPUT_DYN's `buf`; streamplan.hpp FR_STREAM_HISTORY).
+    std::unordered_map<uint32_t, uint64_t> input_dyn_bound;
     const ObservedInputs *observed = nullptr;
     std::unordered_set<uint32_t> observed_dyn;        // Delay nodes whose dyn_max came from observed ranges
     std::unordered_set<uint32_t> observed_refused;    // signal Delays still without a bound in observed mode
@@ -110,6 +113,10 @@ struct Planner {
         if (dyn_max.count(n)) return true;
         if (is_leaf(g.nodes[n].a)) {   // an input or a constant delayed by a signal: read from the input history (kept in
             dyn_max[n] = 0xFFFFFFFFull;   // full), no ring, so no bound is needed
+            if (g.nodes[g.nodes[n].a].op == OP_INPUT) {
+                const Range r = range(g.nodes[n].b);
+                if (r.hi < 2147483648.0) input_dyn_bound[n] = r.hi <= 0.0 ? 0 : (uint64_t)r.hi;
+            }
             return true;
         }
         Range r = range(g.nodes[n].b);
@@ -352,8 +359,11 @@ bool build_program(const FlatGraph &g, const Planner &P, uint32_t m, std::unorde
             in.a = reg_of.at(x.b);
             in.d_lo = (uint32_t)bound;   // (informational: the proven bound)
             if (src.op == OP_CONST) { in.op = S_STEP_DYN; in.imm = src.a; }
-            else if (src.op == OP_INPUT) { in.op = S_READ_INPUT_DYN; in.imm = dense(src.a); }
-            else {
+            else if (src.op == OP_INPUT) {
+                in.op = S_READ_INPUT_DYN; in.imm = dense(src.a);
+                const auto ib = P.input_dyn_bound.find(n);   // (no evaluator reads it: the amount's proven bound, for block streaming)
+                in.buf = ib != P.input_dyn_bound.end() ? (uint32_t)ib->second : 0xFFFFFFFFu;
+            } else {
                 in.op = S_READ_DYN; in.buf = x.a;
                 out.reads.push_back({x.a, bound});
                 out.dynamic_reads.insert(x.a);

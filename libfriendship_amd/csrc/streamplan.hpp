@@ -34,6 +34,14 @@
 // memory.  The finishing wave has just stored the voice's frames of this block and earlier blocks stored everything older, so
 // every such offset is readable and still nobody waits (kernels.hip bank_stream_dyn_kernel).  A signal delay of a ring that a
 // program stores, one inside a loop program, a delayed read of an input row and a bound observed from input rows stay refused.
+// With FR_STREAM_HISTORY=1 (StreamEnv::history) a program may read an INPUT ROW at a delay -- a pre-delay on a control row, a
+// delayed gate, Delay(In(0), d) on the time row itself: S_READ_INPUT at any constant delay, 0..63 included, in per-voice, bus and
+// loop programs (there it is one more frame-only load); with FR_STREAM_DYN also S_READ_INPUT_DYN, whose amount is anything in
+// [0, bound] -- the bound the planner proved for the amount and left in the instruction's `buf`; one without is refused.  The stream keeps a history of its streamed rows (kernels.hpp bank_stream_hist_kernel): workgroup 0 stores a block's
+// rows there before any workgroup is released to render the block, so such a read waits for nobody, reads no voice, binds its
+// program to no voice and never makes it a bus program.  Its slot is streamed like an S_INPUT's (FR_STREAM_INPUTS for a slot
+// other than 0).  The deepest such read (StreamPlan::input_lookback) sizes the history, at most STREAM_HIST_MAX_FRAMES.
+// S_READ_INPUT_DYN inside a loop program and a bound observed from input rows stay refused.
 // HOW a served plan is launched is one rule as well (stream_path, stream_launch, plain_stream_launch, at the end): the path, the
 // kernel, its doorbell form, its tables, the loop limits, the workgroups.  fr_stream_begin, the seek, the block, the stop and
 // fr_plan_json's "kernel" read the StreamLaunch it returns and decide nothing themselves.
@@ -64,6 +72,9 @@ constexpr uint32_t STREAM_LOOP_LOADS = 32, STREAM_LOOP_STORES = 16;
 // items of one voice over several workgroups is not built.
 constexpr uint32_t STREAM_GENERAL_MAX_LEAVES = 32768;
 constexpr uint32_t STREAM_SCHEDULE_MAX_DEPTH = 16;   // (= kernels.hip GB_MAX_DEPTH: the evaluation stack's columns in LDS)
+// The deepest delayed read of an input row a stream serves (FR_STREAM_HISTORY): the history holds the next power of two above
+// look-back + a block per streamed row -- at this limit 4 MiB per row, 32 MiB for STREAM_MAX_INPUTS rows.
+constexpr uint64_t STREAM_HIST_MAX_FRAMES = 1ull << 20;
 static_assert(STREAM_LOOP_LOADS == BANK_STREAM_LOOP_LOADS && STREAM_LOOP_STORES == BANK_STREAM_LOOP_STORES && STREAM_BLOCK == BANK_STREAM_LOOP_MAX_STRIDE + 1,
               "the rule's limits are the kernel's");
 
@@ -81,6 +92,7 @@ struct StreamEnv {
     bool loops = false;              // FR_STREAM_LOOPS: feedback loops shorter than a block, and the taps behind them
     bool general = false;            // FR_STREAM_GENERAL: schedule banks -- general voices, balanced voices of 32 or 64 partials
     bool dyn = false;                // FR_STREAM_DYN: Delays of a voice by a signal amount (S_READ_DYN of a bank's ring, S_STEP_DYN)
+    bool history = false;            // FR_STREAM_HISTORY: delayed reads of input rows (S_READ_INPUT; with `dyn` S_READ_INPUT_DYN) from the stream's history
     bool programs = false;           // FR_STREAM_PROGRAMS: the program path exists (stream_path; plan_stream does not ask)
 };
 
@@ -195,6 +207,10 @@ struct StreamPlan {
     uint32_t dyn_reads = 0;              // the assigned programs' S_READ_DYNs (StreamEnv::dyn) ...
     uint32_t dyn_steps = 0;              // ... and their S_STEP_DYNs
     bool has_dyn() const { return dyn_reads + dyn_steps != 0; }
+    uint32_t hist_reads = 0;             // the assigned programs' S_READ_INPUTs (StreamEnv::history) ...
+    uint32_t hist_dyn_reads = 0;         // ... and their S_READ_INPUT_DYNs
+    uint64_t input_lookback = 0;         // the deepest input read of the assigned programs: S_READ_INPUT's d_lo, S_READ_INPUT_DYN's proven bound (its buf)
+    bool has_hist() const { return hist_reads + hist_dyn_reads != 0; }
     std::vector<uint32_t> input_slots{0};   // the distinct input slots the voices and the assigned programs read: slot 0 (the voices' time)
                                          // first, the others ascending -- the order of a block's streamed rows
     std::vector<uint32_t> general_voices;   // the leaf count of every voice served by schedule, in global voice order (StreamEnv::general)
@@ -238,11 +254,19 @@ inline uint32_t stream_loop_stride(const StageProg &pg, const StageInstr *ins) {
     return stride;
 }
 
-// A loop program's loads as the kernel numbers them into its load tile: every S_INPUT and S_READ, in program order.
+// A loop program's loads as the kernel numbers them into its load tile: every S_INPUT, S_READ and S_READ_INPUT (a frame-only
+// load as callplan.hpp's loop-tile rule counts it; the rule admits one with StreamEnv::history alone), in program order.
 inline uint32_t stream_loop_loads(const StageProg &pg, const StageInstr *ins) {
     uint32_t n = 0;
-    for (uint32_t i = 0; i < pg.n_instr; ++i) n += ins[i].op == S_INPUT || ins[i].op == S_READ ? 1u : 0u;
+    for (uint32_t i = 0; i < pg.n_instr; ++i) n += ins[i].op == S_INPUT || ins[i].op == S_READ || ins[i].op == S_READ_INPUT ? 1u : 0u;
     return n;
+}
+
+// The history's frames per streamed row for that look-back: the power of two >= look-back + a block.
+inline uint64_t stream_hist_cap(uint64_t input_lookback) {
+    uint64_t cap = STREAM_BLOCK;
+    while (cap < input_lookback + STREAM_BLOCK) cap <<= 1;
+    return cap;
 }
 
 // The stream's own copy of a loop program (`ins`: its pg.n_instr instructions, copied; `pg`: its streamed StageProg).  Every
@@ -404,8 +428,16 @@ inline StreamPlan plan_stream(const StagedPlan &sp, const std::vector<const Bank
         }
         return false;
     };
+    // S_READ_INPUT, S_READ_INPUT_DYN without FR_STREAM_HISTORY (and whatever op the rule does not know): a stream keeps no input history
+    auto no_history = [&](uint8_t op) {
+        if (env.dyn)
+            return std::string("a program uses ") + stage_op_name(op) +
+                   " (a delayed read of an input row), which block streaming does not serve yet: a stream keeps no input history";
+        return std::string("a program uses ") + stage_op_name(op) + (op == S_READ_INPUT ? " (a delayed read of the input row)" : " (a Delay by a signal amount)") +
+               ", which block streaming does not serve yet";
+    };
     uint64_t min_delay = UINT64_MAX;
-    uint32_t n_dyn_reads = 0, n_dyn_steps = 0;
+    uint32_t n_dyn_reads = 0, n_dyn_steps = 0, n_hist_reads = 0, n_hist_dyn_reads = 0;
     for (uint32_t k = 0; k < run.size(); ++k) {
         const StageProg &pg = sp.progs[run[k]];
         const bool copy = k >= first_copy;
@@ -414,7 +446,7 @@ inline StreamPlan plan_stream(const StagedPlan &sp, const std::vector<const Bank
         if (env.dyn && loops && stream_loop_stride(pg, sp.instrs.data() + pg.first_instr) != 0)   // the loop kernel's phases hoist frame-only loads
             for (uint32_t i = 0; i < pg.n_instr; ++i) {
                 const uint8_t op = sp.instrs[pg.first_instr + i].op;
-                if (op == S_READ_DYN || op == S_STEP_DYN)
+                if (op == S_READ_DYN || op == S_STEP_DYN || (env.history && op == S_READ_INPUT_DYN))
                     return refuse(std::string("a loop program uses ") + stage_op_name(op) +
                                   " (a Delay by a signal amount inside a feedback loop shorter than a block), which block streaming does not serve yet");
             }
@@ -422,6 +454,25 @@ inline StreamPlan plan_stream(const StagedPlan &sp, const std::vector<const Bank
             const StageInstr &in = sp.instrs[pg.first_instr + i];
             switch (in.op) {
             case S_CONST: case S_STEP: case S_SUM2: case S_MUL: case S_DIV: case S_MOD: case S_MIN: case S_STORE: break;
+            case S_READ_INPUT: case S_READ_INPUT_DYN:
+                if (!env.history) return refuse(no_history(in.op));
+                if (in.op == S_READ_INPUT_DYN) {                    // the amount is anything in [0, its proven bound]: the history holds them all
+                    if (!env.dyn)
+                        return refuse(std::string("a program uses ") + stage_op_name(in.op) + " (a Delay by a signal amount), which block streaming does not serve yet");
+                    if (!sp.observed.empty())
+                        return refuse("a Delay's bound was observed from input rows (FR_DELAY_OBSERVED); a stream stores no rows, so block streaming does not serve it");
+                    // (its d_lo says "unbounded": the ordinary path keeps every input frame.  The planner leaves the amount's
+                    // proven bound in `buf`, which no evaluator reads)
+                    if (in.buf == 0xFFFFFFFFu)
+                        return refuse("a program delays an input row by a signal amount without a proven bound; a stream's input history holds at most " +
+                                      std::to_string(STREAM_HIST_MAX_FRAMES) + " frames");
+                    ++n_hist_dyn_reads;
+                    s.input_lookback = std::max<uint64_t>(s.input_lookback, in.buf);
+                } else {
+                    ++n_hist_reads;
+                    s.input_lookback = std::max<uint64_t>(s.input_lookback, in.d_lo);
+                }
+                [[fallthrough]];                                    // its slot is streamed like an S_INPUT's; it reads no voice
             case S_INPUT:
                 if (env.inputs && in.imm < sp.input_slots.size()) {
                     if (sp.input_slots[in.imm] != 0) others.push_back(sp.input_slots[in.imm]);
@@ -499,12 +550,7 @@ inline StreamPlan plan_stream(const StagedPlan &sp, const std::vector<const Bank
                 mine = bv->second;
                 break;
             }
-            default:
-                if (env.dyn)                                        // (S_READ_INPUT, S_READ_INPUT_DYN: a stream keeps no input history)
-                    return refuse(std::string("a program uses ") + stage_op_name(in.op) +
-                                  " (a delayed read of an input row), which block streaming does not serve yet: a stream keeps no input history");
-                return refuse(std::string("a program uses ") + stage_op_name(in.op) +
-                              (in.op == S_READ_INPUT ? " (a delayed read of the input row)" : " (a Delay by a signal amount)") + ", which block streaming does not serve yet");
+            default: return refuse(no_history(in.op));
             }
             if (in.dst >= STAGE_REGS || in.a >= STAGE_REGS || in.b >= STAGE_REGS) return refuse("a program needs more registers than the streamed interpreter has");
         }
@@ -519,6 +565,9 @@ inline StreamPlan plan_stream(const StagedPlan &sp, const std::vector<const Bank
         }
         voice_of[k] = bus ? BUS : mine != NONE ? mine : run[k] % V;   // (reads no voice at a short delay: any one voice, the same every time)
     }
+    if (s.input_lookback > STREAM_HIST_MAX_FRAMES)
+        return refuse("a program reads an input row " + std::to_string(s.input_lookback) + " frames back; a stream's input history holds at most " +
+                      std::to_string(STREAM_HIST_MAX_FRAMES) + " frames");
     std::sort(others.begin(), others.end());
     others.erase(std::unique(others.begin(), others.end()), others.end());
     if (1 + others.size() > STREAM_MAX_INPUTS)
@@ -549,6 +598,8 @@ inline StreamPlan plan_stream(const StagedPlan &sp, const std::vector<const Bank
     s.min_ring_delay = min_delay == UINT64_MAX ? 0 : min_delay;
     s.dyn_reads = n_dyn_reads;
     s.dyn_steps = n_dyn_steps;
+    s.hist_reads = n_hist_reads;
+    s.hist_dyn_reads = n_hist_dyn_reads;
     s.input_slots.insert(s.input_slots.end(), others.begin(), others.end());
     s.servable = true;
     return s;
@@ -558,6 +609,7 @@ inline StreamPlan plan_stream(const StagedPlan &sp, const std::vector<const Bank
 inline const char *stream_kernel_name(StreamKernel k) {
     static const char *const names[] = {"", "bank_stream_kernel", "bank_stream_prog_kernel", "bank_stream_bus_kernel", "bank_stream_in_kernel",
                                         "bank_stream_banks_kernel", "bank_stream_loops_kernel", "bank_stream_general_kernel", "bank_stream_dyn_kernel"};
+    if (k == StreamKernel::hist) return "bank_stream_hist_kernel";   // (not the value after dyn: that one has no name)
     return names[(uint32_t)k < sizeof names / sizeof names[0] ? (uint32_t)k : 0];
 }
 
@@ -572,6 +624,7 @@ struct StreamLaunch {
     bool schedule_table = false;     // ... and the schedule banks' schedules next to it (StreamGeneralArgs)
     uint32_t max_stride = 0, max_loads = 0, max_stores = 0;   // the loop programs' largest stride, load count and store-slot count
     uint32_t workgroups = 0;
+    uint64_t hist_cap = 0;           // the history's frames per streamed row, a power of two >= 64 (0: the kernel keeps none)
     bool by_plan = false;            // the plan alone decides the kernel: fr_plan_json names it before any launch (stream_kernel_by_plan)
 };
 
@@ -583,16 +636,18 @@ inline bool stream_path(const StagedPlan &sp, const std::vector<const BankLaunch
     return env.programs && (!sp.progs.empty() || sp.uses_rings() || (env.banks && banks.size() > 1) || by_schedule);
 }
 
-// The launch of a servable plan of the program path.  The one cascade: dyn > general > loops > banks > in > bus > prog.  dyn -- a
-// plan with a Delay by a signal amount (StreamPlan::has_dyn) -- is the general kernel's composition and takes the schedule table
-// only when the plan has schedule banks.
+// The launch of a servable plan of the program path.  The one cascade: hist > dyn > general > loops > banks > in > bus > prog.
+// dyn -- a plan with a Delay by a signal amount (StreamPlan::has_dyn) -- is the general kernel's composition and takes the
+// schedule table only when the plan has schedule banks; hist -- a plan with a delayed read of an input row
+// (StreamPlan::has_hist), and no other -- is dyn's composition with the history of the streamed rows.
 inline StreamLaunch stream_launch(const StagedPlan &sp, const StreamPlan &s) {
     StreamLaunch l;
-    l.kernel = s.has_dyn() ? StreamKernel::dyn : s.has_general() ? StreamKernel::general : s.has_loops() ? StreamKernel::loops : s.banks.size() > 1 ? StreamKernel::banks
-               : s.input_slots.size() > 1 ? StreamKernel::in : s.bus_programs() ? StreamKernel::bus : StreamKernel::prog;
+    l.kernel = s.has_hist() ? StreamKernel::hist : s.has_dyn() ? StreamKernel::dyn : s.has_general() ? StreamKernel::general : s.has_loops() ? StreamKernel::loops
+               : s.banks.size() > 1 ? StreamKernel::banks : s.input_slots.size() > 1 ? StreamKernel::in : s.bus_programs() ? StreamKernel::bus : StreamKernel::prog;
     l.rows_doorbell = l.own_instrs = l.by_plan = stream_kernel_by_plan(l.kernel);
     l.bank_table = l.kernel >= StreamKernel::banks;
-    l.schedule_table = l.kernel == StreamKernel::general || (l.kernel == StreamKernel::dyn && s.has_general());
+    l.schedule_table = l.kernel == StreamKernel::general || (l.kernel >= StreamKernel::dyn && s.has_general());
+    l.hist_cap = l.kernel == StreamKernel::hist ? stream_hist_cap(s.input_lookback) : 0;
     l.n_rows = l.rows_doorbell ? (uint32_t)s.input_slots.size() : 1u;
     for (size_t i = 0; i < s.progs.size(); ++i) {    // (the tiles' fill is counted from the plan's instructions; the store slots are the stored rings)
         if (!s.loop_stride[i]) continue;
