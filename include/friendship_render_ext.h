@@ -144,7 +144,25 @@ extern "C" {
  * streamed programs' delayed reads of input rows by a constant and by a signal amount) and "input_lookback" (the deepest of
  * them); "kernel" is "bank_stream_hist_kernel" exactly when there is such a read.  Still refused, each with its reason: a
  * signal delay of an input row without FR_STREAM_DYN, without a proven bound, inside a feedback loop shorter than a block, or
- * next to a bound observed from input rows; a read further back than the limit; a patch without a voice.
+ * next to a bound observed from input rows; a read further back than the limit; a patch without a voice (FR_STREAM_EFFECTS
+ * below).
+ *
+ * FR_STREAM_EFFECTS = 0 / 1 (default 0; read strictly from the environment too; does nothing unless FR_STREAM_PROGRAMS=1):
+ * block streaming also serves a PATCH WITHOUT A VOICE -- no oscillator bank at all: an echo, a comb or a flanger on a row the
+ * host feeds in, a gain or a minimum of two control rows, a one-pole smoother on a knob.  Its stage programs are dealt over
+ * SEGMENTS, one workgroup of one wave each, in a tenth resident kernel (bank_stream_fx_kernel): every program gets a group in
+ * the order the programs run; a program that reads an earlier program's delay line less than a block back (the tap behind a
+ * loop, FR_STREAM_LOOPS) or copies it to a row follows that program's group; one that would follow two groups is a mix bus
+ * (FR_STREAM_BUS) and runs after every segment has finished; group g runs in segment g mod segments, segments = min(groups,
+ * the device's workgroups), so no patch is refused for its number of rows.  Every other rule applies to these programs as to a
+ * voice's: slots other than 0 need FR_STREAM_INPUTS (slot 0 stays row 0 of every block), loops shorter than a block
+ * FR_STREAM_LOOPS, delayed reads of input rows FR_STREAM_HISTORY, signal amounts FR_STREAM_DYN; same bits as fr_fill_buffer,
+ * in both semantics.  With 0 nothing changes: such a patch is refused with "block streaming needs a plan with one voice bank
+ * (this one: 0 bank launches)", and every other plan is served and refused, with the same reasons, by the same kernels.
+ * "stream" gains "segments" (0 for a plan with voices); for a patch without a voice "voices" is 0, "programs_per_voice" lists
+ * the programs of each segment and "kernel" is "bank_stream_fx_kernel".  Still refused, each with its reason: a patch with
+ * neither voices nor programs; a feed-forward delay shorter than a block of a computed value (no fused form) and a signal
+ * delay of one; a program that needs two groups without FR_STREAM_BUS.
  */
 typedef struct fr_option {
     const char *name;              /* e.g. "FR_BANK_SHORT" */

@@ -197,7 +197,7 @@ static std::string stage_variant(const StageLaunchNote &n, const Plan &p) {
     return k;
 }
 
-constexpr size_t N_OPTIONS = 39;        // per-renderer options (friendship_render_ext.h; the table below fr_renderer)
+constexpr size_t N_OPTIONS = 40;        // per-renderer options (friendship_render_ext.h; the table below fr_renderer)
 
 struct TimerClass {
     double ms = 0;
@@ -553,9 +553,9 @@ struct fr_renderer {
         }
         return d_tickets.as<uint32_t>();
     }
-    // FR_STREAM_PROGRAMS, _BUS, _INPUTS, _LOOPS, _BANKS, _GENERAL, _DYN, _HISTORY (the options table says what each serves; streamplan.hpp StreamEnv)
+    // FR_STREAM_PROGRAMS, _BUS, _INPUTS, _LOOPS, _BANKS, _GENERAL, _DYN, _HISTORY, _EFFECTS (the options table says what each serves; streamplan.hpp StreamEnv)
     bool stream_programs = false, stream_bus = false, stream_inputs = false, stream_loops = false, stream_banks = false, stream_general = false, stream_dyn = false,
-         stream_history = false;
+         stream_history = false, stream_effects = false;
     std::vector<const BankLaunch *> stream_bank_list() const {
         std::vector<const BankLaunch *> banks;
         for (const BankStage &bs : plan.banks) banks.push_back(&bs.grp);
@@ -572,6 +572,7 @@ struct fr_renderer {
         env.programs = stream_programs; env.bus = stream_bus; env.inputs = stream_inputs;
         env.banks = stream_banks; env.loops = stream_loops; env.general = stream_general; env.dyn = stream_dyn;
         env.history = stream_history;
+        env.effects = stream_effects;
         return env;
     }
     StreamPlan plan_stream_now() const { return plan_stream(plan.sp, stream_bank_list(), stream_env()); }
@@ -2214,6 +2215,9 @@ void fr_renderer::begin_program_stream(uint32_t n_slots) {
         }
     }
     if (s.banks.size() != plan.banks.size() || s.banks.size() > BANK_STREAM_BANKS) throw Error(FR_ERR_DEVICE, "internal: the stream's banks are not the plan's");
+    // a plan without a voice (FR_STREAM_EFFECTS): its segments are the launch's workgroups, one wave each; no parameters, workspace or tickets
+    if ((s.voices == 0) != (s.segments != 0) || (s.segments && (!plan.banks.empty() || s.voice_first.size() != (size_t)s.segments + 2 || s.segments > BANK_STREAM_WGS)))
+        throw Error(FR_ERR_DEVICE, "internal: a stream with neither voices nor segments");
     for (size_t i = 0; i < plan.banks.size(); ++i) {
         const BankLaunch &grp = plan.banks[i].grp;
         if (grp.rows.size() != s.banks[i].voices) throw Error(FR_ERR_DEVICE, "internal: the stream's banks are not the plan's");
@@ -2340,7 +2344,8 @@ void fr_renderer::seek_program_stream(uint64_t idx) {
         s.banks.size() != plan.banks.size())
         throw Error(FR_ERR_DEVICE, "internal: the rings do not hold a streamed block's look-back");
     StreamLaunchArgs x{};
-    x.a = stream_bank_args(l.bank_table ? nullptr : &plan.banks[0], s.voices, s.chunk_log2, s.chunks);
+    const bool voiceless = s.voices == 0;                        // FR_STREAM_EFFECTS: n_voices = the segments, and `out`; no bank
+    x.a = voiceless ? stream_bank_args(nullptr, s.segments, 0, 1) : stream_bank_args(l.bank_table ? nullptr : &plan.banks[0], s.voices, s.chunk_log2, s.chunks);
     StreamProgArgs &p = x.p;
     p.instrs = l.own_instrs ? strm.d_instrs.as<StageInstr>() : plan.d_instrs.as<StageInstr>();
     p.progs = strm.d_progs.as<StageProg>();
@@ -2350,7 +2355,7 @@ void fr_renderer::seek_program_stream(uint64_t idx) {
     p.n_rings = sp.n_rings;
     p.n_rows = n_slots;
     p.head = idx;
-    p.bank_to_ring = !l.bank_table && plan.banks[0].grp.to_ring ? 1u : 0u;   // (a bank table: each bank has its own)
+    p.bank_to_ring = !l.bank_table && !voiceless && plan.banks[0].grp.to_ring ? 1u : 0u;   // (a bank table: each bank has its own)
     p.sparkle = mirror.sparkle ? 1u : 0u;
     if (l.hist_cap) {                                            // every frame before idx reads 0.0 after a seek: an empty history, on the launch's stream
         const size_t bytes = (size_t)l.n_rows * l.hist_cap * sizeof(float);
@@ -2452,6 +2457,7 @@ int64_t env_strict_stream_loops(const char *e);
 int64_t env_strict_stream_general(const char *e);
 int64_t env_strict_stream_dyn(const char *e);
 int64_t env_strict_stream_history(const char *e);
+int64_t env_strict_stream_effects(const char *e);
 bool parse_option(const Knob &k, const char *s, int64_t &v);
 
 const Knob kKnobs[] = {
@@ -2555,6 +2561,10 @@ const Knob kKnobs[] = {
     // FR_STREAM_DYN by a signal amount -- from a history of the streamed rows (streamplan.hpp StreamEnv::history; fr_plan_json:
     // stream.hist_reads, stream.input_lookback).  Inert without FR_STREAM_PROGRAMS.  Strict and listed once set.
     {"FR_STREAM_HISTORY", 0, 0, 1, 0, nullptr, 0, env_strict_stream_history, [](fr_renderer &r, int64_t v, bool) { r.stream_history = v != 0; }, LISTED_WHEN_SET},
+    // Patches without a voice in block streaming -- an echo, a comb or a flanger on a row the host feeds in, a gain on a control
+    // row, a one-pole smoother on a knob: the programs are dealt over segments, one wave each (streamplan.hpp StreamEnv::effects;
+    // fr_plan_json: stream.segments).  Inert without FR_STREAM_PROGRAMS.  Strict and listed once set.
+    {"FR_STREAM_EFFECTS", 0, 0, 1, 0, nullptr, 0, env_strict_stream_effects, [](fr_renderer &r, int64_t v, bool) { r.stream_effects = v != 0; }, LISTED_WHEN_SET},
 };
 static_assert(sizeof kKnobs / sizeof kKnobs[0] == N_OPTIONS, "N_OPTIONS counts the rows of kKnobs");
 
@@ -2575,6 +2585,7 @@ int64_t env_strict_stream_loops(const char *e) { return env_strict("FR_STREAM_LO
 int64_t env_strict_stream_general(const char *e) { return env_strict("FR_STREAM_GENERAL", e); }
 int64_t env_strict_stream_dyn(const char *e) { return env_strict("FR_STREAM_DYN", e); }
 int64_t env_strict_stream_history(const char *e) { return env_strict("FR_STREAM_HISTORY", e); }
+int64_t env_strict_stream_effects(const char *e) { return env_strict("FR_STREAM_EFFECTS", e); }
 
 bool parse_option(const Knob &k, const char *s, int64_t &v) {
     if (k.word && std::strcmp(s, k.word) == 0) {
@@ -3213,6 +3224,8 @@ const char *fr_plan_json(fr_renderer *r) {
             if (r->stream_history)                               // FR_STREAM_HISTORY: the assigned programs' delayed reads of input rows, and the deepest of them
                 r->plan_json_cache += ",\"hist_reads\":" + std::to_string(s.hist_reads) + ",\"hist_dyn_reads\":" + std::to_string(s.hist_dyn_reads) +
                                       ",\"input_lookback\":" + std::to_string(s.input_lookback);
+            if (r->stream_effects)                               // FR_STREAM_EFFECTS: the workgroups a plan without a voice is dealt over (0: it has voices)
+                r->plan_json_cache += ",\"segments\":" + std::to_string(s.segments);
             const StreamLaunch l = s.servable ? stream_launch(r->plan.sp, s) : StreamLaunch{};
             const char *kernel = stream_kernel_name(l.by_plan ? l.kernel : stream_kernel_by_plan(r->strm.last_kernel) ? StreamKernel::none : r->strm.last_kernel);
             if (r->stream_banks) {                               // FR_STREAM_BANKS: the banks of the launch, in plan order
@@ -3221,7 +3234,7 @@ const char *fr_plan_json(fr_renderer *r) {
                     bl += std::string(bl.empty() ? "" : ",") + "{\"voices\":" + std::to_string(b.voices) + ",\"partials\":" + std::to_string(b.general ? b.max_leaves : 1u << b.log2_p) +
                           ",\"chunks\":" + std::to_string(1u << (b.log2_p - b.chunk_log2)) + ",\"to_ring\":" + (b.to_ring ? "true" : "false") +
                           (r->stream_general ? std::string(",\"general\":") + (b.general ? "true" : "false") : std::string()) + "}";
-                r->plan_json_cache += ",\"banks\":[" + bl + "],\"workgroups\":" + std::to_string(s.workgroups()) +
+                r->plan_json_cache += ",\"banks\":[" + bl + "],\"workgroups\":" + std::to_string(s.servable && s.voices == 0 ? s.segments : s.workgroups()) +   // (without a voice: the segments)
                                       ",\"max_workgroups\":" + std::to_string(stream_max_wgs((uint32_t)std::max(r->device_cus, 0)));
             }
             r->plan_json_cache += std::string(",\"kernel\":\"") + kernel + "\"}";

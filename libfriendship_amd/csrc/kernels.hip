@@ -788,7 +788,7 @@ static hipError_t launch_bank_short(const BankArgs &a, hipStream_t s) {
 
 // ---------------------------------------------------------------------------------------------------
 // Block streaming: the short-call kernel as ONE resident launch (kernels.hpp, BankStreamCtl).  Each step of the protocol is
-// written once, in this section; the skeleton that calls the steps -- stream_resident_body, of which the nine resident
+// written once, in this section; the skeleton that calls the steps -- stream_resident_body, of which the ten resident
 // kernels are instantiations -- follows stage_kernel, whose interpreter's types it uses.
 //
 // A block.  The host rings a doorbell in mapped pinned memory: every word carries a sample and the block's tag.  Wave 0 of
@@ -2067,7 +2067,7 @@ hipError_t launch_stage(const StageArgs &a, hipStream_t s) {
 }
 
 // ---------------------------------------------------------------------------------------------------
-// The nine resident kernels (kernels.hpp StreamKernel; the pieces and the protocol: above, "Block streaming"): ONE body,
+// The ten resident kernels (kernels.hpp StreamKernel; the pieces and the protocol: above, "Block streaming"): ONE body,
 // stream_resident_body, instantiated by the kernel's form (kernels.hpp StreamForm).  The body is the protocol's skeleton -- when
 // `alive` is published, the block loop and its stop test, which wave counts a voice in, when LDS may be reused -- and every
 // kernel is the one before it and one thing more:
@@ -2082,6 +2082,9 @@ hipError_t launch_stage(const StageArgs &a, hipStream_t s) {
 //   bank_stream_general_kernel   schedule banks (stream_render_schedule)                              45 072
 //   bank_stream_dyn_kernel       Delays by a signal amount (stream_prog_dyn)                          45 072
 //   bank_stream_hist_kernel      delayed reads of input rows: the rows' history (StreamHistArgs)      45 072
+//
+// and, beside the cascade, the form without a voice (kernels.hpp bank_stream_fx_kernel): the hist form's programs, doorbell and
+// history with no bank, no render and no hand-over -- a workgroup is ONE wave that runs a segment of programs  32 776
 //
 // The bus segment is progs[voice_first[n_voices] .. voice_first[n_voices + 1]) and may be empty.  Which kernel a plan launches
 // is the host's rule (streamplan.hpp; fr_plan_json["stream"]["kernel"]).  The compiled kernels against their earlier,
@@ -2190,7 +2193,9 @@ __device__ __forceinline__ void stream_resident_body(StreamBanksArgs t, StreamGe
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t local = blockIdx.x - bk.first_wg;
     // (a schedule bank: log2_p = chunk_log2 = 0 makes `local` the voice of the bank and its chunk count 1)
-    const StreamWork w = stream_work(bk.params, bk.rows, schedule ? 0u : bk.log2_p, schedule ? 0u : bk.chunk_log2, bk.fast_ok, bk.to_ring, bk.first_voice, local, wave);
+    // (the voiceless form has no bank: nothing to render, a workgroup's work is its segment of programs)
+    const StreamWork w = F.voiceless ? StreamWork{}
+                                     : stream_work(bk.params, bk.rows, schedule ? 0u : bk.log2_p, schedule ? 0u : bk.chunk_log2, bk.fast_ok, bk.to_ring, bk.first_voice, local, wave);
     const uint32_t *items = nullptr;
     const float *vparams = nullptr;
     uint32_t nitems = 0;
@@ -2217,26 +2222,38 @@ __device__ __forceinline__ void stream_resident_body(StreamBanksArgs t, StreamGe
         if (seq == BANK_STREAM_STOP) break;
         seen = seq;
         const bool live = lane < T;
-        float t_in, result, r;
-        // (the conditional expression the general kernel has always had: as an if / else its compiled loop comes out another)
-        if constexpr (F.schedule)
-            r = schedule ? stream_render_schedule(vparams, items, nitems, bk.fast_ok, stream_time_row(dev), live, wave, lane, sm, stack_mem, zshared, t_in)
-                         : stream_render_chunk(w, stream_time_row(dev), live, wave, lane, sm[0], zshared, t_in);
-        else r = stream_render_chunk(w, stream_time_row(dev), live, wave, lane, sm[0], zshared, t_in);
-        if (wave == 0u && stream_hand_over(w, a.ws, a.tickets, n_voices, lane, r, result)) {
-            // the finishing wave: the voice's frames head + lane to its ring or row, then its programs, then it counts the voice in
-            const auto input = [&] {
-                if constexpr (F.hist) return StreamHistInput{stream_input(dev, lane, t_in), h.hist, h.mask};
-                else return stream_input(dev, lane, t_in);
-            }();
+        if constexpr (F.voiceless) {
+            // no voice: the workgroup is one wave, its segment's programs are the block's work (kernels.hpp bank_stream_fx_kernel).
+            // S_INPUT(0) is the lane's word of the republished time row, as the rendering waves of the other forms load it.
+            const float t_row = live ? __hip_atomic_load(&stream_time_row(dev)[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0f;
+            const StreamHistInput input{stream_input(dev, lane, t_row), h.hist, h.mask};
             auto run = [&](uint32_t p_first, uint32_t p_end) {
-                if constexpr (F.loops) stream_run_programs_loops<F.dyn>(a.out, p, regs, ldt, stt, lins, p_first, p_end, head, T, lane, live, input);
-                else if constexpr (F.progs) stream_run_programs(a.out, p, regs, p_first, p_end, head + lane, lane, live, input);
+                stream_run_programs_loops<true>(a.out, p, regs, ldt, stt, lins, p_first, p_end, head, T, lane, live, input);
             };
-            stream_store_voice(w, a.out, p, head + lane, lane, live, result);
-            if constexpr (F.progs) run(p.voice_first[w.voice], p.voice_first[w.voice + 1]);
-            if constexpr (F.bus) stream_finish_bus(ctl, dev, n_voices, lane, seq, [&] { run(p.voice_first[n_voices], p.voice_first[n_voices + 1]); });
-            else stream_finish(ctl, dev, n_voices, lane, seq);
+            run(p.voice_first[blockIdx.x], p.voice_first[blockIdx.x + 1u]);
+            stream_finish_bus(ctl, dev, n_voices, lane, seq, [&] { run(p.voice_first[n_voices], p.voice_first[n_voices + 1u]); });
+        } else {
+            float t_in, result, r;
+            // (the conditional expression the general kernel has always had: as an if / else its compiled loop comes out another)
+            if constexpr (F.schedule)
+                r = schedule ? stream_render_schedule(vparams, items, nitems, bk.fast_ok, stream_time_row(dev), live, wave, lane, sm, stack_mem, zshared, t_in)
+                             : stream_render_chunk(w, stream_time_row(dev), live, wave, lane, sm[0], zshared, t_in);
+            else r = stream_render_chunk(w, stream_time_row(dev), live, wave, lane, sm[0], zshared, t_in);
+            if (wave == 0u && stream_hand_over(w, a.ws, a.tickets, n_voices, lane, r, result)) {
+                // the finishing wave: the voice's frames head + lane to its ring or row, then its programs, then it counts the voice in
+                const auto input = [&] {
+                    if constexpr (F.hist) return StreamHistInput{stream_input(dev, lane, t_in), h.hist, h.mask};
+                    else return stream_input(dev, lane, t_in);
+                }();
+                auto run = [&](uint32_t p_first, uint32_t p_end) {
+                    if constexpr (F.loops) stream_run_programs_loops<F.dyn>(a.out, p, regs, ldt, stt, lins, p_first, p_end, head, T, lane, live, input);
+                    else if constexpr (F.progs) stream_run_programs(a.out, p, regs, p_first, p_end, head + lane, lane, live, input);
+                };
+                stream_store_voice(w, a.out, p, head + lane, lane, live, result);
+                if constexpr (F.progs) run(p.voice_first[w.voice], p.voice_first[w.voice + 1]);
+                if constexpr (F.bus) stream_finish_bus(ctl, dev, n_voices, lane, seq, [&] { run(p.voice_first[n_voices], p.voice_first[n_voices + 1]); });
+                else stream_finish(ctl, dev, n_voices, lane, seq);
+            }
         }
         head += T;
         __syncthreads();   // LDS is reused by the next block
@@ -2276,6 +2293,13 @@ __global__ void __launch_bounds__(1024) bank_stream_hist_kernel(StreamBanksArgs 
                                                                 BankStreamInCtl *ctl, BankStreamInDev *dev, uint32_t idle_ms) {
     stream_resident_body<StreamKernel::hist>(t, g, h, a, p, n_rows, ctl, dev, idle_ms);
 }
+// (LAUNCHED with one wave per workgroup: a segment of programs needs no more, and nothing is rendered.  The bound stays the other
+// forms': under __launch_bounds__(64) the compiler sees that 32 KiB of LDS leave room for one wave per SIMD and pads the wave's
+// register allocation to 257 VGPRs to say so; with this bound it records the 48 the code uses)
+__global__ void __launch_bounds__(1024) bank_stream_fx_kernel(StreamHistArgs h, BankArgs a, StreamProgArgs p, uint32_t n_rows, BankStreamInCtl *ctl, BankStreamInDev *dev,
+                                                            uint32_t idle_ms) {
+    stream_resident_body<StreamKernel::fx>({}, {}, h, a, p, n_rows, ctl, dev, idle_ms);
+}
 
 // The one entry of the resident launches (kernels.hpp StreamLaunchArgs): the check, then the kernel with what it takes.
 hipError_t launch_bank_stream(StreamKernel k, const StreamLaunchArgs &x, hipStream_t s) {
@@ -2285,7 +2309,7 @@ hipError_t launch_bank_stream(StreamKernel k, const StreamLaunchArgs &x, hipStre
     BankStreamDev *const dev = static_cast<BankStreamDev *>(x.dev);
     BankStreamInCtl *const ctl_in = static_cast<BankStreamInCtl *>(x.ctl_dev);
     BankStreamInDev *const dev_in = static_cast<BankStreamInDev *>(x.dev);
-    const dim3 grid(wgs), block(1024);
+    const dim3 grid(wgs), block(1024), wave(64);   // (the voiceless form: a workgroup is one wave)
     const uint32_t idle_ms = x.idle_ms ? x.idle_ms : BANK_STREAM_IDLE_MS;
     switch (k) {
     case StreamKernel::plain: hipLaunchKernelGGL(bank_stream_kernel, grid, block, 0, s, x.a, ctl, dev, idle_ms); break;
@@ -2297,6 +2321,7 @@ hipError_t launch_bank_stream(StreamKernel k, const StreamLaunchArgs &x, hipStre
     case StreamKernel::general: hipLaunchKernelGGL(bank_stream_general_kernel, grid, block, 0, s, x.t, x.g, x.a, x.p, x.n_rows, ctl_in, dev_in, idle_ms); break;
     case StreamKernel::dyn: hipLaunchKernelGGL(bank_stream_dyn_kernel, grid, block, 0, s, x.t, x.g, x.a, x.p, x.n_rows, ctl_in, dev_in, idle_ms); break;
     case StreamKernel::hist: hipLaunchKernelGGL(bank_stream_hist_kernel, grid, block, 0, s, x.t, x.g, x.h, x.a, x.p, x.n_rows, ctl_in, dev_in, idle_ms); break;
+    case StreamKernel::fx: hipLaunchKernelGGL(bank_stream_fx_kernel, grid, wave, 0, s, x.h, x.a, x.p, x.n_rows, ctl_in, dev_in, idle_ms); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

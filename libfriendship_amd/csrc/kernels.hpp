@@ -332,14 +332,37 @@ struct StreamHistArgs {
     uint64_t mask;
 };
 
-// The nine resident kernels (streamplan.hpp stream_launch chooses; `none`: no resident launch yet) and their one launch entry.
+// bank_stream_fx_kernel (FR_STREAM_EFFECTS): the resident body for a plan WITHOUT A VOICE -- an echo, a comb or a flanger on a row
+// the host feeds in, a gain on a control row -- whose programs the rule has dealt over SEGMENTS (streamplan.hpp): workgroup s is
+// ONE WAVE (64 threads: the 16 waves of the other forms exist only to render partials) that runs progs[voice_first[s] ..
+// voice_first[s + 1]) of every block, lane = frame, with everything the hist form's interpreter knows -- control rows, loop
+// programs, Delays by a signal amount, the history of the streamed rows --, then takes the block's ticket as a finished voice
+// does; the last arriver runs the bus segment progs[voice_first[segments] .. voice_first[segments + 1]) and writes the done tag.
+// There is no bank, no table, no render, no chunk hand-over and no voice to store: BankArgs gives n_voices = segments and out, and
+// its params, rows, ws and tickets are not read.  Row 0 is the time row as ever, S_INPUT(0) the lane's word of it.  Wave 0 of
+// workgroup 0 waits on the doorbell, republishes the rows and stores the history exactly as in the hist form; the history exists
+// also when no program reads it (64 frames per row).  Why no wait, acquire or release is added:
+//   * a read below a block of a ring an EARLIER program stored: the rule put both programs into one segment (the tap behind a
+//     loop, a row copy), so it is the same wave's own store, acknowledged (s_waitcnt vmcnt(0)) before the next program's loads --
+//     the hand-over the tap behind a voice's loop has always relied on;
+//   * a read a block or more back, of any ring and of any row's history: an earlier block's store, acknowledged before that
+//     block's ticket, and the host rang this block only after that block's done tag;
+//   * the bus segment runs in the wave that drew the block's last ticket: every segment had its stores acknowledged before its
+//     ticket, and that wave issues its loads after its own ticket came back -- stream_finish_bus as it stands.
+// LDS: the interpreter's registers, the loop tiles and the instruction copy, 32 776 bytes; the waves' sums and the schedule stack
+// of the other forms take none here.
+//
+// The ten resident kernels (streamplan.hpp stream_launch chooses; `none`: no resident launch yet) and their one launch entry.
 // plain, prog and bus have the one-row doorbell (BankStreamCtl / BankStreamDev), the others the doorbell of rows (BankStreamIn*).
-// (hist is dyn + 2: the value after dyn stays unnamed and refused, as the tests of the launch check have always required)
-enum class StreamKernel : uint32_t { none, plain, prog, bus, in, banks, loops, general, dyn, hist = dyn + 2 };
-constexpr bool stream_kernel_named(StreamKernel k) { return k != StreamKernel::none && (k <= StreamKernel::dyn || k == StreamKernel::hist); }
-// A kernel's form: what it has on top of bank_stream_kernel.  The kernels are a cascade -- each is the one before it and one
-// thing more --, so the enum's order is the form.  kernels.hip's one resident body is instantiated by it, stream_launch_check
-// below reads it.
+// (hist is dyn + 2 and fx is hist + 2: the values after dyn and after hist stay unnamed and refused, as the tests of the launch
+// check have always required)
+enum class StreamKernel : uint32_t { none, plain, prog, bus, in, banks, loops, general, dyn, hist = dyn + 2, fx = hist + 2 };
+constexpr bool stream_kernel_named(StreamKernel k) {
+    return k != StreamKernel::none && (k <= StreamKernel::dyn || k == StreamKernel::hist || k == StreamKernel::fx);
+}
+// A kernel's form: what it has on top of bank_stream_kernel.  The nine kernels with voices are a cascade -- each is the one
+// before it and one thing more --, so the enum's order is their form; fx, which has no voice, is written out.  kernels.hip's one
+// resident body is instantiated by it, stream_launch_check below reads it.
 struct StreamForm {
     bool progs;      // runs the voices' programs (StreamProgArgs) and advances `head`
     bool bus;        // ... and the bus segment in the block's last arriver
@@ -349,10 +372,13 @@ struct StreamForm {
     bool schedule;   // schedule banks (StreamGeneralArgs)
     bool dyn;        // the interpreter knows the Delays by a signal amount; a plan need not have a schedule bank
     bool hist;       // the history of the streamed rows (StreamHistArgs): delayed reads of input rows
+    bool voiceless;  // no bank at all: a workgroup is one wave that runs a segment of programs (fx alone)
 };
 constexpr StreamForm stream_form(StreamKernel k) {
-    return {k >= StreamKernel::prog,  k >= StreamKernel::bus,     k >= StreamKernel::in, k >= StreamKernel::banks,
-            k >= StreamKernel::loops, k >= StreamKernel::general, k >= StreamKernel::dyn, k == StreamKernel::hist};
+    if (k == StreamKernel::fx)   // progs, bus, rows, loops, dyn and hist; no table, no schedule
+        return {true, true, true, false, true, false, true, true, true};
+    return {k >= StreamKernel::prog,  k >= StreamKernel::bus,     k >= StreamKernel::in,  k >= StreamKernel::banks,
+            k >= StreamKernel::loops, k >= StreamKernel::general, k >= StreamKernel::dyn, k == StreamKernel::hist, false};
 }
 // Everything a resident launch may need; stream_launch_check reads and checks what the kernel takes.
 struct StreamLaunchArgs {
@@ -410,10 +436,15 @@ inline uint32_t stream_launch_check(StreamKernel k, const StreamLaunchArgs &x) {
     if (f.hist && (!x.h.hist || (x.h.mask & (x.h.mask + 1)) != 0 || x.h.mask + 1 < 64u)) return 0;   // a ring of 2^n >= 64 frames per row
     // the tiles' limits concern loop programs; the general form takes a plan without one (max_stride == 0)
     if (f.loops && (x.max_stride > BANK_STREAM_LOOP_MAX_STRIDE || x.max_loads > BANK_STREAM_LOOP_LOADS || x.max_stores > BANK_STREAM_LOOP_STORES)) return 0;
-    if ((f.schedule ? x.max_stride != 0 : f.loops) && !x.p.n_rings) return 0;   // a loop lives in a ring
+    if ((f.schedule || f.voiceless ? x.max_stride != 0 : f.loops) && !x.p.n_rings) return 0;   // a loop lives in a ring
     uint32_t wgs = 0;
     bool to_ring = f.progs && x.p.bank_to_ring != 0;
-    if (f.table) {
+    if (f.voiceless) {
+        // no bank: n_voices is the segment count, a workgroup of one wave each; params, rows, ws, tickets and the tables are not read
+        if (a.n_voices == 0 || a.n_voices > BANK_STREAM_WGS) return 0;   // all workgroups must be resident
+        wgs = a.n_voices;
+        to_ring = false;
+    } else if (f.table) {
         const uint32_t mask = f.schedule ? x.g.mask : 0u;
         if (f.schedule && !f.dyn && mask == 0) return 0;   // (only dyn takes a plan without a schedule bank)
         wgs = stream_table_ok(x.t, a, mask, to_ring);

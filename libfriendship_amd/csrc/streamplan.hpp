@@ -42,6 +42,15 @@
 // program to no voice and never makes it a bus program.  Its slot is streamed like an S_INPUT's (FR_STREAM_INPUTS for a slot
 // other than 0).  The deepest such read (StreamPlan::input_lookback) sizes the history, at most STREAM_HIST_MAX_FRAMES.
 // S_READ_INPUT_DYN inside a loop program and a bound observed from input rows stay refused.
+// With FR_STREAM_EFFECTS=1 (StreamEnv::effects) a plan with NO bank launch at all -- an echo, a comb or a flanger on a row the host
+// feeds in, a gain on a control row, a one-pole smoother on a knob -- is served too, with voices == 0: its programs are dealt over
+// SEGMENTS, the ordered lists of programs that one workgroup runs (kernels.hpp bank_stream_fx_kernel; one wave each).  Every
+// program gets a GROUP in `run` order: it follows the group of the earlier program whose ring it reads less than a block back (the
+// tap behind a loop, FR_STREAM_LOOPS) or whose ring it copies to a row, else it opens a new one; one that would follow two groups
+// is a bus program (FR_STREAM_BUS), which runs in the bus segment after every segment has finished.  Group g runs in segment
+// g % segments, segments = min(groups, stream_max_wgs): no plan is refused for its number of rows.  A segment stands where a
+// voice stood -- voice_first has segments + 2 entries -- and still nobody waits: a read below a block is of a ring the same wave
+// stored, a deeper one of an earlier block's frames.  Every other check applies to these programs unchanged.
 // HOW a served plan is launched is one rule as well (stream_path, stream_launch, plain_stream_launch, at the end): the path, the
 // kernel, its doorbell form, its tables, the loop limits, the workgroups.  fr_stream_begin, the seek, the block, the stop and
 // fr_plan_json's "kernel" read the StreamLaunch it returns and decide nothing themselves.
@@ -93,6 +102,7 @@ struct StreamEnv {
     bool general = false;            // FR_STREAM_GENERAL: schedule banks -- general voices, balanced voices of 32 or 64 partials
     bool dyn = false;                // FR_STREAM_DYN: Delays of a voice by a signal amount (S_READ_DYN of a bank's ring, S_STEP_DYN)
     bool history = false;            // FR_STREAM_HISTORY: delayed reads of input rows (S_READ_INPUT; with `dyn` S_READ_INPUT_DYN) from the stream's history
+    bool effects = false;            // FR_STREAM_EFFECTS: plans without a bank launch: the programs are dealt over segments (StreamPlan::segments)
     bool programs = false;           // FR_STREAM_PROGRAMS: the program path exists (stream_path; plan_stream does not ask)
 };
 
@@ -190,6 +200,7 @@ struct StreamPlan {
     bool servable = false;
     std::string reason;              // why not ("" when servable)
     uint32_t voices = 0, chunk_log2 = 0, chunks = 0;   // chunks per voice; one bank: the launch has voices * chunks workgroups
+    uint32_t segments = 0;               // a plan without a voice (StreamEnv::effects): the workgroups its programs are dealt over; 0 for every plan with voices
     bool bank_to_ring = false;
     std::vector<StreamBank> banks;       // one per bank launch, in plan order.  Several: `voices` is their total, `chunks` the
                                          // largest per-voice chunk count, chunk_log2 / bank_to_ring are bank 0's
@@ -202,6 +213,7 @@ struct StreamPlan {
     std::vector<uint32_t> loop_stride;   // per entry of `progs`: the stride of a loop program (1..63), 0 for any other (StreamEnv::loops)
     bool has_loops() const { return std::any_of(loop_stride.begin(), loop_stride.end(), [](uint32_t l) { return l != 0; }); }
     std::vector<uint32_t> voice_first;   // [voices + 2] into `progs`: [voice_first[voices], voice_first[voices + 1]) is the bus segment
+                                         // (a plan without a voice: [segments + 2], a segment where a voice stands)
     uint64_t min_ring_delay = 0;         // shortest delayed read of a ring that a program stores (0: there is none)
     uint64_t lookback = 0;               // deepest ring read of the assigned programs
     uint32_t dyn_reads = 0;              // the assigned programs' S_READ_DYNs (StreamEnv::dyn) ...
@@ -309,7 +321,8 @@ inline StreamPlan plan_stream(const StagedPlan &sp, const std::vector<const Bank
     if (env.pull_mode) return refuse("block streaming of a renderer in FR_MODE_PULL");
     if (!sp.pull_rows.empty()) return refuse(std::to_string(sp.pull_rows.size()) + " output rows are left to the pull interpreter");
     if (env.track_history || !sp.track_window_slots.empty() || sp.track_lookback != 0) return refuse("block streaming with a track history");
-    if (banks.size() != 1 && !(env.banks && banks.size() >= 2 && banks.size() <= STREAM_MAX_BANKS)) {
+    const bool voiceless = env.effects && banks.empty();   // FR_STREAM_EFFECTS: the programs are dealt over segments, not voices
+    if (banks.size() != 1 && !(env.banks && banks.size() >= 2 && banks.size() <= STREAM_MAX_BANKS) && !voiceless) {
         if (env.banks && banks.size() > STREAM_MAX_BANKS)
             return refuse("block streaming serves at most " + std::to_string(STREAM_MAX_BANKS) + " voice banks in one launch (this plan: " +
                           std::to_string(banks.size()) + " bank launches)");
@@ -361,8 +374,10 @@ inline StreamPlan plan_stream(const StagedPlan &sp, const std::vector<const Bank
         s.chunks = std::max(s.chunks, 1u << (sb.log2_p - sb.chunk_log2));
     }
     s.voices = V;
-    s.chunk_log2 = s.banks[0].chunk_log2;
-    s.bank_to_ring = s.banks[0].to_ring;
+    if (!voiceless) {
+        s.chunk_log2 = s.banks[0].chunk_log2;
+        s.bank_to_ring = s.banks[0].to_ring;
+    }
     std::vector<uint32_t> others;                    // slots other than 0 that the assigned programs read (StreamEnv::inputs)
 
     // the programs that do a block's work: the fused form (a feedback plan: level by level, then its row copies); a plan whose
@@ -384,6 +399,7 @@ inline StreamPlan plan_stream(const StagedPlan &sp, const std::vector<const Bank
                           " frames back (or the fused programs exceed the interpreter's budget)");
         for (uint32_t i = sp.level_first[only]; i < sp.level_first[only + 1]; ++i) run.push_back(i);
     }
+    if (voiceless && run.empty()) return refuse("block streaming of a plan with neither voices nor programs");
     std::unordered_map<uint32_t, uint32_t> bank_ring_voice;   // ring -> voice whose frames it holds
     for (size_t i = 0; i < banks.size(); ++i)
         if (banks[i]->to_ring)
@@ -398,7 +414,11 @@ inline StreamPlan plan_stream(const StagedPlan &sp, const std::vector<const Bank
         }
     }
     constexpr uint32_t NONE = UINT32_MAX;
-    const uint32_t BUS = V;                                   // "voice" of a bus program: the segment after the last voice's
+    // "voice" of a bus program: the segment after the last voice's.  A plan without a voice: voice_of holds a program's GROUP until
+    // the groups are counted and dealt over the segments (below), and the bus has a number no group has
+    const uint32_t BUS = voiceless ? UINT32_MAX - 1u : V;
+    uint32_t groups = 0;
+    const std::string whom = voiceless ? "program groups" : "voices", one_whom = voiceless ? "program group" : "voice";
     std::vector<uint32_t> voice_of(run.size(), NONE);
     const bool loops = env.loops && sp.feedback;              // FR_STREAM_LOOPS concerns a feedback plan's one-launch form
     std::vector<uint32_t> stride_of(run.size(), 0);
@@ -518,8 +538,8 @@ inline StreamPlan plan_stream(const StagedPlan &sp, const std::vector<const Bank
                     if (st != stored_by.end() && st->second < k) {
                         const uint32_t theirs = voice_of[st->second];
                         if (mine != NONE && mine != theirs)
-                            return refuse("a program reads voices " + std::to_string(mine) + " and " + std::to_string(theirs) +
-                                          " in the same block (a mix bus across voices); each streamed program follows one voice");
+                            return refuse("a program reads " + whom + " " + std::to_string(mine) + " and " + std::to_string(theirs) +
+                                          " in the same block (a mix bus across " + whom + "); each streamed program follows one " + one_whom);
                         mine = theirs;
                         min_delay = std::min<uint64_t>(min_delay, in.d_lo);
                         break;
@@ -563,7 +583,8 @@ inline StreamPlan plan_stream(const StagedPlan &sp, const std::vector<const Bank
             if (n_st > STREAM_LOOP_STORES)
                 return refuse("a loop program stores " + std::to_string(n_st) + " rings; block streaming serves at most " + std::to_string(STREAM_LOOP_STORES));
         }
-        voice_of[k] = bus ? BUS : mine != NONE ? mine : run[k] % V;   // (reads no voice at a short delay: any one voice, the same every time)
+        // (reads no voice at a short delay: any one voice, the same every time; without a voice: it follows nobody and opens a group)
+        voice_of[k] = bus ? BUS : mine != NONE ? mine : voiceless ? groups++ : run[k] % V;
     }
     if (s.input_lookback > STREAM_HIST_MAX_FRAMES)
         return refuse("a program reads an input row " + std::to_string(s.input_lookback) + " frames back; a stream's input history holds at most " +
@@ -585,6 +606,12 @@ inline StreamPlan plan_stream(const StagedPlan &sp, const std::vector<const Bank
     for (uint32_t r = 0; r < env.n_slots; ++r)
         if (writers[r] != 1)
             return refuse("output row " + std::to_string(r) + " is written by " + std::to_string(writers[r]) + " streamed programs or voices (exactly one is needed)");
+    if (voiceless) {                                          // group g runs in segment g % segments, the bus programs behind the last segment
+        s.segments = (uint32_t)std::min<uint64_t>(groups, max_wgs);
+        if (s.segments == 0) return refuse("internal: a plan without a voice whose programs are all bus programs");
+        for (uint32_t &v : voice_of) v = v == BUS ? s.segments : v % s.segments;
+        V = s.segments;
+    }
     s.voice_first.assign(V + 2, 0);
     for (uint32_t k = 0; k < run.size(); ++k) ++s.voice_first[voice_of[k] + 1];
     for (uint32_t v = 0; v <= V; ++v) s.voice_first[v + 1] += s.voice_first[v];
@@ -610,6 +637,7 @@ inline const char *stream_kernel_name(StreamKernel k) {
     static const char *const names[] = {"", "bank_stream_kernel", "bank_stream_prog_kernel", "bank_stream_bus_kernel", "bank_stream_in_kernel",
                                         "bank_stream_banks_kernel", "bank_stream_loops_kernel", "bank_stream_general_kernel", "bank_stream_dyn_kernel"};
     if (k == StreamKernel::hist) return "bank_stream_hist_kernel";   // (not the value after dyn: that one has no name)
+    if (k == StreamKernel::fx) return "bank_stream_fx_kernel";       // (nor the value after hist)
     return names[(uint32_t)k < sizeof names / sizeof names[0] ? (uint32_t)k : 0];
 }
 
@@ -639,15 +667,19 @@ inline bool stream_path(const StagedPlan &sp, const std::vector<const BankLaunch
 // The launch of a servable plan of the program path.  The one cascade: hist > dyn > general > loops > banks > in > bus > prog.
 // dyn -- a plan with a Delay by a signal amount (StreamPlan::has_dyn) -- is the general kernel's composition and takes the
 // schedule table only when the plan has schedule banks; hist -- a plan with a delayed read of an input row
-// (StreamPlan::has_hist), and no other -- is dyn's composition with the history of the streamed rows.
+// (StreamPlan::has_hist), and no other -- is dyn's composition with the history of the streamed rows.  Ahead of the cascade: fx --
+// a plan without a voice (StreamPlan::voices == 0, FR_STREAM_EFFECTS), and no other --: one workgroup per segment, no bank and
+// no schedule table, and always the history (at least a block per row also when nothing reads it: n_rows x 64 floats spare an
+// eleventh kernel).
 inline StreamLaunch stream_launch(const StagedPlan &sp, const StreamPlan &s) {
     StreamLaunch l;
-    l.kernel = s.has_hist() ? StreamKernel::hist : s.has_dyn() ? StreamKernel::dyn : s.has_general() ? StreamKernel::general : s.has_loops() ? StreamKernel::loops
+    const bool fx = s.voices == 0;
+    l.kernel = fx ? StreamKernel::fx : s.has_hist() ? StreamKernel::hist : s.has_dyn() ? StreamKernel::dyn : s.has_general() ? StreamKernel::general : s.has_loops() ? StreamKernel::loops
                : s.banks.size() > 1 ? StreamKernel::banks : s.input_slots.size() > 1 ? StreamKernel::in : s.bus_programs() ? StreamKernel::bus : StreamKernel::prog;
     l.rows_doorbell = l.own_instrs = l.by_plan = stream_kernel_by_plan(l.kernel);
-    l.bank_table = l.kernel >= StreamKernel::banks;
-    l.schedule_table = l.kernel == StreamKernel::general || (l.kernel >= StreamKernel::dyn && s.has_general());
-    l.hist_cap = l.kernel == StreamKernel::hist ? stream_hist_cap(s.input_lookback) : 0;
+    l.bank_table = !fx && l.kernel >= StreamKernel::banks;
+    l.schedule_table = !fx && (l.kernel == StreamKernel::general || (l.kernel >= StreamKernel::dyn && s.has_general()));
+    l.hist_cap = fx || l.kernel == StreamKernel::hist ? stream_hist_cap(s.input_lookback) : 0;
     l.n_rows = l.rows_doorbell ? (uint32_t)s.input_slots.size() : 1u;
     for (size_t i = 0; i < s.progs.size(); ++i) {    // (the tiles' fill is counted from the plan's instructions; the store slots are the stored rings)
         if (!s.loop_stride[i]) continue;
@@ -656,7 +688,7 @@ inline StreamLaunch stream_launch(const StagedPlan &sp, const StreamPlan &s) {
         l.max_loads = std::max(l.max_loads, stream_loop_loads(pg, sp.instrs.data() + pg.first_instr));
         l.max_stores = std::max(l.max_stores, (uint32_t)stream_stored_rings(pg, sp.instrs.data() + pg.first_instr).size());
     }
-    l.workgroups = s.workgroups();
+    l.workgroups = fx ? s.segments : s.workgroups();
     return l;
 }
 
