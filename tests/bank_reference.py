@@ -5,6 +5,10 @@ sum_tree association (adjacent pairs level by level, an odd element carried up u
 synth.bank_reference_numpy in the same order, over many voices at once.  Voices and frames are processed in slices so that no
 temporary grows beyond about `budget` elements.  tests/test_bank_variants.py pins it bit for bit to the C++ oracle.
 
+Only the sum_tree association is restated here.  For any other Sum2 tree over the same leaves -- chains, unbalanced trees, DAGs:
+what the schedule kernels render item by item -- the dense reference is tests/tree_shapes.py render_shapes, which takes its
+leaves from _leaves and adds them in each tree's own association (pinned to the oracle by tests/test_tree_shapes.py).
+
 render_track_bank is the same bank with w and amp given per frame (control-rate tracks, synth.track_leaves: w[v, k, t] and
 amp[v, k, t] read from input rows); track_params cuts them out of a call's dense input matrix under the slot limit of the
 call.  tests/test_track_variants.py pins both to the oracle."""
