@@ -282,8 +282,18 @@ fr_status fr_fill_buffer_device(fr_renderer *r, float *d_out, uint32_t n_slots, 
  * empty row -- the last value of the previous block when `idx` continues it (idx == previous idx + previous n_times); the
  * first block of a stream, and a block that does not continue the previous one, find nothing stored (as after a seek) and
  * pad with 0.  Results are the bits fr_fill_buffer renders for the same sequence of calls begun with a seek.
- * ANY other call on the renderer (an edit, fr_fill_buffer, fr_stream_end) first retires the resident launch; the frames
- * streamed in between were not stored, so the call after that is a seek (reference.rs:52-58).
+ * ANY other call on the renderer (an edit, fr_fill_buffer, fr_stream_end) first retires the resident launch.  Without the
+ * option FR_STREAM_STORE the frames streamed in between were not stored, so the call after that is a seek (reference.rs:52-58),
+ * and so is the first block of every stream.
+ * With FR_STREAM_STORE=1 on top of FR_STREAM_PROGRAMS=1 (friendship_render_ext.h) a stream STORES what it is fed and the
+ * contract is the whole one: results and statuses are those of fr_fill_buffer for the same sequence of calls AND EDITS,
+ * whatever mixture of fr_fill_buffer, edits and streams the host makes.  A stream's first block whose `idx` continues the
+ * renderer's last call -- fr_fill_buffer's or a streamed block's, before or after an edit -- is no seek: delay lines, loops and
+ * delayed reads of input rows find the past, an empty row pads with the value stored last.  Closing a stream leaves the
+ * renderer as an ordinary call ending at the stream's last frame leaves it, so fr_fill_buffer continues it, and after an edit
+ * (a note-on, a note-off, a knob turn: fr_stream_begin again, as ever) the next stream continues where the last one stopped.
+ * Only a block whose `idx` is not the renderer's next frame is a seek.  A block that is not answered (below) is not in the
+ * store; the blocks answered before it are.
  * Bounds: the kernel ends itself when no block has arrived for FR_STREAM_IDLE_MS = 2000 ms of wall clock (the environment
  * variable of that name overrides it at fr_renderer_create; fr_stream_block then returns FR_ERR_DEVICE: begin again), and
  * fr_stream_block gives up with FR_ERR_DEVICE when a block is not answered within 250 ms (the launch is not fully

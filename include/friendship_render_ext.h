@@ -163,6 +163,34 @@ extern "C" {
  * the programs of each segment and "kernel" is "bank_stream_fx_kernel".  Still refused, each with its reason: a patch with
  * neither voices nor programs; a feed-forward delay shorter than a block of a computed value (no fused form) and a signal
  * delay of one; a program that needs two groups without FR_STREAM_BUS.
+ *
+ * FR_STREAM_STORE = 0 / 1 (default 0; read strictly from the environment too; does nothing unless FR_STREAM_PROGRAMS=1): a
+ * stream that SURVIVES EDITS.  The resident launch appends every row it is fed to the renderer's input store, under the
+ * acknowledgement it already gives the rows (two more resident kernels, bank_stream_store_kernel and, for a patch without a
+ * voice, bank_stream_store_fx_kernel: the top of the cascade and one vector store per streamed row more), and the renderer's
+ * books follow block by block.  The contract of fr_stream_* becomes: results and statuses are those of fr_fill_buffer for
+ * the same sequence of calls and edits, whatever mixture of fr_fill_buffer, edits and streams the host makes.
+ *   - A stream's first block with idx == the renderer's next frame CONTINUES: the stream's history of its rows is filled from
+ *     the store, the delay lines are brought up to idx as the first fr_fill_buffer call of the plan there would bring them before
+ *     its own frames (nothing when that call would be steady, else the look-back rebuild from the stored history, a loop's
+ *     replay, with FR_RING_KEEP its keep-and-repair), then the resident launch starts.  Any other idx is the seek it has always
+ *     been, and resets the store as fr_fill_buffer's seek does.
+ *   - Closing a stream (an edit, fr_fill_buffer*, fr_stream_end) leaves the renderer as after an ordinary call ending at the
+ *     stream's last frame.  After an edit the host calls fr_stream_begin again and the first block continues.
+ *   - Streamed are the slots the plan reads, every slot the store has been fed and every slot a block feeds, slot 0 first: at
+ *     most 8, else fr_stream_begin (or the block) returns FR_ERR_UNSUPPORTED with the count and the limit and the renderer
+ *     stays as it was -- go on with fr_fill_buffer, no seek needed.  Every servable plan takes this path, also one bank of
+ *     balanced voices writing rows.
+ *   - When a slot's buffer has to slide (fr_config.history_frames) or grow, or a block feeds a slot the launch does not
+ *     stream, the launch is stopped, the store does what it does for fr_fill_buffer, and the launch restarts at the block:
+ *     a relaunch, not a seek -- delay lines and history stay.  It costs a launch, once per ~65 000 frames with a bounded history
+ *     and at every doubling (2^20, 2^21 ... frames) without.
+ *   - FR_ERR_INPUT_HISTORY and FR_ERR_INPUT_TOO_LONG across every boundary are fr_fill_buffer's for the same sequence.
+ * Inert -- the stream behaves as without the option, and "store"."inert" says why -- with FR_DELAY_OBSERVED=1 (streamed rows
+ * would escape the observed bounds) and with declared track slots (fr_set_track_inputs).  With 0 nothing changes: not a plan,
+ * not a kernel choice, not a status, not a bit.  "stream" gains "store": {"on", "slots" (the slots such a stream streams),
+ * "continued" (the open stream's first block continued the store), "relaunches" (since fr_stream_begin), "inert"}, and
+ * "kernel" names the two new kernels.
  */
 typedef struct fr_option {
     const char *name;              /* e.g. "FR_BANK_SHORT" */
@@ -183,7 +211,8 @@ const char *fr_options_json(fr_renderer *r);
  * call with one row.  `out` receives the stream's rows of n_times (1..64) floats each.
  *
  * Statuses and output bits are those of fr_fill_buffer for the same sequence of calls (same slot count, idx and rows) on a
- * renderer whose first call is a seek, although a stream stores no input samples: a short row is padded with its own last
+ * renderer whose first call is a seek (with FR_STREAM_STORE=1: on THIS renderer, whatever it has rendered before), although a
+ * stream without that option stores no input samples: a short row is padded with its own last
  * value, an empty row that continues with the previous block's last value; a slot that gets no row in a block reads +0.0
  * there; a supplied row must continue its slot's length exactly (FR_ERR_INPUT_HISTORY) and may not be longer than n_times
  * (FR_ERR_INPUT_TOO_LONG); rows at or beyond the input vector count (slots x frames of the largest call so far) are dropped

@@ -135,6 +135,19 @@ inline StageForm stage_form(const StagedPlan &sp, const CallIn &c, const CallWin
     return f;
 }
 
+// A call of ZERO own frames (CallIn::n_times == 0): what a stream that continues the input store (FR_STREAM_STORE) asks for
+// before its resident launch starts at idx -- the rings brought up to idx the way the first fr_fill_buffer call of the plan at
+// idx would bring them, before that call's own frames.  call_windows answers it as it stands: nothing when the rings are
+// current (w_len == 0, no replay); a kept plan's repair (keep_on: the repair phases, and nothing here); a feedback plan's
+// replay (fb_replay; its own window is empty); else the look-back window [idx - lmax, idx), which the ring-bound banks and the
+// programs render level by level -- the form below -- with nothing written to the output.
+inline StageForm bring_up_form(const StagedPlan &sp, const CallIn &c, const CallWindows &w) {
+    StageForm f;
+    if (c.n_times != 0 || sp.progs.empty() || sp.feedback || w.rings_current || w.w_len == 0) return f;
+    f.kind = StageForm::levels;
+    return f;
+}
+
 // Loop tiles (FR_LOOP_TILES): the strided launches of a feedback plan -- the steady call, the replay after a seek, the replay
 // of kept rings -- run one wave per program that renders the window in tiles of `frames` frames: all 64 lanes fetch the
 // tile's frame-only loads into LDS, lanes < stride walk their residue's frames on LDS operands and the carry, all 64 lanes

@@ -31,6 +31,7 @@
 #include "stage.hpp"
 #include "streamplan.hpp"
 #include "streamrows.hpp"
+#include "streamstore.hpp"
 
 namespace fr {
 
@@ -94,12 +95,9 @@ struct PinnedBuf {
 };
 
 // One external input slot's history on the device (reference.rs:25 `inputs[slot]`).
-struct InSlot {
-    bool fed = false;        // ever received a row (otherwise implicit zeros)
-    uint64_t base = 0;       // zero prefix (seek / late creation), data[i] is time base+i
-    uint64_t len = 0;        // logical length (== base + stored samples)
+// (its books -- fed, base, len, cap -- are streamstore.hpp StoreSlot, which the store's host rules read)
+struct InSlot : StoreSlot {
     DevBuf buf;
-    uint64_t cap = 0;        // capacity in floats
 };
 
 struct BankStage {
@@ -197,7 +195,7 @@ static std::string stage_variant(const StageLaunchNote &n, const Plan &p) {
     return k;
 }
 
-constexpr size_t N_OPTIONS = 40;        // per-renderer options (friendship_render_ext.h; the table below fr_renderer)
+constexpr size_t N_OPTIONS = 41;        // per-renderer options (friendship_render_ext.h; the table below fr_renderer)
 
 struct TimerClass {
     double ms = 0;
@@ -522,6 +520,11 @@ struct fr_renderer {
             // FR_STREAM_GENERAL: per plan bank the word offsets in d_sched of the one-item schedule (groups, group_off) built for a
             // balanced 32- or 64-partial bank (SIZE_MAX: the bank has none of its own here)
             std::vector<std::pair<size_t, size_t>> sched_at;
+            // FR_STREAM_STORE (streamstore.hpp): the launch appends the streamed rows to the input store and the renderer's books
+            // follow block by block; `streamed`: the slots of the launch's rows, in order; `rows_open`: `rows` are the store's books
+            bool store = false, rows_open = false, continued = false;
+            uint32_t relaunches = 0;
+            std::vector<StoreStreamed> streamed;
         } now;
         bool open = false;
         // what outlives a stream: the buffers (they only grow), the last resident launch's kernel (fr_plan_json "stream"), the trace
@@ -555,7 +558,9 @@ struct fr_renderer {
     }
     // FR_STREAM_PROGRAMS, _BUS, _INPUTS, _LOOPS, _BANKS, _GENERAL, _DYN, _HISTORY, _EFFECTS (the options table says what each serves; streamplan.hpp StreamEnv)
     bool stream_programs = false, stream_bus = false, stream_inputs = false, stream_loops = false, stream_banks = false, stream_general = false, stream_dyn = false,
-         stream_history = false, stream_effects = false;
+         stream_history = false, stream_effects = false, stream_store = false;
+    // Why FR_STREAM_STORE does nothing for this renderer ("": it acts; streamstore.hpp)
+    std::string stream_store_inert_now() const { return stream_store_inert(delay_observed, track_from != 0xFFFFFFFFu); }
     std::vector<const BankLaunch *> stream_bank_list() const {
         std::vector<const BankLaunch *> banks;
         for (const BankStage &bs : plan.banks) banks.push_back(&bs.grp);
@@ -573,13 +578,15 @@ struct fr_renderer {
         env.banks = stream_banks; env.loops = stream_loops; env.general = stream_general; env.dyn = stream_dyn;
         env.history = stream_history;
         env.effects = stream_effects;
+        env.store = stream_store && stream_programs && stream_store_inert_now().empty();
         return env;
     }
     StreamPlan plan_stream_now() const { return plan_stream(plan.sp, stream_bank_list(), stream_env()); }
     // Rings the stop and waits for the resident launch to end.  `clean`: the launch was answering when the stop was rung
     // (every block it took was finished).  Otherwise some chunks of a voice may have taken their ticket and others never
-    // run: the counters are cleared before anyone uses them again.
-    void stop_resident(bool clean) {
+    // run: the counters are cleared before anyone uses them again.  Returns whether the stop WAS clean: false also when the wait
+    // for the launch's end failed.
+    bool stop_resident(bool clean) {
         if (strm.now.launched) {
             const StreamDoorbell bell = stream_doorbell(strm.h_ctl.p, strm.now.launch.rows_doorbell);   // (the stop goes to every row)
             for (size_t i = 0; i < bell.n_words; ++i) __atomic_store_n(&bell.words[i], (unsigned long long)BANK_STREAM_STOP << 32, __ATOMIC_RELEASE);
@@ -588,10 +595,20 @@ struct fr_renderer {
         strm.now.launched = false;
         strm.now.have_last = false;
         if (!clean) counters_dirty = true;
+        return clean;
     }
     void end_stream(bool clean = true) {
         if (!strm.open) return;
-        stop_resident(clean);
+        clean = stop_resident(clean);
+        if (strm.now.store) {
+            // the stream stored what it was fed and every answered block is in the renderer's books (commit_streamed_block): the
+            // renderer stands as after an ordinary call that ended at `head`.  An unanswered block: its rows are not in the books,
+            // the rings may hold part of it -- the next call rebuilds them from the history.
+            if (!clean) { plan.stage_valid = false; ring_table.valid = false; }
+            strm.open = false;
+            strm.now = Stream::Open{};
+            return;
+        }
         if (strm.now.prog) {                     // the rings moved on with frames the input store never saw
             plan.stage_valid = false;
             ring_table.valid = false;
@@ -612,6 +629,34 @@ struct fr_renderer {
         strm.now = std::move(o);
         strm.open = true;
         last_pending = false;
+    }
+    // An answered block of a stream that stores its rows: the books an ordinary call ending at idx + n_times leaves -- the fed
+    // slots' lengths, the segments and the vector count (streamstore.hpp), head, and the rings' end.
+    void commit_streamed_block(uint32_t rows_fed, uint64_t idx, uint64_t n_times) {
+        stream_store_commit(slots, segs, n_vecs, strm.now.rows, rows_fed, idx, n_times);
+        head = idx + n_times;
+        if (!plan.sp.uses_rings()) return;
+        plan.stage_valid = true;
+        plan.stage_end = head;
+        if (ring_keep && ring_state.inert.empty() && ring_table.valid) {   // (as commit_rings: the oldest frames of a full ring are gone)
+            ring_table.end = head;
+            const uint64_t oldest = head > ring_cap ? head - ring_cap : 0;
+            for (RingEntry &e : ring_table.rings) e.valid_from = std::max(e.valid_from, oldest);
+        }
+    }
+    // The last stored value of every fed slot that holds samples (one small D2H each, before anything is resident): what an empty
+    // row of the first continuing block pads with.
+    std::vector<float> last_stored_values() {
+        std::vector<float> last(slots.size(), 0.0f);
+        bool any = false;
+        for (size_t r = 0; r < slots.size(); ++r) {
+            const InSlot &s = slots[r];
+            if (!s.fed || s.len <= s.base || !s.buf.p) continue;
+            HIP_CHECK(hipMemcpyAsync(&last[r], s.buf.as<float>() + (s.len - s.base - 1), sizeof(float), hipMemcpyDeviceToHost, stream));
+            any = true;
+        }
+        if (any) HIP_CHECK(hipStreamSynchronize(stream));
+        return last;
     }
     // The BankArgs of a resident launch over the one bank `bs`; null: the banks travel as a table, and what BankArgs says of one
     // bank (params, rows, log2_p, chunk_log2, fast_ok) is not read and stays zero.
@@ -650,7 +695,12 @@ struct fr_renderer {
         last_pending = false;
     }
     void begin_program_stream(uint32_t n_slots);
+    void upload_stream_programs(const StreamPlan &s, const StreamLaunch &l, const std::vector<uint32_t> &row_slots, uint32_t n_slots);
+    void begin_program_stream_rest(Stream::Open &&o, StreamPlan &&s, uint32_t n_slots);
     void seek_program_stream(uint64_t idx);
+    void start_resident(uint64_t idx, bool empty_history);
+    void launch_store_stream(uint64_t idx, uint32_t rows_fed, bool seek);
+    void fill_stream_history(uint64_t idx);
     bool allow_jit = true;               // FR_JIT=0: no hipRTC specialisation (those voices run as programs / pull)
     bool allow_template = true;          // FR_BANK_TEMPLATE=0: template voices go through the JIT path literally
     bool fused_strided_ok = true;        // FR_STAGE_STRIDED=0: a long steady call of the fused form as one launch per sub-window (A/B)
@@ -1123,8 +1173,7 @@ struct fr_renderer {
     // Frames of input history kept per slot (0 = everything since the last seek: the reference, reference.rs:25).  With
     // fr_config.history_frames set, at least what the current plan's constant delays and proven bounds can reach.
     uint64_t keep_frames() const {
-        if (!history_frames) return 0;
-        return std::max<uint64_t>(history_frames, plan.valid ? plan.sp.input_lookback : 0);
+        return store_keep_frames(history_frames, plan.valid, plan.sp.input_lookback);
     }
     // Buffers replaced by bigger ones are freed once the stream has passed the copy out of them -- never by waiting.
     uint64_t call_idx = 0;               // first frame of the call being served
@@ -1157,28 +1206,23 @@ struct fr_renderer {
     // front of a buffer sized 2 * (keep + call) -- one small device copy every `keep` frames, no allocation); unbounded
     // history doubles into a new buffer with an asynchronous copy, the old buffer retired without a stream wait.
     void make_room(InSlot &s, uint64_t n_times, hipStream_t st) {
-        uint64_t stored = s.len - s.base;
-        if (stored + n_times <= s.cap) return;
+        // (which of the three it is: streamstore.hpp store_room, the rule a stream that stores its rows asks before every block)
+        const uint64_t stored = s.len - s.base;
+        const StoreRoom room = store_room(stored, s.cap, keep_frames(), n_times);
+        if (room.kind == StoreRoom::fits) return;
         if (last_pending) HIP_CHECK(hipDeviceSynchronize());   // a call on another stream may still be appending to this buffer
-        const uint64_t keep = keep_frames();
-        if (keep && stored > keep) {
-            const uint64_t drop = stored - keep;
-            if (drop >= keep && keep + n_times <= s.cap) {         // source and destination do not overlap
-                HIP_CHECK(hipMemcpyAsync(s.buf.p, s.buf.as<float>() + drop, keep * sizeof(float), hipMemcpyDeviceToDevice, st));
-                s.base += drop;
-                return;
-            }
+        if (room.kind == StoreRoom::slide) {                    // source and destination do not overlap
+            HIP_CHECK(hipMemcpyAsync(s.buf.p, s.buf.as<float>() + room.drop, room.kept * sizeof(float), hipMemcpyDeviceToDevice, st));
+            s.base += room.drop;
+            return;
         }
-        const uint64_t kept = keep ? std::min(stored, keep) : stored;
-        const uint64_t cap = keep ? std::max<uint64_t>(2 * (keep + n_times), 1u << 16)
-                                  : std::max<uint64_t>(stored + n_times, std::max<uint64_t>(s.cap * 2, 1u << 20));
         DevBuf nb;
-        nb.ensure(cap * sizeof(float));
-        if (kept) HIP_CHECK(hipMemcpyAsync(nb.p, s.buf.as<float>() + (stored - kept), kept * sizeof(float), hipMemcpyDeviceToDevice, st));
-        s.base += stored - kept;
+        nb.ensure(room.cap * sizeof(float));
+        if (room.kept) HIP_CHECK(hipMemcpyAsync(nb.p, s.buf.as<float>() + room.drop, room.kept * sizeof(float), hipMemcpyDeviceToDevice, st));
+        s.base += room.drop;
         if (s.buf.p) bury(std::move(s.buf), st);
         s.buf = std::move(nb);
-        s.cap = cap;
+        s.cap = room.cap;
     }
 
     // A full-length device-resident row feeding a bank's time slot is not copied here: the bank kernel reads
@@ -1320,8 +1364,7 @@ struct fr_renderer {
         }
         {   // bounded history: what this call may see, and no later call may see more (deterministic whatever slack the
             // buffers happen to hold when a longer Delay arrives)
-            const uint64_t keep = keep_frames();
-            if (keep && idx > keep) history_floor = std::max(history_floor, idx - keep);
+            history_floor = store_floor(history_floor, keep_frames(), idx);
         }
         uint64_t want = (uint64_t)n_slots * n_times;   // `buff.len()`, reference.rs:60 (element count, a quirk)
         if (n_vecs < want) { segs.push_back({n_vecs, want, idx}); n_vecs = want; }
@@ -1722,6 +1765,41 @@ struct fr_renderer {
         append_tracks(n_times, idx, st);
     }
 
+    // A call of ZERO own frames at idx (callplan.hpp bring_up_form): the rings are brought up to idx as the first fr_fill_buffer
+    // call of the plan at idx would bring them before its own frames, sized for calls of `ring_frames` frames -- nothing when they
+    // are current, the look-back rebuild from the STORED history, a feedback plan's replay, FR_RING_KEEP's keep-and-repair.  A
+    // stream that continues the input store (FR_STREAM_STORE) starts its resident launch behind it.  The phases are execute()'s.
+    void bring_up_rings(uint32_t n_slots, uint64_t idx, uint64_t ring_frames, hipStream_t st) {
+        bank_launches.clear();
+        stage_launches.clear();
+        bank_form = "call";
+        deferred.clear();
+        track_dev.clear();
+        reap();
+        call_idx = idx;
+        ensure_plan(n_slots, st);
+        rings_touched = true;
+        const StagedPlan &sp = plan.sp;
+        Call c(nullptr, n_slots, 0, idx, st);
+        try {
+            const RingRepair repair = prepare_rings(c, ring_frames);
+            c.w = call_windows(sp, c);
+            c.form = bring_up_form(sp, c, c.w);
+            repair_rings(c, repair);
+            replay_feedback(c);
+            if (c.w.w_len != 0)
+                for (BankStage &bs : plan.banks)
+                    if (bs.grp.to_ring) launch_bank_window(c, bs, c.w.w0, c.w.w_len, -1);
+            launch_stage_programs(c);
+            commit_rings(c);
+        } catch (...) {
+            plan.stage_valid = false;   // (rings may hold part of the window)
+            ring_table.valid = false;
+            counters_dirty = true;
+            throw;
+        }
+    }
+
     // Rings of at least `cap` floats each for the plan in hand (execute(), begin_program_stream); what they held does not
     // survive a re-allocation.
     void grow_rings(uint64_t cap) {
@@ -1736,7 +1814,7 @@ struct fr_renderer {
 
     // The one step that changes state before the call's windows are decided: the rings get the size the call needs and are
     // kept (FR_RING_KEEP: what the repair must rebuild is returned) or grown.  Fills in what callplan.hpp asks about them.
-    RingRepair prepare_rings(Call &c) {
+    RingRepair prepare_rings(Call &c, uint64_t ring_frames = 0) {
         const StagedPlan &sp = plan.sp;
         ring_state = RingState{};
         if (ring_keep) ring_state.inert = ring_keep_inert();
@@ -1745,7 +1823,7 @@ struct fr_renderer {
         if (sp.feedback && history_frames != 0)
             throw Error(FR_ERR_UNSUPPORTED, "feedback through Delay needs the full input history (fr_config.history_frames = 0)");
         if (!sp.uses_rings()) return repair;
-        const uint64_t cap = ring_capacity(sp, c.n_times);
+        const uint64_t cap = ring_capacity(sp, std::max(c.n_times, ring_frames));   // (ring_frames: the calls a zero-frame bring-up is for)
         const bool table_was_valid = ring_table.valid;
         ring_table.valid = false;            // (until the call is through: a failure leaves nothing to keep)
         if (c.keep_on) {
@@ -2203,16 +2281,11 @@ void fr_renderer::begin_program_stream(uint32_t n_slots) {
     if (!plan_current(n_slots)) throw Error(FR_ERR_UNSUPPORTED, "block streaming: the plan is not current");
     StreamPlan s = plan_stream_now();
     if (!s.servable) throw Error(FR_ERR_UNSUPPORTED, "block streaming (FR_STREAM_PROGRAMS): " + s.reason);
-    std::vector<StageProg> progs(s.progs.size());
-    for (size_t i = 0; i < progs.size(); ++i) {
-        progs[i] = sp.progs[s.progs[i]];
-        const StageProg &pg = progs[i];
-        if ((uint64_t)pg.first_instr + pg.n_instr > sp.instrs.size() || (pg.dst_ring != 0xFFFFFFFFu && pg.dst_ring >= sp.n_rings) || pg.out_row >= (int64_t)n_slots)
-            throw Error(FR_ERR_DEVICE, "internal: a streamed program out of the plan's bounds");
-        for (uint32_t k = 0; k < pg.n_instr; ++k) {
-            const StageInstr &in = sp.instrs[pg.first_instr + k];
-            if ((in.op == S_READ || in.op == S_READ_DYN || in.op == S_STORE) && in.buf >= sp.n_rings) throw Error(FR_ERR_DEVICE, "internal: a streamed program reads a ring the plan does not have");
-        }
+    // a stream that stores its rows (FR_STREAM_STORE): the slots it streams as the store stands (streamstore.hpp); a block may add more
+    std::vector<uint32_t> row_slots = s.input_slots;
+    if (s.store) {
+        std::string why;
+        if (!stream_store_slots(s.input_slots, slots, 0, row_slots, &why)) throw Error(FR_ERR_UNSUPPORTED, "block streaming (FR_STREAM_STORE): " + why);
     }
     if (s.banks.size() != plan.banks.size() || s.banks.size() > BANK_STREAM_BANKS) throw Error(FR_ERR_DEVICE, "internal: the stream's banks are not the plan's");
     // a plan without a voice (FR_STREAM_EFFECTS): its segments are the launch's workgroups, one wave each; no parameters, workspace or tickets
@@ -2226,6 +2299,63 @@ void fr_renderer::begin_program_stream(uint32_t n_slots) {
     }
     Stream::Open o;
     o.launch = stream_launch(sp, s);
+    o.store = s.store;
+    if (o.store) o.launch.n_rows = (uint32_t)row_slots.size();
+    upload_stream_programs(s, o.launch, row_slots, n_slots);
+    begin_program_stream_rest(std::move(o), std::move(s), n_slots);
+}
+
+// The stream's own copy of the plan's programs for a launch whose streamed rows are the slots `row_slots`, in that order
+// (StreamPlan::input_slots; a stream that stores its rows: streamstore.hpp stream_store_slots, again whenever the set grows).
+void fr_renderer::upload_stream_programs(const StreamPlan &s, const StreamLaunch &l, const std::vector<uint32_t> &row_slots, uint32_t n_slots) {
+    const StagedPlan &sp = plan.sp;
+    std::vector<StageProg> progs(s.progs.size());
+    for (size_t i = 0; i < progs.size(); ++i) {
+        progs[i] = sp.progs[s.progs[i]];
+        const StageProg &pg = progs[i];
+        if ((uint64_t)pg.first_instr + pg.n_instr > sp.instrs.size() || (pg.dst_ring != 0xFFFFFFFFu && pg.dst_ring >= sp.n_rings) || pg.out_row >= (int64_t)n_slots)
+            throw Error(FR_ERR_DEVICE, "internal: a streamed program out of the plan's bounds");
+        for (uint32_t k = 0; k < pg.n_instr; ++k) {
+            const StageInstr &in = sp.instrs[pg.first_instr + k];
+            if ((in.op == S_READ || in.op == S_READ_DYN || in.op == S_STORE) && in.buf >= sp.n_rings) throw Error(FR_ERR_DEVICE, "internal: a streamed program reads a ring the plan does not have");
+        }
+    }
+    // the stream's own copy of the programs' instructions (StreamLaunch::own_instrs): the operand of S_INPUT -- and of S_READ_INPUT
+    // and S_READ_INPUT_DYN, FR_STREAM_HISTORY -- the streamed row (the position of its slot in row_slots) instead of the plan's
+    // input index; a loop program's store slots.  (The plan's own instructions, which the ordinary path runs, are not touched.)
+    std::vector<StageInstr> instrs;
+    if (l.own_instrs) {
+        if (row_slots.size() > BANK_STREAM_ROWS) throw Error(FR_ERR_DEVICE, "internal: more streamed rows than the kernel takes");
+        for (size_t i = 0; i < progs.size(); ++i) {
+            StageProg &pg = progs[i];
+            std::vector<StageInstr> own;
+            for (uint32_t k = 0; k < pg.n_instr; ++k) {
+                StageInstr in = sp.instrs[pg.first_instr + k];
+                if (in.op == S_INPUT || in.op == S_READ_INPUT || in.op == S_READ_INPUT_DYN) {
+                    const auto it = in.imm < sp.input_slots.size() ? std::find(row_slots.begin(), row_slots.end(), sp.input_slots[in.imm]) : row_slots.end();
+                    if (it == row_slots.end()) throw Error(FR_ERR_DEVICE, "internal: a streamed program reads a slot the stream does not feed");
+                    in.imm = (uint32_t)(it - row_slots.begin());
+                }
+                own.push_back(in);
+            }
+            if (s.loop_stride[i] != 0 && (!stream_loop_prepare(pg, own) || pg.pad[0] != s.loop_stride[i]))
+                throw Error(FR_ERR_DEVICE, "internal: a loop program the stream cannot prepare");
+            pg.first_instr = (uint32_t)instrs.size();
+            instrs.insert(instrs.end(), own.begin(), own.end());
+        }
+        strm.d_instrs.ensure(std::max<size_t>(instrs.size(), 1) * sizeof(StageInstr));
+        if (!instrs.empty()) HIP_CHECK(hipMemcpyAsync(strm.d_instrs.p, instrs.data(), instrs.size() * sizeof(StageInstr), hipMemcpyHostToDevice, stream));
+    }
+    strm.d_progs.ensure(std::max<size_t>(progs.size(), 1) * sizeof(StageProg));
+    strm.d_vfirst.ensure(s.voice_first.size() * sizeof(uint32_t));
+    if (!progs.empty()) HIP_CHECK(hipMemcpyAsync(strm.d_progs.p, progs.data(), progs.size() * sizeof(StageProg), hipMemcpyHostToDevice, stream));
+    HIP_CHECK(hipMemcpyAsync(strm.d_vfirst.p, s.voice_first.data(), s.voice_first.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    HIP_CHECK(hipStreamSynchronize(stream));   // (host vectors go out of scope)
+}
+
+// (the rest of fr_stream_begin of a plan with programs: the schedules, the rings' size, the history, the buffers)
+void fr_renderer::begin_program_stream_rest(Stream::Open &&o, StreamPlan &&s, uint32_t n_slots) {
+    const StagedPlan &sp = plan.sp;
     const StreamLaunch &l = o.launch;
     // schedule banks (FR_STREAM_GENERAL): every voice's schedule stays inside the bank's items and parameters (the rule has
     // validated its stack); the one-item schedules of balanced 32- and 64-partial banks are built and uploaded here, once
@@ -2257,39 +2387,9 @@ void fr_renderer::begin_program_stream(uint32_t n_slots) {
             HIP_CHECK(hipStreamSynchronize(stream));   // (`words` goes out of scope)
         }
     }
-    // the stream's own copy of the programs' instructions (StreamLaunch::own_instrs): the operand of S_INPUT -- and of S_READ_INPUT
-    // and S_READ_INPUT_DYN, FR_STREAM_HISTORY -- the streamed row (the position of its slot in input_slots) instead of the plan's
-    // input index; a loop program's store slots.  (The plan's own instructions, which the ordinary path runs, are not touched.)
-    std::vector<StageInstr> instrs;
-    if (l.own_instrs) {
-        if (s.input_slots.size() > BANK_STREAM_ROWS) throw Error(FR_ERR_DEVICE, "internal: more streamed rows than the kernel takes");
-        for (size_t i = 0; i < progs.size(); ++i) {
-            StageProg &pg = progs[i];
-            std::vector<StageInstr> own;
-            for (uint32_t k = 0; k < pg.n_instr; ++k) {
-                StageInstr in = sp.instrs[pg.first_instr + k];
-                if (in.op == S_INPUT || in.op == S_READ_INPUT || in.op == S_READ_INPUT_DYN) {
-                    const auto it = in.imm < sp.input_slots.size() ? std::find(s.input_slots.begin(), s.input_slots.end(), sp.input_slots[in.imm]) : s.input_slots.end();
-                    if (it == s.input_slots.end()) throw Error(FR_ERR_DEVICE, "internal: a streamed program reads a slot the stream does not feed");
-                    in.imm = (uint32_t)(it - s.input_slots.begin());
-                }
-                own.push_back(in);
-            }
-            if (s.loop_stride[i] != 0 && (!stream_loop_prepare(pg, own) || pg.pad[0] != s.loop_stride[i]))
-                throw Error(FR_ERR_DEVICE, "internal: a loop program the stream cannot prepare");
-            pg.first_instr = (uint32_t)instrs.size();
-            instrs.insert(instrs.end(), own.begin(), own.end());
-        }
-        strm.d_instrs.ensure(std::max<size_t>(instrs.size(), 1) * sizeof(StageInstr));
-        if (!instrs.empty()) HIP_CHECK(hipMemcpyAsync(strm.d_instrs.p, instrs.data(), instrs.size() * sizeof(StageInstr), hipMemcpyHostToDevice, stream));
-    }
-    strm.d_progs.ensure(std::max<size_t>(progs.size(), 1) * sizeof(StageProg));
-    strm.d_vfirst.ensure(s.voice_first.size() * sizeof(uint32_t));
-    if (!progs.empty()) HIP_CHECK(hipMemcpyAsync(strm.d_progs.p, progs.data(), progs.size() * sizeof(StageProg), hipMemcpyHostToDevice, stream));
-    HIP_CHECK(hipMemcpyAsync(strm.d_vfirst.p, s.voice_first.data(), s.voice_first.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-    HIP_CHECK(hipStreamSynchronize(stream));   // (host vectors go out of scope)
     // rings: the deepest look-back and a block, as execute() sizes them for a 64-frame call (which the seek then finds in place)
-    if (sp.uses_rings()) grow_rings(ring_capacity(sp, STREAM_BLOCK));
+    // (a stream that stores its rows sizes them with its first block's bring-up, which keeps what FR_RING_KEEP can keep)
+    if (sp.uses_rings() && !o.store) grow_rings(ring_capacity(sp, STREAM_BLOCK));
     // the history of the streamed rows (FR_STREAM_HISTORY): hist_cap frames for each of the n_rows rows, zeroed by every seek.  It
     // needs no books of its own next to streamrows.hpp's: what accept() puts into a block's doorbell for a slot -- the row, its
     // padding, +0.0 for a slot without a row or beyond the vector count -- is, frame for frame, what fr_fill_buffer's input store
@@ -2297,7 +2397,7 @@ void fr_renderer::begin_program_stream(uint32_t n_slots) {
     // those words.  After a seek the store answers 0.0 for every earlier frame: the zeroed history, and the kernel's frame >= d.
     if (l.hist_cap) {
         if (l.hist_cap < s.input_lookback + STREAM_BLOCK || (l.hist_cap & (l.hist_cap - 1)) != 0) throw Error(FR_ERR_DEVICE, "internal: the input history does not hold the stream's look-back");
-        strm.d_hist.ensure((size_t)l.n_rows * l.hist_cap * sizeof(float));
+        strm.d_hist.ensure((size_t)(o.store ? BANK_STREAM_ROWS : l.n_rows) * l.hist_cap * sizeof(float));   // (store: the set of rows may grow)
     }
     ensure_stream_buffers(l, n_slots);
     o.prog = true;
@@ -2336,6 +2436,14 @@ void fr_renderer::seek_program_stream(uint64_t idx) {
     }
     plan.stage_valid = false;                    // from here on the rings run ahead of the input store
     ring_table.valid = false;
+    start_resident(idx, true);
+}
+
+// The resident launch of the open stream of the program path at head = idx, the rings standing at idx.  `empty_history`: every
+// frame before idx reads 0.0 (a seek); else the history was filled from the input store (fill_stream_history).
+void fr_renderer::start_resident(uint64_t idx, bool empty_history) {
+    const uint32_t n_slots = strm.now.slots;
+    const StagedPlan &sp = plan.sp;
     const StreamPlan &s = strm.now.plan;
     const StreamLaunch &l = strm.now.launch;
     size_t plan_voices = 0;
@@ -2360,7 +2468,7 @@ void fr_renderer::seek_program_stream(uint64_t idx) {
     if (l.hist_cap) {                                            // every frame before idx reads 0.0 after a seek: an empty history, on the launch's stream
         const size_t bytes = (size_t)l.n_rows * l.hist_cap * sizeof(float);
         if (bytes > strm.d_hist.bytes) throw Error(FR_ERR_DEVICE, "internal: the input history does not hold the stream's look-back");
-        HIP_CHECK(hipMemsetAsync(strm.d_hist.p, 0, bytes, stream));
+        if (empty_history) HIP_CHECK(hipMemsetAsync(strm.d_hist.p, 0, bytes, stream));
         x.h.hist = strm.d_hist.as<float>();
         x.h.mask = l.hist_cap - 1;
     }
@@ -2390,7 +2498,90 @@ void fr_renderer::seek_program_stream(uint64_t idx) {
                          b.grp.fast_ok ? 1u : 0u, b.grp.to_ring ? 1u : 0u};
         }
     }
+    // a stream that stores its rows: the buffers of the slots this launch appends to (streamstore.hpp StoreStreamed; the caller
+    // has made room: stream_store_block_relaunches)
+    if (strm.now.store) {
+        if (strm.now.streamed.size() != l.n_rows || l.n_rows > BANK_STREAM_ROWS) throw Error(FR_ERR_DEVICE, "internal: the streamed slots are not the launch's rows");
+        for (size_t j = 0; j < strm.now.streamed.size(); ++j) {
+            const StoreStreamed &ss = strm.now.streamed[j];
+            if (!ss.has_data) continue;
+            const InSlot &in = slots[ss.slot];
+            if (!in.fed || !in.buf.p || idx < in.base || idx - in.base + STREAM_BLOCK > in.cap || in.cap * sizeof(float) > in.buf.bytes)
+                throw Error(FR_ERR_DEVICE, "internal: a streamed slot's buffer has no room for a block");
+            x.s.row[j] = {in.buf.as<float>(), in.base};
+        }
+    }
     launch_resident(strm.now, x);
+}
+
+// The history of a stream that continues the input store: for each streamed row the hist_cap frames before idx as the store
+// answers them -- 0.0 before a slot's base, below the floor, beyond its length and for a slot never fed.
+void fr_renderer::fill_stream_history(uint64_t idx) {
+    const StreamLaunch &l = strm.now.launch;
+    if (!l.hist_cap) return;
+    const size_t bytes = (size_t)l.n_rows * l.hist_cap * sizeof(float);
+    if (bytes > strm.d_hist.bytes || strm.now.streamed.size() != l.n_rows) throw Error(FR_ERR_DEVICE, "internal: the input history does not hold the stream's look-back");
+    HIP_CHECK(hipMemsetAsync(strm.d_hist.p, 0, bytes, stream));
+    const uint64_t mask = l.hist_cap - 1;
+    for (size_t j = 0; j < strm.now.streamed.size(); ++j) {
+        const DevInput d = dev_input(strm.now.streamed[j].slot);
+        if (!d.data) continue;
+        const uint64_t lo = std::max(d.base, idx > l.hist_cap ? idx - l.hist_cap : 0), hi = std::min(d.len, idx);
+        float *row = strm.d_hist.as<float>() + j * l.hist_cap;
+        for (uint64_t t = lo; t < hi;) {                         // (at most two pieces: the ring wraps once)
+            const uint64_t n = std::min(hi - t, l.hist_cap - (t & mask));
+            HIP_CHECK(hipMemcpyAsync(row + (t & mask), d.data + (t - d.base), n * sizeof(float), hipMemcpyDeviceToDevice, stream));
+            t += n;
+        }
+    }
+}
+
+// A stream that stores its rows (FR_STREAM_STORE), the block [idx, idx + n_times) with rows for the slots [0, rows_fed): the
+// resident launch is (re)started at head = idx.  `seek`: the block does not continue the renderer's head -- the store is reset as
+// store_inputs resets it.  A first launch and a seek bring the rings up to idx (bring_up_rings: a call of zero own frames) and
+// fill the stream's history from the store; a relaunch -- room in a slot's buffer, a slot more -- finds both as the stopped launch
+// left them (a slot more moves the history's rows: then it is filled again from the store, which holds what it held).
+void fr_renderer::launch_store_stream(uint64_t idx, uint32_t rows_fed, bool seek) {
+    HIP_CHECK(hipSetDevice(device));
+    Stream::Open &o = strm.now;
+    bool relaunch = o.launched && !seek;
+    const uint32_t n_slots = o.slots;
+    if (!plan_current(n_slots)) throw Error(FR_ERR_DEVICE, "internal: a stream outlived its plan");
+    std::vector<uint32_t> row_slots;
+    std::string why;
+    // (refused before anything is touched: the launch goes on, everything streamed so far is in the store's books)
+    if (!stream_store_slots(o.plan.input_slots, slots, rows_fed, row_slots, &why)) throw Error(FR_ERR_UNSUPPORTED, "block streaming (FR_STREAM_STORE): " + why);
+    if (!stop_resident(true)) {                  // (the launch did not end as it should: what the rings hold is not known)
+        plan.stage_valid = false;
+        ring_table.valid = false;
+        relaunch = false;
+    }
+    reap();
+    if (seek) {
+        stream_store_seek(slots, segs, n_vecs, idx);
+        head = idx;                              // (the store is empty at idx from here on, whatever becomes of the block: a retry there continues it)
+        o.rows_open = false;
+        history_floor = 0;
+        plan.stage_valid = false;                // whatever the rings hold, they do not hold a seek to idx
+        ring_table.valid = false;
+    }
+    history_floor = store_floor(history_floor, keep_frames(), idx);
+    stream_store_feed(slots, rows_fed, idx);
+    for (uint32_t r = 0; r < rows_fed; ++r) make_room(slots[r], STREAM_BLOCK, stream);   // (a block's room, whatever this block's length)
+    bool same = row_slots.size() == o.streamed.size();
+    for (size_t j = 0; same && j < row_slots.size(); ++j) same = o.streamed[j].slot == row_slots[j];
+    if (!same || o.launch.n_rows != row_slots.size()) {
+        o.launch.n_rows = (uint32_t)row_slots.size();
+        upload_stream_programs(o.plan, o.launch, row_slots, n_slots);
+    }
+    o.streamed.resize(row_slots.size());
+    for (size_t j = 0; j < row_slots.size(); ++j) o.streamed[j] = {row_slots[j], row_slots[j] < rows_fed};
+    // (a relaunch with the same rows: rings and history stand as the stopped launch left them.  With another set of rows the
+    //  history's rows change places: it is filled again from the store, which holds what the history held)
+    if (!relaunch) bring_up_rings(n_slots, idx, STREAM_BLOCK, stream);
+    if (!relaunch || !same) fill_stream_history(idx);
+    if (relaunch) ++o.relaunches;
+    start_resident(idx, false);
 }
 
 namespace {
@@ -2458,6 +2649,7 @@ int64_t env_strict_stream_general(const char *e);
 int64_t env_strict_stream_dyn(const char *e);
 int64_t env_strict_stream_history(const char *e);
 int64_t env_strict_stream_effects(const char *e);
+int64_t env_strict_stream_store(const char *e);
 bool parse_option(const Knob &k, const char *s, int64_t &v);
 
 const Knob kKnobs[] = {
@@ -2565,6 +2757,11 @@ const Knob kKnobs[] = {
     // row, a one-pole smoother on a knob: the programs are dealt over segments, one wave each (streamplan.hpp StreamEnv::effects;
     // fr_plan_json: stream.segments).  Inert without FR_STREAM_PROGRAMS.  Strict and listed once set.
     {"FR_STREAM_EFFECTS", 0, 0, 1, 0, nullptr, 0, env_strict_stream_effects, [](fr_renderer &r, int64_t v, bool) { r.stream_effects = v != 0; }, LISTED_WHEN_SET},
+    // A stream that survives edits: the resident launch appends the rows it is fed to the input store, a stream's first block
+    // continues the renderer's head instead of seeking, and closing a stream leaves the renderer as an ordinary call would
+    // (streamstore.hpp; fr_plan_json: stream.store).  Inert without FR_STREAM_PROGRAMS, with FR_DELAY_OBSERVED=1 and with declared
+    // track slots.  Strict and listed once set.
+    {"FR_STREAM_STORE", 0, 0, 1, 0, nullptr, 0, env_strict_stream_store, [](fr_renderer &r, int64_t v, bool) { r.stream_store = v != 0; }, LISTED_WHEN_SET},
 };
 static_assert(sizeof kKnobs / sizeof kKnobs[0] == N_OPTIONS, "N_OPTIONS counts the rows of kKnobs");
 
@@ -2586,6 +2783,7 @@ int64_t env_strict_stream_general(const char *e) { return env_strict("FR_STREAM_
 int64_t env_strict_stream_dyn(const char *e) { return env_strict("FR_STREAM_DYN", e); }
 int64_t env_strict_stream_history(const char *e) { return env_strict("FR_STREAM_HISTORY", e); }
 int64_t env_strict_stream_effects(const char *e) { return env_strict("FR_STREAM_EFFECTS", e); }
+int64_t env_strict_stream_store(const char *e) { return env_strict("FR_STREAM_STORE", e); }
 
 bool parse_option(const Knob &k, const char *s, int64_t &v) {
     if (k.word && std::strcmp(s, k.word) == 0) {
@@ -3002,21 +3200,41 @@ static void stream_block_rows(fr_renderer *r, float *out, uint64_t n_times, uint
     // the first block of a stream, and a block that does not continue the previous one, is a seek: every slot unfed, every
     // input before idx 0.0.  A refused block changes nothing: the next one may follow as if it had not been made.
     fr_renderer::Stream::Open &o = r->strm.now;
-    const bool seek = !o.have_last || idx != o.head || (o.prog && !o.launched);
+    // (a stream that stores its rows, FR_STREAM_STORE: a block is a seek when it does not continue the RENDERER's head, which every
+    //  answered block moves; the first block of a stream that does continue finds the rows' books in the store)
+    const bool seek = o.store ? idx != r->head : !o.have_last || idx != o.head || (o.prog && !o.launched);
+    if (o.store && !seek && !o.rows_open) {
+        stream_rows_from_store(o.rows, r->n_vecs, r->segs, r->slots, r->last_stored_values());
+        o.rows_open = true;
+    }
     {
         std::string why;
         const StreamRowsStatus rs = o.rows.check(o.slots, n_times, idx, seek, offs, n_rows, &why);
         if (rs != STREAM_ROWS_OK) throw Error(rs == STREAM_ROWS_HISTORY ? FR_ERR_INPUT_HISTORY : FR_ERR_INPUT_TOO_LONG, why);
     }
     // a plan with programs: the rings are brought up to idx and the resident launch starts there
-    if (o.prog && seek) r->seek_program_stream(idx);
+    const uint32_t rows_fed = o.store ? store_rows_taken(o.rows.n_vecs, o.slots, n_times, n_rows) : 0;
+    if (o.store) {
+        // append in place, or (re)launch first: a seek, the stream's first block, a slot more, no room in a slot's buffer
+        if (seek || !o.launched || stream_store_block_relaunches(o.streamed, r->slots, rows_fed, r->keep_frames(), idx, n_times)) {
+            const bool first = !o.have_last && !o.launched;
+            r->launch_store_stream(idx, rows_fed, seek);
+            if (first) o.continued = !seek;
+        } else {
+            r->history_floor = store_floor(r->history_floor, r->keep_frames(), idx);
+        }
+    } else if (o.prog && seek) r->seek_program_stream(idx);
     const auto t_in = std::chrono::steady_clock::now();
     // the rows of the slots the plan reads, padded like short rows of fill_buffer (reference.rs:72-73); a slot without a row: +0.0
     // (a one-row doorbell: StreamPlan::input_slots is {0}, also in a stream of the plain path, which has no plan)
     const uint32_t K = o.launch.n_rows;
     float rows[BANK_STREAM_ROWS][STREAM_ROW_FRAMES];
-    o.rows.accept(o.slots, n_times, idx, seek, in_data, offs, n_rows, o.plan.input_slots.data(), K, rows);
-    r->n_vecs = std::max(r->n_vecs, o.rows.n_vecs);   // (the count the stream reached stays with the renderer)
+    uint32_t want[BANK_STREAM_ROWS] = {0};
+    if (o.store)
+        for (uint32_t j = 0; j < K && j < o.streamed.size(); ++j) want[j] = o.streamed[j].slot;
+    o.rows.accept(o.slots, n_times, idx, seek, in_data, offs, n_rows, o.store ? want : o.plan.input_slots.data(), K, rows);
+    o.rows_open = true;
+    if (!o.store) r->n_vecs = std::max(r->n_vecs, o.rows.n_vecs);   // (the count the stream reached stays with the renderer)
     // every word is tagged with the block's number and length: the words are the doorbell (kernels.hpp BankStreamCtl, BankStreamInCtl)
     o.seq = (o.seq + 1u) & 0xFFFFFFu;
     if (o.seq == 0 || o.seq == 0xFFFFFFu) o.seq = 1;
@@ -3050,6 +3268,7 @@ static void stream_block_rows(fr_renderer *r, float *out, uint64_t n_times, uint
     for (uint32_t v = 0; v < o.slots; ++v) std::memcpy(out + (size_t)v * n_times, res + (size_t)v * 64, n_times * sizeof(float));
     o.head = idx + n_times;
     o.have_last = true;
+    if (o.store) r->commit_streamed_block(rows_fed, idx, n_times);   // (a done tag implies the block's rows are in the store)
     if (r->host_trace) {   // FR_HOST_TRACE=1: inside the call, without the caller's wrapper
         r->strm.trace_us[0] += std::chrono::duration<double, std::micro>(t_done - t_in).count();
         r->strm.trace_us[1] += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_done).count();
@@ -3236,6 +3455,19 @@ const char *fr_plan_json(fr_renderer *r) {
                           (r->stream_general ? std::string(",\"general\":") + (b.general ? "true" : "false") : std::string()) + "}";
                 r->plan_json_cache += ",\"banks\":[" + bl + "],\"workgroups\":" + std::to_string(s.servable && s.voices == 0 ? s.segments : s.workgroups()) +   // (without a voice: the segments)
                                       ",\"max_workgroups\":" + std::to_string(stream_max_wgs((uint32_t)std::max(r->device_cus, 0)));
+            }
+            if (r->stream_store) {                               // FR_STREAM_STORE: whether it acts, the slots such a stream streams, the open stream's first block and relaunches
+                const std::string inert = r->stream_store_inert_now();
+                const fr_renderer::Stream::Open &o = r->strm.now;
+                std::vector<uint32_t> ss;
+                if (r->strm.open && o.store && !o.streamed.empty())
+                    for (const StoreStreamed &x : o.streamed) ss.push_back(x.slot);
+                else if (inert.empty()) (void)stream_store_slots(s.input_slots, r->slots, 0, ss);
+                std::string sl;
+                for (uint32_t n : ss) sl += (sl.empty() ? "" : ",") + std::to_string(n);
+                r->plan_json_cache += std::string(",\"store\":{\"on\":") + (inert.empty() ? "true" : "false") + ",\"slots\":[" + sl + "],\"continued\":" +
+                                      (r->strm.open && o.continued ? "true" : "false") + ",\"relaunches\":" + std::to_string(r->strm.open ? o.relaunches : 0u) +
+                                      ",\"inert\":\"" + inert + "\"}";
             }
             r->plan_json_cache += std::string(",\"kernel\":\"") + kernel + "\"}";
         }

@@ -788,7 +788,7 @@ static hipError_t launch_bank_short(const BankArgs &a, hipStream_t s) {
 
 // ---------------------------------------------------------------------------------------------------
 // Block streaming: the short-call kernel as ONE resident launch (kernels.hpp, BankStreamCtl).  Each step of the protocol is
-// written once, in this section; the skeleton that calls the steps -- stream_resident_body, of which the ten resident
+// written once, in this section; the skeleton that calls the steps -- stream_resident_body, of which the twelve resident
 // kernels are instantiations -- follows stage_kernel, whose interpreter's types it uses.
 //
 // A block.  The host rings a doorbell in mapped pinned memory: every word carries a sample and the block's tag.  Wave 0 of
@@ -2067,7 +2067,7 @@ hipError_t launch_stage(const StageArgs &a, hipStream_t s) {
 }
 
 // ---------------------------------------------------------------------------------------------------
-// The ten resident kernels (kernels.hpp StreamKernel; the pieces and the protocol: above, "Block streaming"): ONE body,
+// The twelve resident kernels (kernels.hpp StreamKernel; the pieces and the protocol: above, "Block streaming"): ONE body,
 // stream_resident_body, instantiated by the kernel's form (kernels.hpp StreamForm).  The body is the protocol's skeleton -- when
 // `alive` is published, the block loop and its stop test, which wave counts a voice in, when LDS may be reused -- and every
 // kernel is the one before it and one thing more:
@@ -2082,9 +2082,11 @@ hipError_t launch_stage(const StageArgs &a, hipStream_t s) {
 //   bank_stream_general_kernel   schedule banks (stream_render_schedule)                              45 072
 //   bank_stream_dyn_kernel       Delays by a signal amount (stream_prog_dyn)                          45 072
 //   bank_stream_hist_kernel      delayed reads of input rows: the rows' history (StreamHistArgs)      45 072
+//   bank_stream_store_kernel     the streamed rows appended to the input store (StreamStoreArgs)      45 072
 //
 // and, beside the cascade, the form without a voice (kernels.hpp bank_stream_fx_kernel): the hist form's programs, doorbell and
 // history with no bank, no render and no hand-over -- a workgroup is ONE wave that runs a segment of programs  32 776
+// (bank_stream_store_fx_kernel: the same, and the streamed rows appended to the input store                 32 776)
 //
 // The bus segment is progs[voice_first[n_voices] .. voice_first[n_voices + 1]) and may be empty.  Which kernel a plan launches
 // is the host's rule (streamplan.hpp; fr_plan_json["stream"]["kernel"]).  The compiled kernels against their earlier,
@@ -2124,6 +2126,18 @@ struct StreamHistoryStore {
         if (lane < T) __hip_atomic_store(hist + (size_t)row * (hmask + 1) + ((head + lane) & hmask), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 };
+// The store forms (kernels.hpp bank_stream_store_kernel): the hist form's Keep, and the same lanes of the same words appended to
+// the renderer's input store -- one more relaxed agent-scope VECTOR store per streamed row under the wait's one acknowledgement.
+// `row` is a constant of the unrolled wait, so s.row[row] is a pair of registers; a slot without a buffer is a uniform skip.
+struct StreamStoreKeep {
+    StreamHistoryStore hist;
+    StreamStoreArgs s;
+    __device__ __forceinline__ void operator()(uint32_t row, float v, uint32_t T) const {
+        hist(row, v, T);
+        float *const data = s.row[row].data;
+        if (data != nullptr && hist.lane < T) __hip_atomic_store(data + (hist.head + hist.lane - s.row[row].base), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+};
 struct StreamHistInput {
     static constexpr bool history = true;
     StreamRowsInput rows;
@@ -2161,8 +2175,8 @@ __device__ __forceinline__ StreamRowsInput stream_input(const BankStreamInDev *d
 // (blockIdx.x - first_wg) whole: its chunk count is 1, so stream_hand_over returns at once.
 static_assert(STREAM_STACK_DEPTH == GB_MAX_DEPTH, "a schedule voice's stack is the general voices'");
 template <StreamKernel K, class Ctl, class Dev>
-__device__ __forceinline__ void stream_resident_body(StreamBanksArgs t, StreamGeneralArgs g, StreamHistArgs h, BankArgs a, StreamProgArgs p, uint32_t n_rows, Ctl *ctl,
-                                                     Dev *dev, uint32_t idle_ms) {
+__device__ __forceinline__ void stream_resident_body(StreamBanksArgs t, StreamGeneralArgs g, StreamHistArgs h, StreamStoreArgs st, BankArgs a, StreamProgArgs p,
+                                                     uint32_t n_rows, Ctl *ctl, Dev *dev, uint32_t idle_ms) {
     constexpr StreamForm F = stream_form(K);
     __shared__ float sm[F.schedule ? 2 : 1][STREAM_NW][64];  // the waves' sums: a chunk's in [0], a schedule's items alternate
     __shared__ float stack_mem[STREAM_STACK_DEPTH][64];      // a schedule voice's evaluation stack: [level][frame] of wave 0
@@ -2216,7 +2230,9 @@ __device__ __forceinline__ void stream_resident_body(StreamBanksArgs t, StreamGe
         uint32_t T;
         const uint32_t seq = stream_next_block(dev, wave, lane, seen, idle_ticks, s_seq, s_T, T, [&](uint32_t &T0) {
             // (the hist form: workgroup 0 keeps the block's rows, at the `head` every workgroup of a progs form carries)
-            if constexpr (F.hist) return stream_doorbell_wait(n_rows, ctl, dev, lane, seen, idle_ticks, T0, StreamHistoryStore{h.hist, h.mask, head, lane});
+            // (the store forms: and appends them to the input store, under the same acknowledgement)
+            if constexpr (F.store) return stream_doorbell_wait(n_rows, ctl, dev, lane, seen, idle_ticks, T0, StreamStoreKeep{{h.hist, h.mask, head, lane}, st});
+            else if constexpr (F.hist) return stream_doorbell_wait(n_rows, ctl, dev, lane, seen, idle_ticks, T0, StreamHistoryStore{h.hist, h.mask, head, lane});
             else return stream_doorbell_wait(n_rows, ctl, dev, lane, seen, idle_ticks, T0, StreamNoHistory{});
         });
         if (seq == BANK_STREAM_STOP) break;
@@ -2262,43 +2278,54 @@ __device__ __forceinline__ void stream_resident_body(StreamBanksArgs t, StreamGe
 }
 
 __global__ void __launch_bounds__(1024) bank_stream_kernel(BankArgs a, BankStreamCtl *ctl, BankStreamDev *dev, uint32_t idle_ms) {
-    stream_resident_body<StreamKernel::plain>({}, {}, {}, a, {}, 1u, ctl, dev, idle_ms);
+    stream_resident_body<StreamKernel::plain>({}, {}, {}, {}, a, {}, 1u, ctl, dev, idle_ms);
 }
 __global__ void __launch_bounds__(1024) bank_stream_prog_kernel(BankArgs a, StreamProgArgs p, BankStreamCtl *ctl, BankStreamDev *dev, uint32_t idle_ms) {
-    stream_resident_body<StreamKernel::prog>({}, {}, {}, a, p, 1u, ctl, dev, idle_ms);
+    stream_resident_body<StreamKernel::prog>({}, {}, {}, {}, a, p, 1u, ctl, dev, idle_ms);
 }
 __global__ void __launch_bounds__(1024) bank_stream_bus_kernel(BankArgs a, StreamProgArgs p, BankStreamCtl *ctl, BankStreamDev *dev, uint32_t idle_ms) {
-    stream_resident_body<StreamKernel::bus>({}, {}, {}, a, p, 1u, ctl, dev, idle_ms);
+    stream_resident_body<StreamKernel::bus>({}, {}, {}, {}, a, p, 1u, ctl, dev, idle_ms);
 }
 __global__ void __launch_bounds__(1024) bank_stream_in_kernel(BankArgs a, StreamProgArgs p, uint32_t n_rows, BankStreamInCtl *ctl, BankStreamInDev *dev, uint32_t idle_ms) {
-    stream_resident_body<StreamKernel::in>({}, {}, {}, a, p, n_rows, ctl, dev, idle_ms);
+    stream_resident_body<StreamKernel::in>({}, {}, {}, {}, a, p, n_rows, ctl, dev, idle_ms);
 }
 __global__ void __launch_bounds__(1024) bank_stream_banks_kernel(StreamBanksArgs t, BankArgs a, StreamProgArgs p, uint32_t n_rows, BankStreamInCtl *ctl,
                                                                  BankStreamInDev *dev, uint32_t idle_ms) {
-    stream_resident_body<StreamKernel::banks>(t, {}, {}, a, p, n_rows, ctl, dev, idle_ms);
+    stream_resident_body<StreamKernel::banks>(t, {}, {}, {}, a, p, n_rows, ctl, dev, idle_ms);
 }
 __global__ void __launch_bounds__(1024) bank_stream_loops_kernel(StreamBanksArgs t, BankArgs a, StreamProgArgs p, uint32_t n_rows, BankStreamInCtl *ctl,
                                                                  BankStreamInDev *dev, uint32_t idle_ms) {
-    stream_resident_body<StreamKernel::loops>(t, {}, {}, a, p, n_rows, ctl, dev, idle_ms);
+    stream_resident_body<StreamKernel::loops>(t, {}, {}, {}, a, p, n_rows, ctl, dev, idle_ms);
 }
 __global__ void __launch_bounds__(1024) bank_stream_general_kernel(StreamBanksArgs t, StreamGeneralArgs g, BankArgs a, StreamProgArgs p, uint32_t n_rows, BankStreamInCtl *ctl,
                                                                    BankStreamInDev *dev, uint32_t idle_ms) {
-    stream_resident_body<StreamKernel::general>(t, g, {}, a, p, n_rows, ctl, dev, idle_ms);
+    stream_resident_body<StreamKernel::general>(t, g, {}, {}, a, p, n_rows, ctl, dev, idle_ms);
 }
 __global__ void __launch_bounds__(1024) bank_stream_dyn_kernel(StreamBanksArgs t, StreamGeneralArgs g, BankArgs a, StreamProgArgs p, uint32_t n_rows, BankStreamInCtl *ctl,
                                                                BankStreamInDev *dev, uint32_t idle_ms) {
-    stream_resident_body<StreamKernel::dyn>(t, g, {}, a, p, n_rows, ctl, dev, idle_ms);
+    stream_resident_body<StreamKernel::dyn>(t, g, {}, {}, a, p, n_rows, ctl, dev, idle_ms);
 }
 __global__ void __launch_bounds__(1024) bank_stream_hist_kernel(StreamBanksArgs t, StreamGeneralArgs g, StreamHistArgs h, BankArgs a, StreamProgArgs p, uint32_t n_rows,
                                                                 BankStreamInCtl *ctl, BankStreamInDev *dev, uint32_t idle_ms) {
-    stream_resident_body<StreamKernel::hist>(t, g, h, a, p, n_rows, ctl, dev, idle_ms);
+    stream_resident_body<StreamKernel::hist>(t, g, h, {}, a, p, n_rows, ctl, dev, idle_ms);
 }
 // (LAUNCHED with one wave per workgroup: a segment of programs needs no more, and nothing is rendered.  The bound stays the other
 // forms': under __launch_bounds__(64) the compiler sees that 32 KiB of LDS leave room for one wave per SIMD and pads the wave's
 // register allocation to 257 VGPRs to say so; with this bound it records the 48 the code uses)
 __global__ void __launch_bounds__(1024) bank_stream_fx_kernel(StreamHistArgs h, BankArgs a, StreamProgArgs p, uint32_t n_rows, BankStreamInCtl *ctl, BankStreamInDev *dev,
                                                             uint32_t idle_ms) {
-    stream_resident_body<StreamKernel::fx>({}, {}, h, a, p, n_rows, ctl, dev, idle_ms);
+    stream_resident_body<StreamKernel::fx>({}, {}, h, {}, a, p, n_rows, ctl, dev, idle_ms);
+}
+
+// The store forms (kernels.hpp StreamStoreArgs): the hist form and the fx form, whose workgroup 0 also appends the streamed rows to
+// the input store.
+__global__ void __launch_bounds__(1024) bank_stream_store_kernel(StreamBanksArgs t, StreamGeneralArgs g, StreamHistArgs h, StreamStoreArgs st, BankArgs a, StreamProgArgs p,
+                                                                 uint32_t n_rows, BankStreamInCtl *ctl, BankStreamInDev *dev, uint32_t idle_ms) {
+    stream_resident_body<StreamKernel::store>(t, g, h, st, a, p, n_rows, ctl, dev, idle_ms);
+}
+__global__ void __launch_bounds__(1024) bank_stream_store_fx_kernel(StreamHistArgs h, StreamStoreArgs st, BankArgs a, StreamProgArgs p, uint32_t n_rows, BankStreamInCtl *ctl,
+                                                                    BankStreamInDev *dev, uint32_t idle_ms) {
+    stream_resident_body<StreamKernel::store_fx>({}, {}, h, st, a, p, n_rows, ctl, dev, idle_ms);
 }
 
 // The one entry of the resident launches (kernels.hpp StreamLaunchArgs): the check, then the kernel with what it takes.
@@ -2322,6 +2349,8 @@ hipError_t launch_bank_stream(StreamKernel k, const StreamLaunchArgs &x, hipStre
     case StreamKernel::dyn: hipLaunchKernelGGL(bank_stream_dyn_kernel, grid, block, 0, s, x.t, x.g, x.a, x.p, x.n_rows, ctl_in, dev_in, idle_ms); break;
     case StreamKernel::hist: hipLaunchKernelGGL(bank_stream_hist_kernel, grid, block, 0, s, x.t, x.g, x.h, x.a, x.p, x.n_rows, ctl_in, dev_in, idle_ms); break;
     case StreamKernel::fx: hipLaunchKernelGGL(bank_stream_fx_kernel, grid, wave, 0, s, x.h, x.a, x.p, x.n_rows, ctl_in, dev_in, idle_ms); break;
+    case StreamKernel::store: hipLaunchKernelGGL(bank_stream_store_kernel, grid, block, 0, s, x.t, x.g, x.h, x.s, x.a, x.p, x.n_rows, ctl_in, dev_in, idle_ms); break;
+    case StreamKernel::store_fx: hipLaunchKernelGGL(bank_stream_store_fx_kernel, grid, wave, 0, s, x.h, x.s, x.a, x.p, x.n_rows, ctl_in, dev_in, idle_ms); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

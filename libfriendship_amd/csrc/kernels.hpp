@@ -352,13 +352,29 @@ struct StreamHistArgs {
 // LDS: the interpreter's registers, the loop tiles and the instruction copy, 32 776 bytes; the waves' sums and the schedule stack
 // of the other forms take none here.
 //
-// The ten resident kernels (streamplan.hpp stream_launch chooses; `none`: no resident launch yet) and their one launch entry.
+// bank_stream_store_kernel, bank_stream_store_fx_kernel (FR_STREAM_STORE): the hist form and the fx form with one thing more --
+// the stream STORES what it is fed.  Workgroup 0's wave 0, which holds every streamed row of the block in registers and stores
+// it to the stream's history, also appends it to the renderer's input store: lane i < n_times of streamed row j goes to
+// row[j].data[head + i - row[j].base], the slot's own buffer (engine.cpp InSlot), where fr_fill_buffer, an edited plan's
+// look-back rebuild and the next stream find it.  data == null: the slot has no buffer -- a launch-uniform skip.  The store is
+// a relaxed agent-scope VECTOR store like the history's, issued with it and acknowledged by the wait's one s_waitcnt vmcnt(0),
+// so before n_times and seq: a done tag the host has seen implies that its block's rows are in the store.  Nothing of the
+// launch reads those words, so no poll, acquire or release is added.  The host (streamstore.hpp) keeps
+// head + n_times - base within the buffer for every slot with a buffer and relaunches before it would not.
+struct StreamStoreArgs {
+    struct Row {
+        float *data;           // the slot's buffer (null: none), data[i] is frame base + i
+        uint64_t base;
+    } row[BANK_STREAM_ROWS];
+};
+
+// The twelve resident kernels (streamplan.hpp stream_launch chooses; `none`: no resident launch yet) and their one launch entry.
 // plain, prog and bus have the one-row doorbell (BankStreamCtl / BankStreamDev), the others the doorbell of rows (BankStreamIn*).
-// (hist is dyn + 2 and fx is hist + 2: the values after dyn and after hist stay unnamed and refused, as the tests of the launch
-// check have always required)
-enum class StreamKernel : uint32_t { none, plain, prog, bus, in, banks, loops, general, dyn, hist = dyn + 2, fx = hist + 2 };
+// (hist is dyn + 2, fx is hist + 2, store is fx + 2 and store_fx is store + 2: the values in between stay unnamed and refused, as
+// the tests of the launch check have always required)
+enum class StreamKernel : uint32_t { none, plain, prog, bus, in, banks, loops, general, dyn, hist = dyn + 2, fx = hist + 2, store = fx + 2, store_fx = store + 2 };
 constexpr bool stream_kernel_named(StreamKernel k) {
-    return k != StreamKernel::none && (k <= StreamKernel::dyn || k == StreamKernel::hist || k == StreamKernel::fx);
+    return k != StreamKernel::none && (k <= StreamKernel::dyn || k == StreamKernel::hist || k == StreamKernel::fx || k == StreamKernel::store || k == StreamKernel::store_fx);
 }
 // A kernel's form: what it has on top of bank_stream_kernel.  The nine kernels with voices are a cascade -- each is the one
 // before it and one thing more --, so the enum's order is their form; fx, which has no voice, is written out.  kernels.hip's one
@@ -372,11 +388,14 @@ struct StreamForm {
     bool schedule;   // schedule banks (StreamGeneralArgs)
     bool dyn;        // the interpreter knows the Delays by a signal amount; a plan need not have a schedule bank
     bool hist;       // the history of the streamed rows (StreamHistArgs): delayed reads of input rows
-    bool voiceless;  // no bank at all: a workgroup is one wave that runs a segment of programs (fx alone)
+    bool voiceless;  // no bank at all: a workgroup is one wave that runs a segment of programs (fx, store_fx)
+    bool store = false;   // workgroup 0 also appends the streamed rows to the input store (StreamStoreArgs): store, store_fx
 };
 constexpr StreamForm stream_form(StreamKernel k) {
     if (k == StreamKernel::fx)   // progs, bus, rows, loops, dyn and hist; no table, no schedule
         return {true, true, true, false, true, false, true, true, true};
+    if (k == StreamKernel::store_fx) return {true, true, true, false, true, false, true, true, true, true};   // fx and the store
+    if (k == StreamKernel::store) return {true, true, true, true, true, true, true, true, false, true};       // hist and the store
     return {k >= StreamKernel::prog,  k >= StreamKernel::bus,     k >= StreamKernel::in,  k >= StreamKernel::banks,
             k >= StreamKernel::loops, k >= StreamKernel::general, k >= StreamKernel::dyn, k == StreamKernel::hist, false};
 }
@@ -386,7 +405,8 @@ struct StreamLaunchArgs {
     StreamProgArgs p;
     StreamBanksArgs t;
     StreamGeneralArgs g;
-    StreamHistArgs h;                           // (read for the hist form alone)
+    StreamHistArgs h;                           // (read for the forms with a history)
+    StreamStoreArgs s;                          // (read for the store forms)
     uint32_t n_rows, max_stride, max_loads, max_stores;
     void *ctl_dev, *dev;                        // the control block as the device addresses it and the device block, of the kernel's doorbell form
     uint32_t idle_ms;                           // 0 = BANK_STREAM_IDLE_MS

@@ -104,6 +104,7 @@ struct StreamEnv {
     bool history = false;            // FR_STREAM_HISTORY: delayed reads of input rows (S_READ_INPUT; with `dyn` S_READ_INPUT_DYN) from the stream's history
     bool effects = false;            // FR_STREAM_EFFECTS: plans without a bank launch: the programs are dealt over segments (StreamPlan::segments)
     bool programs = false;           // FR_STREAM_PROGRAMS: the program path exists (stream_path; plan_stream does not ask)
+    bool store = false;              // FR_STREAM_STORE, and not inert (streamstore.hpp): the launch stores the streamed rows; every plan takes the program path
 };
 
 // One bank of a streamed plan.  Voices [first_voice, first_voice + voices) of the global numbering; workgroups
@@ -200,6 +201,7 @@ struct StreamPlan {
     bool servable = false;
     std::string reason;              // why not ("" when servable)
     uint32_t voices = 0, chunk_log2 = 0, chunks = 0;   // chunks per voice; one bank: the launch has voices * chunks workgroups
+    bool store = false;                  // the launch appends the streamed rows to the input store (StreamEnv::store): the store forms
     uint32_t segments = 0;               // a plan without a voice (StreamEnv::effects): the workgroups its programs are dealt over; 0 for every plan with voices
     bool bank_to_ring = false;
     std::vector<StreamBank> banks;       // one per bank launch, in plan order.  Several: `voices` is their total, `chunks` the
@@ -310,6 +312,7 @@ inline bool stream_loop_prepare(StageProg &pg, std::vector<StageInstr> &ins) {
 // `banks`: the plan's bank launches (the engine moves them out of StagedPlan::banks when it uploads them).
 inline StreamPlan plan_stream(const StagedPlan &sp, const std::vector<const BankLaunch *> &banks, const StreamEnv &env) {
     StreamPlan s;
+    s.store = env.store;
     auto refuse = [&](const std::string &why) {
         s.servable = false;
         s.reason = why;
@@ -638,6 +641,8 @@ inline const char *stream_kernel_name(StreamKernel k) {
                                         "bank_stream_banks_kernel", "bank_stream_loops_kernel", "bank_stream_general_kernel", "bank_stream_dyn_kernel"};
     if (k == StreamKernel::hist) return "bank_stream_hist_kernel";   // (not the value after dyn: that one has no name)
     if (k == StreamKernel::fx) return "bank_stream_fx_kernel";       // (nor the value after hist)
+    if (k == StreamKernel::store) return "bank_stream_store_kernel";
+    if (k == StreamKernel::store_fx) return "bank_stream_store_fx_kernel";
     return names[(uint32_t)k < sizeof names / sizeof names[0] ? (uint32_t)k : 0];
 }
 
@@ -658,10 +663,11 @@ struct StreamLaunch {
 
 // The path fr_stream_begin takes: true = the program path (plan_stream, stream_launch), false = the plain path (one balanced bank
 // that writes the rows: plain_stream_launch).  FR_STREAM_BANKS: several banks take the program path even without programs and
-// rings; FR_STREAM_GENERAL: so does a bank that the option may serve by schedule -- general voices, voices below 128 partials.
+// rings; FR_STREAM_GENERAL: so does a bank that the option may serve by schedule -- general voices, voices below 128 partials;
+// FR_STREAM_STORE (StreamEnv::store): every plan, also the one balanced bank that writes rows.
 inline bool stream_path(const StagedPlan &sp, const std::vector<const BankLaunch *> &banks, const StreamEnv &env) {
     const bool by_schedule = env.general && std::any_of(banks.begin(), banks.end(), [](const BankLaunch *b) { return b->general || b->log2_p < 7; });
-    return env.programs && (!sp.progs.empty() || sp.uses_rings() || (env.banks && banks.size() > 1) || by_schedule);
+    return env.programs && (!sp.progs.empty() || sp.uses_rings() || (env.banks && banks.size() > 1) || by_schedule || env.store);
 }
 
 // The launch of a servable plan of the program path.  The one cascade: hist > dyn > general > loops > banks > in > bus > prog.
@@ -670,16 +676,18 @@ inline bool stream_path(const StagedPlan &sp, const std::vector<const BankLaunch
 // (StreamPlan::has_hist), and no other -- is dyn's composition with the history of the streamed rows.  Ahead of the cascade: fx --
 // a plan without a voice (StreamPlan::voices == 0, FR_STREAM_EFFECTS), and no other --: one workgroup per segment, no bank and
 // no schedule table, and always the history (at least a block per row also when nothing reads it: n_rows x 64 floats spare an
-// eleventh kernel).
+// eleventh kernel).  On top of both: the store forms (StreamPlan::store, FR_STREAM_STORE) -- store for every plan with voices,
+// whatever the cascade would have chosen, store_fx for a plan without; the history is at least a block per row in both, and
+// n_rows counts the plan's slots (a store-mode stream may stream more: streamstore.hpp stream_store_slots, the engine's launch).
 inline StreamLaunch stream_launch(const StagedPlan &sp, const StreamPlan &s) {
     StreamLaunch l;
     const bool fx = s.voices == 0;
-    l.kernel = fx ? StreamKernel::fx : s.has_hist() ? StreamKernel::hist : s.has_dyn() ? StreamKernel::dyn : s.has_general() ? StreamKernel::general : s.has_loops() ? StreamKernel::loops
+    l.kernel = s.store ? (fx ? StreamKernel::store_fx : StreamKernel::store) : fx ? StreamKernel::fx : s.has_hist() ? StreamKernel::hist : s.has_dyn() ? StreamKernel::dyn : s.has_general() ? StreamKernel::general : s.has_loops() ? StreamKernel::loops
                : s.banks.size() > 1 ? StreamKernel::banks : s.input_slots.size() > 1 ? StreamKernel::in : s.bus_programs() ? StreamKernel::bus : StreamKernel::prog;
     l.rows_doorbell = l.own_instrs = l.by_plan = stream_kernel_by_plan(l.kernel);
-    l.bank_table = !fx && l.kernel >= StreamKernel::banks;
+    l.bank_table = !fx && l.kernel >= StreamKernel::banks;   // (fx: also store_fx)
     l.schedule_table = !fx && (l.kernel == StreamKernel::general || (l.kernel >= StreamKernel::dyn && s.has_general()));
-    l.hist_cap = fx || l.kernel == StreamKernel::hist ? stream_hist_cap(s.input_lookback) : 0;
+    l.hist_cap = fx || s.store || l.kernel == StreamKernel::hist ? stream_hist_cap(s.input_lookback) : 0;
     l.n_rows = l.rows_doorbell ? (uint32_t)s.input_slots.size() : 1u;
     for (size_t i = 0; i < s.progs.size(); ++i) {    // (the tiles' fill is counted from the plan's instructions; the store slots are the stored rings)
         if (!s.loop_stride[i]) continue;
