@@ -191,6 +191,26 @@ extern "C" {
  * not a kernel choice, not a status, not a bit.  "stream" gains "store": {"on", "slots" (the slots such a stream streams),
  * "continued" (the open stream's first block continued the store), "relaunches" (since fr_stream_begin), "inert"}, and
  * "kernel" names the two new kernels.
+ *
+ * FR_STREAM_TAPS = 0 / 1 (default 0; read strictly from the environment too; does nothing unless FR_STREAM_PROGRAMS=1): block
+ * streaming also serves SHORT AND SIGNAL DELAYS OF COMPUTED VALUES in a patch without feedback -- "envelope, then effect":
+ * e = env * voice, y = e + 0.5 * Delay(e, 1) (a two-tap low-pass behind an envelope); a chorus behind the ADSR or one chorus on the
+ * mix bus (Delay(e, 40 + 30 * lfo(t)), with FR_STREAM_DYN); FIR stages behind a bus (FR_STREAM_BUS); Delay(In(1) * In(2), 10) in a
+ * patch without a voice (FR_STREAM_EFFECTS).  Such a plan has no one-launch form for fr_fill_buffer either: it runs level by
+ * level.  The stream runs the same levels, in order, inside its one resident launch and adds no kernel: a program that reads,
+ * fewer than 64 frames back (0 included) or by a signal amount, a delay line that an earlier program stores runs behind that
+ * program in the same voice's wave (a patch without a voice: the same segment), which has stored and acknowledged those frames;
+ * one that would follow two voices is a mix bus (FR_STREAM_BUS; refused without it with the mix-bus reason), and so is a reader of
+ * a bus program's delay line.  Same bits as fr_fill_buffer, in both semantics; it composes with every option above
+ * (FR_STREAM_STORE: the tails survive an edit).  With 0 nothing changes: such a plan is refused with "the plan has no fused form
+ * ...", a signal delay of a computed value with the reason it has always had, and every other plan is served and refused, with
+ * the same reasons, by the same kernels.  "stream" gains "levels" (the levels the stream runs; 1 for every plan that was served
+ * before), "short_reads" (ALL the streamed programs' reads below a block of delay lines that programs store, signal reads
+ * included -- not only the reads this option admits: with FR_STREAM_LOOPS a loop's reads of its own delay line, the tap behind a
+ * loop and a feedback patch's row copies count too) and "dyn_ring_reads" (the signal reads among them, which only this option
+ * admits; they count in "dyn_reads" too).  Still refused, each with its reason: a
+ * signal delay inside a feedback loop shorter than a block; a feedback patch that delays a computed value by a signal amount (the
+ * planner refuses it for fr_fill_buffer too); a bound observed from input rows.
  */
 typedef struct fr_option {
     const char *name;              /* e.g. "FR_BANK_SHORT" */

@@ -195,7 +195,7 @@ static std::string stage_variant(const StageLaunchNote &n, const Plan &p) {
     return k;
 }
 
-constexpr size_t N_OPTIONS = 41;        // per-renderer options (friendship_render_ext.h; the table below fr_renderer)
+constexpr size_t N_OPTIONS = 42;        // per-renderer options (friendship_render_ext.h; the table below fr_renderer)
 
 struct TimerClass {
     double ms = 0;
@@ -556,9 +556,9 @@ struct fr_renderer {
         }
         return d_tickets.as<uint32_t>();
     }
-    // FR_STREAM_PROGRAMS, _BUS, _INPUTS, _LOOPS, _BANKS, _GENERAL, _DYN, _HISTORY, _EFFECTS (the options table says what each serves; streamplan.hpp StreamEnv)
+    // FR_STREAM_PROGRAMS, _BUS, _INPUTS, _LOOPS, _BANKS, _GENERAL, _DYN, _HISTORY, _EFFECTS, _STORE, _TAPS (the options table says what each serves; streamplan.hpp StreamEnv)
     bool stream_programs = false, stream_bus = false, stream_inputs = false, stream_loops = false, stream_banks = false, stream_general = false, stream_dyn = false,
-         stream_history = false, stream_effects = false, stream_store = false;
+         stream_history = false, stream_effects = false, stream_store = false, stream_taps = false;
     // Why FR_STREAM_STORE does nothing for this renderer ("": it acts; streamstore.hpp)
     std::string stream_store_inert_now() const { return stream_store_inert(delay_observed, track_from != 0xFFFFFFFFu); }
     std::vector<const BankLaunch *> stream_bank_list() const {
@@ -578,6 +578,7 @@ struct fr_renderer {
         env.banks = stream_banks; env.loops = stream_loops; env.general = stream_general; env.dyn = stream_dyn;
         env.history = stream_history;
         env.effects = stream_effects;
+        env.taps = stream_taps;
         env.store = stream_store && stream_programs && stream_store_inert_now().empty();
         return env;
     }
@@ -2650,6 +2651,7 @@ int64_t env_strict_stream_dyn(const char *e);
 int64_t env_strict_stream_history(const char *e);
 int64_t env_strict_stream_effects(const char *e);
 int64_t env_strict_stream_store(const char *e);
+int64_t env_strict_stream_taps(const char *e);
 bool parse_option(const Knob &k, const char *s, int64_t &v);
 
 const Knob kKnobs[] = {
@@ -2762,6 +2764,11 @@ const Knob kKnobs[] = {
     // (streamstore.hpp; fr_plan_json: stream.store).  Inert without FR_STREAM_PROGRAMS, with FR_DELAY_OBSERVED=1 and with declared
     // track slots.  Strict and listed once set.
     {"FR_STREAM_STORE", 0, 0, 1, 0, nullptr, 0, env_strict_stream_store, [](fr_renderer &r, int64_t v, bool) { r.stream_store = v != 0; }, LISTED_WHEN_SET},
+    // Short and signal delays of computed values in block streaming -- a two-tap FIR behind an envelope, a chorus behind the ADSR or
+    // on the mix bus: a plan without feedback and without a fused form is served in its level form, a reader below a block follows
+    // its storer (streamplan.hpp StreamEnv::taps; fr_plan_json: stream.levels, stream.short_reads, stream.dyn_ring_reads).  Inert
+    // without FR_STREAM_PROGRAMS.  Strict and listed once set.
+    {"FR_STREAM_TAPS", 0, 0, 1, 0, nullptr, 0, env_strict_stream_taps, [](fr_renderer &r, int64_t v, bool) { r.stream_taps = v != 0; }, LISTED_WHEN_SET},
 };
 static_assert(sizeof kKnobs / sizeof kKnobs[0] == N_OPTIONS, "N_OPTIONS counts the rows of kKnobs");
 
@@ -2784,6 +2791,7 @@ int64_t env_strict_stream_dyn(const char *e) { return env_strict("FR_STREAM_DYN"
 int64_t env_strict_stream_history(const char *e) { return env_strict("FR_STREAM_HISTORY", e); }
 int64_t env_strict_stream_effects(const char *e) { return env_strict("FR_STREAM_EFFECTS", e); }
 int64_t env_strict_stream_store(const char *e) { return env_strict("FR_STREAM_STORE", e); }
+int64_t env_strict_stream_taps(const char *e) { return env_strict("FR_STREAM_TAPS", e); }
 
 bool parse_option(const Knob &k, const char *s, int64_t &v) {
     if (k.word && std::strcmp(s, k.word) == 0) {
@@ -3445,6 +3453,9 @@ const char *fr_plan_json(fr_renderer *r) {
                                       ",\"input_lookback\":" + std::to_string(s.input_lookback);
             if (r->stream_effects)                               // FR_STREAM_EFFECTS: the workgroups a plan without a voice is dealt over (0: it has voices)
                 r->plan_json_cache += ",\"segments\":" + std::to_string(s.segments);
+            if (r->stream_taps)                                  // FR_STREAM_TAPS: the levels of the run form, the reads below a block of rings that programs store
+                r->plan_json_cache += ",\"levels\":" + std::to_string(s.levels) + ",\"short_reads\":" + std::to_string(s.short_reads) +
+                                      ",\"dyn_ring_reads\":" + std::to_string(s.dyn_ring_reads);
             const StreamLaunch l = s.servable ? stream_launch(r->plan.sp, s) : StreamLaunch{};
             const char *kernel = stream_kernel_name(l.by_plan ? l.kernel : stream_kernel_by_plan(r->strm.last_kernel) ? StreamKernel::none : r->strm.last_kernel);
             if (r->stream_banks) {                               // FR_STREAM_BANKS: the banks of the launch, in plan order

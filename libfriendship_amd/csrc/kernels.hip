@@ -1216,10 +1216,11 @@ __device__ __forceinline__ float stream_prog_load(const StreamProgArgs &p, const
 
 // A Delay by a signal amount (FR_STREAM_DYN; kernels.hpp bank_stream_dyn_kernel), lane = frame: the reference's cast of the
 // amount (delay_frames, as pull_kernel and stage_kernel), then S_READ_DYN reads the ring `frames` back and S_STEP_DYN yields its
-// constant; 0.0 where the cast fails or the source frame lies before frame 0.  The rule admits bank rings only: this wave (a bus
-// program: every voice) has stored and acknowledged the block's frames, earlier blocks everything older, so the load -- L2's,
-// never a CU's L1: the finisher of a voice changes CU from block to block -- finds any offset in [0, bound].  The index is
-// masked.
+// constant; 0.0 where the cast fails or the source frame lies before frame 0.  The rule admits a bank's ring and (FR_STREAM_TAPS)
+// a ring that an EARLIER program of the same voice, segment or bus segment stores: this wave (a bus program: every voice and every
+// voice's programs) has stored and acknowledged the block's frames -- stream_run_programs waits for its own stores before every
+// program --, earlier blocks everything older, so the load -- L2's, never a CU's L1: the finisher of a voice changes CU from block
+// to block -- finds any offset in [0, bound].  The index is masked.
 __device__ __forceinline__ float stream_prog_dyn(const float *rings, uint64_t ring_mask, uint32_t sparkle, uint32_t op, uint32_t imm, uint32_t buf, float amount,
                                                  uint64_t frame) {
     uint64_t fr;

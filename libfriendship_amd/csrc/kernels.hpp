@@ -306,8 +306,10 @@ struct StreamGeneralArgs {
 // frame.  frames = delay_frames(regs[a][lane]) is the reference's cast (shared with pull_kernel and stage_kernel); S_READ_DYN
 // yields ring[buf][(frame - frames) & ring_mask] when the cast succeeds and frame >= frames, else 0.0; S_STEP_DYN yields
 // bits(imm) under the same condition.  The read is a relaxed agent-scope atomic load like every ring access here: the rule
-// admits only bank rings, whose frames of this block the wave itself (a bus program: every voice) has stored and acknowledged,
-// so no acquire, release, poll or wait is added.  The index is masked: an address is inside the rings whatever the amount.
+// admits a bank's ring and (FR_STREAM_TAPS) a ring that an earlier program of the same voice, segment or bus segment stores,
+// whose frames of this block the wave itself (a bus program: every voice and its programs) has stored and acknowledged -- the
+// interpreter waits for the wave's own stores (s_waitcnt vmcnt(0)) before every program --, so no acquire, release, poll or wait
+// is added.  The index is masked: an address is inside the rings whatever the amount.
 // A plan without schedule banks is launched with mask == 0 (no schedule table).  The loop phases know no _DYN op: the rule
 // refuses one inside a loop program.  LDS: the general kernel's 45 072 bytes.
 

@@ -33,7 +33,8 @@
 // block and binds the program to that voice (or, with FR_STREAM_BUS, makes it a bus program); and S_STEP_DYN, which touches no
 // memory.  The finishing wave has just stored the voice's frames of this block and earlier blocks stored everything older, so
 // every such offset is readable and still nobody waits (kernels.hip bank_stream_dyn_kernel).  A signal delay of a ring that a
-// program stores, one inside a loop program, a delayed read of an input row and a bound observed from input rows stay refused.
+// program stores (without FR_STREAM_TAPS), one inside a loop program, a delayed read of an input row and a bound observed from
+// input rows stay refused.
 // With FR_STREAM_HISTORY=1 (StreamEnv::history) a program may read an INPUT ROW at a delay -- a pre-delay on a control row, a
 // delayed gate, Delay(In(0), d) on the time row itself: S_READ_INPUT at any constant delay, 0..63 included, in per-voice, bus and
 // loop programs (there it is one more frame-only load); with FR_STREAM_DYN also S_READ_INPUT_DYN, whose amount is anything in
@@ -51,6 +52,15 @@
 // g % segments, segments = min(groups, stream_max_wgs): no plan is refused for its number of rows.  A segment stands where a
 // voice stood -- voice_first has segments + 2 entries -- and still nobody waits: a read below a block is of a ring the same wave
 // stored, a deeper one of an earlier block's frames.  Every other check applies to these programs unchanged.
+// With FR_STREAM_TAPS=1 (StreamEnv::taps) a plan WITHOUT feedback that has no fused form -- a computed value delayed by fewer than 64
+// frames or by a signal amount: a two-tap FIR behind an envelope, a chorus behind the ADSR or on the mix bus -- is served in its
+// LEVEL FORM: `run` is every level's programs in level order, the row copies included.  The rule that FR_STREAM_LOOPS has for the
+// level behind a loop holds for every level: an S_READ below 64 frames, 0 included, of a ring that an EARLIER program of `run`
+// stores binds the reader to the storer's voice (group), so the same wave stored those frames and acknowledged them before the
+// reader's loads; a reader that would follow two is a bus program (FR_STREAM_BUS, else the mix-bus refusal), and so is a reader of
+// a ring that an earlier bus program stores.  With FR_STREAM_DYN also S_READ_DYN of such a ring: its offset is anything in
+// [0, d_lo], a read below a block whatever the bound.  Still nobody waits.  A feedback plan and a plan with a fused form are what
+// they were; a storer that comes later in `run`, and an S_READ_DYN of a ring that no earlier program stores, stay refused.
 // HOW a served plan is launched is one rule as well (stream_path, stream_launch, plain_stream_launch, at the end): the path, the
 // kernel, its doorbell form, its tables, the loop limits, the workgroups.  fr_stream_begin, the seek, the block, the stop and
 // fr_plan_json's "kernel" read the StreamLaunch it returns and decide nothing themselves.
@@ -103,6 +113,7 @@ struct StreamEnv {
     bool dyn = false;                // FR_STREAM_DYN: Delays of a voice by a signal amount (S_READ_DYN of a bank's ring, S_STEP_DYN)
     bool history = false;            // FR_STREAM_HISTORY: delayed reads of input rows (S_READ_INPUT; with `dyn` S_READ_INPUT_DYN) from the stream's history
     bool effects = false;            // FR_STREAM_EFFECTS: plans without a bank launch: the programs are dealt over segments (StreamPlan::segments)
+    bool taps = false;               // FR_STREAM_TAPS: the level form of a plan without feedback; short and signal delays of a ring an earlier program stores
     bool programs = false;           // FR_STREAM_PROGRAMS: the program path exists (stream_path; plan_stream does not ask)
     bool store = false;              // FR_STREAM_STORE, and not inert (streamstore.hpp): the launch stores the streamed rows; every plan takes the program path
 };
@@ -221,6 +232,10 @@ struct StreamPlan {
     uint32_t dyn_reads = 0;              // the assigned programs' S_READ_DYNs (StreamEnv::dyn) ...
     uint32_t dyn_steps = 0;              // ... and their S_STEP_DYNs
     bool has_dyn() const { return dyn_reads + dyn_steps != 0; }
+    uint32_t levels = 1;                 // the levels of the run form (StreamEnv::taps); 1 for a fused or one-level plan
+    uint32_t short_reads = 0;            // ALL the assigned programs' reads below a block of rings that programs store -- a loop program's own-ring
+                                         // reads, the tap behind a loop and a feedback plan's row copies as well as what StreamEnv::taps admits --, ...
+    uint32_t dyn_ring_reads = 0;         // ... of which S_READ_DYNs (counted in dyn_reads too)
     uint32_t hist_reads = 0;             // the assigned programs' S_READ_INPUTs (StreamEnv::history) ...
     uint32_t hist_dyn_reads = 0;         // ... and their S_READ_INPUT_DYNs
     uint64_t input_lookback = 0;         // the deepest input read of the assigned programs: S_READ_INPUT's d_lo, S_READ_INPUT_DYN's proven bound (its buf)
@@ -397,10 +412,16 @@ inline StreamPlan plan_stream(const StagedPlan &sp, const std::vector<const Bank
         size_t levels = 0, only = 0;
         for (size_t l = 0; l + 1 < sp.level_first.size(); ++l)
             if (sp.level_first[l + 1] > sp.level_first[l]) { ++levels; only = l; }
-        if (levels != 1)
+        if (levels != 1 && !env.taps)
             return refuse("the plan has no fused form: a program's ring is read less than " + std::to_string(STREAM_BLOCK) +
                           " frames back (or the fused programs exceed the interpreter's budget)");
-        for (uint32_t i = sp.level_first[only]; i < sp.level_first[only + 1]; ++i) run.push_back(i);
+        if (levels == 1) {
+            for (uint32_t i = sp.level_first[only]; i < sp.level_first[only + 1]; ++i) run.push_back(i);
+        } else {                                     // FR_STREAM_TAPS: the level form itself, level by level, its row copies included
+            for (size_t l = 0; l + 1 < sp.level_first.size(); ++l)
+                for (uint32_t i = sp.level_first[l]; i < sp.level_first[l + 1]; ++i) run.push_back(i);
+            s.levels = (uint32_t)levels;
+        }
     }
     if (voiceless && run.empty()) return refuse("block streaming of a plan with neither voices nor programs");
     std::unordered_map<uint32_t, uint32_t> bank_ring_voice;   // ring -> voice whose frames it holds
@@ -424,6 +445,10 @@ inline StreamPlan plan_stream(const StagedPlan &sp, const std::vector<const Bank
     const std::string whom = voiceless ? "program groups" : "voices", one_whom = voiceless ? "program group" : "voice";
     std::vector<uint32_t> voice_of(run.size(), NONE);
     const bool loops = env.loops && sp.feedback;              // FR_STREAM_LOOPS concerns a feedback plan's one-launch form
+    const bool taps = env.taps && !sp.feedback;               // FR_STREAM_TAPS concerns every other plan
+    // a read below a block of a ring that an EARLIER program of `run` stores binds the reader to the storer's voice (group): the
+    // level behind a loop (loops), any level of a level form (taps)
+    const bool follows = loops || taps;
     std::vector<uint32_t> stride_of(run.size(), 0);
     // FR_STREAM_BUS: a program is a bus program when, at a delay below a block, it reads the bank rings of two or more voices
     // or a ring that an earlier bus program stores (a feedback plan's row copy of such a ring included)
@@ -433,8 +458,8 @@ inline StreamPlan plan_stream(const StagedPlan &sp, const std::vector<const Bank
         uint32_t one = NONE;
         for (uint32_t i = 0; i < pg.n_instr; ++i) {
             const StageInstr &in = sp.instrs[pg.first_instr + i];
-            const bool dyn_read = env.dyn && in.op == S_READ_DYN;   // (of a bank's ring: its offset may be below a block whatever its bound)
-            if (dyn_read && bank_ring_voice.find(in.buf) == bank_ring_voice.end()) continue;
+            const bool dyn_read = env.dyn && in.op == S_READ_DYN;   // (its offset may be below a block whatever its bound)
+            if (dyn_read && !taps && bank_ring_voice.find(in.buf) == bank_ring_voice.end()) continue;   // (of a program's ring: refused below)
             if (!dyn_read && (in.op != S_READ || in.d_lo >= STREAM_BLOCK)) continue;
             auto bv = bank_ring_voice.find(in.buf);
             if (bv != bank_ring_voice.end()) {
@@ -444,7 +469,7 @@ inline StreamPlan plan_stream(const StagedPlan &sp, const std::vector<const Bank
             }
             auto st = stored_by.find(in.buf);
             if (st != stored_by.end() && st->second < k && voice_of[st->second] == BUS) return true;
-            if (loops && st != stored_by.end() && st->second < k) {   // a tap behind a loop: it follows the storer's voice
+            if (follows && st != stored_by.end() && st->second < k) {   // a tap behind a loop, a level behind a level: it follows the storer's voice
                 if (one != NONE && one != voice_of[st->second]) return true;
                 one = voice_of[st->second];
             }
@@ -459,8 +484,17 @@ inline StreamPlan plan_stream(const StagedPlan &sp, const std::vector<const Bank
         return std::string("a program uses ") + stage_op_name(op) + (op == S_READ_INPUT ? " (a delayed read of the input row)" : " (a Delay by a signal amount)") +
                ", which block streaming does not serve yet";
     };
+    // The reader of a ring that an earlier program stores, below a block: it follows the storer's voice (group) -- `mine` -- or, when
+    // it already follows another, is refused ("" : it follows)
+    auto follow = [&](uint32_t &mine, uint32_t theirs) {
+        if (mine != NONE && mine != theirs)
+            return "a program reads " + whom + " " + std::to_string(mine) + " and " + std::to_string(theirs) + " in the same block (a mix bus across " + whom +
+                   "); each streamed program follows one " + one_whom;
+        mine = theirs;
+        return std::string();
+    };
     uint64_t min_delay = UINT64_MAX;
-    uint32_t n_dyn_reads = 0, n_dyn_steps = 0, n_hist_reads = 0, n_hist_dyn_reads = 0;
+    uint32_t n_dyn_reads = 0, n_dyn_steps = 0, n_hist_reads = 0, n_hist_dyn_reads = 0, n_short = 0, n_dyn_ring_reads = 0;
     for (uint32_t k = 0; k < run.size(); ++k) {
         const StageProg &pg = sp.progs[run[k]];
         const bool copy = k >= first_copy;
@@ -521,12 +555,13 @@ inline StreamPlan plan_stream(const StagedPlan &sp, const std::vector<const Bank
                     auto st = stored_by.find(in.buf);
                     if (st != stored_by.end() && st->second == k) {
                         min_delay = std::min<uint64_t>(min_delay, in.d_lo);
+                        ++n_short;
                         break;                                       // (its stride: stream_loop_stride, below)
                     }
                 }
                 if (bus && in.d_lo < STREAM_BLOCK) {                 // a ring an EARLIER program of the block stores: it has finished
                     auto st = stored_by.find(in.buf);
-                    if (st != stored_by.end() && st->second < k) break;
+                    if (st != stored_by.end() && st->second < k) { ++n_short; break; }
                     return refuse("a program's ring is read " + std::to_string(in.d_lo) + " frames back; a streamed block needs delays of at least " +
                                   std::to_string(STREAM_BLOCK) + " frames");
                 }
@@ -534,17 +569,16 @@ inline StreamPlan plan_stream(const StagedPlan &sp, const std::vector<const Bank
                     auto st = stored_by.find(in.buf);
                     if (st == stored_by.end() || voice_of[st->second] == NONE) return refuse("internal: a row copy of a ring no streamed program stores");
                     mine = voice_of[st->second];
+                    ++n_short;
                     break;
                 }
-                if (loops && in.d_lo < STREAM_BLOCK) {               // a ring an EARLIER program stores, on one voice: the level behind a loop
+                if (follows && in.d_lo < STREAM_BLOCK) {             // a ring an EARLIER program stores, on one voice: the level behind a loop or a level
                     auto st = stored_by.find(in.buf);
                     if (st != stored_by.end() && st->second < k) {
-                        const uint32_t theirs = voice_of[st->second];
-                        if (mine != NONE && mine != theirs)
-                            return refuse("a program reads " + whom + " " + std::to_string(mine) + " and " + std::to_string(theirs) +
-                                          " in the same block (a mix bus across " + whom + "); each streamed program follows one " + one_whom);
-                        mine = theirs;
+                        const std::string two = follow(mine, voice_of[st->second]);
+                        if (!two.empty()) return refuse(two);
                         min_delay = std::min<uint64_t>(min_delay, in.d_lo);
+                        ++n_short;
                         break;
                     }
                 }
@@ -561,9 +595,20 @@ inline StreamPlan plan_stream(const StagedPlan &sp, const std::vector<const Bank
                     return refuse("a Delay's bound was observed from input rows (FR_DELAY_OBSERVED); a stream stores no rows, so block streaming does not serve it");
                 if (in.op == S_STEP_DYN) { ++n_dyn_steps; break; }  // touches no memory
                 auto bv = bank_ring_voice.find(in.buf);
-                if (bv == bank_ring_voice.end())
-                    return refuse("a program uses S_READ_DYN of a ring that a program stores (a Delay of a computed value by a signal amount, which may be 0 "
-                                  "frames); block streaming serves signal delays of voices only");
+                if (bv == bank_ring_voice.end()) {
+                    // FR_STREAM_TAPS: a ring an EARLIER program of `run` stores -- whatever the bound a read below a block, as of a voice
+                    auto st = stored_by.find(in.buf);
+                    if (!(taps && st != stored_by.end() && st->second < k))
+                        return refuse("a program uses S_READ_DYN of a ring that a program stores (a Delay of a computed value by a signal amount, which may be 0 "
+                                      "frames); block streaming serves signal delays of voices only");
+                    s.lookback = std::max<uint64_t>(s.lookback, in.d_lo);
+                    ++n_dyn_reads; ++n_dyn_ring_reads; ++n_short;
+                    if (bus) break;                                 // every earlier program of the block has finished
+                    const std::string two = follow(mine, voice_of[st->second]);
+                    if (!two.empty()) return refuse(two);
+                    min_delay = 0;                                  // (the amount may be 0 frames)
+                    break;
+                }
                 s.lookback = std::max<uint64_t>(s.lookback, in.d_lo);
                 ++n_dyn_reads;
                 if (bus) break;                                     // every voice of the block has finished
@@ -628,6 +673,8 @@ inline StreamPlan plan_stream(const StagedPlan &sp, const std::vector<const Bank
     s.min_ring_delay = min_delay == UINT64_MAX ? 0 : min_delay;
     s.dyn_reads = n_dyn_reads;
     s.dyn_steps = n_dyn_steps;
+    s.short_reads = n_short;
+    s.dyn_ring_reads = n_dyn_ring_reads;
     s.hist_reads = n_hist_reads;
     s.hist_dyn_reads = n_hist_dyn_reads;
     s.input_slots.insert(s.input_slots.end(), others.begin(), others.end());
