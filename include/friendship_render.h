@@ -31,6 +31,11 @@
  * Errors: the reference's trait methods return () and panic on contract violations
  * (reference.rs:69,71,131,145,186,199...).  Here every call returns an fr_status; a conforming shim
  * turns non-zero into panic!.  Nothing in this library aborts the process.
+ *
+ * Feedback: a dependency cycle is rendered when it passes a Delay of a constant >= 1 frames, and refused with FR_ERR_CYCLE
+ * otherwise.  The opt-in engine option FR_LOOP_DYN (friendship_render_ext.h) also renders a cycle whose Delay has a SIGNAL
+ * amount -- a flanger with regeneration, a comb with vibrato, a tape echo whose time wobbles -- when the engine can prove the
+ * amount >= 1 frame at every frame and never NaN, as the reference's recursion renders it.
  */
 #ifndef FRIENDSHIP_RENDER_H
 #define FRIENDSHIP_RENDER_H
@@ -63,7 +68,10 @@ enum {
                                       edge); FR_ERR_UNSUPPORTED where this engine has no evaluator for
                                       it: FR_MODE_PULL, history_frames != 0, FR_SHARD_PARTIALS, a loop
                                       reached by a row left to the pull interpreter, a seek of more
-                                      than 2^28 frames (a loop's state is rebuilt by replay from 0)  */
+                                      than 2^28 frames (a loop's state is rebuilt by replay from 0).
+                                      With FR_LOOP_DYN: also a Delay of a signal amount proven >= 1
+                                      frame and never NaN ends the recursion; one that cannot be
+                                      proven so keeps this status, the message names the interval    */
     FR_ERR_DEVICE = 7,             /* HIP runtime failure; see fr_last_error                       */
     FR_ERR_NO_DEVICE = 8,          /* no gfx950 device / HIP code object unusable                  */
     FR_ERR_OUT_OF_MEMORY = 9,

@@ -88,6 +88,25 @@ extern "C" {
  * (taps at d and 2d), a program of more than 16 frame-only loads or 12 stores, a Delay of a signal amount -- the tiled
  * launches' "variant" carries +tile, and "stage_jit_form" gains "tile".  With the option unset nothing changes.
  *
+ * FR_LOOP_DYN = 0 / 1 / 2 (default 0; read strictly from the environment too): feedback through a Delay of a SIGNAL amount --
+ * a flanger with regeneration, a comb or plucked string with vibrato, a tape echo x = in + g Delay(x, base + depth lfo(t)).
+ * With 0 such a cycle is FR_ERR_CYCLE as ever, every message, plan and kernel unchanged.  With 1 or 2 a cycle that has no Delay
+ * of a constant >= 1 frames on it is cut at its innermost Delay of a signal amount, and the plan is served when interval
+ * arithmetic over the amount's expression proves it never NaN, >= 1.0 and < 2^31; the bound in frames is floor(lo) of the
+ * interval, which is widened outward at every step: 1 + lfo is NOT provable (lo falls below 1), 2 + lfo is, with bound 1, and
+ * 8 + 6 Minimum(1, Modulo(In1 r, 1)) has bound 7, not 8.  An amount fed by a raw input row can be NaN: write the clamp as
+ * Minimum(c, x) with the constant on the LEFT, which is free of NaN in both semantics.  Not provable: FR_ERR_CYCLE, the
+ * message names the lowered node and the interval.  A signal tap of a delay line its own loop stores needs the same proof
+ * (a bound of 0 frames there: FR_ERR_UNSUPPORTED); a tap behind the loop needs none.  Such a plan is a sweep plan: W, the
+ * least bound of the loops' reads of their own delay lines, frames at a time are independent.  1 renders each level of loops in
+ * ONE launch of stage_sweep_kernel (a workgroup per loop, min(W, 256) frames per sweep, a barrier between sweeps); 2 renders the
+ * same programs through stage_kernel, one launch per W frames -- the cross-check and the baseline.  Same bits either way.  The
+ * programs run on the interpreter (stage_jit_form null); FR_LOOP_TILES and FR_RING_KEEP are inert for a sweep plan (their reasons
+ * say so), block streaming refuses it, FR_SHARD_PARTIALS, FR_MODE_PULL and history_frames refuse it as they refuse every
+ * feedback plan.  Once set, fr_plan_json gains "loop_dyn" {sweep: W, frames: min(W, 256), form: "sweep" | "windows" | "",
+ * reason}, and the launches' "variant" reads stage_sweep_kernel/feedback+sweep, stage_sweep_kernel/replay+sweep or
+ * stage_kernel/windows.
+ *
  * FR_STREAM_LOOPS = 0 / 1 (default 0; read strictly from the environment too; does nothing unless FR_STREAM_PROGRAMS=1):
  * block streaming also serves feedback loops shorter than a block -- y = a x + b Delay(y, 1), a comb or plucked string
  * x = voice + g Delay(x, d) with d < 64, a master filter or a 32-frame echo on a bus (with FR_STREAM_BUS) -- and what reads a

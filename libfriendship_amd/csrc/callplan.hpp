@@ -169,6 +169,7 @@ struct LoopTile {
 inline LoopTile loop_tile(const StagedPlan &sp, bool enabled) {
     LoopTile lt;
     if (!sp.feedback) return lt;
+    if (sp.fused_sweep) { lt.reason = "a loop delays by a signal amount (a sweep plan, FR_LOOP_DYN: no stride to tile)"; return lt; }
     if (!enabled) { lt.reason = "FR_LOOP_TILES is off"; return lt; }
     if (sp.fused_stride < 1 || sp.fused_stride > LOOP_TILE_MAX_STRIDE) {
         lt.reason = "the loops' stride is " + std::to_string(sp.fused_stride) + " frames (1.." + std::to_string(LOOP_TILE_MAX_STRIDE) + " are tiled)";
@@ -200,6 +201,40 @@ inline LoopTile loop_tile(const StagedPlan &sp, bool enabled) {
     }
     lt.frames = (uint32_t)(sp.fused_stride * (LOOP_TILE_FRAMES / sp.fused_stride));
     return lt;
+}
+
+// Sweeps (FR_LOOP_DYN): the launches of a sweep plan (stage.hpp StagedPlan::fused_sweep = W: frames [b, b + W) depend only on
+// frames < b) -- the steady call, the replay after a seek, the edit path: every launch of the fused programs.
+//  sweep   (option 1): each fused level is ONE launch of stage_sweep_kernel, a workgroup per program that renders the window
+//          `frames` = min(W, LOOP_SWEEP_MAX) frames at a time, a thread per frame, a barrier between two sweeps (a shorter
+//          sweep than W is as valid: the bound only has to hold);
+//  windows (option 2): the same programs through stage_kernel, unchanged, one launch of stride 0 per W frames, level by level
+//          inside each window -- an evaluator that rests only on a kernel the other forms have proven, and the baseline the
+//          sweep kernel is measured against.
+// A plan that is no sweep plan: none, and `reason` says why ("" without feedback: the option does not concern it).
+constexpr uint32_t LOOP_SWEEP_MAX = 256;
+struct LoopSweep {
+    enum Form { none, kernel, windows } form = none;   // (kernel: the sweep form)
+    uint64_t sweep = 0;              // W
+    uint32_t frames = 0;             // min(W, LOOP_SWEEP_MAX): StageArgs::sweep of the sweep form
+    std::string reason;
+    const char *form_name() const { return form == kernel ? "sweep" : form == windows ? "windows" : ""; }
+};
+inline LoopSweep loop_sweep(const StagedPlan &sp, int option) {
+    LoopSweep ls;
+    if (!sp.feedback) return ls;
+    if (option == 0) { ls.reason = "FR_LOOP_DYN is off"; return ls; }
+    if (sp.fused_sweep == 0) { ls.reason = "no loop delays by a signal amount: the strided form serves the plan"; return ls; }
+    ls.sweep = sp.fused_sweep;
+    ls.frames = (uint32_t)std::min<uint64_t>(sp.fused_sweep, LOOP_SWEEP_MAX);
+    if (option == 2) {
+        ls.form = LoopSweep::windows;
+        ls.reason = "FR_LOOP_DYN=2: stage_kernel, one launch per " + std::to_string(ls.sweep) + " frames and level";
+    } else {
+        ls.form = LoopSweep::kernel;
+        ls.reason = "every read of a loop's own ring reaches at least " + std::to_string(ls.sweep) + " frames back: sweeps of " + std::to_string(ls.frames) + " frames";
+    }
+    return ls;
 }
 
 }  // namespace fr

@@ -130,6 +130,7 @@ struct Plan {
     const FlatGraph *graph = nullptr;    // the lowered graph the plan was made from (Lowering::update: stable)
     bool observed_stale = false;         // FR_DELAY_OBSERVED: stored rows widened an input range past a planned look-back
     LoopTile loop_tile;                  // FR_LOOP_TILES (callplan.hpp loop_tile): frames per tile of the strided launches, 0: not tiled
+    LoopSweep loop_sweep;                // FR_LOOP_DYN (callplan.hpp loop_sweep): the launch form of a sweep plan's fused programs
     std::string json;
 };
 
@@ -152,6 +153,8 @@ struct StageLaunchNote {
     bool carry, carry_only, table;       // use_carry (stage_kernel's LDS carry), carry_only, input table in device memory
     uint32_t grid_parts;                 // launches of at most 65535 programs (grid.y) it was cut into
     bool tile = false;                   // FR_LOOP_TILES: stage_tile_kernel / jit_stage_tile
+    uint32_t sweep = 0;                  // FR_LOOP_DYN: 1 = stage_sweep_kernel (frames = the window, stride = frames per sweep),
+                                         // 2 = one window of the windows form (stage_kernel, stride 0)
 };
 
 // fr_plan_json "stage_jit_form": the #defines plan_stage_jit wrote for the plan's compiled programs, null when interpreted.
@@ -181,12 +184,15 @@ static uint32_t stage_hoisted_max(const StagedPlan &sp) {
 // after the carry flag (tests/loop_tile_cases.py).
 static std::string stage_variant(const StageLaunchNote &n, const Plan &p) {
     std::string k = "stage_kernel";
-    if (n.jit && n.tile) k = std::string("jit_stage[tile") + (p.stage_jit_form.maxp ? ",P" : "") + "]";
+    // (FR_LOOP_DYN: stage_sweep_kernel/feedback+sweep, stage_sweep_kernel/replay+sweep; the windows form: stage_kernel/windows)
+    if (n.sweep == 1) k = "stage_sweep_kernel";
+    else if (n.jit && n.tile) k = std::string("jit_stage[tile") + (p.stage_jit_form.maxp ? ",P" : "") + "]";
     else if (n.jit) {
         const StageJitPlan &f = p.stage_jit_form;
         k = std::string("jit_stage[") + (f.deep ? "deep" : "plain") + (f.maxp ? ",P" : "") + (f.defer ? ",defer" : "") + ",B" + std::to_string(f.blk) + "]";
     }
-    k += std::string("/") + n.form;
+    k += std::string("/") + (n.sweep == 2 ? "windows" : n.form);
+    if (n.sweep == 1) k += "+sweep";
     if (n.carry_only) k += "+carry_only";
     else if (n.carry) k += "+carry";
     if (n.tile) k += "+tile";
@@ -195,7 +201,7 @@ static std::string stage_variant(const StageLaunchNote &n, const Plan &p) {
     return k;
 }
 
-constexpr size_t N_OPTIONS = 42;        // per-renderer options (friendship_render_ext.h; the table below fr_renderer)
+constexpr size_t N_OPTIONS = 43;        // per-renderer options (friendship_render_ext.h; the table below fr_renderer)
 
 struct TimerClass {
     double ms = 0;
@@ -222,6 +228,22 @@ __attribute__((weak)) hipError_t launch_input_range(const RangeArgs &a, hipStrea
     return hipSuccess;
 }
 
+// The sweep launch (FR_LOOP_DYN, kernels.hpp launch_stage_sweep) as a host loop for the simulator, whose launch_stage it calls a
+// sweep at a time: sweeps in order, and inside one the order that launch_stage takes for the threads of any launch -- programs
+// last to first, frames last to first --, the least favourable one the kernel's threads could take.
+__attribute__((weak)) hipError_t launch_stage_sweep(const StageArgs &a, hipStream_t s) {
+    if (a.n_progs == 0 || a.w_len == 0) return hipSuccess;
+    if (a.n_progs > 65535u || a.sweep == 0 || a.sweep > STAGE_SWEEP_MAX || a.stride != 0 || a.tile != 0 || a.use_carry != 0) return hipErrorInvalidValue;
+    StageArgs one = a;
+    one.sweep = 0;
+    for (uint64_t base = 0; base < a.w_len; base += a.sweep) {   // (a sweep: one frame per thread, no stride)
+        one.w0 = a.w0 + base;
+        one.w_len = std::min<uint64_t>(a.sweep, a.w_len - base);
+        const hipError_t e = launch_stage(one, s);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
 // Host loops of the track-history launches for the simulator, the same pattern as launch_input_range above.
 __attribute__((weak)) hipError_t launch_track_tail(const TrackTailArgs &a, hipStream_t) {
     const uint64_t cap = a.mask + 1;
@@ -726,6 +748,11 @@ struct fr_renderer {
     // Loop tiles (FR_LOOP_TILES, callplan.hpp loop_tile): the strided launches of feedback plans of short strides render tiles
     // staged in LDS.  `loop_tiles_given`: the option was set (either way): fr_plan_json then shows "loop_tiles".
     bool loop_tiles = false, loop_tiles_given = false;
+    // Feedback through a Delay of a signal amount (FR_LOOP_DYN; callplan.hpp loop_sweep): 0 = such loops are FR_ERR_CYCLE, 1 = their
+    // plans run on stage_sweep_kernel, 2 = on stage_kernel a window of W frames at a time.  `loop_dyn_given`: the option was set
+    // (to anything): fr_plan_json then shows "loop_dyn".
+    int loop_dyn = 0;
+    bool loop_dyn_given = false;
     struct RingEntry { uint64_t generation; std::vector<uint32_t> key; uint64_t valid_from; };
     struct RingTable {
         bool valid = false;
@@ -759,6 +786,8 @@ struct fr_renderer {
         //  holds what the full history gave, a rebuilt one what the floored history gives: the option would change bits.)
         if (history_frames != 0) return "bounded input history";
         if (!sp.uses_rings()) return "no delay lines";
+        // (what a kept loop's repair replays is decided per ring by the constant delays its readers use; a sweep plan's are signals)
+        if (sp.fused_sweep) return "a loop delays by a signal amount";
         return "";
     }
     static std::vector<uint32_t> ring_key(const StagedPlan &sp, uint32_t r) {
@@ -1463,6 +1492,7 @@ struct fr_renderer {
         uint32_t lower_lo = 0, lower_hi = UINT32_MAX;
         if (sharded() && shard.mode == FR_SHARD_VOICES) my_rows(n_slots, lower_lo, lower_hi);
         // (partial-block sharding: every rank must arrive at the same node ids -- the exchange is ordered by them)
+        lowering.set_loop_dyn(loop_dyn != 0);
         const FlatGraph &fg = lowering.update(mirror, n_slots, lower_lo, lower_hi, sharded() && shard.mode == FR_SHARD_PARTIALS);
         const double lower_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
         p.max_depth = fg.max_depth;
@@ -1474,7 +1504,7 @@ struct fr_renderer {
         p.graph = &fg;
         const ObservedInputs obs = observed_inputs(st);
         const ObservedInputs *observed = delay_observed ? &obs : nullptr;
-        p.sp = plan_stages(fg, mode == FR_MODE_AUTO, mode != FR_MODE_PULL, 20, use_jit, allow_template, matcher.get(), shard_spec, track_from, observed, track_history, loop_tiles);
+        p.sp = plan_stages(fg, mode == FR_MODE_AUTO, mode != FR_MODE_PULL, 20, use_jit, allow_template, matcher.get(), shard_spec, track_from, observed, track_history, loop_tiles, loop_dyn != 0);
         renumber_rings(p.sp);
         std::vector<std::shared_ptr<JitKernel>> jits(p.sp.banks.size());
         p.jit_epoch = jit_cache.epoch();   // (read first: a compile finishing from here on makes this plan stale)
@@ -1501,7 +1531,7 @@ struct fr_renderer {
                     throw Error(FR_ERR_DEVICE, std::string("a kernel of the sharded plan could not be compiled on this rank (every rank must plan alike): ") + e.what());
             }
             if (without) {
-                p.sp = plan_stages(fg, true, true, 20, false, true, nullptr, shard_spec, track_from, observed, track_history, loop_tiles);
+                p.sp = plan_stages(fg, true, true, 20, false, true, nullptr, shard_spec, track_from, observed, track_history, loop_tiles, loop_dyn != 0);
                 renumber_rings(p.sp);
                 jits.assign(p.sp.banks.size(), nullptr);
             }
@@ -1538,7 +1568,9 @@ struct fr_renderer {
             HIP_CHECK(hipMemcpyAsync(p.d_progs.p, p.sp.progs.data(), p.sp.progs.size() * sizeof(StageProg), hipMemcpyHostToDevice, st));
             StageJitPlan sj;
             p.loop_tile = loop_tile(p.sp, loop_tiles);
-            if (allow_jit && stage_jit_mode != 0 && plan_stage_jit(p.sp.progs, p.sp.instrs, 32, stage_jit_mode == 2, sj, mirror.sparkle,
+            p.loop_sweep = loop_sweep(p.sp, loop_dyn);
+            // (a sweep plan runs on the interpreter: there are no generated sweep programs)
+            if (allow_jit && stage_jit_mode != 0 && !p.sp.fused_sweep && plan_stage_jit(p.sp.progs, p.sp.instrs, 32, stage_jit_mode == 2, sj, mirror.sparkle,
                                                                               stage_block_env ? stage_block_env : (p.sp.feedback ? 16u : 1u),
                                                                               p.sp.feedback && p.sp.fused_carry_only, p.loop_tile.frames)) {
                 try {
@@ -1623,6 +1655,9 @@ struct fr_renderer {
         if (loop_tiles_given)
             js << ",\"loop_tiles\":{\"frames\":" << p.loop_tile.frames << ",\"max_stride\":" << LOOP_TILE_MAX_STRIDE << ",\"reason\":\""
                << p.loop_tile.reason << "\"}";
+        if (loop_dyn_given)
+            js << ",\"loop_dyn\":{\"sweep\":" << p.loop_sweep.sweep << ",\"frames\":" << p.loop_sweep.frames << ",\"form\":\"" << p.loop_sweep.form_name()
+               << "\",\"reason\":\"" << p.loop_sweep.reason << "\"}";
         js
            << ",\"track_history\":" << track_history << ",\"track_lookback\":" << p.sp.track_lookback
            << ",\"track_window_slots\":" << p.sp.track_window_slots.size()
@@ -2052,7 +2087,9 @@ struct fr_renderer {
         }
     }
     // What a stage launch is for (StageLaunchNote::form) and the frames its threads stride by (0: one frame per thread).
-    struct StageLaunch { const char *form; uint64_t stride; };
+    // `sweep` (FR_LOOP_DYN): the frames per sweep of a stage_sweep_kernel launch (0: stage_kernel / jit_stage); `window`: the
+    // launch is one window of the windows form.
+    struct StageLaunch { const char *form; uint64_t stride; uint32_t sweep = 0; bool window = false; };
     // The fields JitStageArgs and StageArgs share.
     template <class Args>
     void fill_stage_args(Args &a, const Call &c, const StageLaunch &how, uint64_t s0, uint64_t slen, bool carry_only) const {
@@ -2076,8 +2113,8 @@ struct fr_renderer {
                                   ? plan.loop_tile.frames : 0u;
         const size_t n_inline = std::min<size_t>(stage_tab.size(), STAGE_INLINE_INPUTS);
         if (count && stage_launches.size() < 256)
-            stage_launches.push_back({how.form, plan.stage_jit != nullptr, count, slen, how.stride, carry, carry_only,
-                                      stage_tab.size() > STAGE_INLINE_INPUTS, (count - 1) / 65535u + 1, tile != 0});
+            stage_launches.push_back({how.form, plan.stage_jit != nullptr, count, slen, how.sweep ? how.sweep : how.stride, carry, carry_only,
+                                      stage_tab.size() > STAGE_INLINE_INPUTS, (count - 1) / 65535u + 1, tile != 0, how.sweep ? 1u : how.window ? 2u : 0u});
         for (uint32_t off = 0; off < count; off += 65535u) {
             const uint32_t n = std::min<uint32_t>(count - off, 65535u);
             Scope sc(this, &t_stage, c.st);
@@ -2101,7 +2138,8 @@ struct fr_renderer {
                 a.use_carry = carry ? 1u : 0u;
                 a.sparkle = mirror.sparkle ? 1u : 0u;
                 a.tile = tile;
-                HIP_CHECK(launch_stage(a, c.st));
+                a.sweep = how.sweep;
+                HIP_CHECK(how.sweep ? launch_stage_sweep(a, c.st) : launch_stage(a, c.st));
             }
             sc.done();
         }
@@ -2109,8 +2147,22 @@ struct fr_renderer {
     // A feedback plan's fused form: a strided launch per level.
     void launch_fused_levels(const Call &c, const char *form, uint64_t s0, uint64_t slen) {
         const StagedPlan &sp = plan.sp;
+        // A sweep plan (FR_LOOP_DYN, callplan.hpp loop_sweep): a sweep launch per level, or the windows form -- the window cut into
+        // W frames, the levels inside each.  The strided form is not valid for it (there is no stride).
+        const LoopSweep &ls = plan.loop_sweep;
+        if (sp.fused_sweep && ls.form == LoopSweep::none) throw Error(FR_ERR_DEVICE, "internal: a sweep plan without a launch form");
+        if (ls.form == LoopSweep::windows) {
+            for (uint64_t done = 0; done < slen;) {
+                const uint64_t len = std::min<uint64_t>(ls.sweep, slen - done);
+                for (size_t l = 0; l + 1 < sp.fused_level_first.size(); ++l)
+                    launch_range(c, {form, 0, 0, true}, sp.fused_first + sp.fused_level_first[l], sp.fused_level_first[l + 1] - sp.fused_level_first[l], s0 + done, len);
+                done += len;
+            }
+            return;
+        }
+        const uint32_t sweep = ls.form == LoopSweep::kernel ? ls.frames : 0u;
         for (size_t l = 0; l + 1 < sp.fused_level_first.size(); ++l)
-            launch_range(c, {form, sp.fused_stride}, sp.fused_first + sp.fused_level_first[l], sp.fused_level_first[l + 1] - sp.fused_level_first[l], s0, slen);
+            launch_range(c, {form, sp.fused_stride, sweep}, sp.fused_first + sp.fused_level_first[l], sp.fused_level_first[l + 1] - sp.fused_level_first[l], s0, slen);
     }
 
     // ---- the call's phases ----
@@ -2645,6 +2697,7 @@ int64_t env_strict_stream_bus(const char *e);
 int64_t env_strict_stream_inputs(const char *e);
 int64_t env_strict_stream_banks(const char *e);
 int64_t env_strict_loop_tiles(const char *e);
+int64_t env_strict_loop_dyn(const char *e);
 int64_t env_strict_stream_loops(const char *e);
 int64_t env_strict_stream_general(const char *e);
 int64_t env_strict_stream_dyn(const char *e);
@@ -2769,6 +2822,14 @@ const Knob kKnobs[] = {
     // its storer (streamplan.hpp StreamEnv::taps; fr_plan_json: stream.levels, stream.short_reads, stream.dyn_ring_reads).  Inert
     // without FR_STREAM_PROGRAMS.  Strict and listed once set.
     {"FR_STREAM_TAPS", 0, 0, 1, 0, nullptr, 0, env_strict_stream_taps, [](fr_renderer &r, int64_t v, bool) { r.stream_taps = v != 0; }, LISTED_WHEN_SET},
+    // Feedback through a Delay of a signal amount -- a flanger with regeneration, a comb with vibrato, a tape echo whose time
+    // wobbles: a loop with no constant Delay on it is cut at its Delay of a signal amount when the amount is proven >= 1 frame and
+    // never NaN, and its plan runs W frames at a time: 1 = on stage_sweep_kernel, 2 = on stage_kernel, a launch per W frames
+    // (callplan.hpp loop_sweep; fr_plan_json: loop_dyn, the launches' +sweep and /windows).  Strict and listed once set.
+    {"FR_LOOP_DYN", 0, 0, 2, 0, nullptr, 0, env_strict_loop_dyn, [](fr_renderer &r, int64_t v, bool given) {
+         r.loop_dyn = (int)v;
+         r.loop_dyn_given = given;
+     }, LISTED_WHEN_SET},
 };
 static_assert(sizeof kKnobs / sizeof kKnobs[0] == N_OPTIONS, "N_OPTIONS counts the rows of kKnobs");
 
@@ -2785,6 +2846,7 @@ int64_t env_strict_stream_bus(const char *e) { return env_strict("FR_STREAM_BUS"
 int64_t env_strict_stream_inputs(const char *e) { return env_strict("FR_STREAM_INPUTS", e); }
 int64_t env_strict_stream_banks(const char *e) { return env_strict("FR_STREAM_BANKS", e); }
 int64_t env_strict_loop_tiles(const char *e) { return env_strict("FR_LOOP_TILES", e); }
+int64_t env_strict_loop_dyn(const char *e) { return env_strict("FR_LOOP_DYN", e); }
 int64_t env_strict_stream_loops(const char *e) { return env_strict("FR_STREAM_LOOPS", e); }
 int64_t env_strict_stream_general(const char *e) { return env_strict("FR_STREAM_GENERAL", e); }
 int64_t env_strict_stream_dyn(const char *e) { return env_strict("FR_STREAM_DYN", e); }

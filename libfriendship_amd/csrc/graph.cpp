@@ -656,6 +656,10 @@ struct Lowering::Impl {
         for (size_t i = stack.size(); i-- > 0;)
             if (stack[i].ctx == cycle_at.ctx && stack[i].node == cycle_at.node) { bottom = i; break; }
         if (bottom == stack.size()) return false;   // (in progress but not on this stack: cannot happen on one thread)
+        // FR_LOOP_DYN: a second pass, only when the first found no constant Delay of >= 1 frames, takes the innermost Delay whose
+        // amount is NOT a constant (an edge from another node or an input row); the planner must then prove the amount >= 1
+        // frame at every frame (stage.cpp), or the plan is FR_ERR_CYCLE there
+        for (int pass = 0; pass < (loop_dyn ? 2 : 1); ++pass)
         for (size_t i = stack.size(); i-- > bottom;) {
             Frame &d = stack[i];
             if (d.node->kind != FR_PRIM_DELAY || d.next != 0) continue;
@@ -663,7 +667,8 @@ struct Lowering::Impl {
                 // straight from the constant node (a Delay by 0 frames on the loop is a pass-through: try the next one out)
                 const EdgeRef amt = d.node->inbound.size() > 1 ? d.node->inbound[1] : EdgeRef{};
                 const MNode *src = (amt.present && amt.from != 0) ? find(d.ctx, amt.from) : nullptr;
-                if (!src || src->kind != FR_PRIM_F32CONSTANT || !(f32_from_bits(amt.from_slot) >= 1.0f)) continue;
+                const bool constant = !amt.present || (src && src->kind == FR_PRIM_F32CONSTANT);
+                if (pass == 0 ? (!src || src->kind != FR_PRIM_F32CONSTANT || !(f32_from_bits(amt.from_slot) >= 1.0f)) : constant) continue;
             }
             for (size_t k = stack.size(); k-- > i + 1;) memo.get(key(stack[k].ctx, stack[k].node)) = 0;
             stack.resize(i + 1);
@@ -711,7 +716,9 @@ struct Lowering::Impl {
                     // the Delay that cuts a cycle must move time back by at least one frame, every time (reference.rs:200-215:
                     // NaN and negative amounts are 0 frames)
                     const float d = fg.is_const(f.vals[1]) ? fg.const_val(f.vals[1]) : 0.0f;
-                    if (!fg.is_const(f.vals[1]) || !(d >= 1.0f))
+                    if (loop_dyn && !fg.is_const(f.vals[1])) {
+                        // (FR_LOOP_DYN: a signal amount; stage.cpp proves it >= 1 frame or refuses the plan)
+                    } else if (!fg.is_const(f.vals[1]) || !(d >= 1.0f))
                         throw Error(FR_ERR_CYCLE, std::string("dependency cycle closed through a Delay whose amount is ") +
                                                       (fg.is_const(f.vals[1]) ? "less than one frame" : "a signal") +
                                                       ": only feedback through a constant Delay of >= 1 frames is evaluable");
@@ -758,6 +765,7 @@ struct Lowering::Impl {
     };
     struct alignas(128) ParCellsNext { uint32_t v = 0; char pad[124]; };
     ParCellsNext par_cells_next_s;   // (its own cache line, like FlatGraph's id counter)
+    bool loop_dyn = false;        // FR_LOOP_DYN (Lowering::set_loop_dyn): cut_cycle may cut at a Delay of a signal amount
     bool allow_parallel = true;   // (ids then depend on thread timing; Lowering::update's `deterministic` turns it off)
     uint64_t par_items = 0;       // sub-trees the last update lowered on threads
 
@@ -1112,6 +1120,7 @@ uint64_t Lowering::generation() const { return impl_->generation; }
 bool Lowering::last_was_full() const { return impl_->was_full; }
 uint64_t Lowering::last_relowered() const { return impl_->relowered; }
 uint64_t Lowering::last_parallel_subtrees() const { return impl_->par_items; }
+void Lowering::set_loop_dyn(bool on) { impl_->loop_dyn = on; }
 void Lowering::set_parallel(unsigned threads, size_t min_nodes, size_t min_edit) {
     impl_->par_configured = true;
     impl_->par_threads_set = std::max(1u, threads);

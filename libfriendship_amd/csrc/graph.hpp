@@ -519,6 +519,9 @@ public:
     // A renderer's FR_LOWER_THREADS / FR_LOWER_PAR_MIN_NODES / FR_LOWER_PAR_MIN_EDIT.  Until this is called, every from-scratch
     // lowering reads them from the environment.
     void set_parallel(unsigned threads, size_t min_nodes, size_t min_edit);
+    // A renderer's FR_LOOP_DYN: a dependency cycle with no Delay of a constant >= 1 frames on it is cut at its innermost Delay of a
+    // signal amount (set before the first update(); the planner proves the amount or refuses the plan).
+    void set_loop_dyn(bool on);
 
 private:
     struct Impl;

@@ -1902,7 +1902,8 @@ __global__ void __launch_bounds__(256) stage_kernel(StageArgs a) {
         for (uint32_t i = 0; i < STAGE_MAX_HOISTED; ++i)
             if (i < pg.n_loads) tmp[fetch(i).dst][tid] = ld[i];
     }
-    // 2. everything else in program order
+    // 2. everything else in program order  (stage_sweep_kernel below has its own copy of this step, stage_tile_kernel a third: a
+    //    change to an op or a new S_* case goes into all of them)
     for (uint32_t i = pg.n_loads; i < pg.n_instr; ++i) {
         const StageInstr in = fetch(i);
         float v;
@@ -2064,6 +2065,77 @@ hipError_t launch_stage(const StageArgs &a, hipStream_t s) {
     if (bx > 0x7FFFFFFFull) return hipErrorInvalidValue;
     const size_t carry_bytes = a.use_carry ? (size_t)2 * STAGE_CARRY * 256 * sizeof(float) : 0;
     hipLaunchKernelGGL(stage_kernel, dim3((uint32_t)bx, a.n_progs), dim3(256), carry_bytes, s, a);
+    return hipGetLastError();
+}
+
+// Sweeps (kernels.hpp launch_stage_sweep, callplan.hpp loop_sweep): a feedback plan whose loops delay by a signal amount has no
+// stride that binds a thread to its own stores, but a proven bound: every read of a ring the program stores reaches at least
+// a.sweep frames back.  ONE workgroup per program walks the window a.sweep frames at a time, thread = frame of the sweep, each
+// thread the whole program for its frame exactly as stage_kernel runs it (stage_load, delay_frames, prim_mod, prim_min, the
+// S_*_DYN case, the same stores under the same conditions).  Between two sweeps every thread waits for its own stores
+// (s_waitcnt vmcnt(0): on gfx950 stores count there) and the workgroup passes a barrier: the waves of a workgroup share their
+// CU's vector cache, which writes through, so a plain load after the barrier sees a plain store from before it.  Every thread
+// reaches every barrier -- the loop's bounds are uniform, threads beyond the sweep's frames only skip the work --, every loop
+// is bounded by w_len, nothing polls.  A workgroup of one wave (sweep <= 64) pays the wait alone: its barrier has nobody to wait for.
+__global__ void __launch_bounds__(256) stage_sweep_kernel(StageArgs a) {
+    __shared__ float tmp[STAGE_REGS][256];
+    const StageProg pg = a.progs[blockIdx.y];
+    const uint32_t tid = threadIdx.x;
+    const StageInstr *gins = a.instrs + pg.first_instr;
+    const size_t ring_cap = (size_t)a.ring_mask + 1;
+    const uint32_t sweep = a.sweep;
+    for (uint64_t base = 0; base < a.w_len; base += sweep) {
+        const uint64_t left = a.w_len - base;
+        if (tid < sweep && tid < left) {
+            const uint64_t t = a.w0 + base + tid;
+            {   // 1. the program's hoisted loads, in flight together
+                float ld[STAGE_MAX_HOISTED];
+#pragma unroll
+                for (uint32_t i = 0; i < STAGE_MAX_HOISTED; ++i)
+                    if (i < pg.n_loads) ld[i] = stage_load(a, gins[i], t);
+#pragma unroll
+                for (uint32_t i = 0; i < STAGE_MAX_HOISTED; ++i)
+                    if (i < pg.n_loads) tmp[gins[i].dst][tid] = ld[i];
+            }
+            // 2. everything else in program order
+            for (uint32_t i = pg.n_loads; i < pg.n_instr; ++i) {
+                const StageInstr in = gins[i];
+                float v;
+                switch (in.op) {
+                case S_SUM2: v = tmp[in.a][tid] + tmp[in.b][tid]; break;
+                case S_MUL: v = tmp[in.a][tid] * tmp[in.b][tid]; break;
+                case S_DIV: v = tmp[in.a][tid] / tmp[in.b][tid]; break;
+                case S_MOD: v = prim_mod(tmp[in.a][tid], tmp[in.b][tid]); break;
+                case S_MIN: v = prim_min(tmp[in.a][tid], tmp[in.b][tid], a.sparkle != 0u); break;
+                case S_STORE: a.rings[(size_t)in.buf * ring_cap + (t & a.ring_mask)] = tmp[in.a][tid]; continue;
+                case S_READ_DYN: case S_READ_INPUT_DYN: case S_STEP_DYN: {   // Delay by a signal amount (reference.rs:200-215)
+                    uint64_t fr;
+                    v = 0.0f;
+                    if (delay_frames(tmp[in.a][tid], fr, a.sparkle != 0u) && t >= fr) {
+                        if (in.op == S_READ_DYN) v = a.rings[(size_t)in.buf * ring_cap + ((t - fr) & a.ring_mask)];
+                        else if (in.op == S_READ_INPUT_DYN) v = stage_input(a, in.imm, t - fr);
+                        else v = __uint_as_float(in.imm);
+                    }
+                    break;
+                }
+                default: v = stage_load(a, in, t); break;   // a load that was not hoisted (register budget)
+                }
+                tmp[in.dst][tid] = v;
+            }
+            const float r = tmp[pg.result_reg][tid];
+            if (pg.dst_ring != 0xFFFFFFFFu) a.rings[(size_t)pg.dst_ring * ring_cap + (t & a.ring_mask)] = r;
+            if (pg.out_row >= 0 && t >= a.idx) a.out[(size_t)pg.out_row * a.n_times + (t - a.idx)] = r;
+        }
+        // the sweep's ring stores are in memory before any thread of the workgroup starts the next sweep
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+    }
+}
+
+hipError_t launch_stage_sweep(const StageArgs &a, hipStream_t s) {
+    if (a.n_progs == 0 || a.w_len == 0) return hipSuccess;
+    if (a.n_progs > 65535u || a.sweep == 0 || a.sweep > STAGE_SWEEP_MAX || a.stride != 0 || a.tile != 0 || a.use_carry != 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(stage_sweep_kernel, dim3(1, a.n_progs), dim3(64u * ((a.sweep + 63u) / 64u)), 0, s, a);
     return hipGetLastError();
 }
 

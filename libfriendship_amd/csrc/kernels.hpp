@@ -137,7 +137,8 @@ enum StageOp : uint8_t {
     S_STORE = 10,      // ring[buf][t & mask] = a        (fused form: an inlined cut node still feeds its ring)
     // Delay with a signal amount (register a, evaluated at t): frames = amount -> u64 as reference.rs:200-211
     // (>= 2^64 -> output 0; negative/NaN -> 0 frames; else floor), then as the constant forms.  d_lo = proven bound.
-    S_READ_DYN = 11,        // dst = ring[buf] at t - frames
+    S_READ_DYN = 11,        // dst = ring[buf] at t - frames         (imm: 0, but in the fused programs of a sweep plan -- FR_LOOP_DYN,
+                            //  StagedPlan::fused_sweep != 0 -- the amount's proven LOWER bound in frames; no evaluator reads it)
     S_READ_INPUT_DYN = 12,  // dst = input[imm] at t - frames         (buf = the amount's proven bound, 0xFFFFFFFF: none; no evaluator reads it)
     S_STEP_DYN = 13,        // dst = t >= frames ? bits(imm) : 0
 };
@@ -181,6 +182,7 @@ struct StageArgs {
     uint32_t use_carry;        // the programs carry annotations (feedback plans): the launch gets the carry's LDS
     uint32_t tile;             // 0: stage_kernel.  Else (callplan.hpp loop_tile, FR_LOOP_TILES) stage_tile_kernel: one wave per program
                                // renders the window in tiles of this many frames -- a multiple of `stride`, at most STAGE_TILE_FRAMES
+    uint32_t sweep;            // launch_stage_sweep only (callplan.hpp loop_sweep, FR_LOOP_DYN): frames per sweep, 1..STAGE_SWEEP_MAX
 };
 // stage_tile_kernel's LDS: the tile's frame-only loads and its stores as [slot][frame in tile]
 constexpr uint32_t STAGE_TILE_FRAMES = 256, STAGE_TILE_LOADS = 16, STAGE_TILE_STORES = 12;
@@ -191,6 +193,13 @@ constexpr uint32_t STAGE_TILE_FRAMES = 256, STAGE_TILE_LOADS = 16, STAGE_TILE_ST
 // ring is one the program stores) takes it from there, except in the thread's first iteration of the launch.  0 = no carry.
 constexpr uint32_t STAGE_CARRY = 8;
 hipError_t launch_stage(const StageArgs &a, hipStream_t s);
+// Sweeps (FR_LOOP_DYN): stage_sweep_kernel, one workgroup of 64 * ceil(sweep / 64) threads per program.  For base = 0, sweep,
+// 2 sweep ... < w_len, thread f < min(sweep, w_len - base) runs the whole program for frame w0 + base + f with stage_kernel's
+// arithmetic and stores; the sweep's stores are then waited for and a workgroup barrier passed before any thread starts the next
+// sweep.  Valid when every read of a ring that the program stores reaches at least `sweep` frames back (StagedPlan::fused_sweep);
+// `stride`, `carry_only`, `use_carry` and `tile` must be 0.  Ring indices are masked, whatever the amount.
+constexpr uint32_t STAGE_SWEEP_MAX = 256;
+hipError_t launch_stage_sweep(const StageArgs &a, hipStream_t s);
 
 // ---- block streaming of plans with programs (FR_STREAM_PROGRAMS, streamplan.hpp) ----------------------------------------
 // bank_stream_prog_kernel: bank_stream_kernel with an epilogue.  Wave 0 of the workgroup that finishes voice v holds the

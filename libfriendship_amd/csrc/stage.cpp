@@ -14,6 +14,7 @@
 
 #include "range.hpp"
 
+#include <sstream>
 #include <algorithm>
 #include <cmath>
 #include <memory>
@@ -74,6 +75,16 @@ struct Planner {
     // Delay of an INPUT by a signal amount -> the amount's proven bound, where it has one.  The ordinary path needs none (dyn_max
     // says so); block streaming, whose input history is finite, reads it (S_READ_INPUT_DYN's `buf`; streamplan.hpp FR_STREAM_HISTORY).
     std::unordered_map<uint32_t, uint64_t> input_dyn_bound;
+    // FR_LOOP_DYN, feedback plans: the signal Delays of computed values carry their proven LOWER bound in frames too (dyn_lo;
+    // S_READ_DYN's imm): floor(lo) of the amount's widened interval, 0 where the amount may be NaN (NaN delays by 0 frames).
+    bool loop_dyn = false;
+    uint64_t dyn_lo(uint32_t n) const {
+        const auto it = range_memo.find(g.nodes[n].b);   // (dynamic_delay_ok has asked for the amount's range)
+        if (it == range_memo.end()) return 0;
+        const Range r = it->second;
+        if (r.nan || !(r.lo >= 1.0)) return 0;
+        return r.lo < 2147483648.0 ? (uint64_t)r.lo : 0x7FFFFFFFull;
+    }
     const ObservedInputs *observed = nullptr;
     std::unordered_set<uint32_t> observed_dyn;        // Delay nodes whose dyn_max came from observed ranges
     std::unordered_set<uint32_t> observed_refused;    // signal Delays still without a bound in observed mode
@@ -364,11 +375,15 @@ bool build_program(const FlatGraph &g, const Planner &P, uint32_t m, std::unorde
                 const auto ib = P.input_dyn_bound.find(n);   // (no evaluator reads it: the amount's proven bound, for block streaming)
                 in.buf = ib != P.input_dyn_bound.end() ? (uint32_t)ib->second : 0xFFFFFFFFu;
             } else {
-                in.op = S_READ_DYN; in.buf = x.a;
-                out.reads.push_back({x.a, bound});
-                out.dynamic_reads.insert(x.a);
+                const uint32_t sa = g.src_of(x.a);   // (FR_LOOP_DYN: the Delay may be the one that cuts a loop)
+                in.op = S_READ_DYN; in.buf = sa;
+                out.reads.push_back({sa, bound});
+                out.dynamic_reads.insert(sa);
                 // the offset can be anything in [0, bound]: a ring filled by this very launch is not safe to read
-                if (min_delay && !P.bank_of.count(x.a)) *min_delay = 0;
+                // (FR_LOOP_DYN: anything in [imm, bound]; plan_stages decides once it knows which program stores the ring)
+                // (the bound travels in the fused programs only, and only in a sweep plan: plan_stages clears it otherwise)
+                if (P.loop_dyn) { if (fuse) in.imm = (uint32_t)P.dyn_lo(n); }
+                else if (min_delay && !P.bank_of.count(sa)) *min_delay = 0;
             }
             if (--uses[x.b] == 0) free_regs.push_back(reg_of.at(x.b));
         } else if (x.op == OP_DELAY) {
@@ -567,7 +582,7 @@ void note_observed(const FlatGraph &g, const Planner &P, StagedPlan &sp) {
 
 StagedPlan plan_stages(const FlatGraph &g, bool allow_banks, bool allow_programs, uint32_t max_log2_p, bool allow_jit, bool allow_template,
                        BankMatcher *reuse, const ShardSpec *shard, uint32_t track_from, const ObservedInputs *observed, uint64_t track_history,
-                       bool loop_stride) {
+                       bool loop_stride, bool loop_dyn) {
     StagedPlan sp;
     PlanTrace plan_trace;
     const uint32_t n_rows = (uint32_t)g.outputs.size();
@@ -618,11 +633,26 @@ StagedPlan plan_stages(const FlatGraph &g, bool allow_banks, bool allow_programs
             const FlatNode &x = g.nodes[n];
             if (x.op == OP_CONST || x.op == OP_INPUT) continue;
             if (x.op == OP_FBREF) { live_targets.push_back(g.fb_target[x.a]); st.push_back(g.fb_target[x.a]); continue; }
+            // FR_LOOP_DYN: a loop cut at a Delay of a signal amount (graph.cpp cut_cycle).  The reference's recursion ends only if
+            // the amount is >= 1 frame every time -- a NaN amount is 0 frames --, and the rings need a look-back: all three proven
+            // by the amount's interval, or the graph is what it was without the option, a cycle
+            if (x.op == OP_DELAY && g.nodes[x.a].op == OP_FBREF && !g.is_const(x.b)) {
+                const Range r = P.range(x.b);
+                if (r.nan || !(r.lo >= 1.0) || !(r.hi < 2147483648.0)) {
+                    std::ostringstream os;
+                    os.precision(9);
+                    os << "dependency cycle closed through the Delay of lowered node " << n << ", whose amount is proven to lie in [" << r.lo << ", " << r.hi
+                       << "]" << (r.nan ? " or to be NaN" : "") << ": FR_LOOP_DYN serves the loop only when the amount is proven >= 1 frame (and below 2^31) "
+                       << "at every frame and never NaN";
+                    throw Error(FR_ERR_CYCLE, os.str());
+                }
+            }
             st.push_back(x.a);
             st.push_back(x.b);
         }
     }
     const bool feedback = !live_targets.empty();
+    P.loop_dyn = loop_dyn && feedback;
     sp.feedback_loops = (uint32_t)live_targets.size();
     if (feedback) {
         if (partials) throw Error(FR_ERR_UNSUPPORTED, "feedback through Delay is not available under partial-block sharding");
@@ -711,7 +741,8 @@ StagedPlan plan_stages(const FlatGraph &g, bool allow_banks, bool allow_programs
     std::unordered_set<uint32_t> same_frame_used;
     for (auto &kv : built)
         for (auto &rd : kv.second.reads)
-            if ((rd.second == 0 || kv.second.dynamic_reads.count(rd.first)) && !P.bank_of.count(rd.first)) same_frame_used.insert(rd.first);
+            // (FR_LOOP_DYN, feedback plans: a signal Delay never inlines its source; what it reads is a ring, ordered below)
+            if ((rd.second == 0 || (kv.second.dynamic_reads.count(rd.first) && !P.loop_dyn)) && !P.bank_of.count(rd.first)) same_frame_used.insert(rd.first);
     if (feedback)   // every row root lives in a ring: rows the fused programs do not write themselves (a node another program
         for (auto &kv : rows_of)   // computes inline, a second row of the same node) are copied from it after the launch (post_first),
             if (!P.bank_of.count(kv.first)) needs_ring.insert(kv.first);   // and programs merged into one hand their results over through it
@@ -1032,7 +1063,7 @@ StagedPlan plan_stages(const FlatGraph &g, bool allow_banks, bool allow_programs
                 for (uint32_t k = 0; k < pg.n_instr; ++k) if (finstrs[f0 + k].op == S_STORE) stores[i].insert(finstrs[f0 + k].buf);
                 for (uint32_t k = 0; k < pg.n_instr; ++k) {
                     const StageInstr &in = finstrs[f0 + k];
-                    if (in.op == S_READ && !bank_rings.count(in.buf) && !stores[i].count(in.buf)) foreign[i].insert(in.buf);
+                    if ((in.op == S_READ || in.op == S_READ_DYN) && !bank_rings.count(in.buf) && !stores[i].count(in.buf)) foreign[i].insert(in.buf);
                 }
             }
             std::vector<std::vector<uint32_t>> deps(np);
@@ -1125,7 +1156,18 @@ StagedPlan plan_stages(const FlatGraph &g, bool allow_banks, bool allow_programs
             // earlier level, whose launch has stored the whole window before this one starts: its delay binds no thread to a
             // residue (x = in + Delay(0.75 * x, 5) read at delay 2 by a later level strides by 5, not by 1).
             uint64_t stride = min_delay == ~0ull ? 0 : gcd_delay;
-            if (loop_stride) {
+            // Sweeps (FR_LOOP_DYN, callplan.hpp loop_sweep): some program reads a program's ring through a Delay of a signal amount, so
+            // no stride binds a thread to its own stores.  What holds instead is a lower bound on every read of a ring the reading
+            // program stores itself -- a constant's d, a signal's floor(lo) --: W, the least of them, frames at a time depend only on
+            // frames before them.  A ring an earlier level stores is finished when it is read, a bank's too: no bound needed, a signal
+            // read of one may reach 0 frames back.  A signal read of an OWN ring that may reach 0 frames back reads what is being computed.
+            uint64_t sweep = 0;
+            if (P.loop_dyn) {
+                sweep = sweep_bound(minstrs.data(), fbase, mprogs, std::vector<uint32_t>(bank_rings.begin(), bank_rings.end()));
+                if (sweep) stride = 0;
+                else for (StageInstr &in : minstrs) if (in.op == S_READ_DYN) in.imm = 0;   // not a sweep plan: nobody reads the bound
+            }
+            if (loop_stride && !sweep) {
                 uint64_t own = 0;
                 for (const StageProg &mp : mprogs) {
                     const StageInstr *ins = minstrs.data() + (mp.first_instr - fbase);
@@ -1137,6 +1179,7 @@ StagedPlan plan_stages(const FlatGraph &g, bool allow_banks, bool allow_programs
                 if (own != 0) stride = own;
             }
             for (const StageProg &mp : mprogs) {
+                if (sweep) { carry_only = false; break; }   // (no carry annotations: a sweep's threads read other threads' stores)
                 {
                     std::unordered_map<uint32_t, uint32_t> slot_of;   // ring -> carry slot + 1 (0: it has none)
                     StageInstr *ins = minstrs.data() + (mp.first_instr - fbase);
@@ -1162,6 +1205,7 @@ StagedPlan plan_stages(const FlatGraph &g, bool allow_banks, bool allow_programs
             sp.fused_count = (uint32_t)mprogs.size();
             sp.fused_max_frames = 0;
             sp.fused_stride = stride;
+            sp.fused_sweep = sweep;
             sp.feedback = true;
             sp.fused_carry_only = carry_only;
             sp.instrs.insert(sp.instrs.end(), minstrs.begin(), minstrs.end());

@@ -87,6 +87,12 @@ struct StagedPlan {
     std::vector<uint32_t> fused_level_first;
     uint32_t post_first = 0, post_count = 0;
     bool fused_carry_only = false;   // every fused program reads the rings it stores through the carry only (kernels.hpp STAGE_CARRY)
+    // Sweep plans (FR_LOOP_DYN; 0: not one): a feedback plan some program of which reads a program's ring through a Delay of a
+    // signal amount.  W = the least lower bound, over the fused programs after merging, of their reads of rings they store
+    // themselves (a constant read: its d; a signal read: floor(lo) of its amount's proven interval, S_READ_DYN's imm): frames
+    // [b, b + W) depend only on frames < b.  Such a plan has fused_stride 0, no carry annotations and runs on the interpreter
+    // (callplan.hpp loop_sweep).
+    uint64_t fused_sweep = 0;
     uint32_t n_rings = 0;
     uint64_t lmax = 0;                     // deepest look-back any ring must serve
     // How far back in the INPUT history the staged part can read when it computes frame t (ring look-backs + the delays
@@ -122,6 +128,37 @@ struct StagedPlan {
     bool uses_rings() const { return n_rings != 0; }
 };
 
+// W of the merged fused programs of a feedback plan planned with FR_LOOP_DYN (StagedPlan::fused_sweep; 0: no program reads a
+// program's ring through a Delay of a signal amount, the plan is not a sweep plan).  `instrs[first_instr - base ...]` are a
+// program's instructions, S_READ_DYN's imm the proven lower bound of its amount in frames; `bank_rings`: the rings that bank
+// launches fill (complete before any program runs).  Only reads of rings the reading program stores itself count: a constant
+// read with its d, a signal read with its bound -- and a bound of 0 there is refused: the read may reach what is being computed.
+inline uint64_t sweep_bound(const StageInstr *instrs, size_t base, const std::vector<StageProg> &progs, const std::vector<uint32_t> &bank_rings) {
+    bool any = false;
+    uint64_t w = ~0ull;
+    for (const StageProg &pg : progs) {
+        const StageInstr *ins = instrs + (pg.first_instr - base);
+        auto mine = [&](uint32_t ring) {
+            if (pg.dst_ring == ring) return true;
+            for (uint32_t k = 0; k < pg.n_instr; ++k)
+                if (ins[k].op == S_STORE && ins[k].buf == ring) return true;
+            return false;
+        };
+        for (uint32_t k = 0; k < pg.n_instr; ++k) {
+            const StageInstr &in = ins[k];
+            if (in.op == S_READ_DYN && std::find(bank_rings.begin(), bank_rings.end(), in.buf) == bank_rings.end()) any = true;
+            if (in.op == S_READ && mine(in.buf)) w = std::min<uint64_t>(w, in.d_lo);
+            if (in.op == S_READ_DYN && mine(in.buf)) {
+                if (in.imm == 0) throw Error(FR_ERR_UNSUPPORTED, "a feedback plan reads a program's ring through a signal-dependent Delay");
+                w = std::min<uint64_t>(w, in.imm);
+            }
+        }
+    }
+    if (!any) return 0;
+    if (w == ~0ull || w == 0) throw Error(FR_ERR_UNSUPPORTED, "internal: a sweep plan without a bound on its loops' reads");
+    return w;
+}
+
 // FR_DELAY_OBSERVED: a signal Delay amount with no proven bound is bounded from the values its inputs have actually held
 // since the last seek.  `range(slot)` is that slot's hull (always holding 0.0: unfed slots, zero prefixes and frames beyond
 // what was stored read 0.0); a staged Delay plans a look-back of the bound rounded up to a power of two, at most
@@ -141,9 +178,13 @@ class BankMatcher;
 // interpreter, template voices and voices that feed delay lines may read tracks too, as far back as that.
 StagedPlan plan_stages(const FlatGraph &g, bool allow_banks, bool allow_programs, uint32_t max_log2_p, bool allow_jit = false,
                        bool allow_template = true, BankMatcher *reuse = nullptr, const ShardSpec *shard = nullptr, uint32_t track_from = 0xFFFFFFFFu,
-                       const ObservedInputs *observed = nullptr, uint64_t track_history = 0, bool loop_stride = false);
+                       const ObservedInputs *observed = nullptr, uint64_t track_history = 0, bool loop_stride = false,
+                       bool loop_dyn = false);
 // `loop_stride` (FR_LOOP_TILES): a feedback plan's fused_stride is the gcd of the delays with which its programs read rings they
 // store themselves -- its loops -- and not also of their reads of rings that earlier levels have finished.
+// `loop_dyn` (FR_LOOP_DYN): a feedback plan may read a program's ring through a Delay of a signal amount -- the Delay that cuts a
+// loop, or a tap of a ring its own program stores, when the amount is proven >= 1 frame and never NaN (else FR_ERR_CYCLE for a
+// cutting Delay, FR_ERR_UNSUPPORTED for a tap); a later level's tap needs no proof.  Such a plan is a sweep plan (fused_sweep).
 
 // Do the observed Delays of `sp` (planned from `g` with observed ranges) still fit their planned look-backs under the ranges
 // `obs` gives now?  False: some bound grew past its plan, or has none any more.

@@ -339,6 +339,8 @@ inline StreamPlan plan_stream(const StagedPlan &sp, const std::vector<const Bank
     if (env.pull_mode) return refuse("block streaming of a renderer in FR_MODE_PULL");
     if (!sp.pull_rows.empty()) return refuse(std::to_string(sp.pull_rows.size()) + " output rows are left to the pull interpreter");
     if (env.track_history || !sp.track_window_slots.empty() || sp.track_lookback != 0) return refuse("block streaming with a track history");
+    // (FR_LOOP_DYN: a sweep plan's launch forms are fr_fill_buffer's alone; the resident kernels have neither)
+    if (sp.fused_sweep) return refuse("a feedback loop delays by a signal amount (a sweep plan, FR_LOOP_DYN): block streaming does not serve it");
     const bool voiceless = env.effects && banks.empty();   // FR_STREAM_EFFECTS: the programs are dealt over segments, not voices
     if (banks.size() != 1 && !(env.banks && banks.size() >= 2 && banks.size() <= STREAM_MAX_BANKS) && !voiceless) {
         if (env.banks && banks.size() > STREAM_MAX_BANKS)

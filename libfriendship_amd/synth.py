@@ -342,6 +342,29 @@ def chorus_tree(n_voices, n_partials, seed=0x5EED0004, depth=300.0, base=400.0, 
     return t
 
 
+def feedback_flanger(voices, partials, base=8.0, depth=6.0, rate=0.01, gain=0.5, seed=0x5EED0300, time_slot=0):
+    """Voices through a flanger with regeneration: x = voice + gain * Delay(x, base + depth * lfo(t)) -- feedback through a
+    Delay of a SIGNAL amount (FR_LOOP_DYN), a loop per voice.  lfo = Minimum(C(1), Modulo(t * rate * (v + 1), 1)): the
+    constant on the left keeps the amount free of NaN whatever the time row holds, so the planner can prove it >= 1 frame
+    (base >= 2 for a depth >= 0: the proven interval is widened outward)."""
+    p = voice_params(voices, partials, seed, wrap=64)
+    g = GraphArrays()
+    f = np.float32
+    voice = sum_tree(g, partial_leaves(g, p["w"], p["amp"], time_slot).reshape(voices, partials))
+    rates = (f(rate) * np.arange(1, voices + 1, dtype=np.float32)).astype(np.float32)
+    ramp = g.binop(K_MOD, g.binop(K_MUL, IN(time_slot), C(rates), voices), C(f(1.0)), voices)
+    lfo = g.binop(K_MIN, C(f(1.0)), ramp, voices)
+    amount = g.binop(K_SUM2, C(f(base)), g.binop(K_MUL, C(f(depth)), lfo, voices), voices)
+    x = g.nodes(K_SUM2, voices)
+    wet = g.binop(K_DELAY, x, amount, voices)
+    g.edge(voice, x, 0, 0)
+    g.edge(g.binop(K_MUL, wet, C(f(gain)), voices), x, 0, 1)
+    g.edge(x, 0, 0, np.arange(voices, dtype=np.uint32))
+    t = g.finish(voices)
+    t["params"] = p
+    return t
+
+
 def partial_effect():
     """The partial oscillator as ONE composite effect `Partial(t, w, amp) -> leaf` (what a `.fnd` effect file would
     hold): inputs 0,1,2 = time, w, amp as signals; per instance the host feeds w and amp through F32Constant edges.
