@@ -56,6 +56,9 @@ __device__ __forceinline__ float prim_min(float a, float b, bool sparkle = false
     return take_a ? a : other;
 }
 
+// dst = a op b: THE arithmetic step of every evaluator here.  pull_kernel passes a node's OP_*, the five stage interpreters
+// (stage_kernel, stage_tile_kernel, stage_sweep_kernel, stream_run_programs, stream_run_loop_program) an instruction's S_*
+// through STAGE_ARITH_CASES.
 __device__ __forceinline__ float prim_binop(uint32_t op, float a, float b, bool sparkle = false) {
     switch (op) {
     case OP_SUM2: return a + b;
@@ -65,6 +68,16 @@ __device__ __forceinline__ float prim_binop(uint32_t op, float a, float b, bool 
     default: return prim_min(a, b, sparkle);
     }
 }
+// The arithmetic cases of an interpreter's instruction switch, `v = x op y; break;` each: the S_* -> OP_* mapping, written once.
+// Cases of the interpreter's OWN switch, each op a constant, and not one case that hands in.op to prim_binop: that would be a
+// second dispatch per instruction, which the interpreters' time shows (profiles/stage_step.txt); this way every interpreter
+// compiles to the instructions it has with the cases spelled out.
+#define STAGE_ARITH_CASES(v, x, y, sparkle)                     \
+    case S_SUM2: v = prim_binop(OP_SUM2, x, y, sparkle); break; \
+    case S_MUL: v = prim_binop(OP_MUL, x, y, sparkle); break;   \
+    case S_DIV: v = prim_binop(OP_DIV, x, y, sparkle); break;   \
+    case S_MOD: v = prim_binop(OP_MOD, x, y, sparkle); break;   \
+    case S_MIN: v = prim_binop(OP_MIN, x, y, sparkle); break;
 
 // Delay's amount -> frames (reference.rs:200-211).  Returns false when the output is 0: the amount is >= 2^64, or --
 // SparkleRenderer only, sparkle.rs:531-534 -- it is negative or NaN (`ult 0`), where RefRenderer delays by 0 frames.
@@ -1254,11 +1267,7 @@ __device__ __forceinline__ void stream_run_programs(float *out, const StreamProg
             const StageInstr in = ins[i];
             float v;
             switch (in.op) {
-            case S_SUM2: v = regs[in.a][lane] + regs[in.b][lane]; break;
-            case S_MUL: v = regs[in.a][lane] * regs[in.b][lane]; break;
-            case S_DIV: v = regs[in.a][lane] / regs[in.b][lane]; break;
-            case S_MOD: v = prim_mod(regs[in.a][lane], regs[in.b][lane]); break;
-            case S_MIN: v = prim_min(regs[in.a][lane], regs[in.b][lane], p.sparkle != 0u); break;
+            STAGE_ARITH_CASES(v, regs[in.a][lane], regs[in.b][lane], p.sparkle != 0u)
             case S_STORE:
                 if (live) __hip_atomic_store(p.rings + (size_t)in.buf * ring_cap + (frame & p.ring_mask), regs[in.a][lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 continue;
@@ -1365,11 +1374,7 @@ __device__ __forceinline__ void stream_run_loop_program(float *out, const Stream
                     v = in.imm != 0u && f >= in.d_lo ? stt[(in.imm - 1u) & SM][(f - in.d_lo) & 63u] : ldt[slot][f];
                     break;
                 }
-                case S_SUM2: v = regs[in.a][f] + regs[in.b][f]; break;
-                case S_MUL: v = regs[in.a][f] * regs[in.b][f]; break;
-                case S_DIV: v = regs[in.a][f] / regs[in.b][f]; break;
-                case S_MOD: v = prim_mod(regs[in.a][f], regs[in.b][f]); break;
-                case S_MIN: v = prim_min(regs[in.a][f], regs[in.b][f], p.sparkle != 0u); break;
+                STAGE_ARITH_CASES(v, regs[in.a][f], regs[in.b][f], p.sparkle != 0u)
                 case S_STORE: stt[(in.imm - 1u) & SM][f] = regs[in.a][f]; continue;
                 case S_READ_INPUT:          // (an input with a history: phase 1 loaded it like an S_INPUT)
                     if constexpr (stream_has_history<Input>) {
@@ -1902,17 +1907,13 @@ __global__ void __launch_bounds__(256) stage_kernel(StageArgs a) {
         for (uint32_t i = 0; i < STAGE_MAX_HOISTED; ++i)
             if (i < pg.n_loads) tmp[fetch(i).dst][tid] = ld[i];
     }
-    // 2. everything else in program order  (stage_sweep_kernel below has its own copy of this step, stage_tile_kernel a third: a
-    //    change to an op or a new S_* case goes into all of them)
+    // 2. everything else in program order.  The arithmetic is STAGE_ARITH_CASES; stage_sweep_kernel below repeats the rest of this
+    //    step: this loop's time follows the compiler's output closely, see DESIGN 4.7 and profiles/stage_step.txt before sharing more
     for (uint32_t i = pg.n_loads; i < pg.n_instr; ++i) {
         const StageInstr in = fetch(i);
         float v;
         switch (in.op) {
-        case S_SUM2: v = tmp[in.a][tid] + tmp[in.b][tid]; break;
-        case S_MUL: v = tmp[in.a][tid] * tmp[in.b][tid]; break;
-        case S_DIV: v = tmp[in.a][tid] / tmp[in.b][tid]; break;
-        case S_MOD: v = prim_mod(tmp[in.a][tid], tmp[in.b][tid]); break;
-        case S_MIN: v = prim_min(tmp[in.a][tid], tmp[in.b][tid], a.sparkle != 0u); break;
+        STAGE_ARITH_CASES(v, tmp[in.a][tid], tmp[in.b][tid], a.sparkle != 0u)
         case S_STORE:
             a.rings[(size_t)in.buf * (a.ring_mask + 1) + (t & a.ring_mask)] = tmp[in.a][tid];
             if (in.imm != 0u && in.imm <= STAGE_CARRY && a.use_carry) carry(par, in.imm - 1u) = tmp[in.a][tid];
@@ -2021,11 +2022,7 @@ __global__ void __launch_bounds__(64) stage_tile_kernel(StageArgs a) {
                         else v = cyt[par ^ 1u][(in.imm - 1u) & (STAGE_CARRY - 1u)][lane];
                         break;
                     case S_STEP: v = a.w0 + base + f >= in.d_lo ? __uint_as_float(in.imm) : 0.0f; break;
-                    case S_SUM2: v = tmp[in.a][lane] + tmp[in.b][lane]; break;
-                    case S_MUL: v = tmp[in.a][lane] * tmp[in.b][lane]; break;
-                    case S_DIV: v = tmp[in.a][lane] / tmp[in.b][lane]; break;
-                    case S_MOD: v = prim_mod(tmp[in.a][lane], tmp[in.b][lane]); break;
-                    case S_MIN: v = prim_min(tmp[in.a][lane], tmp[in.b][lane], a.sparkle != 0u); break;
+                    STAGE_ARITH_CASES(v, tmp[in.a][lane], tmp[in.b][lane], a.sparkle != 0u)
                     case S_STORE:
                         stt[s < STAGE_TILE_STORES ? s : STAGE_TILE_STORES - 1u][f] = tmp[in.a][lane];
                         ++s;
@@ -2071,7 +2068,7 @@ hipError_t launch_stage(const StageArgs &a, hipStream_t s) {
 // Sweeps (kernels.hpp launch_stage_sweep, callplan.hpp loop_sweep): a feedback plan whose loops delay by a signal amount has no
 // stride that binds a thread to its own stores, but a proven bound: every read of a ring the program stores reaches at least
 // a.sweep frames back.  ONE workgroup per program walks the window a.sweep frames at a time, thread = frame of the sweep, each
-// thread the whole program for its frame exactly as stage_kernel runs it (stage_load, delay_frames, prim_mod, prim_min, the
+// thread the whole program for its frame exactly as stage_kernel runs it (stage_load, delay_frames, STAGE_ARITH_CASES, the
 // S_*_DYN case, the same stores under the same conditions).  Between two sweeps every thread waits for its own stores
 // (s_waitcnt vmcnt(0): on gfx950 stores count there) and the workgroup passes a barrier: the waves of a workgroup share their
 // CU's vector cache, which writes through, so a plain load after the barrier sees a plain store from before it.  Every thread
@@ -2102,11 +2099,7 @@ __global__ void __launch_bounds__(256) stage_sweep_kernel(StageArgs a) {
                 const StageInstr in = gins[i];
                 float v;
                 switch (in.op) {
-                case S_SUM2: v = tmp[in.a][tid] + tmp[in.b][tid]; break;
-                case S_MUL: v = tmp[in.a][tid] * tmp[in.b][tid]; break;
-                case S_DIV: v = tmp[in.a][tid] / tmp[in.b][tid]; break;
-                case S_MOD: v = prim_mod(tmp[in.a][tid], tmp[in.b][tid]); break;
-                case S_MIN: v = prim_min(tmp[in.a][tid], tmp[in.b][tid], a.sparkle != 0u); break;
+                STAGE_ARITH_CASES(v, tmp[in.a][tid], tmp[in.b][tid], a.sparkle != 0u)
                 case S_STORE: a.rings[(size_t)in.buf * ring_cap + (t & a.ring_mask)] = tmp[in.a][tid]; continue;
                 case S_READ_DYN: case S_READ_INPUT_DYN: case S_STEP_DYN: {   // Delay by a signal amount (reference.rs:200-215)
                     uint64_t fr;

@@ -133,7 +133,8 @@ enum StageOp : uint8_t {
     S_READ = 2,        // dst = t >= d ? ring[buf][(t - d) & mask] : 0          d = {lo, hi}
     S_READ_INPUT = 3,  // dst = t >= d ? input[imm] at t - d : 0
     S_STEP = 4,        // dst = t >= d ? bits(imm) : 0                           Delay of a constant
-    S_SUM2 = 5, S_MUL = 6, S_DIV = 7, S_MOD = 8, S_MIN = 9,   // dst = a op b
+    S_SUM2 = 5, S_MUL = 6, S_DIV = 7, S_MOD = 8, S_MIN = 9,   // dst = a op b    (kernels.hip: prim_binop is the semantics, STAGE_ARITH_CASES
+                                                              //  the cases of all five device interpreters)
     S_STORE = 10,      // ring[buf][t & mask] = a        (fused form: an inlined cut node still feeds its ring)
     // Delay with a signal amount (register a, evaluated at t): frames = amount -> u64 as reference.rs:200-211
     // (>= 2^64 -> output 0; negative/NaN -> 0 frames; else floor), then as the constant forms.  d_lo = proven bound.

@@ -268,6 +268,175 @@ def stream_slot0_expected(voice, op, consts, x, bus=False, semantics="reference"
     return tree_sum(y.reshape(len(consts) // 2, 2, -1).transpose(0, 2, 1)) if bus else y
 
 
+# ---- the interpreters that only feedback plans reach: the op beside a loop that never meets it -------------------------------------
+# stage_tile_kernel and stage_sweep_kernel run every program of a feedback plan's strided launch, so row 0 = op(In0, In1) is a
+# program of its own beside the loop's (row 1), in the same launch: no edge joins the two, row 0's expectation is the float64
+# reference of the pair alone, row 1's the dense reference of the loop alone on its own finite rows.
+LOOP_TILES = {"FR_LOOP_TILES": "1", "FR_STAGE_JIT": "0"}
+LOOP_SWEEP = {"FR_LOOP_DYN": "1"}
+LOOP_GAIN = 0.5
+
+
+def loop_rows(n, seed=0x5EED0900):
+    """The loop's own rows: finite noise (its input) and the frame ramp (the sweep's LFO)."""
+    return [np.random.default_rng(seed).normal(size=n).astype(np.float32), np.arange(n, dtype=np.float32)]
+
+
+def _loop_beside(g, sweep):
+    """x = In2 + 0.5 * Delay(x, d): d = 3 frames (a stride of 3: tiled), or sweep: 8 + 6 * lfo(In3), proven >= 7 (W = 7)."""
+    import loop_dyn_cases as LD
+    x = g.node("Sum2")
+    g.connect(("in", 2), x, 0)
+    g.connect(g.op("Multiply", g.op("Delay", x, LD.amount(g, 8.0, 6.0, slot=3) if sweep else ("c", 3.0)), ("c", LOOP_GAIN)), x, 1)
+    return x
+
+
+def loop_graph(op, sweep=False):
+    """Row 0 = op(In0, In1); row 1 = the loop on In2 (and In3)."""
+    from stage_reference import Graph
+    g = Graph()
+    g.output(g.op(op, ("in", 0), ("in", 1)), 0)
+    g.output(_loop_beside(g, sweep), 1)
+    return g
+
+
+def loop_alone(sweep=False):
+    """The loop of loop_graph with no other row (input slots 0 and 1 unused): what its row is compared with."""
+    from stage_reference import Graph
+    g = Graph()
+    g.output(_loop_beside(g, sweep), 0)
+    return g
+
+
+def loop_expected(sweep, rows):
+    """Row 1 of loop_graph from the loop alone: the dense references of the feedback tests (stage_reference.DenseReference for
+    the constant delay, loop_dyn_reference.DenseForward for the signal amount).  The pair's rows are not passed."""
+    import loop_dyn_reference as ldr
+    import stage_reference as sr
+    n = len(rows[0])
+    store = sr.InputStore()
+    store.call(0, [np.zeros(n, np.float32), np.zeros(n, np.float32)] + list(rows))
+    return (ldr.DenseForward if sweep else sr.DenseReference)(loop_alone(sweep))(store, 0, n)[0]
+
+
+def render_beside_loop(lib, op, sweep, semantics):
+    """op(In0, In1) on both blocks beside the loop: the two rows, after asserting from fr_plan_json that ONE launch of the form
+    ran both programs (stage_tile_kernel: a +tile variant; stage_sweep_kernel)."""
+    from libfriendship_amd.capi import Renderer
+    a, b = both_blocks()
+    g = loop_graph(op, sweep)
+    with Renderer(lib, mode="staged", options=LOOP_SWEEP if sweep else LOOP_TILES, semantics=semantics) as r:
+        g.install(r)
+        got = r.fill_buffer(2, 0, len(a), [a, b] + loop_rows(len(a)))
+        plan = r.plan()
+    launches = plan["stage_launches"]
+    assert plan["feedback"] and plan["pull_rows"] == 0 and not plan["stage_jit"] and len(launches) == 1 and launches[0]["programs"] == 2, (plan["pull_rows"], launches)
+    if sweep:
+        assert launches[0]["variant"] == "stage_sweep_kernel/feedback+sweep" and 1 <= plan["loop_dyn"]["frames"] <= 256, (launches, plan["loop_dyn"])
+    else:
+        kernel, form = launches[0]["variant"].split("/")
+        assert kernel == "stage_kernel" and "tile" in form.split("+") and 1 <= plan["fused_stride"] <= 64 and plan["loop_tiles"]["frames"], (launches, plan["loop_tiles"])
+    return got
+
+
+# Delays by a HOSTILE amount in a sweep plan.  The loop's own Delay is the flanger's (a sweep needs its proof); behind it, all in
+# stage_sweep_kernel: row 1 = Delay(C(2.5), In2) (S_STEP_DYN) and row 2 = Delay(In0, In2) (S_READ_INPUT_DYN) take the amount row
+# as it is -- negative, NaN, +-inf, 2^64, fractional.  S_READ_DYN reads a ring (the loop's, from the next level), and a ring's
+# size needs a finite upper bound of the amount: +inf and 2^64 cannot reach it in a staged plan.  Everything else does, on rows
+# 3 to 5 (SWEEP_RING_AMOUNTS): Minimum(C(5), In2) passes the negative, -inf, -0, subnormal and fractional amounts (NaN, +inf and
+# 2^64 become 5); Modulo(In2, C(8)) is NaN for the NaN and the +-inf entries, in both semantics; Minimum(In2, C(5)) is NaN for
+# the NaN entries under Sparkle.  NaN is where the semantics part for a ring's read: the reference delays by 0 frames, Sparkle
+# yields 0.
+SWEEP_RING_AMOUNTS = (("Minimum", 5.0, True), ("Modulo", 8.0, False), ("Minimum", 5.0, False))     # (op, constant, constant on the left)
+
+
+def sweep_ring_amounts(amt, semantics):
+    """The amounts that reach S_READ_DYN on rows 3 to 5, by the float64 reference."""
+    return [reference(op, np.float32(c), amt, semantics) if left else reference(op, amt, np.float32(c), semantics) for op, c, left in SWEEP_RING_AMOUNTS]
+
+
+def hostile_amounts(n):
+    import stage_variants as sv
+    amounts = (np.arange(n) % 9).astype(np.float32) + np.float32(0.25) * (np.arange(n) % 4).astype(np.float32)
+    amounts[1::3] = np.resize(sv.HOSTILE_AMOUNTS, len(amounts[1::3]))
+    return amounts
+
+
+def sweep_dyn_graph():
+    import loop_dyn_cases as LD
+    from stage_reference import Graph
+    g = Graph()
+    x = g.node("Sum2")
+    g.connect(("in", 0), x, 0)
+    g.connect(g.op("Multiply", g.op("Delay", x, LD.amount(g, 8.0, 6.0, slot=1)), ("c", LOOP_GAIN)), x, 1)
+    g.output(x, 0)
+    g.output(g.op("Delay", ("c", 2.5), ("in", 2)), 1)
+    g.output(g.op("Delay", ("in", 0), ("in", 2)), 2)
+    for k, (op, c, left) in enumerate(SWEEP_RING_AMOUNTS):
+        g.output(g.op("Delay", x, g.op(op, ("c", c), ("in", 2)) if left else g.op(op, ("in", 2), ("c", c))), 3 + k)
+    return g
+
+
+def sweep_dyn_rows(lib, semantics, n=1500):
+    """sweep_dyn_graph on `lib` over n frames, after asserting from fr_plan_json that both levels ran as sweeps: the rows and the
+    dense forward reference's."""
+    import loop_dyn_reference as ldr
+    import stage_reference as sr
+    from libfriendship_amd.capi import Renderer
+    g = sweep_dyn_graph()
+    rows = loop_rows(n) + [hostile_amounts(n)]
+    amt = rows[2]
+    assert np.isnan(amt).any() and (amt == np.inf).any() and (amt == -np.inf).any() and (amt < 0).any() and (amt == 2.0 ** 64).any()
+    assert (np.isfinite(amt) & (amt != np.floor(amt))).any()
+    ring = sweep_ring_amounts(amt, semantics)                            # what S_READ_DYN gets: no +inf, no 2^64, everything else
+    assert (ring[0] < 0).any() and (ring[0] == -np.inf).any() and (np.isfinite(ring[0]) & (ring[0] != np.floor(ring[0]))).any()
+    assert np.isnan(ring[1]).sum() >= n // 20 and np.isnan(ring[2]).any() == (semantics == "sparkle")
+    assert not any(((a == np.inf) | (a >= 2.0 ** 64)).any() for a in ring)
+    n_out = 3 + len(ring)
+    with Renderer(lib, mode="staged", options=LOOP_SWEEP, semantics=semantics) as r:
+        g.install(r)
+        got = r.fill_buffer(n_out, 0, n, rows)
+        plan = r.plan()
+    variants = [l["variant"] for l in plan["stage_launches"]]
+    assert plan["pull_rows"] == 0 and variants == ["stage_sweep_kernel/feedback+sweep"] * 2 and plan["loop_dyn"]["frames"] == 7, (plan["pull_rows"], variants)
+    store = sr.InputStore()
+    store.call(0, rows)
+    exp = ldr.DenseForward(g, semantics)(store, 0, n)
+    assert all((exp[r] != 0).sum() > n // 2 for r in range(n_out))      # (every Delay yields more than its zeros)
+    return got, exp
+
+
+# Block streaming's loop programs.  A streamed program is a voice's, and a loop program is the ONE program that holds the loop, so
+# the op sits in the loop's program: row v = Sum2(Multiply(Multiply(x_v, x_v), In1), op_v(In2, In3)) with x_v = voice_v + 0.5 *
+# Delay(x_v, 5).  The op does not enter the loop.  The loop enters the row as its square -- finite, never negative -- times In1,
+# a row of -0: that product is -0 on every frame whatever x is, and Sum2(-0, r) is r for EVERY r, -0 and +0 included (NaN stays
+# NaN).  So the expectation is the float64 reference of the pair alone; no voice and no loop value is needed for it.
+STREAM_LOOP_DELAY = 5
+
+
+def stream_loop_graph(ops=OPS, P=128):
+    g = synth.GraphArrays()
+    V = len(ops)
+    dl = g.nodes(synth.K_DELAY, V)
+    g.const(dl, np.float32(STREAM_LOOP_DELAY), 1)
+    x = g.binop(synth.K_SUM2, _stream_voices(g, V, P), g.binop(synth.K_MUL, dl, synth.C(np.float32(LOOP_GAIN)), V), V)
+    g.edge(x, dl, 0, 0)
+    r = np.concatenate([g.binop(KIND[op], synth.IN(2), synth.IN(3), 1) for op in ops])
+    return _rows(g, g.binop(synth.K_SUM2, g.binop(synth.K_MUL, g.binop(synth.K_MUL, x, x, V), synth.IN(1), V), r, V))
+
+
+def stream_loop_rows():
+    """[time ramp, the gate of -0, In2, In3] over both blocks."""
+    a, b = both_blocks()
+    return [synth.time_ramp(0, len(a)), np.full(len(a), -0.0, np.float32), a, b]
+
+
+def assert_loop_programs(s, n):
+    """fr_plan_json["stream"]: servable by the loops kernel, a loop program (stride STREAM_LOOP_DELAY) per voice and no other."""
+    assert s["servable"] and s["kernel"] == "bank_stream_loops_kernel", s
+    assert s["loop_programs"] == [STREAM_LOOP_DELAY] * n and s["programs_per_voice"] == [1] * n and s["bus_programs"] == 0, s
+
+
 # ---- running a recipe on a library (the simulator's or the device's) and asserting the evaluator from the plan ---------------------
 SEMANTICS = ("reference", "sparkle")
 EVALUATORS = {"pull": ("pull", {}), "stage_kernel": ("staged", {"FR_STAGE_JIT": "0"}), "stage_jit": ("staged", {"FR_STAGE_JIT": "force"})}

@@ -4,7 +4,9 @@ for bit, every sample compared.  Each test asserts from fr_plan_json that the ev
 Evaluators: pull_kernel (mode="pull": SS, SP / PS, CC), stage_kernel (mode="staged", FR_STAGE_JIT=0: SS, SP / PS, SL / LS), the
 hipRTC-compiled stage programs (FR_STAGE_JIT=force: SS, SP / PS, SL / LS; for the literal forms the generated source is read back
 through FR_JIT_DUMP to show that the constant was baked), the hipRTC-compiled voice leaves (SS, SL / LS, the fma form with
-FR_JIT_FMA on and off, Modulo(x, 1) in its fract and its general body) and the three block-streaming interpreters.
+FR_JIT_FMA on and off, Modulo(x, 1) in its fract and its general body), the three block-streaming interpreters, and the
+interpreters that only a loop brings up: stage_tile_kernel and stage_sweep_kernel (SS beside a loop of a feedback plan, and the
+Delays by a hostile amount in a sweep) and block streaming's loop programs (SS inside the loop's program).
 
 What the leaf forms cannot carry as the design had it: a compiled voice has 32 to 8192 leaves (match.cpp), so P = 2 does not
 exist, and P IDENTICAL leaves are one interned node; every leaf is the operation times its own power of two (prim_pairs.py).
@@ -198,4 +200,56 @@ def test_stream_slot_0_programs(hip_lib, oracle_lib, op, bus):
     assert s["servable"] and s["input_slots"] == [0] and s["kernel"] == ("bank_stream_bus_kernel" if bus else "bank_stream_prog_kernel"), s
     exp = pp.stream_slot0_expected(voice, op, consts, x, bus=bus)
     msg = pp.first_diff(op, f"stream slot 0 bus={bus}", x, 0, got, exp)
+    assert not msg, msg
+
+
+# ---- the interpreters of feedback plans: stage_tile_kernel, stage_sweep_kernel -----------------------------------------------------
+@pytest.fixture(scope="module")
+def loop_rows_expected():
+    """{sweep: row 1 of prim_pairs.loop_graph from the loop alone}, read-only."""
+    out = {sweep: pp.loop_expected(sweep, pp.loop_rows(len(pp.both_blocks()[0]))) for sweep in (False, True)}
+    for v in out.values():
+        v.setflags(write=False)
+    return out
+
+
+@pytest.mark.parametrize("op", pp.OPS)
+@pytest.mark.parametrize("sweep", [False, True], ids=["stage_tile_kernel", "stage_sweep_kernel"])
+def test_two_signals_beside_a_loop(hip_lib, reference_rows, loop_rows_expected, sweep, op):
+    """SS on stage_tile_kernel (FR_LOOP_TILES=1, FR_STAGE_JIT=0, a loop of stride 3) and on stage_sweep_kernel (FR_LOOP_DYN=1,
+    W = 7): op(In0, In1) on both blocks is a program of the feedback plan's one strided launch, beside a loop that it never
+    meets (prim_pairs.loop_graph; the form is asserted from fr_plan_json).  Row 0 is the pair's reference, row 1 the loop's alone."""
+    a, b = pp.both_blocks()
+    for semantics in semantics_of(op):
+        got = pp.render_beside_loop(hip_lib, op, sweep, semantics)
+        msg = pp.first_diff(op, f"SS {semantics} beside a loop, sweep={sweep}", a, b, got[0], reference_rows[semantics][pp.OPS.index(op)])
+        assert not msg, msg
+        msg = pp.first_diff("the loop", f"beside {op}, sweep={sweep}", 0, 0, got[1], loop_rows_expected[sweep])
+        assert not msg, msg
+
+
+@pytest.mark.parametrize("semantics", SEMANTICS)
+def test_hostile_amounts_in_a_sweep(hip_lib, semantics):
+    """stage_sweep_kernel's Delays by a signal amount over a hostile amount row, every frame against the dense forward reference
+    (prim_pairs.sweep_dyn_graph).  S_STEP_DYN and S_READ_INPUT_DYN get the row as it is: negative, NaN, +-inf, 2^64, fractional.
+    S_READ_DYN of the loop's ring gets negative, -inf, -0, subnormal, fractional and NaN amounts (NaN: where reference and Sparkle
+    part); +inf and 2^64 cannot reach a ring's read, whose ring needs a finite bound.  tests/loop_dyn_cases.py keeps every amount
+    in [lo, hi] of its proof -- its hostile call feeds the LFO, which clamps --: none of these amounts occurs there."""
+    got, exp = pp.sweep_dyn_rows(hip_lib, semantics)
+    msg = pp.first_diff("Delay by a hostile amount", f"sweep {semantics}", 0, 0, got, exp)
+    assert not msg, msg
+
+
+# ---- block streaming's loop programs -------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("semantics", SEMANTICS)
+def test_stream_loop_programs(hip_lib, reference_rows, semantics):
+    """bank_stream_loops_kernel, stream_run_loop_program: row v = Sum2(Multiply(Multiply(x_v, x_v), In1), op_v(In2, In3)), x_v the
+    voice through a comb of 5 frames, In1 a row of -0, the 6305 pairs in In2, In3, fed in blocks of 64 frames.  The op is in the
+    loop's program (one loop program per voice, asserted); the loop's square times -0 is -0, and Sum2(-0, r) is r for every r:
+    the rows are the pair's reference bit for bit."""
+    import stream_loop_cases as SL
+    a, b = pp.both_blocks()
+    got, plan = pp.stream_blocks(hip_lib, pp.stream_loop_graph(), len(pp.OPS), pp.stream_loop_rows(), dict(SL.INPUTS, **SL.IDLE), semantics)
+    pp.assert_loop_programs(plan["stream"], len(pp.OPS))
+    msg = pp.first_diff("every op", f"stream loop programs {semantics}", a, b, got, reference_rows[semantics])
     assert not msg, msg

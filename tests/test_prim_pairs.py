@@ -2,7 +2,8 @@
 oracle on both blocks, all five ops, both semantics; the both-constant form through the engine's own constant folder
 (graph.cpp FlatGraph::make) in the host-logic simulator; the signal forms (SS, SP / PS, SL / LS) through the engine's lowering
 and planning in the simulator, in pull and in staged mode, each asserted from fr_plan_json (the simulator's loops restate the
-kernels: the HIP kernels themselves are not run here); and the comparison's own self-test."""
+kernels: the HIP kernels themselves are not run here); the graphs that carry a pair to stage_tile_kernel, stage_sweep_kernel and a
+streamed loop program, with the form each plan must take; and the comparison's own self-test."""
 import os
 import sys
 
@@ -223,3 +224,52 @@ def test_stream_recipe_on_the_simulator(sim, stream_voices, bus):
     exp = pp.stream_expected(stream_voices[:len(ops)], rows[1], a, b, ops, bus=bus)
     msg = pp.first_diff("every op", f"stream bus={bus}", a, b, got, exp)
     assert not msg, msg
+
+
+# ---- the interpreters of feedback plans and of streamed loop programs: the recipes, the forms and the expectations -------------------
+@pytest.fixture(scope="module")
+def loop_rows_expected():
+    """{sweep: row 1 of loop_graph from the loop alone}, read-only."""
+    out = {sweep: pp.loop_expected(sweep, pp.loop_rows(len(pp.both_blocks()[0]))) for sweep in (False, True)}
+    for v in out.values():
+        assert np.isfinite(v).all()
+        v.setflags(write=False)
+    return out
+
+
+@pytest.mark.parametrize("op", pp.OPS)
+@pytest.mark.parametrize("sweep", [False, True], ids=["stage_tile_kernel", "stage_sweep_kernel"])
+def test_two_signals_beside_a_loop_on_the_simulator(sim, reference_rows, loop_rows_expected, sweep, op):
+    """op(In0, In1) on both blocks as a program of the tiled (the sweep) launch of a feedback plan whose loop it never meets:
+    row 0 is the pair's reference, row 1 the loop's alone."""
+    a, b = pp.both_blocks()
+    for semantics in semantics_of(op):
+        got = pp.render_beside_loop(sim, op, sweep, semantics)
+        msg = pp.first_diff(op, f"SS {semantics} beside a loop, sweep={sweep}", a, b, got[0], reference_rows[semantics][pp.OPS.index(op)])
+        assert not msg, msg
+        msg = pp.first_diff("the loop", f"beside {op}, sweep={sweep}", 0, 0, got[1], loop_rows_expected[sweep])
+        assert not msg, msg
+
+
+@pytest.mark.parametrize("semantics", SEMANTICS)
+def test_hostile_amounts_in_a_sweep_on_the_simulator(sim, semantics):
+    """tests/loop_dyn_cases.py keeps every amount in [lo, hi] of its proof (its hostile call feeds the LFO, which clamps), so no
+    case there has a negative, NaN, infinite, >= 2^64 or fractional amount: sweep_dyn_graph does, on every frame -- S_READ_DYN
+    all of them but +inf and 2^64, which cannot reach a ring's read."""
+    got, exp = pp.sweep_dyn_rows(sim, semantics)
+    msg = pp.first_diff("Delay by a hostile amount", f"sweep {semantics}", 0, 0, got, exp)
+    assert not msg, msg
+
+
+def test_stream_loop_recipe_on_the_simulator(sim, reference_rows):
+    """Row v = Sum2(Multiply(Multiply(x_v, x_v), In1), op_v(In2, In3)) with In1 a row of -0: served as ONE loop program per voice,
+    and through fr_fill_buffer the rows are the pair's reference bit for bit -- the loop leaves no trace, not even on -0."""
+    import stream_loop_cases as SL
+    a, b = pp.both_blocks()
+    for semantics in SEMANTICS:
+        with Renderer(sim, options=SL.INPUTS, semantics=semantics) as r:
+            synth.install(r, pp.stream_loop_graph())
+            got = r.fill_buffer(len(pp.OPS), 0, len(a), pp.stream_loop_rows())
+            pp.assert_loop_programs(r.plan()["stream"], len(pp.OPS))
+        msg = pp.first_diff("every op", f"stream loop programs {semantics}", a, b, got, reference_rows[semantics])
+        assert not msg, msg
