@@ -230,6 +230,22 @@ extern "C" {
  * admits; they count in "dyn_reads" too).  Still refused, each with its reason: a
  * signal delay inside a feedback loop shorter than a block; a feedback patch that delays a computed value by a signal amount (the
  * planner refuses it for fr_fill_buffer too); a bound observed from input rows.
+ *
+ * FR_STREAM_SWEEP = 0 / 1 (default 0; read strictly from the environment too; acts on top of FR_STREAM_PROGRAMS=1, FR_STREAM_LOOPS=1
+ * and FR_STREAM_DYN=1 and does nothing where one of them is missing): block streaming also serves FEEDBACK LOOPS THROUGH A DELAY OF A
+ * SIGNAL AMOUNT -- a patch rendered with FR_LOOP_DYN = 1 or 2: a flanger with regeneration, a comb with vibrato, a tape echo
+ * x = in + g * Delay(x, base + depth * lfo(t)), with voices or (FR_STREAM_EFFECTS) on a row the host feeds in -- and two neighbours:
+ * a Delay by a signal amount inside a feedback loop shorter than a block (a chorus into a comb), and in a feedback patch a signal tap
+ * of a delay line that an earlier program stores (a tap behind the loop; a second one makes a mix bus, FR_STREAM_BUS).  The wave that
+ * runs such a loop walks the block w frames at a time, w = the proven lower bound of the amount in frames (1..63; at 64 and more the
+ * loop reads earlier blocks alone and needs no walk); nobody waits for anybody.  Same bits as fr_fill_buffer, in both semantics; a
+ * block that does not continue the previous one is a seek as ever; with FR_STREAM_STORE an edit re-plans and relaunches; FR_RING_KEEP
+ * stays inert for such a plan.  With 0 nothing changes: every such plan is refused with the reason it has always had, and every other
+ * plan is served and refused, with the same reasons, by the same kernels.  "stream" gains "sweep_programs" (the width of every
+ * streamed program, in the order they run; 0: no walk of its own), and "kernel" names the four new kernels (bank_stream_sweep_kernel,
+ * bank_stream_sweep_fx_kernel, bank_stream_sweep_store_kernel, bank_stream_sweep_store_fx_kernel) for exactly these plans.  Still
+ * refused: an amount whose lower bound the planner cannot prove (FR_ERR_CYCLE, as for fr_fill_buffer), a signal tap of a delay line
+ * that a LATER program stores, a bound observed from input rows.
  */
 typedef struct fr_option {
     const char *name;              /* e.g. "FR_BANK_SHORT" */

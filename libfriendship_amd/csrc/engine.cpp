@@ -201,7 +201,7 @@ static std::string stage_variant(const StageLaunchNote &n, const Plan &p) {
     return k;
 }
 
-constexpr size_t N_OPTIONS = 43;        // per-renderer options (friendship_render_ext.h; the table below fr_renderer)
+constexpr size_t N_OPTIONS = 44;        // per-renderer options (friendship_render_ext.h; the table below fr_renderer)
 
 struct TimerClass {
     double ms = 0;
@@ -578,9 +578,9 @@ struct fr_renderer {
         }
         return d_tickets.as<uint32_t>();
     }
-    // FR_STREAM_PROGRAMS, _BUS, _INPUTS, _LOOPS, _BANKS, _GENERAL, _DYN, _HISTORY, _EFFECTS, _STORE, _TAPS (the options table says what each serves; streamplan.hpp StreamEnv)
+    // FR_STREAM_PROGRAMS, _BUS, _INPUTS, _LOOPS, _BANKS, _GENERAL, _DYN, _HISTORY, _EFFECTS, _STORE, _TAPS, _SWEEP (the options table says what each serves; streamplan.hpp StreamEnv)
     bool stream_programs = false, stream_bus = false, stream_inputs = false, stream_loops = false, stream_banks = false, stream_general = false, stream_dyn = false,
-         stream_history = false, stream_effects = false, stream_store = false, stream_taps = false;
+         stream_history = false, stream_effects = false, stream_store = false, stream_taps = false, stream_sweep = false;
     // Why FR_STREAM_STORE does nothing for this renderer ("": it acts; streamstore.hpp)
     std::string stream_store_inert_now() const { return stream_store_inert(delay_observed, track_from != 0xFFFFFFFFu); }
     std::vector<const BankLaunch *> stream_bank_list() const {
@@ -601,6 +601,7 @@ struct fr_renderer {
         env.history = stream_history;
         env.effects = stream_effects;
         env.taps = stream_taps;
+        env.sweep = stream_sweep;
         env.store = stream_store && stream_programs && stream_store_inert_now().empty();
         return env;
     }
@@ -2375,7 +2376,9 @@ void fr_renderer::upload_stream_programs(const StreamPlan &s, const StreamLaunch
     }
     // the stream's own copy of the programs' instructions (StreamLaunch::own_instrs): the operand of S_INPUT -- and of S_READ_INPUT
     // and S_READ_INPUT_DYN, FR_STREAM_HISTORY -- the streamed row (the position of its slot in row_slots) instead of the plan's
-    // input index; a loop program's store slots.  (The plan's own instructions, which the ordinary path runs, are not touched.)
+    // input index; a loop program's store slots; in a plan with a sweep walk (FR_STREAM_SWEEP) S_READ_DYN's imm, a sweep plan's proven
+    // bound, becomes the store slot + 1 of an own ring (stream_sweep_prepare) and 0 everywhere else -- the kernel reads it as that.
+    // (The plan's own instructions, which the ordinary path runs, are not touched.)
     std::vector<StageInstr> instrs;
     if (l.own_instrs) {
         if (row_slots.size() > BANK_STREAM_ROWS) throw Error(FR_ERR_DEVICE, "internal: more streamed rows than the kernel takes");
@@ -2389,9 +2392,12 @@ void fr_renderer::upload_stream_programs(const StreamPlan &s, const StreamLaunch
                     if (it == row_slots.end()) throw Error(FR_ERR_DEVICE, "internal: a streamed program reads a slot the stream does not feed");
                     in.imm = (uint32_t)(it - row_slots.begin());
                 }
+                if (in.op == S_READ_DYN && s.has_sweep() && s.sweep_width[i] == 0) in.imm = 0;
                 own.push_back(in);
             }
-            if (s.loop_stride[i] != 0 && (!stream_loop_prepare(pg, own) || pg.pad[0] != s.loop_stride[i]))
+            if (s.sweep_width[i] != 0 && (s.sweep_width[i] != s.loop_stride[i] || !stream_sweep_prepare(pg, own) || pg.pad[0] != s.sweep_width[i]))
+                throw Error(FR_ERR_DEVICE, "internal: a sweep program the stream cannot prepare");
+            if (s.sweep_width[i] == 0 && s.loop_stride[i] != 0 && (!stream_loop_prepare(pg, own) || pg.pad[0] != s.loop_stride[i]))
                 throw Error(FR_ERR_DEVICE, "internal: a loop program the stream cannot prepare");
             pg.first_instr = (uint32_t)instrs.size();
             instrs.insert(instrs.end(), own.begin(), own.end());
@@ -2705,6 +2711,7 @@ int64_t env_strict_stream_history(const char *e);
 int64_t env_strict_stream_effects(const char *e);
 int64_t env_strict_stream_store(const char *e);
 int64_t env_strict_stream_taps(const char *e);
+int64_t env_strict_stream_sweep(const char *e);
 bool parse_option(const Knob &k, const char *s, int64_t &v);
 
 const Knob kKnobs[] = {
@@ -2830,6 +2837,11 @@ const Knob kKnobs[] = {
          r.loop_dyn = (int)v;
          r.loop_dyn_given = given;
      }, LISTED_WHEN_SET},
+    // Delays by a signal amount inside feedback loops shorter than a block in block streaming -- a flanger with regeneration, a comb
+    // with vibrato (a sweep plan, FR_LOOP_DYN), a chorus into a comb, a signal tap behind a loop: a loop program walks the block in
+    // sweeps of its width (streamplan.hpp StreamEnv::sweep; fr_plan_json: stream.sweep_programs).  Acts on top of FR_STREAM_PROGRAMS,
+    // FR_STREAM_LOOPS and FR_STREAM_DYN; inert without them.  Strict and listed once set.
+    {"FR_STREAM_SWEEP", 0, 0, 1, 0, nullptr, 0, env_strict_stream_sweep, [](fr_renderer &r, int64_t v, bool) { r.stream_sweep = v != 0; }, LISTED_WHEN_SET},
 };
 static_assert(sizeof kKnobs / sizeof kKnobs[0] == N_OPTIONS, "N_OPTIONS counts the rows of kKnobs");
 
@@ -2854,6 +2866,7 @@ int64_t env_strict_stream_history(const char *e) { return env_strict("FR_STREAM_
 int64_t env_strict_stream_effects(const char *e) { return env_strict("FR_STREAM_EFFECTS", e); }
 int64_t env_strict_stream_store(const char *e) { return env_strict("FR_STREAM_STORE", e); }
 int64_t env_strict_stream_taps(const char *e) { return env_strict("FR_STREAM_TAPS", e); }
+int64_t env_strict_stream_sweep(const char *e) { return env_strict("FR_STREAM_SWEEP", e); }
 
 bool parse_option(const Knob &k, const char *s, int64_t &v) {
     if (k.word && std::strcmp(s, k.word) == 0) {
@@ -3518,6 +3531,11 @@ const char *fr_plan_json(fr_renderer *r) {
             if (r->stream_taps)                                  // FR_STREAM_TAPS: the levels of the run form, the reads below a block of rings that programs store
                 r->plan_json_cache += ",\"levels\":" + std::to_string(s.levels) + ",\"short_reads\":" + std::to_string(s.short_reads) +
                                       ",\"dyn_ring_reads\":" + std::to_string(s.dyn_ring_reads);
+            if (r->stream_sweep) {                               // FR_STREAM_SWEEP: the width of every streamed program, in the order of `progs` (0: no sweep program)
+                std::string sw;
+                for (uint32_t w : s.sweep_width) sw += (sw.empty() ? "" : ",") + std::to_string(w);
+                r->plan_json_cache += ",\"sweep_programs\":[" + sw + "]";
+            }
             const StreamLaunch l = s.servable ? stream_launch(r->plan.sp, s) : StreamLaunch{};
             const char *kernel = stream_kernel_name(l.by_plan ? l.kernel : stream_kernel_by_plan(r->strm.last_kernel) ? StreamKernel::none : r->strm.last_kernel);
             if (r->stream_banks) {                               // FR_STREAM_BANKS: the banks of the launch, in plan order

@@ -1317,7 +1317,10 @@ __device__ __forceinline__ StageInstr stream_loop_instr(const uint4 (&lins)[BANK
     return in;
 }
 
-template <class Input>
+// SWEEP (FR_STREAM_SWEEP; kernels.hpp bank_stream_sweep_kernel, where the argument stands): pad[0] is the program's sweep width w
+// (a loop program of constant stride: its stride), and phase 2 walks the block w frames at a time, lanes < w a frame each, with
+// the Delays by a signal amount among its cases.  Phases 0, 1 and 3 are the same.
+template <bool SWEEP = false, class Input>
 __device__ __forceinline__ void stream_run_loop_program(float *out, const StreamProgArgs &p, float (&regs)[STAGE_REGS][64], float (&ldt)[BANK_STREAM_LOOP_LOADS][64],
                                                         float (&stt)[BANK_STREAM_LOOP_STORES][64], uint4 (&lins)[BANK_STREAM_LOOP_INSTRS], const StageProg &pg, uint64_t head,
                                                         uint32_t n, uint32_t lane, bool live, Input &&input) {
@@ -1358,6 +1361,57 @@ __device__ __forceinline__ void stream_run_loop_program(float *out, const Stream
         }
     }
     stream_wave_phase();
+    // 2. (SWEEP) the sweeps: frames [base, base + w) read store-tile columns below `base` only, which earlier iterations of this
+    // wave wrote; the loop's bounds are uniform for the wave, and every sweep ends in a wave phase
+    if constexpr (SWEEP) {
+        const uint32_t w = stride != 0u ? stride : 1u;
+        for (uint32_t base = 0; base < n; base += w) {
+            const uint32_t f = base + lane;
+            if (lane < w && f < n) {
+                uint32_t k = 0;
+                for (uint32_t i = 0; i < pg.n_instr; ++i) {
+                    const StageInstr in = fetch(i);
+                    float v;
+                    switch (in.op) {
+                    case S_CONST: v = __uint_as_float(in.imm); break;
+                    case S_STEP: v = head + f >= in.d_lo ? __uint_as_float(in.imm) : 0.0f; break;
+                    case S_INPUT: v = ldt[k++ & LM][f]; break;
+                    case S_READ: {
+                        const uint32_t slot = k++ & LM;
+                        v = in.imm != 0u && f >= in.d_lo ? stt[(in.imm - 1u) & SM][(f - in.d_lo) & 63u] : ldt[slot][f];
+                        break;
+                    }
+                    STAGE_ARITH_CASES(v, regs[in.a][f], regs[in.b][f], p.sparkle != 0u)
+                    case S_STORE: stt[(in.imm - 1u) & SM][f] = regs[in.a][f]; continue;
+                    case S_READ_DYN: {
+                        // an own ring (imm = store slot + 1) at a frame of this block: the store tile; else the masked load
+                        uint64_t fr;
+                        if (!delay_frames(regs[in.a][f], fr, p.sparkle != 0u) || head + f < fr) v = 0.0f;
+                        else if (in.imm != 0u && fr <= f) v = stt[(in.imm - 1u) & SM][(f - (uint32_t)fr) & 63u];
+                        else v = __hip_atomic_load(p.rings + (size_t)in.buf * ring_cap + ((head + f - fr) & p.ring_mask), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        break;
+                    }
+                    case S_STEP_DYN: v = stream_prog_dyn(p.rings, p.ring_mask, p.sparkle, S_STEP_DYN, in.imm, in.buf, regs[in.a][f], head + f); break;
+                    case S_READ_INPUT_DYN:
+                        if constexpr (stream_has_history<Input>) {
+                            v = stream_prog_dyn(input.hist, input.hmask, p.sparkle, S_READ_DYN, 0u, in.imm & (BANK_STREAM_ROWS - 1u), regs[in.a][f], head + f);
+                            break;
+                        }
+                        [[fallthrough]];
+                    case S_READ_INPUT:          // (an input with a history: phase 1 loaded it like an S_INPUT)
+                        if constexpr (stream_has_history<Input>) {
+                            v = ldt[k++ & LM][f];
+                            break;
+                        }
+                        [[fallthrough]];
+                    default: v = 0.0f; break;
+                    }
+                    regs[in.dst][f] = v;
+                }
+            }
+            stream_wave_phase();
+        }
+    } else
     // 2. the loops, a lane per residue, every frame on its own register column
     if (lane < stride) {
         for (uint32_t f = lane; f < n; f += stride) {
@@ -1403,8 +1457,8 @@ __device__ __forceinline__ void stream_run_loop_program(float *out, const Stream
 }
 
 // stream_run_programs where a program may be a loop program; one of stride 0 is a range of one program of stream_run_programs.
-// (DYN concerns those alone: the rule serves no loop program with a Delay by a signal amount.)
-template <bool DYN = false, class Input>
+// (DYN concerns those alone: without SWEEP the rule serves no loop program with a Delay by a signal amount.)
+template <bool DYN = false, bool SWEEP = false, class Input>
 __device__ __forceinline__ void stream_run_programs_loops(float *out, const StreamProgArgs &p, float (&regs)[STAGE_REGS][64], float (&ldt)[BANK_STREAM_LOOP_LOADS][64],
                                                           float (&stt)[BANK_STREAM_LOOP_STORES][64], uint4 (&lins)[BANK_STREAM_LOOP_INSTRS], uint32_t p_first,
                                                           uint32_t p_end, uint64_t head, uint32_t n, uint32_t lane, bool live, Input &&input) {
@@ -1416,7 +1470,8 @@ __device__ __forceinline__ void stream_run_programs_loops(float *out, const Stre
         // what this wave has stored so far (the voice's ring, an earlier program's rings) is in L2 before it is read back
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         const StageProg pg = p.progs[pi];
-        stream_run_loop_program(out, p, regs, ldt, stt, lins, pg, head, n, lane, live, input);
+        if constexpr (SWEEP) stream_run_loop_program<true>(out, p, regs, ldt, stt, lins, pg, head, n, lane, live, input);
+        else stream_run_loop_program(out, p, regs, ldt, stt, lins, pg, head, n, lane, live, input);
     }
 }
 
@@ -2133,7 +2188,7 @@ hipError_t launch_stage_sweep(const StageArgs &a, hipStream_t s) {
 }
 
 // ---------------------------------------------------------------------------------------------------
-// The twelve resident kernels (kernels.hpp StreamKernel; the pieces and the protocol: above, "Block streaming"): ONE body,
+// The sixteen resident kernels (kernels.hpp StreamKernel; the pieces and the protocol: above, "Block streaming"): ONE body,
 // stream_resident_body, instantiated by the kernel's form (kernels.hpp StreamForm).  The body is the protocol's skeleton -- when
 // `alive` is published, the block loop and its stop test, which wave counts a voice in, when LDS may be reused -- and every
 // kernel is the one before it and one thing more:
@@ -2153,6 +2208,8 @@ hipError_t launch_stage_sweep(const StageArgs &a, hipStream_t s) {
 // and, beside the cascade, the form without a voice (kernels.hpp bank_stream_fx_kernel): the hist form's programs, doorbell and
 // history with no bank, no render and no hand-over -- a workgroup is ONE wave that runs a segment of programs  32 776
 // (bank_stream_store_fx_kernel: the same, and the streamed rows appended to the input store                 32 776)
+// and the four sweep forms (kernels.hpp bank_stream_sweep_kernel): the hist, fx, store and store_fx forms whose loop programs walk
+// the block in sweeps and know the Delays by a signal amount (stream_run_loop_program<true>); LDS as the form underneath.
 //
 // The bus segment is progs[voice_first[n_voices] .. voice_first[n_voices + 1]) and may be empty.  Which kernel a plan launches
 // is the host's rule (streamplan.hpp; fr_plan_json["stream"]["kernel"]).  The compiled kernels against their earlier,
@@ -2310,7 +2367,8 @@ __device__ __forceinline__ void stream_resident_body(StreamBanksArgs t, StreamGe
             const float t_row = live ? __hip_atomic_load(&stream_time_row(dev)[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0f;
             const StreamHistInput input{stream_input(dev, lane, t_row), h.hist, h.mask};
             auto run = [&](uint32_t p_first, uint32_t p_end) {
-                stream_run_programs_loops<true>(a.out, p, regs, ldt, stt, lins, p_first, p_end, head, T, lane, live, input);
+                if constexpr (F.sweep) stream_run_programs_loops<true, true>(a.out, p, regs, ldt, stt, lins, p_first, p_end, head, T, lane, live, input);
+                else stream_run_programs_loops<true>(a.out, p, regs, ldt, stt, lins, p_first, p_end, head, T, lane, live, input);
             };
             run(p.voice_first[blockIdx.x], p.voice_first[blockIdx.x + 1u]);
             stream_finish_bus(ctl, dev, n_voices, lane, seq, [&] { run(p.voice_first[n_voices], p.voice_first[n_voices + 1u]); });
@@ -2328,7 +2386,8 @@ __device__ __forceinline__ void stream_resident_body(StreamBanksArgs t, StreamGe
                     else return stream_input(dev, lane, t_in);
                 }();
                 auto run = [&](uint32_t p_first, uint32_t p_end) {
-                    if constexpr (F.loops) stream_run_programs_loops<F.dyn>(a.out, p, regs, ldt, stt, lins, p_first, p_end, head, T, lane, live, input);
+                    if constexpr (F.sweep) stream_run_programs_loops<true, true>(a.out, p, regs, ldt, stt, lins, p_first, p_end, head, T, lane, live, input);
+                    else if constexpr (F.loops) stream_run_programs_loops<F.dyn>(a.out, p, regs, ldt, stt, lins, p_first, p_end, head, T, lane, live, input);
                     else if constexpr (F.progs) stream_run_programs(a.out, p, regs, p_first, p_end, head + lane, lane, live, input);
                 };
                 stream_store_voice(w, a.out, p, head + lane, lane, live, result);
@@ -2394,6 +2453,24 @@ __global__ void __launch_bounds__(1024) bank_stream_store_fx_kernel(StreamHistAr
     stream_resident_body<StreamKernel::store_fx>({}, {}, h, st, a, p, n_rows, ctl, dev, idle_ms);
 }
 
+// The sweep forms (kernels.hpp bank_stream_sweep_kernel): the hist, fx, store and store_fx forms whose loop programs walk sweeps.
+__global__ void __launch_bounds__(1024) bank_stream_sweep_kernel(StreamBanksArgs t, StreamGeneralArgs g, StreamHistArgs h, BankArgs a, StreamProgArgs p, uint32_t n_rows,
+                                                                 BankStreamInCtl *ctl, BankStreamInDev *dev, uint32_t idle_ms) {
+    stream_resident_body<StreamKernel::sweep>(t, g, h, {}, a, p, n_rows, ctl, dev, idle_ms);
+}
+__global__ void __launch_bounds__(1024) bank_stream_sweep_fx_kernel(StreamHistArgs h, BankArgs a, StreamProgArgs p, uint32_t n_rows, BankStreamInCtl *ctl, BankStreamInDev *dev,
+                                                                    uint32_t idle_ms) {
+    stream_resident_body<StreamKernel::sweep_fx>({}, {}, h, {}, a, p, n_rows, ctl, dev, idle_ms);
+}
+__global__ void __launch_bounds__(1024) bank_stream_sweep_store_kernel(StreamBanksArgs t, StreamGeneralArgs g, StreamHistArgs h, StreamStoreArgs st, BankArgs a,
+                                                                       StreamProgArgs p, uint32_t n_rows, BankStreamInCtl *ctl, BankStreamInDev *dev, uint32_t idle_ms) {
+    stream_resident_body<StreamKernel::sweep_store>(t, g, h, st, a, p, n_rows, ctl, dev, idle_ms);
+}
+__global__ void __launch_bounds__(1024) bank_stream_sweep_store_fx_kernel(StreamHistArgs h, StreamStoreArgs st, BankArgs a, StreamProgArgs p, uint32_t n_rows,
+                                                                          BankStreamInCtl *ctl, BankStreamInDev *dev, uint32_t idle_ms) {
+    stream_resident_body<StreamKernel::sweep_store_fx>({}, {}, h, st, a, p, n_rows, ctl, dev, idle_ms);
+}
+
 // The one entry of the resident launches (kernels.hpp StreamLaunchArgs): the check, then the kernel with what it takes.
 hipError_t launch_bank_stream(StreamKernel k, const StreamLaunchArgs &x, hipStream_t s) {
     const uint32_t wgs = stream_launch_check(k, x);
@@ -2417,6 +2494,10 @@ hipError_t launch_bank_stream(StreamKernel k, const StreamLaunchArgs &x, hipStre
     case StreamKernel::fx: hipLaunchKernelGGL(bank_stream_fx_kernel, grid, wave, 0, s, x.h, x.a, x.p, x.n_rows, ctl_in, dev_in, idle_ms); break;
     case StreamKernel::store: hipLaunchKernelGGL(bank_stream_store_kernel, grid, block, 0, s, x.t, x.g, x.h, x.s, x.a, x.p, x.n_rows, ctl_in, dev_in, idle_ms); break;
     case StreamKernel::store_fx: hipLaunchKernelGGL(bank_stream_store_fx_kernel, grid, wave, 0, s, x.h, x.s, x.a, x.p, x.n_rows, ctl_in, dev_in, idle_ms); break;
+    case StreamKernel::sweep: hipLaunchKernelGGL(bank_stream_sweep_kernel, grid, block, 0, s, x.t, x.g, x.h, x.a, x.p, x.n_rows, ctl_in, dev_in, idle_ms); break;
+    case StreamKernel::sweep_fx: hipLaunchKernelGGL(bank_stream_sweep_fx_kernel, grid, wave, 0, s, x.h, x.a, x.p, x.n_rows, ctl_in, dev_in, idle_ms); break;
+    case StreamKernel::sweep_store: hipLaunchKernelGGL(bank_stream_sweep_store_kernel, grid, block, 0, s, x.t, x.g, x.h, x.s, x.a, x.p, x.n_rows, ctl_in, dev_in, idle_ms); break;
+    case StreamKernel::sweep_store_fx: hipLaunchKernelGGL(bank_stream_sweep_store_fx_kernel, grid, wave, 0, s, x.h, x.s, x.a, x.p, x.n_rows, ctl_in, dev_in, idle_ms); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

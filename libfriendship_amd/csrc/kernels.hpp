@@ -321,7 +321,8 @@ struct StreamGeneralArgs {
 // interpreter waits for the wave's own stores (s_waitcnt vmcnt(0)) before every program --, so no acquire, release, poll or wait
 // is added.  The index is masked: an address is inside the rings whatever the amount.
 // A plan without schedule banks is launched with mask == 0 (no schedule table).  The loop phases know no _DYN op: the rule
-// refuses one inside a loop program.  LDS: the general kernel's 45 072 bytes.
+// refuses one inside a loop program (the sweep forms below, FR_STREAM_SWEEP, have the phase that knows them).  LDS: the general
+// kernel's 45 072 bytes.
 
 // bank_stream_hist_kernel (FR_STREAM_HISTORY): bank_stream_dyn_kernel's composition and one more flag, for plans whose streamed
 // programs read an INPUT ROW at a delay: S_READ_INPUT (any constant delay, also inside a loop program, where it is one more
@@ -380,13 +381,39 @@ struct StreamStoreArgs {
     } row[BANK_STREAM_ROWS];
 };
 
-// The twelve resident kernels (streamplan.hpp stream_launch chooses; `none`: no resident launch yet) and their one launch entry.
+// bank_stream_sweep_kernel, bank_stream_sweep_fx_kernel, bank_stream_sweep_store_kernel, bank_stream_sweep_store_fx_kernel
+// (FR_STREAM_SWEEP): the hist, fx, store and store_fx forms with one flag more (StreamForm::sweep) -- phase 2 of a loop program is
+// a uniform loop over SWEEPS, and its interpreter knows the Delays by a signal amount.  StageProg::pad[0] of a loop program is its
+// sweep width w, 1..63 (streamplan.hpp stream_sweep_prepare; a loop program of constant stride: its stride): every read of a ring
+// the program stores reaches at least w frames back, so the frames [base, base + w) of a block depend only on frames < base.
+// Phases 0, 1 and 3 are the loops kernel's (phase 1 knows no _DYN op and skips it); phase 2 is
+//   for (base = 0; base < n; base += w)      -- w, n uniform for the wave
+//       lane < w, f = base + lane < n: one frame of the interpreter on register column f; then a wave phase
+// with the loops kernel's cases and three more:
+//   S_READ_DYN        fr = delay_frames(regs[a][f]).  The cast fails or head + f < fr: 0.0.  An own ring (imm = store slot + 1) and
+//                     fr <= f: the store tile [slot][(f - fr) & 63] -- a column below `base`, which an earlier iteration of this
+//                     wave wrote.  Else stream_prog_dyn's masked relaxed agent-scope load: a frame before the block, any other ring;
+//   S_STEP_DYN        stream_prog_dyn;
+//   S_READ_INPUT_DYN  stream_prog_dyn on the history of the streamed rows.
+// Why no wait, acquire, release, poll or s_barrier is added:
+//   * frames of this block: a frame of a sweep reads store-tile columns <= f - w < base, which earlier iterations of this ONE wave
+//     wrote -- LDS accesses of a wave complete in program order, the guarantee phase 2 has always relied on, now across lanes;
+//   * frames before the block: earlier blocks' ring stores, acknowledged before those blocks' tickets;
+//   * bank rings and earlier programs' rings: stored by this wave and waited for (s_waitcnt vmcnt(0)) before the program starts.
+// Every index is masked: an amount that violated its proof (fr < w) would read a stale column of the tile, never outside the tile
+// or the rings; every loop is bounded by n <= 64.  LDS: the form's underneath (45 072 with voices, 32 776 without).
+//
+// The sixteen resident kernels (streamplan.hpp stream_launch chooses; `none`: no resident launch yet) and their one launch entry.
 // plain, prog and bus have the one-row doorbell (BankStreamCtl / BankStreamDev), the others the doorbell of rows (BankStreamIn*).
-// (hist is dyn + 2, fx is hist + 2, store is fx + 2 and store_fx is store + 2: the values in between stay unnamed and refused, as
-// the tests of the launch check have always required)
-enum class StreamKernel : uint32_t { none, plain, prog, bus, in, banks, loops, general, dyn, hist = dyn + 2, fx = hist + 2, store = fx + 2, store_fx = store + 2 };
+// (hist is dyn + 2, fx is hist + 2, store is fx + 2, store_fx is store + 2, and the four sweep forms go on by 2: the values in
+// between stay unnamed and refused, as the tests of the launch check have always required)
+enum class StreamKernel : uint32_t {
+    none, plain, prog, bus, in, banks, loops, general, dyn, hist = dyn + 2, fx = hist + 2, store = fx + 2, store_fx = store + 2,
+    sweep = store_fx + 2, sweep_fx = sweep + 2, sweep_store = sweep_fx + 2, sweep_store_fx = sweep_store + 2
+};
 constexpr bool stream_kernel_named(StreamKernel k) {
-    return k != StreamKernel::none && (k <= StreamKernel::dyn || k == StreamKernel::hist || k == StreamKernel::fx || k == StreamKernel::store || k == StreamKernel::store_fx);
+    return k != StreamKernel::none && (k <= StreamKernel::dyn || k == StreamKernel::hist || k == StreamKernel::fx || k == StreamKernel::store || k == StreamKernel::store_fx ||
+                                       k == StreamKernel::sweep || k == StreamKernel::sweep_fx || k == StreamKernel::sweep_store || k == StreamKernel::sweep_store_fx);
 }
 // A kernel's form: what it has on top of bank_stream_kernel.  The nine kernels with voices are a cascade -- each is the one
 // before it and one thing more --, so the enum's order is their form; fx, which has no voice, is written out.  kernels.hip's one
@@ -402,8 +429,14 @@ struct StreamForm {
     bool hist;       // the history of the streamed rows (StreamHistArgs): delayed reads of input rows
     bool voiceless;  // no bank at all: a workgroup is one wave that runs a segment of programs (fx, store_fx)
     bool store = false;   // workgroup 0 also appends the streamed rows to the input store (StreamStoreArgs): store, store_fx
+    bool sweep = false;   // a loop program's phase 2 walks sweeps and knows the Delays by a signal amount: the four sweep forms
 };
 constexpr StreamForm stream_form(StreamKernel k) {
+    // the sweep forms: the form underneath and the flag
+    if (k == StreamKernel::sweep) return {true, true, true, true, true, true, true, true, false, false, true};          // hist
+    if (k == StreamKernel::sweep_fx) return {true, true, true, false, true, false, true, true, true, false, true};      // fx
+    if (k == StreamKernel::sweep_store) return {true, true, true, true, true, true, true, true, false, true, true};     // store
+    if (k == StreamKernel::sweep_store_fx) return {true, true, true, false, true, false, true, true, true, true, true}; // store_fx
     if (k == StreamKernel::fx)   // progs, bus, rows, loops, dyn and hist; no table, no schedule
         return {true, true, true, false, true, false, true, true, true};
     if (k == StreamKernel::store_fx) return {true, true, true, false, true, false, true, true, true, true};   // fx and the store

@@ -33,8 +33,8 @@
 // block and binds the program to that voice (or, with FR_STREAM_BUS, makes it a bus program); and S_STEP_DYN, which touches no
 // memory.  The finishing wave has just stored the voice's frames of this block and earlier blocks stored everything older, so
 // every such offset is readable and still nobody waits (kernels.hip bank_stream_dyn_kernel).  A signal delay of a ring that a
-// program stores (without FR_STREAM_TAPS), one inside a loop program, a delayed read of an input row and a bound observed from
-// input rows stay refused.
+// program stores (without FR_STREAM_TAPS), one inside a loop program (without FR_STREAM_SWEEP), a delayed read of an input row and
+// a bound observed from input rows stay refused.
 // With FR_STREAM_HISTORY=1 (StreamEnv::history) a program may read an INPUT ROW at a delay -- a pre-delay on a control row, a
 // delayed gate, Delay(In(0), d) on the time row itself: S_READ_INPUT at any constant delay, 0..63 included, in per-voice, bus and
 // loop programs (there it is one more frame-only load); with FR_STREAM_DYN also S_READ_INPUT_DYN, whose amount is anything in
@@ -42,7 +42,7 @@
 // rows there before any workgroup is released to render the block, so such a read waits for nobody, reads no voice, binds its
 // program to no voice and never makes it a bus program.  Its slot is streamed like an S_INPUT's (FR_STREAM_INPUTS for a slot
 // other than 0).  The deepest such read (StreamPlan::input_lookback) sizes the history, at most STREAM_HIST_MAX_FRAMES.
-// S_READ_INPUT_DYN inside a loop program and a bound observed from input rows stay refused.
+// S_READ_INPUT_DYN inside a loop program (without FR_STREAM_SWEEP) and a bound observed from input rows stay refused.
 // With FR_STREAM_EFFECTS=1 (StreamEnv::effects) a plan with NO bank launch at all -- an echo, a comb or a flanger on a row the host
 // feeds in, a gain on a control row, a one-pole smoother on a knob -- is served too, with voices == 0: its programs are dealt over
 // SEGMENTS, the ordered lists of programs that one workgroup runs (kernels.hpp bank_stream_fx_kernel; one wave each).  Every
@@ -61,6 +61,13 @@
 // a ring that an earlier bus program stores.  With FR_STREAM_DYN also S_READ_DYN of such a ring: its offset is anything in
 // [0, d_lo], a read below a block whatever the bound.  Still nobody waits.  A feedback plan and a plan with a fused form are what
 // they were; a storer that comes later in `run`, and an S_READ_DYN of a ring that no earlier program stores, stay refused.
+// With FR_STREAM_SWEEP=1 (StreamEnv::sweep), on top of FR_STREAM_LOOPS and FR_STREAM_DYN, a feedback plan's loops may hold Delays by
+// a signal amount: (a) a SWEEP PROGRAM reads a ring it stores itself through S_READ_DYN -- a sweep plan, FR_LOOP_DYN: a flanger with
+// regeneration, a comb with vibrato --; its width w (stream_sweep_width) is the least number of frames any read of its own rings
+// reaches back, S_READ_DYN.imm being the proven lower bound of an amount, and stands where a loop program's stride stands; (b) an
+// S_READ_DYN of a ring that an EARLIER program of `run` stores is admitted as FR_STREAM_TAPS admits it in other plans; (c) a loop
+// program of constant stride may hold S_READ_DYN of a bank's ring, S_STEP_DYN and, with a history, S_READ_INPUT_DYN.  The one wave
+// that runs a loop program walks the block w frames at a time (kernels.hpp bank_stream_sweep_kernel): still nobody waits.
 // HOW a served plan is launched is one rule as well (stream_path, stream_launch, plain_stream_launch, at the end): the path, the
 // kernel, its doorbell form, its tables, the loop limits, the workgroups.  fr_stream_begin, the seek, the block, the stop and
 // fr_plan_json's "kernel" read the StreamLaunch it returns and decide nothing themselves.
@@ -115,6 +122,7 @@ struct StreamEnv {
     bool effects = false;            // FR_STREAM_EFFECTS: plans without a bank launch: the programs are dealt over segments (StreamPlan::segments)
     bool taps = false;               // FR_STREAM_TAPS: the level form of a plan without feedback; short and signal delays of a ring an earlier program stores
     bool programs = false;           // FR_STREAM_PROGRAMS: the program path exists (stream_path; plan_stream does not ask)
+    bool sweep = false;              // FR_STREAM_SWEEP: Delays by a signal amount inside feedback loops shorter than a block (with `loops` and `dyn`)
     bool store = false;              // FR_STREAM_STORE, and not inert (streamstore.hpp): the launch stores the streamed rows; every plan takes the program path
 };
 
@@ -225,6 +233,9 @@ struct StreamPlan {
     std::vector<uint32_t> progs;         // indices into StagedPlan::progs, voice by voice, then the bus programs, in the order they run
     std::vector<uint32_t> loop_stride;   // per entry of `progs`: the stride of a loop program (1..63), 0 for any other (StreamEnv::loops)
     bool has_loops() const { return std::any_of(loop_stride.begin(), loop_stride.end(), [](uint32_t l) { return l != 0; }); }
+    std::vector<uint32_t> sweep_width;   // per entry of `progs`: the width of a sweep program (1..63, = its loop_stride), 0 for any other (StreamEnv::sweep)
+    bool sweep_loops = false;            // a loop program of constant stride holds a Delay by a signal amount: it needs the sweep walk too
+    bool has_sweep() const { return sweep_loops || std::any_of(sweep_width.begin(), sweep_width.end(), [](uint32_t w) { return w != 0; }); }
     std::vector<uint32_t> voice_first;   // [voices + 2] into `progs`: [voice_first[voices], voice_first[voices + 1]) is the bus segment
                                          // (a plan without a voice: [segments + 2], a segment where a voice stands)
     uint64_t min_ring_delay = 0;         // shortest delayed read of a ring that a program stores (0: there is none)
@@ -324,6 +335,53 @@ inline bool stream_loop_prepare(StageProg &pg, std::vector<StageInstr> &ins) {
     return true;
 }
 
+// A program's sweep width (FR_STREAM_SWEEP): the least number of frames that a read of a ring the program stores itself reaches
+// back -- an S_READ of 1 <= d_lo < 64 counts with d_lo, an own-ring S_READ_DYN with its imm, the proven lower bound of its amount
+// in frames (a sweep plan's, kernels.hpp S_READ_DYN).  0: the program has no own-ring S_READ_DYN, it is no sweep program; 64: it
+// has, and no read of its own rings reaches into a block -- it runs lane = frame.  (A bound of 0 answers 0 too: the rule refuses
+// it before it asks.)
+inline uint32_t stream_sweep_width(const StageProg &pg, const StageInstr *ins) {
+    const std::vector<uint32_t> mine = stream_stored_rings(pg, ins);
+    bool any = false;
+    uint32_t w = STREAM_BLOCK;
+    for (uint32_t i = 0; i < pg.n_instr; ++i) {
+        const StageInstr &in = ins[i];
+        if ((in.op != S_READ && in.op != S_READ_DYN) || std::find(mine.begin(), mine.end(), in.buf) == mine.end()) continue;
+        if (in.op == S_READ_DYN) {
+            any = true;
+            w = std::min(w, in.imm);
+        } else if (in.d_lo >= 1 && in.d_lo < STREAM_BLOCK) {
+            w = std::min(w, in.d_lo);
+        }
+    }
+    return any ? w : 0;
+}
+
+// The stream's own copy of a sweep program: stream_loop_prepare's slot marking -- S_STORE.imm = slot + 1, S_READ.imm = slot + 1 of
+// an own ring and 0 of any other, a dst_ring turned into an S_STORE --, and S_READ_DYN.imm = slot + 1 of an own ring and 0 of any
+// other (the bound has been consumed: it is the width); the width goes to pg.pad[0].  False (nothing the kernel may run) when the
+// program is no sweep program -- width 0 or 64 --, an own-ring S_READ_DYN has the bound 0, or the program exceeds the tiles.
+inline bool stream_sweep_prepare(StageProg &pg, std::vector<StageInstr> &ins) {
+    if (ins.size() != pg.n_instr) return false;
+    const uint32_t w = stream_sweep_width(pg, ins.data());
+    const std::vector<uint32_t> mine = stream_stored_rings(pg, ins.data());
+    if (w == 0 || w >= STREAM_BLOCK || mine.size() > STREAM_LOOP_STORES || stream_loop_loads(pg, ins.data()) > STREAM_LOOP_LOADS) return false;
+    auto slot = [&](uint32_t ring) { return (uint32_t)(std::find(mine.begin(), mine.end(), ring) - mine.begin()); };
+    for (StageInstr &in : ins) {
+        if (in.op == S_STORE) in.imm = slot(in.buf) + 1u;
+        if (in.op == S_READ || in.op == S_READ_DYN) in.imm = slot(in.buf) < mine.size() ? slot(in.buf) + 1u : 0u;
+    }
+    if (pg.dst_ring != 0xFFFFFFFFu) {
+        StageInstr st{};
+        st.op = S_STORE; st.a = (uint8_t)pg.result_reg; st.buf = pg.dst_ring; st.imm = slot(pg.dst_ring) + 1u;
+        ins.push_back(st);
+        pg.dst_ring = 0xFFFFFFFFu;
+        ++pg.n_instr;
+    }
+    pg.pad[0] = w;
+    return true;
+}
+
 // `banks`: the plan's bank launches (the engine moves them out of StagedPlan::banks when it uploads them).
 inline StreamPlan plan_stream(const StagedPlan &sp, const std::vector<const BankLaunch *> &banks, const StreamEnv &env) {
     StreamPlan s;
@@ -339,8 +397,10 @@ inline StreamPlan plan_stream(const StagedPlan &sp, const std::vector<const Bank
     if (env.pull_mode) return refuse("block streaming of a renderer in FR_MODE_PULL");
     if (!sp.pull_rows.empty()) return refuse(std::to_string(sp.pull_rows.size()) + " output rows are left to the pull interpreter");
     if (env.track_history || !sp.track_window_slots.empty() || sp.track_lookback != 0) return refuse("block streaming with a track history");
-    // (FR_LOOP_DYN: a sweep plan's launch forms are fr_fill_buffer's alone; the resident kernels have neither)
-    if (sp.fused_sweep) return refuse("a feedback loop delays by a signal amount (a sweep plan, FR_LOOP_DYN): block streaming does not serve it");
+    // (FR_LOOP_DYN: a sweep plan's launch forms are fr_fill_buffer's alone; the resident kernels have neither -- but for the sweep
+    // forms, FR_STREAM_SWEEP on top of FR_STREAM_LOOPS and FR_STREAM_DYN)
+    const bool sweep = env.sweep && env.loops && env.dyn;
+    if (sp.fused_sweep && !sweep) return refuse("a feedback loop delays by a signal amount (a sweep plan, FR_LOOP_DYN): block streaming does not serve it");
     const bool voiceless = env.effects && banks.empty();   // FR_STREAM_EFFECTS: the programs are dealt over segments, not voices
     if (banks.size() != 1 && !(env.banks && banks.size() >= 2 && banks.size() <= STREAM_MAX_BANKS) && !voiceless) {
         if (env.banks && banks.size() > STREAM_MAX_BANKS)
@@ -451,7 +511,11 @@ inline StreamPlan plan_stream(const StagedPlan &sp, const std::vector<const Bank
     // a read below a block of a ring that an EARLIER program of `run` stores binds the reader to the storer's voice (group): the
     // level behind a loop (loops), any level of a level form (taps)
     const bool follows = loops || taps;
-    std::vector<uint32_t> stride_of(run.size(), 0);
+    // FR_STREAM_SWEEP concerns a feedback plan too: S_READ_DYN of a ring the program stores itself (a sweep program), of a ring an
+    // earlier program stores (admitted as `taps` admits it), and the _DYN ops inside a loop program of constant stride
+    const bool sweeps = sweep && loops;
+    const bool dyn_taps = taps || sweeps;
+    std::vector<uint32_t> stride_of(run.size(), 0), width_of(run.size(), 0);
     // FR_STREAM_BUS: a program is a bus program when, at a delay below a block, it reads the bank rings of two or more voices
     // or a ring that an earlier bus program stores (a feedback plan's row copy of such a ring included)
     auto is_bus = [&](uint32_t k) {
@@ -461,7 +525,7 @@ inline StreamPlan plan_stream(const StagedPlan &sp, const std::vector<const Bank
         for (uint32_t i = 0; i < pg.n_instr; ++i) {
             const StageInstr &in = sp.instrs[pg.first_instr + i];
             const bool dyn_read = env.dyn && in.op == S_READ_DYN;   // (its offset may be below a block whatever its bound)
-            if (dyn_read && !taps && bank_ring_voice.find(in.buf) == bank_ring_voice.end()) continue;   // (of a program's ring: refused below)
+            if (dyn_read && !dyn_taps && bank_ring_voice.find(in.buf) == bank_ring_voice.end()) continue;   // (of a program's ring: refused below)
             if (!dyn_read && (in.op != S_READ || in.d_lo >= STREAM_BLOCK)) continue;
             auto bv = bank_ring_voice.find(in.buf);
             if (bv != bank_ring_voice.end()) {
@@ -502,7 +566,7 @@ inline StreamPlan plan_stream(const StagedPlan &sp, const std::vector<const Bank
         const bool copy = k >= first_copy;
         const bool bus = is_bus(k);
         uint32_t mine = NONE;
-        if (env.dyn && loops && stream_loop_stride(pg, sp.instrs.data() + pg.first_instr) != 0)   // the loop kernel's phases hoist frame-only loads
+        if (env.dyn && loops && !sweeps && stream_loop_stride(pg, sp.instrs.data() + pg.first_instr) != 0)   // the loop kernel's phases hoist frame-only loads
             for (uint32_t i = 0; i < pg.n_instr; ++i) {
                 const uint8_t op = sp.instrs[pg.first_instr + i].op;
                 if (op == S_READ_DYN || op == S_STEP_DYN || (env.history && op == S_READ_INPUT_DYN))
@@ -600,7 +664,16 @@ inline StreamPlan plan_stream(const StagedPlan &sp, const std::vector<const Bank
                 if (bv == bank_ring_voice.end()) {
                     // FR_STREAM_TAPS: a ring an EARLIER program of `run` stores -- whatever the bound a read below a block, as of a voice
                     auto st = stored_by.find(in.buf);
-                    if (!(taps && st != stored_by.end() && st->second < k))
+                    if (sweeps && st != stored_by.end() && st->second == k) {   // FR_STREAM_SWEEP: a ring the program stores itself: a sweep program
+                        // (imm: the amount's proven lower bound in frames; the planner refuses a sweep plan without one)
+                        if (in.imm == 0) return refuse("internal: a program delays a ring it stores itself by a signal amount without a proven lower bound");
+                        s.lookback = std::max<uint64_t>(s.lookback, in.d_lo);
+                        ++n_dyn_reads; ++n_dyn_ring_reads;
+                        min_delay = std::min<uint64_t>(min_delay, in.imm);
+                        if (in.imm < STREAM_BLOCK) ++n_short;       // (it may reach into the block: its width, stream_sweep_width, below)
+                        break;
+                    }
+                    if (!(dyn_taps && st != stored_by.end() && st->second < k))
                         return refuse("a program uses S_READ_DYN of a ring that a program stores (a Delay of a computed value by a signal amount, which may be 0 "
                                       "frames); block streaming serves signal delays of voices only");
                     s.lookback = std::max<uint64_t>(s.lookback, in.d_lo);
@@ -625,13 +698,22 @@ inline StreamPlan plan_stream(const StagedPlan &sp, const std::vector<const Bank
             if (in.dst >= STAGE_REGS || in.a >= STAGE_REGS || in.b >= STAGE_REGS) return refuse("a program needs more registers than the streamed interpreter has");
         }
         if (pg.result_reg >= STAGE_REGS) return refuse("a program needs more registers than the streamed interpreter has");
-        if (loops && (stride_of[k] = stream_loop_stride(pg, sp.instrs.data() + pg.first_instr)) != 0) {
+        // FR_STREAM_SWEEP: a sweep program's width stands where a loop program's stride stands; at width 64 no read reaches into a
+        // block and the program runs lane = frame, like a comb of 64 frames
+        const uint32_t width = sweeps ? stream_sweep_width(pg, sp.instrs.data() + pg.first_instr) : 0u;
+        if (width >= 1 && width < STREAM_BLOCK) stride_of[k] = width_of[k] = width;
+        if (loops && (width_of[k] != 0 || (stride_of[k] = stream_loop_stride(pg, sp.instrs.data() + pg.first_instr)) != 0)) {
             const uint32_t n_ld = stream_loop_loads(pg, sp.instrs.data() + pg.first_instr);
             const size_t n_st = stream_stored_rings(pg, sp.instrs.data() + pg.first_instr).size();
             if (n_ld > STREAM_LOOP_LOADS)
                 return refuse("a loop program has " + std::to_string(n_ld) + " frame-only loads; block streaming serves at most " + std::to_string(STREAM_LOOP_LOADS));
             if (n_st > STREAM_LOOP_STORES)
                 return refuse("a loop program stores " + std::to_string(n_st) + " rings; block streaming serves at most " + std::to_string(STREAM_LOOP_STORES));
+            if (sweeps && width_of[k] == 0)                          // (a loop program of constant stride with a _DYN op: the sweep walk runs it)
+                for (uint32_t i = 0; i < pg.n_instr; ++i) {
+                    const uint8_t op = sp.instrs[pg.first_instr + i].op;
+                    if (op == S_READ_DYN || op == S_STEP_DYN || op == S_READ_INPUT_DYN) s.sweep_loops = true;
+                }
         }
         // (reads no voice at a short delay: any one voice, the same every time; without a voice: it follows nobody and opens a group)
         voice_of[k] = bus ? BUS : mine != NONE ? mine : voiceless ? groups++ : run[k] % V;
@@ -667,9 +749,11 @@ inline StreamPlan plan_stream(const StagedPlan &sp, const std::vector<const Bank
     for (uint32_t v = 0; v <= V; ++v) s.voice_first[v + 1] += s.voice_first[v];
     s.progs.resize(run.size());
     s.loop_stride.resize(run.size());
+    s.sweep_width.resize(run.size());
     std::vector<uint32_t> at(s.voice_first.begin(), s.voice_first.end() - 1);
     for (uint32_t k = 0; k < run.size(); ++k) {                                      // (stable: the order of `run` inside a voice)
         s.loop_stride[at[voice_of[k]]] = stride_of[k];
+        s.sweep_width[at[voice_of[k]]] = width_of[k];
         s.progs[at[voice_of[k]]++] = run[k];
     }
     s.min_ring_delay = min_delay == UINT64_MAX ? 0 : min_delay;
@@ -692,6 +776,10 @@ inline const char *stream_kernel_name(StreamKernel k) {
     if (k == StreamKernel::fx) return "bank_stream_fx_kernel";       // (nor the value after hist)
     if (k == StreamKernel::store) return "bank_stream_store_kernel";
     if (k == StreamKernel::store_fx) return "bank_stream_store_fx_kernel";
+    if (k == StreamKernel::sweep) return "bank_stream_sweep_kernel";
+    if (k == StreamKernel::sweep_fx) return "bank_stream_sweep_fx_kernel";
+    if (k == StreamKernel::sweep_store) return "bank_stream_sweep_store_kernel";
+    if (k == StreamKernel::sweep_store_fx) return "bank_stream_sweep_store_fx_kernel";
     return names[(uint32_t)k < sizeof names / sizeof names[0] ? (uint32_t)k : 0];
 }
 
@@ -728,15 +816,19 @@ inline bool stream_path(const StagedPlan &sp, const std::vector<const BankLaunch
 // eleventh kernel).  On top of both: the store forms (StreamPlan::store, FR_STREAM_STORE) -- store for every plan with voices,
 // whatever the cascade would have chosen, store_fx for a plan without; the history is at least a block per row in both, and
 // n_rows counts the plan's slots (a store-mode stream may stream more: streamstore.hpp stream_store_slots, the engine's launch).
+// In front of everything: the sweep forms (StreamPlan::has_sweep, FR_STREAM_SWEEP) -- sweep is the hist form and the sweep walk,
+// sweep_fx the fx form, sweep_store and sweep_store_fx the store forms with it; the history, the tables and n_rows are those of the
+// form underneath.
 inline StreamLaunch stream_launch(const StagedPlan &sp, const StreamPlan &s) {
     StreamLaunch l;
     const bool fx = s.voices == 0;
-    l.kernel = s.store ? (fx ? StreamKernel::store_fx : StreamKernel::store) : fx ? StreamKernel::fx : s.has_hist() ? StreamKernel::hist : s.has_dyn() ? StreamKernel::dyn : s.has_general() ? StreamKernel::general : s.has_loops() ? StreamKernel::loops
+    l.kernel = s.has_sweep() ? (s.store ? (fx ? StreamKernel::sweep_store_fx : StreamKernel::sweep_store) : fx ? StreamKernel::sweep_fx : StreamKernel::sweep)
+               : s.store ? (fx ? StreamKernel::store_fx : StreamKernel::store) : fx ? StreamKernel::fx : s.has_hist() ? StreamKernel::hist : s.has_dyn() ? StreamKernel::dyn : s.has_general() ? StreamKernel::general : s.has_loops() ? StreamKernel::loops
                : s.banks.size() > 1 ? StreamKernel::banks : s.input_slots.size() > 1 ? StreamKernel::in : s.bus_programs() ? StreamKernel::bus : StreamKernel::prog;
     l.rows_doorbell = l.own_instrs = l.by_plan = stream_kernel_by_plan(l.kernel);
     l.bank_table = !fx && l.kernel >= StreamKernel::banks;   // (fx: also store_fx)
     l.schedule_table = !fx && (l.kernel == StreamKernel::general || (l.kernel >= StreamKernel::dyn && s.has_general()));
-    l.hist_cap = fx || s.store || l.kernel == StreamKernel::hist ? stream_hist_cap(s.input_lookback) : 0;
+    l.hist_cap = fx || s.store || l.kernel == StreamKernel::hist || l.kernel == StreamKernel::sweep ? stream_hist_cap(s.input_lookback) : 0;
     l.n_rows = l.rows_doorbell ? (uint32_t)s.input_slots.size() : 1u;
     for (size_t i = 0; i < s.progs.size(); ++i) {    // (the tiles' fill is counted from the plan's instructions; the store slots are the stored rings)
         if (!s.loop_stride[i]) continue;
