@@ -246,6 +246,28 @@ extern "C" {
  * bank_stream_sweep_fx_kernel, bank_stream_sweep_store_kernel, bank_stream_sweep_store_fx_kernel) for exactly these plans.  Still
  * refused: an amount whose lower bound the planner cannot prove (FR_ERR_CYCLE, as for fr_fill_buffer), a signal tap of a delay line
  * that a LATER program stores, a bound observed from input rows.
+ *
+ * FR_STREAM_LEAVES = 0 / 1 (default 0; read strictly from the environment too; does nothing unless FR_STREAM_PROGRAMS=1): block
+ * streaming also serves COMPILED VOICES -- voices whose leaves are not the sine partial but share one expression shape: a triangle
+ * partial (effects/triangle.fnd), a partial multiplied by a control row, a partial with a phase offset or a divisor; the voices
+ * that fr_fill_buffer renders with a kernel generated at run time.  The resident launch does not generate code: it INTERPRETS the
+ * leaf, a register program of one instruction per arithmetic primitive (at most 32 instructions over 8 registers), per partial, every
+ * operation rounded on its own and the leaves added in the graph's own association -- the same bits as fr_fill_buffer and as the
+ * reference, in both semantics.  Such a bank has voices of at least 128 partials and is cut into chunks over the device like a bank
+ * of template voices; envelopes, buses, loops, taps, the input history and FR_STREAM_STORE work behind it as behind any bank; next to
+ * a bank of another kind or of another leaf shape it needs FR_STREAM_BANKS like any second bank (at most 8 banks).  An input slot
+ * other than 0 that a leaf reads -- a gain row, a gate -- is a streamed row: it needs FR_STREAM_INPUTS, counts towards the 8 rows of
+ * a block and is listed in "input_slots"; what the leaf reads is what a program's read of that slot at that frame reads.  With 0
+ * nothing changes: every such patch is refused with the reason it has always had, and every other plan is served and refused, with
+ * the same reasons, by the same kernels.  "stream" gains "leaf_banks" -- per leaf bank in plan order {"ops", "regs", "params",
+ * "inputs"}: the leaf's instructions and registers, the parameters per partial, the distinct input slots it reads; [] when the plan
+ * has none -- and "kernel" names the two new kernels (bank_stream_leaf_kernel, with FR_STREAM_STORE bank_stream_leaf_store_kernel)
+ * for exactly the plans with a leaf bank.  An interpreted leaf costs several times the generated kernel's per partial
+ * (profiles/stream_leaves.txt): the option buys the real-time path's features for such patches, not speed.  Still refused, each
+ * with its own sentence: compiled voices of 32 or 64 partials; voices that read per-leaf track rows (track voices); a leaf of more
+ * than 32 instructions or 8 registers; a compiled bank that is cut over an exchange workspace; a feedback loop through a Delay of a
+ * signal amount (FR_STREAM_SWEEP) in a patch with compiled voices.  A plan that has no compiled bank -- while the run-time compiler
+ * is still at work, or with FR_JIT=0 -- is answered as it is today: the stream serves the plan in force.
  */
 typedef struct fr_option {
     const char *name;              /* e.g. "FR_BANK_SHORT" */

@@ -13,7 +13,7 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG_DIR, "csrc")
 OUT = os.path.join(PKG_DIR, "libfriendship_hip.so")
 SOURCES = ["engine.cpp", "graph.cpp", "match.cpp", "stage.cpp", "jit.cpp", "leafjit.cpp", "stagejit.cpp", "comm_rccl.cpp", "kernels.hip"]
-HEADERS = ["bankplan.hpp", "callplan.hpp", "graph.hpp", "kernels.hpp", "match.hpp", "stage.hpp", "streamplan.hpp", "streamrows.hpp", "streamstore.hpp", "jit.hpp", "leafshape.hpp", "comm.hpp", "range.hpp", os.path.join("..", "..", "include", "friendship_render.h"),
+HEADERS = ["bankplan.hpp", "callplan.hpp", "graph.hpp", "kernels.hpp", "match.hpp", "stage.hpp", "streamplan.hpp", "streamrows.hpp", "streamstore.hpp", "jit.hpp", "leafshape.hpp", "leafprog.hpp", "comm.hpp", "range.hpp", os.path.join("..", "..", "include", "friendship_render.h"),
            os.path.join("..", "..", "include", "friendship_render_ext.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",
          "-fno-slp-vectorize", "-mllvm", "-simplifycfg-sink-common=false", "-Wall", "-Wextra"]

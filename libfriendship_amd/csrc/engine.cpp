@@ -201,7 +201,7 @@ static std::string stage_variant(const StageLaunchNote &n, const Plan &p) {
     return k;
 }
 
-constexpr size_t N_OPTIONS = 44;        // per-renderer options (friendship_render_ext.h; the table below fr_renderer)
+constexpr size_t N_OPTIONS = 45;        // per-renderer options (friendship_render_ext.h; the table below fr_renderer)
 
 struct TimerClass {
     double ms = 0;
@@ -552,6 +552,7 @@ struct fr_renderer {
         // what outlives a stream: the buffers (they only grow), the last resident launch's kernel (fr_plan_json "stream"), the trace
         PinnedBuf h_ctl, h_out;
         DevBuf d_dev, d_progs, d_vfirst, d_sched, d_instrs, d_hist;   // (d_instrs: StreamLaunch::own_instrs; d_hist: StreamLaunch::hist_cap)
+        DevBuf d_leaf;                   // FR_STREAM_LEAVES: the leaf banks' programs, bank after bank (StreamPlan::leaf_progs; LEAF_IN by streamed row)
         StreamKernel last_kernel = StreamKernel::none;
         double trace_us[2] = {0, 0};
         uint64_t trace_n = 0;
@@ -578,9 +579,9 @@ struct fr_renderer {
         }
         return d_tickets.as<uint32_t>();
     }
-    // FR_STREAM_PROGRAMS, _BUS, _INPUTS, _LOOPS, _BANKS, _GENERAL, _DYN, _HISTORY, _EFFECTS, _STORE, _TAPS, _SWEEP (the options table says what each serves; streamplan.hpp StreamEnv)
+    // FR_STREAM_PROGRAMS, _BUS, _INPUTS, _LOOPS, _BANKS, _GENERAL, _DYN, _HISTORY, _EFFECTS, _STORE, _TAPS, _SWEEP, _LEAVES (the options table says what each serves; streamplan.hpp StreamEnv)
     bool stream_programs = false, stream_bus = false, stream_inputs = false, stream_loops = false, stream_banks = false, stream_general = false, stream_dyn = false,
-         stream_history = false, stream_effects = false, stream_store = false, stream_taps = false, stream_sweep = false;
+         stream_history = false, stream_effects = false, stream_store = false, stream_taps = false, stream_sweep = false, stream_leaves = false;
     // Why FR_STREAM_STORE does nothing for this renderer ("": it acts; streamstore.hpp)
     std::string stream_store_inert_now() const { return stream_store_inert(delay_observed, track_from != 0xFFFFFFFFu); }
     std::vector<const BankLaunch *> stream_bank_list() const {
@@ -602,6 +603,7 @@ struct fr_renderer {
         env.effects = stream_effects;
         env.taps = stream_taps;
         env.sweep = stream_sweep;
+        env.leaves = stream_leaves;
         env.store = stream_store && stream_programs && stream_store_inert_now().empty();
         return env;
     }
@@ -2405,6 +2407,26 @@ void fr_renderer::upload_stream_programs(const StreamPlan &s, const StreamLaunch
         strm.d_instrs.ensure(std::max<size_t>(instrs.size(), 1) * sizeof(StageInstr));
         if (!instrs.empty()) HIP_CHECK(hipMemcpyAsync(strm.d_instrs.p, instrs.data(), instrs.size() * sizeof(StageInstr), hipMemcpyHostToDevice, stream));
     }
+    // the leaf banks' programs (FR_STREAM_LEAVES), bank after bank: LEAF_IN's operand the streamed row, as S_INPUT's
+    std::vector<LeafInstr> leaf_ins;
+    for (const LeafProgram &lp : s.leaf_progs)
+        for (LeafInstr in : lp.ins) {
+            for (int side = 0; side < 2; ++side) {
+                if ((side ? in.kb : in.ka) != LEAF_IN) continue;
+                uint32_t &v = side ? in.b : in.a;
+                const auto it = v < lp.input_slots.size() ? std::find(row_slots.begin(), row_slots.end(), lp.input_slots[v]) : row_slots.end();
+                if (it == row_slots.end() || row_slots.size() > BANK_STREAM_ROWS) throw Error(FR_ERR_DEVICE, "internal: a streamed leaf reads a slot the stream does not feed");
+                v = (uint32_t)(it - row_slots.begin());
+            }
+            if (in.dst >= BANK_STREAM_LEAF_REGS || (in.ka == LEAF_REG && in.a >= BANK_STREAM_LEAF_REGS) || (in.kb == LEAF_REG && in.b >= BANK_STREAM_LEAF_REGS) ||
+                (in.ka == LEAF_PARAM && in.a >= lp.k) || (in.kb == LEAF_PARAM && in.b >= lp.k))
+                throw Error(FR_ERR_DEVICE, "internal: a leaf program out of the interpreter's bounds");
+            leaf_ins.push_back(in);
+        }
+    if (!leaf_ins.empty()) {
+        strm.d_leaf.ensure(leaf_ins.size() * sizeof(LeafInstr));
+        HIP_CHECK(hipMemcpyAsync(strm.d_leaf.p, leaf_ins.data(), leaf_ins.size() * sizeof(LeafInstr), hipMemcpyHostToDevice, stream));
+    }
     strm.d_progs.ensure(std::max<size_t>(progs.size(), 1) * sizeof(StageProg));
     strm.d_vfirst.ensure(s.voice_first.size() * sizeof(uint32_t));
     if (!progs.empty()) HIP_CHECK(hipMemcpyAsync(strm.d_progs.p, progs.data(), progs.size() * sizeof(StageProg), hipMemcpyHostToDevice, stream));
@@ -2555,6 +2577,28 @@ void fr_renderer::start_resident(uint64_t idx, bool empty_history) {
             }
             t.bank[i] = {b.d_params.as<float2>(), b.d_rows.as<uint32_t>(), sb.first_wg, sb.first_voice, sb.voices, sb.log2_p, sb.chunk_log2,
                          b.grp.fast_ok ? 1u : 0u, b.grp.to_ring ? 1u : 0u};
+        }
+        // leaf banks (FR_STREAM_LEAVES): each one's program in d_leaf (upload_stream_programs), its parameter table [voice][P][k] as uploaded
+        size_t leaf_at = 0;
+        for (size_t i = 0; i < s.leaf_progs.size() && i < s.banks.size(); ++i) {
+            const LeafProgram &lp = s.leaf_progs[i];
+            if (!s.banks[i].leaf) continue;
+            const BankStage &b = plan.banks[i];
+            if (!b.grp.jit || b.grp.tracks || lp.k == 0 || lp.k != std::max(b.grp.k, 1u) || lp.ins.size() > BANK_STREAM_LEAF_INSTRS ||
+                b.d_params.bytes < ((size_t)s.banks[i].voices << s.banks[i].log2_p) * lp.k * sizeof(float) || (leaf_at + lp.ins.size()) * sizeof(LeafInstr) > strm.d_leaf.bytes)
+                throw Error(FR_ERR_DEVICE, "internal: a leaf bank is not the plan's compiled bank");
+            uint32_t result = lp.result;
+            if (lp.result_kind == LEAF_IN) {                     // (a leaf that is a bare input: its row)
+                size_t row = 0;
+                const uint32_t slot = lp.result < lp.input_slots.size() ? lp.input_slots[lp.result] : UINT32_MAX;
+                if (strm.now.store) { while (row < strm.now.streamed.size() && strm.now.streamed[row].slot != slot) ++row; }
+                else row = (size_t)(std::find(s.input_slots.begin(), s.input_slots.end(), slot) - s.input_slots.begin());
+                if (row >= l.n_rows) throw Error(FR_ERR_DEVICE, "internal: a streamed leaf reads a slot the stream does not feed");
+                result = (uint32_t)row;
+            }
+            x.l.mask |= 1u << i;
+            x.l.bank[i] = {lp.ins.empty() ? nullptr : strm.d_leaf.as<uint4>() + leaf_at, (uint32_t)lp.ins.size(), lp.k, lp.result_kind, result};
+            leaf_at += lp.ins.size();
         }
     }
     // a stream that stores its rows: the buffers of the slots this launch appends to (streamstore.hpp StoreStreamed; the caller
@@ -2712,6 +2756,7 @@ int64_t env_strict_stream_effects(const char *e);
 int64_t env_strict_stream_store(const char *e);
 int64_t env_strict_stream_taps(const char *e);
 int64_t env_strict_stream_sweep(const char *e);
+int64_t env_strict_stream_leaves(const char *e);
 bool parse_option(const Knob &k, const char *s, int64_t &v);
 
 const Knob kKnobs[] = {
@@ -2842,6 +2887,11 @@ const Knob kKnobs[] = {
     // sweeps of its width (streamplan.hpp StreamEnv::sweep; fr_plan_json: stream.sweep_programs).  Acts on top of FR_STREAM_PROGRAMS,
     // FR_STREAM_LOOPS and FR_STREAM_DYN; inert without them.  Strict and listed once set.
     {"FR_STREAM_SWEEP", 0, 0, 1, 0, nullptr, 0, env_strict_stream_sweep, [](fr_renderer &r, int64_t v, bool) { r.stream_sweep = v != 0; }, LISTED_WHEN_SET},
+    // Compiled voices in block streaming -- voices whose leaves are not the sine partial but share one expression shape: a triangle
+    // partial, a partial times a control row, a sawtooth with a divisor: a leaf bank, whose leaf the rendering waves interpret as a
+    // register program (leafprog.hpp; streamplan.hpp StreamEnv::leaves; fr_plan_json: stream.leaf_banks).  Inert without
+    // FR_STREAM_PROGRAMS.  Strict and listed once set.
+    {"FR_STREAM_LEAVES", 0, 0, 1, 0, nullptr, 0, env_strict_stream_leaves, [](fr_renderer &r, int64_t v, bool) { r.stream_leaves = v != 0; }, LISTED_WHEN_SET},
 };
 static_assert(sizeof kKnobs / sizeof kKnobs[0] == N_OPTIONS, "N_OPTIONS counts the rows of kKnobs");
 
@@ -2867,6 +2917,7 @@ int64_t env_strict_stream_effects(const char *e) { return env_strict("FR_STREAM_
 int64_t env_strict_stream_store(const char *e) { return env_strict("FR_STREAM_STORE", e); }
 int64_t env_strict_stream_taps(const char *e) { return env_strict("FR_STREAM_TAPS", e); }
 int64_t env_strict_stream_sweep(const char *e) { return env_strict("FR_STREAM_SWEEP", e); }
+int64_t env_strict_stream_leaves(const char *e) { return env_strict("FR_STREAM_LEAVES", e); }
 
 bool parse_option(const Knob &k, const char *s, int64_t &v) {
     if (k.word && std::strcmp(s, k.word) == 0) {
@@ -3531,6 +3582,14 @@ const char *fr_plan_json(fr_renderer *r) {
             if (r->stream_taps)                                  // FR_STREAM_TAPS: the levels of the run form, the reads below a block of rings that programs store
                 r->plan_json_cache += ",\"levels\":" + std::to_string(s.levels) + ",\"short_reads\":" + std::to_string(s.short_reads) +
                                       ",\"dyn_ring_reads\":" + std::to_string(s.dyn_ring_reads);
+            if (r->stream_leaves) {                              // FR_STREAM_LEAVES: the leaf banks' programs, in plan order ([]: the plan has none)
+                std::string lb;
+                for (size_t i = 0; i < s.leaf_progs.size() && i < s.banks.size(); ++i)
+                    if (s.banks[i].leaf)
+                        lb += std::string(lb.empty() ? "" : ",") + "{\"ops\":" + std::to_string(s.leaf_progs[i].ins.size()) + ",\"regs\":" + std::to_string(s.leaf_progs[i].regs) +
+                              ",\"params\":" + std::to_string(s.leaf_progs[i].k) + ",\"inputs\":" + std::to_string(s.leaf_progs[i].inputs_read) + "}";
+                r->plan_json_cache += ",\"leaf_banks\":[" + lb + "]";
+            }
             if (r->stream_sweep) {                               // FR_STREAM_SWEEP: the width of every streamed program, in the order of `progs` (0: no sweep program)
                 std::string sw;
                 for (uint32_t w : s.sweep_width) sw += (sw.empty() ? "" : ",") + std::to_string(w);

@@ -1165,6 +1165,102 @@ __device__ __forceinline__ float stream_render_schedule(const float *params, con
     return r;
 }
 
+// A LEAF BANK (FR_STREAM_LEAVES, kernels.hpp StreamLeafArgs, where the argument stands): one (voice, chunk) of one block of
+// compiled voices, the leaf interpreted.  Lane = frame; the wave walks its 1/16 of the chunk's partials, and per partial runs
+// the bank's leaf program on its own register columns lr[register][lane] in LDS (a wave's LDS accesses complete in program
+// order, and no other wave touches its columns: no barrier inside).  What is uniform -- the instruction words, the partial's row
+// of the parameter table -- comes through the scalar cache (constant address space); a register and a staged row are LDS reads
+// at the lane's column.  Every arithmetic op is prim_binop's, separately rounded; no fast path, no fract body.
+__device__ __forceinline__ float stream_leaf_operand(uint32_t kind, uint32_t v, const_f32_ptr prow, uint32_t k, const float (&lr)[BANK_STREAM_LEAF_REGS][64],
+                                                     const float (&lin)[BANK_STREAM_ROWS][64], uint32_t lane) {
+    switch (kind) {   // (uniform)
+    case 0u: return lr[v & (BANK_STREAM_LEAF_REGS - 1u)][lane];
+    case 1u: return v < k ? prow[v] : 0.0f;   // (the host numbered the columns below k: the test never bites)
+    case 2u: return __uint_as_float(v);
+    default: return lin[v & (BANK_STREAM_ROWS - 1u)][lane];
+    }
+}
+typedef uint32_t __attribute__((address_space(4))) const *const_leaf_ptr;   // the instruction words: uniform, SMEM loads
+__device__ __forceinline__ float stream_leaf(const StreamLeafArgs::Bank &lb, const_f32_ptr prow, float (&lr)[BANK_STREAM_LEAF_REGS][64],
+                                             const float (&lin)[BANK_STREAM_ROWS][64], uint32_t lane, bool sparkle) {
+    const_leaf_ptr ins = (const_leaf_ptr)lb.instrs;
+    const uint32_t n = lb.n_instr < BANK_STREAM_LEAF_INSTRS ? lb.n_instr : BANK_STREAM_LEAF_INSTRS;
+    float v = 0.0f;
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint32_t head = ins[4u * i], a = ins[4u * i + 1u], b = ins[4u * i + 2u];   // {op | dst << 8 | ka << 16 | kb << 24, a, b, 0}
+        const float x = stream_leaf_operand((head >> 16) & 3u, a, prow, lb.k, lr, lin, lane);
+        const float y = stream_leaf_operand((head >> 24) & 3u, b, prow, lb.k, lr, lin, lane);
+        switch (head & 0xFFu) {   // (the interpreter's own cases, each op a constant, as STAGE_ARITH_CASES)
+        case OP_SUM2: v = prim_binop(OP_SUM2, x, y, sparkle); break;
+        case OP_MUL: v = prim_binop(OP_MUL, x, y, sparkle); break;
+        case OP_DIV: v = prim_binop(OP_DIV, x, y, sparkle); break;
+        case OP_MOD: v = prim_binop(OP_MOD, x, y, sparkle); break;
+        default: v = prim_binop(OP_MIN, x, y, sparkle); break;
+        }
+        lr[(head >> 8) & (BANK_STREAM_LEAF_REGS - 1u)][lane] = v;
+    }
+    // (the last instruction's value is the leaf -- its register is the result -- unless the leaf is a bare constant or input)
+    return lb.result_kind == 0u ? v : stream_leaf_operand(lb.result_kind, lb.result, prow, lb.k, lr, lin, lane);
+}
+
+// The chunk: the block's streamed rows staged in LDS (wave j loads row j; row 0 is the time row; a lane beyond the block holds
+// +0.0, as the republished rows do), then the leaves summed LITERALLY in the graph's association -- a group of 8 as bank_group
+// adds it, the binary-counter carry over the wave's <= 64 groups, the 16 wave sums in tree order through `sm` as
+// stream_render_chunk adds them.  Every add is performed, so a zero sum has the graph's sign: no repair pass.  Two barriers,
+// both under the workgroup-uniform condition that the bank is a leaf bank.  Returns the chunk's sum in wave 0; `t` is the lane's
+// time in every wave.
+__device__ __forceinline__ float stream_render_leaves(const StreamWork &w, const StreamBanksArgs::Bank &bk, const StreamLeafArgs::Bank &lb, const BankStreamInDev *dev,
+                                                      uint32_t n_rows, bool sparkle, bool live, uint32_t wave, uint32_t lane, float (&sm)[STREAM_NW][64],
+                                                      float (&lregs)[STREAM_NW][BANK_STREAM_LEAF_REGS][64], float (&lin)[BANK_STREAM_ROWS][64], float &t) {
+    constexpr int NW = STREAM_NW;
+    if (wave < BANK_STREAM_ROWS)
+        lin[wave][lane] = live && wave < n_rows ? __hip_atomic_load(&dev->rows[wave][lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0f;
+    __syncthreads();
+    t = lin[0][lane];
+    float(&lr)[BANK_STREAM_LEAF_REGS][64] = lregs[wave];
+    // this wave's partials: 8 * ngroups of them, from partial `first` of the bank's table [voice][P][k]
+    const size_t first = ((size_t)w.bank_voice << bk.log2_p) + ((size_t)w.chunk << bk.chunk_log2) + (size_t)wave * (w.ngroups << 3);
+    const_f32_ptr prow = (const_f32_ptr)((const float *)bk.params + first * lb.k);
+    // ONE binary counter over the wave's partials: level k holds the finished left sibling of height k.  Its levels 0..2 add a group
+    // of 8 as ((l0 + l1) + (l2 + l3)) + ((l4 + l5) + (l6 + l7)), the levels above are the carry chain over the groups -- one loop,
+    // one copy of the interpreter.  Named registers: nothing is indexed dynamically (no scratch).  j < 512: stream_bank_ok.
+    float c0 = 0.0f, c1 = 0.0f, c2 = 0.0f, c3 = 0.0f, c4 = 0.0f, c5 = 0.0f, c6 = 0.0f, c7 = 0.0f, c8 = 0.0f, c9 = 0.0f;
+    const uint32_t n = w.ngroups << 3;
+    for (uint32_t j = 0; j < n; ++j) {
+        float v = stream_leaf(lb, prow, lr, lin, lane, sparkle);
+        prow += lb.k;
+        do {
+            if (!(j & 1u)) { c0 = v; break; } v = c0 + v;
+            if (!(j & 2u)) { c1 = v; break; } v = c1 + v;
+            if (!(j & 4u)) { c2 = v; break; } v = c2 + v;
+            if (!(j & 8u)) { c3 = v; break; } v = c3 + v;
+            if (!(j & 16u)) { c4 = v; break; } v = c4 + v;
+            if (!(j & 32u)) { c5 = v; break; } v = c5 + v;
+            if (!(j & 64u)) { c6 = v; break; } v = c6 + v;
+            if (!(j & 128u)) { c7 = v; break; } v = c7 + v;
+            if (!(j & 256u)) { c8 = v; break; } v = c8 + v;
+            c9 = v;
+        } while (0);
+    }
+    const uint32_t top = w.levels + 3u;   // after the last partial (all ones) the chain stopped at level log2(n)
+    float rw = c9;
+    rw = top == 8u ? c8 : rw; rw = top == 7u ? c7 : rw; rw = top == 6u ? c6 : rw;
+    rw = top == 5u ? c5 : rw; rw = top == 4u ? c4 : rw; rw = top == 3u ? c3 : rw;
+    sm[wave][lane] = rw;
+    __syncthreads();
+    float r = 0.0f;
+    if (wave == 0u) {   // the NW wave sums in tree order: adjacent pairs, level by level
+        float s[NW];
+        static_for<0, NW>([&](auto i) { s[i] = sm[i][lane]; });
+        static_for<0, NW / 2>([&](auto i) { s[i] = s[2 * i] + s[2 * i + 1]; });
+        static_for<0, NW / 4>([&](auto i) { s[i] = s[2 * i] + s[2 * i + 1]; });
+        static_for<0, NW / 8>([&](auto i) { s[i] = s[2 * i] + s[2 * i + 1]; });
+        static_for<0, NW / 16>([&](auto i) { s[i] = s[2 * i] + s[2 * i + 1]; });
+        r = s[0];
+    }
+    return r;
+}
+
 // Wave 0 hands its chunk sum `r` over: store, acknowledged, then a ticket; the wave whose ticket is the voice's last reads all
 // chunks back and adds them in tree order, takes the top of the ladder for this voice's chunk count and resets the ticket for
 // the next block.  The chunk sums of all voices share one workspace, [chunk][n_voices][64] by global voice; one ticket per
@@ -2210,6 +2306,8 @@ hipError_t launch_stage_sweep(const StageArgs &a, hipStream_t s) {
 // (bank_stream_store_fx_kernel: the same, and the streamed rows appended to the input store                 32 776)
 // and the four sweep forms (kernels.hpp bank_stream_sweep_kernel): the hist, fx, store and store_fx forms whose loop programs walk
 // the block in sweeps and know the Delays by a signal amount (stream_run_loop_program<true>); LDS as the form underneath.
+// And the two leaf forms (kernels.hpp bank_stream_leaf_kernel): the hist and the store form whose leaf banks -- compiled voices --
+// are rendered by the leaf interpreter (stream_render_leaves); LDS: the form's 45 072 + 32 768 of registers + 2 048 of rows = 79 888.
 //
 // The bus segment is progs[voice_first[n_voices] .. voice_first[n_voices + 1]) and may be empty.  Which kernel a plan launches
 // is the host's rule (streamplan.hpp; fr_plan_json["stream"]["kernel"]).  The compiled kernels against their earlier,
@@ -2298,7 +2396,7 @@ __device__ __forceinline__ StreamRowsInput stream_input(const BankStreamInDev *d
 // (blockIdx.x - first_wg) whole: its chunk count is 1, so stream_hand_over returns at once.
 static_assert(STREAM_STACK_DEPTH == GB_MAX_DEPTH, "a schedule voice's stack is the general voices'");
 template <StreamKernel K, class Ctl, class Dev>
-__device__ __forceinline__ void stream_resident_body(StreamBanksArgs t, StreamGeneralArgs g, StreamHistArgs h, StreamStoreArgs st, BankArgs a, StreamProgArgs p,
+__device__ __forceinline__ void stream_resident_body(StreamBanksArgs t, StreamGeneralArgs g, StreamHistArgs h, StreamStoreArgs st, StreamLeafArgs lf, BankArgs a, StreamProgArgs p,
                                                      uint32_t n_rows, Ctl *ctl, Dev *dev, uint32_t idle_ms) {
     constexpr StreamForm F = stream_form(K);
     __shared__ float sm[F.schedule ? 2 : 1][STREAM_NW][64];  // the waves' sums: a chunk's in [0], a schedule's items alternate
@@ -2307,6 +2405,8 @@ __device__ __forceinline__ void stream_resident_body(StreamBanksArgs t, StreamGe
     __shared__ float ldt[BANK_STREAM_LOOP_LOADS][64];        // a loop program's loads, [load slot][frame]
     __shared__ float stt[BANK_STREAM_LOOP_STORES][64];       // ... and what it stores to its rings, [store slot][frame]
     __shared__ uint4 lins[BANK_STREAM_LOOP_INSTRS];          // ... and its (first) instructions
+    __shared__ float lregs[STREAM_NW][BANK_STREAM_LEAF_REGS][64];   // the leaf interpreter's registers: [wave][register][frame] (leaf forms only)
+    __shared__ float lin[BANK_STREAM_ROWS][64];              // ... and the block's streamed rows, [row][frame]
     __shared__ unsigned long long zshared;
     __shared__ uint32_t s_seq, s_T;
     StreamBanksArgs::Bank bk = {a.params, a.rows, 0u, 0u, a.n_voices, a.log2_p, a.chunk_log2, a.fast_ok, p.bank_to_ring};
@@ -2326,6 +2426,15 @@ __device__ __forceinline__ void stream_resident_body(StreamBanksArgs t, StreamGe
         });
     }
     const bool schedule = F.schedule && ((g.mask >> bi) & 1u);   // uniform: the workgroup's bank is a schedule bank
+    [[maybe_unused]] bool leaves = false;                        // uniform: ... or a leaf bank (the leaf forms only)
+    [[maybe_unused]] StreamLeafArgs::Bank lb = {};
+    if constexpr (F.leaf) {
+        leaves = (lf.mask >> bi) & 1u;
+        lb = lf.bank[0];
+        static_for<1, (int)BANK_STREAM_BANKS>([&](auto j) {
+            if (bi == (uint32_t)j) lb = lf.bank[j];
+        });
+    }
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t local = blockIdx.x - bk.first_wg;
@@ -2375,7 +2484,11 @@ __device__ __forceinline__ void stream_resident_body(StreamBanksArgs t, StreamGe
         } else {
             float t_in, result, r;
             // (the conditional expression the general kernel has always had: as an if / else its compiled loop comes out another)
-            if constexpr (F.schedule)
+            if constexpr (F.leaf)
+                r = leaves     ? stream_render_leaves(w, bk, lb, dev, n_rows, p.sparkle != 0u, live, wave, lane, sm[0], lregs, lin, t_in)
+                    : schedule ? stream_render_schedule(vparams, items, nitems, bk.fast_ok, stream_time_row(dev), live, wave, lane, sm, stack_mem, zshared, t_in)
+                               : stream_render_chunk(w, stream_time_row(dev), live, wave, lane, sm[0], zshared, t_in);
+            else if constexpr (F.schedule)
                 r = schedule ? stream_render_schedule(vparams, items, nitems, bk.fast_ok, stream_time_row(dev), live, wave, lane, sm, stack_mem, zshared, t_in)
                              : stream_render_chunk(w, stream_time_row(dev), live, wave, lane, sm[0], zshared, t_in);
             else r = stream_render_chunk(w, stream_time_row(dev), live, wave, lane, sm[0], zshared, t_in);
@@ -2403,72 +2516,83 @@ __device__ __forceinline__ void stream_resident_body(StreamBanksArgs t, StreamGe
 }
 
 __global__ void __launch_bounds__(1024) bank_stream_kernel(BankArgs a, BankStreamCtl *ctl, BankStreamDev *dev, uint32_t idle_ms) {
-    stream_resident_body<StreamKernel::plain>({}, {}, {}, {}, a, {}, 1u, ctl, dev, idle_ms);
+    stream_resident_body<StreamKernel::plain>({}, {}, {}, {}, {}, a, {}, 1u, ctl, dev, idle_ms);
 }
 __global__ void __launch_bounds__(1024) bank_stream_prog_kernel(BankArgs a, StreamProgArgs p, BankStreamCtl *ctl, BankStreamDev *dev, uint32_t idle_ms) {
-    stream_resident_body<StreamKernel::prog>({}, {}, {}, {}, a, p, 1u, ctl, dev, idle_ms);
+    stream_resident_body<StreamKernel::prog>({}, {}, {}, {}, {}, a, p, 1u, ctl, dev, idle_ms);
 }
 __global__ void __launch_bounds__(1024) bank_stream_bus_kernel(BankArgs a, StreamProgArgs p, BankStreamCtl *ctl, BankStreamDev *dev, uint32_t idle_ms) {
-    stream_resident_body<StreamKernel::bus>({}, {}, {}, {}, a, p, 1u, ctl, dev, idle_ms);
+    stream_resident_body<StreamKernel::bus>({}, {}, {}, {}, {}, a, p, 1u, ctl, dev, idle_ms);
 }
 __global__ void __launch_bounds__(1024) bank_stream_in_kernel(BankArgs a, StreamProgArgs p, uint32_t n_rows, BankStreamInCtl *ctl, BankStreamInDev *dev, uint32_t idle_ms) {
-    stream_resident_body<StreamKernel::in>({}, {}, {}, {}, a, p, n_rows, ctl, dev, idle_ms);
+    stream_resident_body<StreamKernel::in>({}, {}, {}, {}, {}, a, p, n_rows, ctl, dev, idle_ms);
 }
 __global__ void __launch_bounds__(1024) bank_stream_banks_kernel(StreamBanksArgs t, BankArgs a, StreamProgArgs p, uint32_t n_rows, BankStreamInCtl *ctl,
                                                                  BankStreamInDev *dev, uint32_t idle_ms) {
-    stream_resident_body<StreamKernel::banks>(t, {}, {}, {}, a, p, n_rows, ctl, dev, idle_ms);
+    stream_resident_body<StreamKernel::banks>(t, {}, {}, {}, {}, a, p, n_rows, ctl, dev, idle_ms);
 }
 __global__ void __launch_bounds__(1024) bank_stream_loops_kernel(StreamBanksArgs t, BankArgs a, StreamProgArgs p, uint32_t n_rows, BankStreamInCtl *ctl,
                                                                  BankStreamInDev *dev, uint32_t idle_ms) {
-    stream_resident_body<StreamKernel::loops>(t, {}, {}, {}, a, p, n_rows, ctl, dev, idle_ms);
+    stream_resident_body<StreamKernel::loops>(t, {}, {}, {}, {}, a, p, n_rows, ctl, dev, idle_ms);
 }
 __global__ void __launch_bounds__(1024) bank_stream_general_kernel(StreamBanksArgs t, StreamGeneralArgs g, BankArgs a, StreamProgArgs p, uint32_t n_rows, BankStreamInCtl *ctl,
                                                                    BankStreamInDev *dev, uint32_t idle_ms) {
-    stream_resident_body<StreamKernel::general>(t, g, {}, {}, a, p, n_rows, ctl, dev, idle_ms);
+    stream_resident_body<StreamKernel::general>(t, g, {}, {}, {}, a, p, n_rows, ctl, dev, idle_ms);
 }
 __global__ void __launch_bounds__(1024) bank_stream_dyn_kernel(StreamBanksArgs t, StreamGeneralArgs g, BankArgs a, StreamProgArgs p, uint32_t n_rows, BankStreamInCtl *ctl,
                                                                BankStreamInDev *dev, uint32_t idle_ms) {
-    stream_resident_body<StreamKernel::dyn>(t, g, {}, {}, a, p, n_rows, ctl, dev, idle_ms);
+    stream_resident_body<StreamKernel::dyn>(t, g, {}, {}, {}, a, p, n_rows, ctl, dev, idle_ms);
 }
 __global__ void __launch_bounds__(1024) bank_stream_hist_kernel(StreamBanksArgs t, StreamGeneralArgs g, StreamHistArgs h, BankArgs a, StreamProgArgs p, uint32_t n_rows,
                                                                 BankStreamInCtl *ctl, BankStreamInDev *dev, uint32_t idle_ms) {
-    stream_resident_body<StreamKernel::hist>(t, g, h, {}, a, p, n_rows, ctl, dev, idle_ms);
+    stream_resident_body<StreamKernel::hist>(t, g, h, {}, {}, a, p, n_rows, ctl, dev, idle_ms);
 }
 // (LAUNCHED with one wave per workgroup: a segment of programs needs no more, and nothing is rendered.  The bound stays the other
 // forms': under __launch_bounds__(64) the compiler sees that 32 KiB of LDS leave room for one wave per SIMD and pads the wave's
 // register allocation to 257 VGPRs to say so; with this bound it records the 48 the code uses)
 __global__ void __launch_bounds__(1024) bank_stream_fx_kernel(StreamHistArgs h, BankArgs a, StreamProgArgs p, uint32_t n_rows, BankStreamInCtl *ctl, BankStreamInDev *dev,
                                                             uint32_t idle_ms) {
-    stream_resident_body<StreamKernel::fx>({}, {}, h, {}, a, p, n_rows, ctl, dev, idle_ms);
+    stream_resident_body<StreamKernel::fx>({}, {}, h, {}, {}, a, p, n_rows, ctl, dev, idle_ms);
 }
 
 // The store forms (kernels.hpp StreamStoreArgs): the hist form and the fx form, whose workgroup 0 also appends the streamed rows to
 // the input store.
 __global__ void __launch_bounds__(1024) bank_stream_store_kernel(StreamBanksArgs t, StreamGeneralArgs g, StreamHistArgs h, StreamStoreArgs st, BankArgs a, StreamProgArgs p,
                                                                  uint32_t n_rows, BankStreamInCtl *ctl, BankStreamInDev *dev, uint32_t idle_ms) {
-    stream_resident_body<StreamKernel::store>(t, g, h, st, a, p, n_rows, ctl, dev, idle_ms);
+    stream_resident_body<StreamKernel::store>(t, g, h, st, {}, a, p, n_rows, ctl, dev, idle_ms);
 }
 __global__ void __launch_bounds__(1024) bank_stream_store_fx_kernel(StreamHistArgs h, StreamStoreArgs st, BankArgs a, StreamProgArgs p, uint32_t n_rows, BankStreamInCtl *ctl,
                                                                     BankStreamInDev *dev, uint32_t idle_ms) {
-    stream_resident_body<StreamKernel::store_fx>({}, {}, h, st, a, p, n_rows, ctl, dev, idle_ms);
+    stream_resident_body<StreamKernel::store_fx>({}, {}, h, st, {}, a, p, n_rows, ctl, dev, idle_ms);
+}
+
+// The leaf forms (kernels.hpp bank_stream_leaf_kernel): the hist form and the store form whose leaf banks -- compiled voices -- are
+// rendered by the leaf interpreter (stream_render_leaves).
+__global__ void __launch_bounds__(1024) bank_stream_leaf_kernel(StreamBanksArgs t, StreamGeneralArgs g, StreamHistArgs h, StreamLeafArgs lf, BankArgs a, StreamProgArgs p,
+                                                                uint32_t n_rows, BankStreamInCtl *ctl, BankStreamInDev *dev, uint32_t idle_ms) {
+    stream_resident_body<StreamKernel::leaf>(t, g, h, {}, lf, a, p, n_rows, ctl, dev, idle_ms);
+}
+__global__ void __launch_bounds__(1024) bank_stream_leaf_store_kernel(StreamBanksArgs t, StreamGeneralArgs g, StreamHistArgs h, StreamStoreArgs st, StreamLeafArgs lf, BankArgs a,
+                                                                      StreamProgArgs p, uint32_t n_rows, BankStreamInCtl *ctl, BankStreamInDev *dev, uint32_t idle_ms) {
+    stream_resident_body<StreamKernel::leaf_store>(t, g, h, st, lf, a, p, n_rows, ctl, dev, idle_ms);
 }
 
 // The sweep forms (kernels.hpp bank_stream_sweep_kernel): the hist, fx, store and store_fx forms whose loop programs walk sweeps.
 __global__ void __launch_bounds__(1024) bank_stream_sweep_kernel(StreamBanksArgs t, StreamGeneralArgs g, StreamHistArgs h, BankArgs a, StreamProgArgs p, uint32_t n_rows,
                                                                  BankStreamInCtl *ctl, BankStreamInDev *dev, uint32_t idle_ms) {
-    stream_resident_body<StreamKernel::sweep>(t, g, h, {}, a, p, n_rows, ctl, dev, idle_ms);
+    stream_resident_body<StreamKernel::sweep>(t, g, h, {}, {}, a, p, n_rows, ctl, dev, idle_ms);
 }
 __global__ void __launch_bounds__(1024) bank_stream_sweep_fx_kernel(StreamHistArgs h, BankArgs a, StreamProgArgs p, uint32_t n_rows, BankStreamInCtl *ctl, BankStreamInDev *dev,
                                                                     uint32_t idle_ms) {
-    stream_resident_body<StreamKernel::sweep_fx>({}, {}, h, {}, a, p, n_rows, ctl, dev, idle_ms);
+    stream_resident_body<StreamKernel::sweep_fx>({}, {}, h, {}, {}, a, p, n_rows, ctl, dev, idle_ms);
 }
 __global__ void __launch_bounds__(1024) bank_stream_sweep_store_kernel(StreamBanksArgs t, StreamGeneralArgs g, StreamHistArgs h, StreamStoreArgs st, BankArgs a,
                                                                        StreamProgArgs p, uint32_t n_rows, BankStreamInCtl *ctl, BankStreamInDev *dev, uint32_t idle_ms) {
-    stream_resident_body<StreamKernel::sweep_store>(t, g, h, st, a, p, n_rows, ctl, dev, idle_ms);
+    stream_resident_body<StreamKernel::sweep_store>(t, g, h, st, {}, a, p, n_rows, ctl, dev, idle_ms);
 }
 __global__ void __launch_bounds__(1024) bank_stream_sweep_store_fx_kernel(StreamHistArgs h, StreamStoreArgs st, BankArgs a, StreamProgArgs p, uint32_t n_rows,
                                                                           BankStreamInCtl *ctl, BankStreamInDev *dev, uint32_t idle_ms) {
-    stream_resident_body<StreamKernel::sweep_store_fx>({}, {}, h, st, a, p, n_rows, ctl, dev, idle_ms);
+    stream_resident_body<StreamKernel::sweep_store_fx>({}, {}, h, st, {}, a, p, n_rows, ctl, dev, idle_ms);
 }
 
 // The one entry of the resident launches (kernels.hpp StreamLaunchArgs): the check, then the kernel with what it takes.
@@ -2498,6 +2622,8 @@ hipError_t launch_bank_stream(StreamKernel k, const StreamLaunchArgs &x, hipStre
     case StreamKernel::sweep_fx: hipLaunchKernelGGL(bank_stream_sweep_fx_kernel, grid, wave, 0, s, x.h, x.a, x.p, x.n_rows, ctl_in, dev_in, idle_ms); break;
     case StreamKernel::sweep_store: hipLaunchKernelGGL(bank_stream_sweep_store_kernel, grid, block, 0, s, x.t, x.g, x.h, x.s, x.a, x.p, x.n_rows, ctl_in, dev_in, idle_ms); break;
     case StreamKernel::sweep_store_fx: hipLaunchKernelGGL(bank_stream_sweep_store_fx_kernel, grid, wave, 0, s, x.h, x.s, x.a, x.p, x.n_rows, ctl_in, dev_in, idle_ms); break;
+    case StreamKernel::leaf: hipLaunchKernelGGL(bank_stream_leaf_kernel, grid, block, 0, s, x.t, x.g, x.h, x.l, x.a, x.p, x.n_rows, ctl_in, dev_in, idle_ms); break;
+    case StreamKernel::leaf_store: hipLaunchKernelGGL(bank_stream_leaf_store_kernel, grid, block, 0, s, x.t, x.g, x.h, x.s, x.l, x.a, x.p, x.n_rows, ctl_in, dev_in, idle_ms); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

@@ -403,17 +403,46 @@ struct StreamStoreArgs {
 // Every index is masked: an amount that violated its proof (fr < w) would read a stale column of the tile, never outside the tile
 // or the rings; every loop is bounded by n <= 64.  LDS: the form's underneath (45 072 with voices, 32 776 without).
 //
-// The sixteen resident kernels (streamplan.hpp stream_launch chooses; `none`: no resident launch yet) and their one launch entry.
+// bank_stream_leaf_kernel, bank_stream_leaf_store_kernel (FR_STREAM_LEAVES): the hist form and the store form with one flag more
+// (StreamForm::leaf) -- a LEAF BANK, a bank of compiled voices (stage.hpp BankLaunch::jit: leaves of one arbitrary expression
+// shape, which fr_fill_buffer renders with a hipRTC-generated kernel), is rendered by a LEAF INTERPRETER.  Bit `i` of
+// StreamLeafArgs::mask says that bank i of the StreamBanksArgs table is a leaf bank: its Bank::params is the bank's uploaded
+// parameter table [voice][1 << log2_p][k] floats, k = StreamLeafArgs::bank[i].k, and it is chunked over workgroups exactly as a
+// template bank (16 waves x groups of 8, one workgroup per (voice, chunk)).  Its leaf is a program (leafprog.hpp): n_instr
+// instructions `dst = a op b` over BANK_STREAM_LEAF_REGS registers, an operand a register, a parameter column, a literal or a
+// streamed row at the lane's frame (LEAF_IN's operand is the ROW, rewritten by the engine as S_INPUT's is).
+// kernels.hip stream_render_leaves: lane = frame, a wave walks its 1/16 of the chunk's partials; per partial it runs the program
+// on its own LDS register columns regs[wave][register][lane] -- instruction words and parameters are uniform and come through the
+// scalar cache --, every op through prim_binop, separately rounded; the leaves are summed literally in the graph's association
+// (a group of 8 as ((l0+l1)+(l2+l3))+((l4+l5)+(l6+l7)), the binary-counter carry chain over the wave's groups, the 16 wave sums
+// in tree order through LDS, the chunk sums through stream_hand_over).  Every add is performed, so a zero has the graph's sign
+// and there is no repair pass.  The block's streamed rows are staged once per block in LDS (wave j loads row j, one barrier, under
+// the workgroup-uniform condition that its bank is a leaf bank).  No acquire, release, poll or wait is added: the rows were
+// republished before the workgroup saw the block's seq, as the time row always was.
+// LDS: the form underneath (45 072) + the register file 16 x 8 x 256 = 32 768 + the staged rows 8 x 256 = 2 048: 79 888.
+constexpr uint32_t BANK_STREAM_LEAF_INSTRS = 32, BANK_STREAM_LEAF_REGS = 8;
+struct StreamLeafArgs {
+    uint32_t mask;
+    struct Bank {
+        const uint4 *instrs;       // [n_instr] {op | dst << 8 | ka << 16 | kb << 24, a, b, 0} (leafprog.hpp LeafInstr)
+        uint32_t n_instr, k;       // instructions (0: the leaf is its result operand), floats per partial of the parameter table
+        uint32_t result_kind, result;   // the leaf's value as an operand
+    } bank[BANK_STREAM_BANKS];
+};
+
+// The eighteen resident kernels (streamplan.hpp stream_launch chooses; `none`: no resident launch yet) and their one launch entry.
 // plain, prog and bus have the one-row doorbell (BankStreamCtl / BankStreamDev), the others the doorbell of rows (BankStreamIn*).
 // (hist is dyn + 2, fx is hist + 2, store is fx + 2, store_fx is store + 2, and the four sweep forms go on by 2: the values in
 // between stay unnamed and refused, as the tests of the launch check have always required)
 enum class StreamKernel : uint32_t {
     none, plain, prog, bus, in, banks, loops, general, dyn, hist = dyn + 2, fx = hist + 2, store = fx + 2, store_fx = store + 2,
-    sweep = store_fx + 2, sweep_fx = sweep + 2, sweep_store = sweep_fx + 2, sweep_store_fx = sweep_store + 2
+    sweep = store_fx + 2, sweep_fx = sweep + 2, sweep_store = sweep_fx + 2, sweep_store_fx = sweep_store + 2,
+    leaf = sweep_store_fx + 4, leaf_store = leaf + 2   // (the value after the sweep forms stays unnamed as well)
 };
 constexpr bool stream_kernel_named(StreamKernel k) {
     return k != StreamKernel::none && (k <= StreamKernel::dyn || k == StreamKernel::hist || k == StreamKernel::fx || k == StreamKernel::store || k == StreamKernel::store_fx ||
-                                       k == StreamKernel::sweep || k == StreamKernel::sweep_fx || k == StreamKernel::sweep_store || k == StreamKernel::sweep_store_fx);
+                                       k == StreamKernel::sweep || k == StreamKernel::sweep_fx || k == StreamKernel::sweep_store || k == StreamKernel::sweep_store_fx ||
+                                       k == StreamKernel::leaf || k == StreamKernel::leaf_store);
 }
 // A kernel's form: what it has on top of bank_stream_kernel.  The nine kernels with voices are a cascade -- each is the one
 // before it and one thing more --, so the enum's order is their form; fx, which has no voice, is written out.  kernels.hip's one
@@ -430,8 +459,12 @@ struct StreamForm {
     bool voiceless;  // no bank at all: a workgroup is one wave that runs a segment of programs (fx, store_fx)
     bool store = false;   // workgroup 0 also appends the streamed rows to the input store (StreamStoreArgs): store, store_fx
     bool sweep = false;   // a loop program's phase 2 walks sweeps and knows the Delays by a signal amount: the four sweep forms
+    bool leaf = false;    // leaf banks (StreamLeafArgs): compiled voices rendered by the leaf interpreter: leaf, leaf_store
 };
 constexpr StreamForm stream_form(StreamKernel k) {
+    // the leaf forms: the hist form and the store form, and the flag
+    if (k == StreamKernel::leaf) return {true, true, true, true, true, true, true, true, false, false, false, true};
+    if (k == StreamKernel::leaf_store) return {true, true, true, true, true, true, true, true, false, true, false, true};
     // the sweep forms: the form underneath and the flag
     if (k == StreamKernel::sweep) return {true, true, true, true, true, true, true, true, false, false, true};          // hist
     if (k == StreamKernel::sweep_fx) return {true, true, true, false, true, false, true, true, true, false, true};      // fx
@@ -452,6 +485,7 @@ struct StreamLaunchArgs {
     StreamGeneralArgs g;
     StreamHistArgs h;                           // (read for the forms with a history)
     StreamStoreArgs s;                          // (read for the store forms)
+    StreamLeafArgs l;                           // (read for the leaf forms)
     uint32_t n_rows, max_stride, max_loads, max_stores;
     void *ctl_dev, *dev;                        // the control block as the device addresses it and the device block, of the kernel's doorbell form
     uint32_t idle_ms;                           // 0 = BANK_STREAM_IDLE_MS
@@ -514,6 +548,20 @@ inline uint32_t stream_launch_check(StreamKernel k, const StreamLaunchArgs &x) {
         if (f.schedule && !f.dyn && mask == 0) return 0;   // (only dyn takes a plan without a schedule bank)
         wgs = stream_table_ok(x.t, a, mask, to_ring);
         if (!wgs) return 0;
+        if (f.leaf) {
+            // a leaf form is launched for a plan with a leaf bank; a leaf bank is chunked (stream_table_ok has checked it as a
+            // template bank's shape), never a schedule bank, and its program is within the interpreter's limits
+            const uint32_t leaves = x.l.mask;
+            if (leaves == 0 || (leaves >> x.t.n_banks) != 0 || (leaves & mask) != 0) return 0;
+            for (uint32_t i = 0; i < x.t.n_banks; ++i) {
+                if (!((leaves >> i) & 1u)) continue;
+                const StreamLeafArgs::Bank &lb = x.l.bank[i];
+                if (lb.n_instr > BANK_STREAM_LEAF_INSTRS || (lb.n_instr && !lb.instrs) || lb.k == 0 || lb.result_kind > 3u) return 0;
+                if (lb.result_kind == 0u && (lb.n_instr == 0 || lb.result >= BANK_STREAM_LEAF_REGS)) return 0;   // a register nobody wrote
+                if (lb.result_kind == 1u && lb.result >= lb.k) return 0;
+                if (lb.result_kind == 3u && lb.result >= x.n_rows) return 0;
+            }
+        }
         for (uint32_t i = 0; i < x.t.n_banks; ++i)
             if (((mask >> i) & 1u) && (!x.g.bank[i].groups || !x.g.bank[i].group_off)) return 0;
     } else {

@@ -68,6 +68,16 @@
 // S_READ_DYN of a ring that an EARLIER program of `run` stores is admitted as FR_STREAM_TAPS admits it in other plans; (c) a loop
 // program of constant stride may hold S_READ_DYN of a bank's ring, S_STEP_DYN and, with a history, S_READ_INPUT_DYN.  The one wave
 // that runs a loop program walks the block w frames at a time (kernels.hpp bank_stream_sweep_kernel): still nobody waits.
+// With FR_STREAM_LEAVES=1 (StreamEnv::leaves) a bank of COMPILED VOICES -- voices whose leaves are not the hand-matched sine partial
+// but share one arbitrary expression shape: a triangle partial, a partial times a control row, a sawtooth with a divisor; what
+// fr_fill_buffer renders with a hipRTC-generated kernel -- is served as a LEAF BANK: its leaf becomes a register program
+// (leafprog.hpp: at most LEAF_PROG_MAX_INSTRS instructions over LEAF_PROG_MAX_REGS registers) that the rendering waves interpret
+// per partial (kernels.hpp bank_stream_leaf_kernel).  A leaf bank has voices of at least 128 partials and is chunked like a
+// template bank; everything about programs, buses, loops, taps, history and store applies behind it as behind any bank, and next
+// to another bank it needs FR_STREAM_BANKS like any second bank.  The input slots its leaf reads are streamed rows: slot 0 is the
+// time row, any other needs FR_STREAM_INPUTS and counts towards STREAM_MAX_INPUTS.  Track voices, chunked compiled banks, compiled
+// voices of 32 or 64 partials, a leaf over the interpreter's limits and a leaf bank in a sweep plan stay refused.  The rule sees
+// the plan in force: while hipRTC is still compiling (or with FR_JIT=0) a plan has no compiled bank and is answered as ever.
 // HOW a served plan is launched is one rule as well (stream_path, stream_launch, plain_stream_launch, at the end): the path, the
 // kernel, its doorbell form, its tables, the loop limits, the workgroups.  fr_stream_begin, the seek, the block, the stop and
 // fr_plan_json's "kernel" read the StreamLaunch it returns and decide nothing themselves.
@@ -79,6 +89,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "leafprog.hpp"
 #include "stage.hpp"
 
 namespace fr {
@@ -101,6 +112,8 @@ constexpr uint32_t STREAM_SCHEDULE_MAX_DEPTH = 16;   // (= kernels.hip GB_MAX_DE
 // The deepest delayed read of an input row a stream serves (FR_STREAM_HISTORY): the history holds the next power of two above
 // look-back + a block per streamed row -- at this limit 4 MiB per row, 32 MiB for STREAM_MAX_INPUTS rows.
 constexpr uint64_t STREAM_HIST_MAX_FRAMES = 1ull << 20;
+static_assert(LEAF_PROG_MAX_INSTRS == BANK_STREAM_LEAF_INSTRS && LEAF_PROG_MAX_REGS == BANK_STREAM_LEAF_REGS && LEAF_OP_SUM2 == OP_SUM2 && LEAF_OP_MIN == OP_MIN,
+              "the leaf program's limits and ops are the kernel's");
 static_assert(STREAM_LOOP_LOADS == BANK_STREAM_LOOP_LOADS && STREAM_LOOP_STORES == BANK_STREAM_LOOP_STORES && STREAM_BLOCK == BANK_STREAM_LOOP_MAX_STRIDE + 1,
               "the rule's limits are the kernel's");
 
@@ -123,6 +136,7 @@ struct StreamEnv {
     bool taps = false;               // FR_STREAM_TAPS: the level form of a plan without feedback; short and signal delays of a ring an earlier program stores
     bool programs = false;           // FR_STREAM_PROGRAMS: the program path exists (stream_path; plan_stream does not ask)
     bool sweep = false;              // FR_STREAM_SWEEP: Delays by a signal amount inside feedback loops shorter than a block (with `loops` and `dyn`)
+    bool leaves = false;             // FR_STREAM_LEAVES (with `programs`): compiled voices as leaf banks, their leaves interpreted (leafprog.hpp)
     bool store = false;              // FR_STREAM_STORE, and not inert (streamstore.hpp): the launch stores the streamed rows; every plan takes the program path
 };
 
@@ -134,6 +148,7 @@ struct StreamBank {
     uint32_t first_wg = 0;
     bool general = false;            // a schedule bank (StreamEnv::general): one workgroup per voice, log2_p == chunk_log2
     uint32_t max_leaves = 0;         // ... and its largest voice
+    bool leaf = false;               // a leaf bank (StreamEnv::leaves): compiled voices, chunked like a template bank
 };
 
 // Every workgroup of the launch must be resident at once, one per CU: as many as the device has CUs (0: unknown, the kernel's
@@ -255,6 +270,8 @@ struct StreamPlan {
                                          // first, the others ascending -- the order of a block's streamed rows
     std::vector<uint32_t> general_voices;   // the leaf count of every voice served by schedule, in global voice order (StreamEnv::general)
     bool has_general() const { return std::any_of(banks.begin(), banks.end(), [](const StreamBank &b) { return b.general; }); }
+    std::vector<LeafProgram> leaf_progs;    // per bank, in plan order: a leaf bank's program (StreamEnv::leaves); any other bank's is empty (k == 0)
+    bool has_leaves() const { return std::any_of(banks.begin(), banks.end(), [](const StreamBank &b) { return b.leaf; }); }
     std::vector<uint32_t> programs_per_voice() const {
         std::vector<uint32_t> n;
         for (size_t v = 0; v + 2 < voice_first.size(); ++v) n.push_back(voice_first[v + 1] - voice_first[v]);
@@ -389,7 +406,7 @@ inline StreamPlan plan_stream(const StagedPlan &sp, const std::vector<const Bank
     auto refuse = [&](const std::string &why) {
         s.servable = false;
         s.reason = why;
-        if (!s.voices) { s.banks.clear(); s.general_voices.clear(); }   // (refused before the banks were dealt)
+        if (!s.voices) { s.banks.clear(); s.general_voices.clear(); s.leaf_progs.clear(); }   // (refused before the banks were dealt)
         return s;
     };
     if (env.n_slots == 0) return refuse("no output slots");
@@ -408,8 +425,42 @@ inline StreamPlan plan_stream(const StagedPlan &sp, const std::vector<const Bank
                           std::to_string(banks.size()) + " bank launches)");
         return refuse("block streaming needs a plan with one voice bank (this one: " + std::to_string(banks.size()) + " bank launches)");
     }
+    const bool leaves = env.leaves && env.programs;  // FR_STREAM_LEAVES does nothing without FR_STREAM_PROGRAMS
+    std::vector<uint32_t> others;                    // slots other than 0 that the leaves and the assigned programs read (StreamEnv::inputs)
     for (const BankLaunch *bp : banks) {             // (one bank: the checks and their order are what they have always been)
         const BankLaunch &b = *bp;
+        if (leaves && b.jit) {                       // a leaf bank: compiled voices, their leaf interpreted
+            if (b.tracks) return refuse("these compiled voices read per-leaf track rows (track voices); block streaming interprets leaves over constants and streamed input rows only");
+            if (b.to_ws) return refuse("a compiled bank that is cut into chunks over an exchange workspace; block streaming serves whole compiled voices only");
+            if (env.leaf_variant != 1) return refuse("block streaming with FR_BANK_LEAF=0");
+            if (b.log2_p < 7)
+                return refuse("compiled voices of " + std::to_string(1u << b.log2_p) + " partials; block streaming interprets the leaves of voices of at least 128 partials (16 waves x one group of 8)");
+            if (b.rows.empty()) return refuse("block streaming needs a plan with one voice bank (this one has no voices)");
+            LeafProgram lp;
+            std::string why;
+            if (!compile_leaf_program(b.shape, b.varying, b.literal_bits, b.alias, lp, &why)) return refuse(why);
+            if (sp.fused_sweep) return refuse("a sweep plan (a feedback loop that delays by a signal amount) together with compiled voices; block streaming has no sweep form with a leaf interpreter");
+            for (const LeafInstr &in : lp.ins)
+                for (int side = 0; side < 2; ++side) {
+                    if ((side ? in.kb : in.ka) != LEAF_IN) continue;
+                    const uint32_t slot = lp.input_slots[side ? in.b : in.a];
+                    if (slot == 0) continue;
+                    if (!env.inputs) return refuse("a leaf reads input slot " + std::to_string(slot) + "; block streaming feeds slot 0 only");
+                    others.push_back(slot);
+                }
+            if (lp.result_kind == LEAF_IN && lp.input_slots[lp.result] != 0) {
+                if (!env.inputs) return refuse("a leaf reads input slot " + std::to_string(lp.input_slots[lp.result]) + "; block streaming feeds slot 0 only");
+                others.push_back(lp.input_slots[lp.result]);
+            }
+            StreamBank sb;
+            sb.voices = (uint32_t)b.rows.size();
+            sb.log2_p = b.log2_p;
+            sb.to_ring = b.to_ring;
+            sb.leaf = true;
+            s.banks.push_back(sb);
+            s.leaf_progs.push_back(std::move(lp));
+            continue;
+        }
         if (env.general) {
             if (b.jit || b.tracks || b.to_ws) return refuse("block streaming needs template voices (these are compiled or track voices)");
         } else if (b.general || b.jit || b.tracks || b.to_ws) {
@@ -440,7 +491,9 @@ inline StreamPlan plan_stream(const StagedPlan &sp, const std::vector<const Bank
             }
         }
         s.banks.push_back(sb);
+        if (leaves) { s.leaf_progs.emplace_back(); s.leaf_progs.back().k = 0; }
     }
+    if (!s.has_leaves()) s.leaf_progs.clear();       // (a plan without a leaf bank is what it has always been)
     // every workgroup of the launch must be resident at once, one per CU: chunks of >= 128 partials until the CUs are used
     const uint64_t max_wgs = stream_max_wgs(env.device_cus);
     if (!deal_stream_chunks(s.banks, max_wgs)) return refuse("block streaming serves at most one voice per CU (" + std::to_string(max_wgs) + " here)");
@@ -458,7 +511,6 @@ inline StreamPlan plan_stream(const StagedPlan &sp, const std::vector<const Bank
         s.chunk_log2 = s.banks[0].chunk_log2;
         s.bank_to_ring = s.banks[0].to_ring;
     }
-    std::vector<uint32_t> others;                    // slots other than 0 that the assigned programs read (StreamEnv::inputs)
 
     // the programs that do a block's work: the fused form (a feedback plan: level by level, then its row copies); a plan whose
     // programs are ONE level deep has no fused form because that level already is one
@@ -724,7 +776,7 @@ inline StreamPlan plan_stream(const StagedPlan &sp, const std::vector<const Bank
     std::sort(others.begin(), others.end());
     others.erase(std::unique(others.begin(), others.end()), others.end());
     if (1 + others.size() > STREAM_MAX_INPUTS)
-        return refuse("the programs read " + std::to_string(1 + others.size()) + " distinct input slots (slot 0 included); block streaming feeds at most " +
+        return refuse(std::string(s.has_leaves() ? "the leaves and the programs read " : "the programs read ") + std::to_string(1 + others.size()) + " distinct input slots (slot 0 included); block streaming feeds at most " +
                       std::to_string(STREAM_MAX_INPUTS));
     // each output row: one assigned program, or the bank itself
     std::vector<uint32_t> writers(env.n_slots, 0);
@@ -780,6 +832,8 @@ inline const char *stream_kernel_name(StreamKernel k) {
     if (k == StreamKernel::sweep_fx) return "bank_stream_sweep_fx_kernel";
     if (k == StreamKernel::sweep_store) return "bank_stream_sweep_store_kernel";
     if (k == StreamKernel::sweep_store_fx) return "bank_stream_sweep_store_fx_kernel";
+    if (k == StreamKernel::leaf) return "bank_stream_leaf_kernel";
+    if (k == StreamKernel::leaf_store) return "bank_stream_leaf_store_kernel";
     return names[(uint32_t)k < sizeof names / sizeof names[0] ? (uint32_t)k : 0];
 }
 
@@ -804,7 +858,8 @@ struct StreamLaunch {
 // FR_STREAM_STORE (StreamEnv::store): every plan, also the one balanced bank that writes rows.
 inline bool stream_path(const StagedPlan &sp, const std::vector<const BankLaunch *> &banks, const StreamEnv &env) {
     const bool by_schedule = env.general && std::any_of(banks.begin(), banks.end(), [](const BankLaunch *b) { return b->general || b->log2_p < 7; });
-    return env.programs && (!sp.progs.empty() || sp.uses_rings() || (env.banks && banks.size() > 1) || by_schedule || env.store);
+    const bool by_leaves = env.leaves && std::any_of(banks.begin(), banks.end(), [](const BankLaunch *b) { return b->jit; });   // FR_STREAM_LEAVES: a compiled bank
+    return env.programs && (!sp.progs.empty() || sp.uses_rings() || (env.banks && banks.size() > 1) || by_schedule || by_leaves || env.store);
 }
 
 // The launch of a servable plan of the program path.  The one cascade: hist > dyn > general > loops > banks > in > bus > prog.
@@ -818,17 +873,19 @@ inline bool stream_path(const StagedPlan &sp, const std::vector<const BankLaunch
 // n_rows counts the plan's slots (a store-mode stream may stream more: streamstore.hpp stream_store_slots, the engine's launch).
 // In front of everything: the sweep forms (StreamPlan::has_sweep, FR_STREAM_SWEEP) -- sweep is the hist form and the sweep walk,
 // sweep_fx the fx form, sweep_store and sweep_store_fx the store forms with it; the history, the tables and n_rows are those of the
-// form underneath.
+// form underneath.  And the leaf forms (StreamPlan::has_leaves, FR_STREAM_LEAVES; the rule refuses a sweep plan with a leaf bank):
+// leaf is the hist form -- history, both tables -- with the leaf interpreter, leaf_store the store form with it.
 inline StreamLaunch stream_launch(const StagedPlan &sp, const StreamPlan &s) {
     StreamLaunch l;
     const bool fx = s.voices == 0;
-    l.kernel = s.has_sweep() ? (s.store ? (fx ? StreamKernel::sweep_store_fx : StreamKernel::sweep_store) : fx ? StreamKernel::sweep_fx : StreamKernel::sweep)
+    l.kernel = s.has_leaves() ? (s.store ? StreamKernel::leaf_store : StreamKernel::leaf)
+               : s.has_sweep() ? (s.store ? (fx ? StreamKernel::sweep_store_fx : StreamKernel::sweep_store) : fx ? StreamKernel::sweep_fx : StreamKernel::sweep)
                : s.store ? (fx ? StreamKernel::store_fx : StreamKernel::store) : fx ? StreamKernel::fx : s.has_hist() ? StreamKernel::hist : s.has_dyn() ? StreamKernel::dyn : s.has_general() ? StreamKernel::general : s.has_loops() ? StreamKernel::loops
                : s.banks.size() > 1 ? StreamKernel::banks : s.input_slots.size() > 1 ? StreamKernel::in : s.bus_programs() ? StreamKernel::bus : StreamKernel::prog;
     l.rows_doorbell = l.own_instrs = l.by_plan = stream_kernel_by_plan(l.kernel);
     l.bank_table = !fx && l.kernel >= StreamKernel::banks;   // (fx: also store_fx)
     l.schedule_table = !fx && (l.kernel == StreamKernel::general || (l.kernel >= StreamKernel::dyn && s.has_general()));
-    l.hist_cap = fx || s.store || l.kernel == StreamKernel::hist || l.kernel == StreamKernel::sweep ? stream_hist_cap(s.input_lookback) : 0;
+    l.hist_cap = fx || s.store || l.kernel == StreamKernel::hist || l.kernel == StreamKernel::sweep || l.kernel == StreamKernel::leaf ? stream_hist_cap(s.input_lookback) : 0;
     l.n_rows = l.rows_doorbell ? (uint32_t)s.input_slots.size() : 1u;
     for (size_t i = 0; i < s.progs.size(); ++i) {    // (the tiles' fill is counted from the plan's instructions; the store slots are the stored rings)
         if (!s.loop_stride[i]) continue;
