@@ -280,7 +280,9 @@ fr_status fr_fill_buffer_device(fr_renderer *r, float *d_out, uint32_t n_slots, 
  * as long as every Delay of a computed value reaches at least 64 frames back (with FR_STREAM_TAPS=1 shorter ones and Delays of
  * a computed value by a signal amount are served too: a two-tap filter or a chorus behind an envelope or a bus; with FR_STREAM_SWEEP=1 feedback loops through a Delay of a signal
  * amount -- a flanger with regeneration -- as well; with FR_STREAM_LEAVES=1 the voices may be compiled voices -- triangle partials,
- * a partial times a control row: any leaf shape of at most 32 operations, interpreted per partial), no program
+ * a partial times a control row: any leaf shape of at most 32 operations, interpreted per partial; with FR_STREAM_TRACKS=1 on top
+ * of it track voices too -- partials whose frequency and amplitude are track rows (fr_set_track_inputs) of the block's dense
+ * matrix, handed in with fr_stream_block_dense (friendship_render_ext.h)), no program
  * mixes two voices of the same block
  * (with FR_STREAM_BUS=1 that too is served: voices with their own gain, envelope or taps summed to a mono or stereo bus,
  * taps and echoes behind the bus), and the programs read input slot 0 at the current frame only (no delayed reads of the input row, no signal-amount

@@ -299,6 +299,34 @@ const char *fr_options_json(fr_renderer *r);
 fr_status fr_stream_block_rows(fr_renderer *r, float *out, uint64_t n_times, uint64_t idx, const float *in_data,
                                const uint64_t *in_row_offsets, uint32_t n_in_rows);
 
+/* ---- block streaming with a dense matrix: track voices ------------------------------------------
+ * fr_stream_block_rows with the block's inputs as fr_fill_buffer_dense takes them: `in` is an [n_in_rows][n_times] row-major
+ * matrix.  Its rows below the first declared track slot (fr_set_track_inputs; none declared: all rows) are the block's streamed
+ * rows, full length -- row 0 the time row, further rows need FR_STREAM_INPUTS=1 and count towards the 8 rows of a block, exactly
+ * as in fr_stream_block_rows.  Its rows from that slot on are the block's TRACKS: per-partial frequency and amplitude rows that
+ * the leaves of track voices read at the current frame.  Tracks are read from the block's own matrix and never stored, also under
+ * FR_STREAM_STORE=1.
+ *
+ * Every block equals, bit for bit, what fr_fill_buffer_dense of the same (idx, n_times, in, n_in_rows) returns on a twin renderer
+ * with the same call history: a slot at or beyond min(n_in_rows, the input vector count) reads +0.0; a block handed in through
+ * fr_stream_block or fr_stream_block_rows brings no matrix and every track reads +0.0 there (not an error); a block that does
+ * not continue the previous one is a seek.
+ *
+ * A stream serves track voices with FR_STREAM_TRACKS = 0 / 1 (default 0; read strictly from the environment too; does nothing
+ * unless FR_STREAM_PROGRAMS=1 and FR_STREAM_LEAVES=1): a bank of track voices is then a leaf bank like any other (voices of at
+ * least 128 partials, chunks, programs, buses and banks behind it), a track read is one more operand kind of the leaf program (at
+ * most 4 distinct track rows per leaf), and the stream stages the rows from the first track slot to the highest slot a voice
+ * names -- at most 65536 rows, [rows][64] floats of mapped pinned memory -- which the host fills before it rings the doorbell and
+ * the rendering waves read over PCIe one partial ahead of the interpreter.  "stream" gains "tracks": {"first_slot", "rows",
+ * "limit"} (rows 0: no leaf reads a track), every entry of "leaf_banks" gains "track_cols", and "kernel" names
+ * bank_stream_track_kernel (with FR_STREAM_STORE: bank_stream_track_store_kernel) for exactly the plans that stage tracks.  With
+ * 0 nothing changes.  Still refused, each with its own sentence: a track history (FR_TRACK_HISTORY), a program that reads a
+ * track, more than 4 track rows per leaf or 65536 per block, and what stays refused for every compiled voice.  On a stream
+ * without track voices the call is fr_stream_block_rows with full-length rows.  Cost: profiles/stream_tracks.txt.
+ *
+ * An optional symbol, as fr_stream_block_rows is. */
+fr_status fr_stream_block_dense(fr_renderer *r, float *out, uint64_t n_times, uint64_t idx, const float *in, uint32_t n_in_rows);
+
 #ifdef __cplusplus
 }
 #endif

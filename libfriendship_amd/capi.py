@@ -222,6 +222,10 @@ class RendererLib:
         if self.has_stream_rows:
             L.fr_stream_block_rows.argtypes = [vp, vp, C.c_uint64, C.c_uint64, vp, vp, C.c_uint32]
             L.fr_stream_block_rows.restype = C.c_int32
+        self.has_stream_dense = hasattr(L, "fr_stream_block_dense")
+        if self.has_stream_dense:
+            L.fr_stream_block_dense.argtypes = [vp, vp, C.c_uint64, C.c_uint64, vp, C.c_uint32]
+            L.fr_stream_block_dense.restype = C.c_int32
         if L.fr_abi_version() != FR_ABI_VERSION:
             raise RuntimeError(f"{path}: ABI version {L.fr_abi_version()} != {FR_ABI_VERSION}")
 
@@ -333,6 +337,22 @@ class Renderer:
         if out.dtype != np.float32 or not out.flags["C_CONTIGUOUS"] or out.shape != (self._stream_slots, n):
             raise ValueError(f"stream_block_rows: out must be a C-contiguous float32 array of shape ({self._stream_slots}, {n}), got {out.dtype} {out.shape}")
         self._check(self.L.fr_stream_block_rows(self.h, out.ctypes.data, n, start, data.ctypes.data, offs.ctypes.data, len(rows)))
+        return out
+
+    def stream_block_dense(self, start, inputs, out=None):
+        """Render the frames [start, start + n_times) of every slot from the block's dense [n_in_rows, n_times] matrix
+        (fr_stream_block_dense): the rows below the first declared track slot are the block's streamed rows, the others its tracks."""
+        if not self.rlib.has_stream_dense:
+            raise RenderError(FR_ERR_UNSUPPORTED, self.rlib.status_string(FR_ERR_UNSUPPORTED), f"{self.rlib.path} has no fr_stream_block_dense")
+        inputs = np.ascontiguousarray(inputs, dtype=np.float32)
+        if inputs.ndim != 2:
+            raise ValueError(f"stream_block_dense: inputs must be a 2-D array [n_in_rows, n_times], got shape {inputs.shape}")
+        n = inputs.shape[1]
+        if out is None:
+            out = np.empty((self._stream_slots, n), dtype=np.float32)
+        if out.dtype != np.float32 or not out.flags["C_CONTIGUOUS"] or out.shape != (self._stream_slots, n):
+            raise ValueError(f"stream_block_dense: out must be a C-contiguous float32 array of shape ({self._stream_slots}, {n}), got {out.dtype} {out.shape}")
+        self._check(self.L.fr_stream_block_dense(self.h, out.ctypes.data, n, start, inputs.ctypes.data if inputs.size else None, inputs.shape[0]))
         return out
 
     def stream_end(self):

@@ -201,7 +201,7 @@ static std::string stage_variant(const StageLaunchNote &n, const Plan &p) {
     return k;
 }
 
-constexpr size_t N_OPTIONS = 45;        // per-renderer options (friendship_render_ext.h; the table below fr_renderer)
+constexpr size_t N_OPTIONS = 46;        // per-renderer options (friendship_render_ext.h; the table below fr_renderer)
 
 struct TimerClass {
     double ms = 0;
@@ -552,6 +552,7 @@ struct fr_renderer {
         // what outlives a stream: the buffers (they only grow), the last resident launch's kernel (fr_plan_json "stream"), the trace
         PinnedBuf h_ctl, h_out;
         DevBuf d_dev, d_progs, d_vfirst, d_sched, d_instrs, d_hist;   // (d_instrs: StreamLaunch::own_instrs; d_hist: StreamLaunch::hist_cap)
+        PinnedBuf h_trk;                 // FR_STREAM_TRACKS: the staging of a block's track rows, [StreamPlan::track_rows][64] floats (kernels.hpp StreamTrackArgs)
         DevBuf d_leaf;                   // FR_STREAM_LEAVES: the leaf banks' programs, bank after bank (StreamPlan::leaf_progs; LEAF_IN by streamed row)
         StreamKernel last_kernel = StreamKernel::none;
         double trace_us[2] = {0, 0};
@@ -579,11 +580,14 @@ struct fr_renderer {
         }
         return d_tickets.as<uint32_t>();
     }
-    // FR_STREAM_PROGRAMS, _BUS, _INPUTS, _LOOPS, _BANKS, _GENERAL, _DYN, _HISTORY, _EFFECTS, _STORE, _TAPS, _SWEEP, _LEAVES (the options table says what each serves; streamplan.hpp StreamEnv)
+    // FR_STREAM_PROGRAMS, _BUS, _INPUTS, _LOOPS, _BANKS, _GENERAL, _DYN, _HISTORY, _EFFECTS, _STORE, _TAPS, _SWEEP, _LEAVES, _TRACKS (the options table says what each serves; streamplan.hpp StreamEnv)
     bool stream_programs = false, stream_bus = false, stream_inputs = false, stream_loops = false, stream_banks = false, stream_general = false, stream_dyn = false,
-         stream_history = false, stream_effects = false, stream_store = false, stream_taps = false, stream_sweep = false, stream_leaves = false;
-    // Why FR_STREAM_STORE does nothing for this renderer ("": it acts; streamstore.hpp)
-    std::string stream_store_inert_now() const { return stream_store_inert(delay_observed, track_from != 0xFFFFFFFFu); }
+         stream_history = false, stream_effects = false, stream_store = false, stream_taps = false, stream_sweep = false, stream_leaves = false, stream_tracks = false;
+    // Why FR_STREAM_STORE does nothing for this renderer ("": it acts; streamstore.hpp).  Declared track slots make it inert unless
+    // the stream itself reads tracks (FR_STREAM_TRACKS on its two options): then the rows below the first track slot are stored
+    // like any streamed row and the tracks, as in fr_fill_buffer_dense, are not.
+    bool stream_tracks_act() const { return stream_tracks && stream_leaves && stream_programs; }
+    std::string stream_store_inert_now() const { return stream_store_inert(delay_observed, track_from != 0xFFFFFFFFu && !stream_tracks_act()); }
     std::vector<const BankLaunch *> stream_bank_list() const {
         std::vector<const BankLaunch *> banks;
         for (const BankStage &bs : plan.banks) banks.push_back(&bs.grp);
@@ -604,6 +608,8 @@ struct fr_renderer {
         env.taps = stream_taps;
         env.sweep = stream_sweep;
         env.leaves = stream_leaves;
+        env.tracks = stream_tracks;
+        env.track_from = track_from;
         env.store = stream_store && stream_programs && stream_store_inert_now().empty();
         return env;
     }
@@ -2418,6 +2424,15 @@ void fr_renderer::upload_stream_programs(const StreamPlan &s, const StreamLaunch
                 if (it == row_slots.end() || row_slots.size() > BANK_STREAM_ROWS) throw Error(FR_ERR_DEVICE, "internal: a streamed leaf reads a slot the stream does not feed");
                 v = (uint32_t)(it - row_slots.begin());
             }
+            for (int side = 0; side < 2; ++side) {               // a track operand: its place in the bank's track columns (kernels.hpp StreamTrackArgs::Bank::cols)
+                uint8_t &kind = side ? in.kb : in.ka;
+                if (kind != LEAF_TRK && kind != LEAF_TRK_LIT) continue;
+                uint32_t &v = side ? in.b : in.a;
+                const uint32_t q = lp.track_index(kind, v);
+                if (q >= lp.track_cols.size() || q >= BANK_STREAM_LEAF_TRACKS) throw Error(FR_ERR_DEVICE, "internal: a streamed leaf reads a track the program does not list");
+                kind = LEAF_TRK;
+                v = q;
+            }
             if (in.dst >= BANK_STREAM_LEAF_REGS || (in.ka == LEAF_REG && in.a >= BANK_STREAM_LEAF_REGS) || (in.kb == LEAF_REG && in.b >= BANK_STREAM_LEAF_REGS) ||
                 (in.ka == LEAF_PARAM && in.a >= lp.k) || (in.kb == LEAF_PARAM && in.b >= lp.k))
                 throw Error(FR_ERR_DEVICE, "internal: a leaf program out of the interpreter's bounds");
@@ -2480,6 +2495,7 @@ void fr_renderer::begin_program_stream_rest(Stream::Open &&o, StreamPlan &&s, ui
         if (l.hist_cap < s.input_lookback + STREAM_BLOCK || (l.hist_cap & (l.hist_cap - 1)) != 0) throw Error(FR_ERR_DEVICE, "internal: the input history does not hold the stream's look-back");
         strm.d_hist.ensure((size_t)(o.store ? BANK_STREAM_ROWS : l.n_rows) * l.hist_cap * sizeof(float));   // (store: the set of rows may grow)
     }
+    if (s.has_tracks()) strm.h_trk.ensure((size_t)s.track_rows * STREAM_BLOCK * sizeof(float));   // FR_STREAM_TRACKS: a block's track rows
     ensure_stream_buffers(l, n_slots);
     o.prog = true;
     o.plan = std::move(s);
@@ -2584,7 +2600,7 @@ void fr_renderer::start_resident(uint64_t idx, bool empty_history) {
             const LeafProgram &lp = s.leaf_progs[i];
             if (!s.banks[i].leaf) continue;
             const BankStage &b = plan.banks[i];
-            if (!b.grp.jit || b.grp.tracks || lp.k == 0 || lp.k != std::max(b.grp.k, 1u) || lp.ins.size() > BANK_STREAM_LEAF_INSTRS ||
+            if (!b.grp.jit || (b.grp.tracks && !s.has_tracks()) || lp.k == 0 || lp.k != std::max(b.grp.k, 1u) || lp.ins.size() > BANK_STREAM_LEAF_INSTRS ||
                 b.d_params.bytes < ((size_t)s.banks[i].voices << s.banks[i].log2_p) * lp.k * sizeof(float) || (leaf_at + lp.ins.size()) * sizeof(LeafInstr) > strm.d_leaf.bytes)
                 throw Error(FR_ERR_DEVICE, "internal: a leaf bank is not the plan's compiled bank");
             uint32_t result = lp.result;
@@ -2596,9 +2612,29 @@ void fr_renderer::start_resident(uint64_t idx, bool empty_history) {
                 if (row >= l.n_rows) throw Error(FR_ERR_DEVICE, "internal: a streamed leaf reads a slot the stream does not feed");
                 result = (uint32_t)row;
             }
+            uint32_t result_kind = lp.result_kind;
+            if (result_kind == LEAF_TRK || result_kind == LEAF_TRK_LIT) {   // (a leaf that is a bare track: its parked column)
+                result = lp.track_index(result_kind, lp.result);
+                result_kind = LEAF_TRK;
+            }
+            if (!lp.track_cols.empty()) {                        // FR_STREAM_TRACKS: the leaf's track columns
+                if (lp.track_cols.size() > BANK_STREAM_LEAF_TRACKS || !s.has_tracks()) throw Error(FR_ERR_DEVICE, "internal: a leaf bank's tracks are not the plan's");
+                StreamTrackArgs::Bank &tb = x.tr.bank[i];
+                tb.n = (uint32_t)lp.track_cols.size();
+                for (uint32_t q = 0; q < tb.n; ++q) {
+                    tb.cols[q] = lp.track_cols[q].v;
+                    if (lp.track_cols[q].literal) tb.literal |= 1u << q;
+                }
+            }
             x.l.mask |= 1u << i;
-            x.l.bank[i] = {lp.ins.empty() ? nullptr : strm.d_leaf.as<uint4>() + leaf_at, (uint32_t)lp.ins.size(), lp.k, lp.result_kind, result};
+            x.l.bank[i] = {lp.ins.empty() ? nullptr : strm.d_leaf.as<uint4>() + leaf_at, (uint32_t)lp.ins.size(), lp.k, result_kind, result};
             leaf_at += lp.ins.size();
+        }
+        if (s.has_tracks()) {                                    // the staging as the device addresses it
+            if (strm.h_trk.bytes < (size_t)s.track_rows * STREAM_BLOCK * sizeof(float)) throw Error(FR_ERR_DEVICE, "internal: the track staging does not hold the plan's rows");
+            x.tr.staging = strm.h_trk.as_dev<float>();
+            x.tr.first_slot = s.track_first;
+            x.tr.rows = s.track_rows;
         }
     }
     // a stream that stores its rows: the buffers of the slots this launch appends to (streamstore.hpp StoreStreamed; the caller
@@ -2757,6 +2793,7 @@ int64_t env_strict_stream_store(const char *e);
 int64_t env_strict_stream_taps(const char *e);
 int64_t env_strict_stream_sweep(const char *e);
 int64_t env_strict_stream_leaves(const char *e);
+int64_t env_strict_stream_tracks(const char *e);
 bool parse_option(const Knob &k, const char *s, int64_t &v);
 
 const Knob kKnobs[] = {
@@ -2892,6 +2929,10 @@ const Knob kKnobs[] = {
     // register program (leafprog.hpp; streamplan.hpp StreamEnv::leaves; fr_plan_json: stream.leaf_banks).  Inert without
     // FR_STREAM_PROGRAMS.  Strict and listed once set.
     {"FR_STREAM_LEAVES", 0, 0, 1, 0, nullptr, 0, env_strict_stream_leaves, [](fr_renderer &r, int64_t v, bool) { r.stream_leaves = v != 0; }, LISTED_WHEN_SET},
+    // Track voices in block streaming -- compiled voices whose leaves read per-partial track rows (fr_set_track_inputs): a leaf bank
+    // whose program has track operands, the block's matrix (fr_stream_block_dense) staged in mapped pinned memory (streamplan.hpp
+    // StreamEnv::tracks; fr_plan_json: stream.tracks).  Inert without FR_STREAM_PROGRAMS and FR_STREAM_LEAVES.  Strict and listed once set.
+    {"FR_STREAM_TRACKS", 0, 0, 1, 0, nullptr, 0, env_strict_stream_tracks, [](fr_renderer &r, int64_t v, bool) { r.stream_tracks = v != 0; }, LISTED_WHEN_SET},
 };
 static_assert(sizeof kKnobs / sizeof kKnobs[0] == N_OPTIONS, "N_OPTIONS counts the rows of kKnobs");
 
@@ -2918,6 +2959,7 @@ int64_t env_strict_stream_store(const char *e) { return env_strict("FR_STREAM_ST
 int64_t env_strict_stream_taps(const char *e) { return env_strict("FR_STREAM_TAPS", e); }
 int64_t env_strict_stream_sweep(const char *e) { return env_strict("FR_STREAM_SWEEP", e); }
 int64_t env_strict_stream_leaves(const char *e) { return env_strict("FR_STREAM_LEAVES", e); }
+int64_t env_strict_stream_tracks(const char *e) { return env_strict("FR_STREAM_TRACKS", e); }
 
 bool parse_option(const Knob &k, const char *s, int64_t &v) {
     if (k.word && std::strcmp(s, k.word) == 0) {
@@ -3327,7 +3369,10 @@ fr_status fr_stream_begin(fr_renderer *r, uint32_t n_slots) {
 // bits are fr_fill_buffer's for the same sequence of calls: the input store's rules are kept for the rows without storing them
 // (streamrows.hpp), and the rows of the slots the plan reads (StreamPlan::input_slots; a plan without FR_STREAM_INPUTS: slot 0)
 // are the doorbell.
-static void stream_block_rows(fr_renderer *r, float *out, uint64_t n_times, uint64_t idx, const float *in_data, const uint64_t *offs, uint32_t n_rows) {
+// `dense`, `dense_rows`: the block came as an [dense_rows][n_times] matrix (fr_stream_block_dense; the rows above are its rows
+// below the first track slot); a stream of track voices (FR_STREAM_TRACKS) stages its rows from the first track slot on.
+static void stream_block_rows(fr_renderer *r, float *out, uint64_t n_times, uint64_t idx, const float *in_data, const uint64_t *offs, uint32_t n_rows,
+                              const float *dense = nullptr, uint32_t dense_rows = 0) {
     if (n_rows && !offs) throw Error(FR_ERR_INVALID_ARG, "null row offsets");
     if (n_rows && offs[n_rows] > offs[0] && !in_data) throw Error(FR_ERR_INVALID_ARG, "null input data");
     if (r->track_from != 0xFFFFFFFFu && n_rows > r->track_from) throw Error(FR_ERR_UNSUPPORTED, "block streaming takes no rows of track slots");
@@ -3369,6 +3414,25 @@ static void stream_block_rows(fr_renderer *r, float *out, uint64_t n_times, uint
     o.rows.accept(o.slots, n_times, idx, seek, in_data, offs, n_rows, o.store ? want : o.plan.input_slots.data(), K, rows);
     o.rows_open = true;
     if (!o.store) r->n_vecs = std::max(r->n_vecs, o.rows.n_vecs);   // (the count the stream reached stays with the renderer)
+    if (o.prog && o.plan.has_tracks()) {
+        // the block's tracks (kernels.hpp StreamTrackArgs): the slot limit is the dense call's (store_inputs: rows at or beyond the
+        // vector count are dropped; no matrix, or none that reaches the first track slot: every track reads +0.0), the rows from the
+        // first track slot below it go to the staging, stride 64, then the control word, all before the doorbell's words.  One
+        // buffer: the previous block's done tag followed every workgroup's last track read.
+        const uint32_t from = o.plan.track_first;
+        const uint64_t have = dense ? std::min<uint64_t>(dense_rows, o.rows.n_vecs) : 0;
+        const uint32_t limit = have > from ? (uint32_t)have : 0u;
+        const uint32_t staged = limit ? std::min(limit - from, o.plan.track_rows) : 0u;
+        if (from != r->track_from || (size_t)o.plan.track_rows * STREAM_BLOCK * sizeof(float) > r->strm.h_trk.bytes || !o.launch.rows_doorbell)
+            throw Error(FR_ERR_DEVICE, "internal: the track staging is not the plan's");
+        float *stage = r->strm.h_trk.as<float>();
+        const float *first = staged ? dense + (uint64_t)from * n_times : nullptr;
+        if (staged && n_times == STREAM_BLOCK) std::memcpy(stage, first, (size_t)staged * STREAM_BLOCK * sizeof(float));
+        else for (uint32_t q = 0; q < staged; ++q) std::memcpy(stage + (size_t)q * STREAM_BLOCK, first + (uint64_t)q * n_times, n_times * sizeof(float));
+        __atomic_thread_fence(__ATOMIC_RELEASE);
+        __atomic_store_n(&static_cast<BankStreamInCtl *>(r->strm.h_ctl.p)->tracks, (unsigned long long)staged << 32 | limit, __ATOMIC_RELAXED);
+        __atomic_thread_fence(__ATOMIC_RELEASE);
+    }
     // every word is tagged with the block's number and length: the words are the doorbell (kernels.hpp BankStreamCtl, BankStreamInCtl)
     o.seq = (o.seq + 1u) & 0xFFFFFFu;
     if (o.seq == 0 || o.seq == 0xFFFFFFu) o.seq = 1;
@@ -3425,6 +3489,20 @@ fr_status fr_stream_block(fr_renderer *r, float *out, uint64_t n_times, uint64_t
         if (!out || n_times == 0 || n_times > 64 || row_len > n_times || (row_len && !row)) throw Error(FR_ERR_INVALID_ARG, "a streamed block is 1..64 frames");
         const uint64_t offs[2] = {0, row_len};
         stream_block_rows(r, out, n_times, idx, row, offs, 1);
+    }, true);
+}
+
+// (the block as a dense matrix: its rows below the first track slot are fr_stream_block_rows' rows, full length; the rows from
+// that slot on are the block's tracks)
+fr_status fr_stream_block_dense(fr_renderer *r, float *out, uint64_t n_times, uint64_t idx, const float *in, uint32_t n_in_rows) {
+    return guarded(r, [&] {
+        if (!r->strm.open) throw Error(FR_ERR_INVALID_ARG, "no stream is open (fr_stream_begin; any other call on the renderer closes it)");
+        if (!out || n_times == 0 || n_times > 64) throw Error(FR_ERR_INVALID_ARG, "a streamed block is 1..64 frames");
+        if (n_in_rows && !in) throw Error(FR_ERR_INVALID_ARG, "null input matrix");
+        const uint32_t stored = std::min(n_in_rows, r->track_from);
+        std::vector<uint64_t> offs((size_t)stored + 1);
+        for (uint32_t i = 0; i <= stored; ++i) offs[i] = (uint64_t)i * n_times;
+        stream_block_rows(r, out, n_times, idx, in, offs.data(), stored, in, n_in_rows);
     }, true);
 }
 
@@ -3587,9 +3665,13 @@ const char *fr_plan_json(fr_renderer *r) {
                 for (size_t i = 0; i < s.leaf_progs.size() && i < s.banks.size(); ++i)
                     if (s.banks[i].leaf)
                         lb += std::string(lb.empty() ? "" : ",") + "{\"ops\":" + std::to_string(s.leaf_progs[i].ins.size()) + ",\"regs\":" + std::to_string(s.leaf_progs[i].regs) +
-                              ",\"params\":" + std::to_string(s.leaf_progs[i].k) + ",\"inputs\":" + std::to_string(s.leaf_progs[i].inputs_read) + "}";
+                              ",\"params\":" + std::to_string(s.leaf_progs[i].k) + ",\"inputs\":" + std::to_string(s.leaf_progs[i].inputs_read) +
+                              (r->stream_tracks ? ",\"track_cols\":" + std::to_string(s.leaf_progs[i].track_cols.size()) : std::string()) + "}";
                 r->plan_json_cache += ",\"leaf_banks\":[" + lb + "]";
             }
+            if (r->stream_tracks)                                // FR_STREAM_TRACKS: the staged rows (0: no leaf reads a track) and their limit
+                r->plan_json_cache += ",\"tracks\":{\"first_slot\":" + std::to_string(s.has_tracks() ? s.track_first : 0) + ",\"rows\":" + std::to_string(s.track_rows) +
+                                      ",\"limit\":" + std::to_string(STREAM_MAX_TRACK_ROWS) + "}";
             if (r->stream_sweep) {                               // FR_STREAM_SWEEP: the width of every streamed program, in the order of `progs` (0: no sweep program)
                 std::string sw;
                 for (uint32_t w : s.sweep_width) sw += (sw.empty() ? "" : ",") + std::to_string(w);

@@ -1171,8 +1171,13 @@ __device__ __forceinline__ float stream_render_schedule(const float *params, con
 // order, and no other wave touches its columns: no barrier inside).  What is uniform -- the instruction words, the partial's row
 // of the parameter table -- comes through the scalar cache (constant address space); a register and a staged row are LDS reads
 // at the lane's column.  Every arithmetic op is prim_binop's, separately rounded; no fast path, no fract body.
+// TR (the track forms, kernels.hpp StreamTrackArgs): the operand kind is decoded with 3 bits and kind 4 is a track row's value at
+// the lane's frame, which the wave parked in column v of `tp` before it started the partial (stream_render_leaves).
+template <bool TR>
 __device__ __forceinline__ float stream_leaf_operand(uint32_t kind, uint32_t v, const_f32_ptr prow, uint32_t k, const float (&lr)[BANK_STREAM_LEAF_REGS][64],
-                                                     const float (&lin)[BANK_STREAM_ROWS][64], uint32_t lane) {
+                                                     const float (&lin)[BANK_STREAM_ROWS][64], [[maybe_unused]] const float (*tp)[64], uint32_t lane) {
+    if constexpr (TR)
+        if (kind >= 4u) return tp[v & (BANK_STREAM_LEAF_TRACKS - 1u)][lane];
     switch (kind) {   // (uniform)
     case 0u: return lr[v & (BANK_STREAM_LEAF_REGS - 1u)][lane];
     case 1u: return v < k ? prow[v] : 0.0f;   // (the host numbered the columns below k: the test never bites)
@@ -1181,15 +1186,17 @@ __device__ __forceinline__ float stream_leaf_operand(uint32_t kind, uint32_t v, 
     }
 }
 typedef uint32_t __attribute__((address_space(4))) const *const_leaf_ptr;   // the instruction words: uniform, SMEM loads
+template <bool TR>
 __device__ __forceinline__ float stream_leaf(const StreamLeafArgs::Bank &lb, const_f32_ptr prow, float (&lr)[BANK_STREAM_LEAF_REGS][64],
-                                             const float (&lin)[BANK_STREAM_ROWS][64], uint32_t lane, bool sparkle) {
+                                             const float (&lin)[BANK_STREAM_ROWS][64], const float (*tp)[64], uint32_t lane, bool sparkle) {
+    constexpr uint32_t KIND = TR ? 7u : 3u;
     const_leaf_ptr ins = (const_leaf_ptr)lb.instrs;
     const uint32_t n = lb.n_instr < BANK_STREAM_LEAF_INSTRS ? lb.n_instr : BANK_STREAM_LEAF_INSTRS;
     float v = 0.0f;
     for (uint32_t i = 0; i < n; ++i) {
         const uint32_t head = ins[4u * i], a = ins[4u * i + 1u], b = ins[4u * i + 2u];   // {op | dst << 8 | ka << 16 | kb << 24, a, b, 0}
-        const float x = stream_leaf_operand((head >> 16) & 3u, a, prow, lb.k, lr, lin, lane);
-        const float y = stream_leaf_operand((head >> 24) & 3u, b, prow, lb.k, lr, lin, lane);
+        const float x = stream_leaf_operand<TR>((head >> 16) & KIND, a, prow, lb.k, lr, lin, tp, lane);
+        const float y = stream_leaf_operand<TR>((head >> 24) & KIND, b, prow, lb.k, lr, lin, tp, lane);
         switch (head & 0xFFu) {   // (the interpreter's own cases, each op a constant, as STAGE_ARITH_CASES)
         case OP_SUM2: v = prim_binop(OP_SUM2, x, y, sparkle); break;
         case OP_MUL: v = prim_binop(OP_MUL, x, y, sparkle); break;
@@ -1200,8 +1207,67 @@ __device__ __forceinline__ float stream_leaf(const StreamLeafArgs::Bank &lb, con
         lr[(head >> 8) & (BANK_STREAM_LEAF_REGS - 1u)][lane] = v;
     }
     // (the last instruction's value is the leaf -- its register is the result -- unless the leaf is a bare constant or input)
-    return lb.result_kind == 0u ? v : stream_leaf_operand(lb.result_kind, lb.result, prow, lb.k, lr, lin, lane);
+    return lb.result_kind == 0u ? v : stream_leaf_operand<TR>(lb.result_kind, lb.result, prow, lb.k, lr, lin, tp, lane);
 }
+
+// The track rows of ONE partial (the track forms, kernels.hpp StreamTrackArgs, where the argument stands): row q of the partial
+// whose parameter row is `prow` is the slot whose bits stand in column cols[q] (a literal column: cols[q] itself).
+struct StreamTrackWave {
+    const float *staging;
+    uint32_t first_slot, rows;
+    StreamTrackArgs::Bank tb;
+    uint32_t k;
+    __device__ __forceinline__ uint32_t slot(uint32_t q, const_f32_ptr prow) const {   // (uniform; q is a constant of the unrolled callers)
+        const uint32_t c = tb.cols[q];
+        return ((tb.literal >> q) & 1u) ? c : c < k ? __float_as_uint(prow[c]) : 0xFFFFFFFFu;
+    }
+    // The load: a relaxed system-scope atomic load of the lane's frame -- a trip across PCIe -- when the slot lies inside the
+    // ALLOCATION (a launch constant: the address is in bounds whatever the block says); whether the block supplied it is the park's.
+    __device__ __forceinline__ float load(uint32_t q, const_f32_ptr prow, uint32_t lane) const {
+        if (q >= tb.n) return 0.0f;
+        const uint32_t off = slot(q, prow) - first_slot;
+        return off < rows ? __hip_atomic_load(staging + (size_t)off * 64u + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) : 0.0f;
+    }
+    // The park: what jit_track yields -- the loaded value for a slot below the block's limit (and inside the rows the block
+    // staged), +0.0 otherwise and for a lane beyond the block.
+    __device__ __forceinline__ void park(uint32_t q, const_f32_ptr prow, float v, uint32_t limit, uint32_t block_rows, bool live, float (*tp)[64], uint32_t lane) const {
+        if (q >= tb.n) return;
+        const uint32_t s = slot(q, prow);
+        tp[q][lane] = live && s < limit && s - first_slot < block_rows ? v : 0.0f;
+    }
+};
+
+// The rows in flight (the track forms): the values of the NEXT partial's track rows, and the block's control word.  The
+// constructor issues the loads of partial 0 and of the word; step(j) parks partial j's values in half j & 1 of the wave's
+// double buffer -- the wait for the loads stands here --, issues partial j + 1's loads and returns the half.  The other forms'
+// object is empty and its step returns null.
+template <bool TR>
+struct StreamTrackAhead {
+    __device__ __forceinline__ StreamTrackAhead(const StreamTrackWave &, const unsigned long long *, const_f32_ptr, uint32_t) {}
+    __device__ __forceinline__ const float (*step(const StreamTrackWave &, float (*)[2][BANK_STREAM_LEAF_TRACKS][64], uint32_t, uint32_t, uint32_t, const_f32_ptr, uint32_t, bool,
+                                                 uint32_t))[64] { return nullptr; }
+};
+template <>
+struct StreamTrackAhead<true> {
+    float n0, n1, n2, n3;
+    unsigned long long word;
+    __device__ __forceinline__ StreamTrackAhead(const StreamTrackWave &tw, const unsigned long long *block_tracks, const_f32_ptr prow, uint32_t lane) {
+        word = __hip_atomic_load(block_tracks, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        n0 = tw.load(0u, prow, lane); n1 = tw.load(1u, prow, lane); n2 = tw.load(2u, prow, lane); n3 = tw.load(3u, prow, lane);
+    }
+    __device__ __forceinline__ const float (*step(const StreamTrackWave &tw, float (*trk)[2][BANK_STREAM_LEAF_TRACKS][64], uint32_t wave, uint32_t j, uint32_t n,
+                                                 const_f32_ptr prow, uint32_t k, bool live, uint32_t lane))[64] {
+        float(*tp)[64] = trk[wave][j & 1u];
+        const uint32_t limit = __builtin_amdgcn_readfirstlane((uint32_t)word), block_rows = __builtin_amdgcn_readfirstlane((uint32_t)(word >> 32));
+        tw.park(0u, prow, n0, limit, block_rows, live, tp, lane); tw.park(1u, prow, n1, limit, block_rows, live, tp, lane);
+        tw.park(2u, prow, n2, limit, block_rows, live, tp, lane); tw.park(3u, prow, n3, limit, block_rows, live, tp, lane);
+        if (j + 1u < n) {
+            const_f32_ptr next = prow + k;
+            n0 = tw.load(0u, next, lane); n1 = tw.load(1u, next, lane); n2 = tw.load(2u, next, lane); n3 = tw.load(3u, next, lane);
+        }
+        return tp;
+    }
+};
 
 // The chunk: the block's streamed rows staged in LDS (wave j loads row j; row 0 is the time row; a lane beyond the block holds
 // +0.0, as the republished rows do), then the leaves summed LITERALLY in the graph's association -- a group of 8 as bank_group
@@ -1209,9 +1275,16 @@ __device__ __forceinline__ float stream_leaf(const StreamLeafArgs::Bank &lb, con
 // stream_render_chunk adds them.  Every add is performed, so a zero sum has the graph's sign: no repair pass.  Two barriers,
 // both under the workgroup-uniform condition that the bank is a leaf bank.  Returns the chunk's sum in wave 0; `t` is the lane's
 // time in every wave.
+// TR (the track forms): the wave has the track rows of partial j + 1 in flight while it interprets partial j.  It loads partial
+// 0's rows and the block's limit word before the loop; every iteration parks its own rows in its half trk[wave][j & 1] of the
+// wave's double buffer -- the wait for the loads stands here, after a whole partial's interpretation --, issues the next
+// partial's loads and interprets (StreamTrackAhead).  Named registers n0..n3: nothing is indexed dynamically.
+template <bool TR = false>
 __device__ __forceinline__ float stream_render_leaves(const StreamWork &w, const StreamBanksArgs::Bank &bk, const StreamLeafArgs::Bank &lb, const BankStreamInDev *dev,
                                                       uint32_t n_rows, bool sparkle, bool live, uint32_t wave, uint32_t lane, float (&sm)[STREAM_NW][64],
-                                                      float (&lregs)[STREAM_NW][BANK_STREAM_LEAF_REGS][64], float (&lin)[BANK_STREAM_ROWS][64], float &t) {
+                                                      float (&lregs)[STREAM_NW][BANK_STREAM_LEAF_REGS][64], float (&lin)[BANK_STREAM_ROWS][64], float &t,
+                                                      [[maybe_unused]] const StreamTrackWave &tw = {}, [[maybe_unused]] const unsigned long long *block_tracks = nullptr,
+                                                      [[maybe_unused]] float (*trk)[2][BANK_STREAM_LEAF_TRACKS][64] = nullptr) {
     constexpr int NW = STREAM_NW;
     if (wave < BANK_STREAM_ROWS)
         lin[wave][lane] = live && wave < n_rows ? __hip_atomic_load(&dev->rows[wave][lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0f;
@@ -1226,8 +1299,9 @@ __device__ __forceinline__ float stream_render_leaves(const StreamWork &w, const
     // one copy of the interpreter.  Named registers: nothing is indexed dynamically (no scratch).  j < 512: stream_bank_ok.
     float c0 = 0.0f, c1 = 0.0f, c2 = 0.0f, c3 = 0.0f, c4 = 0.0f, c5 = 0.0f, c6 = 0.0f, c7 = 0.0f, c8 = 0.0f, c9 = 0.0f;
     const uint32_t n = w.ngroups << 3;
+    StreamTrackAhead<TR> ahead(tw, block_tracks, prow, lane);
     for (uint32_t j = 0; j < n; ++j) {
-        float v = stream_leaf(lb, prow, lr, lin, lane, sparkle);
+        float v = stream_leaf<TR>(lb, prow, lr, lin, ahead.step(tw, trk, wave, j, n, prow, lb.k, live, lane), lane, sparkle);
         prow += lb.k;
         do {
             if (!(j & 1u)) { c0 = v; break; } v = c0 + v;
@@ -2308,6 +2382,8 @@ hipError_t launch_stage_sweep(const StageArgs &a, hipStream_t s) {
 // the block in sweeps and know the Delays by a signal amount (stream_run_loop_program<true>); LDS as the form underneath.
 // And the two leaf forms (kernels.hpp bank_stream_leaf_kernel): the hist and the store form whose leaf banks -- compiled voices --
 // are rendered by the leaf interpreter (stream_render_leaves); LDS: the form's 45 072 + 32 768 of registers + 2 048 of rows = 79 888.
+// And the two track forms (kernels.hpp bank_stream_track_kernel): the leaf forms whose leaves read track rows of the block's staged
+// matrix, one partial ahead; LDS: the leaf form's 79 888 + 32 768 of parked rows = 112 656.
 //
 // The bus segment is progs[voice_first[n_voices] .. voice_first[n_voices + 1]) and may be empty.  Which kernel a plan launches
 // is the host's rule (streamplan.hpp; fr_plan_json["stream"]["kernel"]).  The compiled kernels against their earlier,
@@ -2396,7 +2472,7 @@ __device__ __forceinline__ StreamRowsInput stream_input(const BankStreamInDev *d
 // (blockIdx.x - first_wg) whole: its chunk count is 1, so stream_hand_over returns at once.
 static_assert(STREAM_STACK_DEPTH == GB_MAX_DEPTH, "a schedule voice's stack is the general voices'");
 template <StreamKernel K, class Ctl, class Dev>
-__device__ __forceinline__ void stream_resident_body(StreamBanksArgs t, StreamGeneralArgs g, StreamHistArgs h, StreamStoreArgs st, StreamLeafArgs lf, BankArgs a, StreamProgArgs p,
+__device__ __forceinline__ void stream_resident_body(StreamBanksArgs t, StreamGeneralArgs g, StreamHistArgs h, StreamStoreArgs st, StreamLeafArgs lf, StreamTrackArgs tk, BankArgs a, StreamProgArgs p,
                                                      uint32_t n_rows, Ctl *ctl, Dev *dev, uint32_t idle_ms) {
     constexpr StreamForm F = stream_form(K);
     __shared__ float sm[F.schedule ? 2 : 1][STREAM_NW][64];  // the waves' sums: a chunk's in [0], a schedule's items alternate
@@ -2407,6 +2483,7 @@ __device__ __forceinline__ void stream_resident_body(StreamBanksArgs t, StreamGe
     __shared__ uint4 lins[BANK_STREAM_LOOP_INSTRS];          // ... and its (first) instructions
     __shared__ float lregs[STREAM_NW][BANK_STREAM_LEAF_REGS][64];   // the leaf interpreter's registers: [wave][register][frame] (leaf forms only)
     __shared__ float lin[BANK_STREAM_ROWS][64];              // ... and the block's streamed rows, [row][frame]
+    __shared__ float ltrk[STREAM_NW][2][BANK_STREAM_LEAF_TRACKS][64];   // the parked track rows: [wave][partial & 1][track][frame] (track forms only)
     __shared__ unsigned long long zshared;
     __shared__ uint32_t s_seq, s_T;
     StreamBanksArgs::Bank bk = {a.params, a.rows, 0u, 0u, a.n_voices, a.log2_p, a.chunk_log2, a.fast_ok, p.bank_to_ring};
@@ -2433,6 +2510,13 @@ __device__ __forceinline__ void stream_resident_body(StreamBanksArgs t, StreamGe
         lb = lf.bank[0];
         static_for<1, (int)BANK_STREAM_BANKS>([&](auto j) {
             if (bi == (uint32_t)j) lb = lf.bank[j];
+        });
+    }
+    [[maybe_unused]] StreamTrackWave tw = {};                    // ... and its leaf's track rows (the track forms only)
+    if constexpr (F.tracks) {
+        tw = {tk.staging, tk.first_slot, tk.rows, tk.bank[0], lb.k};
+        static_for<1, (int)BANK_STREAM_BANKS>([&](auto j) {
+            if (bi == (uint32_t)j) tw.tb = tk.bank[j];
         });
     }
     const uint32_t lane = threadIdx.x & 63u;
@@ -2484,7 +2568,11 @@ __device__ __forceinline__ void stream_resident_body(StreamBanksArgs t, StreamGe
         } else {
             float t_in, result, r;
             // (the conditional expression the general kernel has always had: as an if / else its compiled loop comes out another)
-            if constexpr (F.leaf)
+            if constexpr (F.tracks)
+                r = leaves     ? stream_render_leaves<true>(w, bk, lb, dev, n_rows, p.sparkle != 0u, live, wave, lane, sm[0], lregs, lin, t_in, tw, &ctl->tracks, ltrk)
+                    : schedule ? stream_render_schedule(vparams, items, nitems, bk.fast_ok, stream_time_row(dev), live, wave, lane, sm, stack_mem, zshared, t_in)
+                               : stream_render_chunk(w, stream_time_row(dev), live, wave, lane, sm[0], zshared, t_in);
+            else if constexpr (F.leaf)
                 r = leaves     ? stream_render_leaves(w, bk, lb, dev, n_rows, p.sparkle != 0u, live, wave, lane, sm[0], lregs, lin, t_in)
                     : schedule ? stream_render_schedule(vparams, items, nitems, bk.fast_ok, stream_time_row(dev), live, wave, lane, sm, stack_mem, zshared, t_in)
                                : stream_render_chunk(w, stream_time_row(dev), live, wave, lane, sm[0], zshared, t_in);
@@ -2516,83 +2604,94 @@ __device__ __forceinline__ void stream_resident_body(StreamBanksArgs t, StreamGe
 }
 
 __global__ void __launch_bounds__(1024) bank_stream_kernel(BankArgs a, BankStreamCtl *ctl, BankStreamDev *dev, uint32_t idle_ms) {
-    stream_resident_body<StreamKernel::plain>({}, {}, {}, {}, {}, a, {}, 1u, ctl, dev, idle_ms);
+    stream_resident_body<StreamKernel::plain>({}, {}, {}, {}, {}, {}, a, {}, 1u, ctl, dev, idle_ms);
 }
 __global__ void __launch_bounds__(1024) bank_stream_prog_kernel(BankArgs a, StreamProgArgs p, BankStreamCtl *ctl, BankStreamDev *dev, uint32_t idle_ms) {
-    stream_resident_body<StreamKernel::prog>({}, {}, {}, {}, {}, a, p, 1u, ctl, dev, idle_ms);
+    stream_resident_body<StreamKernel::prog>({}, {}, {}, {}, {}, {}, a, p, 1u, ctl, dev, idle_ms);
 }
 __global__ void __launch_bounds__(1024) bank_stream_bus_kernel(BankArgs a, StreamProgArgs p, BankStreamCtl *ctl, BankStreamDev *dev, uint32_t idle_ms) {
-    stream_resident_body<StreamKernel::bus>({}, {}, {}, {}, {}, a, p, 1u, ctl, dev, idle_ms);
+    stream_resident_body<StreamKernel::bus>({}, {}, {}, {}, {}, {}, a, p, 1u, ctl, dev, idle_ms);
 }
 __global__ void __launch_bounds__(1024) bank_stream_in_kernel(BankArgs a, StreamProgArgs p, uint32_t n_rows, BankStreamInCtl *ctl, BankStreamInDev *dev, uint32_t idle_ms) {
-    stream_resident_body<StreamKernel::in>({}, {}, {}, {}, {}, a, p, n_rows, ctl, dev, idle_ms);
+    stream_resident_body<StreamKernel::in>({}, {}, {}, {}, {}, {}, a, p, n_rows, ctl, dev, idle_ms);
 }
 __global__ void __launch_bounds__(1024) bank_stream_banks_kernel(StreamBanksArgs t, BankArgs a, StreamProgArgs p, uint32_t n_rows, BankStreamInCtl *ctl,
                                                                  BankStreamInDev *dev, uint32_t idle_ms) {
-    stream_resident_body<StreamKernel::banks>(t, {}, {}, {}, {}, a, p, n_rows, ctl, dev, idle_ms);
+    stream_resident_body<StreamKernel::banks>(t, {}, {}, {}, {}, {}, a, p, n_rows, ctl, dev, idle_ms);
 }
 __global__ void __launch_bounds__(1024) bank_stream_loops_kernel(StreamBanksArgs t, BankArgs a, StreamProgArgs p, uint32_t n_rows, BankStreamInCtl *ctl,
                                                                  BankStreamInDev *dev, uint32_t idle_ms) {
-    stream_resident_body<StreamKernel::loops>(t, {}, {}, {}, {}, a, p, n_rows, ctl, dev, idle_ms);
+    stream_resident_body<StreamKernel::loops>(t, {}, {}, {}, {}, {}, a, p, n_rows, ctl, dev, idle_ms);
 }
 __global__ void __launch_bounds__(1024) bank_stream_general_kernel(StreamBanksArgs t, StreamGeneralArgs g, BankArgs a, StreamProgArgs p, uint32_t n_rows, BankStreamInCtl *ctl,
                                                                    BankStreamInDev *dev, uint32_t idle_ms) {
-    stream_resident_body<StreamKernel::general>(t, g, {}, {}, {}, a, p, n_rows, ctl, dev, idle_ms);
+    stream_resident_body<StreamKernel::general>(t, g, {}, {}, {}, {}, a, p, n_rows, ctl, dev, idle_ms);
 }
 __global__ void __launch_bounds__(1024) bank_stream_dyn_kernel(StreamBanksArgs t, StreamGeneralArgs g, BankArgs a, StreamProgArgs p, uint32_t n_rows, BankStreamInCtl *ctl,
                                                                BankStreamInDev *dev, uint32_t idle_ms) {
-    stream_resident_body<StreamKernel::dyn>(t, g, {}, {}, {}, a, p, n_rows, ctl, dev, idle_ms);
+    stream_resident_body<StreamKernel::dyn>(t, g, {}, {}, {}, {}, a, p, n_rows, ctl, dev, idle_ms);
 }
 __global__ void __launch_bounds__(1024) bank_stream_hist_kernel(StreamBanksArgs t, StreamGeneralArgs g, StreamHistArgs h, BankArgs a, StreamProgArgs p, uint32_t n_rows,
                                                                 BankStreamInCtl *ctl, BankStreamInDev *dev, uint32_t idle_ms) {
-    stream_resident_body<StreamKernel::hist>(t, g, h, {}, {}, a, p, n_rows, ctl, dev, idle_ms);
+    stream_resident_body<StreamKernel::hist>(t, g, h, {}, {}, {}, a, p, n_rows, ctl, dev, idle_ms);
 }
 // (LAUNCHED with one wave per workgroup: a segment of programs needs no more, and nothing is rendered.  The bound stays the other
 // forms': under __launch_bounds__(64) the compiler sees that 32 KiB of LDS leave room for one wave per SIMD and pads the wave's
 // register allocation to 257 VGPRs to say so; with this bound it records the 48 the code uses)
 __global__ void __launch_bounds__(1024) bank_stream_fx_kernel(StreamHistArgs h, BankArgs a, StreamProgArgs p, uint32_t n_rows, BankStreamInCtl *ctl, BankStreamInDev *dev,
                                                             uint32_t idle_ms) {
-    stream_resident_body<StreamKernel::fx>({}, {}, h, {}, {}, a, p, n_rows, ctl, dev, idle_ms);
+    stream_resident_body<StreamKernel::fx>({}, {}, h, {}, {}, {}, a, p, n_rows, ctl, dev, idle_ms);
 }
 
 // The store forms (kernels.hpp StreamStoreArgs): the hist form and the fx form, whose workgroup 0 also appends the streamed rows to
 // the input store.
 __global__ void __launch_bounds__(1024) bank_stream_store_kernel(StreamBanksArgs t, StreamGeneralArgs g, StreamHistArgs h, StreamStoreArgs st, BankArgs a, StreamProgArgs p,
                                                                  uint32_t n_rows, BankStreamInCtl *ctl, BankStreamInDev *dev, uint32_t idle_ms) {
-    stream_resident_body<StreamKernel::store>(t, g, h, st, {}, a, p, n_rows, ctl, dev, idle_ms);
+    stream_resident_body<StreamKernel::store>(t, g, h, st, {}, {}, a, p, n_rows, ctl, dev, idle_ms);
 }
 __global__ void __launch_bounds__(1024) bank_stream_store_fx_kernel(StreamHistArgs h, StreamStoreArgs st, BankArgs a, StreamProgArgs p, uint32_t n_rows, BankStreamInCtl *ctl,
                                                                     BankStreamInDev *dev, uint32_t idle_ms) {
-    stream_resident_body<StreamKernel::store_fx>({}, {}, h, st, {}, a, p, n_rows, ctl, dev, idle_ms);
+    stream_resident_body<StreamKernel::store_fx>({}, {}, h, st, {}, {}, a, p, n_rows, ctl, dev, idle_ms);
 }
 
 // The leaf forms (kernels.hpp bank_stream_leaf_kernel): the hist form and the store form whose leaf banks -- compiled voices -- are
 // rendered by the leaf interpreter (stream_render_leaves).
 __global__ void __launch_bounds__(1024) bank_stream_leaf_kernel(StreamBanksArgs t, StreamGeneralArgs g, StreamHistArgs h, StreamLeafArgs lf, BankArgs a, StreamProgArgs p,
                                                                 uint32_t n_rows, BankStreamInCtl *ctl, BankStreamInDev *dev, uint32_t idle_ms) {
-    stream_resident_body<StreamKernel::leaf>(t, g, h, {}, lf, a, p, n_rows, ctl, dev, idle_ms);
+    stream_resident_body<StreamKernel::leaf>(t, g, h, {}, lf, {}, a, p, n_rows, ctl, dev, idle_ms);
 }
 __global__ void __launch_bounds__(1024) bank_stream_leaf_store_kernel(StreamBanksArgs t, StreamGeneralArgs g, StreamHistArgs h, StreamStoreArgs st, StreamLeafArgs lf, BankArgs a,
                                                                       StreamProgArgs p, uint32_t n_rows, BankStreamInCtl *ctl, BankStreamInDev *dev, uint32_t idle_ms) {
-    stream_resident_body<StreamKernel::leaf_store>(t, g, h, st, lf, a, p, n_rows, ctl, dev, idle_ms);
+    stream_resident_body<StreamKernel::leaf_store>(t, g, h, st, lf, {}, a, p, n_rows, ctl, dev, idle_ms);
+}
+
+// The track forms (kernels.hpp bank_stream_track_kernel): the leaf forms whose leaves read track rows of the block's staged matrix.
+__global__ void __launch_bounds__(1024) bank_stream_track_kernel(StreamBanksArgs t, StreamGeneralArgs g, StreamHistArgs h, StreamLeafArgs lf, StreamTrackArgs tk, BankArgs a,
+                                                                 StreamProgArgs p, uint32_t n_rows, BankStreamInCtl *ctl, BankStreamInDev *dev, uint32_t idle_ms) {
+    stream_resident_body<StreamKernel::track>(t, g, h, {}, lf, tk, a, p, n_rows, ctl, dev, idle_ms);
+}
+__global__ void __launch_bounds__(1024) bank_stream_track_store_kernel(StreamBanksArgs t, StreamGeneralArgs g, StreamHistArgs h, StreamStoreArgs st, StreamLeafArgs lf,
+                                                                       StreamTrackArgs tk, BankArgs a, StreamProgArgs p, uint32_t n_rows, BankStreamInCtl *ctl,
+                                                                       BankStreamInDev *dev, uint32_t idle_ms) {
+    stream_resident_body<StreamKernel::track_store>(t, g, h, st, lf, tk, a, p, n_rows, ctl, dev, idle_ms);
 }
 
 // The sweep forms (kernels.hpp bank_stream_sweep_kernel): the hist, fx, store and store_fx forms whose loop programs walk sweeps.
 __global__ void __launch_bounds__(1024) bank_stream_sweep_kernel(StreamBanksArgs t, StreamGeneralArgs g, StreamHistArgs h, BankArgs a, StreamProgArgs p, uint32_t n_rows,
                                                                  BankStreamInCtl *ctl, BankStreamInDev *dev, uint32_t idle_ms) {
-    stream_resident_body<StreamKernel::sweep>(t, g, h, {}, {}, a, p, n_rows, ctl, dev, idle_ms);
+    stream_resident_body<StreamKernel::sweep>(t, g, h, {}, {}, {}, a, p, n_rows, ctl, dev, idle_ms);
 }
 __global__ void __launch_bounds__(1024) bank_stream_sweep_fx_kernel(StreamHistArgs h, BankArgs a, StreamProgArgs p, uint32_t n_rows, BankStreamInCtl *ctl, BankStreamInDev *dev,
                                                                     uint32_t idle_ms) {
-    stream_resident_body<StreamKernel::sweep_fx>({}, {}, h, {}, {}, a, p, n_rows, ctl, dev, idle_ms);
+    stream_resident_body<StreamKernel::sweep_fx>({}, {}, h, {}, {}, {}, a, p, n_rows, ctl, dev, idle_ms);
 }
 __global__ void __launch_bounds__(1024) bank_stream_sweep_store_kernel(StreamBanksArgs t, StreamGeneralArgs g, StreamHistArgs h, StreamStoreArgs st, BankArgs a,
                                                                        StreamProgArgs p, uint32_t n_rows, BankStreamInCtl *ctl, BankStreamInDev *dev, uint32_t idle_ms) {
-    stream_resident_body<StreamKernel::sweep_store>(t, g, h, st, {}, a, p, n_rows, ctl, dev, idle_ms);
+    stream_resident_body<StreamKernel::sweep_store>(t, g, h, st, {}, {}, a, p, n_rows, ctl, dev, idle_ms);
 }
 __global__ void __launch_bounds__(1024) bank_stream_sweep_store_fx_kernel(StreamHistArgs h, StreamStoreArgs st, BankArgs a, StreamProgArgs p, uint32_t n_rows,
                                                                           BankStreamInCtl *ctl, BankStreamInDev *dev, uint32_t idle_ms) {
-    stream_resident_body<StreamKernel::sweep_store_fx>({}, {}, h, st, {}, a, p, n_rows, ctl, dev, idle_ms);
+    stream_resident_body<StreamKernel::sweep_store_fx>({}, {}, h, st, {}, {}, a, p, n_rows, ctl, dev, idle_ms);
 }
 
 // The one entry of the resident launches (kernels.hpp StreamLaunchArgs): the check, then the kernel with what it takes.
@@ -2624,6 +2723,8 @@ hipError_t launch_bank_stream(StreamKernel k, const StreamLaunchArgs &x, hipStre
     case StreamKernel::sweep_store_fx: hipLaunchKernelGGL(bank_stream_sweep_store_fx_kernel, grid, wave, 0, s, x.h, x.s, x.a, x.p, x.n_rows, ctl_in, dev_in, idle_ms); break;
     case StreamKernel::leaf: hipLaunchKernelGGL(bank_stream_leaf_kernel, grid, block, 0, s, x.t, x.g, x.h, x.l, x.a, x.p, x.n_rows, ctl_in, dev_in, idle_ms); break;
     case StreamKernel::leaf_store: hipLaunchKernelGGL(bank_stream_leaf_store_kernel, grid, block, 0, s, x.t, x.g, x.h, x.s, x.l, x.a, x.p, x.n_rows, ctl_in, dev_in, idle_ms); break;
+    case StreamKernel::track: hipLaunchKernelGGL(bank_stream_track_kernel, grid, block, 0, s, x.t, x.g, x.h, x.l, x.tr, x.a, x.p, x.n_rows, ctl_in, dev_in, idle_ms); break;
+    case StreamKernel::track_store: hipLaunchKernelGGL(bank_stream_track_store_kernel, grid, block, 0, s, x.t, x.g, x.h, x.s, x.l, x.tr, x.a, x.p, x.n_rows, ctl_in, dev_in, idle_ms); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

@@ -241,8 +241,11 @@ struct BankStreamInCtl {      // mapped pinned host memory
     unsigned long long rows[BANK_STREAM_ROWS][64];   // host -> device: word i of row j = rows[j][i] (low half) | tag (high half)
     uint32_t done;            // device -> host: tag of the last finished block
     uint32_t alive;           // device -> host: 1 while the kernel is resident, 0 once it has ended
-    uint32_t pad1[14];
+    unsigned long long tracks;   // host -> device (the track forms, StreamTrackArgs): the block's slot limit | staged rows << 32,
+                                 // written before the block's doorbell words; 0: the block brought no matrix
+    uint32_t pad1[12];
 };
+static_assert(sizeof(BankStreamInCtl) == BANK_STREAM_ROWS * 64 * 8 + 64 && offsetof(BankStreamInCtl, tracks) % 8 == 0, "the control block of rows keeps its size");
 struct BankStreamInDev {      // device memory
     uint32_t seq;             // the doorbell, republished by workgroup 0 (0xFFFFFFFF = stop)
     uint32_t n_times;
@@ -430,19 +433,48 @@ struct StreamLeafArgs {
     } bank[BANK_STREAM_BANKS];
 };
 
-// The eighteen resident kernels (streamplan.hpp stream_launch chooses; `none`: no resident launch yet) and their one launch entry.
+//
+// bank_stream_track_kernel, bank_stream_track_store_kernel (FR_STREAM_TRACKS): the two leaf forms with one flag more
+// (StreamForm::tracks) -- a leaf bank's leaf may read TRACK rows (leafshape.hpp LEAF_TRACK: per-partial frequency and amplitude
+// rows of the block's dense input matrix, fr_stream_block_dense).  The host copies the block's track rows into a STAGING matrix
+// of mapped pinned memory, staging[(slot - first_slot) * 64 + frame], before it writes the doorbell, and puts the block's slot
+// limit and row count into BankStreamInCtl::tracks.  A track operand (leafprog.hpp LEAF_TRK, after the engine's upload: `v` = its
+// place q in StreamTrackArgs::Bank::cols) is, for lane = frame,
+//     slot < limit && slot - first_slot < rows && lane < T ? staging[(slot - first_slot) * 64 + lane] : +0.0
+// where slot is the bits of parameter column cols[q] of the partial's row (a literal column: cols[q] itself) -- jit_track's
+// value (leafjit.cpp) with the dense call's limit.  The loads are relaxed SYSTEM-scope atomic loads, issued only after the
+// workgroup has passed stream_next_block for this block (the host wrote the matrix, then a release fence, then the doorbell).
+// Each is a trip across PCIe, so a wave has the rows of partial j + 1 in flight while it interprets partial j: the values wait in
+// registers and are PARKED, at the top of the next iteration, in the wave's own columns trk[wave][j & 1][q][lane] of LDS, where
+// the interpreter's uniform operand switch reads them.  Only the owning wave touches its columns (a wave's LDS accesses complete
+// in program order): no barrier, acquire or poll is added.  One staging buffer suffices: the host writes the next block's matrix
+// only after this block's done tag, which follows every voice's ticket, which follows every wave's last track read.
+// LDS: the leaf form's 79 888 + 16 x 2 x 4 x 256 = 32 768: 112 656.
+constexpr uint32_t BANK_STREAM_LEAF_TRACKS = 4;
+constexpr uint32_t BANK_STREAM_TRACK_ROWS = 65536;   // the staging's largest row count: 256 workgroups x 128 partials x 2 rows, 16 MiB
+struct StreamTrackArgs {
+    const float *staging;          // [rows][64], mapped pinned host memory as the device addresses it
+    uint32_t first_slot, rows;     // the slot of staging row 0 (fr_set_track_inputs), the rows the allocation holds
+    struct Bank {
+        uint32_t n, literal;       // track operands of the bank's leaf (<= BANK_STREAM_LEAF_TRACKS); bit q: cols[q] is the slot itself
+        uint32_t cols[BANK_STREAM_LEAF_TRACKS];   // else the parameter column (< StreamLeafArgs::Bank::k) that holds the slot's bits
+    } bank[BANK_STREAM_BANKS];
+};
+
+// The twenty resident kernels (streamplan.hpp stream_launch chooses; `none`: no resident launch yet) and their one launch entry.
 // plain, prog and bus have the one-row doorbell (BankStreamCtl / BankStreamDev), the others the doorbell of rows (BankStreamIn*).
 // (hist is dyn + 2, fx is hist + 2, store is fx + 2, store_fx is store + 2, and the four sweep forms go on by 2: the values in
 // between stay unnamed and refused, as the tests of the launch check have always required)
 enum class StreamKernel : uint32_t {
     none, plain, prog, bus, in, banks, loops, general, dyn, hist = dyn + 2, fx = hist + 2, store = fx + 2, store_fx = store + 2,
     sweep = store_fx + 2, sweep_fx = sweep + 2, sweep_store = sweep_fx + 2, sweep_store_fx = sweep_store + 2,
-    leaf = sweep_store_fx + 4, leaf_store = leaf + 2   // (the value after the sweep forms stays unnamed as well)
+    leaf = sweep_store_fx + 4, leaf_store = leaf + 2,   // (the value after the sweep forms stays unnamed as well)
+    track = leaf_store + 2, track_store = track + 2
 };
 constexpr bool stream_kernel_named(StreamKernel k) {
     return k != StreamKernel::none && (k <= StreamKernel::dyn || k == StreamKernel::hist || k == StreamKernel::fx || k == StreamKernel::store || k == StreamKernel::store_fx ||
                                        k == StreamKernel::sweep || k == StreamKernel::sweep_fx || k == StreamKernel::sweep_store || k == StreamKernel::sweep_store_fx ||
-                                       k == StreamKernel::leaf || k == StreamKernel::leaf_store);
+                                       k == StreamKernel::leaf || k == StreamKernel::leaf_store || k == StreamKernel::track || k == StreamKernel::track_store);
 }
 // A kernel's form: what it has on top of bank_stream_kernel.  The nine kernels with voices are a cascade -- each is the one
 // before it and one thing more --, so the enum's order is their form; fx, which has no voice, is written out.  kernels.hip's one
@@ -459,9 +491,13 @@ struct StreamForm {
     bool voiceless;  // no bank at all: a workgroup is one wave that runs a segment of programs (fx, store_fx)
     bool store = false;   // workgroup 0 also appends the streamed rows to the input store (StreamStoreArgs): store, store_fx
     bool sweep = false;   // a loop program's phase 2 walks sweeps and knows the Delays by a signal amount: the four sweep forms
-    bool leaf = false;    // leaf banks (StreamLeafArgs): compiled voices rendered by the leaf interpreter: leaf, leaf_store
+    bool leaf = false;    // leaf banks (StreamLeafArgs): compiled voices rendered by the leaf interpreter: leaf, leaf_store, track, track_store
+    bool tracks = false;  // ... whose leaves may read track rows of the block's staged matrix (StreamTrackArgs): track, track_store
 };
 constexpr StreamForm stream_form(StreamKernel k) {
+    // the track forms: the leaf forms and the flag
+    if (k == StreamKernel::track) return {true, true, true, true, true, true, true, true, false, false, false, true, true};
+    if (k == StreamKernel::track_store) return {true, true, true, true, true, true, true, true, false, true, false, true, true};
     // the leaf forms: the hist form and the store form, and the flag
     if (k == StreamKernel::leaf) return {true, true, true, true, true, true, true, true, false, false, false, true};
     if (k == StreamKernel::leaf_store) return {true, true, true, true, true, true, true, true, false, true, false, true};
@@ -486,6 +522,7 @@ struct StreamLaunchArgs {
     StreamHistArgs h;                           // (read for the forms with a history)
     StreamStoreArgs s;                          // (read for the store forms)
     StreamLeafArgs l;                           // (read for the leaf forms)
+    StreamTrackArgs tr = {};                    // (read for the track forms)
     uint32_t n_rows, max_stride, max_loads, max_stores;
     void *ctl_dev, *dev;                        // the control block as the device addresses it and the device block, of the kernel's doorbell form
     uint32_t idle_ms;                           // 0 = BANK_STREAM_IDLE_MS
@@ -556,11 +593,22 @@ inline uint32_t stream_launch_check(StreamKernel k, const StreamLaunchArgs &x) {
             for (uint32_t i = 0; i < x.t.n_banks; ++i) {
                 if (!((leaves >> i) & 1u)) continue;
                 const StreamLeafArgs::Bank &lb = x.l.bank[i];
-                if (lb.n_instr > BANK_STREAM_LEAF_INSTRS || (lb.n_instr && !lb.instrs) || lb.k == 0 || lb.result_kind > 3u) return 0;
+                if (lb.n_instr > BANK_STREAM_LEAF_INSTRS || (lb.n_instr && !lb.instrs) || lb.k == 0 || lb.result_kind > (f.tracks ? 4u : 3u)) return 0;
                 if (lb.result_kind == 0u && (lb.n_instr == 0 || lb.result >= BANK_STREAM_LEAF_REGS)) return 0;   // a register nobody wrote
                 if (lb.result_kind == 1u && lb.result >= lb.k) return 0;
                 if (lb.result_kind == 3u && lb.result >= x.n_rows) return 0;
+                if (f.tracks) {
+                    // a track form: the bank's track operands number at most BANK_STREAM_LEAF_TRACKS, each slot column is one of the
+                    // table's k, and a leaf that is a bare track names one of them
+                    const StreamTrackArgs::Bank &tb = x.tr.bank[i];
+                    if (tb.n > BANK_STREAM_LEAF_TRACKS || (tb.literal >> tb.n) != 0) return 0;
+                    for (uint32_t q = 0; q < tb.n; ++q)
+                        if (!((tb.literal >> q) & 1u) && tb.cols[q] >= lb.k) return 0;
+                    if (lb.result_kind == 4u && lb.result >= tb.n) return 0;
+                }
             }
+            // ... and the staging matrix with its row count (a plan whose slots the staging cannot hold is the rule's to refuse)
+            if (f.tracks && (!x.tr.staging || x.tr.rows == 0 || x.tr.rows > BANK_STREAM_TRACK_ROWS || x.tr.first_slot > UINT32_MAX - x.tr.rows)) return 0;
         }
         for (uint32_t i = 0; i < x.t.n_banks; ++i)
             if (((mask >> i) & 1u) && (!x.g.bank[i].groups || !x.g.bank[i].group_off)) return 0;

@@ -19,6 +19,7 @@ namespace fr {
 
 constexpr uint32_t LEAF_PROG_MAX_INSTRS = 32;   // (= kernels.hpp BANK_STREAM_LEAF_INSTRS)
 constexpr uint32_t LEAF_PROG_MAX_REGS = 8;      // (= kernels.hpp BANK_STREAM_LEAF_REGS: 8 registers x 64 lanes x 16 waves = 32 KiB of LDS)
+constexpr uint32_t LEAF_PROG_MAX_TRACKS = 4;    // (= kernels.hpp BANK_STREAM_LEAF_TRACKS: the distinct track rows a leaf reads, FR_STREAM_TRACKS)
 
 // Where an operand comes from.
 enum LeafOperand : uint32_t {
@@ -26,6 +27,11 @@ enum LeafOperand : uint32_t {
     LEAF_PARAM = 1,   // column `v` of the partial's row of the bank's parameter table [voice][P][k]: uniform per partial
     LEAF_LIT = 2,     // the literal with the bits `v`
     LEAF_IN = 3,      // input `v` at the lane's frame: an index into LeafProgram::input_slots (the engine's upload: the streamed row)
+    // FR_STREAM_TRACKS (compile_leaf_program's allow_tracks) -- a TRACK row of the block's dense matrix at the lane's frame:
+    LEAF_TRK = 4,     // ... the row whose slot number's bits stand in parameter column `v` of the partial's row (a per-partial track)
+    LEAF_TRK_LIT = 5, // ... the row of slot `v`, the same for every partial
+    // (the engine's upload rewrites both to LEAF_TRK with `v` = the operand's place in LeafProgram::track_cols: the column the
+    //  rendering wave parked that row in)
 };
 // The arithmetic ops are FlatOp's numbers (graph.hpp; kernels.hip prim_binop takes them as they are).
 constexpr uint32_t LEAF_OP_SUM2 = 3, LEAF_OP_MUL = 4, LEAF_OP_DIV = 5, LEAF_OP_MOD = 6, LEAF_OP_MIN = 7;
@@ -45,13 +51,24 @@ struct LeafProgram {
     uint32_t result = 0;                  // constant or input, that operand
     std::vector<uint32_t> input_slots;    // the shape's external input slots: LEAF_IN operands index it
     uint32_t inputs_read = 0;             // ... of which the program reads this many distinct ones
+    struct TrackCol {                     // a distinct track operand: LEAF_TRK's parameter column, or LEAF_TRK_LIT's slot
+        uint32_t v;
+        bool literal;
+        bool operator==(const TrackCol &o) const { return v == o.v && literal == o.literal; }
+    };
+    std::vector<TrackCol> track_cols;     // ... in program order (<= LEAF_PROG_MAX_TRACKS; empty without allow_tracks)
+    uint32_t track_index(uint32_t kind, uint32_t v) const {   // the place of a track operand in track_cols (track_cols.size(): none)
+        return (uint32_t)(std::find(track_cols.begin(), track_cols.end(), TrackCol{v, kind == LEAF_TRK_LIT}) - track_cols.begin());
+    }
 };
 
 // The program of a bank's leaf.  `varying`, `literal_bits`, `alias`: per constant column, as for generate_leaf_source -- a column
 // that varies is parameter pidx (aliased columns share one), any other is its literal.  False, with the sentence in `why`: a track
-// leaf, a malformed shape, or more instructions / registers than the interpreter has.
+// leaf, a malformed shape, or more instructions / registers than the interpreter has.  `allow_tracks` (FR_STREAM_TRACKS): a
+// LEAF_TRACK op is an operand of kind LEAF_TRK (its column varies: aliased columns share one) or LEAF_TRK_LIT (its column is a
+// literal: one slot for all partials), listed once in track_cols; more than LEAF_PROG_MAX_TRACKS distinct ones are refused.
 inline bool compile_leaf_program(const LeafShape &shape, const std::vector<bool> &varying, const std::vector<uint32_t> &literal_bits, const std::vector<uint32_t> &alias,
-                                 LeafProgram &out, std::string *why = nullptr) {
+                                 LeafProgram &out, std::string *why = nullptr, bool allow_tracks = false) {
     auto bad = [&](const std::string &w) { if (why) *why = w; return false; };
     out = LeafProgram{};
     const size_t n = shape.ops.size();
@@ -68,8 +85,8 @@ inline bool compile_leaf_program(const LeafShape &shape, const std::vector<bool>
     uint32_t n_arith = 0;
     for (size_t i = 0; i < n; ++i) {
         const LeafShape::Op &o = shape.ops[i];
-        if (o.op == LEAF_TRACK) return bad("a leaf reads a per-leaf track row (a track voice); block streaming interprets leaves over constants and streamed input rows only");
-        if (o.op == 0u) {
+        if (o.op == LEAF_TRACK && !allow_tracks) return bad("a leaf reads a per-leaf track row (a track voice); block streaming interprets leaves over constants and streamed input rows only");
+        if (o.op == 0u || o.op == LEAF_TRACK) {
             if (o.a >= shape.n_consts) return bad("internal: a leaf constant without a column");
         } else if (o.op == 1u) {
             if (o.a >= shape.input_slots.size()) return bad("internal: a leaf input without a slot");
@@ -86,7 +103,7 @@ inline bool compile_leaf_program(const LeafShape &shape, const std::vector<bool>
     // instruction may write the register of an operand it reads last -- the interpreter reads both operands before it writes
     std::vector<size_t> last_use(n, 0);
     for (size_t i = 0; i < n; ++i)
-        if (shape.ops[i].op >= LEAF_OP_SUM2) { last_use[shape.ops[i].a] = i; last_use[shape.ops[i].b] = i; }
+        if (shape.ops[i].op >= LEAF_OP_SUM2 && shape.ops[i].op != LEAF_TRACK) { last_use[shape.ops[i].a] = i; last_use[shape.ops[i].b] = i; }
     last_use[n - 1] = n;
     std::vector<int64_t> reg_of(n, -1);
     std::vector<bool> busy;
@@ -100,6 +117,10 @@ inline bool compile_leaf_program(const LeafShape &shape, const std::vector<bool>
             kind = LEAF_IN;
             v = o.a;
             in_read[o.a] = true;
+        } else if (o.op == LEAF_TRACK) {
+            kind = varying[o.a] ? LEAF_TRK : LEAF_TRK_LIT;
+            v = varying[o.a] ? (uint32_t)pidx[o.a] : literal_bits[o.a];
+            if (out.track_index(kind, v) == out.track_cols.size()) out.track_cols.push_back({v, kind == LEAF_TRK_LIT});
         } else {
             kind = LEAF_REG;
             v = (uint32_t)reg_of[i];
@@ -108,7 +129,7 @@ inline bool compile_leaf_program(const LeafShape &shape, const std::vector<bool>
     uint32_t peak = 0;
     for (size_t i = 0; i < n; ++i) {
         const LeafShape::Op &o = shape.ops[i];
-        if (o.op < LEAF_OP_SUM2) continue;
+        if (o.op < LEAF_OP_SUM2 || o.op == LEAF_TRACK) continue;
         LeafInstr in{};
         in.op = (uint8_t)o.op;
         operand(o.a, in.ka, in.a);
@@ -129,6 +150,8 @@ inline bool compile_leaf_program(const LeafShape &shape, const std::vector<bool>
     uint8_t rk = LEAF_REG;
     operand((uint32_t)(n - 1), rk, out.result);
     out.result_kind = rk;
+    if (out.track_cols.size() > LEAF_PROG_MAX_TRACKS)
+        return bad("a leaf that reads " + std::to_string(out.track_cols.size()) + " distinct track rows; block streaming interprets leaves with at most " + std::to_string(LEAF_PROG_MAX_TRACKS));
     out.regs = peak;
     out.k = k ? k : 1;
     out.input_slots = shape.input_slots;

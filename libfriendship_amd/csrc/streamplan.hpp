@@ -78,6 +78,12 @@
 // time row, any other needs FR_STREAM_INPUTS and counts towards STREAM_MAX_INPUTS.  Track voices, chunked compiled banks, compiled
 // voices of 32 or 64 partials, a leaf over the interpreter's limits and a leaf bank in a sweep plan stay refused.  The rule sees
 // the plan in force: while hipRTC is still compiling (or with FR_JIT=0) a plan has no compiled bank and is answered as ever.
+// With FR_STREAM_TRACKS=1 (StreamEnv::tracks, on top of `leaves`) a bank of TRACK VOICES -- compiled voices whose leaves read
+// per-partial track rows (fr_set_track_inputs, leafshape.hpp LEAF_TRACK) -- is a leaf bank like any other: a track read is one
+// more operand kind of the leaf program (leafprog.hpp LEAF_TRK), at most LEAF_PROG_MAX_TRACKS distinct ones per leaf, and a block
+// brings its matrix (fr_stream_block_dense) through a staging of the rows [track_from, the highest slot a bank's table names],
+// at most STREAM_MAX_TRACK_ROWS of them.  A track history, a program that reads a track (the planner's check_tracks), and what
+// stays refused for every leaf bank stay refused.
 // HOW a served plan is launched is one rule as well (stream_path, stream_launch, plain_stream_launch, at the end): the path, the
 // kernel, its doorbell form, its tables, the loop limits, the workgroups.  fr_stream_begin, the seek, the block, the stop and
 // fr_plan_json's "kernel" read the StreamLaunch it returns and decide nothing themselves.
@@ -112,6 +118,10 @@ constexpr uint32_t STREAM_SCHEDULE_MAX_DEPTH = 16;   // (= kernels.hip GB_MAX_DE
 // The deepest delayed read of an input row a stream serves (FR_STREAM_HISTORY): the history holds the next power of two above
 // look-back + a block per streamed row -- at this limit 4 MiB per row, 32 MiB for STREAM_MAX_INPUTS rows.
 constexpr uint64_t STREAM_HIST_MAX_FRAMES = 1ull << 20;
+// The most track rows a stream stages per block (FR_STREAM_TRACKS): 256 workgroups x 128 partials x 2 rows, the largest one-chunk
+// patch a whole device holds; [rows][64] floats of mapped pinned memory, 16 MiB at the limit.
+constexpr uint32_t STREAM_MAX_TRACK_ROWS = 65536;
+static_assert(STREAM_MAX_TRACK_ROWS == BANK_STREAM_TRACK_ROWS && LEAF_PROG_MAX_TRACKS == BANK_STREAM_LEAF_TRACKS, "the staging's limits are the kernel's");
 static_assert(LEAF_PROG_MAX_INSTRS == BANK_STREAM_LEAF_INSTRS && LEAF_PROG_MAX_REGS == BANK_STREAM_LEAF_REGS && LEAF_OP_SUM2 == OP_SUM2 && LEAF_OP_MIN == OP_MIN,
               "the leaf program's limits and ops are the kernel's");
 static_assert(STREAM_LOOP_LOADS == BANK_STREAM_LOOP_LOADS && STREAM_LOOP_STORES == BANK_STREAM_LOOP_STORES && STREAM_BLOCK == BANK_STREAM_LOOP_MAX_STRIDE + 1,
@@ -137,6 +147,8 @@ struct StreamEnv {
     bool programs = false;           // FR_STREAM_PROGRAMS: the program path exists (stream_path; plan_stream does not ask)
     bool sweep = false;              // FR_STREAM_SWEEP: Delays by a signal amount inside feedback loops shorter than a block (with `loops` and `dyn`)
     bool leaves = false;             // FR_STREAM_LEAVES (with `programs`): compiled voices as leaf banks, their leaves interpreted (leafprog.hpp)
+    bool tracks = false;             // FR_STREAM_TRACKS (with `leaves` and `programs`): track voices as leaf banks, the block's matrix staged
+    uint32_t track_from = 0xFFFFFFFFu;   // ... and the first declared track slot (fr_set_track_inputs; none: 0xFFFFFFFF)
     bool store = false;              // FR_STREAM_STORE, and not inert (streamstore.hpp): the launch stores the streamed rows; every plan takes the program path
 };
 
@@ -272,6 +284,9 @@ struct StreamPlan {
     bool has_general() const { return std::any_of(banks.begin(), banks.end(), [](const StreamBank &b) { return b.general; }); }
     std::vector<LeafProgram> leaf_progs;    // per bank, in plan order: a leaf bank's program (StreamEnv::leaves); any other bank's is empty (k == 0)
     bool has_leaves() const { return std::any_of(banks.begin(), banks.end(), [](const StreamBank &b) { return b.leaf; }); }
+    // FR_STREAM_TRACKS: the staged rows are the slots [track_first, track_first + track_rows) (0 rows: no leaf bank reads a track)
+    uint32_t track_first = 0, track_rows = 0;
+    bool has_tracks() const { return track_rows != 0; }
     std::vector<uint32_t> programs_per_voice() const {
         std::vector<uint32_t> n;
         for (size_t v = 0; v + 2 < voice_first.size(); ++v) n.push_back(voice_first[v + 1] - voice_first[v]);
@@ -406,7 +421,7 @@ inline StreamPlan plan_stream(const StagedPlan &sp, const std::vector<const Bank
     auto refuse = [&](const std::string &why) {
         s.servable = false;
         s.reason = why;
-        if (!s.voices) { s.banks.clear(); s.general_voices.clear(); s.leaf_progs.clear(); }   // (refused before the banks were dealt)
+        if (!s.voices) { s.banks.clear(); s.general_voices.clear(); s.leaf_progs.clear(); s.track_rows = 0; }   // (refused before the banks were dealt)
         return s;
     };
     if (env.n_slots == 0) return refuse("no output slots");
@@ -430,7 +445,8 @@ inline StreamPlan plan_stream(const StagedPlan &sp, const std::vector<const Bank
     for (const BankLaunch *bp : banks) {             // (one bank: the checks and their order are what they have always been)
         const BankLaunch &b = *bp;
         if (leaves && b.jit) {                       // a leaf bank: compiled voices, their leaf interpreted
-            if (b.tracks) return refuse("these compiled voices read per-leaf track rows (track voices); block streaming interprets leaves over constants and streamed input rows only");
+            const bool tracks = env.tracks && b.tracks;  // FR_STREAM_TRACKS: ... track voices too
+            if (b.tracks && !tracks) return refuse("these compiled voices read per-leaf track rows (track voices); block streaming interprets leaves over constants and streamed input rows only");
             if (b.to_ws) return refuse("a compiled bank that is cut into chunks over an exchange workspace; block streaming serves whole compiled voices only");
             if (env.leaf_variant != 1) return refuse("block streaming with FR_BANK_LEAF=0");
             if (b.log2_p < 7)
@@ -438,7 +454,16 @@ inline StreamPlan plan_stream(const StagedPlan &sp, const std::vector<const Bank
             if (b.rows.empty()) return refuse("block streaming needs a plan with one voice bank (this one has no voices)");
             LeafProgram lp;
             std::string why;
-            if (!compile_leaf_program(b.shape, b.varying, b.literal_bits, b.alias, lp, &why)) return refuse(why);
+            if (!compile_leaf_program(b.shape, b.varying, b.literal_bits, b.alias, lp, &why, tracks)) return refuse(why);
+            if (!lp.track_cols.empty()) {            // the staging: from the first declared slot to the highest one a table names
+                if (env.track_from == 0xFFFFFFFFu || b.max_track_slot < env.track_from) return refuse("internal: a track voice without declared track slots");
+                const uint64_t rows = (uint64_t)b.max_track_slot - env.track_from + 1;
+                if (rows > STREAM_MAX_TRACK_ROWS)
+                    return refuse("these track voices name " + std::to_string(rows) + " track rows (slots " + std::to_string(env.track_from) + " .. " + std::to_string(b.max_track_slot) +
+                                  "); block streaming stages at most " + std::to_string(STREAM_MAX_TRACK_ROWS) + " per block");
+                s.track_first = env.track_from;
+                s.track_rows = std::max(s.track_rows, (uint32_t)rows);
+            }
             if (sp.fused_sweep) return refuse("a sweep plan (a feedback loop that delays by a signal amount) together with compiled voices; block streaming has no sweep form with a leaf interpreter");
             for (const LeafInstr &in : lp.ins)
                 for (int side = 0; side < 2; ++side) {
@@ -494,6 +519,7 @@ inline StreamPlan plan_stream(const StagedPlan &sp, const std::vector<const Bank
         if (leaves) { s.leaf_progs.emplace_back(); s.leaf_progs.back().k = 0; }
     }
     if (!s.has_leaves()) s.leaf_progs.clear();       // (a plan without a leaf bank is what it has always been)
+    if (!s.has_leaves()) s.track_rows = 0;
     // every workgroup of the launch must be resident at once, one per CU: chunks of >= 128 partials until the CUs are used
     const uint64_t max_wgs = stream_max_wgs(env.device_cus);
     if (!deal_stream_chunks(s.banks, max_wgs)) return refuse("block streaming serves at most one voice per CU (" + std::to_string(max_wgs) + " here)");
@@ -834,6 +860,8 @@ inline const char *stream_kernel_name(StreamKernel k) {
     if (k == StreamKernel::sweep_store_fx) return "bank_stream_sweep_store_fx_kernel";
     if (k == StreamKernel::leaf) return "bank_stream_leaf_kernel";
     if (k == StreamKernel::leaf_store) return "bank_stream_leaf_store_kernel";
+    if (k == StreamKernel::track) return "bank_stream_track_kernel";
+    if (k == StreamKernel::track_store) return "bank_stream_track_store_kernel";
     return names[(uint32_t)k < sizeof names / sizeof names[0] ? (uint32_t)k : 0];
 }
 
@@ -874,18 +902,20 @@ inline bool stream_path(const StagedPlan &sp, const std::vector<const BankLaunch
 // In front of everything: the sweep forms (StreamPlan::has_sweep, FR_STREAM_SWEEP) -- sweep is the hist form and the sweep walk,
 // sweep_fx the fx form, sweep_store and sweep_store_fx the store forms with it; the history, the tables and n_rows are those of the
 // form underneath.  And the leaf forms (StreamPlan::has_leaves, FR_STREAM_LEAVES; the rule refuses a sweep plan with a leaf bank):
-// leaf is the hist form -- history, both tables -- with the leaf interpreter, leaf_store the store form with it.
+// leaf is the hist form -- history, both tables -- with the leaf interpreter, leaf_store the store form with it.  In front of
+// those, the track forms (StreamPlan::has_tracks, FR_STREAM_TRACKS): the leaf forms whose leaves read the block's staged matrix.
 inline StreamLaunch stream_launch(const StagedPlan &sp, const StreamPlan &s) {
     StreamLaunch l;
     const bool fx = s.voices == 0;
-    l.kernel = s.has_leaves() ? (s.store ? StreamKernel::leaf_store : StreamKernel::leaf)
+    l.kernel = s.has_tracks() ? (s.store ? StreamKernel::track_store : StreamKernel::track)
+               : s.has_leaves() ? (s.store ? StreamKernel::leaf_store : StreamKernel::leaf)
                : s.has_sweep() ? (s.store ? (fx ? StreamKernel::sweep_store_fx : StreamKernel::sweep_store) : fx ? StreamKernel::sweep_fx : StreamKernel::sweep)
                : s.store ? (fx ? StreamKernel::store_fx : StreamKernel::store) : fx ? StreamKernel::fx : s.has_hist() ? StreamKernel::hist : s.has_dyn() ? StreamKernel::dyn : s.has_general() ? StreamKernel::general : s.has_loops() ? StreamKernel::loops
                : s.banks.size() > 1 ? StreamKernel::banks : s.input_slots.size() > 1 ? StreamKernel::in : s.bus_programs() ? StreamKernel::bus : StreamKernel::prog;
     l.rows_doorbell = l.own_instrs = l.by_plan = stream_kernel_by_plan(l.kernel);
     l.bank_table = !fx && l.kernel >= StreamKernel::banks;   // (fx: also store_fx)
     l.schedule_table = !fx && (l.kernel == StreamKernel::general || (l.kernel >= StreamKernel::dyn && s.has_general()));
-    l.hist_cap = fx || s.store || l.kernel == StreamKernel::hist || l.kernel == StreamKernel::sweep || l.kernel == StreamKernel::leaf ? stream_hist_cap(s.input_lookback) : 0;
+    l.hist_cap = fx || s.store || l.kernel == StreamKernel::hist || l.kernel == StreamKernel::sweep || l.kernel == StreamKernel::leaf || l.kernel == StreamKernel::track ? stream_hist_cap(s.input_lookback) : 0;
     l.n_rows = l.rows_doorbell ? (uint32_t)s.input_slots.size() : 1u;
     for (size_t i = 0; i < s.progs.size(); ++i) {    // (the tiles' fill is counted from the plan's instructions; the store slots are the stored rings)
         if (!s.loop_stride[i]) continue;
