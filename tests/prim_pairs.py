@@ -469,13 +469,17 @@ def assert_evaluator(plan, ev, n_rows):
         assert not plan["stage_jit"] and all(v.split("/")[0] == "stage_kernel" for v in variants), (plan["stage_jit"], variants)
 
 
-def render(lib, tree, n_rows, rows, ev, semantics):
+def render(lib, tree, n_rows, rows, ev, semantics, check_plan=None):
+    """check_plan(plan): what else the caller asserts from fr_plan_json."""
     from libfriendship_amd.capi import Renderer
     mode, options = EVALUATORS[ev]
     with Renderer(lib, mode=mode, options=options, semantics=semantics) as r:
         synth.install(r, tree)
         got = r.fill_buffer(n_rows, 0, len(rows[0]), rows)
-        assert_evaluator(r.plan(), ev, n_rows)
+        plan = r.plan()
+        assert_evaluator(plan, ev, n_rows)
+        if check_plan:
+            check_plan(plan)
         return got
 
 

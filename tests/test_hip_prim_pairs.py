@@ -4,7 +4,8 @@ for bit, every sample compared.  Each test asserts from fr_plan_json that the ev
 Evaluators: pull_kernel (mode="pull": SS, SP / PS, CC), stage_kernel (mode="staged", FR_STAGE_JIT=0: SS, SP / PS, SL / LS), the
 hipRTC-compiled stage programs (FR_STAGE_JIT=force: SS, SP / PS, SL / LS; for the literal forms the generated source is read back
 through FR_JIT_DUMP to show that the constant was baked), the hipRTC-compiled voice leaves (SS, SL / LS, the fma form with
-FR_JIT_FMA on and off, Modulo(x, 1) in its fract and its general body), the three block-streaming interpreters, and the
+FR_JIT_FMA on and off -- a no-fold control: an input's product is never contracted; the fold is tests/test_hip_prim_chains.py's
+FOLD_SHAPES --, Modulo(x, 1) in its fract and its general body), the three block-streaming interpreters, and the
 interpreters that only a loop brings up: stage_tile_kernel and stage_sweep_kernel (SS beside a loop of a feedback plan, and the
 Delays by a hostile amount in a sweep) and block streaming's loop programs (SS inside the loop's program).
 
@@ -128,10 +129,17 @@ def test_leaves_signal_and_literal(hip_lib, op, form):
 
 
 @pytest.mark.parametrize("fma", ["1", "0"])
-def test_leaves_fma_fold(hip_lib, fma):
-    """Sum2(x, Multiply(L, y)) with L = 2 and -4 (an exact product: folded into one fma unless FR_JIT_FMA=0) on both blocks."""
+def test_leaves_fma_fold(hip_lib, fma, tmp_path, monkeypatch):
+    """Sum2(x, Multiply(L, y)) with L = 2 and -4 on both blocks, FR_JIT_FMA on and off.  This is the NO-FOLD control: leafjit.cpp
+    contracts y + 2^k * v only where it can bound |2^k * v| <= 1e38, an input's bound is infinite, so both settings generate the
+    same v + v code -- the dumped sources must hold no __builtin_fmaf( under either.  The fold itself is exercised by
+    prim_chains.FOLD_SHAPES (tests/test_hip_prim_chains.py), whose products are bounded by a Modulo."""
+    monkeypatch.setenv("FR_JIT_DUMP", str(tmp_path))
     a, b = pp.both_blocks()
     got = pp.render_leaves(hip_lib, pp.leaf_graph("Sum2", "FMA", pp.FMA_LITERALS, 32), 2, [a, b], 32, 1, options={"FR_JIT_FMA": fma})
+    dumped = sorted(tmp_path.glob("jit_bank_*.hip"))
+    assert len(dumped) == len(pp.FMA_LITERALS), f"expected a generated voice source per literal, found {len(dumped)}"
+    assert not any("__builtin_fmaf(" in p.read_text() for p in dumped), "the control folds after all: an input's product was contracted"
     exp, A, B = pp.leaf_expected("Sum2", "FMA", pp.FMA_LITERALS, 32, a, b)
     msg = pp.first_diff("Sum2", f"leaves Sum2(x, Multiply(L, y)) FR_JIT_FMA={fma}", A, B, got, exp)
     assert not msg, msg
