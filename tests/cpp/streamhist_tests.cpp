@@ -331,7 +331,7 @@ static void test_history() {
     const float inf = std::numeric_limits<float>::infinity(), nan = std::nanf("");
     std::mt19937 rng(0x415);
     for (uint32_t look : {0u, 1u, 63u, 64u, 65u, 100u, 192u, 700u}) {
-        for (uint64_t seek : {0ull, 69ull, 5003ull, (1ull << 32) - 100}) {               // the stream's first frame (a seek: zeros before it)
+        for (uint64_t seek : {0ull, 69ull, 5003ull, (1ull << 32) - 100, 1ull << 62}) {   // the stream's first frame (a seek: zeros before it)
             const uint64_t cap = stream_hist_cap(look);
             const uint32_t rows = 3;
             History h(rows, cap);
